@@ -32,6 +32,8 @@ Objects in the JSON line beyond the contract keys:
                  independent of --steps/--warmup).
   configs      — BASELINE.json configs[0], [1], [4] measured in the same run (N=1), each with its own
                  bytes model, roofline fraction and CPU baseline.
+  dump_outputs — with --dump-outputs DIR only: the .npy files written there (x after the last timed step, sampled by
+                 dump_plan) and their shapes.
   cpu_baseline — the compiled reference header (oracle/_ref, kind "reference") or the C oracle
                  (kind "port") timed on ONE host core on a bounded sample (N=1, rank 0 only).
 """
@@ -53,6 +55,10 @@ MIN_BYTES_PER_PIXEL_PASS = 20.0  # what an unchecked pass must move: black x 4 +
 # full-width oracle test (tests/test_gpu_fullsize.py) were made with.  --tune re-times it on the box.
 DEFAULT_TILING = {(16384, 16384, 1): (8, 364)}
 CONFIG1_TILING = (8, 140)
+# --dump-outputs: the sampled rows of x and the row sums together stay within 64 MB whatever the shape
+DUMP_ROWS_BYTES = 48 << 20
+DUMP_SUMS_BYTES = 16 << 20
+DUMP_SEED = 1234
 TRAFFIC_FILES = [os.path.join(ROOT, "profiles", "r04_traffic.json"), os.path.join(ROOT, "profiles", "r03_traffic.json")]
 
 
@@ -92,9 +98,16 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0, help="host threads that BUILD the CPU baseline's system (the timed gaussSeidel is the "
                                                                "reference's serial sweep whatever this says); default min(32, cores)")
     ap.add_argument("--cpu-deadline", type=float, default=420.0, help="seconds the CPU baseline child may take before the largest finished sample is reported")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (float64, at most 64 MB in all): "
+                         "x_rows = full-width rows of the iterate x at seeded positions (dump_plan), x_row_sums = the sum of "
+                         "every row of x; the same arguments give the same inputs and the same positions on every run")
     ap.add_argument("--cpu-baseline-child", default="", help=argparse.SUPPRESS)     # internal: sizes, e.g. 4096,16384
     ap.add_argument("--cpu-log", default="", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def cpu_gs_timed(v, c, r, b, iters):
@@ -166,6 +179,13 @@ def cpu_baseline_child(sizes, iters_arg: int, threads: int, log_path: str) -> No
     except (FileNotFoundError, OSError):
         ref = None
     for sample in sizes:
+        if ref is None and cpu_needs_wide_index(sample):
+            # the C oracle keeps the reference's int positions (nearest_index's (hi + lo) / 2 included) and has no 64-bit
+            # instantiation: past 2^30 entries its sweep would overflow, so without oracle/_ref the smaller sample stands
+            log.write(f"[cpu_baseline] {sample}^2 skipped: {5 * sample * sample} entries overflow the C oracle's int positions "
+                      f"(the 64-bit sweep needs the compiled reference, oracle/_ref)\n")
+            log.flush()
+            continue
         need = cpu_system_gb(sample)
         avail = mem_available_gb()
         if avail < 1.2 * need + 2.0:
@@ -401,6 +421,56 @@ def oracle_bands_check(g, W, H, iters=16, band=64):
             "iterations": iters, "rows": rows, "bit_identical": ok}
 
 
+def dump_plan(W, H, C):
+    """The pixels --dump-outputs writes of a W x H x C iterate, fixed by the shape alone (seeded): (rows, cols, band).
+    rows: 0, H-1 and seeded random rows, cols: every column (a seeded subset only where 64 rows of all channels would not
+    fit), as many rows as DUMP_ROWS_BYTES holds; band: rows per entry of x_row_sums (1 unless C x H sums exceed DUMP_SUMS_BYTES)."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    values = DUMP_ROWS_BYTES // (8 * C)
+    n_cols = min(W, max(1, values // min(H, 64)))
+    cols = np.arange(W) if n_cols == W else np.sort(rng.choice(W, n_cols, replace=False))
+    n_rows = min(H, max(1, values // n_cols))
+    rows = np.unique(np.concatenate([[0, H - 1], rng.choice(H, max(0, n_rows - 2), replace=False)]))[:n_rows]
+    band = max(1, -(-8 * C * H // DUMP_SUMS_BYTES))
+    return rows, cols, band
+
+
+def dump_outputs(out_dir, g, W, H, C, row_begin, row_count, world, rank, dist):
+    """What the timed steps computed, from the state they left in x (call before anything else sweeps): every rank reads
+    its own rows back band by band, rank 0 gathers them and writes x_rows.npy (C, rows, cols) and x_row_sums.npy
+    (C, ceil(H / band)), both float64.  Returns the names and shapes written (rank 0) or None."""
+    import numpy as np
+    rows, cols, band = dump_plan(W, H, C)
+    mine = rows[(rows >= row_begin) & (rows < row_begin + row_count)]
+    sample = np.empty((C, len(mine), len(cols)))
+    sums = np.empty((C, row_count))
+    chunk = max(1, (64 << 20) // (8 * W))
+    for ch in range(C):
+        for y0 in range(row_begin, row_begin + row_count, chunk):
+            n = min(chunk, row_begin + row_count - y0)
+            xs = g.get_x(ch, y0, n)
+            sums[ch, y0 - row_begin:y0 - row_begin + n] = xs.sum(axis=1)
+            hit = (mine >= y0) & (mine < y0 + n)
+            sample[ch, hit] = xs[mine[hit] - y0][:, cols]
+    parts = [(row_begin, sample, sums)]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, (row_begin, sample, sums))
+    if rank != 0:
+        return None
+    parts.sort(key=lambda p: p[0])
+    x_rows = np.concatenate([p[1] for p in parts], axis=1)
+    row_sums = np.concatenate([p[2] for p in parts], axis=1)
+    x_row_sums = np.add.reduceat(row_sums, np.arange(0, H, band), axis=1) if band > 1 else row_sums
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in (("x_rows", x_rows), ("x_row_sums", x_row_sums)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+        written[name] = list(a.shape)
+    return written
+
+
 # k_lex_wg at 8 sweeps per pass: b row of 76 columns per 62 pixels, x row of 63, x write, edge values both ways
 LEX_WG_BYTES_PER_UPDATE = (76.0 / 62.0 * 8.0 + 63.0 / 62.0 * 8.0 + 8.0) / 8.0 + 2.0 * 16.0 / 62.0
 
@@ -571,7 +641,7 @@ def spawn_ranks(n: int) -> int:
         time.sleep(0.2)
         for pr in list(live):
             code = pr.poll()
-            if code is None:
+            if code is None or pr not in live:                 # running, or gone while the others were being stopped
                 continue
             live.remove(pr)
             if code != 0 and rc == 0:
@@ -697,6 +767,9 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     region_ms, region_launches, region_iters = g.region_end()
+    # untimed: x as the last timed step left it, before anything below sweeps again
+    dumped = (dump_outputs(args.dump_outputs, g, W, H, C, row_begin, row_count, world, rank, dist)
+              if args.dump_outputs else None)
     # the CPU baseline needs minutes of host time and no GPU: a child process beside the untimed rest of the run
     cpu_run = CpuBaselineRun(args) if (world == 1 and rank == 0 and not args.no_cpu_baseline) else None
 
@@ -821,6 +894,10 @@ def main():
             "roofline": roofline,
         }
         out.update(extra)
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped, "dtype": "float64",
+                                   "what": f"x after the last timed step ({total_iters} iterations from x0 = 1): rows and columns "
+                                           f"of bench.dump_plan({W}, {H}, {C}), and the sum of every row"}
         if world > 1:
             # what the multi-rank run really was: the ranks the library's communicator holds, the ghost depth chosen
             # (with the timings that chose it) and what one halo exchange costs beside one exchange interval

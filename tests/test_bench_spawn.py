@@ -9,10 +9,12 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 def test_gpus_n_spawns_ranks_with_the_rendezvous_environment():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"                              # no device visible, even where a GPU is present
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "1", "--warmup", "0"],
                          capture_output=True, text=True, timeout=300, env=env)
-    # no GPU here: every rank must stop with the no-device message (a loud failure, never a CPU fallback) ...
-    assert out.returncode != 0
+    # no GPU: every rank must stop with the no-device message (a loud failure, never a CPU fallback), and the parent
+    # returns their exit code rather than failing itself ...
+    assert out.returncode == 1 and "Traceback" not in out.stderr, out.stderr[-2000:]
     assert out.stderr.count("bench.py needs an MI355X") == 3, out.stderr[-2000:]
     assert "torch.distributed.run" not in out.stderr              # ... and nobody asks for an external launcher any more
 
@@ -77,3 +79,45 @@ def test_the_headline_system_needs_the_wide_index_type():
     assert not bench.cpu_needs_wide_index(4096) and not bench.cpu_needs_wide_index(14336)
     assert bench.cpu_needs_wide_index(16384)                   # 5 x 16384^2 > 2^30: getNearestIndex's (end + idx) / 2 overflows int
     assert 50.0 < bench.cpu_system_gb(16384) < 70.0
+
+
+def test_dump_plan_is_fixed_by_the_shape_and_stays_within_64_mb():
+    """--dump-outputs samples the iterate at positions that depend on the shape alone (two runs, two builds: the same
+    pixels), always holding the first and last row, and never writes more than 64 MB whatever the shape."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    for W, H, C in ((16384, 16384, 1), (4096, 4096, 3), (2048, 1536, 1), (1, 1, 1), (10 ** 7, 3, 3), (64, 2 * 10 ** 6, 3)):
+        rows, cols, band = bench.dump_plan(W, H, C)
+        again = bench.dump_plan(W, H, C)
+        assert np.array_equal(rows, again[0]) and np.array_equal(cols, again[1]) and band == again[2]
+        assert rows[0] == 0 and rows[-1] == H - 1 and np.all(np.diff(rows) > 0) and np.all(np.diff(cols) > 0)
+        assert 0 <= cols[0] and cols[-1] < W
+        assert 8 * C * (len(rows) * len(cols) + -(-H // band)) <= 64 << 20, (W, H, C)
+    rows, cols, _ = bench.dump_plan(16384, 16384, 1)
+    assert len(cols) == 16384 and len(rows) >= 256                # the headline shape: whole rows, hundreds of them
+
+
+def test_steps_must_be_positive():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode != 0 and "--steps must be >= 1" in out.stderr
+
+
+def test_cpu_baseline_child_skips_what_the_c_oracle_cannot_sweep(tmp_path):
+    """Without the compiled reference (oracle/_ref) the baseline is the C oracle, whose int positions overflow past 2^30
+    entries: the child must skip such a size at once, with a line in the log, instead of sweeping it."""
+    sys.path.insert(0, ROOT)
+    import oracle
+    import pytest
+    try:
+        oracle.Ref()
+        pytest.skip("oracle/_ref is built here: the 64-bit reference sweep takes this size")
+    except (FileNotFoundError, OSError):
+        pass
+    log = tmp_path / "phases.log"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-baseline-child", "16384", "--cpu-log", str(log)],
+                         capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert not [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert "16384^2 skipped" in log.read_text() and "oracle/_ref" in log.read_text()
