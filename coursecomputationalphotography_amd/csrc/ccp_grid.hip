@@ -85,6 +85,7 @@ struct ccp_grid {
     bool tuned = false;
     bool all_border = false;     // debug (CCP_GS_ALL_BORDER): every tile of a pass goes through k_fused_border
     bool force_border = false;   // debug (CCP_GS_FORCE_BORDER): and every trip there takes the border body
+    bool red_store_all = false;  // A/B (CCP_GS_RED_STORE=1): every pass stores both colour halves (run_unchecked)
     DevBuf<double> partial;      // per-block partial sums (L1 step / residual / checksums)
     long partial_region = 0;     // doubles per colour region of `partial` (L1 step)
     DevBuf<double> small;        // 4*kMaxChannels doubles of reduced results
@@ -303,7 +304,7 @@ int masked_tile_census(ccp_grid *g, const FusedParams &P, int T)
 // One pass of depth T over a Dirichlet-mask grid: every tile is an ordinary tile (zero lies outside the block
 // as it does outside the region), tiles without any unknown in reach leave at once.
 template <int T>
-int launch_fused_masked(ccp_grid *g, FusedParams &P, int l1, long *l1_blocks)
+int launch_fused_masked(ccp_grid *g, FusedParams &P, int l1, long *l1_blocks, bool store_red)
 {
     if (T > kMaskedMaxT) return CCP_ERR_BAD_ARG;
     constexpr int TM = T <= kMaskedMaxT ? T : 1;
@@ -332,6 +333,7 @@ int launch_fused_masked(ccp_grid *g, FusedParams &P, int l1, long *l1_blocks)
     constexpr int TMC = T <= kMaskedMaxCheckedT ? T : 1;
     if (l1 == 2) hipLaunchKernelGGL((k_fused_sweep_masked<TMC, 2, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P, g->tile_live.p, rows_p);
     else if (l1 == 1) hipLaunchKernelGGL((k_fused_sweep_masked<TM, 1, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P, g->tile_live.p, rows_p);
+    else if (!store_red) hipLaunchKernelGGL((k_fused_sweep_masked<TM, 0, kFusedUnroll, false>), grid, dim3(kBlock), 0, g->stream, P, g->tile_live.p, rows_p);
     else hipLaunchKernelGGL((k_fused_sweep_masked<TM, 0, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P, g->tile_live.p, rows_p);
     CCP_HIP(hipGetLastError());
     g->last_launches++;
@@ -344,9 +346,12 @@ int launch_fused_masked(ccp_grid *g, FusedParams &P, int l1, long *l1_blocks)
 // l1_blocks[0/1]: block results per (sweep, channel) of the ordinary / the border launch.
 // edge_rows > 0: the EDGE kernels (edge chunks first, in-launch signal); *signalled tells the caller
 // whether the pass will publish g->edge_epoch itself.
+// store_red = false: the ordinary tiles of an unchecked pass store only the black halves (fused_wave says when that is
+// safe; run_unchecked decides); border tiles, checked and edge passes always store both.
 template <int T>
 int launch_fused_t(ccp_grid *g, const double *xin, double *xout, int st_lo, int st_hi, const int *active,
-                   int l1 = 0, long *l1_blocks = nullptr, int rows_override = 0, int edge_rows = 0, bool *signalled = nullptr)
+                   int l1 = 0, long *l1_blocks = nullptr, int rows_override = 0, int edge_rows = 0, bool *signalled = nullptr,
+                   bool store_red = true)
 {
     FusedParams P;
     P.xin = xin;
@@ -364,7 +369,8 @@ int launch_fused_t(ccp_grid *g, const double *xin, double *xout, int st_lo, int 
     P.xcd_swizzle = g->xcd_swizzle ? 1 : 0;
     const bool want_edge = edge_rows > 0 && l1 == 0 && active == nullptr && g->edge_counter && g->edge_signal;
     P.mask = g->maskp.p;
-    if (g->masked) return launch_fused_masked<T>(g, P, l1, l1_blocks);
+    if (l1 != 0 || edge_rows > 0) store_red = true;
+    if (g->masked) return launch_fused_masked<T>(g, P, l1, l1_blocks, store_red);
     fused_tile_counts(g, T, P, want_edge ? edge_rows : 0);
     const int waves = kBlock / kWave;
     const int edge_chunks = std::min(P.nb_top + P.nb_bot, P.n_chunks);
@@ -443,6 +449,7 @@ int launch_fused_t(ccp_grid *g, const double *xin, double *xout, int st_lo, int 
         if (l1 == 2) hipLaunchKernelGGL((k_fused_sweep<TC, 2, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P);
         else if (l1 == 1) hipLaunchKernelGGL((k_fused_sweep<T, 1, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P);
         else if (edge) hipLaunchKernelGGL((k_fused_sweep<T, 0, kFusedUnroll, true>), grid, dim3(kBlock), 0, g->stream, P);
+        else if (!store_red) hipLaunchKernelGGL((k_fused_sweep<T, 0, kFusedUnroll, false, false>), grid, dim3(kBlock), 0, g->stream, P);
         else hipLaunchKernelGGL((k_fused_sweep<T, 0, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P);
     }
     if (n_border) {
@@ -475,8 +482,9 @@ int launch_fused_t(ccp_grid *g, const double *xin, double *xout, int st_lo, int 
 
 // `n_passes` passes of depth T as ONE launch (k_fused_multi): xin -> xout -> xin ...; st_lo/st_hi per pass.  Returns
 // CCP_ERR_UNSUPPORTED when the shape does not qualify (the caller then issues the passes one by one).
+// red_skip: the first red_skip passes store only the black halves in their ordinary tiles (launch_fused_t's store_red).
 template <int T>
-int launch_fused_multi_t(ccp_grid *g, int n_passes, const double *xin, double *xout, const int *st_lo, const int *st_hi)
+int launch_fused_multi_t(ccp_grid *g, int n_passes, const double *xin, double *xout, const int *st_lo, const int *st_hi, int red_skip = 0)
 {
     if (n_passes < 2 || n_passes > kMultiMaxPasses || g->trace_file) return CCP_ERR_UNSUPPORTED;
     if (g->masked && T > kMaskedMaxT) return CCP_ERR_UNSUPPORTED;
@@ -538,6 +546,7 @@ int launch_fused_multi_t(ccp_grid *g, int n_passes, const double *xin, double *x
     const int edge_strips = std::min(P.ns_left + P.ns_right, P.n_strips);
     const long n_border = g->masked ? 0 : (long)edge_chunks * (P.n_strips - edge_strips) + (long)P.n_chunks * edge_strips * P.side_subs;
     M.n_passes = n_passes;
+    M.red_skip = red_skip;
     M.gx = (P.n_strips + waves - 1) / waves;
     M.gy = P.n_chunks;
     M.bgx = (int)((n_border + waves - 1) / waves);
@@ -563,30 +572,30 @@ int launch_fused_multi_t(ccp_grid *g, int n_passes, const double *xin, double *x
 
 template <int TMAX>
 struct FusedMultiDepth {
-    static int launch(int T, ccp_grid *g, int n, const double *xin, double *xout, const int *lo, const int *hi)
+    static int launch(int T, ccp_grid *g, int n, const double *xin, double *xout, const int *lo, const int *hi, int red_skip = 0)
     {
-        if (T == TMAX) return launch_fused_multi_t<TMAX>(g, n, xin, xout, lo, hi);
-        return FusedMultiDepth<TMAX - 1>::launch(T, g, n, xin, xout, lo, hi);
+        if (T == TMAX) return launch_fused_multi_t<TMAX>(g, n, xin, xout, lo, hi, red_skip);
+        return FusedMultiDepth<TMAX - 1>::launch(T, g, n, xin, xout, lo, hi, red_skip);
     }
 };
 template <>
 struct FusedMultiDepth<0> {
-    static int launch(int, ccp_grid *, int, const double *, double *, const int *, const int *) { return CCP_ERR_UNSUPPORTED; }
+    static int launch(int, ccp_grid *, int, const double *, double *, const int *, const int *, int = 0) { return CCP_ERR_UNSUPPORTED; }
 };
 
 // run-time depth -> the instantiation of that depth
 template <int TMAX>
 struct FusedDepth {
     static int launch(int T, ccp_grid *g, const double *xin, double *xout, int st_lo, int st_hi, const int *active,
-                      int l1, long *l1_blocks, int rows_override = 0, int edge_rows = 0, bool *signalled = nullptr)
+                      int l1, long *l1_blocks, int rows_override = 0, int edge_rows = 0, bool *signalled = nullptr, bool store_red = true)
     {
-        if (T == TMAX) return launch_fused_t<TMAX>(g, xin, xout, st_lo, st_hi, active, l1, l1_blocks, rows_override, edge_rows, signalled);
-        return FusedDepth<TMAX - 1>::launch(T, g, xin, xout, st_lo, st_hi, active, l1, l1_blocks, rows_override, edge_rows, signalled);
+        if (T == TMAX) return launch_fused_t<TMAX>(g, xin, xout, st_lo, st_hi, active, l1, l1_blocks, rows_override, edge_rows, signalled, store_red);
+        return FusedDepth<TMAX - 1>::launch(T, g, xin, xout, st_lo, st_hi, active, l1, l1_blocks, rows_override, edge_rows, signalled, store_red);
     }
 };
 template <>
 struct FusedDepth<0> {
-    static int launch(int, ccp_grid *, const double *, double *, int, int, const int *, int, long *, int = 0, int = 0, bool * = nullptr) { return CCP_ERR_BAD_ARG; }
+    static int launch(int, ccp_grid *, const double *, double *, int, int, const int *, int, long *, int = 0, int = 0, bool * = nullptr, bool = true) { return CCP_ERR_BAD_ARG; }
 };
 
 __global__ void k_publish_flag(unsigned long long *flag, unsigned long long epoch)
@@ -645,7 +654,7 @@ int edge_wait_on_stream(ccp_grid *g, hipStream_t s)
 // inside the launch and published through the edge flag (see launch_fused_t); without an in-launch
 // signal the flag is published after the pass.  Same tiles, same arithmetic.
 int launch_fused(ccp_grid *g, int T, const double *xin, double *xout, const int *active, int l1 = 0,
-                 long *l1_blocks = nullptr, int edge_rows = 0)
+                 long *l1_blocks = nullptr, int edge_rows = 0, bool store_red = true)
 {
     const bool shrinking = g->shrink_top || g->shrink_bottom;
     const int s = g->half_sweeps_since_refresh;
@@ -653,7 +662,7 @@ int launch_fused(ccp_grid *g, int T, const double *xin, double *xout, const int 
     const int st_lo = g->shrink_top ? std::min(s + 2 * T, g->ghost_top) : 0;
     const int st_hi = g->geom.local_rows - (g->shrink_bottom ? std::min(s + 2 * T, g->ghost_bottom) : 0);
     if (st_hi > st_lo)
-        CCP_TRY(FusedDepth<kFusedMaxT>::launch(T, g, xin, xout, st_lo, st_hi, active, l1, l1_blocks, 0, edge_rows, nullptr));
+        CCP_TRY(FusedDepth<kFusedMaxT>::launch(T, g, xin, xout, st_lo, st_hi, active, l1, l1_blocks, 0, edge_rows, nullptr, store_red));
     if (shrinking) g->half_sweeps_since_refresh += 2 * T;
     return CCP_OK;
 }
@@ -715,6 +724,10 @@ int run_unchecked(ccp_grid *g, int iterations, const int *active = nullptr, bool
         p ^= 1;
     }
     std::sort(plan.begin(), plan.end(), std::greater<int>());
+    // Pass k may leave out its red half (launch_fused_t's store_red, the argument at fused_wave) only when the pass
+    // after it in THIS plan is unchecked: the last pass stores both halves (whatever reads x after the call sees a
+    // whole buffer), and so does the pass before a checked one (l1_last: it reads the red of its input).
+    auto stores_red = [&](size_t k) { return g->red_store_all || k + 1 >= plan.size() || (l1_last && k + 2 == plan.size()); };
     double *cur = g->x.p, *alt = g->x_alt.p;
     for (size_t k = 0; k < plan.size();) {
         // consecutive passes of one depth as ONE launch (k_fused_multi), where that is switched on and the shape
@@ -733,7 +746,9 @@ int run_unchecked(ccp_grid *g, int iterations, const int *active = nullptr, bool
                     lo[q] = g->shrink_top ? std::min(s, g->ghost_top) : 0;
                     hi[q] = g->geom.local_rows - (g->shrink_bottom ? std::min(s, g->ghost_bottom) : 0);
                 }
-                const int st = FusedMultiDepth<kFusedMaxT>::launch(T, g, n, cur, alt, lo, hi);
+                int red_skip = 0;                                 // the leading passes of the group that may skip red
+                while (red_skip < n && !stores_red(k + red_skip)) ++red_skip;
+                const int st = FusedMultiDepth<kFusedMaxT>::launch(T, g, n, cur, alt, lo, hi, red_skip);
                 if (st == CCP_OK) {
                     if (shrinking) g->half_sweeps_since_refresh += 2 * T * n;
                     if (n & 1) std::swap(cur, alt);
@@ -744,7 +759,7 @@ int run_unchecked(ccp_grid *g, int iterations, const int *active = nullptr, bool
             }
         }
         const bool last = k + 1 == plan.size();
-        CCP_TRY(launch_fused(g, plan[k], cur, alt, active, (l1_last && last) ? 1 : 0, l1_blocks, last ? edge_rows : 0));
+        CCP_TRY(launch_fused(g, plan[k], cur, alt, active, (l1_last && last) ? 1 : 0, l1_blocks, last ? edge_rows : 0, stores_red(k)));
         std::swap(cur, alt);
         ++k;
     }
@@ -866,6 +881,7 @@ try {
     if (const char *e = getenv("CCP_GS_TMAX")) g->fuse_tmax = std::max(1, std::min(kFusedMaxT, atoi(e)));
     if (const char *e = getenv("CCP_GS_ALL_BORDER")) g->all_border = atoi(e) != 0;
     if (const char *e = getenv("CCP_GS_FORCE_BORDER")) g->force_border = atoi(e) != 0;
+    if (const char *e = getenv("CCP_GS_RED_STORE")) g->red_store_all = atoi(e) != 0;
     if (const char *e = getenv("CCP_GS_CHUNK")) g->rows_per_chunk = std::max(1, atoi(e));
     choose_tiling(g);
     g->masked = (d->flags & CCP_GRID_DIRICHLET_MASK) != 0;

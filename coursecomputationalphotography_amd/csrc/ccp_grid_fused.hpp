@@ -326,7 +326,8 @@ constexpr int kQuarterHi = 0x3FD00000;                  // high word of 0.25
 // fixed at zero (whose b is 0).  The stencil is the uniform 5-point one — no degree logic anywhere.  Both values of q
 // have a zero low word, so the window keeps the HIGH word only (QWord: one VGPR per pixel instead of two — what lets
 // the masked pass go as deep as the plain one) and the factor is put together at its use (a register move or two).
-template <int T, int MODE, int L1, int UNR, int NT, int AN, bool MASKED = false, int NQ = 1, bool COH = false, class Win = FusedWindow<T, UNR>>
+template <int T, int MODE, int L1, int UNR, int NT, int AN, bool MASKED = false, int NQ = 1, bool COH = false, bool STORE_RED = true,
+          class Win = FusedWindow<T, UNR>>
 __device__ __forceinline__ void fused_step(double (&wr)[NT], double (&wk)[NT], double (&br)[NT], double (&bk)[NT],
                                            double (&acc)[AN], const FusedCtx &cx, const Geom &g, int f, int i,
                                            QWord (&qr)[NQ], QWord (&qk)[NQ])
@@ -410,11 +411,12 @@ __device__ __forceinline__ void fused_step(double (&wr)[NT], double (&wk)[NT], d
         if (c) wk[sr] = nv; else wr[sr] = nv;
     }
     // ---- row f - HS is final: store it (dropped by the range check outside [ra, rb)) ----------
+    // (!STORE_RED: the red half is not stored at all — see fused_wave)
     {
         const int r = f - HS;
         const int sr = Win::slot(i, HS);
         const __amdgpu_buffer_rsrc_t ro = row_rsrc(cx.xout, g, r, r >= cx.ra && r < cx.rb);
-        buf_store<COH>(wr[sr], ro, cx.st_r);
+        if constexpr (STORE_RED) buf_store<COH>(wr[sr], ro, cx.st_r);
         buf_store<COH>(wk[sr], ro, cx.st_k);
     }
     // keep the machine scheduler from pulling later steps' work up across this point:
@@ -462,17 +464,41 @@ __device__ __forceinline__ void fused_ctx_init(FusedCtx &cx, const double *__res
 // BORDERTILE = false: every pixel the wave can touch is ordinary: one straight-line loop of
 // kStepFast trips.  BORDERTILE = true: each trip picks among the three bodies (force_border:
 // debug, every trip takes kStepBorder).
-template <int T, bool BORDERTILE, int L1, int UNR, int AN, bool MASKED = false, bool COH = false>
+//
+// STORE_RED = false (ordinary tiles of an unchecked pass whose output only an unchecked pass reads): the red half of
+// every stored row is left out — half the pass's HBM writes.  Why nothing can miss it:
+//   * the next pass's first half-sweep (h = 1) recomputes every red pixel from black x and b; the red x it loads is
+//     read only where an update keeps `old` or where a step sum is taken (L1 != 0);
+//   * kStepFast never keeps `old` (plain: always the stencil; MASKED: fma(sum, 0, 0) = +0 for a fixed pixel), and
+//     an unchecked pass (L1 = 0) takes no step sum.  The pass before a checked one (L1 = 1 at T = 1 reads the
+//     input's red at h = 1; L1 = 2 always does) stores both halves — the host's rule in run_unchecked;
+//   * the pixels that DO keep `old` — outside the image (px_ok false), a_ii = 0 (the bottom-right corner, every
+//     pixel of a one-pixel-wide image) — lie at an image edge, and a tile whose stored columns or rows touch an image
+//     edge is a border tile in every tiling (fused_tile_counts: an ordinary tile's whole extended region lies in
+//     columns [1, W-2] and rows [1, H-2]).  Border tiles always store both halves, so such a pixel's red value is
+//     carried from pass to pass by the border tiles that own it, whatever the depth of either pass;
+//   * the LAST pass of every call stores both halves: whatever reads x after a call (the host, the in-place
+//     half-sweep kernels, the halo exchange, a checked solve) sees a whole buffer.  The partner buffer's red half
+//     is stale after a call, and it is only ever written next.
+// CCP_RED_SKIP_RUNTIME (experiment build): the same skip through the range check (st_r = kLaneOut) instead of leaving
+// the instruction out.
+#ifndef CCP_RED_SKIP_RUNTIME
+#define CCP_RED_SKIP_RUNTIME 0
+#endif
+template <int T, bool BORDERTILE, int L1, int UNR, int AN, bool MASKED = false, bool COH = false, bool STORE_RED = true>
 __device__ __forceinline__ void fused_wave(const double *__restrict__ xin, double *__restrict__ xout,
                                            const double *__restrict__ bb, const Geom &g, int sx,
                                            int ra, int rb, double (&acc)[AN], bool force_border = false,
                                            const unsigned char *__restrict__ mask = nullptr)
 {
     static_assert(!(MASKED && BORDERTILE), "a Dirichlet-mask grid has no border tiles: everything outside is zero");
+    static_assert(STORE_RED || (!BORDERTILE && L1 == 0), "border tiles and checked passes store both halves");
     using Win = FusedWindow<T, UNR>;
     constexpr int HS = Win::HS, G = Win::G, NT = Win::NT;
+    constexpr bool SR = STORE_RED || CCP_RED_SKIP_RUNTIME;     // the red store instruction is emitted
     FusedCtx cx;
     fused_ctx_init<T>(cx, xin, xout, bb, g, sx, ra, rb, mask);
+    if (!STORE_RED) cx.st_r = kLaneOut;                         // (CCP_RED_SKIP_RUNTIME: dropped by the range check)
     // the march starts on an even image row (y0 + base even) and advances G (even) rows per
     // trip, so the colour parity of every unrolled row update is a compile-time constant
     const int base = cx.m0 - ((g.y0 + cx.m0) & 1);
@@ -520,7 +546,7 @@ __device__ __forceinline__ void fused_wave(const double *__restrict__ xin, doubl
             }                                                                                                                 \
             __builtin_amdgcn_sched_barrier(0);                                                                                \
             _Pragma("unroll") for (int i = 0; i < G; ++i)                                                                     \
-                fused_step<T, kStepFast, L1, UNR, NT, AN, MASKED, NQ, COH>(wr, wk, br, bk, acc, cx, g, (FB) + i, i, qr, qk);   \
+                fused_step<T, kStepFast, L1, UNR, NT, AN, MASKED, NQ, COH, SR>(wr, wk, br, bk, acc, cx, g, (FB) + i, i, qr, qk);   \
             _Pragma("unroll") for (int s = 0; s + G < NT; ++s) {                                                              \
                 wr[s] = wr[s + G]; wk[s] = wk[s + G]; br[s] = br[s + G]; bk[s] = bk[s + G];                                   \
                 if (MASKED) { qr[s] = qr[s + G]; qk[s] = qk[s + G]; }                                                         \
@@ -549,7 +575,7 @@ __device__ __forceinline__ void fused_wave(const double *__restrict__ xin, doubl
         if (!BORDERTILE) {
 #pragma unroll
             for (int i = 0; i < G; ++i)
-                fused_step<T, kStepFast, L1, UNR, NT, AN, MASKED, NQ, COH>(wr, wk, br, bk, acc, cx, g, fb + i, i, qr, qk);
+                fused_step<T, kStepFast, L1, UNR, NT, AN, MASKED, NQ, COH, SR>(wr, wk, br, bk, acc, cx, g, fb + i, i, qr, qk);
         } else {
             // rows the trip updates that matter: fb-HS .. fb+G-2, clipped to the rows this wave holds
             const int r_first = max(fb - HS, cx.m0), r_last = min(fb + G - 2, cx.m1 - 1);
@@ -625,7 +651,8 @@ __device__ __forceinline__ void fused_write_partials(double (&acc)[AN], double *
 
 // Ordinary tiles.  grid = (ceil(n_strips / 4), n_chunks, channels); block = 256 threads = 4 waves =
 // 4 adjacent strips of one chunk; waves of border tiles leave at once (k_fused_border runs them).
-template <int T, int L1, int UNR, bool EDGE = false>
+// STORE_RED = false: the red halves are not stored (fused_wave; the host decides per pass).
+template <int T, int L1, int UNR, bool EDGE = false, bool STORE_RED = true>
 __global__ void __launch_bounds__(kBlock, fused_waves_per_simd(T, L1))
 k_fused_sweep(FusedParams P)
 {
@@ -649,7 +676,7 @@ k_fused_sweep(FusedParams P)
         const long off = (long)ch * g.ch_stride;
         unsigned long long t0 = 0;
         fused_trace_begin(P, t0);
-        fused_wave<T, false, L1, UNR, AN>(P.xin + off, P.xout + off, P.b + off, g, sx, ra, rb, acc);
+        fused_wave<T, false, L1, UNR, AN, false, false, STORE_RED>(P.xin + off, P.xout + off, P.b + off, g, sx, ra, rb, acc);
         if (EDGE && fused_is_edge_chunk(P, chunk)) fused_signal_edge(P);
         fused_trace_end(P, t0, (((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (kBlock / kWave) + wave, chunk, sx, ch, 0);
     }
@@ -676,7 +703,7 @@ __host__ __device__ constexpr int masked_waves_per_simd(int T, int L1 = 0)
 // tile_rows (round 4): the rows of the tile that hold an unknown in the strip's columns, [2i] .. [2i + 1) — a tile on the
 // rim of a region marches only those (rows without an unknown are zero in both ping-pong buffers and stay so, like the
 // dead tiles; what the kept rows read of them is the zero that is there).
-template <int T, int L1, int UNR>
+template <int T, int L1, int UNR, bool STORE_RED = true>
 __global__ void __launch_bounds__(kBlock, masked_waves_per_simd(T, L1))
 k_fused_sweep_masked(FusedParams P, const unsigned char *__restrict__ tile_live, const int *__restrict__ tile_rows)
 {
@@ -702,7 +729,7 @@ k_fused_sweep_masked(FusedParams P, const unsigned char *__restrict__ tile_live,
         if (ra < rb) {
             const Geom &g = P.g;
             const long off = (long)ch * g.ch_stride;
-            fused_wave<T, false, L1, UNR, AN, true>(P.xin + off, P.xout + off, P.b + off, g, sx, ra, rb, acc, false, P.mask);
+            fused_wave<T, false, L1, UNR, AN, true, false, STORE_RED>(P.xin + off, P.xout + off, P.b + off, g, sx, ra, rb, acc, false, P.mask);
         }
     }
     fused_write_partials<L1, AN>(acc, P.partial, ch, scratch, bx, by);
@@ -828,6 +855,7 @@ constexpr int kMultiMaxPasses = 8;
 struct FusedMultiParams {
     FusedParams P;                 // pass 0: xin -> xout with the group's tiling; odd passes run xout -> xin
     int n_passes;
+    int red_skip;                  // passes q < red_skip store only the black halves in their ordinary tiles (fused_wave)
     int st_lo[kMultiMaxPasses], st_hi[kMultiMaxPasses];   // rows pass q finalises and stores
     int gx, gy, bgx;               // workgroups of the ordinary tiles (gx strips-of-4 x gy chunks) and of the border tiles, per channel
     int channels;
@@ -953,9 +981,17 @@ k_fused_multi(FusedMultiParams M)
         const double *xin = ((q & 1) ? P.xout : P.xin) + off;
         double *xout = ((q & 1) ? const_cast<double *>(P.xin) : P.xout) + off;
         double acc[1] = {0.0};
-        if (MASKED) fused_wave<T, false, 0, UNR, 1, MASKED, true>(xin, xout, P.b + off, g, sx, r0, r1, acc, false, P.mask);
-        else if (border) fused_wave<T, true, 0, UNR, 1, false, true>(xin, xout, P.b + off, g, sx, r0, r1, acc, false);
-        else fused_wave<T, false, 0, UNR, 1, false, true>(xin, xout, P.b + off, g, sx, r0, r1, acc);
+        const bool skip_red = q < M.red_skip;                        // (wave-uniform)
+        if (MASKED) {
+            if (skip_red) fused_wave<T, false, 0, UNR, 1, MASKED, true, false>(xin, xout, P.b + off, g, sx, r0, r1, acc, false, P.mask);
+            else fused_wave<T, false, 0, UNR, 1, MASKED, true>(xin, xout, P.b + off, g, sx, r0, r1, acc, false, P.mask);
+        } else if (border) {
+            fused_wave<T, true, 0, UNR, 1, false, true>(xin, xout, P.b + off, g, sx, r0, r1, acc, false);   // (always both halves)
+        } else if (skip_red) {
+            fused_wave<T, false, 0, UNR, 1, false, true, false>(xin, xout, P.b + off, g, sx, r0, r1, acc);
+        } else {
+            fused_wave<T, false, 0, UNR, 1, false, true>(xin, xout, P.b + off, g, sx, r0, r1, acc);
+        }
     }
     // ---- publish: the (write-through) stores acknowledged, then the count ----------------------------------------
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");           // (compiler ordering: the stores stay above the count)
