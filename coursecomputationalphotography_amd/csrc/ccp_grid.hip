@@ -1,6 +1,7 @@
 // ccp_grid.hip — C ABI of the structured (matrix-free) Poisson grid path.  See include/ccp_gs.h.
 #include "ccp_grid_kernels.hpp"
 #include "ccp_grid_fused.hpp"
+#include "ccp_grid_fused_wide.hpp"
 #include "ccp_grid_lex.hpp"
 #include "ccp_cg.hpp"
 #include "ccp_grid_cg.hpp"
@@ -86,6 +87,7 @@ struct ccp_grid {
     bool all_border = false;     // debug (CCP_GS_ALL_BORDER): every tile of a pass goes through k_fused_border
     bool force_border = false;   // debug (CCP_GS_FORCE_BORDER): and every trip there takes the border body
     bool red_store_all = false;  // A/B (CCP_GS_RED_STORE=1): every pass stores both colour halves (run_unchecked)
+    bool wide = true;            // A/B (CCP_GS_WIDE=0): the depth-8 unchecked passes keep 128-px ordinary strips (k_fused_sweep)
     DevBuf<double> partial;      // per-block partial sums (L1 step / residual / checksums)
     long partial_region = 0;     // doubles per colour region of `partial` (L1 step)
     DevBuf<double> small;        // 4*kMaxChannels doubles of reduced results
@@ -421,8 +423,16 @@ int launch_fused_t(ccp_grid *g, const double *xin, double *xout, int st_lo, int 
         P.edge_counter = g->edge_counter + (g->edge_epoch % kEdgeRing);
     }
     if (signalled) *signalled = edge;
+    // The ordinary tiles of an unchecked depth-8 pass run on wide strips (k_fused_sweep_wide): the columns
+    // [wx0, wx1) that the inner narrow strips would store, in the chunks between the border chunk rows.  The border
+    // tiles keep the narrow tiling above, so ns_left / ns_right and the red-skip argument at fused_wave hold as they are.
+    const bool wide = T == kWideT && g->wide && l1 == 0 && !edge && any_plain;
+    const int wx0 = P.ns_left * U, wx1 = (P.n_strips - P.ns_right) * U;
+    const int n_wide = wide ? (wx1 - wx0 + wide_useful_px(T) - 1) / wide_useful_px(T) : 0;
+    const dim3 wgrid((unsigned)((n_wide + kWideWaves - 1) / kWideWaves), (unsigned)(P.n_chunks - edge_chunks), (unsigned)g->desc.channels);
+    const dim3 pgrid = wide ? wgrid : grid;                   // the ordinary launch
     // diagnostics: per-wave time stamps of this pass (ordinary launch first, border launch behind it)
-    const size_t trace_plain = (size_t)grid.x * grid.y * grid.z * waves * 4, trace_border = (size_t)bgrid.x * bgrid.z * waves * 4;
+    const size_t trace_plain = (size_t)pgrid.x * pgrid.y * pgrid.z * waves * 4, trace_border = (size_t)bgrid.x * bgrid.z * waves * 4;
     unsigned long long *trace_p = nullptr, *trace_b = nullptr;
     if (g->trace_file) {
         if (g->trace.n < trace_plain + trace_border) CCP_TRY(g->trace.alloc(trace_plain + trace_border));
@@ -449,6 +459,8 @@ int launch_fused_t(ccp_grid *g, const double *xin, double *xout, int st_lo, int 
         if (l1 == 2) hipLaunchKernelGGL((k_fused_sweep<TC, 2, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P);
         else if (l1 == 1) hipLaunchKernelGGL((k_fused_sweep<T, 1, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P);
         else if (edge) hipLaunchKernelGGL((k_fused_sweep<T, 0, kFusedUnroll, true>), grid, dim3(kBlock), 0, g->stream, P);
+        else if (wide && !store_red) hipLaunchKernelGGL((k_fused_sweep_wide<kWideT, false>), wgrid, dim3(kBlock), 0, g->stream, P, wx0, wx1, n_wide);
+        else if (wide) hipLaunchKernelGGL((k_fused_sweep_wide<kWideT, true>), wgrid, dim3(kBlock), 0, g->stream, P, wx0, wx1, n_wide);
         else if (!store_red) hipLaunchKernelGGL((k_fused_sweep<T, 0, kFusedUnroll, false, false>), grid, dim3(kBlock), 0, g->stream, P);
         else hipLaunchKernelGGL((k_fused_sweep<T, 0, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P);
     }
@@ -467,7 +479,7 @@ int launch_fused_t(ccp_grid *g, const double *xin, double *xout, int st_lo, int 
         std::vector<unsigned long long> host(trace_plain + trace_border);
         CCP_HIP(hipMemcpy(host.data(), g->trace.p, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         if (FILE *f = fopen(g->trace_file, "ab")) {
-            const unsigned long long head[8] = {0x43435054524143ull, (unsigned long long)T, grid.x, grid.y, grid.z, bgrid.x, (unsigned long long)host.size(),
+            const unsigned long long head[8] = {0x43435054524143ull, (unsigned long long)T, pgrid.x, pgrid.y, pgrid.z, bgrid.x, (unsigned long long)host.size(),
                                                 (unsigned long long)P.rows_per_chunk};
             fwrite(head, sizeof(head), 1, f);
             fwrite(host.data(), sizeof(unsigned long long), host.size(), f);
@@ -882,6 +894,7 @@ try {
     if (const char *e = getenv("CCP_GS_ALL_BORDER")) g->all_border = atoi(e) != 0;
     if (const char *e = getenv("CCP_GS_FORCE_BORDER")) g->force_border = atoi(e) != 0;
     if (const char *e = getenv("CCP_GS_RED_STORE")) g->red_store_all = atoi(e) != 0;
+    if (const char *e = getenv("CCP_GS_WIDE")) g->wide = atoi(e) != 0;
     if (const char *e = getenv("CCP_GS_CHUNK")) g->rows_per_chunk = std::max(1, atoi(e));
     choose_tiling(g);
     g->masked = (d->flags & CCP_GRID_DIRICHLET_MASK) != 0;
