@@ -161,6 +161,8 @@ CSR_ROWS = [
     {"matrix": "mask", "W": 320, "H": 240, "world": 2, "iters": 12, "cg": [1e-30, 25]},
     {"matrix": "mask", "W": 400, "H": 300, "world": 3, "iters": 9, "x0": True, "slack": 3, "cuts": [0, 0.21, 0.77, 1.0], "cg": [1e-3, 4000]},
     {"matrix": "mask", "W": 512, "H": 384, "world": 4, "iters": 7, "cuts": [0, 0.5, 0.5, 0.8, 1.0], "cg": [1e-30, 30]},       # an EMPTY block
+    # 1,224,706 unknowns: each block's vector kernels stride (> 524,288 rows) and k_sell_apply<2> takes a second slice per wave
+    {"matrix": "mask", "W": 2100, "H": 1500, "world": 2, "iters": 3, "cg": [1e-30, 20]},
     # random symmetric pattern, the library's greedy colouring (several colours), every block coupled to every other
     {"matrix": "random", "n": 5000, "deg": 3, "world": 3, "iters": 6, "x0": True},
     {"matrix": "random", "n": 3001, "deg": 2, "world": 4, "iters": 5, "empty_rows": True, "slack": 1},
@@ -242,6 +244,8 @@ def test_grid_conjugate_gradient_on_row_blocks(fake_env):
         {"kind": "grid_cg", "world": 3, "W": 513, "H": 300, "C": 2, "ghost": 2, "eps": 1e-30, "iters": 25},
         {"kind": "grid_cg", "world": 4, "W": 640, "H": 480, "C": 1, "ghost": 4, "eps": 1e-3, "iters": 5000, "mask": True, "discs": 30},
         {"kind": "grid_cg", "world": 2, "W": 400, "H": 300, "C": 1, "ghost": 16, "eps": 1e-30, "iters": 40, "mask": True},
+        # blocks of 700 rows x 2 x pitch 784 = 1,097,600 elements: every vector kernel of the blocked loop strides
+        {"kind": "grid_cg", "world": 2, "W": 1537, "H": 1400, "C": 1, "ghost": 4, "eps": 1e-30, "iters": 20},
     ]
     for r in drive(fake_env, cases):
         c = r["case"]
