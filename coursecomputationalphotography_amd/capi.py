@@ -33,6 +33,7 @@ ABI_SYMBOLS = (
     "ccp_grid_synchronize", "ccp_grid_set_b_host", "ccp_grid_set_x_host", "ccp_grid_get_x_host",
     "ccp_grid_get_b_host", "ccp_grid_set_mask_host", "ccp_grid_fill_x", "ccp_grid_b_from_x", "ccp_grid_randomize_x",
     "ccp_grid_sweep", "ccp_grid_sweep_edges_first", "ccp_grid_stream_wait_edges", "ccp_grid_tune", "ccp_grid_set_fused", "ccp_grid_set_tiling", "ccp_grid_get_tiling", "ccp_grid_sweep_l1", "ccp_grid_halo_refreshed", "ccp_grid_gauss_seidel", "ccp_grid_gauss_seidel_lexicographic", "ccp_debug_lex_tickets", "ccp_grid_conjugate_gradient",
+    "ccp_grid_mg_conjugate_gradient", "ccp_grid_mg_apply", "ccp_grid_mg_level",
     "ccp_grid_residual_norm2", "ccp_grid_abs_sum", "ccp_grid_assemble_rhs", "ccp_grid_assemble_from_images", "ccp_grid_store_u8",
     "ccp_grid_set_x_u8", "ccp_grid_last_timing", "ccp_grid_region_begin", "ccp_grid_region_end",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
@@ -158,6 +159,9 @@ def load() -> C.CDLL:
     L.ccp_csr_conjugate_gradient.argtypes = [vp, vp, vp, vp, dbl, i32, C.POINTER(Report)]
     L.ccp_csr_conjugate_gradient_jacobi.argtypes = [vp, vp, vp, dbl, i32, C.POINTER(Report)]
     L.ccp_grid_conjugate_gradient.argtypes = [vp, dbl, i32, C.POINTER(Report)]
+    L.ccp_grid_mg_conjugate_gradient.argtypes = [vp, dbl, i32, i32, C.POINTER(Report)]
+    L.ccp_grid_mg_apply.argtypes = [vp, i32]
+    L.ccp_grid_mg_level.argtypes = [vp, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
     L.ccp_csr_apply_to_vector.argtypes = [vp, vp, vp]
     L.ccp_csr_residual_norm2.argtypes = [vp, vp, vp, C.POINTER(dbl), C.POINTER(dbl)]
     L.ccp_grid_create.argtypes = [C.POINTER(GridDesc), C.POINTER(vp)]
@@ -596,6 +600,29 @@ class Grid:
         reps = (Report * self.C)()
         check(self.L.ccp_grid_conjugate_gradient(self.h, epsilon, max_iteration, reps), "ccp_grid_conjugate_gradient")
         return list(reps)
+
+    def mg_conjugate_gradient(self, epsilon, max_iteration, smoothing_sweeps=2):
+        """Multigrid-preconditioned CG from the resident x, channel by channel (one Report per channel)."""
+        reps = (Report * self.C)()
+        check(self.L.ccp_grid_mg_conjugate_gradient(self.h, epsilon, max_iteration, smoothing_sweeps, reps),
+              "ccp_grid_mg_conjugate_gradient")
+        return list(reps)
+
+    def mg_apply(self, smoothing_sweeps=2):
+        """x := M^-1 b (one V-cycle per channel; diagnostic)."""
+        check(self.L.ccp_grid_mg_apply(self.h, smoothing_sweeps), "ccp_grid_mg_apply")
+
+    def mg_levels(self):
+        """The multigrid hierarchy: one (diag, w_east, w_south) triple of H_k x W_k arrays per level, level 0 first."""
+        n, w, h = C.c_int32(), C.c_int32(), C.c_int32()
+        check(self.L.ccp_grid_mg_level(self.h, 0, C.byref(n), None, None, None, None, None), "ccp_grid_mg_level")
+        levels = []
+        for k in range(n.value):
+            check(self.L.ccp_grid_mg_level(self.h, k, None, C.byref(w), C.byref(h), None, None, None), "ccp_grid_mg_level")
+            d, we, ws = (np.empty((h.value, w.value), dtype=np.float64) for _ in range(3))
+            check(self.L.ccp_grid_mg_level(self.h, k, None, None, None, _ptr(d), _ptr(we), _ptr(ws)), "ccp_grid_mg_level")
+            levels.append((d, we, ws))
+        return levels
 
     def residual_norm2(self):
         out = np.empty(2 * self.C, dtype=np.float64)

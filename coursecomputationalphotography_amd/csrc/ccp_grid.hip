@@ -5,6 +5,7 @@
 #include "ccp_grid_lex.hpp"
 #include "ccp_cg.hpp"
 #include "ccp_grid_cg.hpp"
+#include "ccp_grid_mg_view.hpp"
 #include "ccp_comm.hpp"
 
 #include <algorithm>
@@ -120,6 +121,7 @@ struct ccp_grid {
     bool timing_pending = false;
     int cpt = 2;                 // half-columns per thread of the sweep kernel
     int rows_per_block = 32;
+    MgHierarchy *mg = nullptr;   // multigrid hierarchy (ccp_grid_mg.hip), built at the first ccp_grid_mg_* call
 };
 
 namespace {
@@ -977,6 +979,7 @@ try {
     if (g->edge_flag) (void)hipFree(g->edge_flag);
     if (g->edge_timeout) (void)hipHostFree(g->edge_timeout);
     if (g->lex_order_pin) (void)hipHostFree(g->lex_order_pin);
+    mg_release(g->mg);
     delete g;
     return CCP_OK;
 } CCP_ABI_CATCH
@@ -1055,6 +1058,8 @@ try {
     CCP_HIP(hipStreamSynchronize(g->stream));
     g->unknowns = count;
     g->live_T = -1;                                      // the tile census belongs to the old mask
+    mg_release(g->mg);                                   // ... and so does the multigrid hierarchy
+    g->mg = nullptr;
     CCP_TRY(zero_unmasked(g, g->x.p));
     CCP_TRY(zero_unmasked(g, g->b.p));
     if (g->x_alt.p) CCP_TRY(zero_unmasked(g, g->x_alt.p));
@@ -1062,6 +1067,22 @@ try {
 } CCP_ABI_CATCH
 
 }  // extern "C"
+
+// Library-internal: what ccp_grid_mg.hip needs of a handle
+int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
+{
+    CCP_TRY(bind(g));
+    v->geom = g->geom;
+    v->channels = g->desc.channels;
+    v->masked = g->masked;
+    v->one_block = !g->ghost_top && !g->ghost_bottom && g->desc.row_count == g->desc.height;
+    v->x = g->x.p;
+    v->b = g->b.p;
+    v->mask = g->maskp.p;
+    v->stream = g->stream;
+    v->cache = &g->mg;
+    return CCP_OK;
+}
 
 // Library-internal twin of ccp_grid_set_mask_host for a mask that is already on the device in the grid's layout
 // (the region recognition builds it there: ccp_csr.hip).  Asynchronous on the handle's stream.
@@ -1080,6 +1101,8 @@ int ccp::grid_set_mask_split_device(ccp_grid *g, const unsigned char *split_mask
     CCP_HIP(hipMemcpyAsync(g->maskp.p, split_mask_dev, (size_t)g->geom.ch_stride, hipMemcpyDeviceToDevice, g->stream));
     g->unknowns = unknowns;
     g->live_T = -1;                                      // the tile census belongs to the old mask
+    mg_release(g->mg);                                   // ... and so does the multigrid hierarchy
+    g->mg = nullptr;
     CCP_TRY(zero_unmasked(g, g->x.p));
     CCP_TRY(zero_unmasked(g, g->b.p));
     if (g->x_alt.p) CCP_TRY(zero_unmasked(g, g->x_alt.p));

@@ -1,0 +1,24 @@
+// ccp_grid_mg_view.hpp — what the multigrid solver (ccp_grid_mg.hip) needs of a grid handle (ccp_grid.hip owns the
+// handle, ccp_grid_mg.hip the hierarchy cached on it).  Declarations only: no kernels.
+#pragma once
+
+#include "ccp_grid_stencil.hpp"
+
+namespace ccp {
+
+struct MgHierarchy;
+void mg_release(MgHierarchy *h);
+
+struct GridMgView {
+    Geom geom;
+    int channels;
+    bool masked;
+    bool one_block;                  // no ghost rows: the whole image in this handle
+    double *x, *b;
+    const unsigned char *mask;
+    hipStream_t stream;
+    MgHierarchy **cache;             // the handle's cached hierarchy (built on first use, dropped with the mask)
+};
+int grid_mg_view(ccp_grid *g, GridMgView *v);
+
+}  // namespace ccp

@@ -1,0 +1,106 @@
+// ccp_grid_stencil.hpp — the grid layout (Geom, row_off), 16-byte lane vectors and the 5-point stencil of
+// SolveChannel's matrix (classify, gs_update, apply_row): the device helpers of ccp_grid_kernels.hpp, which explains
+// the layout and the arithmetic.  No kernels here, so that more than one translation unit may include it.
+#pragma once
+
+#include "ccp_common.hpp"
+
+namespace ccp {
+
+struct Geom {
+    int W, H;            // whole image
+    int y0;              // image row of local row 0
+    int local_rows;      // ghost_top + owned + ghost_bottom
+    int own_lo, own_hi;  // owned local rows [own_lo, own_hi)
+    long pitch;          // doubles per colour half-row
+    long ch_stride;      // doubles per channel = local_rows*2*pitch
+};
+
+__device__ __forceinline__ long row_off(const Geom &g, int l, int c)
+{
+    return ((long)l * 2 + c) * g.pitch;
+}
+
+template <int CPT>
+__device__ __forceinline__ void ld_vec(const double *__restrict__ p, double (&v)[CPT])
+{
+    static_assert(CPT % 2 == 0, "CPT must be even (16-byte lane accesses)");
+#pragma unroll
+    for (int k = 0; k < CPT; k += 2) {
+        const double2 t = *reinterpret_cast<const double2 *>(p + k);
+        v[k] = t.x;
+        v[k + 1] = t.y;
+    }
+}
+
+template <int CPT>
+__device__ __forceinline__ void st_vec(double *__restrict__ p, const double (&v)[CPT])
+{
+#pragma unroll
+    for (int k = 0; k < CPT; k += 2) {
+        double2 t;
+        t.x = v[k];
+        t.y = v[k + 1];
+        *reinterpret_cast<double2 *>(p + k) = t;
+    }
+}
+
+template <int CPT>
+__device__ __forceinline__ void zero_vec(double (&v)[CPT])
+{
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) v[k] = 0.0;
+}
+
+// Which neighbours pixel (x,y) has in the reference matrix and its diagonal:
+// cell(x,y) <=> x < W-1 && y < H-1 (the forward-difference loop bounds, PhotoMontage.cpp:551-554).
+struct Stencil {
+    bool up, left, right, down;
+    int diag;
+};
+
+__device__ __forceinline__ Stencil classify(const Geom &g, int x, int y, int l)
+{
+    Stencil s;
+    const bool here = (x < g.W - 1) && (y < g.H - 1);
+    const bool cf_up = (y >= 1) && (x < g.W - 1);
+    s.left = (x >= 1) && (y < g.H - 1);
+    s.right = here;
+    s.diag = (int)cf_up + (int)s.left + 2 * (int)here + (int)((x | y) == 0);
+    // a neighbour row outside the local block (beyond the ghosts) is treated as absent; such
+    // rows are never inside the sweep range of a correctly driven handle.
+    s.up = cf_up && (l >= 1);
+    s.down = here && (l + 1 < g.local_rows);
+    return s;
+}
+
+// (b - sigma) / a_ii with the reference's accumulation order.  Returns false when the row is
+// skipped (a_ii == 0, sparse-matrix.h:361-363).
+__device__ __forceinline__ bool gs_update(const Stencil &s, double bv, double xu, double xl,
+                                          double xr, double xd, double &out)
+{
+    if (s.diag == 0) return false;
+    double sigma = 0.0;
+    if (s.up) sigma += -1.0 * xu;
+    if (s.left) sigma += -1.0 * xl;
+    if (s.right) sigma += -1.0 * xr;
+    if (s.down) sigma += -1.0 * xd;
+    out = (bv - sigma) / (double)s.diag;
+    return true;
+}
+
+// A x for one pixel in applyToVector's order (sparse-matrix.h:382-393): up, left, diagonal,
+// right, down; empty rows give 0.
+__device__ __forceinline__ double apply_row(const Stencil &s, double xi, double xu, double xl,
+                                            double xr, double xd)
+{
+    double sum = 0.0;
+    if (s.up) sum += -1.0 * xu;
+    if (s.left) sum += -1.0 * xl;
+    if (s.diag != 0) sum += (double)s.diag * xi;
+    if (s.right) sum += -1.0 * xr;
+    if (s.down) sum += -1.0 * xd;
+    return sum;
+}
+
+}  // namespace ccp

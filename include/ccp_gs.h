@@ -354,6 +354,25 @@ int ccp_debug_lex_tickets(int32_t width, int32_t depth, int32_t groups, uint32_t
  * entries (may be NULL).  Single-block handles only. */
 int ccp_grid_conjugate_gradient(ccp_grid *g, double epsilon, int32_t max_iteration, ccp_gs_report *report);
 
+/* Multigrid-preconditioned conjugate gradient on the resident system (both grid kinds), channel by channel from the
+ * resident x.  The preconditioner is one V-cycle of a geometric hierarchy built on the device at the first call and
+ * cached on the handle (ccp_grid_set_mask_host drops it): level k+1 aggregates 2x2 live pixels of level k, A_{k+1} =
+ * P^T A_k P with P piecewise constant, down to 1x1; `smoothing_sweeps` red-black sweeps before (red, black) and after
+ * (black, red) each coarse correction, which is scaled by 2.  0 means 2; 1..4 are accepted, anything else is
+ * CCP_ERR_BAD_ARG.  Loop: r = b - A x (stop with 0 iterations if sqrt(r'r) < epsilon), z = M r, p = z; per iteration
+ * alpha = r'z / p'Ap, x += alpha p, r -= alpha Ap, stop if sqrt(r'r) < epsilon, z = M r, beta = new r'z / old r'z,
+ * p = z + beta p.  report: `channels` entries (may be NULL), iterations counted as the Jacobi loop counts them,
+ * last_l1_step = sqrt(r'r) of the last update.  Single-block handles only (ghost rows: CCP_ERR_STATE). */
+int ccp_grid_mg_conjugate_gradient(ccp_grid *g, double epsilon, int32_t max_iteration, int32_t smoothing_sweeps,
+                                   ccp_gs_report *report);
+/* Diagnostic: x := M^-1 b, one V-cycle per channel (smoothing_sweeps as above). */
+int ccp_grid_mg_apply(ccp_grid *g, int32_t smoothing_sweeps);
+/* Diagnostic: the hierarchy's level `level` (0 = the handle's operator): its size and, in raster order, the diagonal
+ * and the (positive) weights to the east and south cells.  Any output may be NULL (n_levels, width, height to ask for
+ * sizes); diag / w_east / w_south hold width * height doubles. */
+int ccp_grid_mg_level(ccp_grid *g, int32_t level, int32_t *n_levels, int32_t *width, int32_t *height, double *diag,
+                      double *w_east, double *w_south);
+
 /* ----------------------------------------------------------------------------------------
  * Row blocks across the GPUs of one node (BASELINE configs[3]).  One process (or host
  * thread) per GPU; each creates a communicator rank and one grid handle owning a contiguous block of
