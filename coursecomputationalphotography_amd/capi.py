@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
     "ccp_grid_attach_comm", "ccp_grid_set_overlap", "ccp_grid_exchange_halos", "ccp_grid_sweep_rowblocked",
     "ccp_grid_gauss_seidel_rowblocked", "ccp_grid_conjugate_gradient_rowblocked", "ccp_grid_residual_norm2_global", "ccp_grid_comm_stats",
+    "ccp_grid_mg_conjugate_gradient_rowblocked", "ccp_grid_mg_apply_rowblocked", "ccp_grid_mg_rowblock_info",
 )
 
 
@@ -208,6 +209,9 @@ def load() -> C.CDLL:
     L.ccp_grid_sweep_rowblocked.argtypes = [vp, i32]
     L.ccp_grid_gauss_seidel_rowblocked.argtypes = [vp, dbl, i32, i32, C.POINTER(Report)]
     L.ccp_grid_conjugate_gradient_rowblocked.argtypes = [vp, dbl, i32, C.POINTER(Report)]
+    L.ccp_grid_mg_conjugate_gradient_rowblocked.argtypes = [vp, dbl, i32, i32, C.POINTER(Report)]
+    L.ccp_grid_mg_apply_rowblocked.argtypes = [vp, i32]
+    L.ccp_grid_mg_rowblock_info.argtypes = [vp] + [C.POINTER(i32)] * 4
     L.ccp_grid_residual_norm2_global.argtypes = [vp, vp]
     L.ccp_grid_comm_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     _lib = L
@@ -691,6 +695,23 @@ class Grid:
         reps = (Report * self.C)()
         check(self.L.ccp_grid_conjugate_gradient_rowblocked(self.h, epsilon, max_iteration, reps), "ccp_grid_conjugate_gradient_rowblocked")
         return list(reps)
+
+    def mg_conjugate_gradient_rowblocked(self, epsilon, max_iteration, smoothing_sweeps=2):
+        """Multigrid-preconditioned CG on the partitioned system (collective; one Report per channel)."""
+        reps = (Report * self.C)()
+        check(self.L.ccp_grid_mg_conjugate_gradient_rowblocked(self.h, epsilon, max_iteration, smoothing_sweeps, reps),
+              "ccp_grid_mg_conjugate_gradient_rowblocked")
+        return list(reps)
+
+    def mg_apply_rowblocked(self, smoothing_sweeps=2):
+        """x := M^-1 b on the owned rows (one V-cycle per channel across the blocks; collective, diagnostic)."""
+        check(self.L.ccp_grid_mg_apply_rowblocked(self.h, smoothing_sweeps), "ccp_grid_mg_apply_rowblocked")
+
+    def mg_rowblock_info(self):
+        """(levels, distributed levels, (width, height) of the first level every rank holds whole) — collective."""
+        n, d, w, h = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(self.L.ccp_grid_mg_rowblock_info(self.h, C.byref(n), C.byref(d), C.byref(w), C.byref(h)), "ccp_grid_mg_rowblock_info")
+        return n.value, d.value, (w.value, h.value)
 
     def residual_norm2_global(self):
         out = np.empty(2 * self.C, dtype=np.float64)

@@ -49,6 +49,7 @@ struct ccp_grid {
     // RCCL (ccp_grid_attach_comm): neighbour ranks, the rows their ghost zones take, the stream the
     // messages are issued on and the event the sweeps wait for
     ccp_comm *comm = nullptr;
+    std::vector<int> part;               // every rank's first image row, then the image height (all-gathered at attach)
     int up_rank = -1, down_rank = -1;
     int send_up = 0, send_down = 0;
     hipStream_t stream_comm = nullptr;
@@ -1081,8 +1082,13 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     v->mask = g->maskp.p;
     v->stream = g->stream;
     v->cache = &g->mg;
+    v->comm = g->comm;
+    v->part = g->part.empty() ? nullptr : g->part.data();
+    v->ghost = g->desc.ghost;
     return CCP_OK;
 }
+
+void ccp::grid_mg_halo_stale(ccp_grid *g) { g->half_sweeps_since_refresh = g->desc.ghost; }
 
 // Library-internal twin of ccp_grid_set_mask_host for a mask that is already on the device in the grid's layout
 // (the region recognition builds it there: ccp_csr.hip).  Asynchronous on the handle's stream.
@@ -2235,8 +2241,11 @@ int sweep_rowblocked(ccp_grid *g, int iterations)
 int ccp_grid_attach_comm(ccp_grid *g, ccp_comm *c)
 try {
     CCP_TRY(bind(g));
+    mg_release(g->mg);                               // the multigrid hierarchy belongs to the partition
+    g->mg = nullptr;
     if (!c) {                                        // detach
         g->comm = nullptr;
+        g->part.clear();
         g->up_rank = g->down_rank = -1;
         return CCP_OK;
     }
@@ -2272,6 +2281,8 @@ try {
         CCP_HIP(hipEventCreateWithFlags(&g->ev_comm, hipEventDisableTiming));
         CCP_HIP(hipEventCreateWithFlags(&g->ev_ready, hipEventDisableTiming));
     }
+    g->part.assign((size_t)c->world + 1, g->desc.height);
+    for (int r = 0; r < c->world; ++r) g->part[(size_t)r] = all[4 * r];
     g->comm = c;
     return CCP_OK;
 } CCP_ABI_CATCH

@@ -1,6 +1,7 @@
 // ccp_grid_mg.hip — multigrid-preconditioned conjugate gradient on the grid handles (include/ccp_gs.h:
 // ccp_grid_mg_*).  Kernels and the algorithm: ccp_grid_mg.hpp.
 #include "ccp_grid_mg.hpp"
+#include "ccp_comm.hpp"
 
 #include <algorithm>
 #include <memory>
@@ -12,9 +13,16 @@ namespace ccp {
 
 // The hierarchy of one handle: level 0 is the handle's own operator and vectors; levels 1.. own d, we, ws, b, z in
 // one allocation (level layout, pads zero).  The PCG work vectors (one channel) are allocated at the first solve.
+// Row blocks (ccp_grid_mg_conjugate_gradient_rowblocked): levels 0 .. dist-1 hold the block's own rows plus up to
+// kMgGhost ghost rows per neighbour side (level 0 in a layout of its own: the MG vectors do not depend on the
+// handle's ghost depth); every level from `dist` on is held whole by every rank.
 struct MgHierarchy {
     int levels = 0;
     int tail = 0;                    // first level of k_mg_tail (>= 1), or `levels` for a one-level hierarchy
+    bool rowblocked = false;
+    int dist = 0;                    // row blocks: the number of distributed levels (>= 1)
+    std::vector<std::vector<int>> own;   // row blocks, per distributed level: every rank's first global row, then H_k
+    DevBuf<unsigned char> mask0;     // row blocks: level 0's mask in the level's layout
     std::vector<MgLevel> lv;
     std::vector<long> base;          // per coarse level: offset of its d in `store` (then we, ws, b, z, t, each `size`)
     std::vector<long> size;
@@ -40,11 +48,17 @@ namespace {
 
 dim3 cells_grid(int w, int h) { return dim3((unsigned)((w + kBlock - 1) / kBlock), (unsigned)h); }
 
-template <int KIND>
-void launch_coarsen(hipStream_t s, const MgLevel &f, const MgLevel &c, double *d, double *we, double *ws)
+// coarse local rows [Y0, Y0 + rows) of c from f (kind: f's operator)
+void coarsen(int kind, hipStream_t s, const MgLevel &f, const MgLevel &c, int Y0, int rows, double *d, double *we, double *ws)
 {
-    hipLaunchKernelGGL((k_mg_coarsen<KIND>), cells_grid(c.W, c.H), dim3(kBlock), 0, s, f, c, d, we, ws);
+    if (rows <= 0) return;
+    const dim3 grid = cells_grid(c.W, rows);
+    if (kind == kMgCoarse) hipLaunchKernelGGL((k_mg_coarsen<kMgCoarse>), grid, dim3(kBlock), 0, s, f, c, Y0, d, we, ws);
+    else if (kind == kMgMasked) hipLaunchKernelGGL((k_mg_coarsen<kMgMasked>), grid, dim3(kBlock), 0, s, f, c, Y0, d, we, ws);
+    else hipLaunchKernelGGL((k_mg_coarsen<kMgSolve>), grid, dim3(kBlock), 0, s, f, c, Y0, d, we, ws);
 }
+
+int level_kind(const MgHierarchy &h, int k) { return k ? kMgCoarse : h.kind0; }
 
 int build(const GridMgView &v, MgHierarchy **out)
 {
@@ -57,6 +71,7 @@ int build(const GridMgView &v, MgHierarchy **out)
     l0.pitch = v.geom.pitch;
     l0.mask = v.mask;
     l0.g0 = v.geom;
+    l0.hi = l0.H;
     h->lv.push_back(l0);
     h->base.push_back(0);
     h->size.push_back(0);
@@ -66,6 +81,7 @@ int build(const GridMgView &v, MgHierarchy **out)
         c.W = (h->lv.back().W + 1) / 2;
         c.H = (h->lv.back().H + 1) / 2;
         c.pitch = (((long)c.W + 1) / 2 + 15) / 16 * 16;
+        c.hi = c.H;
         h->lv.push_back(c);
         h->base.push_back(total);
         h->size.push_back((long)c.H * 2 * c.pitch);
@@ -91,10 +107,7 @@ int build(const GridMgView &v, MgHierarchy **out)
         h->lv[k].ws = h->arr(k, 2);
     }
     for (int k = 0; k + 1 < h->levels; ++k) {
-        double *d = h->arr(k + 1, 0), *we = h->arr(k + 1, 1), *ws = h->arr(k + 1, 2);
-        if (k > 0) launch_coarsen<kMgCoarse>(v.stream, h->lv[k], h->lv[k + 1], d, we, ws);
-        else if (v.masked) launch_coarsen<kMgMasked>(v.stream, h->lv[0], h->lv[1], d, we, ws);
-        else launch_coarsen<kMgSolve>(v.stream, h->lv[0], h->lv[1], d, we, ws);
+        coarsen(level_kind(*h, k), v.stream, h->lv[k], h->lv[k + 1], 0, h->lv[k + 1].H, h->arr(k + 1, 0), h->arr(k + 1, 1), h->arr(k + 1, 2));
         CCP_HIP(hipGetLastError());
     }
     if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return CCP_ERR_HIP;
@@ -104,6 +117,10 @@ int build(const GridMgView &v, MgHierarchy **out)
 
 int hierarchy(const GridMgView &v, MgHierarchy **out)
 {
+    if (*v.cache && (*v.cache)->rowblocked) {            // built for the row-block calls: this call needs its own
+        mg_release(*v.cache);
+        *v.cache = nullptr;
+    }
     if (!*v.cache) CCP_TRY(build(v, v.cache));
     *out = *v.cache;
     return CCP_OK;
@@ -117,45 +134,53 @@ int sweeps_arg(int32_t smoothing_sweeps, int *nu)
 }
 
 // one level above the tail: pre-smoothing and restriction (down), prolongation and post-smoothing (up)
-dim3 tiles(const MgLevel &f) { return dim3((unsigned)((f.W + kMgTileW - 1) / kMgTileW), (unsigned)((f.H + kMgTileH - 1) / kMgTileH)); }
+
+dim3 tiles(const MgLevel &f) { return dim3((unsigned)((f.W + kMgTileW - 1) / kMgTileW), (unsigned)((f.hi - f.lo + kMgTileH - 1) / kMgTileH)); }
 
 // t: the level's pre-smoothed z (restriction and the post-smoothing pass read it), z: its correction
 template <int KIND>
-void level_down(hipStream_t s, const MgLevel &f, const double *b, double *t, const MgLevel &c, double *bc, int nu, const CgState *st)
+void pre_t(hipStream_t s, const MgLevel &f, const double *b, double *t, int nu, const CgState *st)
 {
     hipLaunchKernelGGL((k_mg_tile<KIND, false>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, static_cast<const double *>(nullptr), t,
-                       c, static_cast<const double *>(nullptr), nu, st);
-    hipLaunchKernelGGL((k_mg_restrict<KIND>), cells_grid(c.W, c.H), dim3(kBlock), 0, s, f, b, t, c, bc, st);
+                       f, static_cast<const double *>(nullptr), nu, st);
 }
 
-template <int KIND>
-void level_up(hipStream_t s, const MgLevel &f, const double *b, const double *t, double *z, const MgLevel &c, const double *ec, int nu,
-              const CgState *st)
+void pre(int kind, hipStream_t s, const MgLevel &f, const double *b, double *t, int nu, const CgState *st)
 {
-    hipLaunchKernelGGL((k_mg_tile<KIND, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, nu, st);
+    if (kind == kMgCoarse) pre_t<kMgCoarse>(s, f, b, t, nu, st);
+    else if (kind == kMgMasked) pre_t<kMgMasked>(s, f, b, t, nu, st);
+    else pre_t<kMgSolve>(s, f, b, t, nu, st);
 }
 
-// z0 := M^-1 b0 on level 0 (one channel); every launch is a no-op once st->active is 0 (st may be null)
-int vcycle(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st)
+// coarse local rows [Y0, Y0 + rows) of bc from f's residual
+void restrict_rows(int kind, hipStream_t s, const MgLevel &f, const double *b, const double *t, const MgLevel &c, int Y0, int rows,
+                   double *bc, const CgState *st)
+{
+    if (rows <= 0) return;
+    const dim3 grid = cells_grid(c.W, rows);
+    if (kind == kMgCoarse) hipLaunchKernelGGL((k_mg_restrict<kMgCoarse>), grid, dim3(kBlock), 0, s, f, b, t, c, Y0, bc, st);
+    else if (kind == kMgMasked) hipLaunchKernelGGL((k_mg_restrict<kMgMasked>), grid, dim3(kBlock), 0, s, f, b, t, c, Y0, bc, st);
+    else hipLaunchKernelGGL((k_mg_restrict<kMgSolve>), grid, dim3(kBlock), 0, s, f, b, t, c, Y0, bc, st);
+}
+
+void post(int kind, hipStream_t s, const MgLevel &f, const double *b, const double *t, double *z, const MgLevel &c, const double *ec, int nu,
+          const CgState *st)
+{
+    if (kind == kMgCoarse) hipLaunchKernelGGL((k_mg_tile<kMgCoarse, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, nu, st);
+    else if (kind == kMgMasked) hipLaunchKernelGGL((k_mg_tile<kMgMasked, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, nu, st);
+    else hipLaunchKernelGGL((k_mg_tile<kMgSolve, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, nu, st);
+}
+
+// The levels from `from` (held whole) down: tiles above the tail, then k_mg_tail, then back up to `from`.  Every launch
+// is a no-op once st->active is 0 (st may be null).
+int whole_levels(MgHierarchy &h, hipStream_t s, int from, const double *b0, double *z0, int nu, const CgState *st)
 {
     auto B = [&](int k) -> const double * { return k ? h.arr(k, 3) : b0; };
     auto Z = [&](int k) -> double * { return k ? h.arr(k, 4) : z0; };
     auto T = [&](int k) -> double * { return k ? h.arr(k, 5) : h.t0.p; };
-    if (h.levels == 1) {                                  // 1x1 image: z = b/d, what red updates from z = 0 give
-        if (h.kind0 == kMgMasked)
-            hipLaunchKernelGGL((k_mg_tile<kMgMasked, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
-                               static_cast<const double *>(nullptr), nu, st);
-        else
-            hipLaunchKernelGGL((k_mg_tile<kMgSolve, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
-                               static_cast<const double *>(nullptr), nu, st);
-        CCP_HIP(hipGetLastError());
-        return CCP_OK;
-    }
-    for (int k = 0; k < h.tail; ++k) {
-        double *bc = h.arr(k + 1, 3);
-        if (k > 0) level_down<kMgCoarse>(s, h.lv[k], B(k), T(k), h.lv[k + 1], bc, nu, st);
-        else if (h.kind0 == kMgMasked) level_down<kMgMasked>(s, h.lv[0], b0, T(0), h.lv[1], bc, nu, st);
-        else level_down<kMgSolve>(s, h.lv[0], b0, T(0), h.lv[1], bc, nu, st);
+    for (int k = from; k < h.tail; ++k) {
+        pre(level_kind(h, k), s, h.lv[k], B(k), T(k), nu, st);
+        restrict_rows(level_kind(h, k), s, h.lv[k], B(k), T(k), h.lv[k + 1], 0, h.lv[k + 1].H, h.arr(k + 1, 3), st);
     }
     MgTail t{};
     t.levels = h.levels - h.tail;
@@ -172,14 +197,251 @@ int vcycle(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, 
         off += l.W * l.H;
     }
     hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(kBlock), 0, s, t, B(h.tail), Z(h.tail), nu, st);
-    for (int k = h.tail - 1; k >= 0; --k) {
-        const double *ec = h.arr(k + 1, 4);
-        if (k > 0) level_up<kMgCoarse>(s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], ec, nu, st);
-        else if (h.kind0 == kMgMasked) level_up<kMgMasked>(s, h.lv[0], b0, T(0), z0, h.lv[1], ec, nu, st);
-        else level_up<kMgSolve>(s, h.lv[0], b0, T(0), z0, h.lv[1], ec, nu, st);
+    for (int k = h.tail - 1; k >= from; --k) post(level_kind(h, k), s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], h.arr(k + 1, 4), nu, st);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+// 1x1 image: z = b/d, what red updates from z = 0 give
+int vcycle_1x1(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st)
+{
+    if (h.kind0 == kMgMasked)
+        hipLaunchKernelGGL((k_mg_tile<kMgMasked, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
+                           static_cast<const double *>(nullptr), nu, st);
+    else
+        hipLaunchKernelGGL((k_mg_tile<kMgSolve, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
+                           static_cast<const double *>(nullptr), nu, st);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+// z0 := M^-1 b0 on level 0 (one channel); every launch is a no-op once st->active is 0 (st may be null)
+int vcycle(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st)
+{
+    if (h.levels == 1) return vcycle_1x1(h, s, b0, z0, nu, st);
+    return whole_levels(h, s, 0, b0, z0, nu, st);
+}
+
+// ---- row blocks ----------------------------------------------------------------------------------------------------
+constexpr int kMgGhost = 8;          // ghost rows per neighbour side of a distributed level: 2 x the largest nu
+
+struct Net {
+    const RcclApi *api;
+    ccp_comm *comm;
+    int rank, world;
+    hipStream_t s;
+};
+
+// Rows of the distributed level k to the neighbours' ghost rows next to their owned rows, theirs into ours: up to `req`
+// rows per side (fewer when the sending block owns fewer), `elem` bytes per value of type t, one RCCL group.
+int exchange_rows(const MgHierarchy &h, const Net &n, int k, void *base, size_t elem, ncclDataType_t t, int req)
+{
+    if (n.world == 1) return CCP_OK;
+    const MgLevel &l = h.lv[k];
+    const std::vector<int> &o = h.own[k];
+    const size_t row = (size_t)2 * l.pitch;            // values per row
+    char *p = static_cast<char *>(base);
+    auto at = [&](int r) { return p + (size_t)r * row * elem; };
+    const int mine = o[n.rank + 1] - o[n.rank];
+    const int snd = std::min(req, mine);
+    CCP_RCCL(n.api->GroupStart());
+    ncclResult_t r = ncclSuccess;
+    if (n.rank > 0) {
+        const int rcv = std::min(req, o[n.rank] - o[n.rank - 1]);
+        r = n.api->Send(at(l.lo), (size_t)snd * row, t, n.rank - 1, n.comm->comm, n.s);
+        if (r == ncclSuccess) r = n.api->Recv(at(l.lo - rcv), (size_t)rcv * row, t, n.rank - 1, n.comm->comm, n.s);
+    }
+    if (n.rank + 1 < n.world && r == ncclSuccess) {
+        const int rcv = std::min(req, o[n.rank + 2] - o[n.rank + 1]);
+        r = n.api->Send(at(l.hi - snd), (size_t)snd * row, t, n.rank + 1, n.comm->comm, n.s);
+        if (r == ncclSuccess) r = n.api->Recv(at(l.hi), (size_t)rcv * row, t, n.rank + 1, n.comm->comm, n.s);
+    }
+    const ncclResult_t e = n.api->GroupEnd();
+    if (r != ncclSuccess) return rccl_fail(r, "ncclSend/ncclRecv", __FILE__, __LINE__);
+    CCP_RCCL(e);
+    return CCP_OK;
+}
+
+int exchange_rows(const MgHierarchy &h, const Net &n, int k, double *base, int req)
+{
+    return exchange_rows(h, n, k, base, sizeof(double), ncclDouble, req);
+}
+
+// The one-block hierarchy over the partition `part` (world + 1 global rows).  Level k+1 stays distributed while every
+// block boundary of level k is even, every block owns >= kMgGhost rows of level k+1 and level k+1 is above the tail.
+// Every rank takes the same decisions from the same partition.  COLLECTIVE (ghost rows of the coefficients, the sums
+// that form the first whole level).
+int build_rowblocked(const GridMgView &v, const Net &n, MgHierarchy **out)
+{
+    MgHierarchy *h = new MgHierarchy();
+    std::unique_ptr<MgHierarchy> own(h);
+    h->rowblocked = true;
+    h->kind0 = v.masked ? kMgMasked : kMgSolve;
+    std::vector<int> Ws{v.geom.W}, Hs{v.geom.H};
+    while (Ws.back() > 1 || Hs.back() > 1) {
+        Ws.push_back((Ws.back() + 1) / 2);
+        Hs.push_back((Hs.back() + 1) / 2);
+    }
+    h->levels = (int)Ws.size();
+    h->tail = h->levels;
+    for (int k = 1; k < h->levels; ++k)
+        if (Ws[k] <= kMgTailSide && Hs[k] <= kMgTailSide) {
+            h->tail = k;
+            break;
+        }
+    if (h->levels - h->tail > kMgTailLevels) return CCP_ERR_STATE;
+    h->own.emplace_back(v.part, v.part + n.world + 1);
+    h->dist = 1;
+    for (int k = 0; k + 1 < h->tail; ++k) {
+        const std::vector<int> &o = h->own[k];
+        std::vector<int> next(o.size());
+        bool ok = true;
+        for (int r = 1; r < n.world; ++r) {
+            ok = ok && o[r] % 2 == 0;
+            next[r] = o[r] / 2;
+        }
+        next[n.world] = Hs[k + 1];
+        for (int r = 0; r < n.world; ++r) ok = ok && next[r + 1] - next[r] >= kMgGhost;
+        if (!ok) break;
+        h->own.push_back(next);
+        h->dist = k + 2;
+    }
+    long total = 0;
+    for (int k = 0; k < h->levels; ++k) {
+        MgLevel l{};
+        l.W = Ws[k];
+        l.pitch = k ? (((long)l.W + 1) / 2 + 15) / 16 * 16 : v.geom.pitch;
+        if (k < h->dist) {
+            const int ob = h->own[k][n.rank], oe = h->own[k][n.rank + 1];
+            // (the top ghost zone keeps local row 0 on an even global row: local parity is global parity)
+            const int gt = n.rank > 0 ? std::min(ob, kMgGhost + (ob & 1)) : 0;
+            const int gb = n.rank + 1 < n.world ? std::min(kMgGhost, Hs[k] - oe) : 0;
+            l.y0 = ob - gt;
+            l.lo = gt;
+            l.hi = gt + (oe - ob);
+            l.H = l.hi + gb;
+        } else {
+            l.H = l.hi = Hs[k];
+        }
+        h->lv.push_back(l);
+        h->base.push_back(k ? total : 0);
+        h->size.push_back(k ? (long)l.H * 2 * l.pitch : 0);
+        total += 6 * h->size.back();
+    }
+    MgLevel &l0 = h->lv[0];
+    l0.g0 = v.geom;
+    l0.g0.y0 = l0.y0;
+    l0.g0.local_rows = l0.H;
+    l0.g0.own_lo = l0.lo;
+    l0.g0.own_hi = l0.hi;
+    l0.g0.ch_stride = (long)l0.H * 2 * l0.pitch;
+    const long n0 = l0.g0.ch_stride, row = 2 * l0.pitch;
+    CCP_TRY(h->t0.alloc((size_t)n0));
+    CCP_HIP(hipMemsetAsync(h->t0.p, 0, sizeof(double) * n0, n.s));
+    if (total > 0) {
+        CCP_TRY(h->store.alloc((size_t)total));
+        CCP_HIP(hipMemsetAsync(h->store.p, 0, sizeof(double) * total, n.s));
+    }
+    if (v.masked) {
+        CCP_TRY(h->mask0.alloc((size_t)n0));
+        CCP_HIP(hipMemsetAsync(h->mask0.p, 0, (size_t)n0, n.s));
+        CCP_HIP(hipMemcpyAsync(h->mask0.p + l0.lo * row, v.mask + (long)v.geom.own_lo * row, (size_t)((l0.hi - l0.lo) * row),
+                               hipMemcpyDeviceToDevice, n.s));
+        CCP_TRY(exchange_rows(*h, n, 0, h->mask0.p, 1, ncclUint8, kMgGhost));
+        l0.mask = h->mask0.p;
+    }
+    for (int k = 1; k < h->levels; ++k) {
+        h->lv[k].d = h->arr(k, 0);
+        h->lv[k].we = h->arr(k, 1);
+        h->lv[k].ws = h->arr(k, 2);
+    }
+    for (int k = 0; k + 1 < h->levels; ++k) {
+        const int c = k + 1;
+        double *d = h->arr(c, 0), *we = h->arr(c, 1), *ws = h->arr(c, 2);
+        const MgLevel &f = h->lv[k], &cl = h->lv[c];
+        if (c < h->dist) {                               // the owned coarse rows, then their ghost rows
+            coarsen(level_kind(*h, k), n.s, f, cl, cl.lo, cl.hi - cl.lo, d, we, ws);
+            CCP_HIP(hipGetLastError());
+            for (double *a : {d, we, ws}) CCP_TRY(exchange_rows(*h, n, c, a, kMgGhost));
+        } else if (c == h->dist) {                       // every rank's share of the first whole level, summed (exact)
+            const int fb = f.y0 + f.lo, fe = f.y0 + f.hi;
+            coarsen(level_kind(*h, k), n.s, f, cl, fb / 2, (fe + 1) / 2 - fb / 2, d, we, ws);
+            CCP_HIP(hipGetLastError());
+            CCP_RCCL(n.api->AllReduce(d, d, (size_t)(3 * h->size[c]), ncclDouble, ncclSum, n.comm->comm, n.s));
+        } else {
+            coarsen(kMgCoarse, n.s, f, cl, 0, cl.H, d, we, ws);
+            CCP_HIP(hipGetLastError());
+        }
+    }
+    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return CCP_ERR_HIP;
+    *out = own.release();
+    return CCP_OK;
+}
+
+int hierarchy_rowblocked(const GridMgView &v, const Net &n, MgHierarchy **out)
+{
+    if (*v.cache && !(*v.cache)->rowblocked) {
+        mg_release(*v.cache);
+        *v.cache = nullptr;
+    }
+    if (!*v.cache) CCP_TRY(build_rowblocked(v, n, v.cache));
+    *out = *v.cache;
+    return CCP_OK;
+}
+
+// z0 := M^-1 b0 on level 0's owned rows (one channel; b0 and z0 in level 0's layout, b0's owned rows current).  The
+// distributed levels exchange their right-hand side (2 nu rows) before pre-smoothing, the pre-smoothed t (2 nu rows)
+// after it and the coarse correction (nu + 1 rows) before post-smoothing; the first whole level is every rank's
+// restriction of its own rows, summed.  COLLECTIVE: every rank issues the same messages whatever st says.
+int vcycle_rowblocked(MgHierarchy &h, const Net &n, const double *b0, double *z0, int nu, const CgState *st)
+{
+    if (h.levels == 1) return vcycle_1x1(h, n.s, b0, z0, nu, st);
+    auto B = [&](int k) -> double * { return k ? h.arr(k, 3) : const_cast<double *>(b0); };
+    auto Z = [&](int k) -> double * { return k ? h.arr(k, 4) : z0; };
+    auto T = [&](int k) -> double * { return k ? h.arr(k, 5) : h.t0.p; };
+    for (int k = 0; k < h.dist; ++k) {
+        const MgLevel &f = h.lv[k], &c = h.lv[k + 1];
+        CCP_TRY(exchange_rows(h, n, k, B(k), 2 * nu));
+        pre(level_kind(h, k), n.s, f, B(k), T(k), nu, st);
+        CCP_TRY(exchange_rows(h, n, k, T(k), 2 * nu));
+        if (k + 1 < h.dist) {
+            restrict_rows(level_kind(h, k), n.s, f, B(k), T(k), c, c.lo, c.hi - c.lo, B(k + 1), st);
+        } else {
+            const int fb = f.y0 + f.lo, fe = f.y0 + f.hi;
+            CCP_HIP(hipMemsetAsync(B(k + 1), 0, sizeof(double) * h.size[k + 1], n.s));
+            restrict_rows(level_kind(h, k), n.s, f, B(k), T(k), c, fb / 2, (fe + 1) / 2 - fb / 2, B(k + 1), st);
+            CCP_HIP(hipGetLastError());
+            CCP_RCCL(n.api->AllReduce(B(k + 1), B(k + 1), (size_t)h.size[k + 1], ncclDouble, ncclSum, n.comm->comm, n.s));
+        }
+        CCP_HIP(hipGetLastError());
+    }
+    CCP_TRY(whole_levels(h, n.s, h.dist, b0, z0, nu, st));
+    for (int k = h.dist - 1; k >= 0; --k) {
+        if (k + 1 < h.dist) CCP_TRY(exchange_rows(h, n, k + 1, Z(k + 1), nu + 1));
+        post(level_kind(h, k), n.s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], Z(k + 1), nu, st);
     }
     CCP_HIP(hipGetLastError());
     return CCP_OK;
+}
+
+// The checks every rank makes alike, before any collective call, then the hierarchy (collective on its first use)
+int prepare_rowblocked(ccp_grid *g, int32_t smoothing_sweeps, bool need_nu, GridMgView *v, Net *n, int *nu, MgHierarchy **h)
+{
+    CCP_TRY(grid_mg_view(g, v));
+    if (!v->comm) return CCP_ERR_STATE;
+    n->api = rccl_api();
+    if (!n->api) return CCP_ERR_RCCL;
+    n->comm = v->comm;
+    n->rank = v->comm->rank;
+    n->world = v->comm->world;
+    n->s = v->stream;
+    if (n->world > 1 && v->ghost < 1) return CCP_ERR_STATE;
+    if (need_nu) {
+        CCP_TRY(sweeps_arg(smoothing_sweeps, nu));
+        for (int r = 0; r < n->world; ++r)
+            if (v->part[r + 1] - v->part[r] < 2 * *nu) return CCP_ERR_UNSUPPORTED;
+    }
+    return hierarchy_rowblocked(*v, *n, h);
 }
 
 int check_handle(ccp_grid *g, GridMgView *v)
@@ -335,6 +597,162 @@ try {
             report[ch].seconds = ms * 1e-3;
         }
     }
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+// ---- row blocks ----------------------------------------------------------------------------------------------------
+
+int ccp_grid_mg_apply_rowblocked(ccp_grid *g, int32_t smoothing_sweeps)
+try {
+    GridMgView v{};
+    Net net{};
+    int nu = 2;
+    MgHierarchy *h = nullptr;
+    CCP_TRY(prepare_rowblocked(g, smoothing_sweeps, true, &v, &net, &nu, &h));
+    const MgLevel &l0 = h->lv[0];
+    const long row = 2 * l0.pitch, n0 = (long)l0.H * row, n_own = (long)(l0.hi - l0.lo) * row;
+    if (!h->r.p) {                                        // (PCG work vectors in level 0's layout; zero beyond the owned rows)
+        for (DevBuf<double> *b : {&h->z, &h->r, &h->p, &h->ap}) {
+            CCP_TRY(b->alloc((size_t)n0));
+            CCP_HIP(hipMemsetAsync(b->p, 0, sizeof(double) * n0, net.s));
+        }
+    }
+    const long hoff = (long)v.geom.own_lo * row;
+    for (int ch = 0; ch < v.channels; ++ch) {
+        CCP_HIP(hipMemcpyAsync(h->r.p + l0.lo * row, v.b + ch * v.geom.ch_stride + hoff, sizeof(double) * n_own, hipMemcpyDeviceToDevice, net.s));
+        CCP_TRY(vcycle_rowblocked(*h, net, h->r.p, h->z.p, nu, nullptr));
+        CCP_HIP(hipMemcpyAsync(v.x + ch * v.geom.ch_stride + hoff, h->z.p + l0.lo * row, sizeof(double) * n_own, hipMemcpyDeviceToDevice, net.s));
+    }
+    CCP_HIP(hipStreamSynchronize(net.s));
+    grid_mg_halo_stale(g);
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_rowblock_info(ccp_grid *g, int32_t *n_levels, int32_t *distributed_levels, int32_t *replicated_width,
+                              int32_t *replicated_height)
+try {
+    GridMgView v{};
+    Net net{};
+    int nu = 2;
+    MgHierarchy *h = nullptr;
+    CCP_TRY(prepare_rowblocked(g, 0, false, &v, &net, &nu, &h));
+    CCP_HIP(hipStreamSynchronize(net.s));
+    if (n_levels) *n_levels = h->levels;
+    if (distributed_levels) *distributed_levels = h->dist;
+    const bool any = h->dist < h->levels;
+    if (replicated_width) *replicated_width = any ? h->lv[h->dist].W : 0;
+    if (replicated_height) *replicated_height = any ? h->lv[h->dist].H : 0;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+// The one-block PCG loop over the owned rows: A p fetches one ghost row of p first; every partial sum is reduced to one
+// double and all-reduced, so every rank takes the same decisions and issues the same collectives.  x is updated in
+// place on the handle's owned rows (the owned range of a plane is laid out alike in the handle and in level 0).
+int ccp_grid_mg_conjugate_gradient_rowblocked(ccp_grid *g, double epsilon, int32_t max_iteration, int32_t smoothing_sweeps,
+                                              ccp_gs_report *report)
+try {
+    if (max_iteration < 0) return CCP_ERR_BAD_ARG;
+    GridMgView v{};
+    Net net{};
+    int nu = 2;
+    MgHierarchy *h = nullptr;
+    CCP_TRY(prepare_rowblocked(g, smoothing_sweeps, true, &v, &net, &nu, &h));
+    const MgLevel &l0 = h->lv[0];
+    const long row = 2 * l0.pitch, n0 = (long)l0.H * row, off = (long)l0.lo * row;
+    const long n = (long)(l0.hi - l0.lo) * row;                       // the owned range (pads stay 0 in every vector)
+    const long hoff = (long)v.geom.own_lo * row;
+    const int own_rows = l0.hi - l0.lo;
+    const unsigned agx = cells_grid((l0.W + 1) / 2, 1).x;
+    const dim3 agrid(agx, (unsigned)std::max(1, std::min(own_rows, (int)(1024 / agx))), 2);
+    const int apply_blocks = (int)(agrid.x * agrid.y * agrid.z);
+    const int blocks = (int)std::max<long>(1, std::min<long>(2048, (n + kBlock - 1) / kBlock));
+    hipStream_t s = net.s;
+    if (!h->r.p) {
+        for (DevBuf<double> *b : {&h->z, &h->r, &h->p, &h->ap}) {
+            CCP_TRY(b->alloc((size_t)n0));
+            CCP_HIP(hipMemsetAsync(b->p, 0, sizeof(double) * n0, s));
+        }
+    }
+    if (!h->partial.p) CCP_TRY(h->partial.alloc((size_t)std::max(apply_blocks, blocks)));
+    if (!h->state.p) CCP_TRY(h->state.alloc(1));
+    CgState *st = h->state.p;
+    double *part = h->partial.p;
+    double *total = reinterpret_cast<double *>(net.comm->scratch.p);
+    auto sums = [&](int count) -> int {                                   // total[0] := the partials summed over every rank
+        hipLaunchKernelGGL(k_reduce_to_one, dim3(1), dim3(kBlock), 0, s, part, (long)count, total);
+        CCP_HIP(hipGetLastError());
+        CCP_RCCL(net.api->AllReduce(total, total, 1, ncclDouble, ncclSum, net.comm->comm, s));
+        return CCP_OK;
+    };
+    auto apply = [&](double *in, double *out, bool dot) -> int {          // one ghost row of `in`, then out := A in
+        CCP_TRY(exchange_rows(*h, net, 0, in, 1));
+        if (v.masked) {
+            if (dot) hipLaunchKernelGGL((k_mg_apply<kMgMasked, true>), agrid, dim3(kBlock), 0, s, l0, in, out, part, st);
+            else hipLaunchKernelGGL((k_mg_apply<kMgMasked, false>), agrid, dim3(kBlock), 0, s, l0, in, out, part, static_cast<const CgState *>(nullptr));
+        } else {
+            if (dot) hipLaunchKernelGGL((k_mg_apply<kMgSolve, true>), agrid, dim3(kBlock), 0, s, l0, in, out, part, st);
+            else hipLaunchKernelGGL((k_mg_apply<kMgSolve, false>), agrid, dim3(kBlock), 0, s, l0, in, out, part, static_cast<const CgState *>(nullptr));
+        }
+        CCP_HIP(hipGetLastError());
+        return CCP_OK;
+    };
+    double *r = h->r.p + off, *z = h->z.p + off, *p = h->p.p + off, *ap = h->ap.p + off;
+    for (int ch = 0; ch < v.channels; ++ch) {
+        const double *b = v.b + ch * v.geom.ch_stride + hoff;
+        double *x = v.x + ch * v.geom.ch_stride + hoff;
+        CgState host{};
+        host.active = 1;
+        CCP_HIP(hipMemcpyAsync(st, &host, sizeof(host), hipMemcpyHostToDevice, s));
+        CCP_HIP(hipEventRecord(h->ev0, s));
+        CCP_HIP(hipMemcpyAsync(p, x, sizeof(double) * n, hipMemcpyDeviceToDevice, s));     // x with ghost rows, in p
+        CCP_TRY(apply(h->p.p, h->r.p, false));                                                // r = A x
+        hipLaunchKernelGGL(k_cg_init, dim3(blocks), dim3(kBlock), 0, s, b, r, p, n, part);    // r = b - r; r'r
+        CCP_TRY(sums(blocks));
+        hipLaunchKernelGGL(k_mg_check, dim3(1), dim3(kBlock), 0, s, total, 1, epsilon, st);
+        CCP_TRY(vcycle_rowblocked(*h, net, h->r.p, h->z.p, nu, st));                           // z = M r
+        hipLaunchKernelGGL(k_cg_dot, dim3(blocks), dim3(kBlock), 0, s, r, z, n, part, st);
+        CCP_TRY(sums(blocks));
+        hipLaunchKernelGGL(k_cg_set_rlen, dim3(1), dim3(kBlock), 0, s, total, 1, st);         // rlen = r'z
+        CCP_HIP(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, s));       // p = z
+        CCP_HIP(hipGetLastError());
+        CCP_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
+        CCP_HIP(hipStreamSynchronize(s));
+        int issued = 0;
+        bool active = host.active != 0 && max_iteration > 0;
+        while (active && issued < max_iteration) {
+            const int batch = std::min(16, max_iteration - issued);
+            for (int k = 0; k < batch; ++k) {
+                CCP_TRY(apply(h->p.p, h->ap.p, true));                                         // Ap, p'Ap
+                CCP_TRY(sums(apply_blocks));
+                hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(kBlock), 0, s, total, 1, st);    // alpha = r'z / p'Ap
+                hipLaunchKernelGGL(k_cg_update, dim3(blocks), dim3(kBlock), 0, s, x, p, r, ap, n, part, st);
+                CCP_TRY(sums(blocks));
+                hipLaunchKernelGGL(k_mg_check, dim3(1), dim3(kBlock), 0, s, total, 1, epsilon, st);
+                CCP_TRY(vcycle_rowblocked(*h, net, h->r.p, h->z.p, nu, st));
+                hipLaunchKernelGGL(k_cg_dot, dim3(blocks), dim3(kBlock), 0, s, r, z, n, part, st);
+                CCP_TRY(sums(blocks));
+                hipLaunchKernelGGL(k_mg_beta, dim3(1), dim3(kBlock), 0, s, total, 1, st);
+                hipLaunchKernelGGL(k_cg_direction, dim3(blocks), dim3(kBlock), 0, s, p, z, n, st);   // p = z + beta p
+            }
+            CCP_HIP(hipGetLastError());
+            issued += batch;
+            CCP_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
+            CCP_HIP(hipStreamSynchronize(s));
+            active = host.active != 0;
+        }
+        CCP_HIP(hipEventRecord(h->ev1, s));
+        CCP_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
+        CCP_HIP(hipStreamSynchronize(s));
+        if (report) {
+            float ms = 0.f;
+            CCP_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+            report[ch].iterations = host.iterations;
+            report[ch].converged = host.converged;
+            report[ch].last_l1_step = host.r1norm;
+            report[ch].seconds = ms * 1e-3;
+        }
+    }
+    grid_mg_halo_stale(g);                                                // the ghost rows of x are stale now
     return CCP_OK;
 } CCP_ABI_CATCH
 

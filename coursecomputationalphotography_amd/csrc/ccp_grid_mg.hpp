@@ -21,6 +21,11 @@
 // all of them resident in LDS (at most kMgTailCells cells x 5 doubles = 54.6 KB).  Every other level takes three
 // launches: the nu pre-smoothing sweeps in one pass (k_mg_tile), residual + restriction (k_mg_restrict), prolongation
 // + the nu post-smoothing sweeps in one pass (k_mg_tile).
+//
+// Row blocks (ccp_grid_mg_conjugate_gradient_rowblocked, ccp_grid_mg.hip) run the same kernels on levels that hold the
+// block's own rows [lo, hi) plus ghost rows (MgLevel::y0, lo, hi): a tile pass covers the owned rows and reads its halo
+// from the ghost rows; the restriction and the coarsening skip children outside the owned rows, so a coarse level every
+// rank holds whole is the all-reduced sum of the ranks' shares.
 #pragma once
 
 #include "ccp_cg.hpp"
@@ -41,12 +46,16 @@ __host__ __device__ constexpr int mg_tile_lds(int nu)
     return 2 * (kMgTileW + 4 * nu) * (kMgTileH + 4 * nu) * (int)sizeof(double);   // b and z of the tile and its halo
 }
 
+// A level's buffers hold local rows [0, H) of its global level: global row y0 + y at local row y.  The rows the
+// level owns are [lo, hi); the others are ghost rows filled from the neighbouring row blocks.  One block, or a level
+// every rank holds whole: y0 = 0, lo = 0, hi = H.  y0 is even, so (x + y) & 1 is the global colour of local cell (x, y).
 struct MgLevel {
-    int W, H;
+    int W, H;                         // W: the level's width; H: local rows in the buffers
     long pitch;
     const double *d, *we, *ws;        // coarse levels (level 0 derives its operator from g0 / mask)
     const unsigned char *mask;        // level 0 of a Dirichlet-mask grid
-    Geom g0;                          // level 0: the handle's geometry (one block: local row == image row)
+    Geom g0;                          // level 0: the global image (W, H) and the buffers' local_rows
+    int y0, lo, hi;                   // global row of local row 0; owned local rows
 };
 
 __host__ __device__ __forceinline__ long mg_at(long pitch, int x, int y)
@@ -62,20 +71,20 @@ __device__ __forceinline__ double mg_ld(const double *__restrict__ v, const MgLe
 template <int KIND>
 __device__ __forceinline__ bool mg_live(const MgLevel &lv, int x, int y)
 {
-    if (KIND == kMgSolve) return classify(lv.g0, x, y, y).diag != 0;
+    if (KIND == kMgSolve) return classify(lv.g0, x, lv.y0 + y, y).diag != 0;
     if (KIND == kMgMasked) return lv.mask[mg_at(lv.pitch, x, y)] != 0;
     return lv.d[mg_at(lv.pitch, x, y)] != 0.0;
 }
 
-// the operator's coefficients of (x,y): 0 outside the level and on dead pixels
+// the operator's coefficients of (x,y): 0 outside the level's owned rows and on dead pixels
 template <int KIND>
 __device__ __forceinline__ void mg_coef(const MgLevel &lv, int x, int y, double &d, double &we, double &ws)
 {
     d = we = ws = 0.0;
-    if (x >= lv.W || y >= lv.H) return;
+    if (x >= lv.W || y < lv.lo || y >= lv.hi) return;
     const long at = mg_at(lv.pitch, x, y);
     if (KIND == kMgSolve) {
-        const Stencil s = classify(lv.g0, x, y, y);
+        const Stencil s = classify(lv.g0, x, lv.y0 + y, y);
         d = (double)s.diag;
         we = s.right ? 1.0 : 0.0;
         ws = s.down ? 1.0 : 0.0;
@@ -98,7 +107,7 @@ __device__ __forceinline__ double mg_update(const MgLevel &lv, double bv, double
     const long at = mg_at(lv.pitch, x, y);
     if (KIND == kMgSolve) {
         double out = 0.0;
-        return gs_update(classify(lv.g0, x, y, y), bv, xu, xl, xr, xd, out) ? out : 0.0;
+        return gs_update(classify(lv.g0, x, lv.y0 + y, y), bv, xu, xl, xr, xd, out) ? out : 0.0;
     } else if (KIND == kMgMasked) {
         // k_half_sweep's masked arithmetic: b - sigma with sigma = (((-xu) + (-xl)) + (-xr)) + (-xd); a_ii = 4
         return lv.mask[at] ? (bv + (((xu + xl) + xr) + xd)) * 0.25 : 0.0;
@@ -121,7 +130,7 @@ __device__ __forceinline__ double mg_row0(const MgLevel &lv, const double *__res
     const long at = mg_at(lv.pitch, x, y);
     const double xi = z[at];
     const double xu = mg_ld(z, lv, x, y - 1), xl = mg_ld(z, lv, x - 1, y), xr = mg_ld(z, lv, x + 1, y), xd = mg_ld(z, lv, x, y + 1);
-    if (KIND == kMgSolve) return apply_row(classify(lv.g0, x, y, y), xi, xu, xl, xr, xd);
+    if (KIND == kMgSolve) return apply_row(classify(lv.g0, x, lv.y0 + y, y), xi, xu, xl, xr, xd);
     double ax = 0.0;
     if (lv.mask[at]) {
         ax += -1.0 * xu;
@@ -133,11 +142,11 @@ __device__ __forceinline__ double mg_row0(const MgLevel &lv, const double *__res
     return ax;
 }
 
-// b - A z at (x,y); 0 outside the level and on dead pixels
+// b - A z at (x,y); 0 outside the level's owned rows and on dead pixels
 template <int KIND>
 __device__ __forceinline__ double mg_residual(const MgLevel &lv, const double *__restrict__ b, const double *__restrict__ z, int x, int y)
 {
-    if (x >= lv.W || y >= lv.H) return 0.0;
+    if (x >= lv.W || y < lv.lo || y >= lv.hi) return 0.0;
     const long at = mg_at(lv.pitch, x, y);
     if constexpr (KIND != kMgCoarse) {
         return mg_live<KIND>(lv, x, y) ? b[at] - mg_row0<KIND>(lv, z, x, y) : 0.0;
@@ -155,8 +164,8 @@ __device__ __forceinline__ double mg_residual(const MgLevel &lv, const double *_
     }
 }
 
-// out := A in on level 0 (the PCG's products).  grid = (ceil(ceil(W/2)/kBlock), rows, 2): a thread owns half-column j of
-// colour blockIdx.z in rows blockIdx.y, blockIdx.y + gridDim.y, ...; the caller sizes gridDim.y so that the whole grid has
+// out := A in on level 0's owned rows (the PCG's products).  grid = (ceil(ceil(W/2)/kBlock), rows, 2): a thread owns
+// half-column j of colour blockIdx.z in rows lo + blockIdx.y, lo + blockIdx.y + gridDim.y, ...; the caller sizes gridDim.y so that the whole grid has
 // ~2,048 blocks.  DOT: one partial sum of in'(A in) per block at [(z * gridDim.y + y) * gridDim.x + x].  A no-op once the
 // PCG loop has stopped (st may be null: always run).
 template <int KIND, bool DOT>
@@ -168,7 +177,7 @@ k_mg_apply(MgLevel lv, const double *__restrict__ in, double *__restrict__ out, 
     if (st && !st->active) return;                                   // (uniform)
     const int j = blockIdx.x * kBlock + threadIdx.x, c = blockIdx.z;
     double dot = 0.0;
-    for (int y = blockIdx.y; y < lv.H; y += gridDim.y) {
+    for (int y = lv.lo + blockIdx.y; y < lv.hi; y += gridDim.y) {
         const int x = 2 * j + ((y + c) & 1);
         if (x < lv.W) {
             const long at = mg_at(lv.pitch, x, y);
@@ -185,14 +194,16 @@ k_mg_apply(MgLevel lv, const double *__restrict__ in, double *__restrict__ out, 
 
 // ---- hierarchy ------------------------------------------------------------------------------------------------------
 // coarse cell (X,Y) of level k+1 from level k: d = sum of the live children's diagonals - 2 x their internal edges,
-// we / ws = the weights of the edges that leave the aggregate eastward / southward.  grid = (ceil(Wc/kBlock), Hc).
+// we / ws = the weights of the edges that leave the aggregate eastward / southward.  Children outside the fine level's
+// owned rows count as dead: a row block adds its share of an aggregate split across two blocks, and the shares are
+// summed over the ranks.  grid = (ceil(Wc/kBlock), coarse rows from local row Y0).
 template <int KIND>
 __global__ void __launch_bounds__(kBlock)
-k_mg_coarsen(MgLevel lv, MgLevel cv, double *__restrict__ d, double *__restrict__ we, double *__restrict__ ws)
+k_mg_coarsen(MgLevel lv, MgLevel cv, int Y0, double *__restrict__ d, double *__restrict__ we, double *__restrict__ ws)
 {
-    const int X = blockIdx.x * kBlock + threadIdx.x, Y = blockIdx.y;
+    const int X = blockIdx.x * kBlock + threadIdx.x, Y = Y0 + (int)blockIdx.y;
     if (X >= cv.W) return;
-    const int x = 2 * X, y = 2 * Y;
+    const int x = 2 * X, y = 2 * (cv.y0 + Y) - lv.y0;
     double d00, e00, s00, d10, e10, s10, d01, e01, s01, d11, e11, s11;
     mg_coef<KIND>(lv, x, y, d00, e00, s00);
     mg_coef<KIND>(lv, x + 1, y, d10, e10, s10);
@@ -219,16 +230,17 @@ k_mg_coef0(MgLevel lv, double *__restrict__ d, double *__restrict__ we, double *
 // ---- one level of the V-cycle (levels above the tail) -----------------------------------------------------------------
 // Every kernel does nothing once the PCG loop has stopped (st->active == 0; st may be null: always run).
 
-// residual of the four children of coarse cell (X,Y), added up into the coarse right-hand side.  grid = (ceil(Wc/kBlock), Hc).
+// residual of the four children of coarse cell (X,Y), added up into the coarse right-hand side (children outside the
+// fine level's owned rows give 0, as in k_mg_coarsen).  grid = (ceil(Wc/kBlock), coarse rows from local row Y0).
 template <int KIND>
 __global__ void __launch_bounds__(kBlock)
-k_mg_restrict(MgLevel lv, const double *__restrict__ b, const double *__restrict__ z, MgLevel cv, double *__restrict__ bc,
+k_mg_restrict(MgLevel lv, const double *__restrict__ b, const double *__restrict__ z, MgLevel cv, int Y0, double *__restrict__ bc,
               const CgState *__restrict__ st)
 {
     if (st && !st->active) return;
-    const int X = blockIdx.x * kBlock + threadIdx.x, Y = blockIdx.y;
+    const int X = blockIdx.x * kBlock + threadIdx.x, Y = Y0 + (int)blockIdx.y;
     if (X >= cv.W) return;
-    const int x = 2 * X, y = 2 * Y;
+    const int x = 2 * X, y = 2 * (cv.y0 + Y) - lv.y0;
     const double r00 = mg_residual<KIND>(lv, b, z, x, y), r10 = mg_residual<KIND>(lv, b, z, x + 1, y);
     const double r01 = mg_residual<KIND>(lv, b, z, x, y + 1), r11 = mg_residual<KIND>(lv, b, z, x + 1, y + 1);
     bc[mg_at(cv.pitch, X, Y)] = (r00 + r10) + (r01 + r11);
@@ -242,7 +254,10 @@ k_mg_restrict(MgLevel lv, const double *__restrict__ b, const double *__restrict
 // sweeps over the whole level give.  Bytes per cell of the tile: pre-smoothing b 8 x halo factor + z 8; post-smoothing
 // (b, z 16 + e_c 2) x halo factor + z 8 (halo factor (64 + 4 nu)(32 + 4 nu) / (64 x 32): 1.41 at nu = 2).
 // z_in and z_out must be different buffers: the halo of a tile is read while the neighbouring workgroups store theirs
-// (pre-smoothing reads no z at all).  grid = (ceil(W / kMgTileW), ceil(H / kMgTileH)); dynamic LDS mg_tile_lds(nu) bytes.
+// (pre-smoothing reads no z at all).  On a row block the tiles cover the owned rows and the halo reads the ghost rows,
+// which must hold the neighbours' b (and z_in) for 2 nu rows; cells beyond them are further than 2 nu from an owned
+// row, and only owned rows are stored.  grid = (ceil(W / kMgTileW), ceil((hi - lo) / kMgTileH)); dynamic LDS
+// mg_tile_lds(nu) bytes.
 template <int KIND, bool POST>
 __global__ void __launch_bounds__(kBlock)
 k_mg_tile(MgLevel lv, const double *__restrict__ b, const double *__restrict__ z_in, double *__restrict__ z_out, MgLevel cv,
@@ -252,7 +267,7 @@ k_mg_tile(MgLevel lv, const double *__restrict__ b, const double *__restrict__ z
     if (st && !st->active) return;                                   // (uniform)
     const int h = 2 * nu, RW = kMgTileW + 2 * h, RH = kMgTileH + 2 * h, n = RW * RH;
     double *sb = tile_lds, *sz = tile_lds + n;
-    const int x0 = blockIdx.x * kMgTileW - h, y0 = blockIdx.y * kMgTileH - h;     // x0 even: a cell's x parity is its column's
+    const int x0 = blockIdx.x * kMgTileW - h, y0 = lv.lo + blockIdx.y * kMgTileH - h;   // x0 even: a cell's x parity is its column's
     for (int i = threadIdx.x; i < n; i += kBlock) {
         const int x = x0 + i % RW, y = y0 + i / RW;
         double bv = 0.0, zv = 0.0;                                   // outside the level: 0.0, never updated
@@ -261,7 +276,7 @@ k_mg_tile(MgLevel lv, const double *__restrict__ b, const double *__restrict__ z
             bv = b[at];
             if (POST) {
                 zv = z_in[at];
-                if (mg_live<KIND>(lv, x, y)) zv = zv + 2.0 * ec[mg_at(cv.pitch, x >> 1, y >> 1)];
+                if (mg_live<KIND>(lv, x, y)) zv = zv + 2.0 * ec[mg_at(cv.pitch, x >> 1, ((lv.y0 + y) >> 1) - cv.y0)];
             }
         }
         sb[i] = bv;
@@ -287,7 +302,7 @@ k_mg_tile(MgLevel lv, const double *__restrict__ b, const double *__restrict__ z
     }
     for (int i = threadIdx.x; i < kMgTileW * kMgTileH; i += kBlock) {
         const int col = h + i % kMgTileW, r = h + i / kMgTileW, x = x0 + col, y = y0 + r;
-        if (x < lv.W && y < lv.H) z_out[mg_at(lv.pitch, x, y)] = sz[r * RW + col];
+        if (x < lv.W && y < lv.hi) z_out[mg_at(lv.pitch, x, y)] = sz[r * RW + col];
     }
 }
 

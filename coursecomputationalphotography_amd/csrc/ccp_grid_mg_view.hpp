@@ -17,8 +17,14 @@ struct GridMgView {
     double *x, *b;
     const unsigned char *mask;
     hipStream_t stream;
-    MgHierarchy **cache;             // the handle's cached hierarchy (built on first use, dropped with the mask)
+    MgHierarchy **cache;             // the handle's cached hierarchy (built on first use, dropped with the mask and the partition)
+    // row blocks (ccp_grid_attach_comm): the communicator, every rank's first image row then the image height
+    // (world + 1 entries), and the handle's ghost depth; comm is null when none is attached
+    ccp_comm *comm;
+    const int *part;
+    int ghost;
 };
 int grid_mg_view(ccp_grid *g, GridMgView *v);
+void grid_mg_halo_stale(ccp_grid *g);   // after a row-block solve: the next sweep refreshes the ghost rows first
 
 }  // namespace ccp

@@ -49,6 +49,12 @@ class AbiRowBlockSolver:
         reps = self.block.grid.gauss_seidel_rowblocked(epsilon, max_iteration, check_every)
         return max(r.iterations for r in reps), max(r.last_l1_step for r in reps)
 
+    def mg_conjugate_gradient(self, epsilon: float, max_iteration: int, smoothing_sweeps: int = 2):
+        """Multigrid-preconditioned CG across the blocks (ccp_grid_mg_conjugate_gradient_rowblocked): (iterations,
+        sqrt(r'r) at the stop), the largest over the channels — the same on every rank."""
+        reps = self.block.grid.mg_conjugate_gradient_rowblocked(epsilon, max_iteration, smoothing_sweeps)
+        return max(r.iterations for r in reps), max(r.last_l1_step for r in reps)
+
     def rel_residual(self) -> np.ndarray:
         rr, bb = self.block.grid.residual_norm2_global()
         return np.sqrt(rr / bb)

@@ -427,6 +427,24 @@ int ccp_grid_gauss_seidel_rowblocked(ccp_grid *g, double epsilon, int32_t max_it
  * every rank.  Needs ghost >= 1; works for Dirichlet-mask grids too.  Afterwards the ghost rows of x are stale (the
  * next rowblocked sweep refreshes them).  report: one per channel, as ccp_grid_conjugate_gradient.  Collective. */
 int ccp_grid_conjugate_gradient_rowblocked(ccp_grid *g, double epsilon, int32_t max_iteration, ccp_gs_report *report);
+/* Multigrid-preconditioned conjugate gradient on the partitioned system, from the x the blocks hold: the loop, the
+ * V-cycle, smoothing_sweeps and report as ccp_grid_mg_conjugate_gradient, on both grid kinds.  COLLECTIVE.  Every
+ * dot product is all-reduced, so every rank stops at the same iteration with the same report, and the iterates equal
+ * the one-block call's to rounding.  The V-cycle spans the blocks: on each rank it gives the bits the one-block
+ * V-cycle gives on that rank's rows.  Needs ghost >= 1 on every side that has a neighbour, and every block must own at
+ * least 2*smoothing_sweeps rows.  Otherwise CCP_ERR_STATE / CCP_ERR_UNSUPPORTED, returned on EVERY rank before any
+ * collective call.  Afterwards the ghost rows of x are stale, as after ccp_grid_conjugate_gradient_rowblocked.
+ * Levels stay distributed (each rank holds its own rows plus 8 ghost rows per neighbour side) while every block
+ * boundary falls on an even row and every block keeps >= 8 rows of the next level; from the first level that fails,
+ * every rank holds every level whole and runs the one-block V-cycle on it. */
+int ccp_grid_mg_conjugate_gradient_rowblocked(ccp_grid *g, double epsilon, int32_t max_iteration,
+                                              int32_t smoothing_sweeps, ccp_gs_report *report);
+/* Diagnostic, collective: x := M^-1 b on the owned rows, one V-cycle per channel. */
+int ccp_grid_mg_apply_rowblocked(ccp_grid *g, int32_t smoothing_sweeps);
+/* Diagnostic, collective (builds the hierarchy on first use): the number of levels; how many of them, from level 0
+ * on, hold only the block's own rows; and the size of the first level every rank holds whole (0 x 0 if none). */
+int ccp_grid_mg_rowblock_info(ccp_grid *g, int32_t *n_levels, int32_t *distributed_levels,
+                              int32_t *replicated_width, int32_t *replicated_height);
 /* ccp_grid_residual_norm2 summed over all blocks (refreshes stale ghost rows first).  Collective. */
 int ccp_grid_residual_norm2_global(ccp_grid *g, double *rr_bb);
 /* Statistics: exchanges issued; how the exchange waits for the edge rows (0 hipStreamWaitValue64, 1 polling
