@@ -23,6 +23,8 @@ CCP_OK = 0
 GRID_DIRICHLET_MASK = 1
 ORDER_LEXICOGRAPHIC = 0
 ORDER_MULTICOLOUR = 1
+CLONE_IMPORT = 0
+CLONE_MIXED = 1
 
 # every symbol include/ccp_gs.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = (
@@ -35,7 +37,8 @@ ABI_SYMBOLS = (
     "ccp_grid_sweep", "ccp_grid_sweep_edges_first", "ccp_grid_stream_wait_edges", "ccp_grid_tune", "ccp_grid_set_fused", "ccp_grid_set_tiling", "ccp_grid_get_tiling", "ccp_grid_sweep_l1", "ccp_grid_halo_refreshed", "ccp_grid_gauss_seidel", "ccp_grid_gauss_seidel_lexicographic", "ccp_debug_lex_tickets", "ccp_grid_conjugate_gradient",
     "ccp_grid_mg_conjugate_gradient", "ccp_grid_mg_apply", "ccp_grid_mg_level",
     "ccp_grid_residual_norm2", "ccp_grid_abs_sum", "ccp_grid_assemble_rhs", "ccp_grid_assemble_from_images", "ccp_grid_store_u8",
-    "ccp_grid_set_x_u8", "ccp_grid_last_timing", "ccp_grid_region_begin", "ccp_grid_region_end",
+    "ccp_grid_set_x_u8", "ccp_grid_assemble_region_rhs", "ccp_grid_assemble_clone", "ccp_grid_store_u8_composite",
+    "ccp_grid_last_timing", "ccp_grid_region_begin", "ccp_grid_region_end",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
     "ccp_grid_attach_comm", "ccp_grid_set_overlap", "ccp_grid_exchange_halos", "ccp_grid_sweep_rowblocked",
     "ccp_grid_gauss_seidel_rowblocked", "ccp_grid_conjugate_gradient_rowblocked", "ccp_grid_residual_norm2_global", "ccp_grid_comm_stats",
@@ -193,6 +196,9 @@ def load() -> C.CDLL:
     L.ccp_grid_assemble_from_images.argtypes = [vp, vp, i32, i64, vp, i64, i32]
     L.ccp_grid_store_u8.argtypes = [vp, vp, i64]
     L.ccp_grid_set_x_u8.argtypes = [vp, vp, i64]
+    L.ccp_grid_assemble_region_rhs.argtypes = [vp, vp, vp, i64, vp, i64, i32]
+    L.ccp_grid_assemble_clone.argtypes = [vp, vp, i64, vp, i64, i32, i32]
+    L.ccp_grid_store_u8_composite.argtypes = [vp, vp, i64, vp, i64]
     L.ccp_grid_last_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i32)]
     L.ccp_grid_region_begin.argtypes = [vp]
     L.ccp_grid_region_end.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i64), C.POINTER(i64)]
@@ -660,6 +666,37 @@ class Grid:
     def set_x_u8(self, image: np.ndarray):
         image = np.ascontiguousarray(image, dtype=np.uint8)
         check(self.L.ccp_grid_set_x_u8(self.h, _ptr(image), image.strides[0]), "ccp_grid_set_x_u8")
+
+    # ---- region blends (Dirichlet-mask grids; whole-canvas H x W x channels host images) ----------------
+    def _canvas_image(self, img, dtype) -> np.ndarray:
+        img = np.ascontiguousarray(img, dtype=dtype)
+        if img.reshape(self.H, self.W, -1).shape[2] != self.C:
+            raise ValueError(f"image must be {self.H} x {self.W} x {self.C}")
+        return img
+
+    def assemble_region_rhs(self, gx, gy, canvas, init_x: bool = False):
+        """b := -div(g) + the canvas values of the neighbours outside the region (0 outside); init_x: x := canvas
+        inside the region.  gx, gy: float32 forward differences, canvas: u8."""
+        gx, gy = self._canvas_image(gx, np.float32), self._canvas_image(gy, np.float32)
+        canvas = self._canvas_image(canvas, np.uint8)
+        check(self.L.ccp_grid_assemble_region_rhs(self.h, _ptr(gx), _ptr(gy), gx.strides[0], _ptr(canvas), canvas.strides[0],
+                                                  1 if init_x else 0), "ccp_grid_assemble_region_rhs")
+
+    def assemble_clone(self, source, target, mixed: bool = False, init: int = 1):
+        """Seamless cloning of `source` into `target` (both u8, already on the canvas): imported (mixed False) or
+        mixed gradients, boundary values from the target.  init: 0 leave x, 1 x := target, 2 x := source."""
+        source, target = self._canvas_image(source, np.uint8), self._canvas_image(target, np.uint8)
+        check(self.L.ccp_grid_assemble_clone(self.h, _ptr(source), source.strides[0], _ptr(target), target.strides[0],
+                                             CLONE_MIXED if mixed else CLONE_IMPORT, int(init)), "ccp_grid_assemble_clone")
+
+    def store_u8_composite(self, canvas) -> np.ndarray:
+        """The clamped solution inside the region, the canvas outside; H x W x channels u8.  On a row block only the
+        owned rows are filled (the others stay 0)."""
+        canvas = self._canvas_image(canvas, np.uint8)
+        out = np.zeros((self.H, self.W, self.C), dtype=np.uint8)
+        check(self.L.ccp_grid_store_u8_composite(self.h, _ptr(canvas), canvas.strides[0], _ptr(out), out.strides[0]),
+              "ccp_grid_store_u8_composite")
+        return out
 
     def region_begin(self):
         check(self.L.ccp_grid_region_begin(self.h), "ccp_grid_region_begin")

@@ -6,6 +6,7 @@
 #include "ccp_cg.hpp"
 #include "ccp_grid_cg.hpp"
 #include "ccp_grid_mg_view.hpp"
+#include "ccp_grid_blend.hpp"
 #include "ccp_comm.hpp"
 
 #include <algorithm>
@@ -70,6 +71,13 @@ struct ccp_grid {
     bool masked = false;
     DevBuf<unsigned char> maskp, tile_live;
     DevBuf<int> tile_rows;       // ... and which of a live tile's own rows do (two ints per tile)
+    // the region bytes of image rows y0-1 and y0+local_rows (2 x W, zero where a row does not exist): the blend
+    // assembly reads its neighbours there (ccp_grid_blend.hpp).  Known after ccp_grid_set_mask_host, and after the
+    // device twin on a handle that holds the whole canvas.  mask_border: the region touches the canvas's outer rows
+    // or columns (1 / 0; -1 not known yet, computed at the first clone call).
+    DevBuf<unsigned char> mask_edge;
+    bool mask_edge_known = false;
+    int mask_border = -1;
     int live_T = -1, live_R = -1, live_lo = -1, live_hi = -1;
     long unknowns = 0;           // mask bytes set (owned rows), for the statistics
     bool fuse = true;            // use k_fused_sweep for unchecked sweeps
@@ -913,6 +921,8 @@ try {
     if (st == CCP_OK && g->masked) {
         st = g->maskp.alloc((size_t)geo.ch_stride);
         if (st == CCP_OK && hipMemset(g->maskp.p, 0, (size_t)geo.ch_stride) != hipSuccess) st = CCP_ERR_HIP;
+        if (st == CCP_OK) st = g->mask_edge.alloc(2 * (size_t)d->width);
+        if (st == CCP_OK && hipMemset(g->mask_edge.p, 0, 2 * (size_t)d->width) != hipSuccess) st = CCP_ERR_HIP;
     }
     if (st == CCP_OK) st = g->b.alloc(elems);
     // partial sums: the finest launch is one block per (x tile, row, channel*2) with 2 doubles
@@ -1055,8 +1065,26 @@ try {
             if (l >= geo.own_lo && l < geo.own_hi) ++count;
         }
     }
+    // the rows just beyond the local ones, and whether the region reaches the canvas's outer rows or columns
+    // (every block is handed the whole mask, so every block finds the same answer)
+    std::vector<unsigned char> edge(2 * (size_t)geo.W, 0);
+    const int y_above = geo.y0 - 1, y_below = geo.y0 + geo.local_rows;
+    for (int x = 0; x < geo.W; ++x) {
+        if (y_above >= 0) edge[x] = mask[(size_t)y_above * (size_t)row_stride_bytes + x] != 0;
+        if (y_below < geo.H) edge[geo.W + x] = mask[(size_t)y_below * (size_t)row_stride_bytes + x] != 0;
+    }
+    bool border = false;
+    for (int y = 0; y < geo.H && !border; ++y) {
+        const uint8_t *row = mask + (size_t)y * (size_t)row_stride_bytes;
+        if (row[0] || row[geo.W - 1]) border = true;
+        if (y == 0 || y == geo.H - 1)
+            for (int x = 0; x < geo.W && !border; ++x) border = row[x] != 0;
+    }
     CCP_HIP(hipMemcpyAsync(g->maskp.p, split.data(), split.size(), hipMemcpyHostToDevice, g->stream));
+    CCP_HIP(hipMemcpyAsync(g->mask_edge.p, edge.data(), edge.size(), hipMemcpyHostToDevice, g->stream));
     CCP_HIP(hipStreamSynchronize(g->stream));
+    g->mask_edge_known = true;
+    g->mask_border = border ? 1 : 0;
     g->unknowns = count;
     g->live_T = -1;                                      // the tile census belongs to the old mask
     mg_release(g->mg);                                   // ... and so does the multigrid hierarchy
@@ -1105,6 +1133,10 @@ int ccp::grid_set_mask_split_device(ccp_grid *g, const unsigned char *split_mask
     if (!g->masked) return CCP_ERR_STATE;
     if (!split_mask_dev) return CCP_ERR_BAD_ARG;
     CCP_HIP(hipMemcpyAsync(g->maskp.p, split_mask_dev, (size_t)g->geom.ch_stride, hipMemcpyDeviceToDevice, g->stream));
+    // no rows beyond the local ones on a whole-canvas handle; a row block cannot tell (the blend calls refuse it)
+    CCP_HIP(hipMemsetAsync(g->mask_edge.p, 0, 2 * (size_t)g->geom.W, g->stream));
+    g->mask_edge_known = g->geom.y0 == 0 && g->geom.local_rows == g->geom.H;
+    g->mask_border = -1;
     g->unknowns = unknowns;
     g->live_T = -1;                                      // the tile census belongs to the old mask
     mg_release(g->mg);                                   // ... and so does the multigrid hierarchy
@@ -2149,6 +2181,140 @@ try {
     CCP_TRY(zero_unmasked(g, g->x.p));
     CCP_HIP(hipStreamSynchronize(g->stream));
     return CCP_OK;
+} CCP_ABI_CATCH
+
+}  // extern "C"
+
+// ---- region blend on a Dirichlet-mask grid (ccp_grid_blend.hpp) ------------------------------------------------------
+namespace {
+
+// Rows [ya, yb) of an interleaved host image (W x C elements of T per row, `stride` bytes apart) into a packed
+// device buffer, asynchronously on the handle's stream.
+template <typename T>
+int upload_window(ccp_grid *g, DevBuf<T> &dev, const T *host, int64_t stride, int ya, int yb)
+{
+    const size_t row = (size_t)g->desc.width * g->desc.channels * sizeof(T);
+    CCP_TRY(dev.alloc((size_t)(yb - ya) * g->desc.width * g->desc.channels));
+    CCP_HIP(hipMemcpy2DAsync(dev.p, row, reinterpret_cast<const char *>(host) + (size_t)ya * (size_t)stride, (size_t)stride,
+                             row, (size_t)(yb - ya), hipMemcpyHostToDevice, g->stream));
+    return CCP_OK;
+}
+
+BlendMask blend_mask(const ccp_grid *g) { return BlendMask{g->maskp.p, g->mask_edge.p, g->geom}; }
+
+// the image rows the assembly reads: the local rows and one row above and below where they exist
+void blend_window(const ccp_grid *g, int *ya, int *yb)
+{
+    *ya = std::max(0, g->geom.y0 - 1);
+    *yb = std::min(g->geom.H, g->geom.y0 + g->geom.local_rows + 1);
+}
+
+// Does the region touch the canvas's outer rows or columns?  Known from ccp_grid_set_mask_host; after the device
+// twin (whole-canvas handles only) read back once from the split mask.
+int blend_border(ccp_grid *g, bool *touches)
+{
+    if (g->mask_border < 0) {
+        if (!g->mask_edge_known) return CCP_ERR_STATE;
+        const Geom &geo = g->geom;
+        std::vector<unsigned char> split((size_t)geo.ch_stride);
+        CCP_HIP(hipMemcpyAsync(split.data(), g->maskp.p, split.size(), hipMemcpyDeviceToHost, g->stream));
+        CCP_HIP(hipStreamSynchronize(g->stream));
+        auto at = [&](int y, int x) { return split[(size_t)((2L * y + ((x + y) & 1)) * geo.pitch + (x >> 1))] != 0; };
+        bool border = false;
+        for (int y = 0; y < geo.H && !border; ++y) {
+            border = at(y, 0) || at(y, geo.W - 1);
+            if (y == 0 || y == geo.H - 1)
+                for (int x = 0; x < geo.W && !border; ++x) border = at(y, x);
+        }
+        g->mask_border = border ? 1 : 0;
+    }
+    *touches = g->mask_border != 0;
+    return CCP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ccp_grid_assemble_region_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes,
+                                 const uint8_t *canvas, int64_t canvas_stride_bytes, int32_t init_x_from_canvas)
+try {
+    CCP_TRY(bind(g));
+    if (!gx || !gy || !canvas) return CCP_ERR_BAD_ARG;
+    const int W = g->desc.width, C = g->desc.channels;
+    if (field_stride_bytes < (int64_t)W * C * (int64_t)sizeof(float) || canvas_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
+    if (!g->masked) return CCP_ERR_UNSUPPORTED;           // SolveChannel's matrix has its own assembly
+    if (!g->mask_edge_known) return CCP_ERR_STATE;
+    int ya, yb;
+    blend_window(g, &ya, &yb);
+    DevBuf<float> dgx, dgy;
+    DevBuf<uint8_t> dcan;
+    CCP_TRY(upload_window(g, dgx, gx, field_stride_bytes, ya, yb));
+    CCP_TRY(upload_window(g, dgy, gy, field_stride_bytes, ya, yb));
+    CCP_TRY(upload_window(g, dcan, canvas, canvas_stride_bytes, ya, yb));
+    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->geom.local_rows);
+    if (init_x_from_canvas)
+        hipLaunchKernelGGL((k_blend_field_rhs<true>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), dgx.p, dgy.p,
+                           dcan.p, ya, C);
+    else
+        hipLaunchKernelGGL((k_blend_field_rhs<false>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), dgx.p, dgy.p,
+                           dcan.p, ya, C);
+    CCP_HIP(hipGetLastError());
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    if (init_x_from_canvas) g->half_sweeps_since_refresh = 0;   // x is exact on every local row
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_clone(ccp_grid *g, const uint8_t *source, int64_t source_stride_bytes, const uint8_t *target,
+                            int64_t target_stride_bytes, int32_t mode, int32_t init)
+try {
+    CCP_TRY(bind(g));
+    if (!source || !target) return CCP_ERR_BAD_ARG;
+    const int W = g->desc.width, C = g->desc.channels;
+    if (source_stride_bytes < (int64_t)W * C || target_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
+    if ((mode != CCP_CLONE_IMPORT && mode != CCP_CLONE_MIXED) || init < 0 || init > 2) return CCP_ERR_BAD_ARG;
+    if (!g->masked) return CCP_ERR_UNSUPPORTED;
+    if (!g->mask_edge_known) return CCP_ERR_STATE;
+    bool touches = false;
+    CCP_TRY(blend_border(g, &touches));
+    if (touches) return CCP_ERR_UNSUPPORTED;              // the diagonal is 4 everywhere: no neighbour may be missing
+    int ya, yb;
+    blend_window(g, &ya, &yb);
+    DevBuf<uint8_t> dsrc, dtgt;
+    CCP_TRY(upload_window(g, dsrc, source, source_stride_bytes, ya, yb));
+    CCP_TRY(upload_window(g, dtgt, target, target_stride_bytes, ya, yb));
+    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->geom.local_rows);
+    if (mode == CCP_CLONE_MIXED)
+        hipLaunchKernelGGL((k_blend_clone_rhs<true>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), dsrc.p, dtgt.p,
+                           ya, C, (int)init);
+    else
+        hipLaunchKernelGGL((k_blend_clone_rhs<false>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), dsrc.p, dtgt.p,
+                           ya, C, (int)init);
+    CCP_HIP(hipGetLastError());
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    if (init) g->half_sweeps_since_refresh = 0;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_store_u8_composite(ccp_grid *g, const uint8_t *canvas, int64_t canvas_stride_bytes, uint8_t *out,
+                                int64_t out_stride_bytes)
+try {
+    CCP_TRY(bind(g));
+    if (!canvas || !out) return CCP_ERR_BAD_ARG;
+    const int W = g->desc.width, C = g->desc.channels;
+    if (canvas_stride_bytes < (int64_t)W * C || out_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
+    if (!g->masked) return CCP_ERR_UNSUPPORTED;
+    const int y_lo = g->desc.row_begin, rows = g->desc.row_count;
+    DevBuf<uint8_t> dcan, dout;
+    CCP_TRY(upload_window(g, dcan, canvas, canvas_stride_bytes, y_lo, y_lo + rows));
+    CCP_TRY(dout.alloc((size_t)rows * W * C));
+    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)rows);
+    hipLaunchKernelGGL(k_blend_composite, grid, dim3(kBlock), 0, g->stream, g->x.p, blend_mask(g), dcan.p, dout.p, C);
+    CCP_HIP(hipGetLastError());
+    CCP_HIP(hipMemcpy2DAsync(out + (size_t)y_lo * (size_t)out_stride_bytes, (size_t)out_stride_bytes, dout.p, (size_t)W * C,
+                             (size_t)W * C, (size_t)rows, hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    return edge_timeout_status(g);
 } CCP_ABI_CATCH
 
 // ============================================================================================

@@ -13,6 +13,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -39,9 +40,9 @@ inline void check(int status, const char *what)
 }
 struct GridHandle {
     ccp_grid *g = nullptr;
-    GridHandle(int W, int H, int C, int device)
+    GridHandle(int W, int H, int C, int device, int flags = 0)
     {
-        ccp_grid_desc d{W, H, C, 0, H, 0, device, 0};
+        ccp_grid_desc d{W, H, C, 0, H, 0, device, flags};
         check(ccp_grid_create(&d, &g), "ccp_grid_create");
     }
     ~GridHandle() { ccp_grid_destroy(g); }
@@ -184,6 +185,65 @@ inline void BuildSolveGradientFusion(const std::vector<ImageView> &images, const
     if (!fast_init_value) detail::check(ccp_grid_fill_x(h.g, detail::default_start(solver)), "ccp_grid_fill_x");
     detail::solve(h.g, solver, iterations, 3);
     detail::check(ccp_grid_store_u8(h.g, static_cast<uint8_t *>(result.data), (int64_t)result.step), "ccp_grid_store_u8");
+}
+
+// ---- region blends: the system restricted to a pixel region (a Dirichlet-mask grid) -------------------------------
+// mask: CV_8UC1 view, non-zero = region.  canvas / source / target / out: u8 views with the channel count of the
+// blend, all of the mask's shape.  b and the start vector are built on the device, the solve is any Solver from the
+// canvas (target) inside the region, and `out` receives the composite: the clamped solution inside the region, the
+// canvas (target) outside.  Every failure throws; nothing is computed on the host.
+enum class CloneMode { Import = CCP_CLONE_IMPORT, Mixed = CCP_CLONE_MIXED };
+
+namespace detail {
+inline void check_region_shape(const char *who, const ImageView &mask, std::initializer_list<const ImageView *> views, int C)
+{
+    if (mask.channels != 1 || !mask.data) throw std::invalid_argument(std::string(who) + ": mask must be a one-channel view");
+    for (const ImageView *v : views)
+        if (!v->data || v->rows != mask.rows || v->cols != mask.cols || v->channels != C)
+            throw std::invalid_argument(std::string(who) + ": image shapes differ");
+}
+struct RegionHandle : GridHandle {
+    RegionHandle(const ImageView &mask, int C, int device) : GridHandle(mask.cols, mask.rows, C, device, CCP_GRID_DIRICHLET_MASK)
+    {
+        check(ccp_grid_set_mask_host(g, static_cast<const uint8_t *>(mask.data), (int64_t)mask.step), "ccp_grid_set_mask_host");
+    }
+};
+}  // namespace detail
+
+// Region blend from a guidance field (lab8's union region, hw8_pa.cc:749-810): gx, gy float32 forward differences
+// (CV_32FC<C> views sharing one row step), canvas u8: the Dirichlet values outside the region and the start vector.
+inline void BlendRegion(const ImageView &gx, const ImageView &gy, const ImageView &canvas, const ImageView &mask,
+                        ImageView &out, int iterations, Solver solver = Solver::GaussSeidel, int device = 0)
+{
+    const int C = canvas.channels;
+    detail::check_region_shape("BlendRegion", mask, {&gx, &gy, &canvas, &out}, C);
+    if (gx.step != gy.step) throw std::invalid_argument("BlendRegion: gx and gy must share one row step");
+    detail::RegionHandle h(mask, C, device);
+    detail::check(ccp_grid_assemble_region_rhs(h.g, static_cast<const float *>(gx.data), static_cast<const float *>(gy.data),
+                                               (int64_t)gx.step, static_cast<const uint8_t *>(canvas.data), (int64_t)canvas.step, 1),
+                  "ccp_grid_assemble_region_rhs");
+    detail::solve(h.g, solver, iterations, C);
+    detail::check(ccp_grid_store_u8_composite(h.g, static_cast<const uint8_t *>(canvas.data), (int64_t)canvas.step,
+                                              static_cast<uint8_t *>(out.data), (int64_t)out.step),
+                  "ccp_grid_store_u8_composite");
+}
+
+// Seamless cloning (Perez et al. 2003) of `source` into `target`, the source already placed on the canvas: imported
+// or mixed gradients, boundary values and start vector from the target.  The region must not touch the canvas
+// border (the call throws: CCP_ERR_UNSUPPORTED).
+inline void SeamlessClone(const ImageView &source, const ImageView &target, const ImageView &mask, ImageView &out,
+                          CloneMode mode, int iterations, Solver solver = Solver::GaussSeidel, int device = 0)
+{
+    const int C = target.channels;
+    detail::check_region_shape("SeamlessClone", mask, {&source, &target, &out}, C);
+    detail::RegionHandle h(mask, C, device);
+    detail::check(ccp_grid_assemble_clone(h.g, static_cast<const uint8_t *>(source.data), (int64_t)source.step,
+                                          static_cast<const uint8_t *>(target.data), (int64_t)target.step, (int32_t)mode, 1),
+                  "ccp_grid_assemble_clone");
+    detail::solve(h.g, solver, iterations, C);
+    detail::check(ccp_grid_store_u8_composite(h.g, static_cast<const uint8_t *>(target.data), (int64_t)target.step,
+                                              static_cast<uint8_t *>(out.data), (int64_t)out.step),
+                  "ccp_grid_store_u8_composite");
 }
 
 }  // namespace ccp

@@ -233,7 +233,8 @@ typedef struct ccp_grid_desc {
  * brush / label region solves (BASELINE configs[4]).  The region is one byte per pixel (ccp_grid_set_mask_host);
  * pixels outside it are fixed at 0 in x and b.  Sweeps (red-black, fixed count or stop rule), b := A x, the
  * residual and conjugate gradient honour the mask, and so does the sweep in the reference's order (raster order of
- * the region); SolveChannel's assembly entry points return CCP_ERR_UNSUPPORTED.  Row blocks work as for the plain
+ * the region); SolveChannel's assembly entry points return CCP_ERR_UNSUPPORTED (the region blend has its own:
+ * ccp_grid_assemble_region_rhs, ccp_grid_assemble_clone, ccp_grid_store_u8_composite).  Row blocks work as for the plain
  * grid (ghost rows, ccp_grid_attach_comm, ccp_grid_sweep_rowblocked, ...: the region of BASELINE configs[4] on
  * several GPUs, every block handed the whole mask and keeping its own rows of it).  ccp_csr_gauss_seidel reaches
  * this form by itself when the uploaded matrix is such a Laplacian of a raster region (ccp_csr_last_path). */
@@ -482,6 +483,37 @@ int ccp_grid_store_u8(ccp_grid *g, uint8_t *out, int64_t row_stride_bytes);
 /* Composite initial guess (PhotoMontage.cpp:599-610): x(y,x)[ch] = image(y,x)[ch] from an
  * interleaved u8 host image (the `fast_init_value` extension for GS). */
 int ccp_grid_set_x_u8(ccp_grid *g, const uint8_t *image, int64_t row_stride_bytes);
+
+/* Region blends on a Dirichlet-mask grid: b (and optionally x) assembled on the device from host images, and the
+ * composite image after the solve.  Mask grids only (a plain grid: CCP_ERR_UNSUPPORTED); null pointers or strides
+ * below one row: CCP_ERR_BAD_ARG.  Images are host, interleaved H x W x channels, row stride in bytes, always the
+ * WHOLE canvas; a row block copies to the device only its local rows plus one row above and below.  The assembly
+ * writes every local row, ghost rows included, leaving the handle as ccp_grid_set_b_host / _set_x_host on every
+ * local row would (x and b exactly 0 outside the region).  All three synchronise the stream.
+ *
+ * Region blend from a guidance field (lab8's union region, hw8_pa.cc:749-810): for every region pixel, in double
+ * with gx, gy widened from float32,
+ *     t = 0 - (gx(x,y) + gy(x,y));  t += gx(x-1,y) if x >= 1;  t += gy(x,y-1) if y >= 1
+ *     o = 0;  o += the values of N, then S, W, E;  b = t + o
+ * where a neighbour's value is its canvas value when it lies inside the canvas and outside the region, else 0.
+ * b = 0 outside the region.  gx, gy: float32 forward differences (one stride for both); canvas: u8.
+ * init_x_from_canvas: x := canvas inside the region (0 outside). */
+int ccp_grid_assemble_region_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes,
+                                 const uint8_t *canvas, int64_t canvas_stride_bytes, int32_t init_x_from_canvas);
+/* Seamless cloning (Perez et al. 2003) of `source` into `target`, both already on the canvas (u8):
+ *     b_p = sum over q in {N,S,W,E} of v_pq  +  sum over q outside the region of T_q
+ * with guidance v_pq = S_p - S_q (CCP_CLONE_IMPORT) or the larger in magnitude of T_p - T_q and S_p - S_q
+ * (CCP_CLONE_MIXED, ties take the source); integers, so b is exact.  init: 0 leave x, 1 x := target, 2 x := source
+ * (inside the region, 0 outside).  The grid's diagonal is 4 everywhere, so a region that touches the canvas's outer
+ * rows or columns is refused: CCP_ERR_UNSUPPORTED.  A bad mode or init: CCP_ERR_BAD_ARG. */
+#define CCP_CLONE_IMPORT 0
+#define CCP_CLONE_MIXED 1
+int ccp_grid_assemble_clone(ccp_grid *g, const uint8_t *source, int64_t source_stride_bytes,
+                            const uint8_t *target, int64_t target_stride_bytes, int32_t mode, int32_t init);
+/* Composite epilogue: out(y,x)[ch] = uchar(max(min(x,255),0)) inside the region, canvas(y,x)[ch] outside.  `out`
+ * is a whole-canvas buffer; on a row block only its OWNED rows are written. */
+int ccp_grid_store_u8_composite(ccp_grid *g, const uint8_t *canvas, int64_t canvas_stride_bytes,
+                                uint8_t *out, int64_t out_stride_bytes);
 
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
