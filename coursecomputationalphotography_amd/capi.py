@@ -39,6 +39,9 @@ ABI_SYMBOLS = (
     "ccp_grid_residual_norm2", "ccp_grid_abs_sum", "ccp_grid_assemble_rhs", "ccp_grid_assemble_from_images", "ccp_grid_store_u8",
     "ccp_grid_set_x_u8", "ccp_grid_assemble_region_rhs", "ccp_grid_assemble_clone", "ccp_grid_store_u8_composite",
     "ccp_grid_last_timing", "ccp_grid_region_begin", "ccp_grid_region_end",
+    "ccp_grid_set_b_device", "ccp_grid_set_x_device", "ccp_grid_get_x_device", "ccp_grid_get_b_device",
+    "ccp_grid_assemble_rhs_device", "ccp_grid_assemble_from_images_device", "ccp_grid_store_u8_device", "ccp_grid_set_x_u8_device",
+    "ccp_grid_assemble_region_rhs_device", "ccp_grid_assemble_clone_device", "ccp_grid_store_u8_composite_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
     "ccp_grid_attach_comm", "ccp_grid_set_overlap", "ccp_grid_exchange_halos", "ccp_grid_sweep_rowblocked",
     "ccp_grid_gauss_seidel_rowblocked", "ccp_grid_conjugate_gradient_rowblocked", "ccp_grid_residual_norm2_global", "ccp_grid_comm_stats",
@@ -67,6 +70,15 @@ class GridLayout(C.Structure):
     _fields_ = [("x_dev", C.c_void_p), ("b_dev", C.c_void_p), ("pitch", C.c_int64),
                 ("local_rows", C.c_int32), ("ghost_top", C.c_int32), ("ghost_bottom", C.c_int32),
                 ("channels", C.c_int32)]
+
+
+DTYPE_U8, DTYPE_F32, DTYPE_F64 = 1, 2, 3
+
+
+class DeviceArray(C.Structure):
+    """ccp_device_array: a strided view of device memory, strides in elements."""
+    _fields_ = [("data", C.c_void_p), ("dtype", C.c_int32), ("reserved", C.c_int32),
+                ("stride_n", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("stride_c", C.c_int64)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -199,6 +211,16 @@ def load() -> C.CDLL:
     L.ccp_grid_assemble_region_rhs.argtypes = [vp, vp, vp, i64, vp, i64, i32]
     L.ccp_grid_assemble_clone.argtypes = [vp, vp, i64, vp, i64, i32, i32]
     L.ccp_grid_store_u8_composite.argtypes = [vp, vp, i64, vp, i64]
+    da = C.POINTER(DeviceArray)
+    for name in ("ccp_grid_set_b_device", "ccp_grid_set_x_device", "ccp_grid_get_x_device", "ccp_grid_get_b_device"):
+        getattr(L, name).argtypes = [vp, da, i32, i32]
+    L.ccp_grid_assemble_rhs_device.argtypes = [vp, da, da, vp]
+    L.ccp_grid_assemble_from_images_device.argtypes = [vp, da, i32, da, i32]
+    L.ccp_grid_store_u8_device.argtypes = [vp, da]
+    L.ccp_grid_set_x_u8_device.argtypes = [vp, da]
+    L.ccp_grid_assemble_region_rhs_device.argtypes = [vp, da, da, da, i32]
+    L.ccp_grid_assemble_clone_device.argtypes = [vp, da, da, i32, i32]
+    L.ccp_grid_store_u8_composite_device.argtypes = [vp, da, da]
     L.ccp_grid_last_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i32)]
     L.ccp_grid_region_begin.argtypes = [vp]
     L.ccp_grid_region_end.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i64), C.POINTER(i64)]
@@ -250,6 +272,18 @@ def _f64(a) -> np.ndarray:
 
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _no_overlap(shape, strides) -> bool:
+    """No two elements of a view share an address: sorted by stride, each stride >= stride * extent of the one below
+    (dimensions of extent 1 do not count)."""
+    dims = sorted((s, e) for s, e in zip(strides, shape) if e > 1)
+    span = 1
+    for s, e in dims:
+        if s < span:
+            return False
+        span = s * e
+    return True
 
 
 COMM_ID_BYTES = 128
@@ -696,6 +730,179 @@ class Grid:
         out = np.zeros((self.H, self.W, self.C), dtype=np.uint8)
         check(self.L.ccp_grid_store_u8_composite(self.h, _ptr(canvas), canvas.strides[0], _ptr(out), out.strides[0]),
               "ccp_grid_store_u8_composite")
+        return out
+
+    # ---- device hand-off: torch tensors in, torch tensors out (ccp_grid_*_device) -----------------------------
+    # Every tensor is H x W x channels (n_rows x W x channels for set/get; H x W also accepted when channels == 1),
+    # any strides: interleaved, channel-planar (a C x H x W tensor .permute(1, 2, 0)), a window of a larger image or
+    # an expanded (broadcast) input.  Tensors are checked here (device, dtype, shape, strides) and ValueError is raised
+    # before the library is called.  Each call is enqueued on torch.cuda.current_stream(device) -- the handle's stream
+    # is set to it for the call and restored afterwards -- with no host synchronisation (assemble_from_images_tensor
+    # excepted), and outputs are allocated on that stream.  The caller keeps inputs unchanged until that stream has
+    # passed the call, as for any torch kernel.
+    def _torch(self):
+        import torch
+        return torch
+
+    def _device(self):
+        return self._torch().device("cuda", self.desc.device)
+
+    def _hwc(self, t, name, dtypes, rows=None, output=False):
+        """Check tensor `t` and return (ccp_device_array, t viewed as rows x W x C)."""
+        torch = self._torch()
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if t.device.type != "cuda" or t.device.index != self.desc.device:
+            raise ValueError(f"{name} must be on cuda:{self.desc.device}, not {t.device}")
+        codes = {torch.uint8: DTYPE_U8, torch.float32: DTYPE_F32, torch.float64: DTYPE_F64}
+        if t.dtype not in dtypes:
+            raise ValueError(f"{name} must have dtype {' or '.join(str(d) for d in dtypes)}, not {t.dtype}")
+        rows = self.H if rows is None else rows
+        if t.dim() == 2 and self.C == 1:
+            t = t.unsqueeze(-1)
+        if tuple(t.shape) != (rows, self.W, self.C):
+            raise ValueError(f"{name} must be {rows} x {self.W} x {self.C}, not {tuple(t.shape)}")
+        if any(s < 0 for s in t.stride()):
+            raise ValueError(f"{name} has a negative stride")
+        if output and not _no_overlap(t.shape, t.stride()):
+            raise ValueError(f"{name} is an output whose elements overlap")
+        sy, sx, sc = t.stride()
+        return DeviceArray(t.data_ptr(), codes[t.dtype], 0, 0, sy, sx, sc), t
+
+    def _on_stream(self, fn, what):
+        """Run `fn()` (a library call) on torch's current stream of this device, restoring the handle's stream."""
+        torch = self._torch()
+        stream = torch.cuda.current_stream(self._device()).cuda_stream
+        prev = self.stream_handle
+        self.set_stream(stream)
+        try:
+            check(fn(), what)
+        finally:
+            self.set_stream(prev)
+
+    def _set_tensor(self, which, t, first_row):
+        torch = self._torch()
+        first_row = self.first_local_row if first_row is None else first_row
+        n = t.shape[0] if hasattr(t, "shape") and len(t.shape) else 0
+        arr, _ = self._hwc(t, "rows", (torch.float32, torch.float64), rows=n)
+        fn = getattr(self.L, f"ccp_grid_set_{which}_device")
+        self._on_stream(lambda: fn(self.h, C.byref(arr), first_row, n), f"ccp_grid_set_{which}_device")
+
+    def _get_tensor(self, which, out, dtype, first_row, n_rows):
+        torch = self._torch()
+        first_row, n_rows = self._rows(first_row, n_rows)
+        if out is None:
+            with torch.cuda.device(self._device()):
+                out = torch.empty((n_rows, self.W, self.C), dtype=dtype, device=self._device())
+        arr, _ = self._hwc(out, "out", (torch.float32, torch.float64), rows=n_rows, output=True)
+        fn = getattr(self.L, f"ccp_grid_get_{which}_device")
+        self._on_stream(lambda: fn(self.h, C.byref(arr), first_row, n_rows), f"ccp_grid_get_{which}_device")
+        return out
+
+    def set_b_tensor(self, rows, first_row=None):
+        """b of every channel on image rows [first_row, first_row + len(rows)) from a float32 / float64 tensor
+        (rows x W x channels; first_row: the first local row, ghosts included, by default)."""
+        self._set_tensor("b", rows, first_row)
+
+    def set_x_tensor(self, rows, first_row=None):
+        self._set_tensor("x", rows, first_row)
+
+    def get_x_tensor(self, out=None, dtype=None, first_row=None, n_rows=None):
+        """x of every channel as an n_rows x W x channels tensor (float64 by default; float32 rounds to nearest),
+        written into `out` when given."""
+        dtype = dtype or self._torch().float64
+        return self._get_tensor("x", out, dtype, first_row, n_rows)
+
+    def get_b_tensor(self, out=None, dtype=None, first_row=None, n_rows=None):
+        dtype = dtype or self._torch().float64
+        return self._get_tensor("b", out, dtype, first_row, n_rows)
+
+    def assemble_rhs_tensor(self, gx, gy, constraint):
+        """assemble_rhs from float32 H x W x channels tensors; constraint: one int per channel (host)."""
+        torch = self._torch()
+        a, _ = self._hwc(gx, "gx", (torch.float32,))
+        b, _ = self._hwc(gy, "gy", (torch.float32,))
+        cons = _i32(constraint)
+        if cons.size != self.C:
+            raise ValueError(f"constraint must hold {self.C} values")
+        self._on_stream(lambda: self.L.ccp_grid_assemble_rhs_device(self.h, C.byref(a), C.byref(b), _ptr(cons)),
+                        "ccp_grid_assemble_rhs_device")
+
+    def assemble_from_images_tensor(self, images, label, init_x: bool = False):
+        """assemble_from_images from a u8 N x H x W x 3 tensor (a list of H x W x 3 tensors is stacked into one,
+        which costs a copy) and a u8 H x W label tensor.  Synchronises: the labels are checked on the device first."""
+        torch = self._torch()
+        if isinstance(images, (list, tuple)):
+            images = torch.stack(list(images))
+        if not isinstance(images, torch.Tensor) or images.dim() != 4:
+            raise ValueError("images must be an N x H x W x 3 tensor")
+        n = images.shape[0]
+        arr, _ = self._hwc(images[0], "images", (torch.uint8,))
+        arr.stride_n = images.stride(0)
+        if not 1 <= n <= 256 or images.stride(0) < 0:
+            raise ValueError("images must hold 1 to 256 images")
+        if label.dim() == 2:
+            label = label.unsqueeze(-1)
+        if tuple(label.shape) != (self.H, self.W, 1):
+            raise ValueError(f"label must be {self.H} x {self.W}")
+        lab = DeviceArray(*self._label_array(label))
+        self._on_stream(lambda: self.L.ccp_grid_assemble_from_images_device(self.h, C.byref(arr), n, C.byref(lab), 1 if init_x else 0),
+                        "ccp_grid_assemble_from_images_device")
+
+    def _label_array(self, label):
+        torch = self._torch()
+        if label.device.type != "cuda" or label.device.index != self.desc.device:
+            raise ValueError(f"label must be on cuda:{self.desc.device}, not {label.device}")
+        if label.dtype != torch.uint8:
+            raise ValueError(f"label must have dtype torch.uint8, not {label.dtype}")
+        if any(s < 0 for s in label.stride()):
+            raise ValueError("label has a negative stride")
+        sy, sx, sc = label.stride()
+        return label.data_ptr(), DTYPE_U8, 0, 0, sy, sx, sc
+
+    def store_u8_tensor(self, out=None):
+        """store_u8 into a u8 H x W x channels tensor (allocated when `out` is None)."""
+        torch = self._torch()
+        if out is None:
+            with torch.cuda.device(self._device()):
+                out = torch.empty((self.H, self.W, self.C), dtype=torch.uint8, device=self._device())
+        arr, _ = self._hwc(out, "out", (torch.uint8,), output=True)
+        self._on_stream(lambda: self.L.ccp_grid_store_u8_device(self.h, C.byref(arr)), "ccp_grid_store_u8_device")
+        return out
+
+    def set_x_u8_tensor(self, image):
+        torch = self._torch()
+        arr, _ = self._hwc(image, "image", (torch.uint8,))
+        self._on_stream(lambda: self.L.ccp_grid_set_x_u8_device(self.h, C.byref(arr)), "ccp_grid_set_x_u8_device")
+
+    def assemble_region_rhs_tensor(self, gx, gy, canvas, init_x: bool = False):
+        """assemble_region_rhs from whole-canvas tensors: gx, gy float32, canvas u8, H x W x channels."""
+        torch = self._torch()
+        a, _ = self._hwc(gx, "gx", (torch.float32,))
+        b, _ = self._hwc(gy, "gy", (torch.float32,))
+        c, _ = self._hwc(canvas, "canvas", (torch.uint8,))
+        self._on_stream(lambda: self.L.ccp_grid_assemble_region_rhs_device(self.h, C.byref(a), C.byref(b), C.byref(c), 1 if init_x else 0),
+                        "ccp_grid_assemble_region_rhs_device")
+
+    def assemble_clone_tensor(self, source, target, mixed: bool = False, init: int = 1):
+        torch = self._torch()
+        s_, _ = self._hwc(source, "source", (torch.uint8,))
+        t_, _ = self._hwc(target, "target", (torch.uint8,))
+        self._on_stream(lambda: self.L.ccp_grid_assemble_clone_device(self.h, C.byref(s_), C.byref(t_),
+                                                                      CLONE_MIXED if mixed else CLONE_IMPORT, int(init)),
+                        "ccp_grid_assemble_clone_device")
+
+    def store_u8_composite_tensor(self, canvas, out=None):
+        """The composite into a u8 H x W x channels tensor (allocated, zero-filled, when `out` is None); on a row block
+        only the owned rows are written."""
+        torch = self._torch()
+        c, _ = self._hwc(canvas, "canvas", (torch.uint8,))
+        if out is None:
+            with torch.cuda.device(self._device()):
+                out = torch.zeros((self.H, self.W, self.C), dtype=torch.uint8, device=self._device())
+        o, _ = self._hwc(out, "out", (torch.uint8,), output=True)
+        self._on_stream(lambda: self.L.ccp_grid_store_u8_composite_device(self.h, C.byref(c), C.byref(o)),
+                        "ccp_grid_store_u8_composite_device")
         return out
 
     def region_begin(self):

@@ -101,6 +101,7 @@ struct ccp_grid {
     DevBuf<double> partial;      // per-block partial sums (L1 step / residual / checksums)
     long partial_region = 0;     // doubles per colour region of `partial` (L1 step)
     DevBuf<double> small;        // 4*kMaxChannels doubles of reduced results
+    DevBuf<unsigned> io_bad;     // ccp_grid_assemble_from_images_device: set when a label selects no image
     DevBuf<double> sweep_sums;   // row blocks: step sums of every sweep of a checked pass (kFusedMaxCheckedT * kMaxChannels)
     DevBuf<SolveState> state;
     DevBuf<int> redo_mask;       // per-channel flags for re-running one channel of a checked pass
@@ -930,6 +931,7 @@ try {
     g->partial_region = (long)(part / 2);
     if (st == CCP_OK) st = g->partial.alloc(part);
     if (st == CCP_OK) st = g->small.alloc(4 * kMaxChannels);
+    if (st == CCP_OK) st = g->io_bad.alloc(1);
     if (st == CCP_OK) st = g->state.alloc(1);
     g->stage_rows = std::max<long>(1, std::min<long>(geo.local_rows, (8L << 20) / d->width));
     if (st == CCP_OK) st = g->stage.alloc((size_t)g->stage_rows * d->width);
@@ -2107,7 +2109,9 @@ try {
     }
     CCP_HIP(hipMemcpyAsync(dcons.p, constraint, sizeof(int) * C, hipMemcpyHostToDevice, g->stream));
     dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
-    hipLaunchKernelGGL(k_assemble_rhs, grid, dim3(kBlock), 0, g->stream, g->b.p, g->geom, dgx.p, dgy.p, C, dcons.p);
+    const Packed<const float> pgx{dgx.p, 0, (long)W * C, C, 0}, pgy{dgy.p, 0, (long)W * C, C, 0};
+    hipLaunchKernelGGL((k_assemble_rhs<Packed<const float>, const int *>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->geom, pgx, pgy,
+                       (const int *)dcons.p);
     CCP_HIP(hipGetLastError());
     CCP_HIP(hipStreamSynchronize(g->stream));
     return CCP_OK;
@@ -2139,10 +2143,12 @@ try {
     CCP_HIP(hipMemcpy2DAsync(dlab.p, (size_t)W, label, (size_t)label_stride_bytes, (size_t)W, (size_t)H,
                              hipMemcpyHostToDevice, g->stream));
     dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, 3);
+    using PI = Packed<const uint8_t>;
+    const PI pimg{dimg.p, (long)plane, (long)W * 3, 3, 0}, plab{dlab.p, 0, (long)W, 1, 0};
     if (init_x_from_composite)
-        hipLaunchKernelGGL((k_assemble_from_images<true>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, dimg.p, dlab.p);
+        hipLaunchKernelGGL((k_assemble_from_images<true, PI, PI>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, pimg, plab);
     else
-        hipLaunchKernelGGL((k_assemble_from_images<false>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, dimg.p, dlab.p);
+        hipLaunchKernelGGL((k_assemble_from_images<false, PI, PI>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, pimg, plab);
     CCP_HIP(hipGetLastError());
     CCP_HIP(hipStreamSynchronize(g->stream));
     return CCP_OK;
@@ -2158,7 +2164,8 @@ try {
     DevBuf<uint8_t> d;
     CCP_TRY(d.alloc((size_t)W * H * C));
     dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
-    hipLaunchKernelGGL(k_store_u8, grid, dim3(kBlock), 0, g->stream, g->x.p, g->geom, d.p, C);
+    hipLaunchKernelGGL((k_store_u8<Packed<uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->geom,
+                       Packed<uint8_t>{d.p, 0, (long)W * C, C, 0});
     CCP_HIP(hipGetLastError());
     CCP_HIP(hipMemcpy2DAsync(out, (size_t)row_stride_bytes, d.p, (size_t)W * C, (size_t)W * C, (size_t)H, hipMemcpyDeviceToHost, g->stream));
     CCP_HIP(hipStreamSynchronize(g->stream));
@@ -2176,7 +2183,8 @@ try {
     CCP_TRY(d.alloc((size_t)W * H * C));
     CCP_HIP(hipMemcpy2DAsync(d.p, (size_t)W * C, image, (size_t)row_stride_bytes, (size_t)W * C, (size_t)H, hipMemcpyHostToDevice, g->stream));
     dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
-    hipLaunchKernelGGL(k_load_u8, grid, dim3(kBlock), 0, g->stream, g->x.p, g->geom, d.p, C);
+    hipLaunchKernelGGL((k_load_u8<Packed<const uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->geom,
+                       Packed<const uint8_t>{d.p, 0, (long)W * C, C, 0});
     CCP_HIP(hipGetLastError());
     CCP_TRY(zero_unmasked(g, g->x.p));
     CCP_HIP(hipStreamSynchronize(g->stream));
@@ -2253,12 +2261,17 @@ try {
     CCP_TRY(upload_window(g, dgy, gy, field_stride_bytes, ya, yb));
     CCP_TRY(upload_window(g, dcan, canvas, canvas_stride_bytes, ya, yb));
     dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->geom.local_rows);
+    using PF = Packed<const float>;
+    using PU = Packed<const uint8_t>;
+    const long row = (long)W * C;
+    const PF pgx{dgx.p, 0, row, C, ya}, pgy{dgy.p, 0, row, C, ya};
+    const PU pcan{dcan.p, 0, row, C, ya};
     if (init_x_from_canvas)
-        hipLaunchKernelGGL((k_blend_field_rhs<true>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), dgx.p, dgy.p,
-                           dcan.p, ya, C);
+        hipLaunchKernelGGL((k_blend_field_rhs<true, PF, PU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), pgx, pgy,
+                           pcan, C);
     else
-        hipLaunchKernelGGL((k_blend_field_rhs<false>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), dgx.p, dgy.p,
-                           dcan.p, ya, C);
+        hipLaunchKernelGGL((k_blend_field_rhs<false, PF, PU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), pgx, pgy,
+                           pcan, C);
     CCP_HIP(hipGetLastError());
     CCP_HIP(hipStreamSynchronize(g->stream));
     if (init_x_from_canvas) g->half_sweeps_since_refresh = 0;   // x is exact on every local row
@@ -2284,12 +2297,14 @@ try {
     CCP_TRY(upload_window(g, dsrc, source, source_stride_bytes, ya, yb));
     CCP_TRY(upload_window(g, dtgt, target, target_stride_bytes, ya, yb));
     dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->geom.local_rows);
+    using PU = Packed<const uint8_t>;
+    const PU psrc{dsrc.p, 0, (long)W * C, C, ya}, ptgt{dtgt.p, 0, (long)W * C, C, ya};
     if (mode == CCP_CLONE_MIXED)
-        hipLaunchKernelGGL((k_blend_clone_rhs<true>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), dsrc.p, dtgt.p,
-                           ya, C, (int)init);
+        hipLaunchKernelGGL((k_blend_clone_rhs<true, PU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), psrc, ptgt,
+                           C, (int)init);
     else
-        hipLaunchKernelGGL((k_blend_clone_rhs<false>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), dsrc.p, dtgt.p,
-                           ya, C, (int)init);
+        hipLaunchKernelGGL((k_blend_clone_rhs<false, PU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), psrc, ptgt,
+                           C, (int)init);
     CCP_HIP(hipGetLastError());
     CCP_HIP(hipStreamSynchronize(g->stream));
     if (init) g->half_sweeps_since_refresh = 0;
@@ -2309,7 +2324,9 @@ try {
     CCP_TRY(upload_window(g, dcan, canvas, canvas_stride_bytes, y_lo, y_lo + rows));
     CCP_TRY(dout.alloc((size_t)rows * W * C));
     dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)rows);
-    hipLaunchKernelGGL(k_blend_composite, grid, dim3(kBlock), 0, g->stream, g->x.p, blend_mask(g), dcan.p, dout.p, C);
+    hipLaunchKernelGGL((k_blend_composite<Packed<const uint8_t>, Packed<uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p,
+                       blend_mask(g), Packed<const uint8_t>{dcan.p, 0, (long)W * C, C, y_lo}, Packed<uint8_t>{dout.p, 0, (long)W * C, C, y_lo},
+                       C);
     CCP_HIP(hipGetLastError());
     CCP_HIP(hipMemcpy2DAsync(out + (size_t)y_lo * (size_t)out_stride_bytes, (size_t)out_stride_bytes, dout.p, (size_t)W * C,
                              (size_t)W * C, (size_t)rows, hipMemcpyDeviceToHost, g->stream));
@@ -2803,6 +2820,334 @@ try {
     if (milliseconds) *milliseconds = g->last_ms;
     if (kernel_launches) *kernel_launches = g->last_launches;
     return CCP_OK;
+} CCP_ABI_CATCH
+
+}  // extern "C"
+
+// ============================================================================================
+// Device hand-off (include/ccp_gs.h, ccp_grid_*_device): the host twins' kernels read through strided views
+// (ccp_grid_io.hpp) of the caller's device arrays; nothing is staged, allocated or waited for.
+// ============================================================================================
+namespace {
+
+size_t dtype_bytes(int dtype) { return dtype == CCP_DTYPE_U8 ? 1 : dtype == CCP_DTYPE_F32 ? 4 : dtype == CCP_DTYPE_F64 ? 8 : 0; }
+
+// Refusals of a view with extents (n, y, x, c), checked on the host before anything is enqueued.  `dtypes`: bit
+// (1 << CCP_DTYPE_*) of every accepted dtype.  An output must not have two elements at one address.
+int check_view(const ccp_grid *g, const ccp_device_array *a, unsigned dtypes, bool output, long n, long y, long x, long c)
+{
+    if (!a || !a->data || a->reserved != 0) return CCP_ERR_BAD_ARG;
+    if (a->dtype < 0 || a->dtype > 31 || !(dtypes & (1u << a->dtype))) return CCP_ERR_BAD_ARG;
+    const long ext[4] = {n, y, x, c};
+    const long str[4] = {(long)a->stride_n, (long)a->stride_y, (long)a->stride_x, (long)a->stride_c};
+    for (int k = 0; k < 4; ++k)
+        if (str[k] < 0 || ext[k] < 0) return CCP_ERR_BAD_ARG;
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, a->data) != hipSuccess) {
+        (void)hipGetLastError();                            // pageable host memory: not a runtime allocation
+        return CCP_ERR_BAD_ARG;
+    }
+    if (attr.type != hipMemoryTypeDevice || attr.isManaged || attr.device != g->desc.device) return CCP_ERR_BAD_ARG;
+    if (n == 0 || y == 0 || x == 0 || c == 0) return CCP_OK;
+    const size_t es = dtype_bytes(a->dtype);
+    unsigned long long last = 0;                            // element offset of the last element
+    for (int k = 0; k < 4; ++k) last += (unsigned long long)(ext[k] - 1) * (unsigned long long)str[k];
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(a->data)) != hipSuccess) {
+        (void)hipGetLastError();
+        return CCP_ERR_BAD_ARG;
+    }
+    const unsigned long long lo = (unsigned long long)(uintptr_t)a->data, b0 = (unsigned long long)(uintptr_t)base;
+    if (lo < b0 || lo - b0 + (last + 1) * es > size) return CCP_ERR_BAD_ARG;
+    if (output) {
+        // sorted by stride, each stride >= stride * extent of the one below (dimensions of extent 1 do not count)
+        long s_[4], e_[4];
+        int m = 0;
+        for (int k = 0; k < 4; ++k)
+            if (ext[k] > 1) {
+                s_[m] = str[k];
+                e_[m] = ext[k];
+                ++m;
+            }
+        for (int i = 1; i < m; ++i)
+            for (int k = i; k > 0 && s_[k] < s_[k - 1]; --k) {
+                std::swap(s_[k], s_[k - 1]);
+                std::swap(e_[k], e_[k - 1]);
+            }
+        for (int i = 0; i < m; ++i)
+            if (s_[i] < (i ? s_[i - 1] * e_[i - 1] : 1)) return CCP_ERR_BAD_ARG;
+    }
+    return CCP_OK;
+}
+
+template <typename T>
+View<T> view_of(const ccp_device_array *a)
+{
+    return View<T>{static_cast<T *>(const_cast<void *>(a->data)), (long)a->stride_n, (long)a->stride_y, (long)a->stride_x,
+                   (long)a->stride_c};
+}
+
+// Which gather / scatter form a view of W x C rows allows: the vector forms need every pair 2-element aligned.
+int io_kind(const ccp_device_array *a, int C)
+{
+    const size_t es = dtype_bytes(a->dtype);
+    const bool rows_even = a->stride_y % 2 == 0 && (uintptr_t)a->data % (2 * es) == 0;
+    if (C == 3 && a->stride_c == 1 && a->stride_x == 3 && rows_even) return kRgb;
+    if (a->stride_x == 1 && rows_even && (C == 1 || a->stride_c % 2 == 0)) return kPairs;
+    return kGeneral;
+}
+
+int io_rows(const ccp_grid *g, int first_row, int n_rows)
+{
+    if (n_rows < 0 || first_row < g->geom.y0 || (long)first_row + n_rows > (long)g->geom.y0 + g->geom.local_rows) return CCP_ERR_BAD_ARG;
+    return CCP_OK;
+}
+
+dim3 io_grid(const ccp_grid *g, int n_rows) { return dim3((unsigned)(((g->desc.width + 1) / 2 + kBlock - 1) / kBlock), (unsigned)n_rows); }
+
+template <typename T, bool MASKED>
+int launch_scatter(ccp_grid *g, double *dst, const ccp_device_array *a, int first_row, int n_rows)
+{
+    const View<const T> v = view_of<const T>(a);
+    const int C = g->desc.channels;
+    const dim3 grid = io_grid(g, n_rows);
+    switch (io_kind(a, C)) {
+    case kRgb:
+        hipLaunchKernelGGL((k_io_scatter<kRgb, MASKED, T>), grid, dim3(kBlock), 0, g->stream, dst, v, g->maskp.p, g->geom, first_row, C);
+        break;
+    case kPairs:
+        hipLaunchKernelGGL((k_io_scatter<kPairs, MASKED, T>), grid, dim3(kBlock), 0, g->stream, dst, v, g->maskp.p, g->geom, first_row, C);
+        break;
+    default:
+        hipLaunchKernelGGL((k_io_scatter<kGeneral, MASKED, T>), grid, dim3(kBlock), 0, g->stream, dst, v, g->maskp.p, g->geom, first_row, C);
+    }
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+template <typename T>
+int launch_gather(ccp_grid *g, const double *src, const ccp_device_array *a, int first_row, int n_rows)
+{
+    const View<T> v = view_of<T>(a);
+    const int C = g->desc.channels;
+    const dim3 grid = io_grid(g, n_rows);
+    switch (io_kind(a, C)) {
+    case kRgb:
+        hipLaunchKernelGGL((k_io_gather<kRgb, T>), grid, dim3(kBlock), 0, g->stream, src, v, g->geom, first_row, C);
+        break;
+    case kPairs:
+        hipLaunchKernelGGL((k_io_gather<kPairs, T>), grid, dim3(kBlock), 0, g->stream, src, v, g->geom, first_row, C);
+        break;
+    default:
+        hipLaunchKernelGGL((k_io_gather<kGeneral, T>), grid, dim3(kBlock), 0, g->stream, src, v, g->geom, first_row, C);
+    }
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+constexpr unsigned kF32F64 = (1u << CCP_DTYPE_F32) | (1u << CCP_DTYPE_F64);
+constexpr unsigned kF32 = 1u << CCP_DTYPE_F32;
+constexpr unsigned kU8 = 1u << CCP_DTYPE_U8;
+
+int set_device(ccp_grid *g, double *dst, const ccp_device_array *a, int first_row, int n_rows)
+{
+    CCP_TRY(bind(g));
+    CCP_TRY(io_rows(g, first_row, n_rows));
+    CCP_TRY(check_view(g, a, kF32F64, false, 1, n_rows, g->desc.width, g->desc.channels));
+    if (n_rows == 0) return edge_timeout_status(g);
+    int st;
+    if (a->dtype == CCP_DTYPE_F64)
+        st = g->masked ? launch_scatter<double, true>(g, dst, a, first_row, n_rows) : launch_scatter<double, false>(g, dst, a, first_row, n_rows);
+    else
+        st = g->masked ? launch_scatter<float, true>(g, dst, a, first_row, n_rows) : launch_scatter<float, false>(g, dst, a, first_row, n_rows);
+    CCP_TRY(st);
+    return edge_timeout_status(g);
+}
+
+int get_device(ccp_grid *g, const double *src, const ccp_device_array *a, int first_row, int n_rows)
+{
+    CCP_TRY(bind(g));
+    CCP_TRY(io_rows(g, first_row, n_rows));
+    CCP_TRY(check_view(g, a, kF32F64, true, 1, n_rows, g->desc.width, g->desc.channels));
+    if (n_rows == 0) return edge_timeout_status(g);
+    CCP_TRY(a->dtype == CCP_DTYPE_F64 ? launch_gather<double>(g, src, a, first_row, n_rows) : launch_gather<float>(g, src, a, first_row, n_rows));
+    return edge_timeout_status(g);
+}
+
+bool single_block(const ccp_grid *g) { return !(g->ghost_top || g->ghost_bottom || g->desc.row_count != g->desc.height); }
+
+}  // namespace
+
+extern "C" {
+
+int ccp_grid_set_b_device(ccp_grid *g, const ccp_device_array *rows, int32_t first_row, int32_t n_rows)
+try {
+    if (!g) return CCP_ERR_BAD_ARG;
+    return set_device(g, g->b.p, rows, first_row, n_rows);
+} CCP_ABI_CATCH
+
+int ccp_grid_set_x_device(ccp_grid *g, const ccp_device_array *rows, int32_t first_row, int32_t n_rows)
+try {
+    if (!g) return CCP_ERR_BAD_ARG;
+    return set_device(g, g->x.p, rows, first_row, n_rows);
+} CCP_ABI_CATCH
+
+int ccp_grid_get_x_device(ccp_grid *g, const ccp_device_array *rows, int32_t first_row, int32_t n_rows)
+try {
+    if (!g) return CCP_ERR_BAD_ARG;
+    return get_device(g, g->x.p, rows, first_row, n_rows);
+} CCP_ABI_CATCH
+
+int ccp_grid_get_b_device(ccp_grid *g, const ccp_device_array *rows, int32_t first_row, int32_t n_rows)
+try {
+    if (!g) return CCP_ERR_BAD_ARG;
+    return get_device(g, g->b.p, rows, first_row, n_rows);
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const int32_t *constraint)
+try {
+    CCP_TRY(bind(g));
+    if (!gx || !gy || !constraint) return CCP_ERR_BAD_ARG;
+    if (g->masked) return CCP_ERR_UNSUPPORTED;
+    if (!single_block(g)) return CCP_ERR_STATE;
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    CCP_TRY(check_view(g, gx, kF32, false, 1, H, W, C));
+    CCP_TRY(check_view(g, gy, kF32, false, 1, H, W, C));
+    Pins pins{};
+    for (int ch = 0; ch < C; ++ch) pins.v[ch] = constraint[ch];
+    using VF = View<const float>;
+    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
+    hipLaunchKernelGGL((k_assemble_rhs<VF, Pins>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->geom, view_of<const float>(gx),
+                       view_of<const float>(gy), pins);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_from_images_device(ccp_grid *g, const ccp_device_array *images, int32_t n_images,
+                                         const ccp_device_array *label, int32_t init_x_from_composite)
+try {
+    CCP_TRY(bind(g));
+    if (!images || !label || n_images < 1 || n_images > 256) return CCP_ERR_BAD_ARG;
+    if (g->desc.channels != 3 || g->masked) return CCP_ERR_UNSUPPORTED;
+    if (!single_block(g)) return CCP_ERR_STATE;
+    const int W = g->desc.width, H = g->desc.height;
+    CCP_TRY(check_view(g, images, kU8, false, n_images, H, W, 3));
+    CCP_TRY(check_view(g, label, kU8, false, 1, H, W, 1));
+    using VU = View<const uint8_t>;
+    const VU img = view_of<const uint8_t>(images), lab = view_of<const uint8_t>(label);
+    // labels must select existing images: checked on the device before any image is read
+    unsigned bad = 0;
+    CCP_HIP(hipMemsetAsync(g->io_bad.p, 0, sizeof(unsigned), g->stream));
+    const long blocks = std::min<long>(2048, ((long)W * H + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_io_label_check, dim3((unsigned)blocks), dim3(kBlock), 0, g->stream, lab, W, H, (int)n_images, g->io_bad.p);
+    CCP_HIP(hipGetLastError());
+    CCP_HIP(hipMemcpyAsync(&bad, g->io_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    if (bad) return CCP_ERR_BAD_ARG;
+    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, 3);
+    if (init_x_from_composite)
+        hipLaunchKernelGGL((k_assemble_from_images<true, VU, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, img, lab);
+    else
+        hipLaunchKernelGGL((k_assemble_from_images<false, VU, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, img, lab);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_store_u8_device(ccp_grid *g, const ccp_device_array *out)
+try {
+    CCP_TRY(bind(g));
+    if (!out) return CCP_ERR_BAD_ARG;
+    if (!single_block(g)) return CCP_ERR_STATE;
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    CCP_TRY(check_view(g, out, kU8, true, 1, H, W, C));
+    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
+    hipLaunchKernelGGL((k_store_u8<View<uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->geom, view_of<uint8_t>(out));
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_set_x_u8_device(ccp_grid *g, const ccp_device_array *image)
+try {
+    CCP_TRY(bind(g));
+    if (!image) return CCP_ERR_BAD_ARG;
+    if (!single_block(g)) return CCP_ERR_STATE;
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    CCP_TRY(check_view(g, image, kU8, false, 1, H, W, C));
+    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
+    hipLaunchKernelGGL((k_load_u8<View<const uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->geom, view_of<const uint8_t>(image));
+    CCP_HIP(hipGetLastError());
+    return zero_unmasked(g, g->x.p);
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_region_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy,
+                                        const ccp_device_array *canvas, int32_t init_x_from_canvas)
+try {
+    CCP_TRY(bind(g));
+    if (!gx || !gy || !canvas) return CCP_ERR_BAD_ARG;
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    CCP_TRY(check_view(g, gx, kF32, false, 1, H, W, C));
+    CCP_TRY(check_view(g, gy, kF32, false, 1, H, W, C));
+    CCP_TRY(check_view(g, canvas, kU8, false, 1, H, W, C));
+    if (!g->masked) return CCP_ERR_UNSUPPORTED;
+    if (!g->mask_edge_known) return CCP_ERR_STATE;
+    using VF = View<const float>;
+    using VU = View<const uint8_t>;
+    const VF vgx = view_of<const float>(gx), vgy = view_of<const float>(gy);
+    const VU vcan = view_of<const uint8_t>(canvas);
+    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->geom.local_rows);
+    if (init_x_from_canvas)
+        hipLaunchKernelGGL((k_blend_field_rhs<true, VF, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), vgx, vgy,
+                           vcan, C);
+    else
+        hipLaunchKernelGGL((k_blend_field_rhs<false, VF, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), vgx, vgy,
+                           vcan, C);
+    CCP_HIP(hipGetLastError());
+    if (init_x_from_canvas) g->half_sweeps_since_refresh = 0;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_clone_device(ccp_grid *g, const ccp_device_array *source, const ccp_device_array *target, int32_t mode,
+                                   int32_t init)
+try {
+    CCP_TRY(bind(g));
+    if (!source || !target) return CCP_ERR_BAD_ARG;
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    CCP_TRY(check_view(g, source, kU8, false, 1, H, W, C));
+    CCP_TRY(check_view(g, target, kU8, false, 1, H, W, C));
+    if ((mode != CCP_CLONE_IMPORT && mode != CCP_CLONE_MIXED) || init < 0 || init > 2) return CCP_ERR_BAD_ARG;
+    if (!g->masked) return CCP_ERR_UNSUPPORTED;
+    if (!g->mask_edge_known) return CCP_ERR_STATE;
+    bool touches = false;
+    CCP_TRY(blend_border(g, &touches));
+    if (touches) return CCP_ERR_UNSUPPORTED;
+    using VU = View<const uint8_t>;
+    const VU vsrc = view_of<const uint8_t>(source), vtgt = view_of<const uint8_t>(target);
+    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->geom.local_rows);
+    if (mode == CCP_CLONE_MIXED)
+        hipLaunchKernelGGL((k_blend_clone_rhs<true, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), vsrc, vtgt, C,
+                           (int)init);
+    else
+        hipLaunchKernelGGL((k_blend_clone_rhs<false, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), vsrc, vtgt, C,
+                           (int)init);
+    CCP_HIP(hipGetLastError());
+    if (init) g->half_sweeps_since_refresh = 0;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_store_u8_composite_device(ccp_grid *g, const ccp_device_array *canvas, const ccp_device_array *out)
+try {
+    CCP_TRY(bind(g));
+    if (!canvas || !out) return CCP_ERR_BAD_ARG;
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    CCP_TRY(check_view(g, canvas, kU8, false, 1, H, W, C));
+    CCP_TRY(check_view(g, out, kU8, true, 1, H, W, C));
+    if (!g->masked) return CCP_ERR_UNSUPPORTED;
+    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->desc.row_count);
+    hipLaunchKernelGGL((k_blend_composite<View<const uint8_t>, View<uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p, blend_mask(g),
+                       view_of<const uint8_t>(canvas), view_of<uint8_t>(out), C);
+    CCP_HIP(hipGetLastError());
+    return edge_timeout_status(g);
 } CCP_ABI_CATCH
 
 }  // extern "C"

@@ -3,13 +3,15 @@
 // (ccp_grid_assemble_region_rhs, ccp_grid_assemble_clone, ccp_grid_store_u8_composite).
 //
 // One thread per pixel of a local row; the channels are a loop inside the thread, so the mask and the
-// neighbour rows' region bytes are read once per pixel whatever the channel count.  Inputs are interleaved
-// W x C rows of a row WINDOW of the canvas: window row 0 is image row `ya` (the local rows plus one row above
-// and one below where they exist).  Region membership of a pixel comes from the split mask (`mask`, the
+// neighbour rows' region bytes are read once per pixel whatever the channel count.  Images are read through
+// accessors (ccp_grid_io.hpp) indexed by IMAGE row: the host entry points stage a row window of the canvas (the
+// local rows plus one row above and one below where they exist), the _device twins read the caller's whole-canvas
+// strided views and touch the same rows.  Region membership of a pixel comes from the split mask (`mask`, the
 // layout of x) on local rows and from `edge` (2 x W bytes: image row y0-1, then image row y0+local_rows;
 // zero where the row does not exist) one row beyond them.
 #pragma once
 
+#include "ccp_grid_io.hpp"
 #include "ccp_grid_stencil.hpp"
 
 #include <cstdint>
@@ -36,10 +38,9 @@ struct BlendMask {
 //     b = t + o
 // b = 0 outside the region.  INIT: x := canvas inside the region, 0 outside.
 // grid = (ceil(W / kBlock), local_rows).
-template <bool INIT>
+template <bool INIT, typename F, typename U>
 __global__ void __launch_bounds__(kBlock)
-k_blend_field_rhs(double *__restrict__ b, double *__restrict__ x, BlendMask r, const float *__restrict__ gx,
-                  const float *__restrict__ gy, const uint8_t *__restrict__ canvas, int ya, int C)
+k_blend_field_rhs(double *__restrict__ b, double *__restrict__ x, BlendMask r, F gx, F gy, U canvas, int C)
 {
     const Geom &g = r.g;
     const int xi = blockIdx.x * kBlock + threadIdx.x;
@@ -58,20 +59,17 @@ k_blend_field_rhs(double *__restrict__ b, double *__restrict__ x, BlendMask r, c
     const bool oS = y + 1 < g.H && !r.at(l + 1, xi);
     const bool oW = xi >= 1 && !r.at(l, xi - 1);
     const bool oE = xi + 1 < g.W && !r.at(l, xi + 1);
-    const long row = (long)g.W * C;
-    const long p0 = (long)(y - ya) * row + (long)xi * C;
     for (int ch = 0; ch < C; ++ch) {
-        const long p = p0 + ch;
-        double t = 0.0 - ((double)gx[p] + (double)gy[p]);
-        if (xi >= 1) t += (double)gx[p - C];
-        if (y >= 1) t += (double)gy[p - row];
+        double t = 0.0 - ((double)gx(y, xi, ch) + (double)gy(y, xi, ch));
+        if (xi >= 1) t += (double)gx(y, xi - 1, ch);
+        if (y >= 1) t += (double)gy(y - 1, xi, ch);
         double o = 0.0;
-        o += oN ? (double)canvas[p - row] : 0.0;
-        o += oS ? (double)canvas[p + row] : 0.0;
-        o += oW ? (double)canvas[p - C] : 0.0;
-        o += oE ? (double)canvas[p + C] : 0.0;
+        o += oN ? (double)canvas(y - 1, xi, ch) : 0.0;
+        o += oS ? (double)canvas(y + 1, xi, ch) : 0.0;
+        o += oW ? (double)canvas(y, xi - 1, ch) : 0.0;
+        o += oE ? (double)canvas(y, xi + 1, ch) : 0.0;
         b[(long)ch * g.ch_stride + at] = t + o;
-        if (INIT) x[(long)ch * g.ch_stride + at] = (double)canvas[p];
+        if (INIT) x[(long)ch * g.ch_stride + at] = (double)canvas(y, xi, ch);
     }
 }
 
@@ -81,10 +79,9 @@ k_blend_field_rhs(double *__restrict__ b, double *__restrict__ x, BlendMask r, c
 // true; ties take the source).  Integers throughout: exact in any order.  The host has checked that the region
 // does not touch the canvas's outer rows or columns, so every neighbour of a region pixel exists.
 // init: 0 leave x, 1 x := T, 2 x := S inside the region (0 outside).  grid = (ceil(W / kBlock), local_rows).
-template <bool MIXED>
+template <bool MIXED, typename U>
 __global__ void __launch_bounds__(kBlock)
-k_blend_clone_rhs(double *__restrict__ b, double *__restrict__ x, BlendMask r, const uint8_t *__restrict__ src,
-                  const uint8_t *__restrict__ tgt, int ya, int C, int init)
+k_blend_clone_rhs(double *__restrict__ b, double *__restrict__ x, BlendMask r, U src, U tgt, int C, int init)
 {
     const Geom &g = r.g;
     const int xi = blockIdx.x * kBlock + threadIdx.x;
@@ -99,18 +96,15 @@ k_blend_clone_rhs(double *__restrict__ b, double *__restrict__ x, BlendMask r, c
         }
         return;
     }
-    const long row = (long)g.W * C;
     const bool out[4] = {!r.at(l - 1, xi), !r.at(l + 1, xi), !r.at(l, xi - 1), !r.at(l, xi + 1)};
-    const long off[4] = {-row, row, -(long)C, (long)C};
-    const long p0 = (long)(y - ya) * row + (long)xi * C;
+    const int dy[4] = {-1, 1, 0, 0}, dx[4] = {0, 0, -1, 1};
     for (int ch = 0; ch < C; ++ch) {
-        const long p = p0 + ch;
-        const int sp = src[p], tp = tgt[p];
+        const int sp = src(y, xi, ch), tp = tgt(y, xi, ch);
         int acc = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int tq = tgt[p + off[k]];
-            int v = sp - (int)src[p + off[k]];
+            const int tq = tgt(y + dy[k], xi + dx[k], ch);
+            int v = sp - (int)src(y + dy[k], xi + dx[k], ch);
             if (MIXED) {
                 const int vt = tp - tq;
                 v = abs(vt) > abs(v) ? vt : v;
@@ -123,11 +117,10 @@ k_blend_clone_rhs(double *__restrict__ b, double *__restrict__ x, BlendMask r, c
 }
 
 // Composite epilogue over the OWNED rows: out(y,x)[ch] = uchar(max(min(x,255),0)) inside the region,
-// canvas(y,x)[ch] outside.  canvas / out: interleaved W x C rows, row 0 = the first owned row.
-// grid = (ceil(W / kBlock), owned rows).
+// canvas(y,x)[ch] outside.  canvas / out: accessors by image row.  grid = (ceil(W / kBlock), owned rows).
+template <typename U, typename O>
 __global__ void __launch_bounds__(kBlock)
-k_blend_composite(const double *__restrict__ x, BlendMask r, const uint8_t *__restrict__ canvas,
-                  uint8_t *__restrict__ out, int C)
+k_blend_composite(const double *__restrict__ x, BlendMask r, U canvas, O out, int C)
 {
     const Geom &g = r.g;
     const int xi = blockIdx.x * kBlock + threadIdx.x;
@@ -135,15 +128,15 @@ k_blend_composite(const double *__restrict__ x, BlendMask r, const uint8_t *__re
     const int l = g.own_lo + (int)blockIdx.y;
     const long at = row_off(g, l, (xi + g.y0 + l) & 1) + (xi >> 1);
     const bool in = r.mask[at] != 0;
-    const long p0 = ((long)blockIdx.y * g.W + xi) * C;
+    const int y = g.y0 + l;
     for (int ch = 0; ch < C; ++ch) {
         if (in) {
             double v = x[(long)ch * g.ch_stride + at];
             v = v < 255.0 ? v : 255.0;
             v = v > 0.0 ? v : 0.0;
-            out[p0 + ch] = (uint8_t)v;
+            out(y, xi, ch) = (uint8_t)v;
         } else {
-            out[p0 + ch] = canvas[p0 + ch];
+            out(y, xi, ch) = canvas(y, xi, ch);
         }
     }
 }

@@ -1,0 +1,202 @@
+// ccp_grid_io.hpp — device hand-off of a grid handle (include/ccp_gs.h, the ccp_grid_*_device calls): the element
+// accessors the assembly, clone, composite and u8 kernels read through, and the gather / scatter kernels between a
+// strided natural-order view and the split colour layout of x and b.
+//
+// Accessors.  Every image-shaped input or output of a kernel is read as acc(y, x, c) (acc.at(n, y, x, c) for an
+// image stack) with y the IMAGE row.  Packed<T> is the staging layout of the host entry points: interleaved W x C
+// rows of a row window starting at image row `ya` (planes `plane` elements apart); View<T> is a caller's strided
+// array.  The host entry points instantiate the kernels with Packed, the _device twins with View.
+//
+// Gather / scatter.  One lane owns the pixel pair (2j, 2j+1) of one row for every channel: pixel 2j has colour
+// y&1 and pixel 2j+1 colour (y+1)&1, both at half-column j, so a wave writes (or reads) 64 contiguous doubles of
+// each colour half-row.  KIND picks how the natural side is read: kPairs when stride_x == 1 and a pair is one
+// aligned 2-element vector (channel-planar C x H x W, and any C = 1 row), kRgb when the view is interleaved with
+// C == 3 (the 6 values of a pair are contiguous: three 2-element vectors), kGeneral for any other strides.
+#pragma once
+
+#include "ccp_grid_stencil.hpp"
+
+#include <cstdint>
+
+namespace ccp {
+
+template <typename T>
+struct Packed {
+    T *p;
+    long plane;          // elements between images of a stack
+    long row;            // elements per row (W * C)
+    int C;
+    int ya;              // image row of window row 0
+    __device__ __forceinline__ T &operator()(int y, int x, int c) const { return p[(long)(y - ya) * row + (long)x * C + c]; }
+    __device__ __forceinline__ T &at(int n, int y, int x, int c) const
+    {
+        return p[(long)n * plane + (long)(y - ya) * row + (long)x * C + c];
+    }
+};
+
+template <typename T>
+struct View {
+    T *p;
+    long sn, sy, sx, sc; // strides in elements
+    __device__ __forceinline__ T &operator()(int y, int x, int c) const { return p[(long)y * sy + (long)x * sx + (long)c * sc]; }
+    __device__ __forceinline__ T &at(int n, int y, int x, int c) const
+    {
+        return p[(long)n * sn + (long)y * sy + (long)x * sx + (long)c * sc];
+    }
+};
+
+// the pin values of ccp_grid_assemble_rhs_device, passed by value
+struct Pins {
+    int v[kMaxChannels];
+    __device__ __forceinline__ int operator[](int c) const { return v[c]; }
+};
+
+enum IoKind { kGeneral = 0, kPairs = 1, kRgb = 3 };
+
+template <typename T>
+struct Vec2;
+template <>
+struct Vec2<double> { using type = double2; };
+template <>
+struct Vec2<float> { using type = float2; };
+
+// The pair (2j, 2j+1) of channel c in row y: v[0], v[1] (v[1] only when `two`).
+template <int KIND, typename T>
+__device__ __forceinline__ void load_pair(const View<const T> &a, int y, int x0, int c, bool two, T (&v)[2])
+{
+    if (KIND == kPairs && two) {
+        const auto t = *reinterpret_cast<const typename Vec2<T>::type *>(&a(y, x0, c));
+        v[0] = t.x;
+        v[1] = t.y;
+    } else {
+        v[0] = a(y, x0, c);
+        v[1] = two ? a(y, x0 + 1, c) : T(0);
+    }
+}
+
+template <int KIND, typename T>
+__device__ __forceinline__ void store_pair(const View<T> &a, int y, int x0, int c, bool two, const T (&v)[2])
+{
+    if (KIND == kPairs && two) {
+        typename Vec2<T>::type t;
+        t.x = v[0];
+        t.y = v[1];
+        *reinterpret_cast<typename Vec2<T>::type *>(&a(y, x0, c)) = t;
+    } else {
+        a(y, x0, c) = v[0];
+        if (two) a(y, x0 + 1, c) = v[1];
+    }
+}
+
+// Natural -> split for all channels: image rows [first_row, first_row + gridDim.y) from view rows 0.. (array row r =
+// image row first_row + r).  MASKED: pixels outside the region are written 0 (the mask grid's zero_unmasked, fused).
+// grid = (ceil(ceil(W/2) / kBlock), n_rows).
+template <int KIND, bool MASKED, typename T>
+__global__ void __launch_bounds__(kBlock)
+k_io_scatter(double *__restrict__ split, View<const T> in, const unsigned char *__restrict__ mask, Geom g, int first_row, int C)
+{
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    const int r = blockIdx.y;
+    const int x0 = 2 * j;
+    if (x0 >= g.W) return;
+    const bool two = x0 + 1 < g.W;
+    const int y = first_row + r;
+    const int l = y - g.y0;
+    const long at0 = row_off(g, l, y & 1) + j;          // pixel 2j
+    const long at1 = row_off(g, l, (y + 1) & 1) + j;    // pixel 2j+1
+    bool in0 = true, in1 = true;
+    if (MASKED) {
+        in0 = mask[at0] != 0;
+        in1 = two && mask[at1] != 0;
+    }
+    if (KIND == kRgb) {
+        // interleaved, C == 3: the pair's six values are contiguous (2-element aligned when the host chose kRgb)
+        using V2 = typename Vec2<T>::type;
+        T v[6];
+        const T *src = &in(r, x0, 0);
+        if (two) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const V2 t = reinterpret_cast<const V2 *>(src)[k];
+                v[2 * k] = t.x;
+                v[2 * k + 1] = t.y;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[k] = src[k];
+        }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            split[(long)ch * g.ch_stride + at0] = in0 ? (double)v[ch] : 0.0;
+            if (two) split[(long)ch * g.ch_stride + at1] = in1 ? (double)v[3 + ch] : 0.0;
+        }
+        return;
+    }
+    for (int ch = 0; ch < C; ++ch) {
+        T v[2];
+        load_pair<KIND>(in, r, x0, ch, two, v);
+        split[(long)ch * g.ch_stride + at0] = in0 ? (double)v[0] : 0.0;
+        if (two) split[(long)ch * g.ch_stride + at1] = in1 ? (double)v[1] : 0.0;
+    }
+}
+
+// Split -> natural for all channels (T = float rounds to nearest).  grid as k_io_scatter.
+template <int KIND, typename T>
+__global__ void __launch_bounds__(kBlock)
+k_io_gather(const double *__restrict__ split, View<T> out, Geom g, int first_row, int C)
+{
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    const int r = blockIdx.y;
+    const int x0 = 2 * j;
+    if (x0 >= g.W) return;
+    const bool two = x0 + 1 < g.W;
+    const int y = first_row + r;
+    const int l = y - g.y0;
+    const long at0 = row_off(g, l, y & 1) + j;
+    const long at1 = row_off(g, l, (y + 1) & 1) + j;
+    if (KIND == kRgb) {
+        using V2 = typename Vec2<T>::type;
+        T v[6];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            v[ch] = (T)split[(long)ch * g.ch_stride + at0];
+            v[3 + ch] = two ? (T)split[(long)ch * g.ch_stride + at1] : T(0);
+        }
+        T *dst = &out(r, x0, 0);
+        if (two) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                V2 t;
+                t.x = v[2 * k];
+                t.y = v[2 * k + 1];
+                reinterpret_cast<V2 *>(dst)[k] = t;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dst[k] = v[k];
+        }
+        return;
+    }
+    for (int ch = 0; ch < C; ++ch) {
+        T v[2];
+        v[0] = (T)split[(long)ch * g.ch_stride + at0];
+        v[1] = two ? (T)split[(long)ch * g.ch_stride + at1] : T(0);
+        store_pair<KIND>(out, r, x0, ch, two, v);
+    }
+}
+
+// ccp_grid_assemble_from_images_device's guard: *bad := 1 if any label of the H x W view is >= n_images (*bad is
+// cleared on the stream before).  grid-stride over the pixels.
+__global__ void __launch_bounds__(kBlock)
+k_io_label_check(View<const uint8_t> label, int W, int H, int n_images, unsigned *__restrict__ bad)
+{
+    const long n = (long)W * H;
+    bool any = false;
+    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) {
+        const int y = (int)(i / W), x = (int)(i - (long)y * W);
+        any |= label(y, x, 0) >= n_images;
+    }
+    if (any) atomicOr(bad, 1u);
+}
+
+}  // namespace ccp

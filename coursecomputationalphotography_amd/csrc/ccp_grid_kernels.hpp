@@ -17,6 +17,7 @@
 // -ffp-contract=off (no FMA contraction) — the build enforces it.
 #pragma once
 
+#include "ccp_grid_io.hpp"
 #include "ccp_grid_stencil.hpp"
 
 namespace ccp {
@@ -407,22 +408,22 @@ k_randomize(double *__restrict__ x, Geom g, uint64_t seed, double lo, double hi)
 // ---------------------------------------------------------------------------------------------
 // Poisson right-hand side ATb for all channels (PhotoMontage.cpp:563-572,579-581,592), Eigen's
 // row-major sparse*dense accumulation order: gy above, gx left, -gx here, -gy here, pin.
-// gx, gy: packed H x W x C float32 on device.  grid = (ceil(W/kBlock), H, C).
+// gx, gy: H x W x C float32 on device through accessor F (ccp_grid_io.hpp), the pins through PIN (a device
+// array or Pins by value).  grid = (ceil(W/kBlock), H, C).
+template <typename F, typename PIN>
 __global__ void __launch_bounds__(kBlock)
-k_assemble_rhs(double *__restrict__ b, Geom g, const float *__restrict__ gx,
-               const float *__restrict__ gy, int C, const int *__restrict__ constraint)
+k_assemble_rhs(double *__restrict__ b, Geom g, F gx, F gy, PIN constraint)
 {
     const int x = blockIdx.x * kBlock + threadIdx.x;
     const int y = blockIdx.y;
     const int ch = blockIdx.z;
     if (x >= g.W) return;
-    const long px = ((long)y * g.W + x) * C + ch;
     double acc = 0.0;
-    if (y >= 1 && x < g.W - 1) acc += 1.0 * (double)gy[px - (long)g.W * C];
-    if (x >= 1 && y < g.H - 1) acc += 1.0 * (double)gx[px - C];
+    if (y >= 1 && x < g.W - 1) acc += 1.0 * (double)gy(y - 1, x, ch);
+    if (x >= 1 && y < g.H - 1) acc += 1.0 * (double)gx(y, x - 1, ch);
     if (x < g.W - 1 && y < g.H - 1) {
-        acc += -1.0 * (double)gx[px];
-        acc += -1.0 * (double)gy[px];
+        acc += -1.0 * (double)gx(y, x, ch);
+        acc += -1.0 * (double)gy(y, x, ch);
     }
     if ((x | y) == 0) acc += 1.0 * (double)constraint[ch];
     const int l = y - g.y0;
@@ -434,19 +435,18 @@ k_assemble_rhs(double *__restrict__ b, Geom g, const float *__restrict__ gx,
 // GradientAt (:399-408: integer subtraction of the label-selected image, then float) feed the
 // same ATb accumulation as k_assemble_rhs, with the pin value Images[0](0,0)[ch] (:428).
 // INIT: also write the composite image as the start vector (PhotoMontage.cpp:599-610).
-// images: K stacked H x W x 3 u8 images, label: H x W u8.  grid = (ceil(W/kBlock), H, 3).
-template <bool INIT>
+// images: K stacked H x W x 3 u8 images (accessor IMG, image k = img.at(k, ...)), label: H x W u8 (accessor LAB).
+// grid = (ceil(W/kBlock), H, 3).
+template <bool INIT, typename IMG, typename LAB>
 __global__ void __launch_bounds__(kBlock)
-k_assemble_from_images(double *__restrict__ b, double *__restrict__ x, Geom g,
-                       const uint8_t *__restrict__ images, const uint8_t *__restrict__ label)
+k_assemble_from_images(double *__restrict__ b, double *__restrict__ x, Geom g, IMG images, LAB label)
 {
     const int xi = blockIdx.x * kBlock + threadIdx.x;
     const int y = blockIdx.y;
     const int ch = blockIdx.z;
     if (xi >= g.W) return;
-    const long plane = (long)g.W * g.H * 3;
-    auto pix = [&](int k, int yy, int xx) -> int { return (int)images[(long)k * plane + ((long)yy * g.W + xx) * 3 + ch]; };
-    auto lab = [&](int yy, int xx) -> int { return (int)label[(long)yy * g.W + xx]; };
+    auto pix = [&](int k, int yy, int xx) -> int { return (int)images.at(k, yy, xx, ch); };
+    auto lab = [&](int yy, int xx) -> int { return (int)label(yy, xx, 0); };
     double acc = 0.0;
     if (y >= 1 && xi < g.W - 1) {                       // gy(y-1, x) of the cell above
         const int k = lab(y - 1, xi);
@@ -468,9 +468,10 @@ k_assemble_from_images(double *__restrict__ b, double *__restrict__ x, Geom g,
     if (INIT) x[at] = (double)pix(lab(y, xi), y, xi);
 }
 
-// Solve epilogue: out(y,x)[ch] = uchar(max(min(sol,255),0)) (PhotoMontage.cpp:617-626).
+// Solve epilogue: out(y,x)[ch] = uchar(max(min(sol,255),0)) (PhotoMontage.cpp:617-626).  out: accessor OUT.
+template <typename OUT>
 __global__ void __launch_bounds__(kBlock)
-k_store_u8(const double *__restrict__ x, Geom g, uint8_t *__restrict__ out, int C)
+k_store_u8(const double *__restrict__ x, Geom g, OUT out)
 {
     const int xi = blockIdx.x * kBlock + threadIdx.x;
     const int y = blockIdx.y;
@@ -480,12 +481,13 @@ k_store_u8(const double *__restrict__ x, Geom g, uint8_t *__restrict__ out, int 
     double v = x[(long)ch * g.ch_stride + row_off(g, l, (xi + y) & 1) + (xi >> 1)];
     v = v < 255.0 ? v : 255.0;
     v = v > 0.0 ? v : 0.0;
-    out[((long)y * g.W + xi) * C + ch] = (uint8_t)v;
+    out(y, xi, ch) = (uint8_t)v;
 }
 
-// Composite initial guess: x(y,x)[ch] = image(y,x)[ch] (PhotoMontage.cpp:599-610).
+// Composite initial guess: x(y,x)[ch] = image(y,x)[ch] (PhotoMontage.cpp:599-610).  img: accessor IMG.
+template <typename IMG>
 __global__ void __launch_bounds__(kBlock)
-k_load_u8(double *__restrict__ x, Geom g, const uint8_t *__restrict__ img, int C)
+k_load_u8(double *__restrict__ x, Geom g, IMG img)
 {
     const int xi = blockIdx.x * kBlock + threadIdx.x;
     const int y = blockIdx.y;
@@ -493,7 +495,7 @@ k_load_u8(double *__restrict__ x, Geom g, const uint8_t *__restrict__ img, int C
     if (xi >= g.W) return;
     const int l = y - g.y0;
     x[(long)ch * g.ch_stride + row_off(g, l, (xi + y) & 1) + (xi >> 1)] =
-        (double)img[((long)y * g.W + xi) * C + ch];
+        (double)img(y, xi, ch);
 }
 
 }  // namespace ccp

@@ -515,6 +515,62 @@ int ccp_grid_assemble_clone(ccp_grid *g, const uint8_t *source, int64_t source_s
 int ccp_grid_store_u8_composite(ccp_grid *g, const uint8_t *canvas, int64_t canvas_stride_bytes,
                                 uint8_t *out, int64_t out_stride_bytes);
 
+/* ---- Device hand-off: the twins of the host hand-off calls above, on arrays already in device memory ----------------
+ * A ccp_device_array describes a strided view of device memory of the handle's device (a torch tensor, a hipMalloc
+ * buffer).  Element (n, y, x, c) lives at  data + (n*stride_n + y*stride_y + x*stride_x + c*stride_c) elements  of
+ * the dtype's size; n selects an image of a stack (ccp_grid_assemble_from_images_device), y an image row, x a column,
+ * c a channel.  Interleaved H x W x C is (stride_y, stride_x, stride_c) = (W*C, C, 1); planar C x H x W seen as
+ * H x W x C (tensor.permute(1, 2, 0)) is (W, 1, H*W).  Strides are in elements and >= 0; a zero stride on an input
+ * broadcasts.
+ *
+ * Every _device call leaves the handle, or writes its output, bit for bit as its host twin does on the same data, and
+ * has the host twin's state checks (CCP_ERR_UNSUPPORTED / CCP_ERR_STATE) and row semantics.  It is enqueued on the
+ * handle's stream (ccp_grid_set_stream) without host synchronisation and without device allocation; the caller keeps
+ * the arrays alive and unchanged until the stream has passed the call.  One exception synchronises:
+ * ccp_grid_assemble_from_images_device (see there).  Refused with CCP_ERR_BAD_ARG before anything is enqueued: a null
+ * descriptor or data pointer, data that hipPointerGetAttributes does not report as device memory of the handle's
+ * device (pageable host, pinned host and managed memory are refused), a view that reaches beyond the allocation the
+ * runtime reports for `data`, a wrong dtype, a negative stride, reserved != 0, and an OUTPUT view whose elements
+ * overlap (sorted by stride, each stride must be >= stride * extent of the one below). */
+#define CCP_DTYPE_U8 1
+#define CCP_DTYPE_F32 2
+#define CCP_DTYPE_F64 3
+typedef struct ccp_device_array {
+    const void *data;      /* device memory of the handle's device (outputs are written through it)     */
+    int32_t dtype;         /* CCP_DTYPE_U8 | CCP_DTYPE_F32 | CCP_DTYPE_F64                               */
+    int32_t reserved;      /* 0                                                                          */
+    int64_t stride_n, stride_y, stride_x, stride_c;   /* in elements, >= 0                              */
+} ccp_device_array;
+
+/* ccp_grid_set_b_host & co. for ALL channels in one call: `n_rows` image rows from `first_row` (ghost rows allowed,
+ * as the host twins), array row 0 = image row first_row, n_rows x W x channels.  set: F32 or F64 (widened exactly);
+ * on a Dirichlet-mask grid the pixels outside the region are written 0 in the same pass.  get: F64, or F32 rounded
+ * to nearest. */
+int ccp_grid_set_b_device(ccp_grid *g, const ccp_device_array *rows, int32_t first_row, int32_t n_rows);
+int ccp_grid_set_x_device(ccp_grid *g, const ccp_device_array *rows, int32_t first_row, int32_t n_rows);
+int ccp_grid_get_x_device(ccp_grid *g, const ccp_device_array *rows, int32_t first_row, int32_t n_rows);
+int ccp_grid_get_b_device(ccp_grid *g, const ccp_device_array *rows, int32_t first_row, int32_t n_rows);
+/* ccp_grid_assemble_rhs: gx, gy F32 H x W x channels (only y < H-1, x < W-1 are read); constraint stays a host
+ * array of `channels` ints, passed to the kernel by value. */
+int ccp_grid_assemble_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy,
+                                 const int32_t *constraint);
+/* ccp_grid_assemble_from_images: `images` one U8 N x H x W x 3 array (stride_n selects the image), label U8
+ * H x W (stride_c unused).  Every label must be < n_images: checked ON THE DEVICE before any image is read (one
+ * small reduction and a 4-byte read-back), so this call SYNCHRONISES the stream; a bad label returns CCP_ERR_BAD_ARG
+ * with b and x untouched. */
+int ccp_grid_assemble_from_images_device(ccp_grid *g, const ccp_device_array *images, int32_t n_images,
+                                         const ccp_device_array *label, int32_t init_x_from_composite);
+/* ccp_grid_store_u8 into / ccp_grid_set_x_u8 from a U8 H x W x channels array. */
+int ccp_grid_store_u8_device(ccp_grid *g, const ccp_device_array *out);
+int ccp_grid_set_x_u8_device(ccp_grid *g, const ccp_device_array *image);
+/* The region blend calls on whole-canvas H x W x channels arrays (gx, gy F32; canvas, source, target, out U8); a row
+ * block reads only its local rows plus one row on each side, and the composite writes only its owned rows of out. */
+int ccp_grid_assemble_region_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy,
+                                        const ccp_device_array *canvas, int32_t init_x_from_canvas);
+int ccp_grid_assemble_clone_device(ccp_grid *g, const ccp_device_array *source, const ccp_device_array *target,
+                                   int32_t mode, int32_t init);
+int ccp_grid_store_u8_composite_device(ccp_grid *g, const ccp_device_array *canvas, const ccp_device_array *out);
+
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
 int ccp_grid_last_timing(ccp_grid *g, float *milliseconds, int32_t *kernel_launches);
