@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("CCP_GS_LIB") or os.path.join(_HERE, "lib", "libccp_gs
 
 CCP_OK = 0
 GRID_DIRICHLET_MASK = 1
+GRID_WEIGHTED = 2
 ORDER_LEXICOGRAPHIC = 0
 ORDER_MULTICOLOUR = 1
 CLONE_IMPORT = 0
@@ -42,6 +43,7 @@ ABI_SYMBOLS = (
     "ccp_grid_set_b_device", "ccp_grid_set_x_device", "ccp_grid_get_x_device", "ccp_grid_get_b_device",
     "ccp_grid_assemble_rhs_device", "ccp_grid_assemble_from_images_device", "ccp_grid_store_u8_device", "ccp_grid_set_x_u8_device",
     "ccp_grid_assemble_region_rhs_device", "ccp_grid_assemble_clone_device", "ccp_grid_store_u8_composite_device",
+    "ccp_grid_set_weights_host", "ccp_grid_set_weights_device", "ccp_grid_assemble_weighted_rhs", "ccp_grid_assemble_weighted_rhs_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
     "ccp_grid_attach_comm", "ccp_grid_set_overlap", "ccp_grid_exchange_halos", "ccp_grid_sweep_rowblocked",
     "ccp_grid_gauss_seidel_rowblocked", "ccp_grid_conjugate_gradient_rowblocked", "ccp_grid_residual_norm2_global", "ccp_grid_comm_stats",
@@ -221,6 +223,10 @@ def load() -> C.CDLL:
     L.ccp_grid_assemble_region_rhs_device.argtypes = [vp, da, da, da, i32]
     L.ccp_grid_assemble_clone_device.argtypes = [vp, da, da, i32, i32]
     L.ccp_grid_store_u8_composite_device.argtypes = [vp, da, da]
+    L.ccp_grid_set_weights_host.argtypes = [vp, vp, vp, vp, i64]
+    L.ccp_grid_set_weights_device.argtypes = [vp, da, da, da]
+    L.ccp_grid_assemble_weighted_rhs.argtypes = [vp, vp, vp, i64, vp, i64, i32]
+    L.ccp_grid_assemble_weighted_rhs_device.argtypes = [vp, da, da, da, i32]
     L.ccp_grid_last_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i32)]
     L.ccp_grid_region_begin.argtypes = [vp]
     L.ccp_grid_region_end.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i64), C.POINTER(i64)]
@@ -505,12 +511,14 @@ class CsrMatrix:
 class Grid:
     """Structured Poisson grid block (ccp_grid_*)."""
 
-    def __init__(self, width, height, channels=1, row_begin=0, row_count=None, ghost=0, device=0, mask=None):
-        """mask: H x W array (non-zero = unknown) makes this a Dirichlet-mask grid (CCP_GRID_DIRICHLET_MASK)."""
+    def __init__(self, width, height, channels=1, row_begin=0, row_count=None, ghost=0, device=0, mask=None, weighted=False):
+        """mask: H x W array (non-zero = unknown) makes this a Dirichlet-mask grid (CCP_GRID_DIRICHLET_MASK); weighted:
+        a weighted grid (CCP_GRID_WEIGHTED: set_weights, then assemble_weighted_rhs; single blocks, no mask)."""
         self.L = load()
         self.h = C.c_void_p()
         row_count = height if row_count is None else row_count
-        self.desc = GridDesc(width, height, channels, row_begin, row_count, ghost, device, 0 if mask is None else GRID_DIRICHLET_MASK)
+        flags = (0 if mask is None else GRID_DIRICHLET_MASK) | (GRID_WEIGHTED if weighted else 0)
+        self.desc = GridDesc(width, height, channels, row_begin, row_count, ghost, device, flags)
         check(self.L.ccp_grid_create(C.byref(self.desc), C.byref(self.h)), "ccp_grid_create")
         self.layout = GridLayout()
         check(self.L.ccp_grid_get_layout(self.h, C.byref(self.layout)), "ccp_grid_get_layout")
@@ -904,6 +912,67 @@ class Grid:
         self._on_stream(lambda: self.L.ccp_grid_store_u8_composite_device(self.h, C.byref(c), C.byref(o)),
                         "ccp_grid_store_u8_composite_device")
         return out
+
+    # ---- weighted grids (CCP_GRID_WEIGHTED) -----------------------------------------------------------------
+    def _plane(self, a, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != (self.H, self.W):
+            raise ValueError(f"{name} must be {self.H} x {self.W}")
+        return a
+
+    def set_weights(self, wx=None, wy=None, lam=None):
+        """The operator from H x W float32 host arrays: wx weighs the edge (x,y)-(x+1,y), wy the edge (x,y)-(x,y+1), lam
+        the data term; None: wx, wy 1 everywhere, lam 0.  Negative, NaN or inf weights raise CcpError (BAD_ARG) and
+        leave the handle without an operator."""
+        planes = [self._plane(a, n) for a, n in ((wx, "wx"), (wy, "wy"), (lam, "lam"))]
+        stride = 4 * self.W
+        check(self.L.ccp_grid_set_weights_host(self.h, *[_ptr(p) for p in planes], stride), "ccp_grid_set_weights_host")
+
+    def assemble_weighted_rhs(self, gx=None, gy=None, f=None, init_x: bool = False):
+        """b of every channel from float32 H x W x channels host arrays: guidance gx, gy (None: 0) and data f (None: 0);
+        init_x: x := f on live pixels (0 on dead ones)."""
+        gx = None if gx is None else self._canvas_image(gx, np.float32)
+        gy = None if gy is None else self._canvas_image(gy, np.float32)
+        f = None if f is None else self._canvas_image(f, np.float32)
+        row = 4 * self.W * self.C
+        check(self.L.ccp_grid_assemble_weighted_rhs(self.h, _ptr(gx), _ptr(gy), row, _ptr(f), row, 1 if init_x else 0),
+              "ccp_grid_assemble_weighted_rhs")
+
+    def _weight_array(self, t, name):
+        """ccp_device_array of an H x W float32 / float64 tensor (a broadcast view of a scalar is fine), or None."""
+        if t is None:
+            return None
+        torch = self._torch()
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if t.device.type != "cuda" or t.device.index != self.desc.device:
+            raise ValueError(f"{name} must be on cuda:{self.desc.device}, not {t.device}")
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{name} must have dtype torch.float32 or torch.float64, not {t.dtype}")
+        if tuple(t.shape) != (self.H, self.W):
+            raise ValueError(f"{name} must be {self.H} x {self.W}, not {tuple(t.shape)}")
+        if any(s < 0 for s in t.stride()):
+            raise ValueError(f"{name} has a negative stride")
+        sy, sx = t.stride()
+        return DeviceArray(t.data_ptr(), DTYPE_F64 if t.dtype == torch.float64 else DTYPE_F32, 0, 0, sy, sx, 0)
+
+    def set_weights_tensor(self, wx=None, wy=None, lam=None):
+        """set_weights from H x W float32 / float64 tensors (expanded scalars broadcast); synchronises (the verdict)."""
+        arrs = [self._weight_array(t, n) for t, n in ((wx, "wx"), (wy, "wy"), (lam, "lam"))]
+        refs = [None if a is None else C.byref(a) for a in arrs]
+        self._on_stream(lambda: self.L.ccp_grid_set_weights_device(self.h, *refs), "ccp_grid_set_weights_device")
+
+    def assemble_weighted_rhs_tensor(self, gx=None, gy=None, f=None, init_x: bool = False):
+        """assemble_weighted_rhs from H x W x channels tensors: gx, gy float32, f u8, float32 or float64."""
+        torch = self._torch()
+        a = None if gx is None else self._hwc(gx, "gx", (torch.float32,))[0]
+        b = None if gy is None else self._hwc(gy, "gy", (torch.float32,))[0]
+        c = None if f is None else self._hwc(f, "f", (torch.uint8, torch.float32, torch.float64))[0]
+        refs = [None if v is None else C.byref(v) for v in (a, b, c)]
+        self._on_stream(lambda: self.L.ccp_grid_assemble_weighted_rhs_device(self.h, *refs, 1 if init_x else 0),
+                        "ccp_grid_assemble_weighted_rhs_device")
 
     def region_begin(self):
         check(self.L.ccp_grid_region_begin(self.h), "ccp_grid_region_begin")

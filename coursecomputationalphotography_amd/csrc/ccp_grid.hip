@@ -7,6 +7,7 @@
 #include "ccp_grid_cg.hpp"
 #include "ccp_grid_mg_view.hpp"
 #include "ccp_grid_blend.hpp"
+#include "ccp_grid_weighted.hpp"
 #include "ccp_comm.hpp"
 
 #include <algorithm>
@@ -132,9 +133,16 @@ struct ccp_grid {
     int cpt = 2;                 // half-columns per thread of the sweep kernel
     int rows_per_block = 32;
     MgHierarchy *mg = nullptr;   // multigrid hierarchy (ccp_grid_mg.hip), built at the first ccp_grid_mg_* call
+    // Weighted grid (CCP_GRID_WEIGHTED, ccp_grid_weighted.hpp): the level-0 operator in four planes of one channel's layout
+    // (d, we, ws, lambda), valid once ccp_grid_set_weights_* has accepted one (has_op); wpart: the residual's partial sums
+    bool weighted = false;
+    bool has_op = false;
+    DevBuf<double> wop, wpart;
 };
 
 namespace {
+
+constexpr int kWeightedApplyBlocks = 1024;   // blocks per (channel, colour) of k_weighted_apply
 
 // Did a polling kernel give up on the edge flag (see ccp_grid::edge_timeout)?
 int edge_timeout_status(const ccp_grid *g)
@@ -151,6 +159,14 @@ int bind(ccp_grid *g)
     if (!g) return CCP_ERR_BAD_ARG;
     if (hipSetDevice(g->device) != hipSuccess) return CCP_ERR_NO_DEVICE;
     return edge_timeout_status(g);
+}
+
+// The calls a weighted handle refuses (sweeps, Gauss-Seidel, plain CG, tuning, SolveChannel assembly, region blends,
+// masks, row blocks): include/ccp_gs.h, CCP_GRID_WEIGHTED
+int not_weighted(const ccp_grid *g)
+{
+    if (!g) return CCP_ERR_BAD_ARG;
+    return g->weighted ? CCP_ERR_UNSUPPORTED : CCP_OK;
 }
 
 long sweep_blocks_x(const ccp_grid *g) { return (g->geom.pitch + (long)kBlock * g->cpt - 1) / ((long)kBlock * g->cpt); }
@@ -815,6 +831,13 @@ int zero_unmasked(ccp_grid *g, double *plane)
     return CCP_OK;
 }
 
+// k_weighted_apply: up to kWeightedApplyBlocks blocks per (channel, colour) striding over the colour's cells
+dim3 weighted_apply_grid(const ccp_grid *g)
+{
+    const long cells = (long)g->geom.H * ((g->geom.W + 1) / 2);
+    return dim3((unsigned)std::max<long>(1, std::min<long>(kWeightedApplyBlocks, (cells + kBlock - 1) / kBlock)), 1, 2 * (unsigned)g->desc.channels);
+}
+
 int begin_timing(ccp_grid *g)
 {
     g->last_launches = 0;
@@ -875,6 +898,9 @@ try {
     if (d->row_begin < 0 || d->row_count < 1 || d->row_begin + d->row_count > d->height || d->ghost < 0)
         return CCP_ERR_BAD_ARG;
     if ((long)d->width * d->height > 0x7fffffffL) return CCP_ERR_BAD_ARG;   // int32 indices, as the reference
+    if ((d->flags & CCP_GRID_WEIGHTED) &&
+        ((d->flags & CCP_GRID_DIRICHLET_MASK) || d->ghost != 0 || d->row_begin != 0 || d->row_count != d->height))
+        return CCP_ERR_UNSUPPORTED;                                       // weighted grids: single blocks, no mask
     CCP_TRY(select_device(d->device));
     ccp_grid *g = new (std::nothrow) ccp_grid();
     if (!g) return CCP_ERR_ALLOC;
@@ -926,6 +952,12 @@ try {
         if (st == CCP_OK && hipMemset(g->mask_edge.p, 0, 2 * (size_t)d->width) != hipSuccess) st = CCP_ERR_HIP;
     }
     if (st == CCP_OK) st = g->b.alloc(elems);
+    g->weighted = (d->flags & CCP_GRID_WEIGHTED) != 0;
+    if (st == CCP_OK && g->weighted) {
+        st = g->wop.alloc(4 * (size_t)geo.ch_stride);
+        if (st == CCP_OK && hipMemset(g->wop.p, 0, 4 * sizeof(double) * (size_t)geo.ch_stride) != hipSuccess) st = CCP_ERR_HIP;
+        if (st == CCP_OK) st = g->wpart.alloc(4 * (size_t)d->channels * kWeightedApplyBlocks);
+    }
     // partial sums: the finest launch is one block per (x tile, row, channel*2) with 2 doubles
     const size_t part = (size_t)((geo.pitch + 2L * kBlock - 1) / (2L * kBlock)) * geo.local_rows * d->channels * 2 * 2 + 64;
     g->partial_region = (long)(part / 2);
@@ -1052,6 +1084,7 @@ try {
 
 int ccp_grid_set_mask_host(ccp_grid *g, const uint8_t *mask, int64_t row_stride_bytes)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!g->masked) return CCP_ERR_STATE;
     if (!mask || row_stride_bytes < g->desc.width) return CCP_ERR_BAD_ARG;
@@ -1110,6 +1143,13 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     v->x = g->x.p;
     v->b = g->b.p;
     v->mask = g->maskp.p;
+    v->weighted = g->weighted;
+    const double *op = g->weighted && g->has_op ? g->wop.p : nullptr;
+    const long n = g->geom.ch_stride;
+    v->wd = op;
+    v->wwe = op ? op + n : nullptr;
+    v->wws = op ? op + 2 * n : nullptr;
+    v->wlam = op ? op + 3 * n : nullptr;
     v->stream = g->stream;
     v->cache = &g->mg;
     v->comm = g->comm;
@@ -1177,6 +1217,13 @@ try {
 int ccp_grid_b_from_x(ccp_grid *g)
 try {
     CCP_TRY(bind(g));
+    if (g->weighted) {
+        if (!g->has_op) return CCP_ERR_STATE;
+        hipLaunchKernelGGL((k_weighted_apply<0>), weighted_apply_grid(g), dim3(kBlock), 0, g->stream, g->x.p, g->b.p, g->geom, g->wop.p,
+                           g->geom.ch_stride, g->wpart.p);
+        CCP_HIP(hipGetLastError());
+        return CCP_OK;
+    }
     if ((g->shrink_top || g->shrink_bottom) && g->half_sweeps_since_refresh >= g->desc.ghost) return CCP_ERR_STATE;
     const Geom &geo = g->geom;
     // every local row whose neighbour rows are local too: the ghost rows need their b as well
@@ -1202,6 +1249,7 @@ try {
 
 int ccp_grid_sweep(ccp_grid *g, int32_t iterations)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (iterations < 0) return CCP_ERR_BAD_ARG;
     CCP_TRY(begin_timing(g));
@@ -1212,6 +1260,7 @@ try {
 
 int ccp_grid_sweep_edges_first(ccp_grid *g, int32_t iterations, int32_t edge_rows)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (iterations < 0 || edge_rows < 0) return CCP_ERR_BAD_ARG;
     if (!g->edge_flag) return ccp_grid_sweep(g, iterations);          // no neighbour blocks: nothing to hand over early
@@ -1223,12 +1272,14 @@ try {
 
 int ccp_grid_stream_wait_edges(ccp_grid *g, void *hip_stream)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     return edge_wait_on_stream(g, reinterpret_cast<hipStream_t>(hip_stream));
 } CCP_ABI_CATCH
 
 int ccp_grid_tune(ccp_grid *g, int32_t max_t, int32_t *chosen_t, int32_t *chosen_rows_per_chunk, float *ms_per_iteration)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (max_t < 1) return CCP_ERR_BAD_ARG;
     max_t = std::min<int>(max_t, g->masked ? kMaskedMaxT : kFusedMaxT);
@@ -1375,6 +1426,7 @@ try {
 
 int ccp_grid_set_fused(ccp_grid *g, int32_t on)
 try {
+    CCP_TRY(not_weighted(g));
     if (!g) return CCP_ERR_BAD_ARG;
     g->fuse = on != 0;
     return CCP_OK;
@@ -1382,6 +1434,7 @@ try {
 
 int ccp_grid_set_tiling(ccp_grid *g, int32_t max_t, int32_t rows_per_chunk)
 try {
+    CCP_TRY(not_weighted(g));
     if (!g || max_t < 1 || rows_per_chunk < 2) return CCP_ERR_BAD_ARG;
     g->fuse_tmax = std::min<int>(max_t, kFusedMaxT);
     g->rows_per_chunk = rows_per_chunk + (rows_per_chunk & 1);       // the march advances two rows per trip
@@ -1401,6 +1454,7 @@ try {
 
 int ccp_grid_sweep_l1(ccp_grid *g, double *l1_per_channel)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!l1_per_channel) return CCP_ERR_BAD_ARG;
     const int C = g->desc.channels;
@@ -1418,6 +1472,7 @@ try {
 
 int ccp_grid_gauss_seidel(ccp_grid *g, double epsilon, int32_t max_iteration, int32_t check_every, ccp_gs_report *report)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (g->ghost_top || g->ghost_bottom) return CCP_ERR_STATE;   // row blocks are driven by the caller (halo exchange)
     if (check_every < 0) return CCP_ERR_BAD_ARG;
@@ -1807,6 +1862,7 @@ int lex_run(ccp_grid *g, int iterations, unsigned mask, double *partial)
 int ccp_grid_gauss_seidel_lexicographic(ccp_grid *g, double epsilon, int32_t max_iteration, int32_t check_every,
                                         ccp_gs_report *report)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (g->ghost_top || g->ghost_bottom || g->desc.row_count != g->desc.height) return CCP_ERR_STATE;   // whole image only
     if (g->masked && g->lex_mode != 3) return CCP_ERR_UNSUPPORTED;  // Dirichlet masks: k_lex_wg only
@@ -1959,6 +2015,7 @@ try {
 
 int ccp_grid_conjugate_gradient(ccp_grid *g, double epsilon, int32_t max_iteration, ccp_gs_report *report)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (g->ghost_top || g->ghost_bottom || g->desc.row_count != g->desc.height) return CCP_ERR_STATE;
     const Geom &geo = g->geom;
@@ -2030,9 +2087,18 @@ namespace {
 // g->small.p[2*ch] = sum (b - A x)^2, [2*ch+1] = sum b^2 over the OWNED rows (device, on g->stream)
 int residual_to_small(ccp_grid *g)
 {
+    const int C = g->desc.channels;
+    if (g->weighted) {
+        if (!g->has_op) return CCP_ERR_STATE;
+        const dim3 wg = weighted_apply_grid(g);
+        hipLaunchKernelGGL((k_weighted_apply<1>), wg, dim3(kBlock), 0, g->stream, g->x.p, g->b.p, g->geom, g->wop.p, g->geom.ch_stride, g->wpart.p);
+        CCP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_pair_reduce, dim3((unsigned)C), dim3(kBlock), 0, g->stream, g->wpart.p, (long)wg.x, g->small.p);
+        CCP_HIP(hipGetLastError());
+        return CCP_OK;
+    }
     if ((g->shrink_top || g->shrink_bottom) && g->half_sweeps_since_refresh >= g->desc.ghost) return CCP_ERR_STATE;
     const Geom &geo = g->geom;
-    const int C = g->desc.channels;
     dim3 grid((unsigned)((geo.pitch + 2L * kBlock - 1) / (2L * kBlock)), (unsigned)(geo.own_hi - geo.own_lo), (unsigned)C * 2);
     if (g->masked)
         hipLaunchKernelGGL((k_apply<2, 1, true>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->b.p, g->b.p, geo, geo.own_lo, g->partial.p, g->maskp.p);
@@ -2085,6 +2151,7 @@ try {
 
 int ccp_grid_assemble_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t row_stride_bytes, const int32_t *constraint)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!gx || !gy || !constraint) return CCP_ERR_BAD_ARG;
     if (g->masked) return CCP_ERR_UNSUPPORTED;            // SolveChannel's right-hand side belongs to SolveChannel's matrix
@@ -2121,6 +2188,7 @@ int ccp_grid_assemble_from_images(ccp_grid *g, const uint8_t *const *images, int
                                   int64_t image_stride_bytes, const uint8_t *label, int64_t label_stride_bytes,
                                   int32_t init_x_from_composite)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!images || !label || n_images < 1 || n_images > 256) return CCP_ERR_BAD_ARG;
     if (g->desc.channels != 3 || g->masked) return CCP_ERR_UNSUPPORTED;      // BGR images; SolveChannel's matrix
@@ -2247,6 +2315,7 @@ extern "C" {
 int ccp_grid_assemble_region_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes,
                                  const uint8_t *canvas, int64_t canvas_stride_bytes, int32_t init_x_from_canvas)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!gx || !gy || !canvas) return CCP_ERR_BAD_ARG;
     const int W = g->desc.width, C = g->desc.channels;
@@ -2281,6 +2350,7 @@ try {
 int ccp_grid_assemble_clone(ccp_grid *g, const uint8_t *source, int64_t source_stride_bytes, const uint8_t *target,
                             int64_t target_stride_bytes, int32_t mode, int32_t init)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!source || !target) return CCP_ERR_BAD_ARG;
     const int W = g->desc.width, C = g->desc.channels;
@@ -2314,6 +2384,7 @@ try {
 int ccp_grid_store_u8_composite(ccp_grid *g, const uint8_t *canvas, int64_t canvas_stride_bytes, uint8_t *out,
                                 int64_t out_stride_bytes)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!canvas || !out) return CCP_ERR_BAD_ARG;
     const int W = g->desc.width, C = g->desc.channels;
@@ -2423,6 +2494,7 @@ int sweep_rowblocked(ccp_grid *g, int iterations)
 
 int ccp_grid_attach_comm(ccp_grid *g, ccp_comm *c)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     mg_release(g->mg);                               // the multigrid hierarchy belongs to the partition
     g->mg = nullptr;
@@ -2472,6 +2544,7 @@ try {
 
 int ccp_grid_set_overlap(ccp_grid *g, int32_t on)
 try {
+    CCP_TRY(not_weighted(g));
     if (!g) return CCP_ERR_BAD_ARG;
     g->overlap = on != 0;
     return CCP_OK;
@@ -2479,12 +2552,14 @@ try {
 
 int ccp_grid_exchange_halos(ccp_grid *g)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     return exchange(g, false);
 } CCP_ABI_CATCH
 
 int ccp_grid_sweep_rowblocked(ccp_grid *g, int32_t iterations)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (iterations < 0) return CCP_ERR_BAD_ARG;
     if (!g->comm) return CCP_ERR_STATE;
@@ -2496,6 +2571,7 @@ try {
 
 int ccp_grid_residual_norm2_global(ccp_grid *g, double *rr_bb)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!rr_bb) return CCP_ERR_BAD_ARG;
     if (!g->comm) return CCP_ERR_STATE;
@@ -2510,6 +2586,7 @@ try {
 int ccp_grid_gauss_seidel_rowblocked(ccp_grid *g, double epsilon, int32_t max_iteration, int32_t check_every,
                                      ccp_gs_report *report)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!g->comm) return CCP_ERR_STATE;
     if (max_iteration < 0 || check_every < 0) return CCP_ERR_BAD_ARG;
@@ -2671,6 +2748,7 @@ try {
 // the neighbours before every product (one image row per neighbour), every dot product all-reduced.
 int ccp_grid_conjugate_gradient_rowblocked(ccp_grid *g, double epsilon, int32_t max_iteration, ccp_gs_report *report)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!g->comm) return CCP_ERR_STATE;
     if (max_iteration < 0) return CCP_ERR_BAD_ARG;
@@ -3007,6 +3085,7 @@ try {
 
 int ccp_grid_assemble_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const int32_t *constraint)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!gx || !gy || !constraint) return CCP_ERR_BAD_ARG;
     if (g->masked) return CCP_ERR_UNSUPPORTED;
@@ -3027,6 +3106,7 @@ try {
 int ccp_grid_assemble_from_images_device(ccp_grid *g, const ccp_device_array *images, int32_t n_images,
                                          const ccp_device_array *label, int32_t init_x_from_composite)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!images || !label || n_images < 1 || n_images > 256) return CCP_ERR_BAD_ARG;
     if (g->desc.channels != 3 || g->masked) return CCP_ERR_UNSUPPORTED;
@@ -3083,6 +3163,7 @@ try {
 int ccp_grid_assemble_region_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy,
                                         const ccp_device_array *canvas, int32_t init_x_from_canvas)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!gx || !gy || !canvas) return CCP_ERR_BAD_ARG;
     const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
@@ -3110,6 +3191,7 @@ try {
 int ccp_grid_assemble_clone_device(ccp_grid *g, const ccp_device_array *source, const ccp_device_array *target, int32_t mode,
                                    int32_t init)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!source || !target) return CCP_ERR_BAD_ARG;
     const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
@@ -3137,6 +3219,7 @@ try {
 
 int ccp_grid_store_u8_composite_device(ccp_grid *g, const ccp_device_array *canvas, const ccp_device_array *out)
 try {
+    CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
     if (!canvas || !out) return CCP_ERR_BAD_ARG;
     const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
@@ -3148,6 +3231,144 @@ try {
                        view_of<const uint8_t>(canvas), view_of<uint8_t>(out), C);
     CCP_HIP(hipGetLastError());
     return edge_timeout_status(g);
+} CCP_ABI_CATCH
+
+}  // extern "C"
+
+// ============================================================================================
+// Weighted grids (include/ccp_gs.h, CCP_GRID_WEIGHTED; kernels: ccp_grid_weighted.hpp)
+// ============================================================================================
+namespace {
+
+int weighted_handle(ccp_grid *g)
+{
+    CCP_TRY(bind(g));
+    return g->weighted ? CCP_OK : CCP_ERR_UNSUPPORTED;
+}
+
+// The operator from three weight views in one pass; the device's verdict on the weights is read back once.  The old
+// operator and the hierarchy built on it are gone either way: a refusal leaves the handle with none.
+int set_weights(ccp_grid *g, const WeightView &wx, const WeightView &wy, const WeightView &lam)
+{
+    const Geom &geo = g->geom;
+    const long n = geo.ch_stride;
+    mg_release(g->mg);
+    g->mg = nullptr;
+    g->has_op = false;
+    unsigned bad = 0;
+    CCP_HIP(hipMemsetAsync(g->io_bad.p, 0, sizeof(unsigned), g->stream));
+    hipLaunchKernelGGL(k_weighted_coef, dim3((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)geo.H), dim3(kBlock), 0, g->stream, wx, wy,
+                       lam, geo.W, geo.H, geo.pitch, g->wop.p, g->wop.p + n, g->wop.p + 2 * n, g->wop.p + 3 * n, g->io_bad.p);
+    CCP_HIP(hipGetLastError());
+    CCP_HIP(hipMemcpyAsync(&bad, g->io_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    if (bad) return CCP_ERR_BAD_ARG;
+    g->has_op = true;
+    return edge_timeout_status(g);
+}
+
+template <bool INIT, typename G, typename F>
+void launch_weighted_rhs(ccp_grid *g, const G &gx, const G &gy, const F &f, int has)
+{
+    const Geom &geo = g->geom;
+    hipLaunchKernelGGL((k_weighted_rhs<INIT, G, F>), dim3((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)geo.H), dim3(kBlock), 0, g->stream,
+                       g->b.p, g->x.p, geo, static_cast<const double *>(g->wop.p), geo.ch_stride, gx, gy, f, has, g->desc.channels);
+}
+
+template <typename G, typename F>
+int weighted_rhs(ccp_grid *g, const G &gx, const G &gy, const F &f, int has, bool init)
+{
+    if (init) launch_weighted_rhs<true>(g, gx, gy, f, has);
+    else launch_weighted_rhs<false>(g, gx, gy, f, has);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ccp_grid_set_weights_host(ccp_grid *g, const float *wx, const float *wy, const float *lambda, int64_t row_stride_bytes)
+try {
+    CCP_TRY(weighted_handle(g));
+    const int W = g->desc.width, H = g->desc.height;
+    const float *src[3] = {wx, wy, lambda};
+    if ((wx || wy || lambda) && row_stride_bytes < (int64_t)W * (int64_t)sizeof(float)) return CCP_ERR_BAD_ARG;
+    const double dflt[3] = {1.0, 1.0, 0.0};
+    DevBuf<float> dev[3];
+    WeightView v[3];
+    for (int i = 0; i < 3; ++i) {
+        v[i] = WeightView{nullptr, 0, 0, 0, dflt[i]};
+        if (!src[i]) continue;
+        CCP_TRY(dev[i].alloc((size_t)W * H));
+        CCP_HIP(hipMemcpy2DAsync(dev[i].p, (size_t)W * sizeof(float), src[i], (size_t)row_stride_bytes, (size_t)W * sizeof(float), (size_t)H,
+                                 hipMemcpyHostToDevice, g->stream));
+        v[i] = WeightView{dev[i].p, (long)W, 1, 0, dflt[i]};
+    }
+    return set_weights(g, v[0], v[1], v[2]);
+} CCP_ABI_CATCH
+
+int ccp_grid_set_weights_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda)
+try {
+    CCP_TRY(weighted_handle(g));
+    const int W = g->desc.width, H = g->desc.height;
+    const ccp_device_array *src[3] = {wx, wy, lambda};
+    const double dflt[3] = {1.0, 1.0, 0.0};
+    WeightView v[3];
+    for (int i = 0; i < 3; ++i) {
+        v[i] = WeightView{nullptr, 0, 0, 0, dflt[i]};
+        if (!src[i]) continue;
+        CCP_TRY(check_view(g, src[i], kF32F64, false, 1, H, W, 1));
+        v[i] = WeightView{src[i]->data, (long)src[i]->stride_y, (long)src[i]->stride_x, src[i]->dtype == CCP_DTYPE_F64 ? 1 : 0, dflt[i]};
+    }
+    return set_weights(g, v[0], v[1], v[2]);
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_weighted_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes, const float *f,
+                                   int64_t f_stride_bytes, int32_t init_x_from_f)
+try {
+    CCP_TRY(weighted_handle(g));
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    const int64_t row = (int64_t)W * C * (int64_t)sizeof(float);
+    if ((gx || gy) && field_stride_bytes < row) return CCP_ERR_BAD_ARG;
+    if (f && f_stride_bytes < row) return CCP_ERR_BAD_ARG;
+    if (!g->has_op) return CCP_ERR_STATE;
+    const float *src[3] = {gx, gy, f};
+    const int64_t stride[3] = {field_stride_bytes, field_stride_bytes, f_stride_bytes};
+    DevBuf<float> dev[3];
+    using PF = Packed<const float>;
+    PF acc[3];
+    int has = 0;
+    for (int i = 0; i < 3; ++i) {
+        acc[i] = PF{nullptr, 0, (long)W * C, C, 0};
+        if (!src[i]) continue;
+        has |= 1 << i;
+        CCP_TRY(upload_window(g, dev[i], src[i], stride[i], 0, H));
+        acc[i].p = dev[i].p;
+    }
+    CCP_TRY(weighted_rhs(g, acc[0], acc[1], acc[2], has, init_x_from_f != 0));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f,
+                                          int32_t init_x_from_f)
+try {
+    CCP_TRY(weighted_handle(g));
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    if (gx) CCP_TRY(check_view(g, gx, kF32, false, 1, H, W, C));
+    if (gy) CCP_TRY(check_view(g, gy, kF32, false, 1, H, W, C));
+    if (f) CCP_TRY(check_view(g, f, kF32F64 | kU8, false, 1, H, W, C));
+    if (!g->has_op) return CCP_ERR_STATE;
+    using VF = View<const float>;
+    const VF none{nullptr, 0, 0, 0, 0};
+    const VF vgx = gx ? view_of<const float>(gx) : none, vgy = gy ? view_of<const float>(gy) : none;
+    const int has = (gx ? 1 : 0) | (gy ? 2 : 0) | (f ? 4 : 0);
+    const bool init = init_x_from_f != 0;
+    if (!f) return weighted_rhs(g, vgx, vgy, none, has, init);
+    if (f->dtype == CCP_DTYPE_U8) return weighted_rhs(g, vgx, vgy, view_of<const uint8_t>(f), has, init);
+    if (f->dtype == CCP_DTYPE_F32) return weighted_rhs(g, vgx, vgy, view_of<const float>(f), has, init);
+    return weighted_rhs(g, vgx, vgy, view_of<const double>(f), has, init);
 } CCP_ABI_CATCH
 
 }  // extern "C"

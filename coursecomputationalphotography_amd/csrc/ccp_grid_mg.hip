@@ -12,7 +12,7 @@ using namespace ccp;
 namespace ccp {
 
 // The hierarchy of one handle: level 0 is the handle's own operator and vectors; levels 1.. own d, we, ws, b, z in
-// one allocation (level layout, pads zero).  The PCG work vectors (one channel) are allocated at the first solve.
+// one allocation (level layout, pads zero; a weighted hierarchy adds lambda).  The PCG work vectors (one channel) are allocated at the first solve.
 // Row blocks (ccp_grid_mg_conjugate_gradient_rowblocked): levels 0 .. dist-1 hold the block's own rows plus up to
 // kMgGhost ghost rows per neighbour side (level 0 in a layout of its own: the MG vectors do not depend on the
 // handle's ghost depth); every level from `dist` on is held whole by every rank.
@@ -24,7 +24,7 @@ struct MgHierarchy {
     std::vector<std::vector<int>> own;   // row blocks, per distributed level: every rank's first global row, then H_k
     DevBuf<unsigned char> mask0;     // row blocks: level 0's mask in the level's layout
     std::vector<MgLevel> lv;
-    std::vector<long> base;          // per coarse level: offset of its d in `store` (then we, ws, b, z, t, each `size`)
+    std::vector<long> base;          // per coarse level: offset of its d in `store` (then we, ws, b, z, t, [lambda], each `size`)
     std::vector<long> size;
     DevBuf<double> store;
     DevBuf<double> t0;               // level 0's pre-smoothed z (one channel): k_mg_tile reads it while it writes z
@@ -32,7 +32,8 @@ struct MgHierarchy {
     DevBuf<CgState> state;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int kind0 = kMgSolve;
-    double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t
+    bool weighted = false;           // level 0 is a weighted handle's stored operator; every level carries lambda (arr 6)
+    double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda
     ~MgHierarchy()
     {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -64,12 +65,19 @@ int build(const GridMgView &v, MgHierarchy **out)
 {
     MgHierarchy *h = new MgHierarchy();
     std::unique_ptr<MgHierarchy> own(h);
-    h->kind0 = v.masked ? kMgMasked : kMgSolve;
+    h->kind0 = v.weighted ? kMgCoarse : v.masked ? kMgMasked : kMgSolve;
+    h->weighted = v.weighted;
+    const int per_level = v.weighted ? 7 : 6;
     MgLevel l0{};
     l0.W = v.geom.W;
     l0.H = v.geom.H;
     l0.pitch = v.geom.pitch;
     l0.mask = v.mask;
+    if (v.weighted) {
+        l0.d = v.wd;
+        l0.we = v.wwe;
+        l0.ws = v.wws;
+    }
     l0.g0 = v.geom;
     l0.hi = l0.H;
     h->lv.push_back(l0);
@@ -85,7 +93,7 @@ int build(const GridMgView &v, MgHierarchy **out)
         h->lv.push_back(c);
         h->base.push_back(total);
         h->size.push_back((long)c.H * 2 * c.pitch);
-        total += 6 * h->size.back();
+        total += per_level * h->size.back();
     }
     h->levels = (int)h->lv.size();
     h->tail = h->levels;
@@ -107,7 +115,12 @@ int build(const GridMgView &v, MgHierarchy **out)
         h->lv[k].ws = h->arr(k, 2);
     }
     for (int k = 0; k + 1 < h->levels; ++k) {
-        coarsen(level_kind(*h, k), v.stream, h->lv[k], h->lv[k + 1], 0, h->lv[k + 1].H, h->arr(k + 1, 0), h->arr(k + 1, 1), h->arr(k + 1, 2));
+        if (v.weighted)
+            hipLaunchKernelGGL(k_mg_coarsen_weighted, cells_grid(h->lv[k + 1].W, h->lv[k + 1].H), dim3(kBlock), 0, v.stream, h->lv[k],
+                               k ? static_cast<const double *>(h->arr(k, 6)) : v.wlam, h->lv[k + 1], h->arr(k + 1, 0), h->arr(k + 1, 1),
+                               h->arr(k + 1, 2), h->arr(k + 1, 6));
+        else
+            coarsen(level_kind(*h, k), v.stream, h->lv[k], h->lv[k + 1], 0, h->lv[k + 1].H, h->arr(k + 1, 0), h->arr(k + 1, 1), h->arr(k + 1, 2));
         CCP_HIP(hipGetLastError());
     }
     if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return CCP_ERR_HIP;
@@ -117,7 +130,7 @@ int build(const GridMgView &v, MgHierarchy **out)
 
 int hierarchy(const GridMgView &v, MgHierarchy **out)
 {
-    if (*v.cache && (*v.cache)->rowblocked) {            // built for the row-block calls: this call needs its own
+    if (*v.cache && ((*v.cache)->rowblocked || (*v.cache)->weighted != v.weighted)) {            // built for the row-block calls: this call needs its own
         mg_release(*v.cache);
         *v.cache = nullptr;
     }
@@ -205,7 +218,10 @@ int whole_levels(MgHierarchy &h, hipStream_t s, int from, const double *b0, doub
 // 1x1 image: z = b/d, what red updates from z = 0 give
 int vcycle_1x1(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st)
 {
-    if (h.kind0 == kMgMasked)
+    if (h.kind0 == kMgCoarse)
+        hipLaunchKernelGGL((k_mg_tile<kMgCoarse, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
+                           static_cast<const double *>(nullptr), nu, st);
+    else if (h.kind0 == kMgMasked)
         hipLaunchKernelGGL((k_mg_tile<kMgMasked, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
                            static_cast<const double *>(nullptr), nu, st);
     else
@@ -428,6 +444,7 @@ int vcycle_rowblocked(MgHierarchy &h, const Net &n, const double *b0, double *z0
 int prepare_rowblocked(ccp_grid *g, int32_t smoothing_sweeps, bool need_nu, GridMgView *v, Net *n, int *nu, MgHierarchy **h)
 {
     CCP_TRY(grid_mg_view(g, v));
+    if (v->weighted) return CCP_ERR_UNSUPPORTED;                   // weighted handles are single blocks
     if (!v->comm) return CCP_ERR_STATE;
     n->api = rccl_api();
     if (!n->api) return CCP_ERR_RCCL;
@@ -448,6 +465,7 @@ int check_handle(ccp_grid *g, GridMgView *v)
 {
     CCP_TRY(grid_mg_view(g, v));
     if (!v->one_block) return CCP_ERR_STATE;
+    if (v->weighted && !v->wd) return CCP_ERR_STATE;              // no operator set (or the last one was refused)
     return CCP_OK;
 }
 
@@ -488,7 +506,11 @@ try {
     if (level == 0) {
         CCP_TRY(tmp.alloc((size_t)(3 * n)));
         CCP_HIP(hipMemsetAsync(tmp.p, 0, sizeof(double) * 3 * n, v.stream));
-        if (v.masked)
+        if (v.weighted) {                                          // the stored operator itself
+            CCP_HIP(hipMemcpyAsync(tmp.p, l.d, sizeof(double) * n, hipMemcpyDeviceToDevice, v.stream));
+            CCP_HIP(hipMemcpyAsync(tmp.p + n, l.we, sizeof(double) * n, hipMemcpyDeviceToDevice, v.stream));
+            CCP_HIP(hipMemcpyAsync(tmp.p + 2 * n, l.ws, sizeof(double) * n, hipMemcpyDeviceToDevice, v.stream));
+        } else if (v.masked)
             hipLaunchKernelGGL((k_mg_coef0<kMgMasked>), cells_grid(l.W, l.H), dim3(kBlock), 0, v.stream, l, tmp.p, tmp.p + n, tmp.p + 2 * n);
         else
             hipLaunchKernelGGL((k_mg_coef0<kMgSolve>), cells_grid(l.W, l.H), dim3(kBlock), 0, v.stream, l, tmp.p, tmp.p + n, tmp.p + 2 * n);
@@ -540,7 +562,10 @@ try {
     double *part = h->partial.p;
     const MgLevel &l0 = h->lv[0];
     auto apply = [&](const double *in, double *out, bool dot) {           // the product of an iteration stops with the loop
-        if (v.masked) {
+        if (v.weighted) {
+            if (dot) hipLaunchKernelGGL((k_mg_apply<kMgCoarse, true>), agrid, dim3(kBlock), 0, s, l0, in, out, part, st);
+            else hipLaunchKernelGGL((k_mg_apply<kMgCoarse, false>), agrid, dim3(kBlock), 0, s, l0, in, out, part, static_cast<const CgState *>(nullptr));
+        } else if (v.masked) {
             if (dot) hipLaunchKernelGGL((k_mg_apply<kMgMasked, true>), agrid, dim3(kBlock), 0, s, l0, in, out, part, st);
             else hipLaunchKernelGGL((k_mg_apply<kMgMasked, false>), agrid, dim3(kBlock), 0, s, l0, in, out, part, static_cast<const CgState *>(nullptr));
         } else {

@@ -1,11 +1,14 @@
 // ccp_grid_mg.hpp — geometric multigrid V-cycle as the preconditioner of conjugate gradient on the grid handles
 // (ccp_grid_mg_conjugate_gradient, include/ccp_gs.h), hand-written for gfx950.
 //
-// Hierarchy.  Level 0 is the handle's own operator: SolveChannel's matrix (classify) or the Dirichlet-mask Laplacian.
+// Hierarchy.  Level 0 is the handle's own operator: SolveChannel's matrix (classify), the Dirichlet-mask Laplacian, or
+// the stored operator of a weighted handle (kind kMgCoarse on the handle's d, we, ws planes: ccp_grid_weighted.hpp).
 // Level k+1 is ceil(W_k/2) x ceil(H_k/2); coarse cell (X,Y) aggregates the live pixels (diagonal != 0) among
 // (2X..2X+1, 2Y..2Y+1), down to 1x1.  A_{k+1} = P^T A_k P with P piecewise constant over the aggregates is again a
 // 5-point operator, stored per cell as d (diagonal), we (weight to the east cell), ws (weight to the south cell);
-// the weights are the positive couplings (A_ij = -w).  Every value is a small integer: exact in fp64.
+// the weights are the positive couplings (A_ij = -w).  Every value is a small integer: exact in fp64.  A weighted
+// hierarchy carries the data weight lambda on every level too and forms d without cancellation (k_mg_coarsen_weighted):
+// its weights are real numbers, and d - 2 x internal edges could round to a tiny or negative diagonal.
 //
 // Layout.  Every level uses the fine grid's colour-split layout: cell (X,Y) sits in colour plane (X+Y)&1 of row Y at
 // half-column X>>1, pitch a multiple of 16 (mg_at).  Aggregate X of rows 2Y, 2Y+1 is half-column X of both planes of
@@ -31,6 +34,7 @@
 #include "ccp_cg.hpp"
 #include "ccp_grid_mg_view.hpp"
 #include "ccp_grid_stencil.hpp"
+#include "ccp_grid_weighted.hpp"
 
 namespace ccp {
 
@@ -131,6 +135,7 @@ __device__ __forceinline__ double mg_row0(const MgLevel &lv, const double *__res
     const double xi = z[at];
     const double xu = mg_ld(z, lv, x, y - 1), xl = mg_ld(z, lv, x - 1, y), xr = mg_ld(z, lv, x + 1, y), xd = mg_ld(z, lv, x, y + 1);
     if (KIND == kMgSolve) return apply_row(classify(lv.g0, x, lv.y0 + y, y), xi, xu, xl, xr, xd);
+    if (KIND == kMgCoarse) return weighted_row(lv.d, lv.we, lv.ws, lv.pitch, lv.W, lv.H, z, x, y);   // a weighted handle's level 0
     double ax = 0.0;
     if (lv.mask[at]) {
         ax += -1.0 * xu;
@@ -214,6 +219,35 @@ k_mg_coarsen(MgLevel lv, MgLevel cv, int Y0, double *__restrict__ d, double *__r
     d[at] = ((d00 + d10) + (d01 + d11)) - 2.0 * ((e00 + e01) + (s00 + s10));
     we[at] = e10 + e11;
     ws[at] = s01 + s11;
+}
+
+// Weighted hierarchies: coarse cell (X,Y) of level k+1 from level k and its data weights lam (one block, whole levels):
+// lambda_c = (l00 + l10) + (l01 + l11); d = lambda_c; d += north; d += west; d += east; d += south, each side the sum
+// of the two fine edge weights that leave the aggregate there (north: the ws of the row above, left child first; west:
+// the we of the column to the left, upper child first); we / ws as k_mg_coarsen forms them.  Every term is >= 0, so a
+// coarse diagonal is never a difference.  grid = (ceil(Wc/kBlock), Hc).
+static __global__ void __launch_bounds__(kBlock)
+k_mg_coarsen_weighted(MgLevel lv, const double *__restrict__ lam, MgLevel cv, double *__restrict__ d, double *__restrict__ we,
+                      double *__restrict__ ws, double *__restrict__ lam_c)
+{
+    const int X = blockIdx.x * kBlock + threadIdx.x, Y = blockIdx.y;
+    if (X >= cv.W) return;
+    const int x = 2 * X, y = 2 * Y;
+    const double lc = (mg_ld(lam, lv, x, y) + mg_ld(lam, lv, x + 1, y)) + (mg_ld(lam, lv, x, y + 1) + mg_ld(lam, lv, x + 1, y + 1));
+    const double n = mg_ld(lv.ws, lv, x, y - 1) + mg_ld(lv.ws, lv, x + 1, y - 1);
+    const double w = mg_ld(lv.we, lv, x - 1, y) + mg_ld(lv.we, lv, x - 1, y + 1);
+    const double e = mg_ld(lv.we, lv, x + 1, y) + mg_ld(lv.we, lv, x + 1, y + 1);
+    const double s = mg_ld(lv.ws, lv, x, y + 1) + mg_ld(lv.ws, lv, x + 1, y + 1);
+    double dc = lc;
+    dc += n;
+    dc += w;
+    dc += e;
+    dc += s;
+    const long at = mg_at(cv.pitch, X, Y);
+    d[at] = dc;
+    we[at] = e;
+    ws[at] = s;
+    lam_c[at] = lc;
 }
 
 // level 0's coefficients in the level layout (ccp_grid_mg_level only).  grid = (ceil(W/kBlock), H).

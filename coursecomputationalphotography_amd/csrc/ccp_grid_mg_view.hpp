@@ -16,6 +16,10 @@ struct GridMgView {
     bool one_block;                  // no ghost rows: the whole image in this handle
     double *x, *b;
     const unsigned char *mask;
+    // a weighted handle (CCP_GRID_WEIGHTED): its level-0 planes d, we, ws, lambda in the layout of one channel of x, all
+    // null while it has no operator
+    bool weighted;
+    const double *wd, *wwe, *wws, *wlam;
     hipStream_t stream;
     MgHierarchy **cache;             // the handle's cached hierarchy (built on first use, dropped with the mask and the partition)
     // row blocks (ccp_grid_attach_comm): the communicator, every rank's first image row then the image height

@@ -111,3 +111,71 @@ def seamless_clone(source, target, mask, iterations: int, mixed: bool = False, s
         return g.store_u8_composite_tensor(target)
     finally:
         g.close()
+
+
+def _weight(w, H, W, dev):
+    """A weight argument of weighted_solve: None stays None (the library's default), a scalar becomes a broadcast
+    H x W float64 view (stride 0: nothing is materialised), a tensor is passed as it is."""
+    import torch
+    if w is None or isinstance(w, torch.Tensor):
+        return w
+    return torch.tensor(float(w), dtype=torch.float64, device=torch.device("cuda", dev)).expand(H, W)
+
+
+def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=None, out_dtype=None, epsilon: float = 1e-10):
+    """Minimise  sum wx (u(x+1,y) - u(x,y) - gx)^2 + sum wy (u(x,y+1) - u(x,y) - gy)^2 + sum data_weight (u - f)^2
+    for every channel on a weighted grid handle (CCP_GRID_WEIGHTED), by multigrid-preconditioned CG (at most
+    `iterations` iterations to sqrt(r'r) < epsilon) from x = f.  gx, gy: float32 H x W x C tensors or None (zero
+    guidance); f: u8 / float32 / float64 H x W x C or None (zero, and x starts at 0).  wx, wy, data_weight: H x W
+    float32 / float64 tensors or scalars (None: wx = wy = 1, data_weight = 0).  out_dtype: torch.uint8 (the default: the
+    clamped solution) or a float dtype (x itself)."""
+    import torch
+    out_dtype = torch.uint8 if out_dtype is None else out_dtype
+    ref = next((t for t in (f, gx, gy) if t is not None), None)
+    if ref is None:
+        raise ValueError("weighted_solve needs at least one of gx, gy, f")
+    dev = _device_index(ref)
+    H, W = ref.shape[0], ref.shape[1]
+    C = ref.shape[2] if ref.dim() == 3 else 1
+    g = capi.Grid(W, H, C, device=dev, weighted=True)
+    g.set_stream(torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream)
+    try:
+        g.set_weights_tensor(_weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev))
+        g.assemble_weighted_rhs_tensor(gx, gy, f, init_x=f is not None)
+        if f is None:
+            g.fill_x(0.0)
+        g.mg_conjugate_gradient(epsilon, iterations, 2)
+        if out_dtype == torch.uint8:
+            return g.store_u8_tensor()
+        return g.get_x_tensor(dtype=out_dtype)
+    finally:
+        g.close()
+
+
+def wls_weights(image, lam: float = 1.0, alpha: float = 1.2, eps: float = 1e-4):
+    """The edge weights of WLS edge-preserving smoothing (Farbman et al. 2008) for a u8 or float H x W (x C) tensor:
+    wx = lam / (|d/dx log(L + eps)|^alpha + eps), wy likewise, L the channel mean (u8 scaled to [0, 1]).  float64
+    H x W tensors; the last column of wx and the last row of wy are never read (set to 0)."""
+    import torch
+    img = image.to(torch.float64)
+    if image.dtype == torch.uint8:
+        img = img / 255.0
+    lum = img.mean(dim=-1) if img.dim() == 3 else img
+    ell = torch.log(lum + eps)
+    wx = torch.zeros_like(ell)
+    wy = torch.zeros_like(ell)
+    wx[:, :-1] = lam / (torch.abs(ell[:, 1:] - ell[:, :-1]) ** alpha + eps)
+    wy[:-1, :] = lam / (torch.abs(ell[1:, :] - ell[:-1, :]) ** alpha + eps)
+    return wx, wy
+
+
+def wls_smooth(image, iterations: int, lam: float = 1.0, alpha: float = 1.2, eps: float = 1e-4, epsilon: float = 1e-10):
+    """WLS edge-preserving smoothing (Farbman et al. 2008): u minimises sum (u - image)^2 + sum wx (du/dx)^2 +
+    sum wy (du/dy)^2 with wls_weights (torch ops: plumbing), solved on a weighted grid handle.  image: u8 or float
+    H x W (x C) tensor; returns the same dtype and shape (u8: clamped)."""
+    import torch
+    wx, wy = wls_weights(image, lam, alpha, eps)
+    f = image if image.dim() == 3 else image.unsqueeze(-1)
+    out_dtype = torch.uint8 if image.dtype == torch.uint8 else image.dtype
+    u = weighted_solve(None, None, f, iterations, wx=wx, wy=wy, data_weight=1.0, out_dtype=out_dtype, epsilon=epsilon)
+    return u if image.dim() == 3 else u[..., 0]

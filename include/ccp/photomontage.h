@@ -246,4 +246,42 @@ inline void SeamlessClone(const ImageView &source, const ImageView &target, cons
                   "ccp_grid_store_u8_composite");
 }
 
+// Weighted gradient-domain solve (CCP_GRID_WEIGHTED; screened Poisson fusion, WLS smoothing, soft constraints): for
+// every channel, u minimises  sum wx (u(x+1,y) - u(x,y) - gx)^2 + sum wy (u(x,y+1) - u(x,y) - gy)^2 + sum lambda (u - f)^2.
+// gx, gy, f: CV_32FC<C> views of out's shape (gx and gy sharing one row step), each may be null (zero); wx, wy, lambda:
+// CV_32FC1 views sharing one row step, each may be null (wx, wy: 1 everywhere; lambda: 0).  The start vector is f (0
+// without it); out: u8, the clamped solution.  Only Solver::MultigridConjugateGradient (at most `iterations` iterations,
+// epsilon 1e-10) solves this system; any other solver throws std::invalid_argument, as does every other failure.
+inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageView *f, const ImageView *wx, const ImageView *wy,
+                          const ImageView *lambda, ImageView &out, int iterations,
+                          Solver solver = Solver::MultigridConjugateGradient, int device = 0)
+{
+    if (solver != Solver::MultigridConjugateGradient)
+        throw std::invalid_argument("SolveWeighted: only Solver::MultigridConjugateGradient solves a weighted system");
+    const int C = out.channels;
+    if (!out.data) throw std::invalid_argument("SolveWeighted: no output image");
+    for (const ImageView *v : {gx, gy, f})
+        if (v && (!v->data || v->rows != out.rows || v->cols != out.cols || v->channels != C))
+            throw std::invalid_argument("SolveWeighted: image shapes differ");
+    for (const ImageView *v : {wx, wy, lambda})
+        if (v && (!v->data || v->rows != out.rows || v->cols != out.cols || v->channels != 1))
+            throw std::invalid_argument("SolveWeighted: weights must be one-channel views of the image's shape");
+    if (gx && gy && gx->step != gy->step) throw std::invalid_argument("SolveWeighted: gx and gy must share one row step");
+    std::size_t wstep = 0;
+    for (const ImageView *v : {wx, wy, lambda})
+        if (v) {
+            if (wstep && v->step != wstep) throw std::invalid_argument("SolveWeighted: the weights must share one row step");
+            wstep = v->step;
+        }
+    auto fp = [](const ImageView *v) { return v ? static_cast<const float *>(v->data) : nullptr; };
+    detail::GridHandle h(out.cols, out.rows, C, device, CCP_GRID_WEIGHTED);
+    detail::check(ccp_grid_set_weights_host(h.g, fp(wx), fp(wy), fp(lambda), (int64_t)wstep), "ccp_grid_set_weights_host");
+    const int64_t gstep = gx ? (int64_t)gx->step : gy ? (int64_t)gy->step : 0;
+    detail::check(ccp_grid_assemble_weighted_rhs(h.g, fp(gx), fp(gy), gstep, fp(f), f ? (int64_t)f->step : 0, f ? 1 : 0),
+                  "ccp_grid_assemble_weighted_rhs");
+    if (!f) detail::check(ccp_grid_fill_x(h.g, 0.0), "ccp_grid_fill_x");
+    detail::solve(h.g, solver, iterations, C);
+    detail::check(ccp_grid_store_u8(h.g, static_cast<uint8_t *>(out.data), (int64_t)out.step), "ccp_grid_store_u8");
+}
+
 }  // namespace ccp

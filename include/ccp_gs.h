@@ -240,6 +240,33 @@ typedef struct ccp_grid_desc {
  * this form by itself when the uploaded matrix is such a Laplacian of a raster region (ccp_csr_last_path). */
 #define CCP_GRID_DIRICHLET_MASK 1
 
+/* flags: a weighted grid.  Instead of SolveChannel's matrix the handle carries the normal equations of
+ *     E(u) = sum wx (u(x+1,y) - u(x,y) - gx)^2 + sum wy (u(x,y+1) - u(x,y) - gy)^2 + sum lambda (u - f)^2,
+ * one operator shared by all channels: screened Poisson fusion, WLS edge-preserving smoothing, soft constraints.
+ * wx(x,y) weighs the edge (x,y)-(x+1,y) (read for x < W-1 only), wy(x,y) the edge (x,y)-(x,y+1) (y < H-1 only),
+ * lambda(x,y) is the data weight; each is widened to fp64 on the device.  Coefficients, in this order:
+ *     d = lambda; d += wN; d += wW; d += wE; d += wS       (wN = wy(x,y-1), wW = wx(x-1,y), wE = wx(x,y), wS = wy(x,y))
+ * a term whose edge lies outside the canvas skipped; the weight to the east / south cell is wE / wS (0 where the edge is
+ * absent).  A pixel with d = 0 is dead: its row of A is empty.  Right-hand side per channel, in this order:
+ *     t = 0; t += wN gy(x,y-1); t += wW gx(x-1,y); t += -(wE gx(x,y)); t += -(wS gy(x,y)); t += lambda f(x,y)
+ * (ccp_grid_assemble_rhs's order: SolveChannel's weights -- wx = wy = 1 on x < W-1 and y < H-1, lambda = 1 at (0,0) --
+ * give its bits for finite inputs).  The product A z, in this order: a = 0; a += -(wN zN); a += -(wW zW); a += d z;
+ * a += -(wE zE); a += -(wS zS) (0 on dead pixels).
+ *
+ * Single-block handles only: ccp_grid_create refuses this flag with ghost != 0, row_count < height or
+ * CCP_GRID_DIRICHLET_MASK (CCP_ERR_UNSUPPORTED).  Before ccp_grid_set_weights_* has succeeded the handle has no operator
+ * and the calls that need one return CCP_ERR_STATE.  What works on a weighted handle: set / get of x and b (host and
+ * device), ccp_grid_fill_x, _randomize_x, _set_x_u8(_device), _store_u8(_device), _abs_sum, ccp_grid_b_from_x,
+ * ccp_grid_residual_norm2, ccp_grid_mg_conjugate_gradient, ccp_grid_mg_apply, ccp_grid_mg_level (level 0 is the stored
+ * operator) and the calls below.  Every sweep, Gauss-Seidel, reference-order, plain conjugate-gradient, tuning,
+ * SolveChannel-assembly, region-blend, mask and row-block call returns CCP_ERR_UNSUPPORTED.
+ *
+ * The multigrid hierarchy of a weighted handle carries lambda on every level and forms each coarse diagonal as a sum of
+ * non-negative terms (no cancellation with real-valued weights):
+ *     lambda_c = (l00 + l10) + (l01 + l11);   d_c = lambda_c; d_c += north; += west; += east; += south
+ * each side's term the sum of the two fine edge weights that leave the aggregate there. */
+#define CCP_GRID_WEIGHTED 2
+
 /* Device layout, for callers that move halos themselves (torch.distributed / RCCL).
  * Element (channel ch, local row l, colour c, half-column j) of x or b lives at
  *   base + (((ch*local_rows + l)*2 + c)*pitch + j) * 8 bytes,
@@ -570,6 +597,26 @@ int ccp_grid_assemble_region_rhs_device(ccp_grid *g, const ccp_device_array *gx,
 int ccp_grid_assemble_clone_device(ccp_grid *g, const ccp_device_array *source, const ccp_device_array *target,
                                    int32_t mode, int32_t init);
 int ccp_grid_store_u8_composite_device(ccp_grid *g, const ccp_device_array *canvas, const ccp_device_array *out);
+
+/* ---- Weighted grids (CCP_GRID_WEIGHTED) ------------------------------------------------------------------------------
+ * The operator: wx, wy, lambda as H x W float32 host arrays with one row stride in bytes.  wx or wy NULL: 1 everywhere;
+ * lambda NULL: 0 everywhere.  One HIP pass forms d, we, ws and checks on the device that every weight it reads is finite
+ * and >= 0; the call then synchronises once to read the verdict and drops the cached multigrid hierarchy.  A refused
+ * operator (negative, NaN or inf): CCP_ERR_BAD_ARG, and the handle is left with NO operator (CCP_ERR_STATE from the
+ * solves until a valid set).  Not a weighted handle: CCP_ERR_UNSUPPORTED. */
+int ccp_grid_set_weights_host(ccp_grid *g, const float *wx, const float *wy, const float *lambda, int64_t row_stride_bytes);
+/* The twin on device views of H x W (stride_c unused): F32 or F64 each, a NULL descriptor as a NULL host array above,
+ * broadcast views (stride 0) for constant weights.  Synchronises (the verdict), as the host twin. */
+int ccp_grid_set_weights_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy,
+                                const ccp_device_array *lambda);
+/* b of every channel in one launch, by the formula above, from H x W x channels float32 interleaved host arrays:
+ * gx, gy with one row stride (either may be NULL: zero guidance), f with its own (NULL: zero).  init_x_from_f:
+ * x := f on live pixels and 0 on dead ones.  Needs the operator (CCP_ERR_STATE).  Synchronises. */
+int ccp_grid_assemble_weighted_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes,
+                                   const float *f, int64_t f_stride_bytes, int32_t init_x_from_f);
+/* The twin on device views: gx, gy F32, f U8, F32 or F64; NULL descriptors as NULL host arrays.  Async. */
+int ccp_grid_assemble_weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy,
+                                          const ccp_device_array *f, int32_t init_x_from_f);
 
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */

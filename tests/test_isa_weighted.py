@@ -1,0 +1,47 @@
+"""CPU: the weighted-grid kernels (csrc/ccp_grid_weighted.hpp, k_mg_coarsen_weighted in csrc/ccp_grid_mg.hpp, and the
+stored-operator instantiations of the multigrid kernels a weighted handle runs on level 0) in the BUILT gfx950 code
+object: all present, no VGPR/SGPR spills, no scratch."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+LIB = os.path.join(ROOT, "coursecomputationalphotography_amd", "lib", "libccp_gs.so")
+LLVM = "/opt/rocm/lib/llvm/bin"
+NAMES = ("k_weighted_coef", "k_weighted_rhs", "k_weighted_apply", "k_mg_coarsen_weighted", "k_mg_apply", "k_mg_tile")
+
+
+@pytest.fixture(scope="module")
+def kernels(tmp_path_factory):
+    if not (os.path.exists(LIB) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))):
+        pytest.skip("libccp_gs.so or llvm-readelf missing")
+    d = tmp_path_factory.mktemp("isa_weighted")
+    so = shutil.copy(LIB, d)
+    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", so], check=True, capture_output=True, cwd=d)
+    objs = sorted(str(p) for p in d.iterdir() if "gfx950" in p.name)
+    assert objs, "no gfx950 code object in libccp_gs.so"
+    found = {}
+    for o in objs:
+        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", o], check=True, capture_output=True, text=True).stdout
+        for block in notes.split("  - .agpr_count")[1:]:
+            name = re.search(r"\.name:\s+(\S+)", block)
+            if name and any(n in name.group(1) for n in NAMES):
+                found[name.group(1)] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", block, re.M)}
+    return found
+
+
+def test_every_weighted_kernel_is_present(kernels):
+    for k in NAMES[:4]:
+        assert any(k in n for n in kernels), k
+    # the multigrid kernels on a stored level-0 operator: kind kMgCoarse (= 2) of the PCG product, with and without dot
+    assert sum(1 for n in kernels if "k_mg_apply" in n and "ILi2E" in n) == 2
+
+
+def test_no_spills_no_scratch(kernels):
+    for name, m in kernels.items():
+        assert m.get("vgpr_spill_count", 0) == 0, name
+        assert m.get("sgpr_spill_count", 0) == 0, name
+        assert m.get("private_segment_fixed_size", 0) == 0, name
