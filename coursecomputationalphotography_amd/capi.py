@@ -22,6 +22,8 @@ LIB_PATH = os.environ.get("CCP_GS_LIB") or os.path.join(_HERE, "lib", "libccp_gs
 CCP_OK = 0
 GRID_DIRICHLET_MASK = 1
 GRID_WEIGHTED = 2
+MG_HIERARCHY_GALERKIN, MG_HIERARCHY_RESCALED = 0, 1
+MG_HIERARCHIES = {"galerkin": MG_HIERARCHY_GALERKIN, "rescaled": MG_HIERARCHY_RESCALED}
 ORDER_LEXICOGRAPHIC = 0
 ORDER_MULTICOLOUR = 1
 CLONE_IMPORT = 0
@@ -37,6 +39,7 @@ ABI_SYMBOLS = (
     "ccp_grid_get_b_host", "ccp_grid_set_mask_host", "ccp_grid_fill_x", "ccp_grid_b_from_x", "ccp_grid_randomize_x",
     "ccp_grid_sweep", "ccp_grid_sweep_edges_first", "ccp_grid_stream_wait_edges", "ccp_grid_tune", "ccp_grid_set_fused", "ccp_grid_set_tiling", "ccp_grid_get_tiling", "ccp_grid_sweep_l1", "ccp_grid_halo_refreshed", "ccp_grid_gauss_seidel", "ccp_grid_gauss_seidel_lexicographic", "ccp_debug_lex_tickets", "ccp_grid_conjugate_gradient",
     "ccp_grid_mg_conjugate_gradient", "ccp_grid_mg_apply", "ccp_grid_mg_level",
+    "ccp_grid_mg_set_hierarchy", "ccp_grid_mg_get_hierarchy",
     "ccp_grid_residual_norm2", "ccp_grid_abs_sum", "ccp_grid_assemble_rhs", "ccp_grid_assemble_from_images", "ccp_grid_store_u8",
     "ccp_grid_set_x_u8", "ccp_grid_assemble_region_rhs", "ccp_grid_assemble_clone", "ccp_grid_store_u8_composite",
     "ccp_grid_last_timing", "ccp_grid_region_begin", "ccp_grid_region_end",
@@ -180,6 +183,8 @@ def load() -> C.CDLL:
     L.ccp_grid_mg_conjugate_gradient.argtypes = [vp, dbl, i32, i32, C.POINTER(Report)]
     L.ccp_grid_mg_apply.argtypes = [vp, i32]
     L.ccp_grid_mg_level.argtypes = [vp, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
+    L.ccp_grid_mg_set_hierarchy.argtypes = [vp, i32]
+    L.ccp_grid_mg_get_hierarchy.argtypes = [vp, C.POINTER(i32)]
     L.ccp_csr_apply_to_vector.argtypes = [vp, vp, vp]
     L.ccp_csr_residual_norm2.argtypes = [vp, vp, vp, C.POINTER(dbl), C.POINTER(dbl)]
     L.ccp_grid_create.argtypes = [C.POINTER(GridDesc), C.POINTER(vp)]
@@ -663,6 +668,23 @@ class Grid:
     def mg_apply(self, smoothing_sweeps=2):
         """x := M^-1 b (one V-cycle per channel; diagnostic)."""
         check(self.L.ccp_grid_mg_apply(self.h, smoothing_sweeps), "ccp_grid_mg_apply")
+
+    def mg_set_hierarchy(self, kind):
+        """The hierarchy kind of a weighted handle: "galerkin" (the default: coarse correction scaled by 2) or "rescaled"
+        (edge weights halved per level, correction unscaled: the one to choose with data weights > 0), or the integers
+        MG_HIERARCHY_*.  A change drops the cached hierarchy."""
+        if isinstance(kind, str):
+            if kind not in MG_HIERARCHIES:
+                raise ValueError(f"hierarchy must be one of {sorted(MG_HIERARCHIES)}, not {kind!r}")
+            kind = MG_HIERARCHIES[kind]
+        check(self.L.ccp_grid_mg_set_hierarchy(self.h, int(kind)), "ccp_grid_mg_set_hierarchy")
+
+    @property
+    def mg_hierarchy(self):
+        """The handle's hierarchy kind: "galerkin" or "rescaled"."""
+        kind = C.c_int32()
+        check(self.L.ccp_grid_mg_get_hierarchy(self.h, C.byref(kind)), "ccp_grid_mg_get_hierarchy")
+        return next(name for name, value in MG_HIERARCHIES.items() if value == kind.value)
 
     def mg_levels(self):
         """The multigrid hierarchy: one (diag, w_east, w_south) triple of H_k x W_k arrays per level, level 0 first."""

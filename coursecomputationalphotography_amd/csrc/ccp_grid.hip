@@ -138,6 +138,7 @@ struct ccp_grid {
     bool weighted = false;
     bool has_op = false;
     DevBuf<double> wop, wpart;
+    int mg_kind = CCP_MG_HIERARCHY_GALERKIN;   // ccp_grid_mg_set_hierarchy (weighted handles; survives ccp_grid_set_weights_*)
 };
 
 namespace {
@@ -1150,11 +1151,21 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     v->wwe = op ? op + n : nullptr;
     v->wws = op ? op + 2 * n : nullptr;
     v->wlam = op ? op + 3 * n : nullptr;
+    v->hierarchy_kind = g->mg_kind;
     v->stream = g->stream;
     v->cache = &g->mg;
     v->comm = g->comm;
     v->part = g->part.empty() ? nullptr : g->part.data();
     v->ghost = g->desc.ghost;
+    return CCP_OK;
+}
+
+int ccp::grid_mg_hierarchy_slot(ccp_grid *g, bool *weighted, int **kind, MgHierarchy ***cache)
+{
+    CCP_TRY(bind(g));
+    *weighted = g->weighted;
+    *kind = &g->mg_kind;
+    *cache = &g->mg;
     return CCP_OK;
 }
 

@@ -33,6 +33,7 @@ struct MgHierarchy {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int kind0 = kMgSolve;
     bool weighted = false;           // level 0 is a weighted handle's stored operator; every level carries lambda (arr 6)
+    double cs = 2.0;                 // the coarse correction's scale (`cs` of k_mg_tile, k_mg_tail): 1.0 on a rescaled weighted hierarchy
     double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda
     ~MgHierarchy()
     {
@@ -67,6 +68,9 @@ int build(const GridMgView &v, MgHierarchy **out)
     std::unique_ptr<MgHierarchy> own(h);
     h->kind0 = v.weighted ? kMgCoarse : v.masked ? kMgMasked : kMgSolve;
     h->weighted = v.weighted;
+    // (ccp_grid_mg_set_hierarchy drops the cached hierarchy when the kind changes: a cached one is of the handle's kind)
+    const bool rescaled = v.weighted && v.hierarchy_kind == CCP_MG_HIERARCHY_RESCALED;
+    h->cs = rescaled ? 1.0 : 2.0;
     const int per_level = v.weighted ? 7 : 6;
     MgLevel l0{};
     l0.W = v.geom.W;
@@ -118,7 +122,7 @@ int build(const GridMgView &v, MgHierarchy **out)
         if (v.weighted)
             hipLaunchKernelGGL(k_mg_coarsen_weighted, cells_grid(h->lv[k + 1].W, h->lv[k + 1].H), dim3(kBlock), 0, v.stream, h->lv[k],
                                k ? static_cast<const double *>(h->arr(k, 6)) : v.wlam, h->lv[k + 1], h->arr(k + 1, 0), h->arr(k + 1, 1),
-                               h->arr(k + 1, 2), h->arr(k + 1, 6));
+                               h->arr(k + 1, 2), h->arr(k + 1, 6), rescaled ? 0.5 : 1.0);
         else
             coarsen(level_kind(*h, k), v.stream, h->lv[k], h->lv[k + 1], 0, h->lv[k + 1].H, h->arr(k + 1, 0), h->arr(k + 1, 1), h->arr(k + 1, 2));
         CCP_HIP(hipGetLastError());
@@ -155,7 +159,7 @@ template <int KIND>
 void pre_t(hipStream_t s, const MgLevel &f, const double *b, double *t, int nu, const CgState *st)
 {
     hipLaunchKernelGGL((k_mg_tile<KIND, false>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, static_cast<const double *>(nullptr), t,
-                       f, static_cast<const double *>(nullptr), nu, st);
+                       f, static_cast<const double *>(nullptr), 2.0, nu, st);
 }
 
 void pre(int kind, hipStream_t s, const MgLevel &f, const double *b, double *t, int nu, const CgState *st)
@@ -176,12 +180,13 @@ void restrict_rows(int kind, hipStream_t s, const MgLevel &f, const double *b, c
     else hipLaunchKernelGGL((k_mg_restrict<kMgSolve>), grid, dim3(kBlock), 0, s, f, b, t, c, Y0, bc, st);
 }
 
-void post(int kind, hipStream_t s, const MgLevel &f, const double *b, const double *t, double *z, const MgLevel &c, const double *ec, int nu,
-          const CgState *st)
+// cs: the scale of the coarse correction (MgHierarchy::cs)
+void post(int kind, hipStream_t s, const MgLevel &f, const double *b, const double *t, double *z, const MgLevel &c, const double *ec, double cs,
+          int nu, const CgState *st)
 {
-    if (kind == kMgCoarse) hipLaunchKernelGGL((k_mg_tile<kMgCoarse, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, nu, st);
-    else if (kind == kMgMasked) hipLaunchKernelGGL((k_mg_tile<kMgMasked, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, nu, st);
-    else hipLaunchKernelGGL((k_mg_tile<kMgSolve, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, nu, st);
+    if (kind == kMgCoarse) hipLaunchKernelGGL((k_mg_tile<kMgCoarse, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, cs, nu, st);
+    else if (kind == kMgMasked) hipLaunchKernelGGL((k_mg_tile<kMgMasked, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, cs, nu, st);
+    else hipLaunchKernelGGL((k_mg_tile<kMgSolve, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, cs, nu, st);
 }
 
 // The levels from `from` (held whole) down: tiles above the tail, then k_mg_tail, then back up to `from`.  Every launch
@@ -209,8 +214,8 @@ int whole_levels(MgHierarchy &h, hipStream_t s, int from, const double *b0, doub
         t.ws[i] = l.ws;
         off += l.W * l.H;
     }
-    hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(kBlock), 0, s, t, B(h.tail), Z(h.tail), nu, st);
-    for (int k = h.tail - 1; k >= from; --k) post(level_kind(h, k), s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], h.arr(k + 1, 4), nu, st);
+    hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(kBlock), 0, s, t, B(h.tail), Z(h.tail), h.cs, nu, st);
+    for (int k = h.tail - 1; k >= from; --k) post(level_kind(h, k), s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], h.arr(k + 1, 4), h.cs, nu, st);
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 }
@@ -220,13 +225,13 @@ int vcycle_1x1(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int 
 {
     if (h.kind0 == kMgCoarse)
         hipLaunchKernelGGL((k_mg_tile<kMgCoarse, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
-                           static_cast<const double *>(nullptr), nu, st);
+                           static_cast<const double *>(nullptr), 2.0, nu, st);
     else if (h.kind0 == kMgMasked)
         hipLaunchKernelGGL((k_mg_tile<kMgMasked, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
-                           static_cast<const double *>(nullptr), nu, st);
+                           static_cast<const double *>(nullptr), 2.0, nu, st);
     else
         hipLaunchKernelGGL((k_mg_tile<kMgSolve, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
-                           static_cast<const double *>(nullptr), nu, st);
+                           static_cast<const double *>(nullptr), 2.0, nu, st);
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 }
@@ -434,7 +439,7 @@ int vcycle_rowblocked(MgHierarchy &h, const Net &n, const double *b0, double *z0
     CCP_TRY(whole_levels(h, n.s, h.dist, b0, z0, nu, st));
     for (int k = h.dist - 1; k >= 0; --k) {
         if (k + 1 < h.dist) CCP_TRY(exchange_rows(h, n, k + 1, Z(k + 1), nu + 1));
-        post(level_kind(h, k), n.s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], Z(k + 1), nu, st);
+        post(level_kind(h, k), n.s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], Z(k + 1), 2.0, nu, st);
     }
     CCP_HIP(hipGetLastError());
     return CCP_OK;
@@ -484,6 +489,32 @@ try {
     const long n = v.geom.ch_stride;
     for (int ch = 0; ch < v.channels; ++ch) CCP_TRY(vcycle(*h, v.stream, v.b + ch * n, v.x + ch * n, nu, nullptr));
     CCP_HIP(hipStreamSynchronize(v.stream));
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_set_hierarchy(ccp_grid *g, int32_t kind)
+try {
+    bool weighted = false;
+    int *slot = nullptr;
+    MgHierarchy **cache = nullptr;
+    CCP_TRY(grid_mg_hierarchy_slot(g, &weighted, &slot, &cache));
+    if (kind != CCP_MG_HIERARCHY_GALERKIN && kind != CCP_MG_HIERARCHY_RESCALED) return CCP_ERR_BAD_ARG;
+    if (!weighted) return CCP_ERR_UNSUPPORTED;
+    if (*slot == kind) return CCP_OK;
+    *slot = kind;
+    mg_release(*cache);                                            // the cached levels belong to the other kind
+    *cache = nullptr;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_get_hierarchy(ccp_grid *g, int32_t *kind)
+try {
+    bool weighted = false;
+    int *slot = nullptr;
+    MgHierarchy **cache = nullptr;
+    CCP_TRY(grid_mg_hierarchy_slot(g, &weighted, &slot, &cache));
+    if (!kind) return CCP_ERR_BAD_ARG;
+    *kind = *slot;
     return CCP_OK;
 } CCP_ABI_CATCH
 

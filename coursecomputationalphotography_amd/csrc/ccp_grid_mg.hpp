@@ -20,6 +20,11 @@
 // (gs_update / apply_row, the masked kernels' interior formula); coarse levels s = 0; s += wN xN; s += wW xW;
 // s += wE xE; s += wS xS; x = (b + s) / d; r = b - (d x - s).  Dead pixels are written 0 by every sweep.
 //
+// The 2.0 is the hierarchy's correction scale, a uniform kernel argument `cs`: a weighted handle's rescaled hierarchy
+// (CCP_MG_HIERARCHY_RESCALED: its coarsening halves the edge weights once per level and leaves lambda alone) passes 1.0,
+// everything else 2.0.  cs * e_c is exact for both, so z + cs * e_c gives the same bits whether or not the compiler
+// contracts it to an fma.
+//
 // The levels whose sides are both <= kMgTailSide (below level 0) run in ONE single-workgroup launch, k_mg_tail, with
 // all of them resident in LDS (at most kMgTailCells cells x 5 doubles = 54.6 KB).  Every other level takes three
 // launches: the nu pre-smoothing sweeps in one pass (k_mg_tile), residual + restriction (k_mg_restrict), prolongation
@@ -225,19 +230,21 @@ k_mg_coarsen(MgLevel lv, MgLevel cv, int Y0, double *__restrict__ d, double *__r
 // lambda_c = (l00 + l10) + (l01 + l11); d = lambda_c; d += north; d += west; d += east; d += south, each side the sum
 // of the two fine edge weights that leave the aggregate there (north: the ws of the row above, left child first; west:
 // the we of the column to the left, upper child first); we / ws as k_mg_coarsen forms them.  Every term is >= 0, so a
-// coarse diagonal is never a difference.  grid = (ceil(Wc/kBlock), Hc).
+// coarse diagonal is never a difference.  `edge` (uniform) scales the four side sums: 1.0 for the Galerkin hierarchy,
+// 0.5 for the rescaled one (CCP_MG_HIERARCHY_RESCALED), whose correction is then added unscaled; both products are
+// exact, and lambda_c takes no factor.  grid = (ceil(Wc/kBlock), Hc).
 static __global__ void __launch_bounds__(kBlock)
 k_mg_coarsen_weighted(MgLevel lv, const double *__restrict__ lam, MgLevel cv, double *__restrict__ d, double *__restrict__ we,
-                      double *__restrict__ ws, double *__restrict__ lam_c)
+                      double *__restrict__ ws, double *__restrict__ lam_c, double edge)
 {
     const int X = blockIdx.x * kBlock + threadIdx.x, Y = blockIdx.y;
     if (X >= cv.W) return;
     const int x = 2 * X, y = 2 * Y;
     const double lc = (mg_ld(lam, lv, x, y) + mg_ld(lam, lv, x + 1, y)) + (mg_ld(lam, lv, x, y + 1) + mg_ld(lam, lv, x + 1, y + 1));
-    const double n = mg_ld(lv.ws, lv, x, y - 1) + mg_ld(lv.ws, lv, x + 1, y - 1);
-    const double w = mg_ld(lv.we, lv, x - 1, y) + mg_ld(lv.we, lv, x - 1, y + 1);
-    const double e = mg_ld(lv.we, lv, x + 1, y) + mg_ld(lv.we, lv, x + 1, y + 1);
-    const double s = mg_ld(lv.ws, lv, x, y + 1) + mg_ld(lv.ws, lv, x + 1, y + 1);
+    const double n = edge * (mg_ld(lv.ws, lv, x, y - 1) + mg_ld(lv.ws, lv, x + 1, y - 1));
+    const double w = edge * (mg_ld(lv.we, lv, x - 1, y) + mg_ld(lv.we, lv, x - 1, y + 1));
+    const double e = edge * (mg_ld(lv.we, lv, x + 1, y) + mg_ld(lv.we, lv, x + 1, y + 1));
+    const double s = edge * (mg_ld(lv.ws, lv, x, y + 1) + mg_ld(lv.ws, lv, x + 1, y + 1));
     double dc = lc;
     dc += n;
     dc += w;
@@ -280,7 +287,7 @@ k_mg_restrict(MgLevel lv, const double *__restrict__ b, const double *__restrict
     bc[mg_at(cv.pitch, X, Y)] = (r00 + r10) + (r01 + r11);
 }
 
-// All nu pre-smoothing sweeps from z = 0 (POST = false: red, black), or the prolongation z += 2.0 * e_c on live pixels and
+// All nu pre-smoothing sweeps from z = 0 (POST = false: red, black), or the prolongation z += cs * e_c on live pixels and
 // all nu post-smoothing sweeps (POST = true: black, red), in ONE pass: a workgroup owns a kMgTileW x kMgTileH tile of the
 // level, loads b (and z, e_c) of the tile plus a halo of 2 nu cells on every side into LDS, runs the 2 nu half-sweeps
 // there and stores the tile.  A halo cell next to the edge of the LDS region sees 0.0 for its missing neighbour; the
@@ -295,7 +302,7 @@ k_mg_restrict(MgLevel lv, const double *__restrict__ b, const double *__restrict
 template <int KIND, bool POST>
 __global__ void __launch_bounds__(kBlock)
 k_mg_tile(MgLevel lv, const double *__restrict__ b, const double *__restrict__ z_in, double *__restrict__ z_out, MgLevel cv,
-          const double *__restrict__ ec, int nu, const CgState *__restrict__ st)
+          const double *__restrict__ ec, double cs, int nu, const CgState *__restrict__ st)
 {
     extern __shared__ double tile_lds[];
     if (st && !st->active) return;                                   // (uniform)
@@ -310,7 +317,7 @@ k_mg_tile(MgLevel lv, const double *__restrict__ b, const double *__restrict__ z
             bv = b[at];
             if (POST) {
                 zv = z_in[at];
-                if (mg_live<KIND>(lv, x, y)) zv = zv + 2.0 * ec[mg_at(cv.pitch, x >> 1, ((lv.y0 + y) >> 1) - cv.y0)];
+                if (mg_live<KIND>(lv, x, y)) zv = zv + cs * ec[mg_at(cv.pitch, x >> 1, ((lv.y0 + y) >> 1) - cv.y0)];   // (cs * e_c is exact)
             }
         }
         sb[i] = bv;
@@ -348,9 +355,10 @@ struct MgTail {
     const double *d[kMgTailLevels], *we[kMgTailLevels], *ws[kMgTailLevels];
 };
 
-// b_top: right-hand side of the tail's first level (its level layout); z_top: its correction.  grid = 1 workgroup.
+// b_top: right-hand side of the tail's first level (its level layout); z_top: its correction; cs: the correction scale
+// (2.0 or 1.0, as k_mg_tile's).  grid = 1 workgroup.
 static __global__ void __launch_bounds__(kBlock)
-k_mg_tail(MgTail t, const double *__restrict__ b_top, double *__restrict__ z_top, int nu, const CgState *__restrict__ st)
+k_mg_tail(MgTail t, const double *__restrict__ b_top, double *__restrict__ z_top, double cs, int nu, const CgState *__restrict__ st)
 {
     if (st && !st->active) return;
     __shared__ double sd[kMgTailCells], swe[kMgTailCells], sws[kMgTailCells], sb[kMgTailCells], sz[kMgTailCells];
@@ -425,7 +433,7 @@ k_mg_tail(MgTail t, const double *__restrict__ b_top, double *__restrict__ z_top
         const int W = t.W[k], n = t.W[k] * t.H[k], o = t.off[k], Wc = t.W[k + 1], oc = t.off[k + 1];
         for (int i = threadIdx.x; i < n; i += kBlock) {
             const int X = i % W, Y = i / W;
-            if (sd[o + i] != 0.0) sz[o + i] = sz[o + i] + 2.0 * sz[oc + (Y >> 1) * Wc + (X >> 1)];
+            if (sd[o + i] != 0.0) sz[o + i] = sz[o + i] + cs * sz[oc + (Y >> 1) * Wc + (X >> 1)];
         }
         __syncthreads();
         for (int s = 0; s < nu; ++s) {

@@ -122,13 +122,15 @@ def _weight(w, H, W, dev):
     return torch.tensor(float(w), dtype=torch.float64, device=torch.device("cuda", dev)).expand(H, W)
 
 
-def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=None, out_dtype=None, epsilon: float = 1e-10):
+def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=None, out_dtype=None, epsilon: float = 1e-10,
+                   hierarchy="galerkin"):
     """Minimise  sum wx (u(x+1,y) - u(x,y) - gx)^2 + sum wy (u(x,y+1) - u(x,y) - gy)^2 + sum data_weight (u - f)^2
     for every channel on a weighted grid handle (CCP_GRID_WEIGHTED), by multigrid-preconditioned CG (at most
     `iterations` iterations to sqrt(r'r) < epsilon) from x = f.  gx, gy: float32 H x W x C tensors or None (zero
     guidance); f: u8 / float32 / float64 H x W x C or None (zero, and x starts at 0).  wx, wy, data_weight: H x W
     float32 / float64 tensors or scalars (None: wx = wy = 1, data_weight = 0).  out_dtype: torch.uint8 (the default: the
-    clamped solution) or a float dtype (x itself)."""
+    clamped solution) or a float dtype (x itself).  hierarchy: "galerkin" (the default) or "rescaled"
+    (capi.Grid.mg_set_hierarchy): with data_weight > 0 "rescaled" needs far fewer iterations."""
     import torch
     out_dtype = torch.uint8 if out_dtype is None else out_dtype
     ref = next((t for t in (f, gx, gy) if t is not None), None)
@@ -140,6 +142,7 @@ def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=Non
     g = capi.Grid(W, H, C, device=dev, weighted=True)
     g.set_stream(torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream)
     try:
+        g.mg_set_hierarchy(hierarchy)
         g.set_weights_tensor(_weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev))
         g.assemble_weighted_rhs_tensor(gx, gy, f, init_x=f is not None)
         if f is None:
@@ -169,13 +172,15 @@ def wls_weights(image, lam: float = 1.0, alpha: float = 1.2, eps: float = 1e-4):
     return wx, wy
 
 
-def wls_smooth(image, iterations: int, lam: float = 1.0, alpha: float = 1.2, eps: float = 1e-4, epsilon: float = 1e-10):
+def wls_smooth(image, iterations: int, lam: float = 1.0, alpha: float = 1.2, eps: float = 1e-4, epsilon: float = 1e-10,
+               hierarchy="galerkin"):
     """WLS edge-preserving smoothing (Farbman et al. 2008): u minimises sum (u - image)^2 + sum wx (du/dx)^2 +
     sum wy (du/dy)^2 with wls_weights (torch ops: plumbing), solved on a weighted grid handle.  image: u8 or float
-    H x W (x C) tensor; returns the same dtype and shape (u8: clamped)."""
+    H x W (x C) tensor; returns the same dtype and shape (u8: clamped).  hierarchy: as weighted_solve's."""
     import torch
     wx, wy = wls_weights(image, lam, alpha, eps)
     f = image if image.dim() == 3 else image.unsqueeze(-1)
     out_dtype = torch.uint8 if image.dtype == torch.uint8 else image.dtype
-    u = weighted_solve(None, None, f, iterations, wx=wx, wy=wy, data_weight=1.0, out_dtype=out_dtype, epsilon=epsilon)
+    u = weighted_solve(None, None, f, iterations, wx=wx, wy=wy, data_weight=1.0, out_dtype=out_dtype, epsilon=epsilon,
+                       hierarchy=hierarchy)
     return u if image.dim() == 3 else u[..., 0]

@@ -252,9 +252,14 @@ inline void SeamlessClone(const ImageView &source, const ImageView &target, cons
 // CV_32FC1 views sharing one row step, each may be null (wx, wy: 1 everywhere; lambda: 0).  The start vector is f (0
 // without it); out: u8, the clamped solution.  Only Solver::MultigridConjugateGradient (at most `iterations` iterations,
 // epsilon 1e-10) solves this system; any other solver throws std::invalid_argument, as does every other failure.
+// hierarchy: the preconditioner's hierarchy kind (ccp_grid_mg_set_hierarchy); with lambda > 0 Hierarchy::Rescaled needs far
+// fewer iterations, the default keeps the Galerkin one.
+enum class Hierarchy { Galerkin = CCP_MG_HIERARCHY_GALERKIN, Rescaled = CCP_MG_HIERARCHY_RESCALED };
+
 inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageView *f, const ImageView *wx, const ImageView *wy,
                           const ImageView *lambda, ImageView &out, int iterations,
-                          Solver solver = Solver::MultigridConjugateGradient, int device = 0)
+                          Solver solver = Solver::MultigridConjugateGradient, int device = 0,
+                          Hierarchy hierarchy = Hierarchy::Galerkin)
 {
     if (solver != Solver::MultigridConjugateGradient)
         throw std::invalid_argument("SolveWeighted: only Solver::MultigridConjugateGradient solves a weighted system");
@@ -275,6 +280,7 @@ inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageV
         }
     auto fp = [](const ImageView *v) { return v ? static_cast<const float *>(v->data) : nullptr; };
     detail::GridHandle h(out.cols, out.rows, C, device, CCP_GRID_WEIGHTED);
+    detail::check(ccp_grid_mg_set_hierarchy(h.g, (int32_t)hierarchy), "ccp_grid_mg_set_hierarchy");
     detail::check(ccp_grid_set_weights_host(h.g, fp(wx), fp(wy), fp(lambda), (int64_t)wstep), "ccp_grid_set_weights_host");
     const int64_t gstep = gx ? (int64_t)gx->step : gy ? (int64_t)gy->step : 0;
     detail::check(ccp_grid_assemble_weighted_rhs(h.g, fp(gx), fp(gy), gstep, fp(f), f ? (int64_t)f->step : 0, f ? 1 : 0),

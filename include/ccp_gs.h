@@ -264,7 +264,21 @@ typedef struct ccp_grid_desc {
  * The multigrid hierarchy of a weighted handle carries lambda on every level and forms each coarse diagonal as a sum of
  * non-negative terms (no cancellation with real-valued weights):
  *     lambda_c = (l00 + l10) + (l01 + l11);   d_c = lambda_c; d_c += north; += west; += east; += south
- * each side's term the sum of the two fine edge weights that leave the aggregate there. */
+ * each side's term the sum of the two fine edge weights that leave the aggregate there.
+ *
+ * That hierarchy (CCP_MG_HIERARCHY_GALERKIN, the default) doubles every coarse correction.  The factor 2 suits the edge
+ * part of the operator and not the data part, so with lambda > 0 the corrections over-shoot from the level where lambda_c
+ * dominates.  ccp_grid_mg_set_hierarchy(g, CCP_MG_HIERARCHY_RESCALED) chooses the consistent one instead.  Level 0 is the
+ * stored operator either way; level k+1 from level k, per coarse cell (X,Y), in this order:
+ *     lambda_c = (l00 + l10) + (l01 + l11)
+ *     north = 0.5 * (ws(2X,2Y-1) + ws(2X+1,2Y-1))     west  = 0.5 * (we(2X-1,2Y) + we(2X-1,2Y+1))
+ *     east  = 0.5 * (we(2X+1,2Y) + we(2X+1,2Y+1))     south = 0.5 * (ws(2X,2Y+1) + ws(2X+1,2Y+1))
+ *     d_c = lambda_c; d_c += north; d_c += west; d_c += east; d_c += south;   we_c = east;  ws_c = south
+ * and the V-cycle adds the coarse correction unscaled (z += e_c on live pixels); everything else is the V-cycle of
+ * ccp_grid_mg_conjugate_gradient.  Halving is exact: on level k the rescaled we, ws are 2^-k times the default
+ * hierarchy's bit for bit, lambda is the same bit for bit, only d differs.  With lambda = 0 the two preconditioners are
+ * the same in exact arithmetic; with lambda > 0 choose RESCALED (NOTES R10.1: the screened iteration count stops growing
+ * with the image and with 1 / lambda). */
 #define CCP_GRID_WEIGHTED 2
 
 /* Device layout, for callers that move halos themselves (torch.distributed / RCCL).
@@ -400,6 +414,17 @@ int ccp_grid_mg_apply(ccp_grid *g, int32_t smoothing_sweeps);
  * sizes); diag / w_east / w_south hold width * height doubles. */
 int ccp_grid_mg_level(ccp_grid *g, int32_t level, int32_t *n_levels, int32_t *width, int32_t *height, double *diag,
                       double *w_east, double *w_south);
+
+/* The hierarchy kind of a weighted handle (CCP_GRID_WEIGHTED above has both definitions).  ccp_grid_mg_conjugate_gradient,
+ * ccp_grid_mg_apply and ccp_grid_mg_level work on the chosen kind. */
+#define CCP_MG_HIERARCHY_GALERKIN 0      /* coarse correction scaled by 2 (the default) */
+#define CCP_MG_HIERARCHY_RESCALED 1      /* edge weights halved per level, lambda carried, correction unscaled */
+/* Weighted handles only (structured and Dirichlet-mask handles: CCP_ERR_UNSUPPORTED); an unknown kind or a NULL handle:
+ * CCP_ERR_BAD_ARG.  A change of kind drops the cached hierarchy, as ccp_grid_set_weights_* does; setting the current kind
+ * does nothing.  May be called before the operator is set, and the kind survives ccp_grid_set_weights_*. */
+int ccp_grid_mg_set_hierarchy(ccp_grid *g, int32_t kind);
+/* The handle's kind (GALERKIN on every handle that is not weighted).  NULL: CCP_ERR_BAD_ARG. */
+int ccp_grid_mg_get_hierarchy(ccp_grid *g, int32_t *kind);
 
 /* ----------------------------------------------------------------------------------------
  * Row blocks across the GPUs of one node (BASELINE configs[3]).  One process (or host

@@ -3,7 +3,9 @@
 screened Poisson system (lambda = 1e-2, wx = wy = 1) at 16384^2, WLS edge-preserving smoothing (Farbman et al. 2008:
 lambda 1, alpha 1.2) at 4096^2 x 3 and at the reference's image size 752x566 x 3, and the structured handle's MG-PCG at
 16384^2 beside them (ms per PCG iteration: the weighted level 0 reads its 24 B/px of stored coefficients).  One JSON
-line per case, as tools/mg_bench.py.  The screened and structured systems are manufactured (b = A x, x uniform
+line per case and hierarchy kind (--hierarchy: a comma list of galerkin / rescaled, solved in that order on the same handle;
+the default runs both, and a list such as galerkin,galerkin,rescaled measures the spread of one kind against itself beside
+the difference between the kinds), as tools/mg_bench.py.  The screened and structured systems are manufactured (b = A x, x uniform
 [0, 255)); the WLS systems smooth a synthetic image of flat patches with edges and noise, built on the device."""
 import argparse, ctypes, json, os, sys, time
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
@@ -24,53 +26,67 @@ def image(W, H, C, dev):
     return img.clamp(0, 255).to(torch.uint8)
 
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--cases", default=",".join(CASES))
-ap.add_argument("--sweeps", type=int, default=2)
-ap.add_argument("--repeat", type=int, default=3)
-ap.add_argument("--max-iterations", type=int, default=200)
-a = ap.parse_args()
-dev = torch.device("cuda", 0)
-for name in a.cases.split(","):
-    W, H, C, kind = CASES[name]
-    g = capi.Grid(W, H, C, weighted=kind != "structured")
-    f = None
-    if kind == "screened":
-        lam = torch.tensor(1e-2, dtype=torch.float64, device=dev).expand(H, W)
-        g.set_weights_tensor(None, None, lam)
-    elif kind == "wls":
-        f = image(W, H, C, dev)
-        wx, wy = tensor_ops.wls_weights(f, lam=1.0, alpha=1.2, eps=1e-4)
-        g.set_weights_tensor(wx, wy, torch.tensor(1.0, dtype=torch.float64, device=dev).expand(H, W))
-        g.assemble_weighted_rhs_tensor(None, None, f, init_x=True)
-        torch.cuda.synchronize()
-    if f is None:
-        g.randomize_x(1234, 0.0, 255.0)
-        g.b_from_x()
-    g.synchronize()
-    t0 = time.perf_counter()
-    nl = ctypes.c_int32()                                       # the first MG call builds the hierarchy
-    capi.check(g.L.ccp_grid_mg_level(g.h, 0, ctypes.byref(nl), None, None, None, None, None), "ccp_grid_mg_level")
-    g.synchronize()
-    setup_ms = (time.perf_counter() - t0) * 1e3
-    best = None
-    for _ in range(a.repeat):
-        if f is None:
-            g.fill_x(0.0)
-        else:
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--hierarchy", default="galerkin,rescaled", help="comma list of galerkin / rescaled, in the order to run them")
+    ap.add_argument("--sweeps", type=int, default=2)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--max-iterations", type=int, default=200)
+    a = ap.parse_args()
+    kinds = a.hierarchy.split(",")
+    for k in kinds:
+        if k not in capi.MG_HIERARCHIES:
+            ap.error(f"--hierarchy: {k!r} is not one of {sorted(capi.MG_HIERARCHIES)}")
+    dev = torch.device("cuda", 0)
+    for name in a.cases.split(","):
+        W, H, C, kind = CASES[name]
+        g = capi.Grid(W, H, C, weighted=kind != "structured")
+        f = None
+        if kind == "screened":
+            lam = torch.tensor(1e-2, dtype=torch.float64, device=dev).expand(H, W)
+            g.set_weights_tensor(None, None, lam)
+        elif kind == "wls":
+            f = image(W, H, C, dev)
+            wx, wy = tensor_ops.wls_weights(f, lam=1.0, alpha=1.2, eps=1e-4)
+            g.set_weights_tensor(wx, wy, torch.tensor(1.0, dtype=torch.float64, device=dev).expand(H, W))
             g.assemble_weighted_rhs_tensor(None, None, f, init_x=True)
             torch.cuda.synchronize()
-        _, bb = g.residual_norm2()
-        eps = 1e-10 * float(np.sqrt(bb.max()))
-        reps = g.mg_conjugate_gradient(eps, a.max_iterations, a.sweeps)
-        secs = sum(r.seconds for r in reps)
-        if best is None or secs < best[0]:
-            best = (secs, [r.iterations for r in reps], [bool(r.converged) for r in reps])
-    rr, bb = g.residual_norm2()
-    secs, its, conv = best
-    updates = sum(i + 1 for i in its)                           # as tools/mg_bench.py counts them
-    print(json.dumps({"case": name, "width": W, "height": H, "channels": C, "kind": kind, "levels": nl.value,
-                      "smoothing_sweeps": a.sweeps, "iterations": its, "converged": conv, "ms_to_1e-10": secs * 1e3,
-                      "ms_per_pcg_iteration": secs * 1e3 / updates, "setup_ms": setup_ms,
-                      "rel_residual": float(np.sqrt(rr / bb).max())}), flush=True)
-    g.close()
+        if f is None:
+            g.randomize_x(1234, 0.0, 255.0)
+            g.b_from_x()
+        g.synchronize()
+        # a structured handle has the one hierarchy
+        for run, hierarchy in enumerate(kinds if kind != "structured" else ["galerkin"]):
+            if kind != "structured":
+                g.mg_set_hierarchy(hierarchy)
+            t0 = time.perf_counter()
+            nl = ctypes.c_int32()                                   # the first MG call of a kind builds its hierarchy
+            capi.check(g.L.ccp_grid_mg_level(g.h, 0, ctypes.byref(nl), None, None, None, None, None), "ccp_grid_mg_level")
+            g.synchronize()
+            setup_ms = (time.perf_counter() - t0) * 1e3
+            best = None
+            for _ in range(a.repeat):
+                if f is None:
+                    g.fill_x(0.0)
+                else:
+                    g.assemble_weighted_rhs_tensor(None, None, f, init_x=True)
+                    torch.cuda.synchronize()
+                _, bb = g.residual_norm2()
+                eps = 1e-10 * float(np.sqrt(bb.max()))
+                reps = g.mg_conjugate_gradient(eps, a.max_iterations, a.sweeps)
+                secs = sum(r.seconds for r in reps)
+                if best is None or secs < best[0]:
+                    best = (secs, [r.iterations for r in reps], [bool(r.converged) for r in reps])
+            rr, bb = g.residual_norm2()
+            secs, its, conv = best
+            updates = sum(i + 1 for i in its)                       # as tools/mg_bench.py counts them
+            print(json.dumps({"case": name, "width": W, "height": H, "channels": C, "kind": kind, "hierarchy": hierarchy, "run": run,
+                              "levels": nl.value, "smoothing_sweeps": a.sweeps, "max_iterations": a.max_iterations, "iterations": its, "converged": conv,
+                              "ms_to_1e-10": secs * 1e3, "ms_per_pcg_iteration": secs * 1e3 / updates, "setup_ms": setup_ms,
+                              "rel_residual": float(np.sqrt(rr / bb).max())}), flush=True)
+        g.close()
+
+
+if __name__ == "__main__":
+    main()
