@@ -2160,262 +2160,6 @@ try {
     return edge_timeout_status(g);
 } CCP_ABI_CATCH
 
-int ccp_grid_assemble_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t row_stride_bytes, const int32_t *constraint)
-try {
-    CCP_TRY(not_weighted(g));
-    CCP_TRY(bind(g));
-    if (!gx || !gy || !constraint) return CCP_ERR_BAD_ARG;
-    if (g->masked) return CCP_ERR_UNSUPPORTED;            // SolveChannel's right-hand side belongs to SolveChannel's matrix
-    if (g->ghost_top || g->ghost_bottom || g->desc.row_count != g->desc.height) return CCP_ERR_STATE;
-    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
-    const size_t row_bytes = (size_t)W * C * sizeof(float);
-    if (row_stride_bytes < (int64_t)row_bytes) return CCP_ERR_BAD_ARG;
-    DevBuf<float> dgx, dgy;
-    DevBuf<int> dcons;
-    CCP_TRY(dgx.alloc((size_t)W * H * C));
-    CCP_TRY(dgy.alloc((size_t)W * H * C));
-    CCP_TRY(dcons.alloc(C));
-    // only rows y < H-1 and columns x < W-1 are defined in the reference (PhotoMontage.cpp:416-425);
-    // the kernel never reads the rest, but the copy must not touch it on the host either.
-    const size_t copy_rows = H > 1 ? (size_t)(H - 1) : 0;
-    CCP_HIP(hipMemsetAsync(dgx.p, 0, (size_t)W * H * C * sizeof(float), g->stream));
-    CCP_HIP(hipMemsetAsync(dgy.p, 0, (size_t)W * H * C * sizeof(float), g->stream));
-    if (copy_rows && W > 1) {
-        const size_t width_bytes = (size_t)(W - 1) * C * sizeof(float);
-        CCP_HIP(hipMemcpy2DAsync(dgx.p, row_bytes, gx, (size_t)row_stride_bytes, width_bytes, copy_rows, hipMemcpyHostToDevice, g->stream));
-        CCP_HIP(hipMemcpy2DAsync(dgy.p, row_bytes, gy, (size_t)row_stride_bytes, width_bytes, copy_rows, hipMemcpyHostToDevice, g->stream));
-    }
-    CCP_HIP(hipMemcpyAsync(dcons.p, constraint, sizeof(int) * C, hipMemcpyHostToDevice, g->stream));
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
-    const Packed<const float> pgx{dgx.p, 0, (long)W * C, C, 0}, pgy{dgy.p, 0, (long)W * C, C, 0};
-    hipLaunchKernelGGL((k_assemble_rhs<Packed<const float>, const int *>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->geom, pgx, pgy,
-                       (const int *)dcons.p);
-    CCP_HIP(hipGetLastError());
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_assemble_from_images(ccp_grid *g, const uint8_t *const *images, int32_t n_images,
-                                  int64_t image_stride_bytes, const uint8_t *label, int64_t label_stride_bytes,
-                                  int32_t init_x_from_composite)
-try {
-    CCP_TRY(not_weighted(g));
-    CCP_TRY(bind(g));
-    if (!images || !label || n_images < 1 || n_images > 256) return CCP_ERR_BAD_ARG;
-    if (g->desc.channels != 3 || g->masked) return CCP_ERR_UNSUPPORTED;      // BGR images; SolveChannel's matrix
-    if (g->ghost_top || g->ghost_bottom || g->desc.row_count != g->desc.height) return CCP_ERR_STATE;
-    const int W = g->desc.width, H = g->desc.height;
-    if (image_stride_bytes < (int64_t)W * 3 || label_stride_bytes < W) return CCP_ERR_BAD_ARG;
-    for (int k = 0; k < n_images; ++k)
-        if (!images[k]) return CCP_ERR_BAD_ARG;
-    // labels must select existing images (the reference indexes Images[label] unchecked)
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x)
-            if (label[(size_t)y * label_stride_bytes + x] >= n_images) return CCP_ERR_BAD_ARG;
-    DevBuf<uint8_t> dimg, dlab;
-    const size_t plane = (size_t)W * H * 3;
-    CCP_TRY(dimg.alloc(plane * n_images));
-    CCP_TRY(dlab.alloc((size_t)W * H));
-    for (int k = 0; k < n_images; ++k)
-        CCP_HIP(hipMemcpy2DAsync(dimg.p + plane * k, (size_t)W * 3, images[k], (size_t)image_stride_bytes, (size_t)W * 3,
-                                 (size_t)H, hipMemcpyHostToDevice, g->stream));
-    CCP_HIP(hipMemcpy2DAsync(dlab.p, (size_t)W, label, (size_t)label_stride_bytes, (size_t)W, (size_t)H,
-                             hipMemcpyHostToDevice, g->stream));
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, 3);
-    using PI = Packed<const uint8_t>;
-    const PI pimg{dimg.p, (long)plane, (long)W * 3, 3, 0}, plab{dlab.p, 0, (long)W, 1, 0};
-    if (init_x_from_composite)
-        hipLaunchKernelGGL((k_assemble_from_images<true, PI, PI>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, pimg, plab);
-    else
-        hipLaunchKernelGGL((k_assemble_from_images<false, PI, PI>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, pimg, plab);
-    CCP_HIP(hipGetLastError());
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_store_u8(ccp_grid *g, uint8_t *out, int64_t row_stride_bytes)
-try {
-    CCP_TRY(bind(g));
-    if (!out) return CCP_ERR_BAD_ARG;
-    if (g->ghost_top || g->ghost_bottom || g->desc.row_count != g->desc.height) return CCP_ERR_STATE;
-    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
-    if (row_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
-    DevBuf<uint8_t> d;
-    CCP_TRY(d.alloc((size_t)W * H * C));
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
-    hipLaunchKernelGGL((k_store_u8<Packed<uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->geom,
-                       Packed<uint8_t>{d.p, 0, (long)W * C, C, 0});
-    CCP_HIP(hipGetLastError());
-    CCP_HIP(hipMemcpy2DAsync(out, (size_t)row_stride_bytes, d.p, (size_t)W * C, (size_t)W * C, (size_t)H, hipMemcpyDeviceToHost, g->stream));
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_set_x_u8(ccp_grid *g, const uint8_t *image, int64_t row_stride_bytes)
-try {
-    CCP_TRY(bind(g));
-    if (!image) return CCP_ERR_BAD_ARG;
-    if (g->ghost_top || g->ghost_bottom || g->desc.row_count != g->desc.height) return CCP_ERR_STATE;
-    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
-    if (row_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
-    DevBuf<uint8_t> d;
-    CCP_TRY(d.alloc((size_t)W * H * C));
-    CCP_HIP(hipMemcpy2DAsync(d.p, (size_t)W * C, image, (size_t)row_stride_bytes, (size_t)W * C, (size_t)H, hipMemcpyHostToDevice, g->stream));
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
-    hipLaunchKernelGGL((k_load_u8<Packed<const uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->geom,
-                       Packed<const uint8_t>{d.p, 0, (long)W * C, C, 0});
-    CCP_HIP(hipGetLastError());
-    CCP_TRY(zero_unmasked(g, g->x.p));
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-}  // extern "C"
-
-// ---- region blend on a Dirichlet-mask grid (ccp_grid_blend.hpp) ------------------------------------------------------
-namespace {
-
-// Rows [ya, yb) of an interleaved host image (W x C elements of T per row, `stride` bytes apart) into a packed
-// device buffer, asynchronously on the handle's stream.
-template <typename T>
-int upload_window(ccp_grid *g, DevBuf<T> &dev, const T *host, int64_t stride, int ya, int yb)
-{
-    const size_t row = (size_t)g->desc.width * g->desc.channels * sizeof(T);
-    CCP_TRY(dev.alloc((size_t)(yb - ya) * g->desc.width * g->desc.channels));
-    CCP_HIP(hipMemcpy2DAsync(dev.p, row, reinterpret_cast<const char *>(host) + (size_t)ya * (size_t)stride, (size_t)stride,
-                             row, (size_t)(yb - ya), hipMemcpyHostToDevice, g->stream));
-    return CCP_OK;
-}
-
-BlendMask blend_mask(const ccp_grid *g) { return BlendMask{g->maskp.p, g->mask_edge.p, g->geom}; }
-
-// the image rows the assembly reads: the local rows and one row above and below where they exist
-void blend_window(const ccp_grid *g, int *ya, int *yb)
-{
-    *ya = std::max(0, g->geom.y0 - 1);
-    *yb = std::min(g->geom.H, g->geom.y0 + g->geom.local_rows + 1);
-}
-
-// Does the region touch the canvas's outer rows or columns?  Known from ccp_grid_set_mask_host; after the device
-// twin (whole-canvas handles only) read back once from the split mask.
-int blend_border(ccp_grid *g, bool *touches)
-{
-    if (g->mask_border < 0) {
-        if (!g->mask_edge_known) return CCP_ERR_STATE;
-        const Geom &geo = g->geom;
-        std::vector<unsigned char> split((size_t)geo.ch_stride);
-        CCP_HIP(hipMemcpyAsync(split.data(), g->maskp.p, split.size(), hipMemcpyDeviceToHost, g->stream));
-        CCP_HIP(hipStreamSynchronize(g->stream));
-        auto at = [&](int y, int x) { return split[(size_t)((2L * y + ((x + y) & 1)) * geo.pitch + (x >> 1))] != 0; };
-        bool border = false;
-        for (int y = 0; y < geo.H && !border; ++y) {
-            border = at(y, 0) || at(y, geo.W - 1);
-            if (y == 0 || y == geo.H - 1)
-                for (int x = 0; x < geo.W && !border; ++x) border = at(y, x);
-        }
-        g->mask_border = border ? 1 : 0;
-    }
-    *touches = g->mask_border != 0;
-    return CCP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ccp_grid_assemble_region_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes,
-                                 const uint8_t *canvas, int64_t canvas_stride_bytes, int32_t init_x_from_canvas)
-try {
-    CCP_TRY(not_weighted(g));
-    CCP_TRY(bind(g));
-    if (!gx || !gy || !canvas) return CCP_ERR_BAD_ARG;
-    const int W = g->desc.width, C = g->desc.channels;
-    if (field_stride_bytes < (int64_t)W * C * (int64_t)sizeof(float) || canvas_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
-    if (!g->masked) return CCP_ERR_UNSUPPORTED;           // SolveChannel's matrix has its own assembly
-    if (!g->mask_edge_known) return CCP_ERR_STATE;
-    int ya, yb;
-    blend_window(g, &ya, &yb);
-    DevBuf<float> dgx, dgy;
-    DevBuf<uint8_t> dcan;
-    CCP_TRY(upload_window(g, dgx, gx, field_stride_bytes, ya, yb));
-    CCP_TRY(upload_window(g, dgy, gy, field_stride_bytes, ya, yb));
-    CCP_TRY(upload_window(g, dcan, canvas, canvas_stride_bytes, ya, yb));
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->geom.local_rows);
-    using PF = Packed<const float>;
-    using PU = Packed<const uint8_t>;
-    const long row = (long)W * C;
-    const PF pgx{dgx.p, 0, row, C, ya}, pgy{dgy.p, 0, row, C, ya};
-    const PU pcan{dcan.p, 0, row, C, ya};
-    if (init_x_from_canvas)
-        hipLaunchKernelGGL((k_blend_field_rhs<true, PF, PU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), pgx, pgy,
-                           pcan, C);
-    else
-        hipLaunchKernelGGL((k_blend_field_rhs<false, PF, PU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), pgx, pgy,
-                           pcan, C);
-    CCP_HIP(hipGetLastError());
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    if (init_x_from_canvas) g->half_sweeps_since_refresh = 0;   // x is exact on every local row
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_assemble_clone(ccp_grid *g, const uint8_t *source, int64_t source_stride_bytes, const uint8_t *target,
-                            int64_t target_stride_bytes, int32_t mode, int32_t init)
-try {
-    CCP_TRY(not_weighted(g));
-    CCP_TRY(bind(g));
-    if (!source || !target) return CCP_ERR_BAD_ARG;
-    const int W = g->desc.width, C = g->desc.channels;
-    if (source_stride_bytes < (int64_t)W * C || target_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
-    if ((mode != CCP_CLONE_IMPORT && mode != CCP_CLONE_MIXED) || init < 0 || init > 2) return CCP_ERR_BAD_ARG;
-    if (!g->masked) return CCP_ERR_UNSUPPORTED;
-    if (!g->mask_edge_known) return CCP_ERR_STATE;
-    bool touches = false;
-    CCP_TRY(blend_border(g, &touches));
-    if (touches) return CCP_ERR_UNSUPPORTED;              // the diagonal is 4 everywhere: no neighbour may be missing
-    int ya, yb;
-    blend_window(g, &ya, &yb);
-    DevBuf<uint8_t> dsrc, dtgt;
-    CCP_TRY(upload_window(g, dsrc, source, source_stride_bytes, ya, yb));
-    CCP_TRY(upload_window(g, dtgt, target, target_stride_bytes, ya, yb));
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->geom.local_rows);
-    using PU = Packed<const uint8_t>;
-    const PU psrc{dsrc.p, 0, (long)W * C, C, ya}, ptgt{dtgt.p, 0, (long)W * C, C, ya};
-    if (mode == CCP_CLONE_MIXED)
-        hipLaunchKernelGGL((k_blend_clone_rhs<true, PU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), psrc, ptgt,
-                           C, (int)init);
-    else
-        hipLaunchKernelGGL((k_blend_clone_rhs<false, PU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), psrc, ptgt,
-                           C, (int)init);
-    CCP_HIP(hipGetLastError());
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    if (init) g->half_sweeps_since_refresh = 0;
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_store_u8_composite(ccp_grid *g, const uint8_t *canvas, int64_t canvas_stride_bytes, uint8_t *out,
-                                int64_t out_stride_bytes)
-try {
-    CCP_TRY(not_weighted(g));
-    CCP_TRY(bind(g));
-    if (!canvas || !out) return CCP_ERR_BAD_ARG;
-    const int W = g->desc.width, C = g->desc.channels;
-    if (canvas_stride_bytes < (int64_t)W * C || out_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
-    if (!g->masked) return CCP_ERR_UNSUPPORTED;
-    const int y_lo = g->desc.row_begin, rows = g->desc.row_count;
-    DevBuf<uint8_t> dcan, dout;
-    CCP_TRY(upload_window(g, dcan, canvas, canvas_stride_bytes, y_lo, y_lo + rows));
-    CCP_TRY(dout.alloc((size_t)rows * W * C));
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)rows);
-    hipLaunchKernelGGL((k_blend_composite<Packed<const uint8_t>, Packed<uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p,
-                       blend_mask(g), Packed<const uint8_t>{dcan.p, 0, (long)W * C, C, y_lo}, Packed<uint8_t>{dout.p, 0, (long)W * C, C, y_lo},
-                       C);
-    CCP_HIP(hipGetLastError());
-    CCP_HIP(hipMemcpy2DAsync(out + (size_t)y_lo * (size_t)out_stride_bytes, (size_t)out_stride_bytes, dout.p, (size_t)W * C,
-                             (size_t)W * C, (size_t)rows, hipMemcpyDeviceToHost, g->stream));
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    return edge_timeout_status(g);
-} CCP_ABI_CATCH
-
 // ============================================================================================
 // Row blocks over RCCL: neighbour halo exchange and all-reduced norms behind the C ABI.
 // ============================================================================================
@@ -2914,8 +2658,10 @@ try {
 }  // extern "C"
 
 // ============================================================================================
-// Device hand-off (include/ccp_gs.h, ccp_grid_*_device): the host twins' kernels read through strided views
-// (ccp_grid_io.hpp) of the caller's device arrays; nothing is staged, allocated or waited for.
+// Image I/O and assembly (include/ccp_gs.h): every image-shaped input or output is read through a strided view
+// (ccp_grid_io.hpp).  The ccp_grid_*_device calls pass views of the caller's device arrays; nothing is staged,
+// allocated or waited for.  Their host twins stage into device memory, launch the same kernels on views of the
+// staging buffers, and wait.
 // ============================================================================================
 namespace {
 
@@ -3066,6 +2812,165 @@ int get_device(ccp_grid *g, const double *src, const ccp_device_array *a, int fi
 
 bool single_block(const ccp_grid *g) { return !(g->ghost_top || g->ghost_bottom || g->desc.row_count != g->desc.height); }
 
+int weighted_handle(ccp_grid *g)
+{
+    CCP_TRY(bind(g));
+    return g->weighted ? CCP_OK : CCP_ERR_UNSUPPORTED;
+}
+
+// Rows [ya, yb) of an interleaved host image (W x C elements of T per row, `stride` bytes apart) into a packed
+// device buffer, asynchronously on the handle's stream.
+template <typename T>
+int upload_window(ccp_grid *g, DevBuf<T> &dev, const T *host, int64_t stride, int ya, int yb)
+{
+    const size_t row = (size_t)g->desc.width * g->desc.channels * sizeof(T);
+    CCP_TRY(dev.alloc((size_t)(yb - ya) * g->desc.width * g->desc.channels));
+    CCP_HIP(hipMemcpy2DAsync(dev.p, row, reinterpret_cast<const char *>(host) + (size_t)ya * (size_t)stride, (size_t)stride,
+                             row, (size_t)(yb - ya), hipMemcpyHostToDevice, g->stream));
+    return CCP_OK;
+}
+
+// A packed staging buffer of the host entry points as the view the kernels read: interleaved W x C rows of a row
+// window that starts at image row `ya` (the images of a stack `plane` elements apart).  Views are indexed by IMAGE
+// row, so the base is moved back by `ya` rows here on the host; a kernel only touches the rows its window covers
+// (blend_window below, the owned rows for the composite), so nothing in front of `p` is ever dereferenced.
+template <typename T>
+View<T> staged_view(T *p, int W, int C, int ya = 0, long plane = 0)
+{
+    const long row = (long)W * C;
+    return View<T>{p - (long)ya * row, plane, row, (long)C, 1};
+}
+
+BlendMask blend_mask(const ccp_grid *g) { return BlendMask{g->maskp.p, g->mask_edge.p, g->geom}; }
+
+// the image rows the assembly reads: the local rows and one row above and below where they exist
+void blend_window(const ccp_grid *g, int *ya, int *yb)
+{
+    *ya = std::max(0, g->geom.y0 - 1);
+    *yb = std::min(g->geom.H, g->geom.y0 + g->geom.local_rows + 1);
+}
+
+// Does the region touch the canvas's outer rows or columns?  Known from ccp_grid_set_mask_host; after the device
+// twin (whole-canvas handles only) read back once from the split mask.
+int blend_border(ccp_grid *g, bool *touches)
+{
+    if (g->mask_border < 0) {
+        if (!g->mask_edge_known) return CCP_ERR_STATE;
+        const Geom &geo = g->geom;
+        std::vector<unsigned char> split((size_t)geo.ch_stride);
+        CCP_HIP(hipMemcpyAsync(split.data(), g->maskp.p, split.size(), hipMemcpyDeviceToHost, g->stream));
+        CCP_HIP(hipStreamSynchronize(g->stream));
+        auto at = [&](int y, int x) { return split[(size_t)((2L * y + ((x + y) & 1)) * geo.pitch + (x >> 1))] != 0; };
+        bool border = false;
+        for (int y = 0; y < geo.H && !border; ++y) {
+            border = at(y, 0) || at(y, geo.W - 1);
+            if (y == 0 || y == geo.H - 1)
+                for (int x = 0; x < geo.W && !border; ++x) border = at(y, x);
+        }
+        g->mask_border = border ? 1 : 0;
+    }
+    *touches = g->mask_border != 0;
+    return CCP_OK;
+}
+
+// ---- one launcher per operation: launch geometry, template dispatch, the launch status and the handle state the
+// operation leaves behind.  The arguments are validated; the _device entry points pass the caller's views, the host
+// entry points the views of what they staged.
+using VF = View<const float>;
+using VU = View<const uint8_t>;
+
+// one lane per pixel of a row: ceil(W / kBlock) blocks by `rows` (by `channels` where a lane serves one channel)
+dim3 pixel_grid(const ccp_grid *g, int rows, int channels = 1)
+{
+    return dim3((unsigned)((g->desc.width + kBlock - 1) / kBlock), (unsigned)rows, (unsigned)channels);
+}
+
+int assemble_rhs(ccp_grid *g, const VF &gx, const VF &gy, const int32_t *constraint)
+{
+    const int C = g->desc.channels;
+    Pins pins{};
+    for (int ch = 0; ch < C; ++ch) pins.v[ch] = constraint[ch];
+    hipLaunchKernelGGL((k_assemble_rhs<VF, Pins>), pixel_grid(g, g->desc.height, C), dim3(kBlock), 0, g->stream, g->b.p, g->geom, gx, gy, pins);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+int assemble_from_images(ccp_grid *g, const VU &images, const VU &label, bool init_x)
+{
+    const dim3 grid = pixel_grid(g, g->desc.height, 3);
+    if (init_x)
+        hipLaunchKernelGGL((k_assemble_from_images<true, VU, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, images, label);
+    else
+        hipLaunchKernelGGL((k_assemble_from_images<false, VU, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, images, label);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+int store_u8(ccp_grid *g, const View<uint8_t> &out)
+{
+    hipLaunchKernelGGL((k_store_u8<View<uint8_t>>), pixel_grid(g, g->desc.height, g->desc.channels), dim3(kBlock), 0, g->stream, g->x.p,
+                       g->geom, out);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+int load_u8(ccp_grid *g, const VU &image)
+{
+    hipLaunchKernelGGL((k_load_u8<VU>), pixel_grid(g, g->desc.height, g->desc.channels), dim3(kBlock), 0, g->stream, g->x.p, g->geom, image);
+    CCP_HIP(hipGetLastError());
+    return zero_unmasked(g, g->x.p);
+}
+
+int blend_field_rhs(ccp_grid *g, const VF &gx, const VF &gy, const VU &canvas, bool init_x)
+{
+    const dim3 grid = pixel_grid(g, g->geom.local_rows);
+    const int C = g->desc.channels;
+    if (init_x)
+        hipLaunchKernelGGL((k_blend_field_rhs<true, VF, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), gx, gy, canvas, C);
+    else
+        hipLaunchKernelGGL((k_blend_field_rhs<false, VF, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), gx, gy, canvas, C);
+    CCP_HIP(hipGetLastError());
+    if (init_x) g->half_sweeps_since_refresh = 0;         // x is exact on every local row
+    return CCP_OK;
+}
+
+int blend_clone_rhs(ccp_grid *g, const VU &source, const VU &target, int mode, int init)
+{
+    const dim3 grid = pixel_grid(g, g->geom.local_rows);
+    const int C = g->desc.channels;
+    if (mode == CCP_CLONE_MIXED)
+        hipLaunchKernelGGL((k_blend_clone_rhs<true, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), source, target, C, init);
+    else
+        hipLaunchKernelGGL((k_blend_clone_rhs<false, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), source, target, C, init);
+    CCP_HIP(hipGetLastError());
+    if (init) g->half_sweeps_since_refresh = 0;
+    return CCP_OK;
+}
+
+int blend_composite(ccp_grid *g, const VU &canvas, const View<uint8_t> &out)
+{
+    hipLaunchKernelGGL((k_blend_composite<VU, View<uint8_t>>), pixel_grid(g, g->desc.row_count), dim3(kBlock), 0, g->stream, g->x.p,
+                       blend_mask(g), canvas, out, g->desc.channels);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+// F: the view of the data term f, float, double or u8; an absent input is a null view (guarded by its `has` bit)
+template <typename F>
+int weighted_rhs(ccp_grid *g, const VF &gx, const VF &gy, const F &f, int has, bool init_x)
+{
+    const Geom &geo = g->geom;
+    const dim3 grid = pixel_grid(g, geo.H);
+    const double *op = g->wop.p;
+    const int C = g->desc.channels;
+    if (init_x)
+        hipLaunchKernelGGL((k_weighted_rhs<true, VF, F>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx, gy, f, has, C);
+    else
+        hipLaunchKernelGGL((k_weighted_rhs<false, VF, F>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx, gy, f, has, C);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3094,6 +2999,38 @@ try {
     return get_device(g, g->b.p, rows, first_row, n_rows);
 } CCP_ABI_CATCH
 
+// ---- the image-shaped entry points in pairs: the host form stages into device memory, calls the launcher its
+// _device twin calls on the caller's arrays, and waits; the twin enqueues and returns.  Each keeps its own order of
+// refusals.
+
+int ccp_grid_assemble_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t row_stride_bytes, const int32_t *constraint)
+try {
+    CCP_TRY(not_weighted(g));
+    CCP_TRY(bind(g));
+    if (!gx || !gy || !constraint) return CCP_ERR_BAD_ARG;
+    if (g->masked) return CCP_ERR_UNSUPPORTED;            // SolveChannel's right-hand side belongs to SolveChannel's matrix
+    if (!single_block(g)) return CCP_ERR_STATE;
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    const size_t row_bytes = (size_t)W * C * sizeof(float);
+    if (row_stride_bytes < (int64_t)row_bytes) return CCP_ERR_BAD_ARG;
+    DevBuf<float> dgx, dgy;
+    CCP_TRY(dgx.alloc((size_t)W * H * C));
+    CCP_TRY(dgy.alloc((size_t)W * H * C));
+    // only rows y < H-1 and columns x < W-1 are defined in the reference (PhotoMontage.cpp:416-425);
+    // the kernel never reads the rest, but the copy must not touch it on the host either.
+    const size_t copy_rows = H > 1 ? (size_t)(H - 1) : 0;
+    CCP_HIP(hipMemsetAsync(dgx.p, 0, (size_t)W * H * C * sizeof(float), g->stream));
+    CCP_HIP(hipMemsetAsync(dgy.p, 0, (size_t)W * H * C * sizeof(float), g->stream));
+    if (copy_rows && W > 1) {
+        const size_t width_bytes = (size_t)(W - 1) * C * sizeof(float);
+        CCP_HIP(hipMemcpy2DAsync(dgx.p, row_bytes, gx, (size_t)row_stride_bytes, width_bytes, copy_rows, hipMemcpyHostToDevice, g->stream));
+        CCP_HIP(hipMemcpy2DAsync(dgy.p, row_bytes, gy, (size_t)row_stride_bytes, width_bytes, copy_rows, hipMemcpyHostToDevice, g->stream));
+    }
+    CCP_TRY(assemble_rhs(g, staged_view<const float>(dgx.p, W, C), staged_view<const float>(dgy.p, W, C), constraint));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    return CCP_OK;
+} CCP_ABI_CATCH
+
 int ccp_grid_assemble_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const int32_t *constraint)
 try {
     CCP_TRY(not_weighted(g));
@@ -3104,13 +3041,38 @@ try {
     const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
     CCP_TRY(check_view(g, gx, kF32, false, 1, H, W, C));
     CCP_TRY(check_view(g, gy, kF32, false, 1, H, W, C));
-    Pins pins{};
-    for (int ch = 0; ch < C; ++ch) pins.v[ch] = constraint[ch];
-    using VF = View<const float>;
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
-    hipLaunchKernelGGL((k_assemble_rhs<VF, Pins>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->geom, view_of<const float>(gx),
-                       view_of<const float>(gy), pins);
-    CCP_HIP(hipGetLastError());
+    return assemble_rhs(g, view_of<const float>(gx), view_of<const float>(gy), constraint);
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_from_images(ccp_grid *g, const uint8_t *const *images, int32_t n_images,
+                                  int64_t image_stride_bytes, const uint8_t *label, int64_t label_stride_bytes,
+                                  int32_t init_x_from_composite)
+try {
+    CCP_TRY(not_weighted(g));
+    CCP_TRY(bind(g));
+    if (!images || !label || n_images < 1 || n_images > 256) return CCP_ERR_BAD_ARG;
+    if (g->desc.channels != 3 || g->masked) return CCP_ERR_UNSUPPORTED;      // BGR images; SolveChannel's matrix
+    if (!single_block(g)) return CCP_ERR_STATE;
+    const int W = g->desc.width, H = g->desc.height;
+    if (image_stride_bytes < (int64_t)W * 3 || label_stride_bytes < W) return CCP_ERR_BAD_ARG;
+    for (int k = 0; k < n_images; ++k)
+        if (!images[k]) return CCP_ERR_BAD_ARG;
+    // labels must select existing images (the reference indexes Images[label] unchecked)
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x)
+            if (label[(size_t)y * label_stride_bytes + x] >= n_images) return CCP_ERR_BAD_ARG;
+    DevBuf<uint8_t> dimg, dlab;
+    const size_t plane = (size_t)W * H * 3;
+    CCP_TRY(dimg.alloc(plane * n_images));
+    CCP_TRY(dlab.alloc((size_t)W * H));
+    for (int k = 0; k < n_images; ++k)
+        CCP_HIP(hipMemcpy2DAsync(dimg.p + plane * k, (size_t)W * 3, images[k], (size_t)image_stride_bytes, (size_t)W * 3,
+                                 (size_t)H, hipMemcpyHostToDevice, g->stream));
+    CCP_HIP(hipMemcpy2DAsync(dlab.p, (size_t)W, label, (size_t)label_stride_bytes, (size_t)W, (size_t)H,
+                             hipMemcpyHostToDevice, g->stream));
+    CCP_TRY(assemble_from_images(g, staged_view<const uint8_t>(dimg.p, W, 3, 0, (long)plane), staged_view<const uint8_t>(dlab.p, W, 1),
+                                 init_x_from_composite != 0));
+    CCP_HIP(hipStreamSynchronize(g->stream));
     return CCP_OK;
 } CCP_ABI_CATCH
 
@@ -3125,8 +3087,7 @@ try {
     const int W = g->desc.width, H = g->desc.height;
     CCP_TRY(check_view(g, images, kU8, false, n_images, H, W, 3));
     CCP_TRY(check_view(g, label, kU8, false, 1, H, W, 1));
-    using VU = View<const uint8_t>;
-    const VU img = view_of<const uint8_t>(images), lab = view_of<const uint8_t>(label);
+    const VU lab = view_of<const uint8_t>(label);
     // labels must select existing images: checked on the device before any image is read
     unsigned bad = 0;
     CCP_HIP(hipMemsetAsync(g->io_bad.p, 0, sizeof(unsigned), g->stream));
@@ -3136,12 +3097,21 @@ try {
     CCP_HIP(hipMemcpyAsync(&bad, g->io_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
     CCP_HIP(hipStreamSynchronize(g->stream));
     if (bad) return CCP_ERR_BAD_ARG;
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, 3);
-    if (init_x_from_composite)
-        hipLaunchKernelGGL((k_assemble_from_images<true, VU, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, img, lab);
-    else
-        hipLaunchKernelGGL((k_assemble_from_images<false, VU, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->geom, img, lab);
-    CCP_HIP(hipGetLastError());
+    return assemble_from_images(g, view_of<const uint8_t>(images), lab, init_x_from_composite != 0);
+} CCP_ABI_CATCH
+
+int ccp_grid_store_u8(ccp_grid *g, uint8_t *out, int64_t row_stride_bytes)
+try {
+    CCP_TRY(bind(g));
+    if (!out) return CCP_ERR_BAD_ARG;
+    if (!single_block(g)) return CCP_ERR_STATE;
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    if (row_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
+    DevBuf<uint8_t> d;
+    CCP_TRY(d.alloc((size_t)W * H * C));
+    CCP_TRY(store_u8(g, staged_view(d.p, W, C)));
+    CCP_HIP(hipMemcpy2DAsync(out, (size_t)row_stride_bytes, d.p, (size_t)W * C, (size_t)W * C, (size_t)H, hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
     return CCP_OK;
 } CCP_ABI_CATCH
 
@@ -3150,11 +3120,21 @@ try {
     CCP_TRY(bind(g));
     if (!out) return CCP_ERR_BAD_ARG;
     if (!single_block(g)) return CCP_ERR_STATE;
+    CCP_TRY(check_view(g, out, kU8, true, 1, g->desc.height, g->desc.width, g->desc.channels));
+    return store_u8(g, view_of<uint8_t>(out));
+} CCP_ABI_CATCH
+
+int ccp_grid_set_x_u8(ccp_grid *g, const uint8_t *image, int64_t row_stride_bytes)
+try {
+    CCP_TRY(bind(g));
+    if (!image) return CCP_ERR_BAD_ARG;
+    if (!single_block(g)) return CCP_ERR_STATE;
     const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
-    CCP_TRY(check_view(g, out, kU8, true, 1, H, W, C));
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
-    hipLaunchKernelGGL((k_store_u8<View<uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->geom, view_of<uint8_t>(out));
-    CCP_HIP(hipGetLastError());
+    if (row_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
+    DevBuf<uint8_t> d;
+    CCP_TRY(upload_window(g, d, image, row_stride_bytes, 0, H));
+    CCP_TRY(load_u8(g, staged_view<const uint8_t>(d.p, W, C)));
+    CCP_HIP(hipStreamSynchronize(g->stream));
     return CCP_OK;
 } CCP_ABI_CATCH
 
@@ -3163,12 +3143,31 @@ try {
     CCP_TRY(bind(g));
     if (!image) return CCP_ERR_BAD_ARG;
     if (!single_block(g)) return CCP_ERR_STATE;
-    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
-    CCP_TRY(check_view(g, image, kU8, false, 1, H, W, C));
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C);
-    hipLaunchKernelGGL((k_load_u8<View<const uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->geom, view_of<const uint8_t>(image));
-    CCP_HIP(hipGetLastError());
-    return zero_unmasked(g, g->x.p);
+    CCP_TRY(check_view(g, image, kU8, false, 1, g->desc.height, g->desc.width, g->desc.channels));
+    return load_u8(g, view_of<const uint8_t>(image));
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_region_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes,
+                                 const uint8_t *canvas, int64_t canvas_stride_bytes, int32_t init_x_from_canvas)
+try {
+    CCP_TRY(not_weighted(g));
+    CCP_TRY(bind(g));
+    if (!gx || !gy || !canvas) return CCP_ERR_BAD_ARG;
+    const int W = g->desc.width, C = g->desc.channels;
+    if (field_stride_bytes < (int64_t)W * C * (int64_t)sizeof(float) || canvas_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
+    if (!g->masked) return CCP_ERR_UNSUPPORTED;           // SolveChannel's matrix has its own assembly
+    if (!g->mask_edge_known) return CCP_ERR_STATE;
+    int ya, yb;
+    blend_window(g, &ya, &yb);
+    DevBuf<float> dgx, dgy;
+    DevBuf<uint8_t> dcan;
+    CCP_TRY(upload_window(g, dgx, gx, field_stride_bytes, ya, yb));
+    CCP_TRY(upload_window(g, dgy, gy, field_stride_bytes, ya, yb));
+    CCP_TRY(upload_window(g, dcan, canvas, canvas_stride_bytes, ya, yb));
+    CCP_TRY(blend_field_rhs(g, staged_view<const float>(dgx.p, W, C, ya), staged_view<const float>(dgy.p, W, C, ya),
+                            staged_view<const uint8_t>(dcan.p, W, C, ya), init_x_from_canvas != 0));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    return CCP_OK;
 } CCP_ABI_CATCH
 
 int ccp_grid_assemble_region_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy,
@@ -3183,19 +3182,30 @@ try {
     CCP_TRY(check_view(g, canvas, kU8, false, 1, H, W, C));
     if (!g->masked) return CCP_ERR_UNSUPPORTED;
     if (!g->mask_edge_known) return CCP_ERR_STATE;
-    using VF = View<const float>;
-    using VU = View<const uint8_t>;
-    const VF vgx = view_of<const float>(gx), vgy = view_of<const float>(gy);
-    const VU vcan = view_of<const uint8_t>(canvas);
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->geom.local_rows);
-    if (init_x_from_canvas)
-        hipLaunchKernelGGL((k_blend_field_rhs<true, VF, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), vgx, vgy,
-                           vcan, C);
-    else
-        hipLaunchKernelGGL((k_blend_field_rhs<false, VF, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), vgx, vgy,
-                           vcan, C);
-    CCP_HIP(hipGetLastError());
-    if (init_x_from_canvas) g->half_sweeps_since_refresh = 0;
+    return blend_field_rhs(g, view_of<const float>(gx), view_of<const float>(gy), view_of<const uint8_t>(canvas), init_x_from_canvas != 0);
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_clone(ccp_grid *g, const uint8_t *source, int64_t source_stride_bytes, const uint8_t *target,
+                            int64_t target_stride_bytes, int32_t mode, int32_t init)
+try {
+    CCP_TRY(not_weighted(g));
+    CCP_TRY(bind(g));
+    if (!source || !target) return CCP_ERR_BAD_ARG;
+    const int W = g->desc.width, C = g->desc.channels;
+    if (source_stride_bytes < (int64_t)W * C || target_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
+    if ((mode != CCP_CLONE_IMPORT && mode != CCP_CLONE_MIXED) || init < 0 || init > 2) return CCP_ERR_BAD_ARG;
+    if (!g->masked) return CCP_ERR_UNSUPPORTED;
+    if (!g->mask_edge_known) return CCP_ERR_STATE;
+    bool touches = false;
+    CCP_TRY(blend_border(g, &touches));
+    if (touches) return CCP_ERR_UNSUPPORTED;              // the diagonal is 4 everywhere: no neighbour may be missing
+    int ya, yb;
+    blend_window(g, &ya, &yb);
+    DevBuf<uint8_t> dsrc, dtgt;
+    CCP_TRY(upload_window(g, dsrc, source, source_stride_bytes, ya, yb));
+    CCP_TRY(upload_window(g, dtgt, target, target_stride_bytes, ya, yb));
+    CCP_TRY(blend_clone_rhs(g, staged_view<const uint8_t>(dsrc.p, W, C, ya), staged_view<const uint8_t>(dtgt.p, W, C, ya), mode, init));
+    CCP_HIP(hipStreamSynchronize(g->stream));
     return CCP_OK;
 } CCP_ABI_CATCH
 
@@ -3214,18 +3224,27 @@ try {
     bool touches = false;
     CCP_TRY(blend_border(g, &touches));
     if (touches) return CCP_ERR_UNSUPPORTED;
-    using VU = View<const uint8_t>;
-    const VU vsrc = view_of<const uint8_t>(source), vtgt = view_of<const uint8_t>(target);
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->geom.local_rows);
-    if (mode == CCP_CLONE_MIXED)
-        hipLaunchKernelGGL((k_blend_clone_rhs<true, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), vsrc, vtgt, C,
-                           (int)init);
-    else
-        hipLaunchKernelGGL((k_blend_clone_rhs<false, VU>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, blend_mask(g), vsrc, vtgt, C,
-                           (int)init);
-    CCP_HIP(hipGetLastError());
-    if (init) g->half_sweeps_since_refresh = 0;
-    return CCP_OK;
+    return blend_clone_rhs(g, view_of<const uint8_t>(source), view_of<const uint8_t>(target), mode, init);
+} CCP_ABI_CATCH
+
+int ccp_grid_store_u8_composite(ccp_grid *g, const uint8_t *canvas, int64_t canvas_stride_bytes, uint8_t *out,
+                                int64_t out_stride_bytes)
+try {
+    CCP_TRY(not_weighted(g));
+    CCP_TRY(bind(g));
+    if (!canvas || !out) return CCP_ERR_BAD_ARG;
+    const int W = g->desc.width, C = g->desc.channels;
+    if (canvas_stride_bytes < (int64_t)W * C || out_stride_bytes < (int64_t)W * C) return CCP_ERR_BAD_ARG;
+    if (!g->masked) return CCP_ERR_UNSUPPORTED;
+    const int y_lo = g->desc.row_begin, rows = g->desc.row_count;
+    DevBuf<uint8_t> dcan, dout;
+    CCP_TRY(upload_window(g, dcan, canvas, canvas_stride_bytes, y_lo, y_lo + rows));
+    CCP_TRY(dout.alloc((size_t)rows * W * C));
+    CCP_TRY(blend_composite(g, staged_view<const uint8_t>(dcan.p, W, C, y_lo), staged_view(dout.p, W, C, y_lo)));
+    CCP_HIP(hipMemcpy2DAsync(out + (size_t)y_lo * (size_t)out_stride_bytes, (size_t)out_stride_bytes, dout.p, (size_t)W * C,
+                             (size_t)W * C, (size_t)rows, hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    return edge_timeout_status(g);
 } CCP_ABI_CATCH
 
 int ccp_grid_store_u8_composite_device(ccp_grid *g, const ccp_device_array *canvas, const ccp_device_array *out)
@@ -3237,11 +3256,53 @@ try {
     CCP_TRY(check_view(g, canvas, kU8, false, 1, H, W, C));
     CCP_TRY(check_view(g, out, kU8, true, 1, H, W, C));
     if (!g->masked) return CCP_ERR_UNSUPPORTED;
-    dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)g->desc.row_count);
-    hipLaunchKernelGGL((k_blend_composite<View<const uint8_t>, View<uint8_t>>), grid, dim3(kBlock), 0, g->stream, g->x.p, blend_mask(g),
-                       view_of<const uint8_t>(canvas), view_of<uint8_t>(out), C);
-    CCP_HIP(hipGetLastError());
+    CCP_TRY(blend_composite(g, view_of<const uint8_t>(canvas), view_of<uint8_t>(out)));
     return edge_timeout_status(g);
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_weighted_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes, const float *f,
+                                   int64_t f_stride_bytes, int32_t init_x_from_f)
+try {
+    CCP_TRY(weighted_handle(g));
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    const int64_t row = (int64_t)W * C * (int64_t)sizeof(float);
+    if ((gx || gy) && field_stride_bytes < row) return CCP_ERR_BAD_ARG;
+    if (f && f_stride_bytes < row) return CCP_ERR_BAD_ARG;
+    if (!g->has_op) return CCP_ERR_STATE;
+    const float *src[3] = {gx, gy, f};
+    const int64_t stride[3] = {field_stride_bytes, field_stride_bytes, f_stride_bytes};
+    DevBuf<float> dev[3];
+    VF v[3];
+    int has = 0;
+    for (int i = 0; i < 3; ++i) {
+        v[i] = VF{nullptr, 0, 0, 0, 0};
+        if (!src[i]) continue;
+        has |= 1 << i;
+        CCP_TRY(upload_window(g, dev[i], src[i], stride[i], 0, H));
+        v[i] = staged_view<const float>(dev[i].p, W, C);
+    }
+    CCP_TRY(weighted_rhs(g, v[0], v[1], v[2], has, init_x_from_f != 0));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f,
+                                          int32_t init_x_from_f)
+try {
+    CCP_TRY(weighted_handle(g));
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    if (gx) CCP_TRY(check_view(g, gx, kF32, false, 1, H, W, C));
+    if (gy) CCP_TRY(check_view(g, gy, kF32, false, 1, H, W, C));
+    if (f) CCP_TRY(check_view(g, f, kF32F64 | kU8, false, 1, H, W, C));
+    if (!g->has_op) return CCP_ERR_STATE;
+    const VF none{nullptr, 0, 0, 0, 0};
+    const VF vgx = gx ? view_of<const float>(gx) : none, vgy = gy ? view_of<const float>(gy) : none;
+    const int has = (gx ? 1 : 0) | (gy ? 2 : 0) | (f ? 4 : 0);
+    const bool init = init_x_from_f != 0;
+    if (!f) return weighted_rhs(g, vgx, vgy, none, has, init);
+    if (f->dtype == CCP_DTYPE_U8) return weighted_rhs(g, vgx, vgy, view_of<const uint8_t>(f), has, init);
+    if (f->dtype == CCP_DTYPE_F32) return weighted_rhs(g, vgx, vgy, view_of<const float>(f), has, init);
+    return weighted_rhs(g, vgx, vgy, view_of<const double>(f), has, init);
 } CCP_ABI_CATCH
 
 }  // extern "C"
@@ -3250,12 +3311,6 @@ try {
 // Weighted grids (include/ccp_gs.h, CCP_GRID_WEIGHTED; kernels: ccp_grid_weighted.hpp)
 // ============================================================================================
 namespace {
-
-int weighted_handle(ccp_grid *g)
-{
-    CCP_TRY(bind(g));
-    return g->weighted ? CCP_OK : CCP_ERR_UNSUPPORTED;
-}
 
 // The operator from three weight views in one pass; the device's verdict on the weights is read back once.  The old
 // operator and the hierarchy built on it are gone either way: a refusal leaves the handle with none.
@@ -3276,23 +3331,6 @@ int set_weights(ccp_grid *g, const WeightView &wx, const WeightView &wy, const W
     if (bad) return CCP_ERR_BAD_ARG;
     g->has_op = true;
     return edge_timeout_status(g);
-}
-
-template <bool INIT, typename G, typename F>
-void launch_weighted_rhs(ccp_grid *g, const G &gx, const G &gy, const F &f, int has)
-{
-    const Geom &geo = g->geom;
-    hipLaunchKernelGGL((k_weighted_rhs<INIT, G, F>), dim3((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)geo.H), dim3(kBlock), 0, g->stream,
-                       g->b.p, g->x.p, geo, static_cast<const double *>(g->wop.p), geo.ch_stride, gx, gy, f, has, g->desc.channels);
-}
-
-template <typename G, typename F>
-int weighted_rhs(ccp_grid *g, const G &gx, const G &gy, const F &f, int has, bool init)
-{
-    if (init) launch_weighted_rhs<true>(g, gx, gy, f, has);
-    else launch_weighted_rhs<false>(g, gx, gy, f, has);
-    CCP_HIP(hipGetLastError());
-    return CCP_OK;
 }
 
 }  // namespace
@@ -3333,53 +3371,6 @@ try {
         v[i] = WeightView{src[i]->data, (long)src[i]->stride_y, (long)src[i]->stride_x, src[i]->dtype == CCP_DTYPE_F64 ? 1 : 0, dflt[i]};
     }
     return set_weights(g, v[0], v[1], v[2]);
-} CCP_ABI_CATCH
-
-int ccp_grid_assemble_weighted_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes, const float *f,
-                                   int64_t f_stride_bytes, int32_t init_x_from_f)
-try {
-    CCP_TRY(weighted_handle(g));
-    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
-    const int64_t row = (int64_t)W * C * (int64_t)sizeof(float);
-    if ((gx || gy) && field_stride_bytes < row) return CCP_ERR_BAD_ARG;
-    if (f && f_stride_bytes < row) return CCP_ERR_BAD_ARG;
-    if (!g->has_op) return CCP_ERR_STATE;
-    const float *src[3] = {gx, gy, f};
-    const int64_t stride[3] = {field_stride_bytes, field_stride_bytes, f_stride_bytes};
-    DevBuf<float> dev[3];
-    using PF = Packed<const float>;
-    PF acc[3];
-    int has = 0;
-    for (int i = 0; i < 3; ++i) {
-        acc[i] = PF{nullptr, 0, (long)W * C, C, 0};
-        if (!src[i]) continue;
-        has |= 1 << i;
-        CCP_TRY(upload_window(g, dev[i], src[i], stride[i], 0, H));
-        acc[i].p = dev[i].p;
-    }
-    CCP_TRY(weighted_rhs(g, acc[0], acc[1], acc[2], has, init_x_from_f != 0));
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_assemble_weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f,
-                                          int32_t init_x_from_f)
-try {
-    CCP_TRY(weighted_handle(g));
-    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
-    if (gx) CCP_TRY(check_view(g, gx, kF32, false, 1, H, W, C));
-    if (gy) CCP_TRY(check_view(g, gy, kF32, false, 1, H, W, C));
-    if (f) CCP_TRY(check_view(g, f, kF32F64 | kU8, false, 1, H, W, C));
-    if (!g->has_op) return CCP_ERR_STATE;
-    using VF = View<const float>;
-    const VF none{nullptr, 0, 0, 0, 0};
-    const VF vgx = gx ? view_of<const float>(gx) : none, vgy = gy ? view_of<const float>(gy) : none;
-    const int has = (gx ? 1 : 0) | (gy ? 2 : 0) | (f ? 4 : 0);
-    const bool init = init_x_from_f != 0;
-    if (!f) return weighted_rhs(g, vgx, vgy, none, has, init);
-    if (f->dtype == CCP_DTYPE_U8) return weighted_rhs(g, vgx, vgy, view_of<const uint8_t>(f), has, init);
-    if (f->dtype == CCP_DTYPE_F32) return weighted_rhs(g, vgx, vgy, view_of<const float>(f), has, init);
-    return weighted_rhs(g, vgx, vgy, view_of<const double>(f), has, init);
 } CCP_ABI_CATCH
 
 }  // extern "C"

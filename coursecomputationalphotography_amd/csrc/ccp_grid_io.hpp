@@ -3,9 +3,9 @@
 // strided natural-order view and the split colour layout of x and b.
 //
 // Accessors.  Every image-shaped input or output of a kernel is read as acc(y, x, c) (acc.at(n, y, x, c) for an
-// image stack) with y the IMAGE row.  Packed<T> is the staging layout of the host entry points: interleaved W x C
-// rows of a row window starting at image row `ya` (planes `plane` elements apart); View<T> is a caller's strided
-// array.  The host entry points instantiate the kernels with Packed, the _device twins with View.
+// image stack) with y the IMAGE row.  View<T> is the one accessor: four element strides over a caller's device array
+// (the _device calls) or over a staging buffer of a host entry point, whose packed row window (interleaved W x C
+// rows from image row `ya` on) is the strides (plane, W * C, C, 1) with the base moved back by `ya` rows.
 //
 // Gather / scatter.  One lane owns the pixel pair (2j, 2j+1) of one row for every channel: pixel 2j has colour
 // y&1 and pixel 2j+1 colour (y+1)&1, both at half-column j, so a wave writes (or reads) 64 contiguous doubles of
@@ -21,20 +21,6 @@
 namespace ccp {
 
 template <typename T>
-struct Packed {
-    T *p;
-    long plane;          // elements between images of a stack
-    long row;            // elements per row (W * C)
-    int C;
-    int ya;              // image row of window row 0
-    __device__ __forceinline__ T &operator()(int y, int x, int c) const { return p[(long)(y - ya) * row + (long)x * C + c]; }
-    __device__ __forceinline__ T &at(int n, int y, int x, int c) const
-    {
-        return p[(long)n * plane + (long)(y - ya) * row + (long)x * C + c];
-    }
-};
-
-template <typename T>
 struct View {
     T *p;
     long sn, sy, sx, sc; // strides in elements
@@ -45,7 +31,7 @@ struct View {
     }
 };
 
-// the pin values of ccp_grid_assemble_rhs_device, passed by value
+// the pin values of k_assemble_rhs, passed by value
 struct Pins {
     int v[kMaxChannels];
     __device__ __forceinline__ int operator[](int c) const { return v[c]; }

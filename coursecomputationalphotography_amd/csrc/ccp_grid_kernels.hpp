@@ -408,8 +408,8 @@ k_randomize(double *__restrict__ x, Geom g, uint64_t seed, double lo, double hi)
 // ---------------------------------------------------------------------------------------------
 // Poisson right-hand side ATb for all channels (PhotoMontage.cpp:563-572,579-581,592), Eigen's
 // row-major sparse*dense accumulation order: gy above, gx left, -gx here, -gy here, pin.
-// gx, gy: H x W x C float32 on device through accessor F (ccp_grid_io.hpp), the pins through PIN (a device
-// array or Pins by value).  grid = (ceil(W/kBlock), H, C).
+// gx, gy: H x W x C float32 on device through accessor F (ccp_grid_io.hpp), the pins through PIN (Pins by
+// value).  grid = (ceil(W/kBlock), H, C).
 template <typename F, typename PIN>
 __global__ void __launch_bounds__(kBlock)
 k_assemble_rhs(double *__restrict__ b, Geom g, F gx, F gy, PIN constraint)

@@ -87,8 +87,8 @@ k_weighted_coef(WeightView wx, WeightView wy, WeightView lam, int W, int H, long
 }
 
 // b of all C channels from the stored operator (op: d, we, ws, lambda planes `plane` doubles apart) and the guidance
-// gx, gy / data f (accessors G, F: Packed for the host entry point, View for the device twin; has & 1: gx, has & 2:
-// gy, has & 4: f, a missing one reads 0).  INIT: x := f on live pixels, 0 on dead ones.  grid = (ceil(W/kBlock), H).
+// gx, gy / data f (accessors G, F: Views of the caller's arrays or of a host entry point's staging; has & 1: gx, has &
+// 2: gy, has & 4: f, a missing one reads 0).  INIT: x := f on live pixels, 0 on dead ones.  grid = (ceil(W/kBlock), H).
 template <bool INIT, typename G, typename F>
 __global__ void __launch_bounds__(kBlock)
 k_weighted_rhs(double *__restrict__ b, double *__restrict__ xo, Geom g, const double *__restrict__ op, long plane, G gx, G gy, F f,
