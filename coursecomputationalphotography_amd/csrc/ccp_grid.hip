@@ -99,6 +99,8 @@ struct ccp_grid {
     bool force_border = false;   // debug (CCP_GS_FORCE_BORDER): and every trip there takes the border body
     bool red_store_all = false;  // A/B (CCP_GS_RED_STORE=1): every pass stores both colour halves (run_unchecked)
     bool wide = true;            // A/B (CCP_GS_WIDE=0): the depth-8 unchecked passes keep 128-px ordinary strips (k_fused_sweep)
+    int cus = 0;                 // compute units of the device: k_fused_sweep_wide holds one wave per SIMD, 4 per CU
+    int wide_segments = -1;      // A/B (CCP_GS_WIDE_SEGMENTS): -1 the planner (ccp_wide_plan.hpp), 0 the interior chunks, n > 0: n segments
     DevBuf<double> partial;      // per-block partial sums (L1 step / residual / checksums)
     long partial_region = 0;     // doubles per colour region of `partial` (L1 step)
     DevBuf<double> small;        // 4*kMaxChannels doubles of reduced results
@@ -453,12 +455,46 @@ int launch_fused_t(ccp_grid *g, const double *xin, double *xout, int st_lo, int 
     }
     if (signalled) *signalled = edge;
     // The ordinary tiles of an unchecked depth-8 pass run on wide strips (k_fused_sweep_wide): the columns
-    // [wx0, wx1) that the inner narrow strips would store, in the chunks between the border chunk rows.  The border
-    // tiles keep the narrow tiling above, so ns_left / ns_right and the red-skip argument at fused_wave hold as they are.
-    const bool wide = T == kWideT && g->wide && l1 == 0 && !edge && any_plain;
+    // [wx0, wx1) that the inner narrow strips would store, in the rows of the chunks between the border chunk rows.  The
+    // border tiles keep the narrow tiling above, so ns_left / ns_right and the red-skip argument at fused_wave hold as
+    // they are.  The interior rows are one contiguous range, cut into segments sized to the device's wave slots instead
+    // of into the chunks (ccp_wide_plan.hpp); the launch is a flat list of tiles.
     const int wx0 = P.ns_left * U, wx1 = (P.n_strips - P.ns_right) * U;
-    const int n_wide = wide ? (wx1 - wx0 + wide_useful_px(T) - 1) / wide_useful_px(T) : 0;
-    const dim3 wgrid((unsigned)((n_wide + kWideWaves - 1) / kWideWaves), (unsigned)(P.n_chunks - edge_chunks), (unsigned)g->desc.channels);
+    const int n_wide = (T == kWideT && any_plain) ? (wx1 - wx0 + wide_useful_px(T) - 1) / wide_useful_px(T) : 0;
+    const bool wide = T == kWideT && g->wide && l1 == 0 && !edge && any_plain && n_wide > 0;
+    P.wide_y0 = P.wide_y1 = P.wide_nseg = P.wide_tiles = 0;
+    P.wide_stride = 1;
+    P.wide_h = 2;
+    if (wide) {
+        int t;
+        fused_chunk_rows(P, P.nb_top, P.wide_y0, t);
+        fused_chunk_rows(P, P.n_chunks - P.nb_bot - 1, t, P.wide_y1);
+        const int rows = P.wide_y1 - P.wide_y0;
+        const long per_seg = (long)n_wide * g->desc.channels;
+        // what the border kernel has to march beside the wide tiles (ccp_wide_plan.hpp: the plan leaves it CUs)
+        WideBorder border;
+        for (int e = 0; e < edge_chunks; ++e) {
+            int ra, rb;
+            fused_chunk_rows(P, e < P.nb_top ? e : P.n_chunks - edge_chunks + e, ra, rb);
+            border.steps += (long)(rb - ra + 4 * T) * (P.n_strips - edge_strips);
+            border.longest = std::max(border.longest, rb - ra + 4 * T);
+        }
+        if (edge_strips > 0) {
+            border.steps += (long)P.n_chunks * edge_strips * P.side_subs * (P.side_rows + 4 * T);
+            border.longest = std::max(border.longest, P.side_rows + 4 * T);
+        }
+        border.steps *= g->desc.channels;
+        const int slots = kWideWaves * g->cus;
+        const WidePlan plan = g->wide_segments == 0 ? wide_plan_height(rows, P.rows_per_chunk)
+                              : g->wide_segments > 0 ? wide_plan_count(rows, g->wide_segments)
+                                                     : wide_plan(P.wide_y0, P.wide_y1, per_seg, slots, T, border);
+        P.wide_h = plan.h;
+        P.wide_nseg = plan.n_seg;
+        // (the A/B form pads every segment's strips to whole blocks: exactly the blocks of the per-chunk grid it stands for)
+        P.wide_stride = g->wide_segments == 0 ? (n_wide + kWideWaves - 1) / kWideWaves * kWideWaves : n_wide;
+        P.wide_tiles = P.wide_stride * plan.n_seg * g->desc.channels;
+    }
+    const dim3 wgrid((unsigned)((P.wide_tiles + kWideWaves - 1) / kWideWaves), 1, 1);
     const dim3 pgrid = wide ? wgrid : grid;                   // the ordinary launch
     // diagnostics: per-wave time stamps of this pass (ordinary launch first, border launch behind it)
     const size_t trace_plain = (size_t)pgrid.x * pgrid.y * pgrid.z * waves * 4, trace_border = (size_t)bgrid.x * bgrid.z * waves * 4;
@@ -934,6 +970,11 @@ try {
     if (const char *e = getenv("CCP_GS_FORCE_BORDER")) g->force_border = atoi(e) != 0;
     if (const char *e = getenv("CCP_GS_RED_STORE")) g->red_store_all = atoi(e) != 0;
     if (const char *e = getenv("CCP_GS_WIDE")) g->wide = atoi(e) != 0;
+    if (const char *e = getenv("CCP_GS_WIDE_SEGMENTS")) g->wide_segments = std::max(0, atoi(e));
+    if (hipDeviceGetAttribute(&g->cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess || g->cus < 1) {
+        delete g;
+        return CCP_ERR_HIP;
+    }
     if (const char *e = getenv("CCP_GS_CHUNK")) g->rows_per_chunk = std::max(1, atoi(e));
     choose_tiling(g);
     g->masked = (d->flags & CCP_GRID_DIRICHLET_MASK) != 0;

@@ -115,6 +115,10 @@ struct FusedParams {
     // workgroups that share an L2 at any moment are neighbours in x and the halo columns they both read are
     // fetched from HBM once.  Speed only: placement is never assumed for correctness.
     int xcd_swizzle;
+    // k_fused_sweep_wide (ccp_grid_fused_wide.hpp): the interior rows [wide_y0, wide_y1) in wide_nseg segments of wide_h
+    // rows (ccp_wide_plan.hpp); a row of wide_stride tile ids per (channel, segment), of which the first n_wide are
+    // strips (wide_stride = n_wide: no gaps); wide_tiles = wide_stride x wide_nseg x channels
+    int wide_y0, wide_y1, wide_h, wide_nseg, wide_stride, wide_tiles;
     // Diagnostics (CCP_GS_TRACE_FILE): 4 words per wave — start and end time (100 MHz constant clock), HW_ID |
     // XCC_ID << 32, and chunk | strip << 16 | channel << 32 | kernel << 40 — written by lane 0; nullptr otherwise.
     unsigned long long *__restrict__ trace;

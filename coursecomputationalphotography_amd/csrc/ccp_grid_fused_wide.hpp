@@ -12,17 +12,19 @@
 //   * the ring's slot of a row is (row - base) mod kWideRing, a compile-time constant in every unrolled step because
 //     the trip loop is unrolled over one whole turn of the ring (kWideRing / G trips).
 // It runs only the interior: the columns [wx0, wx1) that the narrow ordinary strips would store (the narrow side
-// strips stay border tiles in k_fused_border) and the chunks between the top and bottom border chunks.  Every pixel
+// strips stay border tiles in k_fused_border) and the rows between the top and bottom border chunks.  Those rows are one
+// contiguous range, and nothing here needs the chunk height: the host cuts them into row SEGMENTS sized to the device's
+// wave slots (ccp_wide_plan.hpp), and the launch is a flat list of (channel, segment, strip) tiles.  Every pixel
 // column an interior wide strip stores or depends on (2T columns either side) lies in [1, W-2], so the plain stencil
 // is exact wherever it matters; pixels further out are halo, computed with whatever was loaded and never stored.
 #pragma once
 
 #include "ccp_grid_fused.hpp"
+#include "ccp_wide_plan.hpp"                  // kWideRing = 20 b/4 rows per wave in LDS: 2 KB each, 40 KB per wave, 160 KB per block
 
 namespace ccp {
 
 constexpr int kWideT = 8;                     // the only depth built on wide strips
-constexpr int kWideRing = 20;                 // b/4 rows per wave in LDS: 2 KB each, 40 KB per wave, 160 KB per block
 constexpr int kWideWaves = kBlock / kWave;    // waves (wide strips) per workgroup: one per SIMD
 __host__ __device__ constexpr int wide_useful_px(int T) { return 4 * kStripLanes - 4 * T; }
 
@@ -197,7 +199,10 @@ __device__ __forceinline__ void fused_wave_wide(const double *__restrict__ xin, 
     for (int fb = base; fb <= f_end; fb += kWideRing) wide_turn<T, STORE_RED, NT, 0>(wr, wk, cx, g, fb, la, lb);
 }
 
-// grid = (ceil(n_wide / 4), chunks between the border chunk rows, channels); block = 4 waves = 4 adjacent wide strips.
+// grid = ceil(wide_tiles / 4) blocks; block = 4 waves = 4 consecutive tiles.  Tile t = (channel * wide_nseg + segment) *
+// wide_stride + strip, strip fastest (wide_stride = n_wide, but for the A/B form of the old per-chunk blocks): the waves
+// of a block are adjacent wide strips of one segment (they share their halo columns in L1 / L2) and every block but the
+// last is full.  The tiles of a pass are independent (xin -> xout).
 template <int T, bool STORE_RED>
 __global__ void __launch_bounds__(kBlock, 2)
 k_fused_sweep_wide(FusedParams P, int wx0, int wx1, int n_wide)
@@ -206,19 +211,23 @@ k_fused_sweep_wide(FusedParams P, int wx0, int wx1, int n_wide)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     unsigned bx, by, bz;
     fused_tile_coords(P, bx, by, bz);
-    const int sw = (int)bx * kWideWaves + wave;
-    const int ch = (int)bz;
-    const int chunk = P.nb_top + (int)by;
+    const int tile = (int)bx * kWideWaves + wave;
+    if (tile >= P.wide_tiles) return;
+    const int row = tile / P.wide_stride;         // channel * wide_nseg + segment
+    const int sw = tile - row * P.wide_stride;
+    if (sw >= n_wide) return;                     // (CCP_GS_WIDE_SEGMENTS=0 pads a row to whole blocks)
+    const int ch = row / P.wide_nseg;
+    const int seg = row - ch * P.wide_nseg;
     int ra, rb;
-    fused_chunk_rows(P, chunk, ra, rb);
+    wide_segment_rows(P.wide_y0, P.wide_y1, P.wide_h, seg, ra, rb);
     const bool run = (P.active == nullptr) || (P.active[ch] != 0);
-    if (run && sw < n_wide && ra < rb) {
+    if (run && ra < rb) {
         const Geom &g = P.g;
         const long off = (long)ch * g.ch_stride;
         unsigned long long t0 = 0;
         fused_trace_begin(P, t0);
         fused_wave_wide<T, STORE_RED>(P.xin + off, P.xout + off, P.b + off, g, wx0, wx1, sw, ra, rb, ring[wave]);
-        fused_trace_end(P, t0, (((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * kWideWaves + wave, chunk, sw, ch, 3);
+        fused_trace_end(P, t0, tile, seg, sw, ch, 3);      // slot = tile id, chunk field = segment
     }
 }
 

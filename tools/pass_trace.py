@@ -1,9 +1,12 @@
 """Where the time of ONE temporally blocked pass goes: per-wave start/end stamps (CCP_GS_TRACE_FILE, written by
-k_fused_sweep / k_fused_border themselves) turned into a timeline — waves in flight over time, tile durations by kind,
-how many CUs carry one or two workgroups, when the last tile of each kind starts.
+k_fused_sweep / k_fused_sweep_wide / k_fused_border themselves) turned into a timeline — waves in flight over time, tile
+durations by kind, how many CUs carry one or two workgroups, when the last tile of each kind starts.
 
   python tools/pass_trace.py W H C T R [row_begin rows ghost [edge]]      -> one JSON object on stdout
 (edge = 1: the pass is issued as the edges-first pass of a row block — ccp_grid_sweep_edges_first)
+The last call's two passes are summarised: "interior_pass" (its output is read by another unchecked pass) and the
+last-of-call pass at the top level.  Wide tiles (kernel id 3) hold one wave slot per SIMD (1024 on 256 CUs) and their
+chunk field is the row segment; the other kernels' slots are counted at 2 per SIMD.
 """
 import json
 import os
@@ -45,7 +48,8 @@ def summarise(head, words, bins=24):
     t_min = min(r[0] for r in recs)
     t_max = max(r[1] for r in recs)
     span = (t_max - t_min) / 100.0                                   # us (100 MHz clock)
-    kinds = {0: "ordinary", 1: "top/bottom chunk (border kernel)", 2: "side strip (border kernel)"}
+    kinds = {0: "ordinary", 1: "top/bottom chunk (border kernel)", 2: "side strip (border kernel)", 3: "wide (segment, strip)"}
+    is_wide = any(r[4] == 3 for r in recs)
     out = {"T": T, "rows_per_chunk": R, "grid": [gx, gy, gz], "border_grid_x": bgx, "waves": len(recs), "span_us": span, "by_kind": {}}
     for k, name in kinds.items():
         d = [(r[1] - r[0]) / 100.0 for r in recs if r[4] == k]
@@ -63,6 +67,28 @@ def summarise(head, words, bins=24):
             ov = min(r[1], hi) - max(r[0], lo)
             if ov > 0:
                 hist[b] += ov / w
+    if is_wide:
+        # one round? waves of the wide kernel that start after the first wide wave has ended; spread of their end times;
+        # the border kernel's waves: when they run, on how many CUs, and how many wide waves share a CU with them
+        wide = [r for r in recs if r[4] == 3]
+        first_end = min(r[1] for r in wide)
+        ends_w = sorted((r[1] - t_min) / 100.0 for r in wide)
+        border = [r for r in recs if r[4] in (1, 2)]
+        bcus = {r[2] for r in border}
+        dur_shared = [(r[1] - r[0]) / 100.0 for r in wide if r[2] in bcus]
+        dur_alone = [(r[1] - r[0]) / 100.0 for r in wide if r[2] not in bcus]
+        late = sorted(wide, key=lambda r: r[0])
+        out["wide"] = {"waves": len(wide), "segments": len({r[5] for r in wide}), "strips": len({r[6] for r in wide}),
+                       "slots_on_cus_seen": 4 * len({r[2] for r in recs}), "starts_after_first_end": sum(1 for r in wide if r[0] >= first_end),
+                       "first_end_us": (first_end - t_min) / 100.0, "last_start_us": (late[-1][0] - t_min) / 100.0,
+                       "end_us_min_p50_p90_max": [ends_w[0], ends_w[len(ends_w) // 2], ends_w[int(len(ends_w) * 0.9)], ends_w[-1]],
+                       "dur_us_by_start_quartile": [round(sum((r[1] - r[0]) for r in q) / 100.0 / max(1, len(q)), 1)
+                                                    for q in (late[i * len(late) // 4:(i + 1) * len(late) // 4] for i in range(4))],
+                       "border_waves": len(border), "border_cus": len(bcus),
+                       "border_first_start_us": min(((r[0] - t_min) / 100.0 for r in border), default=None),
+                       "border_last_end_us": max(((r[1] - t_min) / 100.0 for r in border), default=None),
+                       "wide_dur_us_avg_on_border_cus": round(sum(dur_shared) / max(1, len(dur_shared)), 1),
+                       "wide_dur_us_avg_elsewhere": round(sum(dur_alone) / max(1, len(dur_alone)), 1)}
     out["waves_in_flight_per_bin"] = [round(h, 1) for h in hist]
     out["wave_time_integral_us"] = sum((r[1] - r[0]) for r in recs) / 100.0
     cus = {}
@@ -73,7 +99,7 @@ def summarise(head, words, bins=24):
     out["waves_per_cu_min_med_max"] = [per_cu[0], per_cu[len(per_cu) // 2], per_cu[-1]]
     busy = []
     for v in cus.values():
-        busy.append(sum(r[1] - r[0] for r in v) / 100.0 / span / 8.0)  # fraction of the CU's 8 wave slots (2 per SIMD) over the span
+        busy.append(sum(r[1] - r[0] for r in v) / 100.0 / span / (4.0 if is_wide else 8.0))  # fraction of the CU's wave slots (2 per SIMD; wide: 1) over the span
     busy.sort()
     out["cu_slot_utilisation_min_med_max"] = [round(busy[0], 3), round(busy[len(busy) // 2], 3), round(busy[-1], 3)]
     # the waves that end last: (kind, chunk, strip, start us, duration us)
@@ -110,6 +136,8 @@ def main():
     passes = parse(path)
     os.unlink(path)
     res = summarise(*passes[-1])
+    if len(passes) >= 2:
+        res["interior_pass"] = summarise(*passes[-2])
     res["shape"] = [W, H, C, rb, rows, ghost]
     res["edges_first"] = bool(edge)
     print(json.dumps(res), flush=True)
