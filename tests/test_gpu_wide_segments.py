@@ -7,9 +7,10 @@ hold every (segment, strip, channel) tile of every wide pass exactly once, and a
 import numpy as np
 import pytest
 
+from rowblock_sweep_helpers import wide_passes, wide_strips      # the trace reader, shared with test_gpu_rowblock_depth8.py
+
 pytestmark = pytest.mark.gpu
 
-KERNEL_WIDE = 3
 T = 8
 MODES = [None, 0, 1, 2, 3, 5, 7]          # CCP_GS_WIDE_SEGMENTS: unset (the planner), the interior chunks, forced counts
 MIN_SEG = 64                              # kWideMinSegRows
@@ -60,17 +61,6 @@ def interior_rows(H, R):
     return rows(nb_top)[0], rows(n_chunks - nb_bot - 1)[1]
 
 
-def wide_strips(W):
-    U, n = 128 - 4 * T, -(-W // (128 - 4 * T))
-    left = 0
-    while left < n and left * U - 2 * T <= 0:
-        left += 1
-    right = 0
-    while left + right < n and (n - 1 - right) * U - 2 * T + 128 >= W - 1:
-        right += 1
-    return -(-((n - right) * U - left * U) // (256 - 4 * T))
-
-
 def by_count(rows, n):
     h = -(-rows // max(n, 1))
     h += h & 1
@@ -79,22 +69,6 @@ def by_count(rows, n):
 
 def expected_segments(mode, rows, R):
     return -(-rows // R) if mode == 0 else by_count(rows, mode)[0]
-
-
-def wide_passes(path):
-    """per recorded pass that ran the wide kernel: the (segment, strip, channel) of its records"""
-    raw = np.fromfile(path, dtype=np.uint64)
-    out, i = [], 0
-    while i < raw.size:
-        assert raw[i] == 0x43435054524143
-        n = int(raw[i + 6])
-        rec = raw[i + 8:i + 8 + n].reshape(-1, 4)
-        rec = rec[rec[:, 1] != 0]
-        tile = rec[((rec[:, 3] >> np.uint64(40)) & np.uint64(0xff)) == KERNEL_WIDE, 3]
-        if tile.size:
-            out.append([(int(t) & 0xffff, (int(t) >> 16) & 0xffff, (int(t) >> 32) & 0xff) for t in tile])
-        i += 8 + n
-    return out
 
 
 def run(capi, monkeypatch, mode, red_store, W, H, C, bs, rows, calls, trace=None, wide=True, checked_between=False):
