@@ -47,6 +47,8 @@ ABI_SYMBOLS = (
     "ccp_grid_assemble_rhs_device", "ccp_grid_assemble_from_images_device", "ccp_grid_store_u8_device", "ccp_grid_set_x_u8_device",
     "ccp_grid_assemble_region_rhs_device", "ccp_grid_assemble_clone_device", "ccp_grid_store_u8_composite_device",
     "ccp_grid_set_weights_host", "ccp_grid_set_weights_device", "ccp_grid_assemble_weighted_rhs", "ccp_grid_assemble_weighted_rhs_device",
+    "ccp_grid_set_weights_constrained_host", "ccp_grid_set_weights_constrained_device", "ccp_grid_assemble_constrained_rhs",
+    "ccp_grid_assemble_constrained_rhs_device", "ccp_grid_constraint_info",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
     "ccp_grid_attach_comm", "ccp_grid_set_overlap", "ccp_grid_exchange_halos", "ccp_grid_sweep_rowblocked",
     "ccp_grid_gauss_seidel_rowblocked", "ccp_grid_conjugate_gradient_rowblocked", "ccp_grid_residual_norm2_global", "ccp_grid_comm_stats",
@@ -232,6 +234,11 @@ def load() -> C.CDLL:
     L.ccp_grid_set_weights_device.argtypes = [vp, da, da, da]
     L.ccp_grid_assemble_weighted_rhs.argtypes = [vp, vp, vp, i64, vp, i64, i32]
     L.ccp_grid_assemble_weighted_rhs_device.argtypes = [vp, da, da, da, i32]
+    L.ccp_grid_set_weights_constrained_host.argtypes = [vp, vp, vp, vp, i64, vp, i64]
+    L.ccp_grid_set_weights_constrained_device.argtypes = [vp, da, da, da, da]
+    L.ccp_grid_assemble_constrained_rhs.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i32]
+    L.ccp_grid_assemble_constrained_rhs_device.argtypes = [vp, da, da, da, da, i32]
+    L.ccp_grid_constraint_info.argtypes = [vp, vp, vp, vp]
     L.ccp_grid_last_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i32)]
     L.ccp_grid_region_begin.argtypes = [vp]
     L.ccp_grid_region_end.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i64), C.POINTER(i64)]
@@ -944,13 +951,39 @@ class Grid:
             raise ValueError(f"{name} must be {self.H} x {self.W}")
         return a
 
-    def set_weights(self, wx=None, wy=None, lam=None):
+    def set_weights(self, wx=None, wy=None, lam=None, fixed=None):
         """The operator from H x W float32 host arrays: wx weighs the edge (x,y)-(x+1,y), wy the edge (x,y)-(x,y+1), lam
         the data term; None: wx, wy 1 everywhere, lam 0.  Negative, NaN or inf weights raise CcpError (BAD_ARG) and
-        leave the handle without an operator."""
+        leave the handle without an operator.  fixed: an H x W mask (non-zero = a pixel whose value is prescribed:
+        assemble_constrained_rhs), None: no fixed pixels."""
         planes = [self._plane(a, n) for a, n in ((wx, "wx"), (wy, "wy"), (lam, "lam"))]
         stride = 4 * self.W
-        check(self.L.ccp_grid_set_weights_host(self.h, *[_ptr(p) for p in planes], stride), "ccp_grid_set_weights_host")
+        if fixed is None:
+            check(self.L.ccp_grid_set_weights_host(self.h, *[_ptr(p) for p in planes], stride), "ccp_grid_set_weights_host")
+            return
+        fixed = np.ascontiguousarray(np.asarray(fixed) != 0, dtype=np.uint8)
+        if fixed.shape != (self.H, self.W):
+            raise ValueError(f"fixed must be {self.H} x {self.W}")
+        check(self.L.ccp_grid_set_weights_constrained_host(self.h, *[_ptr(p) for p in planes], stride, _ptr(fixed), self.W),
+              "ccp_grid_set_weights_constrained_host")
+
+    def assemble_constrained_rhs(self, gx=None, gy=None, f=None, values=None, init_x: bool = False):
+        """assemble_weighted_rhs on an operator with fixed pixels: `values` (float32 H x W x channels, None: 0) are the
+        prescribed values; x := values at the fixed pixels, whose neighbours' b takes them in.  init_x: x := f on the
+        live free pixels (0 on dead ones); otherwise x of the free pixels is left as it is."""
+        gx = None if gx is None else self._canvas_image(gx, np.float32)
+        gy = None if gy is None else self._canvas_image(gy, np.float32)
+        f = None if f is None else self._canvas_image(f, np.float32)
+        values = None if values is None else self._canvas_image(values, np.float32)
+        row = 4 * self.W * self.C
+        check(self.L.ccp_grid_assemble_constrained_rhs(self.h, _ptr(gx), _ptr(gy), row, _ptr(f), row, _ptr(values), row,
+                                                       1 if init_x else 0), "ccp_grid_assemble_constrained_rhs")
+
+    def constraint_info(self):
+        """(fixed pixels, free pixels with a non-empty row, edges with exactly one fixed end) of the installed operator."""
+        n = [C.c_int64() for _ in range(3)]
+        check(self.L.ccp_grid_constraint_info(self.h, *[C.byref(v) for v in n]), "ccp_grid_constraint_info")
+        return tuple(v.value for v in n)
 
     def assemble_weighted_rhs(self, gx=None, gy=None, f=None, init_x: bool = False):
         """b of every channel from float32 H x W x channels host arrays: guidance gx, gy (None: 0) and data f (None: 0);
@@ -980,11 +1013,37 @@ class Grid:
         sy, sx = t.stride()
         return DeviceArray(t.data_ptr(), DTYPE_F64 if t.dtype == torch.float64 else DTYPE_F32, 0, 0, sy, sx, 0)
 
-    def set_weights_tensor(self, wx=None, wy=None, lam=None):
-        """set_weights from H x W float32 / float64 tensors (expanded scalars broadcast); synchronises (the verdict)."""
+    def set_weights_tensor(self, wx=None, wy=None, lam=None, fixed=None):
+        """set_weights from H x W float32 / float64 tensors (expanded scalars broadcast); synchronises (the verdict).
+        fixed: an H x W uint8, bool, float32 or float64 tensor (!= 0: fixed), read on the device; None: no fixed pixels."""
         arrs = [self._weight_array(t, n) for t, n in ((wx, "wx"), (wy, "wy"), (lam, "lam"))]
         refs = [None if a is None else C.byref(a) for a in arrs]
-        self._on_stream(lambda: self.L.ccp_grid_set_weights_device(self.h, *refs), "ccp_grid_set_weights_device")
+        if fixed is None:
+            self._on_stream(lambda: self.L.ccp_grid_set_weights_device(self.h, *refs), "ccp_grid_set_weights_device")
+            return
+        torch = self._torch()
+        if isinstance(fixed, torch.Tensor) and fixed.dtype == torch.bool:
+            fixed = fixed.view(torch.uint8)
+        if isinstance(fixed, torch.Tensor) and fixed.dtype == torch.uint8:
+            if tuple(fixed.shape) != (self.H, self.W):
+                raise ValueError(f"fixed must be {self.H} x {self.W}, not {tuple(fixed.shape)}")
+            m = DeviceArray(*self._label_array(fixed.unsqueeze(-1)))
+        else:
+            m = self._weight_array(fixed, "fixed")
+        self._on_stream(lambda: self.L.ccp_grid_set_weights_constrained_device(self.h, *refs, C.byref(m)),
+                        "ccp_grid_set_weights_constrained_device")
+
+    def assemble_constrained_rhs_tensor(self, gx=None, gy=None, f=None, values=None, init_x: bool = False):
+        """assemble_constrained_rhs from H x W x channels tensors: gx, gy float32; f and values u8, float32 or float64."""
+        torch = self._torch()
+        any_ = (torch.uint8, torch.float32, torch.float64)
+        a = None if gx is None else self._hwc(gx, "gx", (torch.float32,))[0]
+        b = None if gy is None else self._hwc(gy, "gy", (torch.float32,))[0]
+        c = None if f is None else self._hwc(f, "f", any_)[0]
+        d = None if values is None else self._hwc(values, "values", any_)[0]
+        refs = [None if v is None else C.byref(v) for v in (a, b, c, d)]
+        self._on_stream(lambda: self.L.ccp_grid_assemble_constrained_rhs_device(self.h, *refs, 1 if init_x else 0),
+                        "ccp_grid_assemble_constrained_rhs_device")
 
     def assemble_weighted_rhs_tensor(self, gx=None, gy=None, f=None, init_x: bool = False):
         """assemble_weighted_rhs from H x W x channels tensors: gx, gy float32, f u8, float32 or float64."""

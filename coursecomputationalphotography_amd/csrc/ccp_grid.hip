@@ -140,6 +140,13 @@ struct ccp_grid {
     bool weighted = false;
     bool has_op = false;
     DevBuf<double> wop, wpart;
+    // Fixed pixels (ccp_grid_set_weights_constrained_*): wcons holds the planes ce, cs and lambda' (ccp_grid_weighted.hpp)
+    // while the operator has any (has_fixed), and is released otherwise.  wcount: the formation pass's verdict and counts;
+    // w_fixed / w_live / w_edges: ccp_grid_constraint_info's figures (w_live < 0: not counted yet)
+    bool has_fixed = false;
+    DevBuf<double> wcons;
+    DevBuf<unsigned long long> wcount;
+    long w_fixed = 0, w_live = -1, w_edges = 0;
     int mg_kind = CCP_MG_HIERARCHY_GALERKIN;   // ccp_grid_mg_set_hierarchy (weighted handles; survives ccp_grid_set_weights_*)
 };
 
@@ -999,6 +1006,7 @@ try {
         st = g->wop.alloc(4 * (size_t)geo.ch_stride);
         if (st == CCP_OK && hipMemset(g->wop.p, 0, 4 * sizeof(double) * (size_t)geo.ch_stride) != hipSuccess) st = CCP_ERR_HIP;
         if (st == CCP_OK) st = g->wpart.alloc(4 * (size_t)d->channels * kWeightedApplyBlocks);
+        if (st == CCP_OK) st = g->wcount.alloc(4);
     }
     // partial sums: the finest launch is one block per (x tile, row, channel*2) with 2 doubles
     const size_t part = (size_t)((geo.pitch + 2L * kBlock - 1) / (2L * kBlock)) * geo.local_rows * d->channels * 2 * 2 + 64;
@@ -1191,7 +1199,7 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     v->wd = op;
     v->wwe = op ? op + n : nullptr;
     v->wws = op ? op + 2 * n : nullptr;
-    v->wlam = op ? op + 3 * n : nullptr;
+    v->wlam = !op ? nullptr : g->has_fixed ? g->wcons.p + 2 * n : op + 3 * n;   // with fixed pixels: lambda' (ccp_grid_weighted.hpp)
     v->hierarchy_kind = g->mg_kind;
     v->stream = g->stream;
     v->cache = &g->mg;
@@ -2996,20 +3004,90 @@ int blend_composite(ccp_grid *g, const VU &canvas, const View<uint8_t> &out)
     return CCP_OK;
 }
 
-// F: the view of the data term f, float, double or u8; an absent input is a null view (guarded by its `has` bit)
-template <typename F>
-int weighted_rhs(ccp_grid *g, const VF &gx, const VF &gy, const F &f, int has, bool init_x)
+// F: the view of the data term f, float, double or u8; an absent input is a null view (guarded by its `has` bit).
+// V: the view of the prescribed values (has & 8), read only where the operator has fixed pixels.
+template <typename F, typename V>
+int weighted_rhs(ccp_grid *g, const VF &gx, const VF &gy, const F &f, int has, bool init_x, const V &values)
 {
     const Geom &geo = g->geom;
     const dim3 grid = pixel_grid(g, geo.H);
     const double *op = g->wop.p;
     const int C = g->desc.channels;
-    if (init_x)
-        hipLaunchKernelGGL((k_weighted_rhs<true, VF, F>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx, gy, f, has, C);
-    else
-        hipLaunchKernelGGL((k_weighted_rhs<false, VF, F>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx, gy, f, has, C);
+    if (g->has_fixed) {
+        if (init_x)
+            hipLaunchKernelGGL((k_weighted_rhs<true, true, VF, F, V>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx,
+                               gy, f, has, C, g->wcons.p, values);
+        else
+            hipLaunchKernelGGL((k_weighted_rhs<false, true, VF, F, V>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx,
+                               gy, f, has, C, g->wcons.p, values);
+    } else {
+        const VF none{nullptr, 0, 0, 0, 0};
+        const double *no_planes = nullptr;
+        if (init_x)
+            hipLaunchKernelGGL((k_weighted_rhs<true, false, VF, F, VF>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx,
+                               gy, f, has & 7, C, no_planes, none);
+        else
+            hipLaunchKernelGGL((k_weighted_rhs<false, false, VF, F, VF>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx,
+                               gy, f, has & 7, C, no_planes, none);
+    }
     CCP_HIP(hipGetLastError());
     return CCP_OK;
+}
+
+// the dispatch over f's dtype (NULL: no data term)
+template <typename V>
+int weighted_rhs_views(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f, int has, bool init,
+                       const V &values)
+{
+    const VF none{nullptr, 0, 0, 0, 0};
+    const VF vgx = gx ? view_of<const float>(gx) : none, vgy = gy ? view_of<const float>(gy) : none;
+    if (!f) return weighted_rhs(g, vgx, vgy, none, has, init, values);
+    if (f->dtype == CCP_DTYPE_U8) return weighted_rhs(g, vgx, vgy, view_of<const uint8_t>(f), has, init, values);
+    if (f->dtype == CCP_DTYPE_F32) return weighted_rhs(g, vgx, vgy, view_of<const float>(f), has, init, values);
+    return weighted_rhs(g, vgx, vgy, view_of<const double>(f), has, init, values);
+}
+
+// ccp_grid_assemble_weighted_rhs and ccp_grid_assemble_constrained_rhs: the host arrays staged, one launch, one wait
+int weighted_rhs_host(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes, const float *f, int64_t f_stride_bytes,
+                      const float *values, int64_t values_stride_bytes, bool init_x)
+{
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    const int64_t row = (int64_t)W * C * (int64_t)sizeof(float);
+    if ((gx || gy) && field_stride_bytes < row) return CCP_ERR_BAD_ARG;
+    if (f && f_stride_bytes < row) return CCP_ERR_BAD_ARG;
+    if (values && values_stride_bytes < row) return CCP_ERR_BAD_ARG;
+    if (!g->has_op) return CCP_ERR_STATE;
+    const float *src[4] = {gx, gy, f, values};
+    const int64_t stride[4] = {field_stride_bytes, field_stride_bytes, f_stride_bytes, values_stride_bytes};
+    DevBuf<float> dev[4];
+    VF v[4];
+    int has = 0;
+    for (int i = 0; i < 4; ++i) {
+        v[i] = VF{nullptr, 0, 0, 0, 0};
+        if (!src[i]) continue;
+        has |= 1 << i;
+        CCP_TRY(upload_window(g, dev[i], src[i], stride[i], 0, H));
+        v[i] = staged_view<const float>(dev[i].p, W, C);
+    }
+    CCP_TRY(weighted_rhs(g, v[0], v[1], v[2], has, init_x, v[3]));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    return CCP_OK;
+}
+
+int weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f,
+                        const ccp_device_array *values, bool init)
+{
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    if (gx) CCP_TRY(check_view(g, gx, kF32, false, 1, H, W, C));
+    if (gy) CCP_TRY(check_view(g, gy, kF32, false, 1, H, W, C));
+    if (f) CCP_TRY(check_view(g, f, kF32F64 | kU8, false, 1, H, W, C));
+    if (values) CCP_TRY(check_view(g, values, kF32F64 | kU8, false, 1, H, W, C));
+    if (!g->has_op) return CCP_ERR_STATE;
+    const int has = (gx ? 1 : 0) | (gy ? 2 : 0) | (f ? 4 : 0) | (values ? 8 : 0);
+    if (!values) return weighted_rhs_views(g, gx, gy, f, has, init, VF{nullptr, 0, 0, 0, 0});
+    if (values->dtype == CCP_DTYPE_U8) return weighted_rhs_views(g, gx, gy, f, has, init, view_of<const uint8_t>(values));
+    if (values->dtype == CCP_DTYPE_F32) return weighted_rhs_views(g, gx, gy, f, has, init, view_of<const float>(values));
+    return weighted_rhs_views(g, gx, gy, f, has, init, view_of<const double>(values));
 }
 
 }  // namespace
@@ -3305,45 +3383,28 @@ int ccp_grid_assemble_weighted_rhs(ccp_grid *g, const float *gx, const float *gy
                                    int64_t f_stride_bytes, int32_t init_x_from_f)
 try {
     CCP_TRY(weighted_handle(g));
-    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
-    const int64_t row = (int64_t)W * C * (int64_t)sizeof(float);
-    if ((gx || gy) && field_stride_bytes < row) return CCP_ERR_BAD_ARG;
-    if (f && f_stride_bytes < row) return CCP_ERR_BAD_ARG;
-    if (!g->has_op) return CCP_ERR_STATE;
-    const float *src[3] = {gx, gy, f};
-    const int64_t stride[3] = {field_stride_bytes, field_stride_bytes, f_stride_bytes};
-    DevBuf<float> dev[3];
-    VF v[3];
-    int has = 0;
-    for (int i = 0; i < 3; ++i) {
-        v[i] = VF{nullptr, 0, 0, 0, 0};
-        if (!src[i]) continue;
-        has |= 1 << i;
-        CCP_TRY(upload_window(g, dev[i], src[i], stride[i], 0, H));
-        v[i] = staged_view<const float>(dev[i].p, W, C);
-    }
-    CCP_TRY(weighted_rhs(g, v[0], v[1], v[2], has, init_x_from_f != 0));
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    return CCP_OK;
+    return weighted_rhs_host(g, gx, gy, field_stride_bytes, f, f_stride_bytes, nullptr, 0, init_x_from_f != 0);
 } CCP_ABI_CATCH
 
 int ccp_grid_assemble_weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f,
                                           int32_t init_x_from_f)
 try {
     CCP_TRY(weighted_handle(g));
-    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
-    if (gx) CCP_TRY(check_view(g, gx, kF32, false, 1, H, W, C));
-    if (gy) CCP_TRY(check_view(g, gy, kF32, false, 1, H, W, C));
-    if (f) CCP_TRY(check_view(g, f, kF32F64 | kU8, false, 1, H, W, C));
-    if (!g->has_op) return CCP_ERR_STATE;
-    const VF none{nullptr, 0, 0, 0, 0};
-    const VF vgx = gx ? view_of<const float>(gx) : none, vgy = gy ? view_of<const float>(gy) : none;
-    const int has = (gx ? 1 : 0) | (gy ? 2 : 0) | (f ? 4 : 0);
-    const bool init = init_x_from_f != 0;
-    if (!f) return weighted_rhs(g, vgx, vgy, none, has, init);
-    if (f->dtype == CCP_DTYPE_U8) return weighted_rhs(g, vgx, vgy, view_of<const uint8_t>(f), has, init);
-    if (f->dtype == CCP_DTYPE_F32) return weighted_rhs(g, vgx, vgy, view_of<const float>(f), has, init);
-    return weighted_rhs(g, vgx, vgy, view_of<const double>(f), has, init);
+    return weighted_rhs_device(g, gx, gy, f, nullptr, init_x_from_f != 0);
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_constrained_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes, const float *f,
+                                      int64_t f_stride_bytes, const float *values, int64_t values_stride_bytes, int32_t init)
+try {
+    CCP_TRY(weighted_handle(g));
+    return weighted_rhs_host(g, gx, gy, field_stride_bytes, f, f_stride_bytes, values, values_stride_bytes, init != 0);
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_constrained_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f,
+                                             const ccp_device_array *values, int32_t init)
+try {
+    CCP_TRY(weighted_handle(g));
+    return weighted_rhs_device(g, gx, gy, f, values, init != 0);
 } CCP_ABI_CATCH
 
 }  // extern "C"
@@ -3353,15 +3414,24 @@ try {
 // ============================================================================================
 namespace {
 
+// a new operator is coming: the old one, its counts and the hierarchy built on it go
+void drop_operator(ccp_grid *g)
+{
+    mg_release(g->mg);
+    g->mg = nullptr;
+    g->has_op = g->has_fixed = false;
+    g->w_fixed = g->w_edges = 0;
+    g->w_live = -1;
+}
+
 // The operator from three weight views in one pass; the device's verdict on the weights is read back once.  The old
 // operator and the hierarchy built on it are gone either way: a refusal leaves the handle with none.
 int set_weights(ccp_grid *g, const WeightView &wx, const WeightView &wy, const WeightView &lam)
 {
     const Geom &geo = g->geom;
     const long n = geo.ch_stride;
-    mg_release(g->mg);
-    g->mg = nullptr;
-    g->has_op = false;
+    drop_operator(g);
+    g->wcons.release();
     unsigned bad = 0;
     CCP_HIP(hipMemsetAsync(g->io_bad.p, 0, sizeof(unsigned), g->stream));
     hipLaunchKernelGGL(k_weighted_coef, dim3((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)geo.H), dim3(kBlock), 0, g->stream, wx, wy,
@@ -3374,18 +3444,60 @@ int set_weights(ccp_grid *g, const WeightView &wx, const WeightView &wy, const W
     return edge_timeout_status(g);
 }
 
+// set_weights with a mask of fixed pixels (M: its view): the planes of ccp_grid_weighted.hpp in one pass, whose verdict
+// and counts come back in one read.  The three extra planes stay only if any pixel is fixed: with none the four planes
+// are what set_weights forms, bit for bit.
+template <typename M>
+int set_weights_fixed(ccp_grid *g, const WeightView &wx, const WeightView &wy, const WeightView &lam, const M &fixed)
+{
+    const Geom &geo = g->geom;
+    const long n = geo.ch_stride;
+    drop_operator(g);
+    CCP_TRY(g->wcons.alloc(3 * (size_t)n));
+    CCP_HIP(hipMemsetAsync(g->wcons.p, 0, 3 * sizeof(double) * (size_t)n, g->stream));   // the pads
+    CCP_HIP(hipMemsetAsync(g->wcount.p, 0, 4 * sizeof(unsigned long long), g->stream));
+    hipLaunchKernelGGL((k_weighted_coef_fixed<M>), dim3((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)geo.H), dim3(kBlock), 0, g->stream,
+                       wx, wy, lam, fixed, geo.W, geo.H, geo.pitch, g->wop.p, g->wop.p + n, g->wop.p + 2 * n, g->wop.p + 3 * n, g->wcons.p,
+                       g->wcons.p + n, g->wcons.p + 2 * n, g->wcount.p);
+    CCP_HIP(hipGetLastError());
+    unsigned long long count[4] = {1, 0, 0, 0};
+    CCP_HIP(hipMemcpyAsync(count, g->wcount.p, sizeof(count), hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    if (count[0] || !count[1]) g->wcons.release();
+    if (count[0]) return CCP_ERR_BAD_ARG;
+    g->has_op = true;
+    g->has_fixed = count[1] != 0;
+    g->w_fixed = (long)count[1];
+    g->w_live = (long)geo.W * geo.H - (long)count[1] - (long)count[2];
+    g->w_edges = (long)count[3];
+    return edge_timeout_status(g);
+}
+
 }  // namespace
 
 extern "C" {
 
 int ccp_grid_set_weights_host(ccp_grid *g, const float *wx, const float *wy, const float *lambda, int64_t row_stride_bytes)
 try {
+    return ccp_grid_set_weights_constrained_host(g, wx, wy, lambda, row_stride_bytes, nullptr, 0);
+} CCP_ABI_CATCH
+
+int ccp_grid_set_weights_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda)
+try {
+    return ccp_grid_set_weights_constrained_device(g, wx, wy, lambda, nullptr);
+} CCP_ABI_CATCH
+
+int ccp_grid_set_weights_constrained_host(ccp_grid *g, const float *wx, const float *wy, const float *lambda, int64_t row_stride_bytes,
+                                          const uint8_t *fixed, int64_t fixed_stride_bytes)
+try {
     CCP_TRY(weighted_handle(g));
     const int W = g->desc.width, H = g->desc.height;
     const float *src[3] = {wx, wy, lambda};
     if ((wx || wy || lambda) && row_stride_bytes < (int64_t)W * (int64_t)sizeof(float)) return CCP_ERR_BAD_ARG;
+    if (fixed && fixed_stride_bytes < (int64_t)W) return CCP_ERR_BAD_ARG;
     const double dflt[3] = {1.0, 1.0, 0.0};
     DevBuf<float> dev[3];
+    DevBuf<uint8_t> dfix;
     WeightView v[3];
     for (int i = 0; i < 3; ++i) {
         v[i] = WeightView{nullptr, 0, 0, 0, dflt[i]};
@@ -3395,10 +3507,14 @@ try {
                                  hipMemcpyHostToDevice, g->stream));
         v[i] = WeightView{dev[i].p, (long)W, 1, 0, dflt[i]};
     }
-    return set_weights(g, v[0], v[1], v[2]);
+    if (!fixed) return set_weights(g, v[0], v[1], v[2]);
+    CCP_TRY(dfix.alloc((size_t)W * H));
+    CCP_HIP(hipMemcpy2DAsync(dfix.p, (size_t)W, fixed, (size_t)fixed_stride_bytes, (size_t)W, (size_t)H, hipMemcpyHostToDevice, g->stream));
+    return set_weights_fixed(g, v[0], v[1], v[2], View<const uint8_t>{dfix.p, 0, (long)W, 1, 0});
 } CCP_ABI_CATCH
 
-int ccp_grid_set_weights_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda)
+int ccp_grid_set_weights_constrained_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
+                                            const ccp_device_array *fixed)
 try {
     CCP_TRY(weighted_handle(g));
     const int W = g->desc.width, H = g->desc.height;
@@ -3411,7 +3527,32 @@ try {
         CCP_TRY(check_view(g, src[i], kF32F64, false, 1, H, W, 1));
         v[i] = WeightView{src[i]->data, (long)src[i]->stride_y, (long)src[i]->stride_x, src[i]->dtype == CCP_DTYPE_F64 ? 1 : 0, dflt[i]};
     }
-    return set_weights(g, v[0], v[1], v[2]);
+    if (!fixed) return set_weights(g, v[0], v[1], v[2]);
+    CCP_TRY(check_view(g, fixed, kF32F64 | kU8, false, 1, H, W, 1));
+    if (fixed->dtype == CCP_DTYPE_U8) return set_weights_fixed(g, v[0], v[1], v[2], view_of<const uint8_t>(fixed));
+    if (fixed->dtype == CCP_DTYPE_F32) return set_weights_fixed(g, v[0], v[1], v[2], view_of<const float>(fixed));
+    return set_weights_fixed(g, v[0], v[1], v[2], view_of<const double>(fixed));
+} CCP_ABI_CATCH
+
+int ccp_grid_constraint_info(ccp_grid *g, int64_t *fixed_pixels, int64_t *free_live_pixels, int64_t *boundary_edges)
+try {
+    CCP_TRY(weighted_handle(g));
+    if (!g->has_op) return CCP_ERR_STATE;
+    if (g->w_live < 0) {                                   // an operator of ccp_grid_set_weights_*: its dead pixels counted once
+        const Geom &geo = g->geom;
+        unsigned long long dead = 0;
+        CCP_HIP(hipMemsetAsync(g->wcount.p, 0, sizeof(unsigned long long), g->stream));
+        hipLaunchKernelGGL(k_weighted_count_dead, pixel_grid(g, geo.H), dim3(kBlock), 0, g->stream, g->wop.p, geo.W, geo.H, geo.pitch,
+                           g->wcount.p);
+        CCP_HIP(hipGetLastError());
+        CCP_HIP(hipMemcpyAsync(&dead, g->wcount.p, sizeof(dead), hipMemcpyDeviceToHost, g->stream));
+        CCP_HIP(hipStreamSynchronize(g->stream));
+        g->w_live = (long)geo.W * geo.H - (long)dead;
+    }
+    if (fixed_pixels) *fixed_pixels = g->w_fixed;
+    if (free_live_pixels) *free_live_pixels = g->w_live;
+    if (boundary_edges) *boundary_edges = g->w_edges;
+    return CCP_OK;
 } CCP_ABI_CATCH
 
 }  // extern "C"

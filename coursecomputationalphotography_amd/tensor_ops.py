@@ -184,3 +184,78 @@ def wls_smooth(image, iterations: int, lam: float = 1.0, alpha: float = 1.2, eps
     u = weighted_solve(None, None, f, iterations, wx=wx, wy=wy, data_weight=1.0, out_dtype=out_dtype, epsilon=epsilon,
                        hierarchy=hierarchy)
     return u if image.dim() == 3 else u[..., 0]
+
+
+def constrained_solve(gx, gy, f, values, fixed, iterations: int, wx=None, wy=None, data_weight=None, out_dtype=None,
+                      epsilon: float = 1e-10, hierarchy="rescaled"):
+    """weighted_solve with hard constraints: the pixels where `fixed` (an H x W uint8, bool, float32 or float64 tensor) is
+    non-zero keep the value `values` prescribes (u8 / float32 / float64 H x W x C, None: 0) and the energy of
+    weighted_solve is minimised over the others; edges that leave the canvas are absent, so the free region may touch
+    the canvas border.  The mask stays on the device: it is read by the kernel that forms the operator and never copied
+    to the host.  The start vector is f on the free pixels (0 without f).  Returns the composite -- the solution on the
+    free pixels, `values` on the fixed ones -- as out_dtype (torch.uint8 by default: clamped).  With data_weight None or
+    0 every connected set of free pixels needs a fixed neighbour, or the system is singular there."""
+    import torch
+    out_dtype = torch.uint8 if out_dtype is None else out_dtype
+    dev = _device_index(fixed)
+    H, W = fixed.shape[0], fixed.shape[1]
+    ref = next((t for t in (values, f, gx, gy) if t is not None), None)
+    C = ref.shape[2] if ref is not None and ref.dim() == 3 else 1
+    g = capi.Grid(W, H, C, device=dev, weighted=True)
+    g.set_stream(torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream)
+    try:
+        g.mg_set_hierarchy(hierarchy)
+        g.set_weights_tensor(_weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev), fixed=fixed)
+        if f is None:
+            g.fill_x(0.0)
+        g.assemble_constrained_rhs_tensor(gx, gy, f, values, init_x=f is not None)
+        g.mg_conjugate_gradient(epsilon, iterations, 2)
+        if out_dtype == torch.uint8:
+            return g.store_u8_tensor()
+        return g.get_x_tensor(dtype=out_dtype)
+    finally:
+        g.close()
+
+
+def clone_gradients(source, target=None):
+    """The guidance field of seamless cloning as float32 H x W x C forward differences (torch ops: plumbing): the source's,
+    or with `target` whichever of the two images' differences is larger in magnitude (ties take the source).  The last
+    column of gx and the last row of gy are 0 (never read)."""
+    import torch
+    s = source.to(torch.float32)
+    gx, gy = torch.zeros_like(s), torch.zeros_like(s)
+    gx[:, :-1] = s[:, 1:] - s[:, :-1]
+    gy[:-1] = s[1:] - s[:-1]
+    if target is not None:
+        t = target.to(torch.float32)
+        tx, ty = t[:, 1:] - t[:, :-1], t[1:] - t[:-1]
+        gx[:, :-1] = torch.where(tx.abs() > gx[:, :-1].abs(), tx, gx[:, :-1])
+        gy[:-1] = torch.where(ty.abs() > gy[:-1].abs(), ty, gy[:-1])
+    return gx, gy
+
+
+def seamless_clone_constrained(source, target, mask, iterations: int, mixed: bool = False, data_weight=None):
+    """Seamless cloning (Perez et al. 2003) on a weighted handle with fixed pixels: inside `mask` (H x W, non-zero = region)
+    the result follows the gradients of the u8 H x W x C tensor `source` (mixed: the stronger of source's and target's),
+    outside it is `target`.  Unlike seamless_clone the region may touch the canvas border (no condition is imposed there)
+    and the mask stays on the device.  data_weight (a scalar or an H x W tensor) > 0 also pulls the region towards the
+    source's colours (screened cloning).  The start vector is the target; multigrid-preconditioned CG, at most
+    `iterations` iterations.  Returns the composite, a u8 H x W x C tensor."""
+    import torch
+    if source.dim() == 2:
+        return seamless_clone_constrained(source.unsqueeze(-1), target.unsqueeze(-1), mask, iterations, mixed, data_weight)[..., 0]
+    dev = _device_index(target)
+    H, W, C = target.shape
+    gx, gy = clone_gradients(source, target if mixed else None)
+    fixed = mask == 0
+    g = capi.Grid(W, H, C, device=dev, weighted=True)
+    g.set_stream(torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream)
+    try:
+        g.mg_set_hierarchy("rescaled")
+        g.set_weights_tensor(None, None, _weight(data_weight, H, W, dev), fixed=fixed)
+        g.set_x_u8_tensor(target)
+        g.assemble_constrained_rhs_tensor(gx, gy, None if data_weight is None else source, target, init_x=False)
+        g.mg_conjugate_gradient(1e-10, iterations, 2)
+        return g.store_u8_tensor()
+    finally:
+        g.close()

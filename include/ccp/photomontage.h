@@ -290,4 +290,43 @@ inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageV
     detail::check(ccp_grid_store_u8(h.g, static_cast<uint8_t *>(out.data), (int64_t)out.step), "ccp_grid_store_u8");
 }
 
+// SolveWeighted with hard constraints (include/ccp_gs.h, "Hard constraints on weighted grids"): the pixels where `fixed`
+// (a one-channel u8 view, non-zero = fixed) is set keep the value `values` prescribes (float32, the image's shape; NULL:
+// 0), and the energy is minimised over the others from the start vector f (0 without f).  The free region may touch the
+// canvas border.  out: the clamped composite, the solution on the free pixels and `values` on the fixed ones.  With
+// lambda NULL or 0 every connected set of free pixels needs a fixed neighbour.
+inline void SolveConstrained(const ImageView *gx, const ImageView *gy, const ImageView *f, const ImageView *values, const ImageView &fixed,
+                             const ImageView *wx, const ImageView *wy, const ImageView *lambda, ImageView &out, int iterations,
+                             int device = 0, Hierarchy hierarchy = Hierarchy::Rescaled)
+{
+    const int C = out.channels;
+    if (!out.data) throw std::invalid_argument("SolveConstrained: no output image");
+    for (const ImageView *v : {gx, gy, f, values})
+        if (v && (!v->data || v->rows != out.rows || v->cols != out.cols || v->channels != C))
+            throw std::invalid_argument("SolveConstrained: image shapes differ");
+    for (const ImageView *v : {wx, wy, lambda, &fixed})
+        if (v && (!v->data || v->rows != out.rows || v->cols != out.cols || v->channels != 1))
+            throw std::invalid_argument("SolveConstrained: weights and mask must be one-channel views of the image's shape");
+    if (gx && gy && gx->step != gy->step) throw std::invalid_argument("SolveConstrained: gx and gy must share one row step");
+    std::size_t wstep = 0;
+    for (const ImageView *v : {wx, wy, lambda})
+        if (v) {
+            if (wstep && v->step != wstep) throw std::invalid_argument("SolveConstrained: the weights must share one row step");
+            wstep = v->step;
+        }
+    auto fp = [](const ImageView *v) { return v ? static_cast<const float *>(v->data) : nullptr; };
+    detail::GridHandle h(out.cols, out.rows, C, device, CCP_GRID_WEIGHTED);
+    detail::check(ccp_grid_mg_set_hierarchy(h.g, (int32_t)hierarchy), "ccp_grid_mg_set_hierarchy");
+    detail::check(ccp_grid_set_weights_constrained_host(h.g, fp(wx), fp(wy), fp(lambda), (int64_t)wstep,
+                                                        static_cast<const uint8_t *>(fixed.data), (int64_t)fixed.step),
+                  "ccp_grid_set_weights_constrained_host");
+    if (!f) detail::check(ccp_grid_fill_x(h.g, 0.0), "ccp_grid_fill_x");
+    const int64_t gstep = gx ? (int64_t)gx->step : gy ? (int64_t)gy->step : 0;
+    detail::check(ccp_grid_assemble_constrained_rhs(h.g, fp(gx), fp(gy), gstep, fp(f), f ? (int64_t)f->step : 0, fp(values),
+                                                    values ? (int64_t)values->step : 0, f ? 1 : 0),
+                  "ccp_grid_assemble_constrained_rhs");
+    detail::solve(h.g, Solver::MultigridConjugateGradient, iterations, C);
+    detail::check(ccp_grid_store_u8(h.g, static_cast<uint8_t *>(out.data), (int64_t)out.step), "ccp_grid_store_u8");
+}
+
 }  // namespace ccp

@@ -643,6 +643,67 @@ int ccp_grid_assemble_weighted_rhs(ccp_grid *g, const float *gx, const float *gy
 int ccp_grid_assemble_weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy,
                                           const ccp_device_array *f, int32_t init_x_from_f);
 
+/* ---- Hard constraints on weighted grids: fixed pixels ------------------------------------------------------------------
+ * A weighted handle's operator may carry a set F of fixed pixels: pixels whose value is prescribed, as the pixels
+ * around a Dirichlet region are, with weights, lambda and a region that may touch the canvas border (edges that leave
+ * the canvas are simply absent, as on every weighted handle).  With the names above (wN = wy(x,y-1), wW = wx(x-1,y),
+ * wE = wx(x,y), wS = wy(x,y), terms of absent edges skipped):
+ *   free pixel p:   d is formed exactly as above -- lambda; += wN; += wW; += wE; += wS over ALL in-canvas edges, whether
+ *                   or not the neighbour is fixed.  The stored weight to the east / south cell is wE / wS if both ends
+ *                   are free, else 0.  lambda' = lambda; += cN; += cW; += cE; += cS, where c. is the edge's weight if
+ *                   that neighbour is fixed and the term is skipped otherwise.  lambda' is the lambda the multigrid
+ *                   hierarchy carries, so every coarse diagonal is still lambda_c plus the leaving edge weights, for
+ *                   both CCP_MG_HIERARCHY_* kinds.
+ *   fixed pixel:    d = we = ws = lambda' = 0: dead.
+ * Right-hand side per channel at a free pixel, w. the ORIGINAL weights of all in-canvas edges, lambda the caller's (not
+ * lambda'), v the prescribed values:
+ *     t = 0; t += wN gy(x,y-1); t += wW gx(x-1,y); t += -(wE gx(x,y)); t += -(wS gy(x,y)); t += lambda f(x,y);
+ *     t += cN v(x,y-1); t += cW v(x-1,y); t += cE v(x+1,y); t += cS v(x,y+1)
+ * (terms of free neighbours and of absent edges skipped).  At a fixed pixel b = 0 and x := v.  With init, x := f on live
+ * free pixels and 0 on dead free ones; without, x of the free pixels is left untouched.  With F empty the operator and b
+ * are those of ccp_grid_set_weights_* and ccp_grid_assemble_weighted_rhs, bit for bit.
+ *
+ * ccp_grid_mg_conjugate_gradient, ccp_grid_mg_apply, ccp_grid_b_from_x and ccp_grid_residual_norm2 treat fixed pixels as
+ * dead, and ccp_grid_mg_conjugate_gradient leaves x at a fixed pixel unchanged (its search direction is 0 there): get_x,
+ * ccp_grid_store_u8 and their device twins return the composite -- the solution on the free pixels, the prescribed values
+ * on the fixed ones -- with no extra pass.  ccp_grid_mg_apply writes 0 there, as on every dead pixel, and
+ * ccp_grid_fill_x, _randomize_x and _set_x* overwrite the whole plane, the prescribed values included: assemble again
+ * (without init) to put them back.
+ *
+ * Storage: the boundary weights c. (an east and a south plane) and lambda' live in three more planes of one channel's
+ * layout, 24 bytes per pixel, allocated while a non-empty F is installed and released otherwise; the caller's lambda
+ * cannot be recovered from lambda', so both are kept.
+ *
+ * Known limit: edge-aware (WLS) weights with lambda = 0 that are anchored only by sparse fixed pixels do not converge
+ * within hundreds of iterations: the point smoother's weakness on strongly anisotropic weights (NOTES R10.1), not a
+ * property of the constraints.  Uniform or constant weights anchored by fixed pixels, and any weights with lambda > 0,
+ * converge as on an unconstrained handle.
+ *
+ * ccp_grid_set_weights_constrained_host: ccp_grid_set_weights_host plus `fixed`, uint8 H x W with its own row stride,
+ * non-zero = fixed, NULL = none.  One HIP pass forms every plane and validates the weights (those of fixed pixels
+ * too); the read-back of the verdict also brings the counts of ccp_grid_constraint_info.  A refused operator leaves the
+ * handle with none.  ccp_grid_set_weights_host / _device install F = empty. */
+int ccp_grid_set_weights_constrained_host(ccp_grid *g, const float *wx, const float *wy, const float *lambda,
+                                          int64_t row_stride_bytes, const uint8_t *fixed, int64_t fixed_stride_bytes);
+/* The twin on device views: `fixed` U8, F32 or F64, H x W (stride_c unused), != 0 is fixed; NULL: none.  The mask is
+ * read on the device only.  Synchronises (the verdict), as ccp_grid_set_weights_device. */
+int ccp_grid_set_weights_constrained_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy,
+                                            const ccp_device_array *lambda, const ccp_device_array *fixed);
+/* b and the prescribed values of every channel in one launch: ccp_grid_assemble_weighted_rhs plus `values`, float32
+ * H x W x channels with its own row stride (NULL: 0 everywhere; read at fixed pixels only).  ccp_grid_assemble_weighted_rhs
+ * on an operator with fixed pixels is this call with values NULL.  Synchronises. */
+int ccp_grid_assemble_constrained_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes,
+                                      const float *f, int64_t f_stride_bytes, const float *values,
+                                      int64_t values_stride_bytes, int32_t init);
+/* The twin on device views: gx, gy F32; f and values U8, F32 or F64; NULL descriptors as NULL host arrays.  Async: no
+ * allocation, no host synchronisation. */
+int ccp_grid_assemble_constrained_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy,
+                                             const ccp_device_array *f, const ccp_device_array *values, int32_t init);
+/* The installed operator's counts (any pointer may be NULL): fixed pixels, free pixels with d != 0, and edges with
+ * exactly one fixed end.  After ccp_grid_set_weights_* the live pixels are counted at the first call (one small pass
+ * and a read-back).  Not a weighted handle: CCP_ERR_UNSUPPORTED; no operator: CCP_ERR_STATE. */
+int ccp_grid_constraint_info(ccp_grid *g, int64_t *fixed_pixels, int64_t *free_live_pixels, int64_t *boundary_edges);
+
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
 int ccp_grid_last_timing(ccp_grid *g, float *milliseconds, int32_t *kernel_launches);
