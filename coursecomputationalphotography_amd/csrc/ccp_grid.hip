@@ -250,78 +250,104 @@ int one_iteration(ccp_grid *g, bool l1, const int *active, long *blocks_out)
     return CCP_OK;
 }
 
-// Which tiles of a pass can touch a pixel with a missing neighbour (same predicates the kernels
-// used to evaluate per wave): leading / trailing chunks by rows, leading / trailing strips by columns.
-// edge_rows > 0 (row block with neighbours, the pass whose result is exchanged): chunk 0 / the last chunk
-// are cut to exactly the owned rows the upper / lower neighbour takes, so they finish — and are
-// signalled — early (FusedParams::first_edge / last_edge).
-void fused_tile_counts(const ccp_grid *g, int T, FusedParams &P, int edge_rows = 0)
+// The handle as the pass planner sees it (ccp_fused_plan.hpp), with the chunk height in force at depth T.
+FusedPlanInput plan_input(const ccp_grid *g, int T)
 {
-    const Geom &geo = g->geom;
-    const int HS = 2 * T, R = P.rows_per_chunk;
-    // Only IMAGE edges need the border arithmetic.  At the stale edge of a ghost zone the rows next to
-    // the edge are invalid by construction (validity recedes one row per half-sweep, they are neither
-    // stored nor used), so a tile there is an ordinary tile: the rows beyond the block read as 0.
-    // A chunk row at an image edge is cut short: HS + 16 rows, enough for the chunk next to it to be
-    // clear of the edge (its halo starts below image row 0 / ends above image row H-1).
-    const int rows = P.st_hi - P.st_lo;
-    const int edge_short = HS + 16;
-    const bool at_top = geo.y0 + P.st_lo - HS <= 0, at_bot = geo.y0 + P.st_hi + HS >= geo.H - 1;
-    const bool short_edges = g->short_edges;
-    P.first_rows = (short_edges && at_top && rows > 2 * edge_short + R / 2 && R > edge_short) ? edge_short : 0;
-    P.last_rows = (short_edges && at_bot && rows > 2 * edge_short + R / 2 && R > edge_short) ? edge_short : 0;
-    P.first_edge = P.last_edge = 0;
-    if (edge_rows > 0) {
-        // rows from the first / last stored row that cover the neighbour's share of the owned rows
-        int want_top = (g->shrink_top && !at_top) ? geo.own_lo + std::min(edge_rows, g->send_up > 0 ? g->send_up : edge_rows) - P.st_lo : 0;
-        int want_bot = (g->shrink_bottom && !at_bot) ? P.st_hi - (geo.own_hi - std::min(edge_rows, g->send_down > 0 ? g->send_down : edge_rows)) : 0;
-        want_top += want_top & 1;
-        want_bot += want_bot & 1;
-        const int others = P.first_rows + P.last_rows;
-        if (want_top > 0 && want_bot > 0 && rows < want_top + want_bot + others + 2) want_top = want_bot = 0;   // too thin a block
-        if (want_top > 0 && rows >= want_top + others + 2 && P.first_rows == 0) {
-            P.first_rows = want_top;
-            P.first_edge = 1;
-        }
-        if (want_bot > 0 && rows >= want_bot + P.first_rows + 2 && P.last_rows == 0) {
-            P.last_rows = want_bot;
-            P.last_edge = 1;
-        }
-    }
-    const int mid = rows - P.first_rows - P.last_rows;
-    if (P.first_edge || P.last_edge) {
-        // the edge chunks take tile slots too: give the middle correspondingly fewer, taller chunks, so the
-        // pass needs no more rounds on the chip's wave slots than it would without the hand-off (one
-        // workgroup past a whole round costs a round).  (Round 3 tried the alternative — regular chunks of the usual
-        // height plus short FOLLOW-UP chunks dispatched last, which take over the slots the edge tiles free after a
-        // third of the pass: 0.760 ms per 32-iteration interval of a 2048-row block against 0.752 ms for this scheme and
-        // 0.714 ms without the hand-off, profiles/r03_rank_block_edges.jsonl — two more chunk rows of halo cost what
-        // the better packing saves.)
-        const int n_whole = (rows + R - 1) / R;
-        const int n_mid = std::max(1, n_whole - P.first_edge - P.last_edge);
-        int r_mid = (mid + n_mid - 1) / n_mid;
-        r_mid += r_mid & 1;
-        P.rows_per_chunk = std::max(R, r_mid);
-    }
-    P.n_chunks = (mid + P.rows_per_chunk - 1) / P.rows_per_chunk + (P.first_rows > 0) + (P.last_rows > 0);
-    auto top = [&](int c) { int ra, rb; fused_chunk_rows(P, c, ra, rb); return geo.y0 + ra - HS <= 0; };
-    auto bot = [&](int c) { int ra, rb; fused_chunk_rows(P, c, ra, rb); return geo.y0 + rb + HS >= geo.H - 1; };
-    P.nb_top = 0;
-    while (P.nb_top < P.n_chunks && top(P.nb_top)) ++P.nb_top;
-    P.nb_bot = 0;
-    while (P.nb_top + P.nb_bot < P.n_chunks && bot(P.n_chunks - 1 - P.nb_bot)) ++P.nb_bot;
-    const int U = fused_useful_px(T);
-    auto left = [&](int s) { return s * U - fused_halo_px(T) <= 0; };
-    auto right = [&](int s) { return s * U - fused_halo_px(T) + 2 * kStripLanes >= geo.W - 1; };
-    P.ns_left = 0;
-    while (P.ns_left < P.n_strips && left(P.ns_left)) ++P.ns_left;
-    P.ns_right = 0;
-    while (P.ns_left + P.ns_right < P.n_strips && right(P.n_strips - 1 - P.ns_right)) ++P.ns_right;
-    if (g->all_border) {                 // debug: every tile through the border launch
-        P.nb_top = P.n_chunks;
-        P.nb_bot = 0;
-    }
+    FusedPlanInput in;
+    in.g = g->geom;
+    in.stale_top = g->shrink_top;
+    in.stale_bottom = g->shrink_bottom;
+    in.ghost = g->desc.ghost;
+    in.ghost_top = g->ghost_top;
+    in.ghost_bottom = g->ghost_bottom;
+    in.send_up = g->send_up;
+    in.send_down = g->send_down;
+    in.channels = g->desc.channels;
+    in.cus = g->cus;
+    in.rows_per_chunk = (g->tuned && g->tune_rows[T] > 0) ? g->tune_rows[T] : g->rows_per_chunk;
+    in.short_edges = g->short_edges;
+    in.all_border = g->all_border;
+    in.side_rows_override = g->side_rows_override;
+    in.wide = g->wide;
+    in.wide_segments = g->wide_segments;
+    return in;
 }
+
+// One planned pass: all a launcher needs beside the handle.
+// l1: 0 none, 1 step of the last sweep, 2 step of every sweep of the pass; l1_blocks[0/1]: block results per
+// (sweep, channel) of the ordinary / the border launch.
+// store_red = false: the ordinary tiles of an unchecked pass store only the black halves (fused_wave says when that is
+// safe; run_unchecked decides); border tiles, checked and edge passes always store both.
+struct FusedPass {
+    FusedPlan plan;
+    const double *xin = nullptr;
+    double *xout = nullptr;
+    const int *active = nullptr;
+    int l1 = 0;
+    long *l1_blocks = nullptr;
+    bool store_red = true;
+};
+
+// Plans the pass `kind` (depth, rows, l1, multi) on this handle.  edge_rows > 0: the EDGE kernels (edge chunks first,
+// in-launch signal) where the pass can signal by itself: unchecked, every channel, a counter to count in.
+FusedPass plan_pass(const ccp_grid *g, FusedPassKind kind, const int *active = nullptr, int edge_rows = 0)
+{
+    kind.masked = g->masked;
+    kind.edge_rows = (edge_rows > 0 && kind.l1 == 0 && active == nullptr && g->edge_counter && g->edge_signal) ? edge_rows : 0;
+    FusedPass pass;
+    pass.plan = fused_plan(plan_input(g, kind.T), kind);
+    pass.active = active;
+    pass.l1 = kind.l1;
+    return pass;
+}
+
+// The kernels' argument: the plan's tiling and the handle's buffers (no hand-off, no trace).
+FusedParams fused_params(const ccp_grid *g, const FusedPass &pass)
+{
+    const FusedPlan &L = pass.plan;
+    FusedParams P{};
+    P.xin = pass.xin;
+    P.xout = pass.xout;
+    P.b = g->b.p;
+    P.g = g->geom;
+    P.st_lo = L.st_lo;
+    P.st_hi = L.st_hi;
+    P.rows_per_chunk = L.rows_per_chunk;
+    P.first_rows = L.first_rows;
+    P.last_rows = L.last_rows;
+    P.n_strips = L.n_strips;
+    P.partial = g->partial.p;
+    P.active = pass.active;
+    P.n_chunks = L.n_chunks;
+    P.nb_top = L.nb_top;
+    P.nb_bot = L.nb_bot;
+    P.ns_left = L.ns_left;
+    P.ns_right = L.ns_right;
+    P.side_rows = L.side_rows;
+    P.side_subs = L.side_subs;
+    P.side_rows_edge = L.side_rows_edge;
+    P.partial_border = g->partial.p + g->partial_region;
+    P.mask = g->maskp.p;
+    P.first_edge = L.first_edge;
+    P.last_edge = L.last_edge;
+    P.xcd_swizzle = g->xcd_swizzle ? 1 : 0;
+    P.wide_y0 = L.wide_y0;
+    P.wide_y1 = L.wide_y1;
+    P.wide_h = L.wide_h;
+    P.wide_nseg = L.wide_nseg;
+    P.wide_stride = L.wide_stride;
+    P.wide_tiles = L.wide_tiles;
+    return P;
+}
+
+void report_l1_blocks(const FusedPass &pass)
+{
+    if (!pass.l1_blocks) return;
+    const FusedPlan &L = pass.plan;
+    pass.l1_blocks[0] = L.any_plain ? (long)L.grid_x * L.grid_y : 0;
+    pass.l1_blocks[1] = L.n_border ? (long)L.bgrid_x : 0;
+}
+
 
 // Which tiles of a Dirichlet-mask grid hold unknowns: one census per tiling (depth, chunk rows, row range).
 int masked_tile_census(ccp_grid *g, const FusedParams &P, int T)
@@ -344,28 +370,13 @@ int masked_tile_census(ccp_grid *g, const FusedParams &P, int T)
 // One pass of depth T over a Dirichlet-mask grid: every tile is an ordinary tile (zero lies outside the block
 // as it does outside the region), tiles without any unknown in reach leave at once.
 template <int T>
-int launch_fused_masked(ccp_grid *g, FusedParams &P, int l1, long *l1_blocks, bool store_red)
+int launch_fused_masked(ccp_grid *g, const FusedParams &P, const FusedPass &pass)
 {
     if (T > kMaskedMaxT) return CCP_ERR_BAD_ARG;
     constexpr int TM = T <= kMaskedMaxT ? T : 1;
-    const int rows = P.st_hi - P.st_lo;
-    P.first_rows = P.last_rows = 0;
-    P.first_edge = P.last_edge = 0;
-    P.n_chunks = (rows + P.rows_per_chunk - 1) / P.rows_per_chunk;
-    P.nb_top = P.nb_bot = P.ns_left = P.ns_right = 0;
-    P.side_rows = P.rows_per_chunk;
-    P.side_subs = 1;
-    P.side_rows_edge = P.rows_per_chunk;
-    P.edge_counter = nullptr;
-    P.edge_flag = nullptr;
-    P.edge_target = P.edge_epoch = 0;
-    P.trace = nullptr;
-    const int waves = kBlock / kWave;
-    dim3 grid((unsigned)((P.n_strips + waves - 1) / waves), (unsigned)P.n_chunks, (unsigned)g->desc.channels);
-    if (l1_blocks) {
-        l1_blocks[0] = (long)grid.x * grid.y;
-        l1_blocks[1] = 0;
-    }
+    const int l1 = pass.l1;
+    const dim3 grid(pass.plan.grid_x, pass.plan.grid_y, (unsigned)g->desc.channels);
+    report_l1_blocks(pass);
     CCP_TRY(masked_tile_census(g, P, T));
     static const bool clip_rows = !(getenv("CCP_GS_MASK_ROWS") && atoi(getenv("CCP_GS_MASK_ROWS")) == 0);   // A/B: march every row of a live tile
     const int *rows_p = clip_rows ? g->tile_rows.p : nullptr;
@@ -373,7 +384,7 @@ int launch_fused_masked(ccp_grid *g, FusedParams &P, int l1, long *l1_blocks, bo
     constexpr int TMC = T <= kMaskedMaxCheckedT ? T : 1;
     if (l1 == 2) hipLaunchKernelGGL((k_fused_sweep_masked<TMC, 2, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P, g->tile_live.p, rows_p);
     else if (l1 == 1) hipLaunchKernelGGL((k_fused_sweep_masked<TM, 1, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P, g->tile_live.p, rows_p);
-    else if (!store_red) hipLaunchKernelGGL((k_fused_sweep_masked<TM, 0, kFusedUnroll, false>), grid, dim3(kBlock), 0, g->stream, P, g->tile_live.p, rows_p);
+    else if (!pass.store_red) hipLaunchKernelGGL((k_fused_sweep_masked<TM, 0, kFusedUnroll, false>), grid, dim3(kBlock), 0, g->stream, P, g->tile_live.p, rows_p);
     else hipLaunchKernelGGL((k_fused_sweep_masked<TM, 0, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P, g->tile_live.p, rows_p);
     CCP_HIP(hipGetLastError());
     g->last_launches++;
@@ -382,126 +393,32 @@ int launch_fused_masked(ccp_grid *g, FusedParams &P, int l1, long *l1_blocks, bo
     return CCP_OK;
 }
 
-// One pass of depth T.  l1: 0 none, 1 step of the last sweep, 2 step of every sweep of the pass;
-// l1_blocks[0/1]: block results per (sweep, channel) of the ordinary / the border launch.
-// edge_rows > 0: the EDGE kernels (edge chunks first, in-launch signal); *signalled tells the caller
-// whether the pass will publish g->edge_epoch itself.
-// store_red = false: the ordinary tiles of an unchecked pass store only the black halves (fused_wave says when that is
-// safe; run_unchecked decides); border tiles, checked and edge passes always store both.
+// One pass of depth T = pass.plan.T: the kernels' argument from the plan, the instantiation, the launches on two streams.
 template <int T>
-int launch_fused_t(ccp_grid *g, const double *xin, double *xout, int st_lo, int st_hi, const int *active,
-                   int l1 = 0, long *l1_blocks = nullptr, int rows_override = 0, int edge_rows = 0, bool *signalled = nullptr,
-                   bool store_red = true)
+int launch_fused_t(ccp_grid *g, const FusedPass &pass)
 {
-    FusedParams P;
-    P.xin = xin;
-    P.xout = xout;
-    P.b = g->b.p;
-    P.g = g->geom;
-    P.st_lo = st_lo;
-    P.st_hi = st_hi;
-    P.rows_per_chunk = rows_override > 0 ? rows_override : ((g->tuned && g->tune_rows[T] > 0) ? g->tune_rows[T] : g->rows_per_chunk);
-    const int U = fused_useful_px(T);
-    P.n_strips = (g->geom.W + U - 1) / U;
-    P.partial = g->partial.p;
-    P.partial_border = g->partial.p + g->partial_region;
-    P.active = active;
-    P.xcd_swizzle = g->xcd_swizzle ? 1 : 0;
-    const bool want_edge = edge_rows > 0 && l1 == 0 && active == nullptr && g->edge_counter && g->edge_signal;
-    P.mask = g->maskp.p;
-    if (l1 != 0 || edge_rows > 0) store_red = true;
-    if (g->masked) return launch_fused_masked<T>(g, P, l1, l1_blocks, store_red);
-    fused_tile_counts(g, T, P, want_edge ? edge_rows : 0);
+    const FusedPlan &L = pass.plan;
+    const int l1 = pass.l1;
+    FusedParams P = fused_params(g, pass);
+    if (g->masked) return launch_fused_masked<T>(g, P, pass);
     const int waves = kBlock / kWave;
-    const int edge_chunks = std::min(P.nb_top + P.nb_bot, P.n_chunks);
-    const int edge_strips = std::min(P.ns_left + P.ns_right, P.n_strips);
-    // side-strip tiles: ~2.5x the time per march step of an ordinary tile -> 2/5 of its march length
-    {
-        const int HS = 2 * T, R = P.rows_per_chunk;               // (possibly raised by fused_tile_counts for an edge pass)
-        int sr = std::max(16, (R + 2 * HS) * 2 / 5 - 2 * HS);
-        sr += sr & 1;
-        if (g->side_rows_override > 0) sr = std::max(2, g->side_rows_override);
-        P.side_rows = std::min(sr, R);
-        P.side_subs = (R + P.side_rows - 1) / P.side_rows;
-        // the side strips of an edge chunk are cut finer (their waves march ~2.5x slower and a sub-tile pays
-        // 4T rows of halo march whatever its height: 16 rows end at about half a pass)
-        P.side_rows_edge = std::min(P.side_rows, 16);
-        if (P.first_edge || P.last_edge)
-            P.side_subs = std::max(P.side_subs, (std::max(P.first_rows, P.last_rows) + P.side_rows_edge - 1) / P.side_rows_edge);
-    }
-    const long n_border = (long)edge_chunks * (P.n_strips - edge_strips) + (long)P.n_chunks * edge_strips * P.side_subs;
-    const bool any_plain = edge_chunks < P.n_chunks && edge_strips < P.n_strips;
-    dim3 grid((unsigned)((P.n_strips + waves - 1) / waves), (unsigned)P.n_chunks, (unsigned)g->desc.channels);
-    dim3 bgrid((unsigned)((n_border + waves - 1) / waves), 1, (unsigned)g->desc.channels);
-    if (l1_blocks) {
-        l1_blocks[0] = any_plain ? (long)grid.x * grid.y : 0;
-        l1_blocks[1] = n_border ? (long)bgrid.x : 0;
-    }
+    const long n_border = L.n_border;
+    const bool any_plain = L.any_plain, edge = L.edge, wide = L.wide, store_red = pass.store_red;
+    const dim3 grid(L.grid_x, L.grid_y, (unsigned)g->desc.channels);
+    const dim3 bgrid(L.bgrid_x, 1, (unsigned)g->desc.channels);
+    const dim3 wgrid(L.wgrid_x, 1, 1);
+    report_l1_blocks(pass);
     if (l1 == 2 && T > kFusedMaxCheckedT) return CCP_ERR_BAD_ARG;
-    // in-launch signal: every wave of an edge chunk (inner strips: one wave per strip in either kernel;
-    // edge strips: one wave per non-empty sub-tile) counts itself once per channel
-    const bool edge = want_edge && (P.first_edge || P.last_edge);
     P.edge_counter = g->edge_counter;
     P.edge_flag = g->edge_flag;
     P.edge_epoch = g->edge_epoch;
-    P.edge_target = 0;
+    P.edge_target = L.edge_target;
     if (edge) {
-        long waves_expected = 0;
-        for (int c = 0; c < P.n_chunks; c += std::max(1, P.n_chunks - 1)) {      // chunk 0 and chunk n_chunks-1, once each
-            if (!fused_is_edge_chunk(P, c)) continue;
-            int ra, rb;
-            fused_chunk_rows(P, c, ra, rb);
-            const int subs = std::min(P.side_subs, (rb - ra + P.side_rows_edge - 1) / P.side_rows_edge);
-            waves_expected += (P.n_strips - edge_strips) + (long)edge_strips * subs;
-        }
-        P.edge_target = (unsigned long long)waves_expected * g->desc.channels;
         // every edge pass counts from zero in a ring slot of its own (a miscount can cost one overlap, never
         // the next); the whole ring is cleared once per kEdgeRing epochs, off the critical path of a pass
         if (g->edge_epoch % kEdgeRing == 0) CCP_HIP(hipMemsetAsync(g->edge_counter, 0, sizeof(unsigned long long) * kEdgeRing, g->stream));
         P.edge_counter = g->edge_counter + (g->edge_epoch % kEdgeRing);
     }
-    if (signalled) *signalled = edge;
-    // The ordinary tiles of an unchecked depth-8 pass run on wide strips (k_fused_sweep_wide): the columns
-    // [wx0, wx1) that the inner narrow strips would store, in the rows of the chunks between the border chunk rows.  The
-    // border tiles keep the narrow tiling above, so ns_left / ns_right and the red-skip argument at fused_wave hold as
-    // they are.  The interior rows are one contiguous range, cut into segments sized to the device's wave slots instead
-    // of into the chunks (ccp_wide_plan.hpp); the launch is a flat list of tiles.
-    const int wx0 = P.ns_left * U, wx1 = (P.n_strips - P.ns_right) * U;
-    const int n_wide = (T == kWideT && any_plain) ? (wx1 - wx0 + wide_useful_px(T) - 1) / wide_useful_px(T) : 0;
-    const bool wide = T == kWideT && g->wide && l1 == 0 && !edge && any_plain && n_wide > 0;
-    P.wide_y0 = P.wide_y1 = P.wide_nseg = P.wide_tiles = 0;
-    P.wide_stride = 1;
-    P.wide_h = 2;
-    if (wide) {
-        int t;
-        fused_chunk_rows(P, P.nb_top, P.wide_y0, t);
-        fused_chunk_rows(P, P.n_chunks - P.nb_bot - 1, t, P.wide_y1);
-        const int rows = P.wide_y1 - P.wide_y0;
-        const long per_seg = (long)n_wide * g->desc.channels;
-        // what the border kernel has to march beside the wide tiles (ccp_wide_plan.hpp: the plan leaves it CUs)
-        WideBorder border;
-        for (int e = 0; e < edge_chunks; ++e) {
-            int ra, rb;
-            fused_chunk_rows(P, e < P.nb_top ? e : P.n_chunks - edge_chunks + e, ra, rb);
-            border.steps += (long)(rb - ra + 4 * T) * (P.n_strips - edge_strips);
-            border.longest = std::max(border.longest, rb - ra + 4 * T);
-        }
-        if (edge_strips > 0) {
-            border.steps += (long)P.n_chunks * edge_strips * P.side_subs * (P.side_rows + 4 * T);
-            border.longest = std::max(border.longest, P.side_rows + 4 * T);
-        }
-        border.steps *= g->desc.channels;
-        const int slots = kWideWaves * g->cus;
-        const WidePlan plan = g->wide_segments == 0 ? wide_plan_height(rows, P.rows_per_chunk)
-                              : g->wide_segments > 0 ? wide_plan_count(rows, g->wide_segments)
-                                                     : wide_plan(P.wide_y0, P.wide_y1, per_seg, slots, T, border);
-        P.wide_h = plan.h;
-        P.wide_nseg = plan.n_seg;
-        // (the A/B form pads every segment's strips to whole blocks: exactly the blocks of the per-chunk grid it stands for)
-        P.wide_stride = g->wide_segments == 0 ? (n_wide + kWideWaves - 1) / kWideWaves * kWideWaves : n_wide;
-        P.wide_tiles = P.wide_stride * plan.n_seg * g->desc.channels;
-    }
-    const dim3 wgrid((unsigned)((P.wide_tiles + kWideWaves - 1) / kWideWaves), 1, 1);
     const dim3 pgrid = wide ? wgrid : grid;                   // the ordinary launch
     // diagnostics: per-wave time stamps of this pass (ordinary launch first, border launch behind it)
     const size_t trace_plain = (size_t)pgrid.x * pgrid.y * pgrid.z * waves * 4, trace_border = (size_t)bgrid.x * bgrid.z * waves * 4;
@@ -531,8 +448,8 @@ int launch_fused_t(ccp_grid *g, const double *xin, double *xout, int st_lo, int 
         if (l1 == 2) hipLaunchKernelGGL((k_fused_sweep<TC, 2, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P);
         else if (l1 == 1) hipLaunchKernelGGL((k_fused_sweep<T, 1, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P);
         else if (edge) hipLaunchKernelGGL((k_fused_sweep<T, 0, kFusedUnroll, true>), grid, dim3(kBlock), 0, g->stream, P);
-        else if (wide && !store_red) hipLaunchKernelGGL((k_fused_sweep_wide<kWideT, false>), wgrid, dim3(kBlock), 0, g->stream, P, wx0, wx1, n_wide);
-        else if (wide) hipLaunchKernelGGL((k_fused_sweep_wide<kWideT, true>), wgrid, dim3(kBlock), 0, g->stream, P, wx0, wx1, n_wide);
+        else if (wide && !store_red) hipLaunchKernelGGL((k_fused_sweep_wide<kWideT, false>), wgrid, dim3(kBlock), 0, g->stream, P, L.wx0, L.wx1, L.n_wide);
+        else if (wide) hipLaunchKernelGGL((k_fused_sweep_wide<kWideT, true>), wgrid, dim3(kBlock), 0, g->stream, P, L.wx0, L.wx1, L.n_wide);
         else if (!store_red) hipLaunchKernelGGL((k_fused_sweep<T, 0, kFusedUnroll, false, false>), grid, dim3(kBlock), 0, g->stream, P);
         else hipLaunchKernelGGL((k_fused_sweep<T, 0, kFusedUnroll>), grid, dim3(kBlock), 0, g->stream, P);
     }
@@ -564,53 +481,30 @@ int launch_fused_t(ccp_grid *g, const double *xin, double *xout, int st_lo, int 
     return CCP_OK;
 }
 
-// `n_passes` passes of depth T as ONE launch (k_fused_multi): xin -> xout -> xin ...; st_lo/st_hi per pass.  Returns
-// CCP_ERR_UNSUPPORTED when the shape does not qualify (the caller then issues the passes one by one).
-// red_skip: the first red_skip passes store only the black halves in their ordinary tiles (launch_fused_t's store_red).
+// `n_passes` passes of one depth as ONE launch (k_fused_multi): xin -> xout -> xin ...  `first` is pass 0, planned with
+// FusedPassKind::multi: its tiling serves the whole group; st_lo / st_hi: the rows each pass stores.
+// red_skip: the first red_skip passes store only the black halves in their ordinary tiles (FusedPass::store_red).
+struct FusedMultiPass {
+    FusedPass first;
+    int n_passes = 0;
+    int st_lo[kMultiMaxPasses], st_hi[kMultiMaxPasses];
+    int red_skip = 0;
+};
+
+// Returns CCP_ERR_UNSUPPORTED when the shape does not qualify (the caller then issues the passes one by one).
 template <int T>
-int launch_fused_multi_t(ccp_grid *g, int n_passes, const double *xin, double *xout, const int *st_lo, const int *st_hi, int red_skip = 0)
+int launch_fused_multi_t(ccp_grid *g, const FusedMultiPass &group)
 {
+    const int n_passes = group.n_passes;
     if (n_passes < 2 || n_passes > kMultiMaxPasses || g->trace_file) return CCP_ERR_UNSUPPORTED;
     if (g->masked && T > kMaskedMaxT) return CCP_ERR_UNSUPPORTED;
+    const FusedPlan &L = group.first.plan;
     FusedMultiParams M{};
     FusedParams &P = M.P;
-    P.xin = xin;
-    P.xout = xout;
-    P.b = g->b.p;
-    P.g = g->geom;
-    P.st_lo = st_lo[0];
-    P.st_hi = st_hi[0];
-    P.rows_per_chunk = (g->tuned && g->tune_rows[T] > 0) ? g->tune_rows[T] : g->rows_per_chunk;
-    const int U = fused_useful_px(T);
-    P.n_strips = (g->geom.W + U - 1) / U;
-    P.partial = g->partial.p;
-    P.partial_border = g->partial.p + g->partial_region;
-    P.active = nullptr;
+    P = fused_params(g, group.first);
     P.xcd_swizzle = 0;
-    P.mask = g->maskp.p;
-    P.trace = nullptr;
     const int HS = 2 * T;
-    if (g->masked) {
-        // every tile an ordinary tile, uniform chunks (launch_fused_masked's geometry)
-        P.first_rows = P.last_rows = P.first_edge = P.last_edge = 0;
-        P.n_chunks = (P.st_hi - P.st_lo + P.rows_per_chunk - 1) / P.rows_per_chunk;
-        P.nb_top = P.nb_bot = P.ns_left = P.ns_right = 0;
-        P.side_rows = P.side_rows_edge = P.rows_per_chunk;
-        P.side_subs = 1;
-        CCP_TRY(masked_tile_census(g, P, T));
-    } else {
-        fused_tile_counts(g, T, P, 0);
-        const int R = P.rows_per_chunk;
-        int sr = std::max(16, (R + 2 * HS) * 2 / 5 - 2 * HS);
-        sr += sr & 1;
-        if (g->side_rows_override > 0) sr = std::max(2, g->side_rows_override);
-        P.side_rows = std::min(sr, R);
-        P.side_subs = (R + P.side_rows - 1) / P.side_rows;
-        P.side_rows_edge = P.side_rows;
-    }
-    P.edge_counter = nullptr;
-    P.edge_flag = nullptr;
-    P.edge_epoch = P.edge_target = 0;
+    if (g->masked) CCP_TRY(masked_tile_census(g, P, T));
     // a tile waits for the tiles two chunks up and down: of any two adjacent chunks at least one must be as tall
     // as the halo (2T rows) — true when the regular and the special chunk heights are, whatever the remainder chunk
     if (P.rows_per_chunk < HS || (P.first_rows > 0 && P.first_rows < HS) || (P.last_rows > 0 && P.last_rows < HS)) return CCP_ERR_UNSUPPORTED;
@@ -621,19 +515,15 @@ int launch_fused_multi_t(ccp_grid *g, int n_passes, const double *xin, double *x
         if (rb - ra < HS && rd - rc < HS) return CCP_ERR_UNSUPPORTED;
     }
     for (int q = 0; q < n_passes; ++q) {
-        if (st_hi[q] <= st_lo[q] || st_lo[q] < st_lo[0] || st_hi[q] > st_hi[0]) return CCP_ERR_UNSUPPORTED;
-        M.st_lo[q] = st_lo[q];
-        M.st_hi[q] = st_hi[q];
+        if (group.st_hi[q] <= group.st_lo[q] || group.st_lo[q] < group.st_lo[0] || group.st_hi[q] > group.st_hi[0]) return CCP_ERR_UNSUPPORTED;
+        M.st_lo[q] = group.st_lo[q];
+        M.st_hi[q] = group.st_hi[q];
     }
-    const int waves = kBlock / kWave;
-    const int edge_chunks = std::min(P.nb_top + P.nb_bot, P.n_chunks);
-    const int edge_strips = std::min(P.ns_left + P.ns_right, P.n_strips);
-    const long n_border = g->masked ? 0 : (long)edge_chunks * (P.n_strips - edge_strips) + (long)P.n_chunks * edge_strips * P.side_subs;
     M.n_passes = n_passes;
-    M.red_skip = red_skip;
-    M.gx = (P.n_strips + waves - 1) / waves;
-    M.gy = P.n_chunks;
-    M.bgx = (int)((n_border + waves - 1) / waves);
+    M.red_skip = group.red_skip;
+    M.gx = (int)L.grid_x;
+    M.gy = (int)L.grid_y;
+    M.bgx = (int)L.bgrid_x;
     M.channels = g->desc.channels;
     const size_t cells = (size_t)n_passes * M.channels * P.n_chunks * P.n_strips;
     if (g->multi_words.n < cells + 2) CCP_TRY(g->multi_words.alloc(cells + 2));
@@ -654,33 +544,62 @@ int launch_fused_multi_t(ccp_grid *g, int n_passes, const double *xin, double *x
     return CCP_OK;
 }
 
-template <int TMAX>
-struct FusedMultiDepth {
-    static int launch(int T, ccp_grid *g, int n, const double *xin, double *xout, const int *lo, const int *hi, int red_skip = 0)
-    {
-        if (T == TMAX) return launch_fused_multi_t<TMAX>(g, n, xin, xout, lo, hi, red_skip);
-        return FusedMultiDepth<TMAX - 1>::launch(T, g, n, xin, xout, lo, hi, red_skip);
-    }
-};
-template <>
-struct FusedMultiDepth<0> {
-    static int launch(int, ccp_grid *, int, const double *, double *, const int *, const int *, int = 0) { return CCP_ERR_UNSUPPORTED; }
-};
-
-// run-time depth -> the instantiation of that depth
+// run-time depth (the plan's) -> the instantiation of that depth
 template <int TMAX>
 struct FusedDepth {
-    static int launch(int T, ccp_grid *g, const double *xin, double *xout, int st_lo, int st_hi, const int *active,
-                      int l1, long *l1_blocks, int rows_override = 0, int edge_rows = 0, bool *signalled = nullptr, bool store_red = true)
+    static int launch(ccp_grid *g, const FusedPass &pass)
     {
-        if (T == TMAX) return launch_fused_t<TMAX>(g, xin, xout, st_lo, st_hi, active, l1, l1_blocks, rows_override, edge_rows, signalled, store_red);
-        return FusedDepth<TMAX - 1>::launch(T, g, xin, xout, st_lo, st_hi, active, l1, l1_blocks, rows_override, edge_rows, signalled, store_red);
+        if (pass.plan.T == TMAX) return launch_fused_t<TMAX>(g, pass);
+        return FusedDepth<TMAX - 1>::launch(g, pass);
+    }
+    static int launch(ccp_grid *g, const FusedMultiPass &group)
+    {
+        if (group.first.plan.T == TMAX) return launch_fused_multi_t<TMAX>(g, group);
+        return FusedDepth<TMAX - 1>::launch(g, group);
     }
 };
 template <>
 struct FusedDepth<0> {
-    static int launch(int, ccp_grid *, const double *, double *, int, int, const int *, int, long *, int = 0, int = 0, bool * = nullptr, bool = true) { return CCP_ERR_BAD_ARG; }
+    static int launch(ccp_grid *, const FusedPass &) { return CCP_ERR_BAD_ARG; }
+    static int launch(ccp_grid *, const FusedMultiPass &) { return CCP_ERR_UNSUPPORTED; }
 };
+
+// A planned pass / group of passes of any depth: what ccp_grid_tune and the loops below launch through.
+int launch_pass(ccp_grid *g, const FusedPass &pass) { return FusedDepth<kFusedMaxT>::launch(g, pass); }
+int launch_pass(ccp_grid *g, const FusedMultiPass &group) { return FusedDepth<kFusedMaxT>::launch(g, group); }
+
+// An unchecked pass over every local row, whatever the ghosts hold (ccp_grid_tune times these)
+FusedPass whole_block_pass(const ccp_grid *g, int T, const double *xin, double *xout)
+{
+    FusedPassKind kind;
+    kind.T = T;
+    kind.st_hi = g->geom.local_rows;
+    FusedPass pass = plan_pass(g, kind);
+    pass.xin = xin;
+    pass.xout = xout;
+    return pass;
+}
+
+// The group of n passes of depth T whose pass q stores rows [lo[q], hi[q]), from xin to xout and back
+FusedMultiPass plan_multi_pass(const ccp_grid *g, int T, int n, const int *lo, const int *hi, const double *xin, double *xout, int red_skip = 0)
+{
+    FusedMultiPass group;
+    FusedPassKind kind;
+    kind.T = T;
+    kind.st_lo = lo[0];
+    kind.st_hi = hi[0];
+    kind.multi = true;
+    group.first = plan_pass(g, kind);
+    group.first.xin = xin;
+    group.first.xout = xout;
+    group.n_passes = n;
+    for (int q = 0; q < kMultiMaxPasses; ++q) {
+        group.st_lo[q] = q < n ? lo[q] : 0;
+        group.st_hi[q] = q < n ? hi[q] : 0;
+    }
+    group.red_skip = red_skip;
+    return group;
+}
 
 __global__ void k_publish_flag(unsigned long long *flag, unsigned long long epoch)
 {
@@ -735,19 +654,28 @@ int edge_wait_on_stream(ccp_grid *g, hipStream_t s)
 
 // T fused iterations xin -> xout, with the ghost bookkeeping of 2T half-sweeps.
 // edge_rows > 0 (row blocks with neighbours): the owned rows next to each neighbour are finished first
-// inside the launch and published through the edge flag (see launch_fused_t); without an in-launch
+// inside the launch and published through the edge flag (see plan_pass); without an in-launch
 // signal the flag is published after the pass.  Same tiles, same arithmetic.
 int launch_fused(ccp_grid *g, int T, const double *xin, double *xout, const int *active, int l1 = 0,
                  long *l1_blocks = nullptr, int edge_rows = 0, bool store_red = true)
 {
-    const bool shrinking = g->shrink_top || g->shrink_bottom;
-    const int s = g->half_sweeps_since_refresh;
-    if (shrinking && s + 2 * T > g->desc.ghost) return CCP_ERR_STATE;   // ghosts exhausted: refresh first
-    const int st_lo = g->shrink_top ? std::min(s + 2 * T, g->ghost_top) : 0;
-    const int st_hi = g->geom.local_rows - (g->shrink_bottom ? std::min(s + 2 * T, g->ghost_bottom) : 0);
-    if (st_hi > st_lo)
-        CCP_TRY(FusedDepth<kFusedMaxT>::launch(T, g, xin, xout, st_lo, st_hi, active, l1, l1_blocks, 0, edge_rows, nullptr, store_red));
-    if (shrinking) g->half_sweeps_since_refresh += 2 * T;
+    if (T < 1 || T > kFusedMaxT) return CCP_ERR_BAD_ARG;
+    const FusedPlanInput in = plan_input(g, T);
+    const int s = g->half_sweeps_since_refresh + 2 * T;
+    if (fused_ghosts_exhausted(in, s)) return CCP_ERR_STATE;            // refresh first
+    FusedPassKind kind;
+    kind.T = T;
+    kind.l1 = l1;
+    fused_stored_rows(in, s, kind.st_lo, kind.st_hi);
+    if (kind.st_hi > kind.st_lo) {
+        FusedPass pass = plan_pass(g, kind, active, edge_rows);
+        pass.xin = xin;
+        pass.xout = xout;
+        pass.l1_blocks = l1_blocks;
+        pass.store_red = store_red || l1 != 0 || edge_rows > 0;
+        CCP_TRY(launch_pass(g, pass));
+    }
+    if (in.stale_top || in.stale_bottom) g->half_sweeps_since_refresh = s;
     return CCP_OK;
 }
 
@@ -770,48 +698,17 @@ int run_unchecked(ccp_grid *g, int iterations, const int *active = nullptr, bool
         CCP_TRY(g->x_alt.alloc(elems));
         CCP_HIP(hipMemsetAsync(g->x_alt.p, 0, elems * sizeof(double), g->stream));
     }
-    // Split `iterations` into an EVEN number of launches of depth <= tmax with the least total
-    // cost: measured per-depth launch times when the handle was tuned, otherwise "fewer, deeper
-    // launches are cheaper".  f[i][p]: best cost for i iterations with launch-count parity p.
-    const int tmax = g->fuse_tmax;
-    // depth-1 passes only (a handle tuned for one iteration per exchange, CCP_GS_TMAX=1) cannot cover an odd
-    // count in an even number of launches: the odd iteration goes through the in-place kernels
-    if (tmax == 1 && (iterations & 1)) {
-        if (l1_last) return CCP_ERR_STATE;
-        CCP_TRY(run_unchecked(g, iterations - 1, active, false, nullptr, 0));
-        CCP_TRY(one_iteration(g, false, active, nullptr));
-        if (edge_rows > 0) CCP_TRY(edge_epoch_publish_after_pass(g));
-        return CCP_OK;
-    }
-    auto cost = [&](int T) -> double { return g->tuned && g->tune_ms[T] > 0 ? (double)g->tune_ms[T] : 1.0 + 0.01 * T; };
-    const double inf = 1e300;
-    std::vector<double> f((size_t)(iterations + 1) * 2, inf);
-    std::vector<int> step((size_t)(iterations + 1) * 2, 0);
-    f[0] = 0.0;
-    for (int i = 1; i <= iterations; ++i)
-        for (int p = 0; p < 2; ++p)
-            for (int T = 1; T <= tmax && T <= i; ++T) {
-                const double c = f[(size_t)(i - T) * 2 + (p ^ 1)] + cost(T);
-                if (c < f[(size_t)i * 2 + p]) {
-                    f[(size_t)i * 2 + p] = c;
-                    step[(size_t)i * 2 + p] = T;
-                }
-            }
-    const bool free_parity = g->allow_swap && !g->ghost_top && !g->ghost_bottom && edge_rows == 0 &&
-                             f[(size_t)iterations * 2 + 1] < f[(size_t)iterations * 2];
-    std::vector<int> plan;
-    for (int i = iterations, p = free_parity ? 1 : 0; i > 0;) {
-        const int T = step[(size_t)i * 2 + p];
-        if (T == 0) return CCP_ERR_STATE;
-        plan.push_back(T);
-        i -= T;
-        p ^= 1;
-    }
-    std::sort(plan.begin(), plan.end(), std::greater<int>());
-    // Pass k may leave out its red half (launch_fused_t's store_red, the argument at fused_wave) only when the pass
-    // after it in THIS plan is unchecked: the last pass stores both halves (whatever reads x after the call sees a
-    // whole buffer), and so does the pass before a checked one (l1_last: it reads the red of its input).
-    auto stores_red = [&](size_t k) { return g->red_store_all || k + 1 >= plan.size() || (l1_last && k + 2 == plan.size()); };
+    // The passes (fused_pass_split): measured per-depth launch times when the handle was tuned, otherwise "fewer, deeper
+    // launches are cheaper"; an odd number of them only where x and x_alt may swap roles.
+    double cost[kFusedMaxT + 1] = {0};
+    for (int T = 1; T <= kFusedMaxT; ++T) cost[T] = g->tuned && g->tune_ms[T] > 0 ? (double)g->tune_ms[T] : fused_default_cost(T);
+    const FusedPassSplit split = fused_pass_split(iterations, g->fuse_tmax, cost, g->allow_swap && !g->ghost_top && !g->ghost_bottom && edge_rows == 0);
+    if (split.in_place && l1_last) return CCP_ERR_STATE;
+    if (split.depths.empty()) return CCP_ERR_STATE;
+    const std::vector<int> &plan = split.depths;
+    // the hand-off belongs to the last iteration: a pass hands over only when no in-place iteration follows it
+    const int pass_edge_rows = split.in_place ? 0 : edge_rows;
+    auto stores_red = [&](size_t k) { return fused_stores_red(k, plan.size(), l1_last, g->red_store_all); };
     double *cur = g->x.p, *alt = g->x_alt.p;
     for (size_t k = 0; k < plan.size();) {
         // consecutive passes of one depth as ONE launch (k_fused_multi), where that is switched on and the shape
@@ -819,22 +716,19 @@ int run_unchecked(ccp_grid *g, int iterations, const int *active = nullptr, bool
         if (g->multi && active == nullptr) {
             size_t j = k;
             while (j < plan.size() && plan[j] == plan[k] && (int)(j - k) < kMultiMaxPasses &&
-                   !(j + 1 == plan.size() && (l1_last || edge_rows > 0)))
+                   !(j + 1 == plan.size() && (l1_last || pass_edge_rows > 0)))
                 ++j;
             const int n = (int)(j - k), T = plan[k];
-            const bool shrinking = g->shrink_top || g->shrink_bottom;
-            if (n >= 2 && !(shrinking && g->half_sweeps_since_refresh + 2 * T * n > g->desc.ghost)) {
+            const FusedPlanInput in = plan_input(g, T);
+            const int since = g->half_sweeps_since_refresh;
+            if (n >= 2 && !fused_ghosts_exhausted(in, since + 2 * T * n)) {
                 int lo[kMultiMaxPasses], hi[kMultiMaxPasses];
-                for (int q = 0; q < n; ++q) {
-                    const int s = g->half_sweeps_since_refresh + 2 * T * (q + 1);
-                    lo[q] = g->shrink_top ? std::min(s, g->ghost_top) : 0;
-                    hi[q] = g->geom.local_rows - (g->shrink_bottom ? std::min(s, g->ghost_bottom) : 0);
-                }
+                for (int q = 0; q < n; ++q) fused_stored_rows(in, since + 2 * T * (q + 1), lo[q], hi[q]);
                 int red_skip = 0;                                 // the leading passes of the group that may skip red
                 while (red_skip < n && !stores_red(k + red_skip)) ++red_skip;
-                const int st = FusedMultiDepth<kFusedMaxT>::launch(T, g, n, cur, alt, lo, hi, red_skip);
+                const int st = launch_pass(g, plan_multi_pass(g, T, n, lo, hi, cur, alt, red_skip));
                 if (st == CCP_OK) {
-                    if (shrinking) g->half_sweeps_since_refresh += 2 * T * n;
+                    if (in.stale_top || in.stale_bottom) g->half_sweeps_since_refresh += 2 * T * n;
                     if (n & 1) std::swap(cur, alt);
                     k = j;
                     continue;
@@ -843,16 +737,17 @@ int run_unchecked(ccp_grid *g, int iterations, const int *active = nullptr, bool
             }
         }
         const bool last = k + 1 == plan.size();
-        CCP_TRY(launch_fused(g, plan[k], cur, alt, active, (l1_last && last) ? 1 : 0, l1_blocks, last ? edge_rows : 0, stores_red(k)));
+        CCP_TRY(launch_fused(g, plan[k], cur, alt, active, (l1_last && last) ? 1 : 0, l1_blocks, last ? pass_edge_rows : 0, stores_red(k)));
         std::swap(cur, alt);
         ++k;
     }
     if (cur != g->x.p) {
         // an odd number of passes (free_parity): the result is in the partner buffer, which becomes x
-        if (!free_parity) return CCP_ERR_STATE;
+        if (!split.free_parity) return CCP_ERR_STATE;
         std::swap(g->x.p, g->x_alt.p);
         std::swap(g->x.n, g->x_alt.n);
     }
+    for (int k = 0; k < split.in_place; ++k) CCP_TRY(one_iteration(g, false, active, nullptr));
     if (edge_rows > 0) CCP_TRY(edge_epoch_publish_after_pass(g));
     return CCP_OK;
 }
@@ -1354,7 +1249,6 @@ try {
     float tab_ms[kFusedMaxT + 1] = {0};
     int tab_rows[kFusedMaxT + 1] = {0};
     const int rows = g->geom.local_rows;
-    const int fixed_candidates[] = {32, 48, 64, 80, 96, 112, 128, 160, 192, 256};
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device);
     float best = 1e30f;
@@ -1364,31 +1258,12 @@ try {
     CCP_HIP(hipEventCreate(&e1));
     int status = CCP_OK;
     for (int T = 1; T <= max_t && status == CCP_OK; ++T) {
-        // plus the chunk heights that fill the chip's wave slots in exactly 1..4 rounds: a short
-        // row block has few tiles, and one tile past a whole round costs a round
-        std::vector<int> chunk_candidates(std::begin(fixed_candidates), std::end(fixed_candidates));
-        {
-            const int U = fused_useful_px(T);
-            const long blocks_x = ((g->geom.W + U - 1) / U + kBlock / kWave - 1) / (kBlock / kWave);
-            const long slots = (long)cus * (g->masked ? masked_waves_per_simd(T) : fused_waves_per_simd(T));       // resident workgroups
-            // chunk rows at an image edge are short ones of their own (fused_tile_counts)
-            const int n_short = (g->geom.y0 - 2 * T <= 0) + (g->geom.y0 + rows + 2 * T >= g->geom.H - 1);
-            const int short_rows = n_short * (2 * T + 16);
-            for (int rounds = 1; rounds <= 4; ++rounds) {
-                const long chunks = rounds * slots / (blocks_x * g->desc.channels) - n_short;
-                if (chunks < 1 || rows <= short_rows) continue;
-                int R = (int)((rows - short_rows + chunks - 1) / chunks);
-                R += R & 1;
-                if (R >= 16 && R <= 1024 && std::find(chunk_candidates.begin(), chunk_candidates.end(), R) == chunk_candidates.end())
-                    chunk_candidates.push_back(R);
-            }
-        }
+        const long slots = (long)cus * (g->masked ? masked_waves_per_simd(T) : fused_waves_per_simd(T));       // resident workgroups
+        const std::vector<int> chunk_candidates = fused_tune_chunk_rows(g->geom, g->desc.channels, T, slots);
         for (int R : chunk_candidates) {
             if (R > rows && R != chunk_candidates[0]) continue;
             g->rows_per_chunk = R;
-            auto once = [&]() -> int {
-                return FusedDepth<kFusedMaxT>::launch(T, g, g->x.p, g->x_alt.p, 0, rows, nullptr, 0, nullptr);
-            };
+            auto once = [&]() -> int { return launch_pass(g, whole_block_pass(g, T, g->x.p, g->x_alt.p)); };
             status = once();                                   // warm (code, TLB)
             if (status != CCP_OK) break;
             (void)hipEventRecord(e0, g->stream);
@@ -1448,9 +1323,9 @@ try {
             int st = CCP_OK;
             auto singles = [&]() {
                 for (int q = 0; q < 4 && st == CCP_OK; ++q)
-                    st = FusedDepth<kFusedMaxT>::launch(best_t, g, (q & 1) ? g->x_alt.p : g->x.p, (q & 1) ? g->x.p : g->x_alt.p, 0, rows, nullptr, 0, nullptr);
+                    st = launch_pass(g, whole_block_pass(g, best_t, (q & 1) ? g->x_alt.p : g->x.p, (q & 1) ? g->x.p : g->x_alt.p));
             };
-            auto multi = [&]() { if (st == CCP_OK) st = FusedMultiDepth<kFusedMaxT>::launch(best_t, g, 4, g->x.p, g->x_alt.p, lo, hi); };
+            auto multi = [&]() { if (st == CCP_OK) st = launch_pass(g, plan_multi_pass(g, best_t, 4, lo, hi, g->x.p, g->x_alt.p)); };
             singles();                                          // warm both
             multi();
             (void)hipEventRecord(t0, g->stream);

@@ -31,6 +31,7 @@
 // border pixels as classify()/gs_update() do.
 #pragma once
 
+#include "ccp_fused_plan.hpp"      // the chunk and strip arithmetic, shared with the host's pass planner
 #include "ccp_grid_kernels.hpp"
 
 namespace ccp {
@@ -52,10 +53,7 @@ constexpr int kFusedUnroll = CCP_FUSED_UNROLL;          // march steps unrolled 
 // pair and keep 1).  Measured (profiles/r03_window_forms.jsonl):
 // +2-3 % at 16384^2 and 4096^2 x 3 over one trip.
 constexpr int kFusedLand = CCP_FUSED_LAND;
-constexpr int kStripLanes = kWave;       // half-columns per strip
-
-__host__ __device__ constexpr int fused_halo_px(int T) { return 2 * T; }               // per side
-__host__ __device__ constexpr int fused_useful_px(int T) { return 2 * kStripLanes - 4 * T; }
+static_assert(kStripLanes == kWave && kTileWaves == kBlock / kWave, "ccp_fused_plan.hpp plans for one half-column per lane, one wave per SIMD");
 
 // lane i <- lane i-1 (lane 0 gets 0) / lane i <- lane i+1 (lane 63 gets 0): the strip-edge lanes
 // have no neighbour inside the wave; their pixels are halo (never stored) or image-edge pixels
@@ -91,7 +89,7 @@ struct FusedParams {
     const int *__restrict__ active; // nullable: per-channel "still iterating" flags (device)
     // Tiles (chunk c, strip s) that can touch a pixel with a missing neighbour — image edges, the
     // stale edge of a ghost zone — are "border tiles": the first nb_top / last nb_bot chunks and the
-    // first ns_left / last ns_right strips (host: fused_tile_counts).  k_fused_sweep skips them,
+    // first ns_left / last ns_right strips (host: fused_tile_counts, ccp_fused_plan.hpp).  k_fused_sweep skips them,
     // k_fused_border runs exactly them, concurrently on a second stream.
     int n_chunks;
     int nb_top, nb_bot, ns_left, ns_right;
@@ -127,18 +125,8 @@ struct FusedParams {
     unsigned long long edge_target, edge_epoch;
 };
 
-// blockIdx.y -> chunk with the edge chunks first (workgroups are dispatched in block-index order)
-__host__ __device__ __forceinline__ int fused_chunk_of(const FusedParams &P, int y)
-{
-    const int n_e = P.first_edge + P.last_edge;
-    if (y < n_e) return (P.first_edge && y == 0) ? 0 : P.n_chunks - 1;
-    return y - n_e + P.first_edge;
-}
-
-__host__ __device__ __forceinline__ bool fused_is_edge_chunk(const FusedParams &P, int chunk)
-{
-    return (P.first_edge && chunk == 0) || (P.last_edge && chunk == P.n_chunks - 1);
-}
+static_assert(sizeof(FusedParams) == 232, "FusedParams is the kernels' argument: its fields, order and size stay");
+// fused_chunk_of, fused_is_edge_chunk, fused_chunk_rows: ccp_fused_plan.hpp
 
 // One wave reports a finished edge tile.  Producer side of the hand-off (MI355X_MICROARCH.md, correctness
 // boundaries): the wave's stores are drained and written back at agent scope before it counts itself.
@@ -188,23 +176,6 @@ __device__ __forceinline__ void fused_trace_end(const FusedParams &P, unsigned l
                | ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) << 32);   // HW_REG_XCC_ID[3:0]
         r[3] = (unsigned long long)(unsigned)chunk | ((unsigned long long)(unsigned)sx << 16) | ((unsigned long long)ch << 32) |
                ((unsigned long long)kernel << 40);
-    }
-}
-
-// rows [ra, rb) of chunk c
-__host__ __device__ __forceinline__ void fused_chunk_rows(const FusedParams &P, int c, int &ra, int &rb)
-{
-    if (P.first_rows > 0 && c == 0) {
-        ra = P.st_lo;
-        rb = P.st_lo + P.first_rows;
-    } else if (P.last_rows > 0 && c == P.n_chunks - 1) {
-        ra = P.st_hi - P.last_rows;
-        rb = P.st_hi;
-    } else {
-        const int k = c - (P.first_rows > 0 ? 1 : 0);
-        const int end = P.st_hi - P.last_rows;
-        ra = P.st_lo + P.first_rows + k * P.rows_per_chunk;
-        rb = ra + P.rows_per_chunk < end ? ra + P.rows_per_chunk : end;
     }
 }
 

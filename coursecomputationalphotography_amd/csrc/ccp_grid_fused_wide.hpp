@@ -24,9 +24,7 @@
 
 namespace ccp {
 
-constexpr int kWideT = 8;                     // the only depth built on wide strips
-constexpr int kWideWaves = kBlock / kWave;    // waves (wide strips) per workgroup: one per SIMD
-__host__ __device__ constexpr int wide_useful_px(int T) { return 4 * kStripLanes - 4 * T; }
+// kWideT, kWideWaves and wide_useful_px: ccp_fused_plan.hpp
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));   // the lane's pixels A and B of one colour

@@ -4,17 +4,9 @@
 #pragma once
 
 #include "ccp_common.hpp"
+#include "ccp_grid_geom.hpp"       // Geom
 
 namespace ccp {
-
-struct Geom {
-    int W, H;            // whole image
-    int y0;              // image row of local row 0
-    int local_rows;      // ghost_top + owned + ghost_bottom
-    int own_lo, own_hi;  // owned local rows [own_lo, own_hi)
-    long pitch;          // doubles per colour half-row
-    long ch_stride;      // doubles per channel = local_rows*2*pitch
-};
 
 __device__ __forceinline__ long row_off(const Geom &g, int l, int c)
 {

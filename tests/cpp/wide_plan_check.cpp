@@ -40,7 +40,7 @@ static void check_partition(const WidePlan &p, int y0, int y1, bool even_h, cons
     CHECK(at == y1, "%s ends at %d, not %d", what, at, y1);
 }
 
-// the rows of chunk c of the narrow tiling (ccp_grid_fused.hpp, fused_chunk_rows), restated
+// the rows of chunk c of the narrow tiling (ccp_fused_plan.hpp, fused_chunk_rows), restated
 static void chunk_rows(int st_lo, int st_hi, int first_rows, int last_rows, int R, int n_chunks, int c, int &ra, int &rb)
 {
     if (first_rows > 0 && c == 0) {
