@@ -24,6 +24,7 @@ GRID_DIRICHLET_MASK = 1
 GRID_WEIGHTED = 2
 MG_HIERARCHY_GALERKIN, MG_HIERARCHY_RESCALED = 0, 1
 MG_HIERARCHIES = {"galerkin": MG_HIERARCHY_GALERKIN, "rescaled": MG_HIERARCHY_RESCALED}
+MG_PRECISIONS = {"f64": 0, "f32": 1}
 ORDER_LEXICOGRAPHIC = 0
 ORDER_MULTICOLOUR = 1
 CLONE_IMPORT = 0
@@ -39,7 +40,7 @@ ABI_SYMBOLS = (
     "ccp_grid_get_b_host", "ccp_grid_set_mask_host", "ccp_grid_fill_x", "ccp_grid_b_from_x", "ccp_grid_randomize_x",
     "ccp_grid_sweep", "ccp_grid_sweep_edges_first", "ccp_grid_stream_wait_edges", "ccp_grid_tune", "ccp_grid_set_fused", "ccp_grid_set_tiling", "ccp_grid_get_tiling", "ccp_grid_sweep_l1", "ccp_grid_halo_refreshed", "ccp_grid_gauss_seidel", "ccp_grid_gauss_seidel_lexicographic", "ccp_debug_lex_tickets", "ccp_grid_conjugate_gradient",
     "ccp_grid_mg_conjugate_gradient", "ccp_grid_mg_apply", "ccp_grid_mg_level",
-    "ccp_grid_mg_set_hierarchy", "ccp_grid_mg_get_hierarchy",
+    "ccp_grid_mg_set_hierarchy", "ccp_grid_mg_get_hierarchy", "ccp_grid_mg_set_precision", "ccp_grid_mg_get_precision",
     "ccp_grid_residual_norm2", "ccp_grid_abs_sum", "ccp_grid_assemble_rhs", "ccp_grid_assemble_from_images", "ccp_grid_store_u8",
     "ccp_grid_set_x_u8", "ccp_grid_assemble_region_rhs", "ccp_grid_assemble_clone", "ccp_grid_store_u8_composite",
     "ccp_grid_last_timing", "ccp_grid_region_begin", "ccp_grid_region_end",
@@ -187,6 +188,8 @@ def load() -> C.CDLL:
     L.ccp_grid_mg_level.argtypes = [vp, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
     L.ccp_grid_mg_set_hierarchy.argtypes = [vp, i32]
     L.ccp_grid_mg_get_hierarchy.argtypes = [vp, C.POINTER(i32)]
+    L.ccp_grid_mg_set_precision.argtypes = [vp, i32]
+    L.ccp_grid_mg_get_precision.argtypes = [vp, C.POINTER(i32)]
     L.ccp_csr_apply_to_vector.argtypes = [vp, vp, vp]
     L.ccp_csr_residual_norm2.argtypes = [vp, vp, vp, C.POINTER(dbl), C.POINTER(dbl)]
     L.ccp_grid_create.argtypes = [C.POINTER(GridDesc), C.POINTER(vp)]
@@ -692,6 +695,22 @@ class Grid:
         kind = C.c_int32()
         check(self.L.ccp_grid_mg_get_hierarchy(self.h, C.byref(kind)), "ccp_grid_mg_get_hierarchy")
         return next(name for name, value in MG_HIERARCHIES.items() if value == kind.value)
+
+    def mg_set_precision(self, precision):
+        """The precision of the multigrid preconditioner: "f64" (the default) or "f32" (the V-cycle in float, the outer
+        PCG loop and its stop test in fp64: same answer, for weighted handles best with the "rescaled" hierarchy), or the
+        integers of MG_PRECISIONS.  A change drops the cached hierarchy."""
+        if isinstance(precision, str):
+            if precision not in MG_PRECISIONS:
+                raise ValueError(f"precision must be one of {sorted(MG_PRECISIONS)}, not {precision!r}")
+            precision = MG_PRECISIONS[precision]
+        check(self.L.ccp_grid_mg_set_precision(self.h, int(precision)), "ccp_grid_mg_set_precision")
+
+    def mg_precision(self):
+        """The handle's preconditioner precision: "f64" or "f32"."""
+        value = C.c_int32()
+        check(self.L.ccp_grid_mg_get_precision(self.h, C.byref(value)), "ccp_grid_mg_get_precision")
+        return next(name for name, v in MG_PRECISIONS.items() if v == value.value)
 
     def mg_levels(self):
         """The multigrid hierarchy: one (diag, w_east, w_south) triple of H_k x W_k arrays per level, level 0 first."""

@@ -1,6 +1,7 @@
 // ccp_grid_mg.hip — multigrid-preconditioned conjugate gradient on the grid handles (include/ccp_gs.h:
 // ccp_grid_mg_*).  Kernels and the algorithm: ccp_grid_mg.hpp.
 #include "ccp_grid_mg.hpp"
+#include "ccp_grid_mgs.hpp"
 #include "ccp_comm.hpp"
 
 #include <algorithm>
@@ -34,7 +35,18 @@ struct MgHierarchy {
     int kind0 = kMgSolve;
     bool weighted = false;           // level 0 is a weighted handle's stored operator; every level carries lambda (arr 6)
     double cs = 2.0;                 // the coarse correction's scale (`cs` of k_mg_tile, k_mg_tail): 1.0 on a rescaled weighted hierarchy
-    double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda
+    // CCP_MG_PRECISION_F32 (ccp_grid_mgs.hpp): the narrowed coefficients and the float vectors of the V-cycle, made at the
+    // first V-cycle (narrow_levels).  fstore: per coarse level d, we, ws, b, z, t, each `size` floats; w32: a weighted
+    // handle's level-0 d, we, ws; t0f: level 0's pre-smoothed z (the fp64 t0 is not allocated then).
+    int precision = CCP_MG_PRECISION_F64;
+    int narrowed = 0;                // 0: not yet, 1: ready, -1: refused (a coefficient does not narrow to a usable float)
+    std::vector<MgsLevel> flv;
+    std::vector<long> fbase;
+    DevBuf<float> fstore, w32, t0f;
+    DevBuf<unsigned> fbad;
+    float *farr(int k, int which) { return fstore.p + fbase[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t
+    int lam_slot = 6;                // F32: 3 (the fp64 store then holds d, we, ws and lambda only)
+    double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda (lam_slot)
     ~MgHierarchy()
     {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -68,10 +80,16 @@ int build(const GridMgView &v, MgHierarchy **out)
     std::unique_ptr<MgHierarchy> own(h);
     h->kind0 = v.weighted ? kMgCoarse : v.masked ? kMgMasked : kMgSolve;
     h->weighted = v.weighted;
+    h->precision = v.precision;
     // (ccp_grid_mg_set_hierarchy drops the cached hierarchy when the kind changes: a cached one is of the handle's kind)
     const bool rescaled = v.weighted && v.hierarchy_kind == CCP_MG_HIERARCHY_RESCALED;
     h->cs = rescaled ? 1.0 : 2.0;
-    const int per_level = v.weighted ? 7 : 6;
+    // per coarse level d, we, ws, the V-cycle's b, z, t, and a weighted handle's lambda; the fp32 V-cycle keeps its vectors
+    // in float (narrow_levels), so its fp64 store holds the coefficients alone: what ccp_grid_mg_level returns and the
+    // narrowing reads
+    const bool f32 = v.precision == CCP_MG_PRECISION_F32;
+    h->lam_slot = f32 ? 3 : 6;
+    const int per_level = (f32 ? 3 : 6) + (v.weighted ? 1 : 0);
     MgLevel l0{};
     l0.W = v.geom.W;
     l0.H = v.geom.H;
@@ -107,8 +125,10 @@ int build(const GridMgView &v, MgHierarchy **out)
             break;
         }
     if (h->levels - h->tail > kMgTailLevels) return CCP_ERR_STATE;     // (cannot happen: sides <= 32 leave <= 6 levels)
-    CCP_TRY(h->t0.alloc((size_t)v.geom.ch_stride));
-    CCP_HIP(hipMemsetAsync(h->t0.p, 0, sizeof(double) * v.geom.ch_stride, v.stream));
+    if (!f32) {                                                     // (the fp32 V-cycle keeps its own, in float: narrow_levels)
+        CCP_TRY(h->t0.alloc((size_t)v.geom.ch_stride));
+        CCP_HIP(hipMemsetAsync(h->t0.p, 0, sizeof(double) * v.geom.ch_stride, v.stream));
+    }
     if (total > 0) {
         CCP_TRY(h->store.alloc((size_t)total));
         CCP_HIP(hipMemsetAsync(h->store.p, 0, sizeof(double) * total, v.stream));
@@ -121,8 +141,8 @@ int build(const GridMgView &v, MgHierarchy **out)
     for (int k = 0; k + 1 < h->levels; ++k) {
         if (v.weighted)
             hipLaunchKernelGGL(k_mg_coarsen_weighted, cells_grid(h->lv[k + 1].W, h->lv[k + 1].H), dim3(kBlock), 0, v.stream, h->lv[k],
-                               k ? static_cast<const double *>(h->arr(k, 6)) : v.wlam, h->lv[k + 1], h->arr(k + 1, 0), h->arr(k + 1, 1),
-                               h->arr(k + 1, 2), h->arr(k + 1, 6), rescaled ? 0.5 : 1.0);
+                               k ? static_cast<const double *>(h->arr(k, h->lam_slot)) : v.wlam, h->lv[k + 1], h->arr(k + 1, 0), h->arr(k + 1, 1),
+                               h->arr(k + 1, 2), h->arr(k + 1, h->lam_slot), rescaled ? 0.5 : 1.0);
         else
             coarsen(level_kind(*h, k), v.stream, h->lv[k], h->lv[k + 1], 0, h->lv[k + 1].H, h->arr(k + 1, 0), h->arr(k + 1, 1), h->arr(k + 1, 2));
         CCP_HIP(hipGetLastError());
@@ -134,7 +154,7 @@ int build(const GridMgView &v, MgHierarchy **out)
 
 int hierarchy(const GridMgView &v, MgHierarchy **out)
 {
-    if (*v.cache && ((*v.cache)->rowblocked || (*v.cache)->weighted != v.weighted)) {            // built for the row-block calls: this call needs its own
+    if (*v.cache && ((*v.cache)->rowblocked || (*v.cache)->weighted != v.weighted || (*v.cache)->precision != v.precision)) {   // built for the row-block calls: this call needs its own
         mg_release(*v.cache);
         *v.cache = nullptr;
     }
@@ -236,9 +256,134 @@ int vcycle_1x1(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int 
     return CCP_OK;
 }
 
+// ---- CCP_MG_PRECISION_F32 (ccp_grid_mgs.hpp) -------------------------------------------------------------------------
+// The float copies of every level's coefficients and the float vectors, once per hierarchy: CCP_ERR_UNSUPPORTED (now
+// and at every later V-cycle of this hierarchy) if a coefficient narrows to inf or a non-zero one to 0.  One read-back.
+int narrow_levels(const GridMgView &v, MgHierarchy &h)
+{
+    if (h.narrowed) return h.narrowed > 0 ? CCP_OK : CCP_ERR_UNSUPPORTED;
+    hipStream_t s = v.stream;
+    const long n0 = v.geom.ch_stride;
+    long total = 0;
+    h.fbase.assign((size_t)h.levels, 0);
+    for (int k = 1; k < h.levels; ++k) {
+        h.fbase[k] = total;
+        total += 6 * h.size[k];
+    }
+    CCP_TRY(h.fbad.alloc(1));
+    CCP_HIP(hipMemsetAsync(h.fbad.p, 0, sizeof(unsigned), s));
+    CCP_TRY(h.t0f.alloc((size_t)n0));
+    CCP_HIP(hipMemsetAsync(h.t0f.p, 0, sizeof(float) * n0, s));
+    if (total > 0) {
+        CCP_TRY(h.fstore.alloc((size_t)total));
+        CCP_HIP(hipMemsetAsync(h.fstore.p, 0, sizeof(float) * total, s));
+    }
+    auto narrow = [&](const double *src, float *dst, long n) {
+        hipLaunchKernelGGL(k_mgs_narrow, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, src, dst, n, h.fbad.p);
+    };
+    h.flv.assign((size_t)h.levels, MgsLevel{});
+    for (int k = 0; k < h.levels; ++k) {
+        MgsLevel &f = h.flv[k];
+        f.W = h.lv[k].W;
+        f.H = h.lv[k].H;
+        f.pitch = h.lv[k].pitch;
+        f.mask = h.lv[k].mask;
+        f.g0 = h.lv[k].g0;
+        if (k) {
+            narrow(h.arr(k, 0), h.farr(k, 0), 3 * h.size[k]);        // d, we, ws lie one after the other in both stores
+            f.d = h.farr(k, 0);
+            f.we = h.farr(k, 1);
+            f.ws = h.farr(k, 2);
+        } else if (h.weighted) {                                    // the handle's d, we, ws planes, n0 doubles apart
+            CCP_TRY(h.w32.alloc((size_t)(3 * n0)));
+            narrow(h.lv[0].d, h.w32.p, 3 * n0);
+            f.d = h.w32.p;
+            f.we = h.w32.p + n0;
+            f.ws = h.w32.p + 2 * n0;
+        }
+    }
+    CCP_HIP(hipGetLastError());
+    unsigned bad = 0;
+    CCP_HIP(hipMemcpyAsync(&bad, h.fbad.p, sizeof(bad), hipMemcpyDeviceToHost, s));
+    CCP_HIP(hipStreamSynchronize(s));
+    h.narrowed = bad ? -1 : 1;
+    return bad ? CCP_ERR_UNSUPPORTED : CCP_OK;
+}
+
+template <int KIND, bool POST, typename B, typename Z>
+void tile32(hipStream_t s, dim3 grid, const MgsLevel &f, const B *b, const float *t, Z *z, const MgsLevel &c, const float *ec, float cs, int nu,
+            const CgState *st)
+{
+    hipLaunchKernelGGL((k_mgs_tile<KIND, POST, B, Z>), grid, dim3(kBlock), mgs_tile_lds(nu), s, f, b, t, z, c, ec, cs, nu, st);
+}
+
+// a level-0 pass: b is the PCG's fp64 r; Z = double where the pass writes the PCG's z
+template <bool POST, typename Z>
+void tile32_top(int kind, hipStream_t s, dim3 grid, const MgsLevel &f, const double *b, const float *t, Z *z, const MgsLevel &c, const float *ec,
+                float cs, int nu, const CgState *st)
+{
+    if (kind == kMgCoarse) tile32<kMgCoarse, POST>(s, grid, f, b, t, z, c, ec, cs, nu, st);
+    else if (kind == kMgMasked) tile32<kMgMasked, POST>(s, grid, f, b, t, z, c, ec, cs, nu, st);
+    else tile32<kMgSolve, POST>(s, grid, f, b, t, z, c, ec, cs, nu, st);
+}
+
+dim3 tiles32(const MgsLevel &f) { return dim3((unsigned)((f.W + kMgsTileW - 1) / kMgsTileW), (unsigned)((f.H + kMgsTileH - 1) / kMgsTileH)); }
+
+// vcycle in float: z0 := (double) M32^-1 (float) b0, the launch structure of whole_levels / vcycle_1x1
+int vcycle32(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st)
+{
+    const float *none = nullptr;
+    const float cs = (float)h.cs;
+    const MgsLevel &l0 = h.flv[0];
+    if (h.levels == 1) {
+        tile32_top<false>(h.kind0, s, dim3(1), l0, b0, none, z0, l0, none, 2.0f, nu, st);
+        CCP_HIP(hipGetLastError());
+        return CCP_OK;
+    }
+    auto T = [&](int k) -> float * { return k ? h.farr(k, 5) : h.t0f.p; };
+    for (int k = 0; k < h.tail; ++k) {
+        const MgsLevel &f = h.flv[k], &c = h.flv[k + 1];
+        const dim3 rgrid = cells_grid(c.W, c.H);
+        if (k == 0) {
+            tile32_top<false>(h.kind0, s, tiles32(f), f, b0, none, T(0), f, none, 2.0f, nu, st);
+            if (h.kind0 == kMgCoarse) hipLaunchKernelGGL((k_mgs_restrict<kMgCoarse, double>), rgrid, dim3(kBlock), 0, s, f, b0, T(0), c, h.farr(1, 3), st);
+            else if (h.kind0 == kMgMasked) hipLaunchKernelGGL((k_mgs_restrict<kMgMasked, double>), rgrid, dim3(kBlock), 0, s, f, b0, T(0), c, h.farr(1, 3), st);
+            else hipLaunchKernelGGL((k_mgs_restrict<kMgSolve, double>), rgrid, dim3(kBlock), 0, s, f, b0, T(0), c, h.farr(1, 3), st);
+        } else {
+            const float *b = h.farr(k, 3);
+            tile32<kMgCoarse, false>(s, tiles32(f), f, b, none, T(k), f, none, 2.0f, nu, st);
+            hipLaunchKernelGGL((k_mgs_restrict<kMgCoarse, float>), rgrid, dim3(kBlock), 0, s, f, b, T(k), c, h.farr(k + 1, 3), st);
+        }
+    }
+    MgsTail t{};
+    t.levels = h.levels - h.tail;
+    int off = 0;
+    for (int i = 0; i < t.levels; ++i) {
+        const MgsLevel &l = h.flv[h.tail + i];
+        t.W[i] = l.W;
+        t.H[i] = l.H;
+        t.pitch[i] = l.pitch;
+        t.off[i] = off;
+        t.d[i] = l.d;
+        t.we[i] = l.we;
+        t.ws[i] = l.ws;
+        off += l.W * l.H;
+    }
+    hipLaunchKernelGGL(k_mgs_tail, dim3(1), dim3(kBlock), 0, s, t, static_cast<const float *>(h.farr(h.tail, 3)), h.farr(h.tail, 4), cs, nu, st);
+    for (int k = h.tail - 1; k >= 0; --k) {
+        const MgsLevel &f = h.flv[k], &c = h.flv[k + 1];
+        const float *ec = h.farr(k + 1, 4);
+        if (k == 0) tile32_top<true>(h.kind0, s, tiles32(f), f, b0, static_cast<const float *>(T(0)), z0, c, ec, cs, nu, st);
+        else tile32<kMgCoarse, true>(s, tiles32(f), f, static_cast<const float *>(h.farr(k, 3)), static_cast<const float *>(T(k)), h.farr(k, 4), c, ec, cs, nu, st);
+    }
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
 // z0 := M^-1 b0 on level 0 (one channel); every launch is a no-op once st->active is 0 (st may be null)
 int vcycle(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st)
 {
+    if (h.precision == CCP_MG_PRECISION_F32) return vcycle32(h, s, b0, z0, nu, st);
     if (h.levels == 1) return vcycle_1x1(h, s, b0, z0, nu, st);
     return whole_levels(h, s, 0, b0, z0, nu, st);
 }
@@ -450,6 +595,7 @@ int prepare_rowblocked(ccp_grid *g, int32_t smoothing_sweeps, bool need_nu, Grid
 {
     CCP_TRY(grid_mg_view(g, v));
     if (v->weighted) return CCP_ERR_UNSUPPORTED;                   // weighted handles are single blocks
+    if (v->precision != CCP_MG_PRECISION_F64) return CCP_ERR_UNSUPPORTED;   // the fp32 V-cycle too (a world-1 communicator on a whole image)
     if (!v->comm) return CCP_ERR_STATE;
     n->api = rccl_api();
     if (!n->api) return CCP_ERR_RCCL;
@@ -486,6 +632,7 @@ try {
     CCP_TRY(sweeps_arg(smoothing_sweeps, &nu));
     MgHierarchy *h = nullptr;
     CCP_TRY(hierarchy(v, &h));
+    if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
     const long n = v.geom.ch_stride;
     for (int ch = 0; ch < v.channels; ++ch) CCP_TRY(vcycle(*h, v.stream, v.b + ch * n, v.x + ch * n, nu, nullptr));
     CCP_HIP(hipStreamSynchronize(v.stream));
@@ -515,6 +662,32 @@ try {
     CCP_TRY(grid_mg_hierarchy_slot(g, &weighted, &slot, &cache));
     if (!kind) return CCP_ERR_BAD_ARG;
     *kind = *slot;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_set_precision(ccp_grid *g, int32_t precision)
+try {
+    int *slot = nullptr;
+    MgHierarchy **cache = nullptr;
+    bool row_block = false;
+    CCP_TRY(grid_mg_precision_slot(g, &slot, &cache, &row_block));
+    if (precision != CCP_MG_PRECISION_F64 && precision != CCP_MG_PRECISION_F32) return CCP_ERR_BAD_ARG;
+    if (precision == CCP_MG_PRECISION_F32 && row_block) return CCP_ERR_UNSUPPORTED;   // (local: nothing collective happens here)
+    if (*slot == precision) return CCP_OK;
+    *slot = precision;
+    mg_release(*cache);                                            // the cached vectors belong to the other precision
+    *cache = nullptr;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_get_precision(ccp_grid *g, int32_t *precision)
+try {
+    int *slot = nullptr;
+    MgHierarchy **cache = nullptr;
+    bool row_block = false;
+    CCP_TRY(grid_mg_precision_slot(g, &slot, &cache, &row_block));
+    if (!precision) return CCP_ERR_BAD_ARG;
+    *precision = *slot;
     return CCP_OK;
 } CCP_ABI_CATCH
 
@@ -572,6 +745,7 @@ try {
     if (max_iteration < 0) return CCP_ERR_BAD_ARG;
     MgHierarchy *h = nullptr;
     CCP_TRY(hierarchy(v, &h));
+    if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
     const Geom &geo = v.geom;
     const long n = geo.ch_stride;                                  // one channel incl. pads (pads stay 0 in every vector)
     // k_mg_apply: rows folded so that the grid has ~2,048 blocks (and as many partial sums for k_cg_alpha)

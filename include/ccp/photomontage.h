@@ -255,11 +255,15 @@ inline void SeamlessClone(const ImageView &source, const ImageView &target, cons
 // hierarchy: the preconditioner's hierarchy kind (ccp_grid_mg_set_hierarchy); with lambda > 0 Hierarchy::Rescaled needs far
 // fewer iterations, the default keeps the Galerkin one.
 enum class Hierarchy { Galerkin = CCP_MG_HIERARCHY_GALERKIN, Rescaled = CCP_MG_HIERARCHY_RESCALED };
+// precision: the preconditioner's precision (ccp_grid_mg_set_precision).  Precision::Single runs the V-cycle in float inside
+// the fp64 loop: the same answer to the same epsilon; pair it with Hierarchy::Rescaled (with Hierarchy::Galerkin it costs
+// iterations).  A weight too large or too small for a float makes the solve throw.  The default is the fp64 V-cycle.
+enum class Precision { Double = CCP_MG_PRECISION_F64, Single = CCP_MG_PRECISION_F32 };
 
 inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageView *f, const ImageView *wx, const ImageView *wy,
                           const ImageView *lambda, ImageView &out, int iterations,
                           Solver solver = Solver::MultigridConjugateGradient, int device = 0,
-                          Hierarchy hierarchy = Hierarchy::Galerkin)
+                          Hierarchy hierarchy = Hierarchy::Galerkin, Precision precision = Precision::Double)
 {
     if (solver != Solver::MultigridConjugateGradient)
         throw std::invalid_argument("SolveWeighted: only Solver::MultigridConjugateGradient solves a weighted system");
@@ -281,6 +285,7 @@ inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageV
     auto fp = [](const ImageView *v) { return v ? static_cast<const float *>(v->data) : nullptr; };
     detail::GridHandle h(out.cols, out.rows, C, device, CCP_GRID_WEIGHTED);
     detail::check(ccp_grid_mg_set_hierarchy(h.g, (int32_t)hierarchy), "ccp_grid_mg_set_hierarchy");
+    detail::check(ccp_grid_mg_set_precision(h.g, (int32_t)precision), "ccp_grid_mg_set_precision");
     detail::check(ccp_grid_set_weights_host(h.g, fp(wx), fp(wy), fp(lambda), (int64_t)wstep), "ccp_grid_set_weights_host");
     const int64_t gstep = gx ? (int64_t)gx->step : gy ? (int64_t)gy->step : 0;
     detail::check(ccp_grid_assemble_weighted_rhs(h.g, fp(gx), fp(gy), gstep, fp(f), f ? (int64_t)f->step : 0, f ? 1 : 0),
@@ -297,7 +302,7 @@ inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageV
 // lambda NULL or 0 every connected set of free pixels needs a fixed neighbour.
 inline void SolveConstrained(const ImageView *gx, const ImageView *gy, const ImageView *f, const ImageView *values, const ImageView &fixed,
                              const ImageView *wx, const ImageView *wy, const ImageView *lambda, ImageView &out, int iterations,
-                             int device = 0, Hierarchy hierarchy = Hierarchy::Rescaled)
+                             int device = 0, Hierarchy hierarchy = Hierarchy::Rescaled, Precision precision = Precision::Double)
 {
     const int C = out.channels;
     if (!out.data) throw std::invalid_argument("SolveConstrained: no output image");
@@ -317,6 +322,7 @@ inline void SolveConstrained(const ImageView *gx, const ImageView *gy, const Ima
     auto fp = [](const ImageView *v) { return v ? static_cast<const float *>(v->data) : nullptr; };
     detail::GridHandle h(out.cols, out.rows, C, device, CCP_GRID_WEIGHTED);
     detail::check(ccp_grid_mg_set_hierarchy(h.g, (int32_t)hierarchy), "ccp_grid_mg_set_hierarchy");
+    detail::check(ccp_grid_mg_set_precision(h.g, (int32_t)precision), "ccp_grid_mg_set_precision");
     detail::check(ccp_grid_set_weights_constrained_host(h.g, fp(wx), fp(wy), fp(lambda), (int64_t)wstep,
                                                         static_cast<const uint8_t *>(fixed.data), (int64_t)fixed.step),
                   "ccp_grid_set_weights_constrained_host");

@@ -426,6 +426,35 @@ int ccp_grid_mg_set_hierarchy(ccp_grid *g, int32_t kind);
 /* The handle's kind (GALERKIN on every handle that is not weighted).  NULL: CCP_ERR_BAD_ARG. */
 int ccp_grid_mg_get_hierarchy(ccp_grid *g, int32_t *kind);
 
+/* The precision of the multigrid preconditioner, per handle.  The default, F64, is the V-cycle above, bit for bit.  With
+ * F32 the V-cycle runs in float while the outer loop -- x, r, p, Ap, every dot product and the stop test on sqrt(r'r) --
+ * stays fp64, so the answer is held to the same epsilon; only the iteration count may move.
+ *   Definition.  The hierarchy is built in fp64 exactly as for F64 (all three level-0 kinds, both hierarchy kinds).  Every
+ *   level's d, we, ws are then narrowed to float, round to nearest (level 0 of a structured or mask handle has small
+ *   integers; a weighted handle's level 0 gets float copies of its stored planes, 12 bytes per pixel, allocated only in
+ *   F32 mode); a pixel is live if its float d != 0.  z = M^-1 r narrows r to float once on the way in, runs the V-cycle
+ *   above with every value a float -- the same sweeps, operation order, restriction order, correction scale, and IEEE
+ *   division; nothing is contracted to an fma and denormals are kept -- and widens the result on the way out.  The two
+ *   conversions happen inside the level-0 kernels' loads and stores.
+ *   Verdict.  If a coefficient narrows to an infinity, or a non-zero one to 0, ccp_grid_mg_conjugate_gradient and
+ *   ccp_grid_mg_apply return CCP_ERR_UNSUPPORTED with x and b untouched; the handle works again after
+ *   ccp_grid_mg_set_precision(g, CCP_MG_PRECISION_F64).  ccp_grid_mg_level returns the fp64 coefficients in both modes.
+ *   Which hierarchy.  On a weighted handle use F32 together with CCP_MG_HIERARCHY_RESCALED: in the model of
+ *   tests/mixed_helpers.py (257x131 and 512x384, fp64 -> fp32 V-cycle) the float V-cycle there costs no iterations on the
+ *   screened system (6 -> 6, 6 -> 6) and the constrained ellipse (8 -> 8, 7 -> 7) and up to 4 % on WLS (105 -> 109,
+ *   110 -> 112), while the Galerkin hierarchy pays for it: SolveChannel's weights 8 -> 10 iterations.  (WLS on the
+ *   Galerkin hierarchy was not run in that model; the model of the issue that asked for F32 had 121 -> 161 and
+ *   204 -> 259 there.)  The speed of F32 against F64 is unmeasured: no timing of the float V-cycle has been taken.
+ * Every single-block grid handle takes either value; a NULL handle or an unknown value: CCP_ERR_BAD_ARG.  A row block (a
+ * handle with ghost rows or row_count < height) refuses F32 with CCP_ERR_UNSUPPORTED, locally; on a whole-image handle
+ * set to F32 the _rowblocked calls (a world-1 communicator) return CCP_ERR_UNSUPPORTED before any collective call.  A
+ * change drops the cached hierarchy, as ccp_grid_mg_set_hierarchy does; setting the current value does nothing.  The
+ * value survives ccp_grid_set_weights_*, ccp_grid_set_mask_host and ccp_grid_mg_set_hierarchy. */
+#define CCP_MG_PRECISION_F64 0     /* the default: the fp64 V-cycle */
+#define CCP_MG_PRECISION_F32 1     /* V-cycle in fp32; outer PCG loop, x, r, p, Ap and all dot products fp64 */
+int ccp_grid_mg_set_precision(ccp_grid *g, int32_t precision);
+int ccp_grid_mg_get_precision(ccp_grid *g, int32_t *precision);
+
 /* ----------------------------------------------------------------------------------------
  * Row blocks across the GPUs of one node (BASELINE configs[3]).  One process (or host
  * thread) per GPU; each creates a communicator rank and one grid handle owning a contiguous block of

@@ -5,7 +5,11 @@ lambda 1, alpha 1.2) at 4096^2 x 3 and at the reference's image size 752x566 x 3
 16384^2 beside them (ms per PCG iteration: the weighted level 0 reads its 24 B/px of stored coefficients).  One JSON
 line per case and hierarchy kind (--hierarchy: a comma list of galerkin / rescaled, solved in that order on the same handle;
 the default runs both, and a list such as galerkin,galerkin,rescaled measures the spread of one kind against itself beside
-the difference between the kinds), as tools/mg_bench.py.  The screened and structured systems are manufactured (b = A x, x uniform
+the difference between the kinds), as tools/mg_bench.py.  --precision: a comma list of f64 / f32 (capi.Grid.mg_set_precision),
+alternated on the same handle in the same way: every entry runs the whole --hierarchy list, so f64,f32,f64,f32,f64,f32
+gives three alternations and f64 against itself as the noise floor.  first_apply_ms and apply_ms are the wall times of
+the first and the second ccp_grid_mg_apply after the hierarchy is built (one V-cycle per channel; in f32 the first also
+narrows the coefficients, which setup_ms and the solve's own timing leave out).  The screened and structured systems are manufactured (b = A x, x uniform
 [0, 255)); the WLS systems smooth a synthetic image of flat patches with edges and noise, built on the device."""
 import argparse, ctypes, json, os, sys, time
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
@@ -30,6 +34,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default=",".join(CASES))
     ap.add_argument("--hierarchy", default="galerkin,rescaled", help="comma list of galerkin / rescaled, in the order to run them")
+    ap.add_argument("--precision", default="f64", help="comma list of f64 / f32, in the order to run them")
     ap.add_argument("--sweeps", type=int, default=2)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--max-iterations", type=int, default=200)
@@ -38,6 +43,10 @@ def main():
     for k in kinds:
         if k not in capi.MG_HIERARCHIES:
             ap.error(f"--hierarchy: {k!r} is not one of {sorted(capi.MG_HIERARCHIES)}")
+    precisions = a.precision.split(",")
+    for p in precisions:
+        if p not in capi.MG_PRECISIONS:
+            ap.error(f"--precision: {p!r} is not one of {sorted(capi.MG_PRECISIONS)}")
     dev = torch.device("cuda", 0)
     for name in a.cases.split(","):
         W, H, C, kind = CASES[name]
@@ -57,14 +66,23 @@ def main():
             g.b_from_x()
         g.synchronize()
         # a structured handle has the one hierarchy
-        for run, hierarchy in enumerate(kinds if kind != "structured" else ["galerkin"]):
+        runs = [(p, h) for p in precisions for h in (kinds if kind != "structured" else ["galerkin"])]
+        for run, (precision, hierarchy) in enumerate(runs):
             if kind != "structured":
                 g.mg_set_hierarchy(hierarchy)
+            g.mg_set_precision(precision)
             t0 = time.perf_counter()
             nl = ctypes.c_int32()                                   # the first MG call of a kind builds its hierarchy
             capi.check(g.L.ccp_grid_mg_level(g.h, 0, ctypes.byref(nl), None, None, None, None, None), "ccp_grid_mg_level")
-            g.synchronize()
+            g.synchronize()                                         # (f32: the coefficients are narrowed at the first solve)
             setup_ms = (time.perf_counter() - t0) * 1e3
+            # one V-cycle per channel, twice: the first also narrows the coefficients in f32 (x is set anew below)
+            t0 = time.perf_counter()
+            g.mg_apply(a.sweeps)
+            first_apply_ms = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            g.mg_apply(a.sweeps)
+            apply_ms = (time.perf_counter() - t0) * 1e3
             best = None
             for _ in range(a.repeat):
                 if f is None:
@@ -81,10 +99,10 @@ def main():
             rr, bb = g.residual_norm2()
             secs, its, conv = best
             updates = sum(i + 1 for i in its)                       # as tools/mg_bench.py counts them
-            print(json.dumps({"case": name, "width": W, "height": H, "channels": C, "kind": kind, "hierarchy": hierarchy, "run": run,
+            print(json.dumps({"case": name, "width": W, "height": H, "channels": C, "kind": kind, "hierarchy": hierarchy, "precision": precision, "run": run,
                               "levels": nl.value, "smoothing_sweeps": a.sweeps, "max_iterations": a.max_iterations, "iterations": its, "converged": conv,
                               "ms_to_1e-10": secs * 1e3, "ms_per_pcg_iteration": secs * 1e3 / updates, "setup_ms": setup_ms,
-                              "rel_residual": float(np.sqrt(rr / bb).max())}), flush=True)
+                              "first_apply_ms": first_apply_ms, "apply_ms": apply_ms, "rel_residual": float(np.sqrt(rr / bb).max())}), flush=True)
         g.close()
 
 
