@@ -25,6 +25,18 @@ GRID_WEIGHTED = 2
 MG_HIERARCHY_GALERKIN, MG_HIERARCHY_RESCALED = 0, 1
 MG_HIERARCHIES = {"galerkin": MG_HIERARCHY_GALERKIN, "rescaled": MG_HIERARCHY_RESCALED}
 MG_PRECISIONS = {"f64": 0, "f32": 1}
+MG_CHANNELS = {"sequential": 0, "batched": 1}
+
+
+def mg_channels_value(mode):
+    """The CCP_MG_CHANNELS_* integer of "sequential" / "batched" (or of an integer of MG_CHANNELS): ValueError otherwise."""
+    if isinstance(mode, str):
+        if mode not in MG_CHANNELS:
+            raise ValueError(f"channels must be one of {sorted(MG_CHANNELS)}, not {mode!r}")
+        return MG_CHANNELS[mode]
+    if int(mode) not in MG_CHANNELS.values():
+        raise ValueError(f"channels must be one of {sorted(MG_CHANNELS.values())}, not {mode!r}")
+    return int(mode)
 ORDER_LEXICOGRAPHIC = 0
 ORDER_MULTICOLOUR = 1
 CLONE_IMPORT = 0
@@ -41,6 +53,7 @@ ABI_SYMBOLS = (
     "ccp_grid_sweep", "ccp_grid_sweep_edges_first", "ccp_grid_stream_wait_edges", "ccp_grid_tune", "ccp_grid_set_fused", "ccp_grid_set_tiling", "ccp_grid_get_tiling", "ccp_grid_sweep_l1", "ccp_grid_halo_refreshed", "ccp_grid_gauss_seidel", "ccp_grid_gauss_seidel_lexicographic", "ccp_debug_lex_tickets", "ccp_grid_conjugate_gradient",
     "ccp_grid_mg_conjugate_gradient", "ccp_grid_mg_apply", "ccp_grid_mg_level",
     "ccp_grid_mg_set_hierarchy", "ccp_grid_mg_get_hierarchy", "ccp_grid_mg_set_precision", "ccp_grid_mg_get_precision",
+    "ccp_grid_mg_set_channels", "ccp_grid_mg_get_channels", "ccp_debug_mgb_tile_lds",
     "ccp_grid_residual_norm2", "ccp_grid_abs_sum", "ccp_grid_assemble_rhs", "ccp_grid_assemble_from_images", "ccp_grid_store_u8",
     "ccp_grid_set_x_u8", "ccp_grid_assemble_region_rhs", "ccp_grid_assemble_clone", "ccp_grid_store_u8_composite",
     "ccp_grid_last_timing", "ccp_grid_region_begin", "ccp_grid_region_end",
@@ -190,6 +203,9 @@ def load() -> C.CDLL:
     L.ccp_grid_mg_get_hierarchy.argtypes = [vp, C.POINTER(i32)]
     L.ccp_grid_mg_set_precision.argtypes = [vp, i32]
     L.ccp_grid_mg_get_precision.argtypes = [vp, C.POINTER(i32)]
+    L.ccp_grid_mg_set_channels.argtypes = [vp, i32]
+    L.ccp_grid_mg_get_channels.argtypes = [vp, C.POINTER(i32)]
+    L.ccp_debug_mgb_tile_lds.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.ccp_csr_apply_to_vector.argtypes = [vp, vp, vp]
     L.ccp_csr_residual_norm2.argtypes = [vp, vp, vp, C.POINTER(dbl), C.POINTER(dbl)]
     L.ccp_grid_create.argtypes = [C.POINTER(GridDesc), C.POINTER(vp)]
@@ -711,6 +727,18 @@ class Grid:
         value = C.c_int32()
         check(self.L.ccp_grid_mg_get_precision(self.h, C.byref(value)), "ccp_grid_mg_get_precision")
         return next(name for name, v in MG_PRECISIONS.items() if v == value.value)
+
+    def mg_set_channels(self, mode):
+        """How the multigrid PCG goes through the handle's channels: "sequential" (the default: one loop per channel) or
+        "batched" (one loop, every launch serves all channels; every channel gets the sequential call's bits), or the
+        integers of MG_CHANNELS.  A change drops the cached PCG vectors and keeps the hierarchy."""
+        check(self.L.ccp_grid_mg_set_channels(self.h, mg_channels_value(mode)), "ccp_grid_mg_set_channels")
+
+    def mg_channels(self):
+        """The handle's channel mode: "sequential" or "batched"."""
+        value = C.c_int32()
+        check(self.L.ccp_grid_mg_get_channels(self.h, C.byref(value)), "ccp_grid_mg_get_channels")
+        return next(name for name, v in MG_CHANNELS.items() if v == value.value)
 
     def mg_levels(self):
         """The multigrid hierarchy: one (diag, w_east, w_south) triple of H_k x W_k arrays per level, level 0 first."""

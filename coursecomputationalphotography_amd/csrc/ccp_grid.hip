@@ -148,6 +148,7 @@ struct ccp_grid {
     DevBuf<unsigned long long> wcount;
     long w_fixed = 0, w_live = -1, w_edges = 0;
     int mg_kind = CCP_MG_HIERARCHY_GALERKIN;   // ccp_grid_mg_set_hierarchy (weighted handles; survives ccp_grid_set_weights_*)
+    int mg_channels = CCP_MG_CHANNELS_SEQUENTIAL;   // ccp_grid_mg_set_channels (survives what mg_precision survives, and set_precision)
     int mg_precision = CCP_MG_PRECISION_F64;   // ccp_grid_mg_set_precision (survives set_weights, set_mask and set_hierarchy)
 };
 
@@ -1098,6 +1099,7 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     v->wlam = !op ? nullptr : g->has_fixed ? g->wcons.p + 2 * n : op + 3 * n;   // with fixed pixels: lambda' (ccp_grid_weighted.hpp)
     v->hierarchy_kind = g->mg_kind;
     v->precision = g->mg_precision;
+    v->channels_mode = g->mg_channels;
     v->stream = g->stream;
     v->cache = &g->mg;
     v->comm = g->comm;
@@ -1121,6 +1123,14 @@ int ccp::grid_mg_precision_slot(ccp_grid *g, int **precision, MgHierarchy ***cac
     *precision = &g->mg_precision;
     *cache = &g->mg;
     *row_block = g->desc.ghost != 0 || g->desc.row_count < g->desc.height;
+    return CCP_OK;
+}
+
+int ccp::grid_mg_channels_slot(ccp_grid *g, int **mode, MgHierarchy ***cache)
+{
+    CCP_TRY(bind(g));
+    *mode = &g->mg_channels;
+    *cache = &g->mg;
     return CCP_OK;
 }
 

@@ -2,9 +2,11 @@
 // ccp_grid_mg_*).  Kernels and the algorithm: ccp_grid_mg.hpp.
 #include "ccp_grid_mg.hpp"
 #include "ccp_grid_mgs.hpp"
+#include "ccp_grid_mgb.hpp"
 #include "ccp_comm.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <memory>
 #include <vector>
 
@@ -46,6 +48,15 @@ struct MgHierarchy {
     DevBuf<unsigned> fbad;
     float *farr(int k, int which) { return fstore.p + fbase[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t
     int lam_slot = 6;                // F32: 3 (the fp64 store then holds d, we, ws and lambda only)
+    // CCP_MG_CHANNELS_BATCHED (ccp_grid_mgb.hpp): C of every vector, made at the first batched V-cycle (bt0: level 0's t;
+    // bstore: per coarse level b, z, t, each C x `size`) and at the first batched solve (the PCG vectors, CgState[C], the
+    // partial sums: C slices of bps).  The levels' coefficients are shared with the sequential mode.
+    int bC = 0;
+    long bps = 0;
+    std::vector<long> bbase;
+    DevBuf<double> bt0, bstore, bz, br, bp, bap, bpartial;
+    DevBuf<CgState> bstate;
+    double *barr(int k, int which) { return bstore.p + bbase[k] + (long)which * bC * size[k]; }   // 0 b, 1 z, 2 t: channel ch at + ch * size[k]
     double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda (lam_slot)
     ~MgHierarchy()
     {
@@ -388,6 +399,228 @@ int vcycle(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, 
     return whole_levels(h, s, 0, b0, z0, nu, st);
 }
 
+// ---- CCP_MG_CHANNELS_BATCHED (ccp_grid_mgb.hpp) ----------------------------------------------------------------------
+// The dynamic LDS a k_mgb_tile launch asks for: the one figure behind the launch, the limit below and
+// ccp_debug_mgb_tile_lds.
+int tile_b_lds(int kind, int nu) { return mgb_tile_lds(kind, nu); }
+
+template <int KIND>
+int tile_lds_limit_of()
+{
+    const int bytes = tile_b_lds(KIND, 4);                            // the largest nu
+    CCP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mgb_tile<KIND, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    CCP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mgb_tile<KIND, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return CCP_OK;
+}
+
+// The stored-operator kind passes the 64 KiB a kernel may take without asking; the others come within 256 B of it
+// (65,280 B at nu = 4) and are given their size too.  Once per device and process.
+int tile_lds_limit()
+{
+    static std::atomic<unsigned long long> raised{0};
+    int dev = 0;
+    CCP_HIP(hipGetDevice(&dev));
+    const unsigned long long bit = dev < 64 ? 1ull << dev : 0;
+    if (raised.load() & bit) return CCP_OK;
+    CCP_TRY(tile_lds_limit_of<kMgSolve>());
+    CCP_TRY(tile_lds_limit_of<kMgMasked>());
+    CCP_TRY(tile_lds_limit_of<kMgCoarse>());
+    raised.fetch_or(bit);
+    return CCP_OK;
+}
+
+// C of level 0's t and of every coarse level's b, z, t, once per hierarchy
+int batched_levels(const GridMgView &v, MgHierarchy &h)
+{
+    if (h.bC == v.channels && h.bt0.p) return CCP_OK;
+    const int C = v.channels;
+    const long n0 = v.geom.ch_stride;
+    CCP_TRY(tile_lds_limit());
+    long total = 0;
+    h.bbase.assign((size_t)h.levels, 0);
+    for (int k = 1; k < h.levels; ++k) {
+        h.bbase[k] = total;
+        total += 3 * C * h.size[k];
+    }
+    CCP_TRY(h.bt0.alloc((size_t)(C * n0)));
+    CCP_HIP(hipMemsetAsync(h.bt0.p, 0, sizeof(double) * C * n0, v.stream));
+    if (total > 0) {
+        CCP_TRY(h.bstore.alloc((size_t)total));
+        CCP_HIP(hipMemsetAsync(h.bstore.p, 0, sizeof(double) * total, v.stream));
+    }
+    h.bC = C;
+    return CCP_OK;
+}
+
+void batched_release(MgHierarchy &h)
+{
+    for (DevBuf<double> *b : {&h.bt0, &h.bstore, &h.bz, &h.br, &h.bp, &h.bap, &h.bpartial}) b->release();
+    h.bstate.release();
+    h.bC = 0;
+}
+
+template <int KIND, bool POST>
+void tile_b(hipStream_t s, dim3 grid, const MgLevel &f, const double *b, const double *t, double *z, long fs, const MgLevel &c,
+            const double *ec, long es, double cs, int nu, int C, const CgState *st)
+{
+    hipLaunchKernelGGL((k_mgb_tile<KIND, POST>), grid, dim3(mgb_tile_threads(KIND)), tile_b_lds(KIND, nu), s, f, b, t, z, fs, c, ec, es, cs, nu, C, st);
+}
+
+template <bool POST>
+void tile_b(int kind, hipStream_t s, dim3 grid, const MgLevel &f, const double *b, const double *t, double *z, long fs, const MgLevel &c,
+            const double *ec, long es, double cs, int nu, int C, const CgState *st)
+{
+    if (kind == kMgCoarse) tile_b<kMgCoarse, POST>(s, grid, f, b, t, z, fs, c, ec, es, cs, nu, C, st);
+    else if (kind == kMgMasked) tile_b<kMgMasked, POST>(s, grid, f, b, t, z, fs, c, ec, es, cs, nu, C, st);
+    else tile_b<kMgSolve, POST>(s, grid, f, b, t, z, fs, c, ec, es, cs, nu, C, st);
+}
+
+// z0 := M^-1 b0 for all C channels (n0 doubles apart in b0 and z0): whole_levels / vcycle_1x1 with every launch serving
+// all channels; st: CgState[C] or null
+int vcycle_batched(MgHierarchy &h, hipStream_t s, int C, long n0, const double *b0, double *z0, int nu, const CgState *st)
+{
+    const double *none = nullptr;
+    if (h.levels == 1) {
+        tile_b<false>(h.kind0, s, dim3(1), h.lv[0], b0, none, z0, n0, h.lv[0], none, 0, 2.0, nu, C, st);
+        CCP_HIP(hipGetLastError());
+        return CCP_OK;
+    }
+    auto S = [&](int k) -> long { return k ? h.size[k] : n0; };      // the channel stride of level k's vectors
+    auto B = [&](int k) -> const double * { return k ? h.barr(k, 0) : b0; };
+    auto Z = [&](int k) -> double * { return k ? h.barr(k, 1) : z0; };
+    auto T = [&](int k) -> double * { return k ? h.barr(k, 2) : h.bt0.p; };
+    const unsigned groups = (unsigned)((C + kMgbGroup - 1) / kMgbGroup);
+    for (int k = 0; k < h.tail; ++k) {
+        const MgLevel &f = h.lv[k], &c = h.lv[k + 1];
+        const int kind = level_kind(h, k);
+        tile_b<false>(kind, s, tiles(f), f, B(k), none, T(k), S(k), f, none, 0, 2.0, nu, C, st);
+        dim3 grid = cells_grid(c.W, c.H);
+        grid.z = groups;
+        if (kind == kMgCoarse) hipLaunchKernelGGL((k_mgb_restrict<kMgCoarse>), grid, dim3(kBlock), 0, s, f, B(k), static_cast<const double *>(T(k)), S(k), c, 0, h.barr(k + 1, 0), S(k + 1), C, st);
+        else if (kind == kMgMasked) hipLaunchKernelGGL((k_mgb_restrict<kMgMasked>), grid, dim3(kBlock), 0, s, f, B(k), static_cast<const double *>(T(k)), S(k), c, 0, h.barr(k + 1, 0), S(k + 1), C, st);
+        else hipLaunchKernelGGL((k_mgb_restrict<kMgSolve>), grid, dim3(kBlock), 0, s, f, B(k), static_cast<const double *>(T(k)), S(k), c, 0, h.barr(k + 1, 0), S(k + 1), C, st);
+    }
+    MgTail t{};
+    t.levels = h.levels - h.tail;
+    int off = 0;
+    for (int i = 0; i < t.levels; ++i) {
+        const MgLevel &l = h.lv[h.tail + i];
+        t.W[i] = l.W;
+        t.H[i] = l.H;
+        t.pitch[i] = l.pitch;
+        t.off[i] = off;
+        t.d[i] = l.d;
+        t.we[i] = l.we;
+        t.ws[i] = l.ws;
+        off += l.W * l.H;
+    }
+    hipLaunchKernelGGL(k_mgb_tail, dim3((unsigned)C), dim3(kBlock), 0, s, t, B(h.tail), Z(h.tail), S(h.tail), S(h.tail), h.cs, nu, st);
+    for (int k = h.tail - 1; k >= 0; --k)
+        tile_b<true>(level_kind(h, k), s, tiles(h.lv[k]), h.lv[k], B(k), static_cast<const double *>(T(k)), Z(k), S(k), h.lv[k + 1],
+                     static_cast<const double *>(h.barr(k + 1, 1)), S(k + 1), h.cs, nu, C, st);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+// ccp_grid_mg_conjugate_gradient in batched mode: the sequential loop's launches, each for all channels
+int pcg_batched(const GridMgView &v, MgHierarchy &h, double epsilon, int max_iteration, int nu, ccp_gs_report *report)
+{
+    const Geom &geo = v.geom;
+    const int C = v.channels;
+    const long n = geo.ch_stride;
+    const unsigned groups = (unsigned)((C + kMgbGroup - 1) / kMgbGroup);
+    const unsigned agx = cells_grid((geo.W + 1) / 2, 1).x;             // (the sequential loop's grids within a channel)
+    const dim3 agrid(agx, (unsigned)std::max(1, std::min(geo.H, (int)(1024 / agx))), 2 * groups);
+    const int apply_blocks = (int)(agrid.x * agrid.y * 2);
+    const int blocks = (int)std::max<long>(1, std::min<long>(2048, (n + kBlock - 1) / kBlock));
+    const dim3 vgrid((unsigned)blocks, (unsigned)C), sgrid((unsigned)C);
+    hipStream_t s = v.stream;
+    CCP_TRY(batched_levels(v, h));
+    if (!h.bz.p) {
+        h.bps = std::max(apply_blocks, blocks);
+        for (DevBuf<double> *b : {&h.bz, &h.br, &h.bp, &h.bap}) {
+            CCP_TRY(b->alloc((size_t)(C * n)));
+            CCP_HIP(hipMemsetAsync(b->p, 0, sizeof(double) * C * n, s));
+        }
+        CCP_TRY(h.bpartial.alloc((size_t)(C * h.bps)));
+        CCP_TRY(h.bstate.alloc((size_t)C));
+    }
+    CgState *st = h.bstate.p;
+    double *part = h.bpartial.p;
+    const long ps = h.bps;
+    const MgLevel &l0 = h.lv[0];
+    auto apply = [&](const double *in, double *out, bool dot) {
+        const CgState *a = dot ? st : nullptr;
+        if (v.weighted) {
+            if (dot) hipLaunchKernelGGL((k_mgb_apply<kMgCoarse, true>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
+            else hipLaunchKernelGGL((k_mgb_apply<kMgCoarse, false>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
+        } else if (v.masked) {
+            if (dot) hipLaunchKernelGGL((k_mgb_apply<kMgMasked, true>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
+            else hipLaunchKernelGGL((k_mgb_apply<kMgMasked, false>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
+        } else {
+            if (dot) hipLaunchKernelGGL((k_mgb_apply<kMgSolve, true>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
+            else hipLaunchKernelGGL((k_mgb_apply<kMgSolve, false>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
+        }
+    };
+    std::vector<CgState> host((size_t)C);
+    for (CgState &c : host) {
+        c = CgState{};
+        c.active = 1;
+    }
+    const size_t st_bytes = sizeof(CgState) * (size_t)C;
+    auto any_active = [&]() {
+        for (const CgState &c : host)
+            if (c.active) return true;
+        return false;
+    };
+    CCP_HIP(hipMemcpyAsync(st, host.data(), st_bytes, hipMemcpyHostToDevice, s));
+    CCP_HIP(hipEventRecord(h.ev0, s));
+    apply(v.x, h.br.p, false);                                                                   // r = A x
+    hipLaunchKernelGGL(k_mgb_init, vgrid, dim3(kBlock), 0, s, static_cast<const double *>(v.b), h.br.p, h.bp.p, n, part, ps);   // r = b - r; r'r
+    hipLaunchKernelGGL(k_mgb_check, sgrid, dim3(kBlock), 0, s, part, ps, blocks, epsilon, st);
+    CCP_TRY(vcycle_batched(h, s, C, n, h.br.p, h.bz.p, nu, st));                                  // z = M r
+    hipLaunchKernelGGL(k_mgb_dot, vgrid, dim3(kBlock), 0, s, h.br.p, h.bz.p, n, part, ps, st);
+    hipLaunchKernelGGL(k_mgb_set_rlen, sgrid, dim3(kBlock), 0, s, part, ps, blocks, st);          // rlen = r'z
+    CCP_HIP(hipMemcpyAsync(h.bp.p, h.bz.p, sizeof(double) * C * n, hipMemcpyDeviceToDevice, s));  // p = z
+    CCP_HIP(hipGetLastError());
+    CCP_HIP(hipMemcpyAsync(host.data(), st, st_bytes, hipMemcpyDeviceToHost, s));
+    CCP_HIP(hipStreamSynchronize(s));
+    int issued = 0;
+    bool active = any_active() && max_iteration > 0;
+    while (active && issued < max_iteration) {
+        const int batch = std::min(16, max_iteration - issued);
+        for (int k = 0; k < batch; ++k) {
+            apply(h.bp.p, h.bap.p, true);                                                        // Ap, p'Ap partials
+            hipLaunchKernelGGL(k_mgb_alpha, sgrid, dim3(kBlock), 0, s, part, ps, apply_blocks, st);
+            hipLaunchKernelGGL(k_mgb_update, vgrid, dim3(kBlock), 0, s, v.x, h.bp.p, h.br.p, h.bap.p, n, part, ps, st);
+            hipLaunchKernelGGL(k_mgb_check, sgrid, dim3(kBlock), 0, s, part, ps, blocks, epsilon, st);
+            CCP_TRY(vcycle_batched(h, s, C, n, h.br.p, h.bz.p, nu, st));
+            hipLaunchKernelGGL(k_mgb_dot, vgrid, dim3(kBlock), 0, s, h.br.p, h.bz.p, n, part, ps, st);
+            hipLaunchKernelGGL(k_mgb_beta, sgrid, dim3(kBlock), 0, s, part, ps, blocks, st);
+            hipLaunchKernelGGL(k_mgb_direction, vgrid, dim3(kBlock), 0, s, h.bp.p, h.bz.p, n, st);   // p = z + beta p
+        }
+        CCP_HIP(hipGetLastError());
+        issued += batch;
+        CCP_HIP(hipMemcpyAsync(host.data(), st, st_bytes, hipMemcpyDeviceToHost, s));
+        CCP_HIP(hipStreamSynchronize(s));
+        active = any_active();
+    }
+    CCP_HIP(hipEventRecord(h.ev1, s));
+    CCP_HIP(hipMemcpyAsync(host.data(), st, st_bytes, hipMemcpyDeviceToHost, s));
+    CCP_HIP(hipStreamSynchronize(s));
+    if (report) {
+        float ms = 0.f;
+        CCP_HIP(hipEventElapsedTime(&ms, h.ev0, h.ev1));
+        for (int ch = 0; ch < C; ++ch) {
+            report[ch].iterations = host[ch].iterations;
+            report[ch].converged = host[ch].converged;
+            report[ch].last_l1_step = host[ch].r1norm;
+            report[ch].seconds = ms * 1e-3;                                                       // the whole batched solve
+        }
+    }
+    return CCP_OK;
+}
+
 // ---- row blocks ----------------------------------------------------------------------------------------------------
 constexpr int kMgGhost = 8;          // ghost rows per neighbour side of a distributed level: 2 x the largest nu
 
@@ -596,6 +829,7 @@ int prepare_rowblocked(ccp_grid *g, int32_t smoothing_sweeps, bool need_nu, Grid
     CCP_TRY(grid_mg_view(g, v));
     if (v->weighted) return CCP_ERR_UNSUPPORTED;                   // weighted handles are single blocks
     if (v->precision != CCP_MG_PRECISION_F64) return CCP_ERR_UNSUPPORTED;   // the fp32 V-cycle too (a world-1 communicator on a whole image)
+    if (v->channels_mode != CCP_MG_CHANNELS_SEQUENTIAL) return CCP_ERR_UNSUPPORTED;   // ... and the batched mode
     if (!v->comm) return CCP_ERR_STATE;
     n->api = rccl_api();
     if (!n->api) return CCP_ERR_RCCL;
@@ -630,10 +864,18 @@ try {
     CCP_TRY(check_handle(g, &v));
     int nu = 2;
     CCP_TRY(sweeps_arg(smoothing_sweeps, &nu));
+    const bool batched = v.channels_mode == CCP_MG_CHANNELS_BATCHED;
+    if (batched && v.precision == CCP_MG_PRECISION_F32) return CCP_ERR_UNSUPPORTED;
     MgHierarchy *h = nullptr;
     CCP_TRY(hierarchy(v, &h));
     if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
     const long n = v.geom.ch_stride;
+    if (batched) {
+        CCP_TRY(batched_levels(v, *h));
+        CCP_TRY(vcycle_batched(*h, v.stream, v.channels, n, v.b, v.x, nu, nullptr));
+        CCP_HIP(hipStreamSynchronize(v.stream));
+        return CCP_OK;
+    }
     for (int ch = 0; ch < v.channels; ++ch) CCP_TRY(vcycle(*h, v.stream, v.b + ch * n, v.x + ch * n, nu, nullptr));
     CCP_HIP(hipStreamSynchronize(v.stream));
     return CCP_OK;
@@ -691,6 +933,41 @@ try {
     return CCP_OK;
 } CCP_ABI_CATCH
 
+int ccp_grid_mg_set_channels(ccp_grid *g, int32_t mode)
+try {
+    int *slot = nullptr;
+    MgHierarchy **cache = nullptr;
+    CCP_TRY(grid_mg_channels_slot(g, &slot, &cache));
+    if (mode != CCP_MG_CHANNELS_SEQUENTIAL && mode != CCP_MG_CHANNELS_BATCHED) return CCP_ERR_BAD_ARG;
+    if (*slot == mode) return CCP_OK;
+    *slot = mode;
+    if (*cache) {                                                  // the other mode's vectors go; the levels stay
+        MgHierarchy &h = **cache;
+        batched_release(h);
+        for (DevBuf<double> *b : {&h.z, &h.r, &h.p, &h.ap, &h.partial}) b->release();
+        h.state.release();
+    }
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_get_channels(ccp_grid *g, int32_t *mode)
+try {
+    int *slot = nullptr;
+    MgHierarchy **cache = nullptr;
+    CCP_TRY(grid_mg_channels_slot(g, &slot, &cache));
+    if (!mode) return CCP_ERR_BAD_ARG;
+    *mode = *slot;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_debug_mgb_tile_lds(int32_t level_kind, int32_t smoothing_sweeps, int32_t *bytes, int32_t *threads)
+try {
+    if (level_kind < kMgSolve || level_kind > kMgCoarse || smoothing_sweeps < 1 || smoothing_sweeps > 4) return CCP_ERR_BAD_ARG;
+    if (bytes) *bytes = tile_b_lds(level_kind, smoothing_sweeps);
+    if (threads) *threads = mgb_tile_threads(level_kind);
+    return CCP_OK;
+} CCP_ABI_CATCH
+
 int ccp_grid_mg_level(ccp_grid *g, int32_t level, int32_t *n_levels, int32_t *width, int32_t *height, double *diag,
                       double *w_east, double *w_south)
 try {
@@ -743,8 +1020,11 @@ try {
     int nu = 2;
     CCP_TRY(sweeps_arg(smoothing_sweeps, &nu));
     if (max_iteration < 0) return CCP_ERR_BAD_ARG;
+    const bool batched = v.channels_mode == CCP_MG_CHANNELS_BATCHED;
+    if (batched && v.precision == CCP_MG_PRECISION_F32) return CCP_ERR_UNSUPPORTED;
     MgHierarchy *h = nullptr;
     CCP_TRY(hierarchy(v, &h));
+    if (batched) return pcg_batched(v, *h, epsilon, max_iteration, nu, report);
     if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
     const Geom &geo = v.geom;
     const long n = geo.ch_stride;                                  // one channel incl. pads (pads stay 0 in every vector)

@@ -356,7 +356,8 @@ struct MgTail {
 };
 
 // b_top: right-hand side of the tail's first level (its level layout); z_top: its correction; cs: the correction scale
-// (2.0 or 1.0, as k_mg_tile's).  grid = 1 workgroup.
+// (2.0 or 1.0, as k_mg_tile's).  grid = 1 workgroup.  k_mgb_tail (ccp_grid_mgb.hpp) is this body once per channel and
+// must give the same bits: a change here is made there too.
 static __global__ void __launch_bounds__(kBlock)
 k_mg_tail(MgTail t, const double *__restrict__ b_top, double *__restrict__ z_top, double cs, int nu, const CgState *__restrict__ st)
 {

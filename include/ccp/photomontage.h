@@ -259,11 +259,16 @@ enum class Hierarchy { Galerkin = CCP_MG_HIERARCHY_GALERKIN, Rescaled = CCP_MG_H
 // the fp64 loop: the same answer to the same epsilon; pair it with Hierarchy::Rescaled (with Hierarchy::Galerkin it costs
 // iterations).  A weight too large or too small for a float makes the solve throw.  The default is the fp64 V-cycle.
 enum class Precision { Double = CCP_MG_PRECISION_F64, Single = CCP_MG_PRECISION_F32 };
+// channels: how the solve goes through the channels (ccp_grid_mg_set_channels).  Channels::Batched runs one PCG loop whose
+// launches serve all channels; every channel gets the bits of the default, Channels::Sequential.  Not together with
+// Precision::Single: that solve throws.
+enum class Channels { Sequential = CCP_MG_CHANNELS_SEQUENTIAL, Batched = CCP_MG_CHANNELS_BATCHED };
 
 inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageView *f, const ImageView *wx, const ImageView *wy,
                           const ImageView *lambda, ImageView &out, int iterations,
                           Solver solver = Solver::MultigridConjugateGradient, int device = 0,
-                          Hierarchy hierarchy = Hierarchy::Galerkin, Precision precision = Precision::Double)
+                          Hierarchy hierarchy = Hierarchy::Galerkin, Precision precision = Precision::Double,
+                          Channels channels = Channels::Sequential)
 {
     if (solver != Solver::MultigridConjugateGradient)
         throw std::invalid_argument("SolveWeighted: only Solver::MultigridConjugateGradient solves a weighted system");
@@ -286,6 +291,7 @@ inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageV
     detail::GridHandle h(out.cols, out.rows, C, device, CCP_GRID_WEIGHTED);
     detail::check(ccp_grid_mg_set_hierarchy(h.g, (int32_t)hierarchy), "ccp_grid_mg_set_hierarchy");
     detail::check(ccp_grid_mg_set_precision(h.g, (int32_t)precision), "ccp_grid_mg_set_precision");
+    detail::check(ccp_grid_mg_set_channels(h.g, (int32_t)channels), "ccp_grid_mg_set_channels");
     detail::check(ccp_grid_set_weights_host(h.g, fp(wx), fp(wy), fp(lambda), (int64_t)wstep), "ccp_grid_set_weights_host");
     const int64_t gstep = gx ? (int64_t)gx->step : gy ? (int64_t)gy->step : 0;
     detail::check(ccp_grid_assemble_weighted_rhs(h.g, fp(gx), fp(gy), gstep, fp(f), f ? (int64_t)f->step : 0, f ? 1 : 0),
@@ -302,7 +308,8 @@ inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageV
 // lambda NULL or 0 every connected set of free pixels needs a fixed neighbour.
 inline void SolveConstrained(const ImageView *gx, const ImageView *gy, const ImageView *f, const ImageView *values, const ImageView &fixed,
                              const ImageView *wx, const ImageView *wy, const ImageView *lambda, ImageView &out, int iterations,
-                             int device = 0, Hierarchy hierarchy = Hierarchy::Rescaled, Precision precision = Precision::Double)
+                             int device = 0, Hierarchy hierarchy = Hierarchy::Rescaled, Precision precision = Precision::Double,
+                             Channels channels = Channels::Sequential)
 {
     const int C = out.channels;
     if (!out.data) throw std::invalid_argument("SolveConstrained: no output image");
@@ -323,6 +330,7 @@ inline void SolveConstrained(const ImageView *gx, const ImageView *gy, const Ima
     detail::GridHandle h(out.cols, out.rows, C, device, CCP_GRID_WEIGHTED);
     detail::check(ccp_grid_mg_set_hierarchy(h.g, (int32_t)hierarchy), "ccp_grid_mg_set_hierarchy");
     detail::check(ccp_grid_mg_set_precision(h.g, (int32_t)precision), "ccp_grid_mg_set_precision");
+    detail::check(ccp_grid_mg_set_channels(h.g, (int32_t)channels), "ccp_grid_mg_set_channels");
     detail::check(ccp_grid_set_weights_constrained_host(h.g, fp(wx), fp(wy), fp(lambda), (int64_t)wstep,
                                                         static_cast<const uint8_t *>(fixed.data), (int64_t)fixed.step),
                   "ccp_grid_set_weights_constrained_host");

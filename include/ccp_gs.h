@@ -455,6 +455,35 @@ int ccp_grid_mg_get_hierarchy(ccp_grid *g, int32_t *kind);
 int ccp_grid_mg_set_precision(ccp_grid *g, int32_t precision);
 int ccp_grid_mg_get_precision(ccp_grid *g, int32_t *precision);
 
+/* How ccp_grid_mg_conjugate_gradient and ccp_grid_mg_apply go through the channels of a handle, per handle.  SEQUENTIAL,
+ * the default, runs one PCG loop (one V-cycle) per channel.  BATCHED runs one loop for all channels: every launch serves
+ * all of them, the operator's coefficients are fetched once per launch for all channels, and every channel keeps its own
+ * scalars and its own stop.  The channels never mix, so every channel gets, bit for bit, the x, iteration count,
+ * `converged` and `last_l1_step` of the sequential call; report[ch].seconds alone differs: in BATCHED mode it is the
+ * elapsed time of the whole batched solve, the same value in every channel.
+ * Every single-block grid handle (structured, Dirichlet-mask, weighted with either hierarchy kind, with fixed pixels) takes
+ * either value; a NULL handle or an unknown value: CCP_ERR_BAD_ARG.  Setting the current value does nothing; a change
+ * drops the cached PCG vectors and keeps the hierarchy (ccp_grid_mg_level returns the same bits in both modes).  The value
+ * survives ccp_grid_set_weights_*, ccp_grid_set_mask_host, ccp_grid_mg_set_hierarchy and ccp_grid_mg_set_precision.
+ * Two combinations are refused at the solve, whatever order the setters were called in:
+ *   BATCHED with CCP_MG_PRECISION_F32: ccp_grid_mg_conjugate_gradient and ccp_grid_mg_apply return CCP_ERR_UNSUPPORTED with
+ *   x and b untouched;
+ *   BATCHED with row blocks: the _rowblocked multigrid calls on a BATCHED handle (with or without ghost rows) return
+ *   CCP_ERR_UNSUPPORTED before any collective call.
+ * Memory.  BATCHED adds to what the handle holds, it does not replace it: the hierarchy keeps the sequential mode's
+ * level-0 t and its b, z, t of every coarse level, and the first BATCHED V-cycle or solve allocates beside them C of
+ * level 0's t and of every coarse level's b, z, t, and C of r, z, p, Ap (about 5 C n doubles at n pixels per channel,
+ * plus 3 C of every coarse level).  A change of mode frees the PCG vectors and all BATCHED buffers; the sequential
+ * slots inside the hierarchy stay until the hierarchy is dropped. */
+#define CCP_MG_CHANNELS_SEQUENTIAL 0   /* the default: one PCG loop per channel */
+#define CCP_MG_CHANNELS_BATCHED    1   /* one PCG loop, every launch serves all channels */
+int ccp_grid_mg_set_channels(ccp_grid *g, int32_t mode);
+int ccp_grid_mg_get_channels(ccp_grid *g, int32_t *mode);
+/* Diagnostic (host only, no device needed): the dynamic LDS in bytes and the workgroup size of a BATCHED tile-pass launch
+ * on a level of kind `level_kind` -- 0 structured, 1 Dirichlet mask, 2 stored operator (level 0 of a weighted handle and
+ * every coarse level) -- with `smoothing_sweeps` 1..4; anything else: CCP_ERR_BAD_ARG.  Either output may be NULL. */
+int ccp_debug_mgb_tile_lds(int32_t level_kind, int32_t smoothing_sweeps, int32_t *bytes, int32_t *threads);
+
 /* ----------------------------------------------------------------------------------------
  * Row blocks across the GPUs of one node (BASELINE configs[3]).  One process (or host
  * thread) per GPU; each creates a communicator rank and one grid handle owning a contiguous block of

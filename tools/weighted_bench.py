@@ -9,7 +9,12 @@ the difference between the kinds), as tools/mg_bench.py.  --precision: a comma l
 alternated on the same handle in the same way: every entry runs the whole --hierarchy list, so f64,f32,f64,f32,f64,f32
 gives three alternations and f64 against itself as the noise floor.  first_apply_ms and apply_ms are the wall times of
 the first and the second ccp_grid_mg_apply after the hierarchy is built (one V-cycle per channel; in f32 the first also
-narrows the coefficients, which setup_ms and the solve's own timing leave out).  The screened and structured systems are manufactured (b = A x, x uniform
+narrows the coefficients, which setup_ms and the solve's own timing leave out).  --channels: a comma list of sequential /
+batched (capi.Grid.mg_set_channels), the outermost alternation on the same handle: every entry runs the whole --precision x
+--hierarchy list.  A batched solve reports the elapsed time of the whole solve in every channel, so its time is one
+report's seconds, not their sum; ms_per_pcg_iteration divides by the updates summed over the channels in both modes (ms
+per channel-iteration).  A list of `sequential` alone never calls the setter, so it also runs on a library without it.
+The screened and structured systems are manufactured (b = A x, x uniform
 [0, 255)); the WLS systems smooth a synthetic image of flat patches with edges and noise, built on the device."""
 import argparse, ctypes, json, os, sys, time
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
@@ -19,6 +24,7 @@ from coursecomputationalphotography_amd import capi, tensor_ops
 
 CASES = {"screened_16384sq": (16384, 16384, 1, "screened"), "wls_4096sq_x3": (4096, 4096, 3, "wls"),
          "wls_752x566_x3": (752, 566, 3, "wls"), "structured_16384sq": (16384, 16384, 1, "structured")}
+MORE_CASES = {"screened_4096sq_x3": (4096, 4096, 3, "screened")}   # by name only: not part of the default list
 
 
 def image(W, H, C, dev):
@@ -35,6 +41,7 @@ def main():
     ap.add_argument("--cases", default=",".join(CASES))
     ap.add_argument("--hierarchy", default="galerkin,rescaled", help="comma list of galerkin / rescaled, in the order to run them")
     ap.add_argument("--precision", default="f64", help="comma list of f64 / f32, in the order to run them")
+    ap.add_argument("--channels", default="sequential", help="comma list of sequential / batched, in the order to run them")
     ap.add_argument("--sweeps", type=int, default=2)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--max-iterations", type=int, default=200)
@@ -47,9 +54,14 @@ def main():
     for p in precisions:
         if p not in capi.MG_PRECISIONS:
             ap.error(f"--precision: {p!r} is not one of {sorted(capi.MG_PRECISIONS)}")
+    modes = a.channels.split(",")
+    for m in modes:
+        if m not in capi.MG_CHANNELS:
+            ap.error(f"--channels: {m!r} is not one of {sorted(capi.MG_CHANNELS)}")
+    set_mode = modes != ["sequential"] * len(modes)
     dev = torch.device("cuda", 0)
     for name in a.cases.split(","):
-        W, H, C, kind = CASES[name]
+        W, H, C, kind = {**CASES, **MORE_CASES}[name]
         g = capi.Grid(W, H, C, weighted=kind != "structured")
         f = None
         if kind == "screened":
@@ -66,11 +78,13 @@ def main():
             g.b_from_x()
         g.synchronize()
         # a structured handle has the one hierarchy
-        runs = [(p, h) for p in precisions for h in (kinds if kind != "structured" else ["galerkin"])]
-        for run, (precision, hierarchy) in enumerate(runs):
+        runs = [(m, p, h) for m in modes for p in precisions for h in (kinds if kind != "structured" else ["galerkin"])]
+        for run, (mode, precision, hierarchy) in enumerate(runs):
             if kind != "structured":
                 g.mg_set_hierarchy(hierarchy)
             g.mg_set_precision(precision)
+            if set_mode:
+                g.mg_set_channels(mode)
             t0 = time.perf_counter()
             nl = ctypes.c_int32()                                   # the first MG call of a kind builds its hierarchy
             capi.check(g.L.ccp_grid_mg_level(g.h, 0, ctypes.byref(nl), None, None, None, None, None), "ccp_grid_mg_level")
@@ -93,13 +107,13 @@ def main():
                 _, bb = g.residual_norm2()
                 eps = 1e-10 * float(np.sqrt(bb.max()))
                 reps = g.mg_conjugate_gradient(eps, a.max_iterations, a.sweeps)
-                secs = sum(r.seconds for r in reps)
+                secs = reps[0].seconds if mode == "batched" else sum(r.seconds for r in reps)
                 if best is None or secs < best[0]:
                     best = (secs, [r.iterations for r in reps], [bool(r.converged) for r in reps])
             rr, bb = g.residual_norm2()
             secs, its, conv = best
             updates = sum(i + 1 for i in its)                       # as tools/mg_bench.py counts them
-            print(json.dumps({"case": name, "width": W, "height": H, "channels": C, "kind": kind, "hierarchy": hierarchy, "precision": precision, "run": run,
+            print(json.dumps({"case": name, "width": W, "height": H, "channels": C, "kind": kind, "hierarchy": hierarchy, "precision": precision, "mg_channels": mode, "run": run,
                               "levels": nl.value, "smoothing_sweeps": a.sweeps, "max_iterations": a.max_iterations, "iterations": its, "converged": conv,
                               "ms_to_1e-10": secs * 1e3, "ms_per_pcg_iteration": secs * 1e3 / updates, "setup_ms": setup_ms,
                               "first_apply_ms": first_apply_ms, "apply_ms": apply_ms, "rel_residual": float(np.sqrt(rr / bb).max())}), flush=True)
