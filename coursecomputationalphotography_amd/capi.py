@@ -37,6 +37,18 @@ def mg_channels_value(mode):
     if int(mode) not in MG_CHANNELS.values():
         raise ValueError(f"channels must be one of {sorted(MG_CHANNELS.values())}, not {mode!r}")
     return int(mode)
+MG_SMOOTHERS = {"point": 0, "line": 1}
+
+
+def mg_smoother_value(kind):
+    """The CCP_MG_SMOOTHER_* integer of "point" / "line" (or of an integer of MG_SMOOTHERS): ValueError otherwise."""
+    if isinstance(kind, str):
+        if kind not in MG_SMOOTHERS:
+            raise ValueError(f"smoother must be one of {sorted(MG_SMOOTHERS)}, not {kind!r}")
+        return MG_SMOOTHERS[kind]
+    if int(kind) not in MG_SMOOTHERS.values():
+        raise ValueError(f"smoother must be one of {sorted(MG_SMOOTHERS.values())}, not {kind!r}")
+    return int(kind)
 ORDER_LEXICOGRAPHIC = 0
 ORDER_MULTICOLOUR = 1
 CLONE_IMPORT = 0
@@ -54,6 +66,7 @@ ABI_SYMBOLS = (
     "ccp_grid_mg_conjugate_gradient", "ccp_grid_mg_apply", "ccp_grid_mg_level",
     "ccp_grid_mg_set_hierarchy", "ccp_grid_mg_get_hierarchy", "ccp_grid_mg_set_precision", "ccp_grid_mg_get_precision",
     "ccp_grid_mg_set_channels", "ccp_grid_mg_get_channels", "ccp_debug_mgb_tile_lds",
+    "ccp_grid_mg_set_smoother", "ccp_grid_mg_get_smoother",
     "ccp_grid_residual_norm2", "ccp_grid_abs_sum", "ccp_grid_assemble_rhs", "ccp_grid_assemble_from_images", "ccp_grid_store_u8",
     "ccp_grid_set_x_u8", "ccp_grid_assemble_region_rhs", "ccp_grid_assemble_clone", "ccp_grid_store_u8_composite",
     "ccp_grid_last_timing", "ccp_grid_region_begin", "ccp_grid_region_end",
@@ -205,6 +218,8 @@ def load() -> C.CDLL:
     L.ccp_grid_mg_get_precision.argtypes = [vp, C.POINTER(i32)]
     L.ccp_grid_mg_set_channels.argtypes = [vp, i32]
     L.ccp_grid_mg_get_channels.argtypes = [vp, C.POINTER(i32)]
+    L.ccp_grid_mg_set_smoother.argtypes = [vp, i32]
+    L.ccp_grid_mg_get_smoother.argtypes = [vp, C.POINTER(i32)]
     L.ccp_debug_mgb_tile_lds.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.ccp_csr_apply_to_vector.argtypes = [vp, vp, vp]
     L.ccp_csr_residual_norm2.argtypes = [vp, vp, vp, C.POINTER(dbl), C.POINTER(dbl)]
@@ -739,6 +754,18 @@ class Grid:
         value = C.c_int32()
         check(self.L.ccp_grid_mg_get_channels(self.h, C.byref(value)), "ccp_grid_mg_get_channels")
         return next(name for name, v in MG_CHANNELS.items() if v == value.value)
+
+    def mg_set_smoother(self, kind):
+        """The V-cycle's smoother: "point" (the default: red-black Gauss-Seidel) or "line" (alternating zebra line
+        relaxation on the levels above the tail; weighted handles, fp64, sequential channels: anything else is refused
+        at the solve), or the integers of MG_SMOOTHERS.  With "line" smoothing_sweeps 0 means 1 sweep."""
+        check(self.L.ccp_grid_mg_set_smoother(self.h, mg_smoother_value(kind)), "ccp_grid_mg_set_smoother")
+
+    def mg_smoother(self):
+        """The handle's smoother: "point" or "line"."""
+        value = C.c_int32()
+        check(self.L.ccp_grid_mg_get_smoother(self.h, C.byref(value)), "ccp_grid_mg_get_smoother")
+        return next(name for name, v in MG_SMOOTHERS.items() if v == value.value)
 
     def mg_levels(self):
         """The multigrid hierarchy: one (diag, w_east, w_south) triple of H_k x W_k arrays per level, level 0 first."""

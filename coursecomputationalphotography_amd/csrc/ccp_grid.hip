@@ -149,6 +149,7 @@ struct ccp_grid {
     long w_fixed = 0, w_live = -1, w_edges = 0;
     int mg_kind = CCP_MG_HIERARCHY_GALERKIN;   // ccp_grid_mg_set_hierarchy (weighted handles; survives ccp_grid_set_weights_*)
     int mg_channels = CCP_MG_CHANNELS_SEQUENTIAL;   // ccp_grid_mg_set_channels (survives what mg_precision survives, and set_precision)
+    int mg_smoother = CCP_MG_SMOOTHER_POINT;   // ccp_grid_mg_set_smoother (survives what mg_channels survives, and set_channels)
     int mg_precision = CCP_MG_PRECISION_F64;   // ccp_grid_mg_set_precision (survives set_weights, set_mask and set_hierarchy)
 };
 
@@ -1100,6 +1101,7 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     v->hierarchy_kind = g->mg_kind;
     v->precision = g->mg_precision;
     v->channels_mode = g->mg_channels;
+    v->smoother = g->mg_smoother;
     v->stream = g->stream;
     v->cache = &g->mg;
     v->comm = g->comm;
@@ -1130,6 +1132,14 @@ int ccp::grid_mg_channels_slot(ccp_grid *g, int **mode, MgHierarchy ***cache)
 {
     CCP_TRY(bind(g));
     *mode = &g->mg_channels;
+    *cache = &g->mg;
+    return CCP_OK;
+}
+
+int ccp::grid_mg_smoother_slot(ccp_grid *g, int **kind, MgHierarchy ***cache)
+{
+    CCP_TRY(bind(g));
+    *kind = &g->mg_smoother;
     *cache = &g->mg;
     return CCP_OK;
 }

@@ -3,6 +3,7 @@
 #include "ccp_grid_mg.hpp"
 #include "ccp_grid_mgs.hpp"
 #include "ccp_grid_mgb.hpp"
+#include "ccp_grid_mgl.hpp"
 #include "ccp_comm.hpp"
 
 #include <algorithm>
@@ -57,6 +58,12 @@ struct MgHierarchy {
     DevBuf<double> bt0, bstore, bz, br, bp, bap, bpartial;
     DevBuf<CgState> bstate;
     double *barr(int k, int which) { return bstore.p + bbase[k] + (long)which * bC * size[k]; }   // 0 b, 1 z, 2 t: channel ch at + ch * size[k]
+    // CCP_MG_SMOOTHER_LINE (ccp_grid_mgl.hpp): the smoother of the levels above the tail, taken from the handle at every
+    // call (hierarchy), and the three work planes of the line solves, made at the first line V-cycle (line_planes): each
+    // as long as the largest level above the tail, lwork holds them one after the other.
+    int smoother = CCP_MG_SMOOTHER_POINT;
+    long lplane = 0;
+    DevBuf<double> lwork;
     double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda (lam_slot)
     ~MgHierarchy()
     {
@@ -171,13 +178,15 @@ int hierarchy(const GridMgView &v, MgHierarchy **out)
     }
     if (!*v.cache) CCP_TRY(build(v, v.cache));
     *out = *v.cache;
+    (*out)->smoother = v.smoother;
     return CCP_OK;
 }
 
-int sweeps_arg(int32_t smoothing_sweeps, int *nu)
+// smoothing_sweeps 0: the smoother's default, 2 red-black sweeps or 1 line sweep
+int sweeps_arg(int32_t smoothing_sweeps, int *nu, int smoother = CCP_MG_SMOOTHER_POINT)
 {
     if (smoothing_sweeps < 0 || smoothing_sweeps > 4) return CCP_ERR_BAD_ARG;
-    *nu = smoothing_sweeps == 0 ? 2 : smoothing_sweeps;
+    *nu = smoothing_sweeps == 0 ? (smoother == CCP_MG_SMOOTHER_LINE ? 1 : 2) : smoothing_sweeps;
     return CCP_OK;
 }
 
@@ -220,6 +229,69 @@ void post(int kind, hipStream_t s, const MgLevel &f, const double *b, const doub
     else hipLaunchKernelGGL((k_mg_tile<kMgSolve, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, cs, nu, st);
 }
 
+// ---- CCP_MG_SMOOTHER_LINE (ccp_grid_mgl.hpp) ---------------------------------------------------------------------------
+// What the line mode serves: a weighted handle, the fp64 V-cycle, the sequential channel mode (the row-block calls refuse
+// it in prepare_rowblocked).
+int line_check(const GridMgView &v)
+{
+    if (v.smoother != CCP_MG_SMOOTHER_LINE) return CCP_OK;
+    if (!v.weighted || v.precision != CCP_MG_PRECISION_F64 || v.channels_mode != CCP_MG_CHANNELS_SEQUENTIAL) return CCP_ERR_UNSUPPORTED;
+    return CCP_OK;
+}
+
+// the work planes of the line solves, once per hierarchy
+int line_planes(const GridMgView &v, MgHierarchy &h)
+{
+    if (h.smoother != CCP_MG_SMOOTHER_LINE || h.lwork.p) return CCP_OK;
+    long n = 0;
+    // level 0 is indexed by mg_at(pitch, x, y) < H * 2 * pitch, which is ch_stride on a weighted handle (one block, no ghost rows)
+    for (int k = 0; k < h.tail && k < h.levels; ++k) n = std::max(n, k ? h.size[k] : (long)v.geom.ch_stride);
+    CCP_TRY(h.lwork.alloc((size_t)(3 * n)));                       // (not cleared: a lane reads only what it wrote in the same launch)
+    h.lplane = n;
+    return CCP_OK;
+}
+
+// one half pass: the lines of direction DIR and parity `parity` of level f
+template <int DIR, bool FIRST, bool ADD>
+void lines(MgHierarchy &h, hipStream_t s, const MgLevel &f, const double *b, const double *z_in, double *z_out, const MgLevel &c,
+           const double *ec, double cs, int parity, const CgState *st)
+{
+    const int n = DIR == kMglX ? f.W : f.H, across = DIR == kMglX ? f.H : f.W;
+    const int count = (across - parity + 1) / 2;                   // lines of this parity
+    if (count <= 0) return;
+    const int L = mgl_lanes(DIR, n), per = kBlock / L;
+    double *w = h.lwork.p;
+    hipLaunchKernelGGL((k_mgl_lines<DIR, FIRST, ADD>), dim3((unsigned)((count + per - 1) / per)), dim3(kBlock), 0, s, f, b, z_in, z_out, w,
+                       w + h.lplane, w + 2 * h.lplane, c, ec, cs, parity, L, st);
+}
+
+// nu line sweeps from t = 0, in place: x even (the first one from b alone), x odd, y even, y odd
+void pre_lines(MgHierarchy &h, hipStream_t s, const MgLevel &f, const double *b, double *t, int nu, const CgState *st)
+{
+    const double *none = nullptr;
+    for (int i = 0; i < nu; ++i) {
+        if (i == 0) lines<kMglX, true, false>(h, s, f, b, t, t, f, none, 0.0, 0, st);
+        else lines<kMglX, false, false>(h, s, f, b, t, t, f, none, 0.0, 0, st);
+        lines<kMglX, false, false>(h, s, f, b, t, t, f, none, 0.0, 1, st);
+        lines<kMglY, false, false>(h, s, f, b, t, t, f, none, 0.0, 0, st);
+        lines<kMglY, false, false>(h, s, f, b, t, t, f, none, 0.0, 1, st);
+    }
+}
+
+// z = t + cs e_c, then nu line sweeps in the reverse order: y odd (reads t + cs e_c, writes z), y even, x odd, x even
+void post_lines(MgHierarchy &h, hipStream_t s, const MgLevel &f, const double *b, const double *t, double *z, const MgLevel &c,
+                const double *ec, double cs, int nu, const CgState *st)
+{
+    const double *none = nullptr;
+    for (int i = 0; i < nu; ++i) {
+        if (i == 0) lines<kMglY, false, true>(h, s, f, b, t, z, c, ec, cs, 1, st);
+        else lines<kMglY, false, false>(h, s, f, b, z, z, f, none, 0.0, 1, st);
+        lines<kMglY, false, false>(h, s, f, b, z, z, f, none, 0.0, 0, st);
+        lines<kMglX, false, false>(h, s, f, b, z, z, f, none, 0.0, 1, st);
+        lines<kMglX, false, false>(h, s, f, b, z, z, f, none, 0.0, 0, st);
+    }
+}
+
 // The levels from `from` (held whole) down: tiles above the tail, then k_mg_tail, then back up to `from`.  Every launch
 // is a no-op once st->active is 0 (st may be null).
 int whole_levels(MgHierarchy &h, hipStream_t s, int from, const double *b0, double *z0, int nu, const CgState *st)
@@ -227,8 +299,10 @@ int whole_levels(MgHierarchy &h, hipStream_t s, int from, const double *b0, doub
     auto B = [&](int k) -> const double * { return k ? h.arr(k, 3) : b0; };
     auto Z = [&](int k) -> double * { return k ? h.arr(k, 4) : z0; };
     auto T = [&](int k) -> double * { return k ? h.arr(k, 5) : h.t0.p; };
+    const bool line = h.smoother == CCP_MG_SMOOTHER_LINE;
     for (int k = from; k < h.tail; ++k) {
-        pre(level_kind(h, k), s, h.lv[k], B(k), T(k), nu, st);
+        if (line) pre_lines(h, s, h.lv[k], B(k), T(k), nu, st);
+        else pre(level_kind(h, k), s, h.lv[k], B(k), T(k), nu, st);
         restrict_rows(level_kind(h, k), s, h.lv[k], B(k), T(k), h.lv[k + 1], 0, h.lv[k + 1].H, h.arr(k + 1, 3), st);
     }
     MgTail t{};
@@ -246,7 +320,10 @@ int whole_levels(MgHierarchy &h, hipStream_t s, int from, const double *b0, doub
         off += l.W * l.H;
     }
     hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(kBlock), 0, s, t, B(h.tail), Z(h.tail), h.cs, nu, st);
-    for (int k = h.tail - 1; k >= from; --k) post(level_kind(h, k), s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], h.arr(k + 1, 4), h.cs, nu, st);
+    for (int k = h.tail - 1; k >= from; --k) {
+        if (line) post_lines(h, s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], h.arr(k + 1, 4), h.cs, nu, st);
+        else post(level_kind(h, k), s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], h.arr(k + 1, 4), h.cs, nu, st);
+    }
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 }
@@ -830,6 +907,7 @@ int prepare_rowblocked(ccp_grid *g, int32_t smoothing_sweeps, bool need_nu, Grid
     if (v->weighted) return CCP_ERR_UNSUPPORTED;                   // weighted handles are single blocks
     if (v->precision != CCP_MG_PRECISION_F64) return CCP_ERR_UNSUPPORTED;   // the fp32 V-cycle too (a world-1 communicator on a whole image)
     if (v->channels_mode != CCP_MG_CHANNELS_SEQUENTIAL) return CCP_ERR_UNSUPPORTED;   // ... and the batched mode
+    if (v->smoother != CCP_MG_SMOOTHER_POINT) return CCP_ERR_UNSUPPORTED;   // ... and the line smoother
     if (!v->comm) return CCP_ERR_STATE;
     n->api = rccl_api();
     if (!n->api) return CCP_ERR_RCCL;
@@ -863,12 +941,14 @@ try {
     GridMgView v{};
     CCP_TRY(check_handle(g, &v));
     int nu = 2;
-    CCP_TRY(sweeps_arg(smoothing_sweeps, &nu));
+    CCP_TRY(sweeps_arg(smoothing_sweeps, &nu, v.smoother));
     const bool batched = v.channels_mode == CCP_MG_CHANNELS_BATCHED;
     if (batched && v.precision == CCP_MG_PRECISION_F32) return CCP_ERR_UNSUPPORTED;
+    CCP_TRY(line_check(v));
     MgHierarchy *h = nullptr;
     CCP_TRY(hierarchy(v, &h));
     if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
+    CCP_TRY(line_planes(v, *h));
     const long n = v.geom.ch_stride;
     if (batched) {
         CCP_TRY(batched_levels(v, *h));
@@ -960,6 +1040,31 @@ try {
     return CCP_OK;
 } CCP_ABI_CATCH
 
+int ccp_grid_mg_set_smoother(ccp_grid *g, int32_t kind)
+try {
+    int *slot = nullptr;
+    MgHierarchy **cache = nullptr;
+    CCP_TRY(grid_mg_smoother_slot(g, &slot, &cache));
+    if (kind != CCP_MG_SMOOTHER_POINT && kind != CCP_MG_SMOOTHER_LINE) return CCP_ERR_BAD_ARG;
+    if (*slot == kind) return CCP_OK;
+    *slot = kind;
+    if (*cache) {                                                  // the line solves' work planes go; everything else is shared
+        (*cache)->lwork.release();
+        (*cache)->lplane = 0;
+    }
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_get_smoother(ccp_grid *g, int32_t *kind)
+try {
+    int *slot = nullptr;
+    MgHierarchy **cache = nullptr;
+    CCP_TRY(grid_mg_smoother_slot(g, &slot, &cache));
+    if (!kind) return CCP_ERR_BAD_ARG;
+    *kind = *slot;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
 int ccp_debug_mgb_tile_lds(int32_t level_kind, int32_t smoothing_sweeps, int32_t *bytes, int32_t *threads)
 try {
     if (level_kind < kMgSolve || level_kind > kMgCoarse || smoothing_sweeps < 1 || smoothing_sweeps > 4) return CCP_ERR_BAD_ARG;
@@ -1018,12 +1123,14 @@ try {
     GridMgView v{};
     CCP_TRY(check_handle(g, &v));
     int nu = 2;
-    CCP_TRY(sweeps_arg(smoothing_sweeps, &nu));
+    CCP_TRY(sweeps_arg(smoothing_sweeps, &nu, v.smoother));
     if (max_iteration < 0) return CCP_ERR_BAD_ARG;
     const bool batched = v.channels_mode == CCP_MG_CHANNELS_BATCHED;
     if (batched && v.precision == CCP_MG_PRECISION_F32) return CCP_ERR_UNSUPPORTED;
+    CCP_TRY(line_check(v));
     MgHierarchy *h = nullptr;
     CCP_TRY(hierarchy(v, &h));
+    CCP_TRY(line_planes(v, *h));
     if (batched) return pcg_batched(v, *h, epsilon, max_iteration, nu, report);
     if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
     const Geom &geo = v.geom;

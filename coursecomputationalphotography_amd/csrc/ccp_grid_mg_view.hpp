@@ -23,6 +23,7 @@ struct GridMgView {
     int hierarchy_kind;              // CCP_MG_HIERARCHY_* (ccp_grid_mg_set_hierarchy; GALERKIN unless the handle is weighted)
     int precision;                   // CCP_MG_PRECISION_* (ccp_grid_mg_set_precision)
     int channels_mode;               // CCP_MG_CHANNELS_* (ccp_grid_mg_set_channels)
+    int smoother;                    // CCP_MG_SMOOTHER_* (ccp_grid_mg_set_smoother)
     hipStream_t stream;
     MgHierarchy **cache;             // the handle's cached hierarchy (built on first use, dropped with the mask and the partition)
     // row blocks (ccp_grid_attach_comm): the communicator, every rank's first image row then the image height
@@ -38,6 +39,8 @@ int grid_mg_hierarchy_slot(ccp_grid *g, bool *weighted, int **kind, MgHierarchy 
 int grid_mg_precision_slot(ccp_grid *g, int **precision, MgHierarchy ***cache, bool *row_block);
 // the handle's channel mode (ccp_grid_mg_set_channels / _get_channels)
 int grid_mg_channels_slot(ccp_grid *g, int **mode, MgHierarchy ***cache);
+// the handle's smoother (ccp_grid_mg_set_smoother / _get_smoother)
+int grid_mg_smoother_slot(ccp_grid *g, int **kind, MgHierarchy ***cache);
 void grid_mg_halo_stale(ccp_grid *g);   // after a row-block solve: the next sweep refreshes the ghost rows first
 
 }  // namespace ccp

@@ -132,7 +132,7 @@ def _weight(w, H, W, dev):
 
 
 def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=None, out_dtype=None, epsilon: float = 1e-10,
-                   hierarchy="galerkin", precision="f64", channels="sequential"):
+                   hierarchy="galerkin", precision="f64", channels="sequential", smoother="point"):
     """Minimise  sum wx (u(x+1,y) - u(x,y) - gx)^2 + sum wy (u(x,y+1) - u(x,y) - gy)^2 + sum data_weight (u - f)^2
     for every channel on a weighted grid handle (CCP_GRID_WEIGHTED), by multigrid-preconditioned CG (at most
     `iterations` iterations to sqrt(r'r) < epsilon) from x = f.  gx, gy: float32 H x W x C tensors or None (zero
@@ -143,7 +143,8 @@ def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=Non
     default) or "f32" (capi.Grid.mg_set_precision: the V-cycle in float inside the fp64 loop, the same answer to the same
     epsilon; choose it together with "rescaled", the Galerkin hierarchy pays iterations for it).  channels: "sequential" (the
     default) or "batched" (capi.Grid.mg_set_channels: one PCG loop whose launches serve all channels; every channel gets
-    the same bits; not together with "f32")."""
+    the same bits; not together with "f32").  smoother: "point" (the default) or "line" (capi.Grid.mg_set_smoother:
+    alternating zebra line relaxation, for strongly anisotropic weights; fp64 and sequential channels only)."""
     import torch
     out_dtype = torch.uint8 if out_dtype is None else out_dtype
     ref = next((t for t in (f, gx, gy) if t is not None), None)
@@ -158,6 +159,7 @@ def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=Non
         g.mg_set_hierarchy(hierarchy)
         g.mg_set_precision(precision)
         g.mg_set_channels(channels)
+        g.mg_set_smoother(smoother)
         g.set_weights_tensor(_weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev))
         g.assemble_weighted_rhs_tensor(gx, gy, f, init_x=f is not None)
         if f is None:
@@ -188,29 +190,30 @@ def wls_weights(image, lam: float = 1.0, alpha: float = 1.2, eps: float = 1e-4):
 
 
 def wls_smooth(image, iterations: int, lam: float = 1.0, alpha: float = 1.2, eps: float = 1e-4, epsilon: float = 1e-10,
-               hierarchy="galerkin", precision="f64", channels="sequential"):
+               hierarchy="galerkin", precision="f64", channels="sequential", smoother="point"):
     """WLS edge-preserving smoothing (Farbman et al. 2008): u minimises sum (u - image)^2 + sum wx (du/dx)^2 +
     sum wy (du/dy)^2 with wls_weights (torch ops: plumbing), solved on a weighted grid handle.  image: u8 or float
-    H x W (x C) tensor; returns the same dtype and shape (u8: clamped).  hierarchy, precision, channels: as
+    H x W (x C) tensor; returns the same dtype and shape (u8: clamped).  hierarchy, precision, channels, smoother: as
     weighted_solve's."""
     import torch
     wx, wy = wls_weights(image, lam, alpha, eps)
     f = image if image.dim() == 3 else image.unsqueeze(-1)
     out_dtype = torch.uint8 if image.dtype == torch.uint8 else image.dtype
     u = weighted_solve(None, None, f, iterations, wx=wx, wy=wy, data_weight=1.0, out_dtype=out_dtype, epsilon=epsilon,
-                       hierarchy=hierarchy, precision=precision, channels=channels)
+                       hierarchy=hierarchy, precision=precision, channels=channels, smoother=smoother)
     return u if image.dim() == 3 else u[..., 0]
 
 
 def constrained_solve(gx, gy, f, values, fixed, iterations: int, wx=None, wy=None, data_weight=None, out_dtype=None,
-                      epsilon: float = 1e-10, hierarchy="rescaled", precision="f64", channels="sequential"):
+                      epsilon: float = 1e-10, hierarchy="rescaled", precision="f64", channels="sequential",
+                      smoother="point"):
     """weighted_solve with hard constraints: the pixels where `fixed` (an H x W uint8, bool, float32 or float64 tensor) is
     non-zero keep the value `values` prescribes (u8 / float32 / float64 H x W x C, None: 0) and the energy of
     weighted_solve is minimised over the others; edges that leave the canvas are absent, so the free region may touch
     the canvas border.  The mask stays on the device: it is read by the kernel that forms the operator and never copied
     to the host.  The start vector is f on the free pixels (0 without f).  Returns the composite -- the solution on the
     free pixels, `values` on the fixed ones -- as out_dtype (torch.uint8 by default: clamped).  With data_weight None or
-    0 every connected set of free pixels needs a fixed neighbour, or the system is singular there.  precision, channels: as
+    0 every connected set of free pixels needs a fixed neighbour, or the system is singular there.  precision, channels, smoother: as
     weighted_solve's."""
     import torch
     out_dtype = torch.uint8 if out_dtype is None else out_dtype
@@ -224,6 +227,7 @@ def constrained_solve(gx, gy, f, values, fixed, iterations: int, wx=None, wy=Non
         g.mg_set_hierarchy(hierarchy)
         g.mg_set_precision(precision)
         g.mg_set_channels(channels)
+        g.mg_set_smoother(smoother)
         g.set_weights_tensor(_weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev), fixed=fixed)
         if f is None:
             g.fill_x(0.0)
@@ -254,18 +258,18 @@ def clone_gradients(source, target=None):
 
 
 def seamless_clone_constrained(source, target, mask, iterations: int, mixed: bool = False, data_weight=None, precision="f64",
-                               channels="sequential"):
+                               channels="sequential", smoother="point"):
     """Seamless cloning (Perez et al. 2003) on a weighted handle with fixed pixels: inside `mask` (H x W, non-zero = region)
     the result follows the gradients of the u8 H x W x C tensor `source` (mixed: the stronger of source's and target's),
     outside it is `target`.  Unlike seamless_clone the region may touch the canvas border (no condition is imposed there)
     and the mask stays on the device.  data_weight (a scalar or an H x W tensor) > 0 also pulls the region towards the
     source's colours (screened cloning).  The start vector is the target; multigrid-preconditioned CG, at most
     `iterations` iterations (precision: "f64" or "f32", the V-cycle's: capi.Grid.mg_set_precision; channels: "sequential" or
-    "batched", capi.Grid.mg_set_channels).  Returns the composite,
+    "batched", capi.Grid.mg_set_channels; smoother: "point" or "line", capi.Grid.mg_set_smoother).  Returns the composite,
     a u8 H x W x C tensor."""
     import torch
     if source.dim() == 2:
-        return seamless_clone_constrained(source.unsqueeze(-1), target.unsqueeze(-1), mask, iterations, mixed, data_weight, precision, channels)[..., 0]
+        return seamless_clone_constrained(source.unsqueeze(-1), target.unsqueeze(-1), mask, iterations, mixed, data_weight, precision, channels, smoother)[..., 0]
     dev = _device_index(target)
     H, W, C = target.shape
     gx, gy = clone_gradients(source, target if mixed else None)
@@ -276,6 +280,7 @@ def seamless_clone_constrained(source, target, mask, iterations: int, mixed: boo
         g.mg_set_hierarchy("rescaled")
         g.mg_set_precision(precision)
         g.mg_set_channels(channels)
+        g.mg_set_smoother(smoother)
         g.set_weights_tensor(None, None, _weight(data_weight, H, W, dev), fixed=fixed)
         g.set_x_u8_tensor(target)
         g.assemble_constrained_rhs_tensor(gx, gy, None if data_weight is None else source, target, init_x=False)

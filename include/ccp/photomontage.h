@@ -263,12 +263,16 @@ enum class Precision { Double = CCP_MG_PRECISION_F64, Single = CCP_MG_PRECISION_
 // launches serve all channels; every channel gets the bits of the default, Channels::Sequential.  Not together with
 // Precision::Single: that solve throws.
 enum class Channels { Sequential = CCP_MG_CHANNELS_SEQUENTIAL, Batched = CCP_MG_CHANNELS_BATCHED };
+// smoother: the V-cycle's smoother (ccp_grid_mg_set_smoother).  Smoother::Line is alternating zebra line relaxation, for
+// strongly anisotropic weights (edge-aware smoothing, sparse fixed pixels); the default, Smoother::Point, is red-black
+// Gauss-Seidel.  Not together with Precision::Single or Channels::Batched: that solve throws.
+enum class Smoother { Point = CCP_MG_SMOOTHER_POINT, Line = CCP_MG_SMOOTHER_LINE };
 
 inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageView *f, const ImageView *wx, const ImageView *wy,
                           const ImageView *lambda, ImageView &out, int iterations,
                           Solver solver = Solver::MultigridConjugateGradient, int device = 0,
                           Hierarchy hierarchy = Hierarchy::Galerkin, Precision precision = Precision::Double,
-                          Channels channels = Channels::Sequential)
+                          Channels channels = Channels::Sequential, Smoother smoother = Smoother::Point)
 {
     if (solver != Solver::MultigridConjugateGradient)
         throw std::invalid_argument("SolveWeighted: only Solver::MultigridConjugateGradient solves a weighted system");
@@ -292,6 +296,7 @@ inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageV
     detail::check(ccp_grid_mg_set_hierarchy(h.g, (int32_t)hierarchy), "ccp_grid_mg_set_hierarchy");
     detail::check(ccp_grid_mg_set_precision(h.g, (int32_t)precision), "ccp_grid_mg_set_precision");
     detail::check(ccp_grid_mg_set_channels(h.g, (int32_t)channels), "ccp_grid_mg_set_channels");
+    detail::check(ccp_grid_mg_set_smoother(h.g, (int32_t)smoother), "ccp_grid_mg_set_smoother");
     detail::check(ccp_grid_set_weights_host(h.g, fp(wx), fp(wy), fp(lambda), (int64_t)wstep), "ccp_grid_set_weights_host");
     const int64_t gstep = gx ? (int64_t)gx->step : gy ? (int64_t)gy->step : 0;
     detail::check(ccp_grid_assemble_weighted_rhs(h.g, fp(gx), fp(gy), gstep, fp(f), f ? (int64_t)f->step : 0, f ? 1 : 0),
@@ -309,7 +314,7 @@ inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageV
 inline void SolveConstrained(const ImageView *gx, const ImageView *gy, const ImageView *f, const ImageView *values, const ImageView &fixed,
                              const ImageView *wx, const ImageView *wy, const ImageView *lambda, ImageView &out, int iterations,
                              int device = 0, Hierarchy hierarchy = Hierarchy::Rescaled, Precision precision = Precision::Double,
-                             Channels channels = Channels::Sequential)
+                             Channels channels = Channels::Sequential, Smoother smoother = Smoother::Point)
 {
     const int C = out.channels;
     if (!out.data) throw std::invalid_argument("SolveConstrained: no output image");
@@ -331,6 +336,7 @@ inline void SolveConstrained(const ImageView *gx, const ImageView *gy, const Ima
     detail::check(ccp_grid_mg_set_hierarchy(h.g, (int32_t)hierarchy), "ccp_grid_mg_set_hierarchy");
     detail::check(ccp_grid_mg_set_precision(h.g, (int32_t)precision), "ccp_grid_mg_set_precision");
     detail::check(ccp_grid_mg_set_channels(h.g, (int32_t)channels), "ccp_grid_mg_set_channels");
+    detail::check(ccp_grid_mg_set_smoother(h.g, (int32_t)smoother), "ccp_grid_mg_set_smoother");
     detail::check(ccp_grid_set_weights_constrained_host(h.g, fp(wx), fp(wy), fp(lambda), (int64_t)wstep,
                                                         static_cast<const uint8_t *>(fixed.data), (int64_t)fixed.step),
                   "ccp_grid_set_weights_constrained_host");

@@ -479,6 +479,36 @@ int ccp_grid_mg_get_precision(ccp_grid *g, int32_t *precision);
 #define CCP_MG_CHANNELS_BATCHED    1   /* one PCG loop, every launch serves all channels */
 int ccp_grid_mg_set_channels(ccp_grid *g, int32_t mode);
 int ccp_grid_mg_get_channels(ccp_grid *g, int32_t *mode);
+/* The smoother of the V-cycle of ccp_grid_mg_conjugate_gradient and ccp_grid_mg_apply, per handle.  POINT, the default,
+ * is red-black point Gauss-Seidel on every level, unchanged bit for bit.  LINE is alternating zebra line relaxation for
+ * WEIGHTED handles, whose strongly anisotropic weights (edge-aware smoothing, sparse anchors) a point smoother cannot
+ * smooth: on every level above the single-workgroup tail (the levels with a side > 32, and level 0) one smoothing sweep
+ * is four half passes -- the rows of even y, the rows of odd y, the columns of even x, the columns of odd x -- and
+ * every line is solved exactly, as a tridiagonal system with the other direction's neighbours on the right-hand side.
+ * Pre-smoothing runs the sweeps from z = 0 in that order, post-smoothing in the exact reverse order (columns odd, columns
+ * even, rows odd, rows even) after the coarse correction, so the preconditioner stays symmetric.  The tail levels and a
+ * 1x1 image keep red-black sweeps.  The line systems are diagonally dominant (d = lambda + the four weights, off-
+ * diagonals -w) and are solved without pivoting; a fixed pixel inside a line is the identity row with right-hand side
+ * 0: the line falls apart into independent segments there, z = 0 is written on it and no zero diagonal is divided by.
+ * smoothing_sweeps: the value 0 means the smoother's default, 2 sweeps in POINT mode and 1 sweep in LINE mode; 1 to 4 are
+ * taken as given in both modes.
+ * LINE serves weighted handles with either hierarchy kind, with or without fixed pixels, any channel count, in the
+ * sequential channel mode and fp64.  The setter itself takes either value on every grid handle (a NULL handle or an
+ * unknown value: CCP_ERR_BAD_ARG); what LINE does not serve is refused at the solve or apply with CCP_ERR_UNSUPPORTED,
+ * x and b untouched, whatever order the setters were called in, and the handle works again once the smoother is POINT:
+ *   LINE on a structured handle or on a Dirichlet-mask handle;
+ *   LINE with CCP_MG_PRECISION_F32;
+ *   LINE with CCP_MG_CHANNELS_BATCHED;
+ *   LINE on the _rowblocked multigrid calls (refused before any collective call).
+ * Setting the current value does nothing.  The value survives ccp_grid_set_weights_*, ccp_grid_set_mask_host,
+ * ccp_grid_mg_set_hierarchy, ccp_grid_mg_set_precision and ccp_grid_mg_set_channels.  A change keeps the hierarchy and
+ * the PCG vectors, which both modes share.  Memory: the first LINE V-cycle allocates three work planes of the line
+ * solves, 3 doubles (24 B) per pixel of one channel; going back to POINT frees them. */
+#define CCP_MG_SMOOTHER_POINT 0   /* the default: red-black point Gauss-Seidel */
+#define CCP_MG_SMOOTHER_LINE  1   /* alternating zebra line relaxation (weighted handles) */
+int ccp_grid_mg_set_smoother(ccp_grid *g, int32_t kind);
+int ccp_grid_mg_get_smoother(ccp_grid *g, int32_t *kind);
+
 /* Diagnostic (host only, no device needed): the dynamic LDS in bytes and the workgroup size of a BATCHED tile-pass launch
  * on a level of kind `level_kind` -- 0 structured, 1 Dirichlet mask, 2 stored operator (level 0 of a weighted handle and
  * every coarse level) -- with `smoothing_sweeps` 1..4; anything else: CCP_ERR_BAD_ARG.  Either output may be NULL. */

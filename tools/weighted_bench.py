@@ -14,6 +14,10 @@ batched (capi.Grid.mg_set_channels), the outermost alternation on the same handl
 --hierarchy list.  A batched solve reports the elapsed time of the whole solve in every channel, so its time is one
 report's seconds, not their sum; ms_per_pcg_iteration divides by the updates summed over the channels in both modes (ms
 per channel-iteration).  A list of `sequential` alone never calls the setter, so it also runs on a library without it.
+--smoother: a comma list of point / line (capi.Grid.mg_set_smoother), outermost of all, alternated on the same handle in the
+same way: point,line,point,line,point,line gives three alternations and point against itself as the noise floor; a list
+of `point` alone never calls the setter.  --sweeps 0 (the default) is the smoother's own default: 2 point sweeps, 1 line
+sweep.  With --max-iterations below the count either smoother needs, ms_per_pcg_iteration compares them at equal counts.
 The screened and structured systems are manufactured (b = A x, x uniform
 [0, 255)); the WLS systems smooth a synthetic image of flat patches with edges and noise, built on the device."""
 import argparse, ctypes, json, os, sys, time
@@ -42,7 +46,8 @@ def main():
     ap.add_argument("--hierarchy", default="galerkin,rescaled", help="comma list of galerkin / rescaled, in the order to run them")
     ap.add_argument("--precision", default="f64", help="comma list of f64 / f32, in the order to run them")
     ap.add_argument("--channels", default="sequential", help="comma list of sequential / batched, in the order to run them")
-    ap.add_argument("--sweeps", type=int, default=2)
+    ap.add_argument("--smoother", default="point", help="comma list of point / line, in the order to run them")
+    ap.add_argument("--sweeps", type=int, default=0, help="0: the smoother's default, 2 point sweeps or 1 line sweep")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--max-iterations", type=int, default=200)
     a = ap.parse_args()
@@ -59,6 +64,11 @@ def main():
         if m not in capi.MG_CHANNELS:
             ap.error(f"--channels: {m!r} is not one of {sorted(capi.MG_CHANNELS)}")
     set_mode = modes != ["sequential"] * len(modes)
+    smoothers = a.smoother.split(",")
+    for sm in smoothers:
+        if sm not in capi.MG_SMOOTHERS:
+            ap.error(f"--smoother: {sm!r} is not one of {sorted(capi.MG_SMOOTHERS)}")
+    set_smoother = smoothers != ["point"] * len(smoothers)
     dev = torch.device("cuda", 0)
     for name in a.cases.split(","):
         W, H, C, kind = {**CASES, **MORE_CASES}[name]
@@ -78,8 +88,10 @@ def main():
             g.b_from_x()
         g.synchronize()
         # a structured handle has the one hierarchy
-        runs = [(m, p, h) for m in modes for p in precisions for h in (kinds if kind != "structured" else ["galerkin"])]
-        for run, (mode, precision, hierarchy) in enumerate(runs):
+        runs = [(sm, m, p, h) for sm in smoothers for m in modes for p in precisions for h in (kinds if kind != "structured" else ["galerkin"])]
+        for run, (smoother, mode, precision, hierarchy) in enumerate(runs):
+            if set_smoother:
+                g.mg_set_smoother(smoother)
             if kind != "structured":
                 g.mg_set_hierarchy(hierarchy)
             g.mg_set_precision(precision)
@@ -113,8 +125,8 @@ def main():
             rr, bb = g.residual_norm2()
             secs, its, conv = best
             updates = sum(i + 1 for i in its)                       # as tools/mg_bench.py counts them
-            print(json.dumps({"case": name, "width": W, "height": H, "channels": C, "kind": kind, "hierarchy": hierarchy, "precision": precision, "mg_channels": mode, "run": run,
-                              "levels": nl.value, "smoothing_sweeps": a.sweeps, "max_iterations": a.max_iterations, "iterations": its, "converged": conv,
+            print(json.dumps({"case": name, "width": W, "height": H, "channels": C, "kind": kind, "hierarchy": hierarchy, "precision": precision, "mg_channels": mode, "smoother": smoother, "run": run,
+                              "levels": nl.value, "smoothing_sweeps": a.sweeps or (1 if smoother == "line" else 2), "max_iterations": a.max_iterations, "iterations": its, "converged": conv,
                               "ms_to_1e-10": secs * 1e3, "ms_per_pcg_iteration": secs * 1e3 / updates, "setup_ms": setup_ms,
                               "first_apply_ms": first_apply_ms, "apply_ms": apply_ms, "rel_residual": float(np.sqrt(rr / bb).max())}), flush=True)
         g.close()
