@@ -10,7 +10,9 @@ and 2.0e-12.  Measured on an MI355X: the device is 5.5e-15 to 1.05e-13 from the 
 deviation, on every shape, nu and hierarchy kind; the PCG counts equal the model's (42, 42, 42; 56; 43).
 
 Shapes: 67x3 (chunk remainder), 1x40 and 40x1 (lines of length 1 in one direction), 257x131 (odd sizes, three line
-levels), 2053x9 and 9x2053 (a line longer than one wave's worth of chunks in either direction), 512x384, and 257x131
+levels), 2053x9 and 9x2053 (a line longer than one wave's worth of chunks in either direction), 4099x3 and 8200x2 (rows
+beyond 4096 cells: 256 lanes with 17 and 33 cells each, longer than kMglChunk, a short last chunk; the model's deviation
+there is 6.9e-14 to 8.0e-14 and 3.6e-14 to 5.6e-14, the device 2.3e-14 to 7.1e-14 from the model), 512x384, and 257x131
 with fixed pixels (an ellipse's outside, a whole fixed row, a whole fixed column, isolated fixed pixels inside lines).
 Weights are the WLS weights of the seeded numpy image, uploaded as the float32 arrays the model reads."""
 import functools
@@ -29,7 +31,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 BAD_ARG, UNSUPPORTED = 1, 6
 SHAPES = [(67, 3, False), (1, 40, False), (40, 1, False), (257, 131, False), (2053, 9, False), (9, 2053, False), (512, 384, False),
-          (257, 131, True)]
+          (257, 131, True), (4099, 3, False), (8200, 2, False)]
 FACTOR = 16.0
 
 

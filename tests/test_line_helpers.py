@@ -19,7 +19,7 @@ import weighted_helpers as wh
 
 # (case) -> the line model's iteration count, nu = 1, rescaled hierarchy
 COUNTS = {"wls_188x142": 42, "wls_376x283": 56, "anchors32_188x142": 87, "anchors16_188x142": 43}
-GPU_SHAPES = [(67, 3), (1, 40), (40, 1), (257, 131), (2053, 9), (9, 2053), (512, 384)]
+GPU_SHAPES = [(67, 3), (1, 40), (40, 1), (257, 131), (2053, 9), (9, 2053), (512, 384), (4099, 3), (8200, 2)]
 
 
 @functools.lru_cache(maxsize=None)
