@@ -76,6 +76,7 @@ ABI_SYMBOLS = (
     "ccp_grid_set_weights_host", "ccp_grid_set_weights_device", "ccp_grid_assemble_weighted_rhs", "ccp_grid_assemble_weighted_rhs_device",
     "ccp_grid_set_weights_constrained_host", "ccp_grid_set_weights_constrained_device", "ccp_grid_assemble_constrained_rhs",
     "ccp_grid_assemble_constrained_rhs_device", "ccp_grid_constraint_info",
+    "ccp_grid_adjoint_begin_device", "ccp_grid_weighted_adjoint_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
     "ccp_grid_attach_comm", "ccp_grid_set_overlap", "ccp_grid_exchange_halos", "ccp_grid_sweep_rowblocked",
     "ccp_grid_gauss_seidel_rowblocked", "ccp_grid_conjugate_gradient_rowblocked", "ccp_grid_residual_norm2_global", "ccp_grid_comm_stats",
@@ -113,6 +114,20 @@ class DeviceArray(C.Structure):
     """ccp_device_array: a strided view of device memory, strides in elements."""
     _fields_ = [("data", C.c_void_p), ("dtype", C.c_int32), ("reserved", C.c_int32),
                 ("stride_n", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("stride_c", C.c_int64)]
+
+
+ADJOINT_INPUTS = ("u", "grad_x", "gx", "gy", "f", "wx", "wy", "lambda", "fixed")
+ADJOINT_OUTPUTS = ("g_wx", "g_wy", "g_lambda", "g_gx", "g_gy", "g_f", "g_values")
+
+
+class AdjointInputs(C.Structure):
+    """ccp_adjoint_inputs: one ccp_device_array pointer per input of the gradient pass (NULL: absent)."""
+    _fields_ = [(n, C.POINTER(DeviceArray)) for n in ADJOINT_INPUTS]
+
+
+class AdjointOutputs(C.Structure):
+    """ccp_adjoint_outputs: one ccp_device_array pointer per gradient (NULL: not asked for)."""
+    _fields_ = [(n, C.POINTER(DeviceArray)) for n in ADJOINT_OUTPUTS]
 
 
 _lib: Optional[C.CDLL] = None
@@ -273,6 +288,8 @@ def load() -> C.CDLL:
     L.ccp_grid_assemble_constrained_rhs.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i32]
     L.ccp_grid_assemble_constrained_rhs_device.argtypes = [vp, da, da, da, da, i32]
     L.ccp_grid_constraint_info.argtypes = [vp, vp, vp, vp]
+    L.ccp_grid_adjoint_begin_device.argtypes = [vp, da]
+    L.ccp_grid_weighted_adjoint_device.argtypes = [vp, C.POINTER(AdjointInputs), C.POINTER(AdjointOutputs)]
     L.ccp_grid_last_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i32)]
     L.ccp_grid_region_begin.argtypes = [vp]
     L.ccp_grid_region_end.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i64), C.POINTER(i64)]
@@ -1087,6 +1104,17 @@ class Grid:
         sy, sx = t.stride()
         return DeviceArray(t.data_ptr(), DTYPE_F64 if t.dtype == torch.float64 else DTYPE_F32, 0, 0, sy, sx, 0)
 
+    def _mask_array(self, fixed):
+        """ccp_device_array of an H x W uint8, bool, float32 or float64 mask tensor."""
+        torch = self._torch()
+        if isinstance(fixed, torch.Tensor) and fixed.dtype == torch.bool:
+            fixed = fixed.view(torch.uint8)
+        if isinstance(fixed, torch.Tensor) and fixed.dtype == torch.uint8:
+            if tuple(fixed.shape) != (self.H, self.W):
+                raise ValueError(f"fixed must be {self.H} x {self.W}, not {tuple(fixed.shape)}")
+            return DeviceArray(*self._label_array(fixed.unsqueeze(-1)))
+        return self._weight_array(fixed, "fixed")
+
     def set_weights_tensor(self, wx=None, wy=None, lam=None, fixed=None):
         """set_weights from H x W float32 / float64 tensors (expanded scalars broadcast); synchronises (the verdict).
         fixed: an H x W uint8, bool, float32 or float64 tensor (!= 0: fixed), read on the device; None: no fixed pixels."""
@@ -1095,15 +1123,7 @@ class Grid:
         if fixed is None:
             self._on_stream(lambda: self.L.ccp_grid_set_weights_device(self.h, *refs), "ccp_grid_set_weights_device")
             return
-        torch = self._torch()
-        if isinstance(fixed, torch.Tensor) and fixed.dtype == torch.bool:
-            fixed = fixed.view(torch.uint8)
-        if isinstance(fixed, torch.Tensor) and fixed.dtype == torch.uint8:
-            if tuple(fixed.shape) != (self.H, self.W):
-                raise ValueError(f"fixed must be {self.H} x {self.W}, not {tuple(fixed.shape)}")
-            m = DeviceArray(*self._label_array(fixed.unsqueeze(-1)))
-        else:
-            m = self._weight_array(fixed, "fixed")
+        m = self._mask_array(fixed)
         self._on_stream(lambda: self.L.ccp_grid_set_weights_constrained_device(self.h, *refs, C.byref(m)),
                         "ccp_grid_set_weights_constrained_device")
 
@@ -1128,6 +1148,61 @@ class Grid:
         refs = [None if v is None else C.byref(v) for v in (a, b, c)]
         self._on_stream(lambda: self.L.ccp_grid_assemble_weighted_rhs_device(self.h, *refs, 1 if init_x else 0),
                         "ccp_grid_assemble_weighted_rhs_device")
+
+    # ---- the backward pass of a weighted solve (ccp_gs.h, "Differentiating a weighted solve") ---------------------
+    def adjoint_begin_tensor(self, grad):
+        """Load the adjoint right-hand side: b := grad (float32 / float64 H x W x channels, dL/du) on free live pixels and
+        0 on fixed and dead ones, x := 0.  mg_conjugate_gradient then leaves the adjoint solution v in x."""
+        torch = self._torch()
+        arr, _ = self._hwc(grad, "grad", (torch.float32, torch.float64))
+        self._on_stream(lambda: self.L.ccp_grid_adjoint_begin_device(self.h, C.byref(arr)), "ccp_grid_adjoint_begin_device")
+
+    def _plane_out(self, t, name):
+        """ccp_device_array of an H x W float32 / float64 output tensor."""
+        arr = self._weight_array(t, name)
+        if not _no_overlap(t.shape, t.stride()):
+            raise ValueError(f"{name} is an output whose elements overlap")
+        return arr
+
+    def weighted_adjoint_tensor(self, u, grad=None, gx=None, gy=None, f=None, wx=None, wy=None, lam=None, fixed=None,
+                                want=("wx", "wy", "lam", "gx", "gy", "f", "values"), out=None, dtype=None):
+        """The gradients of a weighted solve in one pass, from the forward composite `u` (float64 H x W x channels), the
+        adjoint solution in the handle's x, and the inputs of the forward solve as they were installed (gx, gy, f as
+        assemble_constrained_rhs_tensor takes them; wx, wy, lam, fixed as set_weights_tensor takes them).  want: which
+        gradients to compute, of "wx", "wy", "lam" (H x W) and "gx", "gy", "f", "values" (H x W x channels); "values"
+        needs `grad` (dL/du).  Only those are computed, and only the inputs they need are read.  Returns {name: tensor};
+        a tensor given in `out` ({name: tensor}, float32 or float64, any non-overlapping view) is filled, the others are
+        allocated as `dtype` (float64 by default)."""
+        torch = self._torch()
+        want = tuple(want)
+        planes, images = ("wx", "wy", "lam"), ("gx", "gy", "f", "values")
+        unknown = [n for n in want if n not in planes + images] + [n for n in (out or {}) if n not in want]
+        if unknown:
+            raise ValueError(f"unknown or unrequested gradients: {unknown}")
+        if "values" in want and grad is None:
+            raise ValueError("the gradient of values needs grad")
+        floats, any_ = (torch.float32, torch.float64), (torch.uint8, torch.float32, torch.float64)
+        ins = {"u": self._hwc(u, "u", (torch.float64,))[0],
+               "grad_x": None if grad is None else self._hwc(grad, "grad", floats)[0],
+               "gx": None if gx is None else self._hwc(gx, "gx", (torch.float32,))[0],
+               "gy": None if gy is None else self._hwc(gy, "gy", (torch.float32,))[0],
+               "f": None if f is None else self._hwc(f, "f", any_)[0],
+               "wx": self._weight_array(wx, "wx"), "wy": self._weight_array(wy, "wy"), "lambda": self._weight_array(lam, "lam"),
+               "fixed": None if fixed is None else self._mask_array(fixed)}
+        result, outs = {}, {}
+        for n in want:
+            t = (out or {}).get(n)
+            if t is None:
+                shape = (self.H, self.W) if n in planes else (self.H, self.W, self.C)
+                with torch.cuda.device(self._device()):
+                    t = torch.empty(shape, dtype=dtype or torch.float64, device=self._device())
+            outs["g_lambda" if n == "lam" else "g_" + n] = self._plane_out(t, n) if n in planes else self._hwc(t, n, floats, output=True)[0]
+            result[n] = t
+        a = AdjointInputs(*[None if ins[n] is None else C.pointer(ins[n]) for n in ADJOINT_INPUTS])
+        b = AdjointOutputs(*[None if outs.get(n) is None else C.pointer(outs[n]) for n in ADJOINT_OUTPUTS])
+        self._on_stream(lambda: self.L.ccp_grid_weighted_adjoint_device(self.h, C.byref(a), C.byref(b)),
+                        "ccp_grid_weighted_adjoint_device")
+        return result
 
     def region_begin(self):
         check(self.L.ccp_grid_region_begin(self.h), "ccp_grid_region_begin")

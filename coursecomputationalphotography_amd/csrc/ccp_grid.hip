@@ -8,6 +8,7 @@
 #include "ccp_grid_mg_view.hpp"
 #include "ccp_grid_blend.hpp"
 #include "ccp_grid_weighted.hpp"
+#include "ccp_grid_adjoint.hpp"
 #include "ccp_comm.hpp"
 
 #include <algorithm>
@@ -3459,6 +3460,93 @@ try {
     if (free_live_pixels) *free_live_pixels = g->w_live;
     if (boundary_edges) *boundary_edges = g->w_edges;
     return CCP_OK;
+} CCP_ABI_CATCH
+
+}  // extern "C"
+
+// ============================================================================================
+// The backward pass of a weighted solve (include/ccp_gs.h, "Differentiating a weighted solve"; kernels: ccp_grid_adjoint.hpp)
+// ============================================================================================
+namespace {
+
+AdjIn adj_in(const ccp_device_array *a)
+{
+    if (!a) return AdjIn{nullptr, 0, 0, 0, 0};
+    return AdjIn{a->data, (long)a->stride_y, (long)a->stride_x, (long)a->stride_c, a->dtype};
+}
+
+AdjOut adj_out(const ccp_device_array *a)
+{
+    if (!a) return AdjOut{nullptr, 0, 0, 0, 0};
+    return AdjOut{const_cast<void *>(a->data), (long)a->stride_y, (long)a->stride_x, (long)a->stride_c, a->dtype};
+}
+
+}  // namespace
+
+extern "C" {
+
+int ccp_grid_adjoint_begin_device(ccp_grid *g, const ccp_device_array *grad_x)
+try {
+    CCP_TRY(weighted_handle(g));
+    const Geom &geo = g->geom;
+    CCP_TRY(check_view(g, grad_x, kF32F64, false, 1, geo.H, geo.W, g->desc.channels));
+    if (!g->has_op) return CCP_ERR_STATE;
+    hipLaunchKernelGGL(k_adjoint_begin, pixel_grid(g, geo.H), dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->wop.p, geo.pitch, geo.ch_stride,
+                       geo.W, g->desc.channels, adj_in(grad_x));
+    CCP_HIP(hipGetLastError());
+    return edge_timeout_status(g);
+} CCP_ABI_CATCH
+
+int ccp_grid_weighted_adjoint_device(ccp_grid *g, const ccp_adjoint_inputs *in, const ccp_adjoint_outputs *out)
+try {
+    CCP_TRY(weighted_handle(g));
+    if (!in || !out) return CCP_ERR_BAD_ARG;
+    const Geom &geo = g->geom;
+    const int W = geo.W, H = geo.H, C = g->desc.channels;
+    CCP_TRY(check_view(g, in->u, 1u << CCP_DTYPE_F64, false, 1, H, W, C));
+    if (in->grad_x || out->g_values) CCP_TRY(check_view(g, in->grad_x, kF32F64, false, 1, H, W, C));
+    if (in->gx) CCP_TRY(check_view(g, in->gx, kF32, false, 1, H, W, C));
+    if (in->gy) CCP_TRY(check_view(g, in->gy, kF32, false, 1, H, W, C));
+    if (in->f) CCP_TRY(check_view(g, in->f, kF32F64 | kU8, false, 1, H, W, C));
+    if (in->wx) CCP_TRY(check_view(g, in->wx, kF32F64, false, 1, H, W, 1));
+    if (in->wy) CCP_TRY(check_view(g, in->wy, kF32F64, false, 1, H, W, 1));
+    if (in->lambda) CCP_TRY(check_view(g, in->lambda, kF32F64, false, 1, H, W, 1));
+    if (in->fixed) CCP_TRY(check_view(g, in->fixed, kF32F64 | kU8, false, 1, H, W, 1));
+    const ccp_device_array *planes[3] = {out->g_wx, out->g_wy, out->g_lambda};
+    const ccp_device_array *images[4] = {out->g_gx, out->g_gy, out->g_f, out->g_values};
+    for (const ccp_device_array *a : planes)
+        if (a) CCP_TRY(check_view(g, a, kF32F64, true, 1, H, W, 1));
+    for (const ccp_device_array *a : images)
+        if (a) CCP_TRY(check_view(g, a, kF32F64, true, 1, H, W, C));
+    if (!g->has_op) return CCP_ERR_STATE;
+    AdjointArgs a{};
+    a.v = g->x.p;
+    a.pitch = geo.pitch;
+    a.ch_stride = geo.ch_stride;
+    a.W = W;
+    a.H = H;
+    a.C = C;
+    a.u = adj_in(in->u);
+    a.grad = adj_in(in->grad_x);
+    a.gx = adj_in(in->gx);
+    a.gy = adj_in(in->gy);
+    a.f = adj_in(in->f);
+    a.wx = adj_in(in->wx);
+    a.wy = adj_in(in->wy);
+    a.lam = adj_in(in->lambda);
+    a.fixed = adj_in(in->fixed);
+    a.wx.sc = a.wy.sc = a.lam.sc = a.fixed.sc = 0;         // H x W: stride_c unused
+    a.g_wx = adj_out(out->g_wx);
+    a.g_wy = adj_out(out->g_wy);
+    a.g_lam = adj_out(out->g_lambda);
+    a.g_wx.sc = a.g_wy.sc = a.g_lam.sc = 0;
+    a.g_gx = adj_out(out->g_gx);
+    a.g_gy = adj_out(out->g_gy);
+    a.g_f = adj_out(out->g_f);
+    a.g_val = adj_out(out->g_values);
+    hipLaunchKernelGGL(k_weighted_adjoint, pixel_grid(g, H), dim3(kBlock), 0, g->stream, a);
+    CCP_HIP(hipGetLastError());
+    return edge_timeout_status(g);
 } CCP_ABI_CATCH
 
 }  // extern "C"

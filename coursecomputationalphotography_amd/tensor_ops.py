@@ -288,3 +288,129 @@ def seamless_clone_constrained(source, target, mask, iterations: int, mixed: boo
         return g.store_u8_tensor()
     finally:
         g.close()
+
+
+# ---- differentiable weighted solves -----------------------------------------------------------------------------------
+_GRAD_INPUTS = ("gx", "gy", "f", "wx", "wy", "lam", "values")
+
+
+def _converged(reports, what, strict):
+    if strict and not all(r.converged for r in reports):
+        its = [int(r.iterations) for r in reports]
+        raise RuntimeError(f"weighted_solve_grad: the {what} solve did not converge (iterations per channel {its}); the "
+                           "gradient of an unconverged solve is not the gradient: raise `iterations`, loosen `epsilon`, or pass strict=False")
+
+
+def _solve_function():
+    """The torch.autograd.Function behind weighted_solve_grad (built on first use: torch is imported lazily here)."""
+    global _WeightedSolve
+    if _WeightedSolve is not None:
+        return _WeightedSolve
+    import weakref
+
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class WeightedSolve(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, gx, gy, f, wx, wy, lam, values, fixed, cfg):
+            ref = next(t for t in (values, f, gx, gy) if t is not None)
+            dev = _device_index(ref)
+            H, W = ref.shape[0], ref.shape[1]
+            C = ref.shape[2] if ref.dim() == 3 else 1
+            g = capi.Grid(W, H, C, device=dev, weighted=True)
+            try:
+                g.set_stream(torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream)
+                g.mg_set_hierarchy(cfg["hierarchy"])
+                g.mg_set_precision(cfg["precision"])
+                g.mg_set_channels(cfg["channels"])
+                g.mg_set_smoother(cfg["smoother"])
+                g.set_weights_tensor(wx, wy, lam, fixed=fixed)
+                if f is None:
+                    g.fill_x(0.0)
+                g.assemble_constrained_rhs_tensor(gx, gy, f, values, init_x=f is not None)
+                _converged(g.mg_conjugate_gradient(cfg["epsilon"], cfg["iterations"], 2), "forward", cfg["strict"])
+                u = g.get_x_tensor()
+            except BaseException:
+                g.close()
+                raise
+            # The handle lives as long as autograd keeps this node's saved tensors: `token` is saved with them, and
+            # its finaliser closes the handle when they are released -- after a backward without retain_graph, or when
+            # the graph is dropped without a backward.
+            token = torch.empty(0, device=u.device)
+            weakref.finalize(token, g.close)
+            ctx.grid, ctx.cfg = g, cfg
+            ctx.present = [t is not None for t in (gx, gy, f, wx, wy, lam, values, fixed)]
+            ctx.save_for_backward(*[t for t in (gx, gy, f, wx, wy, lam, values, fixed) if t is not None], u, token)
+            return u if ref.dim() == 3 else u[..., 0]
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad):
+            saved = list(ctx.saved_tensors)
+            u = saved[-2]
+            it = iter(saved[:-2])
+            gx, gy, f, wx, wy, lam, values, fixed = [next(it) if p else None for p in ctx.present]
+            g, cfg = ctx.grid, ctx.cfg
+            want = tuple(n for n, need in zip(_GRAD_INPUTS, ctx.needs_input_grad[:7]) if need)
+            grad = grad.reshape(u.shape)
+            if grad.dtype not in (torch.float32, torch.float64):
+                grad = grad.to(torch.float64)
+            g.set_stream(torch.cuda.current_stream(u.device).cuda_stream)
+            g.adjoint_begin_tensor(grad)
+            _converged(g.mg_conjugate_gradient(cfg["epsilon"], cfg["iterations"], 2), "adjoint", cfg["strict"])
+            inputs = dict(gx=gx, gy=gy, f=f, wx=wx, wy=wy, lam=lam, values=values)
+            out = {}
+            for n in want:                                 # each gradient in its input's dtype and shape
+                t = inputs[n]
+                out[n] = torch.empty(t.shape, dtype=t.dtype, device=t.device)
+            got = g.weighted_adjoint_tensor(u, grad if "values" in want else None, gx, gy, f, wx, wy, lam, fixed, want=want, out=out)
+            return tuple(got.get(n) for n in _GRAD_INPUTS) + (None, None)
+
+    _WeightedSolve = WeightedSolve
+    return WeightedSolve
+
+
+_WeightedSolve = None
+
+
+def weighted_solve_grad(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=None, values=None, fixed=None,
+                        epsilon: float = 1e-10, hierarchy="rescaled", precision="f64", channels="sequential", smoother="point",
+                        strict: bool = True):
+    """weighted_solve / constrained_solve as a differentiable torch function: returns x, a float64 H x W x C tensor (the
+    composite: the minimiser on the free pixels, `values` on the fixed ones) with a grad_fn, so that a loss of x can be
+    differentiated with respect to gx, gy, f, wx, wy, data_weight and values.  Inputs as constrained_solve's (`fixed` None:
+    no fixed pixels); wx, wy, data_weight may also be python scalars (no gradient) or 0-dim tensors, which are expanded to
+    H x W here, outside the autograd function, so that torch sums their gradient to a scalar.  u8 inputs get no gradient.
+
+    Backward.  The operator is symmetric, so the backward pass is one more multigrid PCG on the same handle -- same
+    hierarchy, precision, channel mode and smoother, the same epsilon and iteration cap -- with dL/dx as the right-hand
+    side (v: A v = dL/dx on the free pixels, 0 on fixed ones), then one kernel pass for all channels that forms only the
+    gradients autograd asks for (s_x = v(x+1,y) - v(x,y), r_x = gx - (x(x+1,y) - x(x,y)), likewise to the south):
+        d/dwx = sum_c s_x r_x    d/dgx = wx s_x    d/ddata_weight = sum_c v (f - x)   (0 at fixed pixels)
+        d/dwy = sum_c s_y r_y    d/dgy = wy s_y    d/df = data_weight v               (0 at fixed pixels)
+        d/dvalues = dL/dx + the four-neighbour sum of w v at fixed pixels, 0 at free pixels
+    each returned in its input's dtype.  The operator is never formed again.  Backward is once-differentiable.
+
+    Memory.  The grid handle -- x, b, the operator planes, the multigrid hierarchy and the PCG vectors, about what the
+    forward solve itself held -- and x stay in device memory until backward has run (with retain_graph=True: until the
+    graph is dropped); it is released as soon as autograd releases the node's saved tensors.  Under torch.no_grad(), or
+    when no input requires a gradient, use weighted_solve / constrained_solve, which release it at once.
+
+    strict (the default): a forward or adjoint solve that does not report `converged` within `iterations` raises
+    RuntimeError -- these are the gradients of the converged solution, and an unconverged solve's are not them."""
+    import torch
+    ref = next((t for t in (values, f, gx, gy) if t is not None), None)
+    if ref is None:
+        raise ValueError("weighted_solve_grad needs at least one of gx, gy, f, values")
+    dev = _device_index(ref)
+    H, W = ref.shape[0], ref.shape[1]
+
+    def plane(w):
+        if isinstance(w, torch.Tensor) and w.dim() == 0:
+            return w.expand(H, W)
+        return _weight(w, H, W, dev)
+
+    cfg = dict(iterations=int(iterations), epsilon=float(epsilon), hierarchy=hierarchy, precision=precision, channels=channels,
+               smoother=smoother, strict=bool(strict))
+    return _solve_function().apply(gx, gy, f, plane(wx), plane(wy), plane(data_weight), values, fixed, cfg)

@@ -792,6 +792,57 @@ int ccp_grid_assemble_constrained_rhs_device(ccp_grid *g, const ccp_device_array
  * and a read-back).  Not a weighted handle: CCP_ERR_UNSUPPORTED; no operator: CCP_ERR_STATE. */
 int ccp_grid_constraint_info(ccp_grid *g, int64_t *fixed_pixels, int64_t *free_live_pixels, int64_t *boundary_edges);
 
+/* ---- Differentiating a weighted solve: the adjoint right-hand side and the gradient pass ---------------------------------
+ * Let u be the composite a converged solve on a weighted handle returns (the minimiser of E on the free pixels, `values`
+ * on the fixed ones), L a scalar function of u and G = dL/du (H x W x channels).  The operator is symmetric, so the
+ * backward pass is one more solve on the SAME handle -- the same hierarchy, precision, channel mode and smoother: v solves
+ * A_FF v_F = G_F on the free pixels, v = 0 on fixed and dead pixels.  With, per channel,
+ *     s_x = v(x+1,y) - v(x,y),  r_x = gx(x,y) - (u(x+1,y) - u(x,y))      and s_y, r_y likewise to the south,
+ * the gradients with respect to every input of the solve are
+ *     dL/dwx(x,y) = sum_c s_x r_x        dL/dgx = wx s_x        dL/dlambda = sum_c v (f - u)   at free pixels, 0 at fixed
+ *     dL/dwy(x,y) = sum_c s_y r_y        dL/dgy = wy s_y        dL/df      = lambda v          at free pixels, 0 at fixed
+ *     dL/dvalues  = G + wN vN + wW vW + wE vE + wS vS  at a fixed pixel (absent edges skipped, the ORIGINAL edge weights),
+ *                   0 at free pixels
+ * and the edge formulas hold unchanged on edges with one or two fixed ends, because v is 0 there.  These are the
+ * gradients of a CONVERGED solve: run both solves to a tight epsilon.
+ *
+ * Both calls follow the conventions of the _device calls above: enqueued on the handle's stream, no allocation, no host
+ * synchronisation, views checked as there (an output view whose elements overlap, a wrong dtype, memory that is not the
+ * handle's device's: CCP_ERR_BAD_ARG before anything is enqueued).  Not a weighted handle: CCP_ERR_UNSUPPORTED; no
+ * operator: CCP_ERR_STATE.
+ *
+ * ccp_grid_adjoint_begin_device: grad_x is G, F32 or F64, H x W x channels.  One launch for all channels: b := G
+ * (widened exactly) on free live pixels, b := +0.0 on fixed and dead pixels, x := +0.0 on every pixel.  A following
+ * ccp_grid_mg_conjugate_gradient leaves v in x.  The forward solution is overwritten: read it out first. */
+int ccp_grid_adjoint_begin_device(ccp_grid *g, const ccp_device_array *grad_x);
+
+/* ccp_grid_weighted_adjoint_device: the gradients from u, the handle's x (= v, read as +0.0 at a fixed pixel whatever it
+ * holds there) and the inputs of the forward solve, in ONE pass for all channels.
+ * in:  u       F64 H x W x channels, the forward composite (required);
+ *      grad_x  F32 or F64, G: required when out->g_values is asked for, unused otherwise (may be NULL);
+ *      gx, gy  F32 H x W x channels (NULL: 0);   f  U8, F32 or F64 (NULL: 0);
+ *      wx, wy, lambda, fixed: H x W, exactly the meaning, dtypes and NULL defaults of
+ *              ccp_grid_set_weights_constrained_device.  The caller passes what it installed: the weights are not
+ *              validated again, and the mask comes in again because the handle's stored planes cannot tell a fixed pixel
+ *              from a dead free one.
+ * out: g_wx, g_wy, g_lambda (H x W, stride_c unused) and g_gx, g_gy, g_f, g_values (H x W x channels), each F32 or F64,
+ *      any of them NULL: not computed, and inputs only it needs are not read.  Every element of a given output is
+ *      written.  in, out NULL: CCP_ERR_BAD_ARG.
+ * Operation order, fp64 with inputs widened exactly and no fused multiply-add; one thread per pixel (x,y):
+ *     east edge (x + 1 < W), per channel in channel order:  s = vE - v;  r = gx - (uE - u);  g_gx = w * s;  acc += s * r
+ *          with w = wx(x,y) and acc starting at +0.0;  g_wx = acc.  South edge (y + 1 < H) likewise with vS, uS, gy, wy.
+ *     free pixel, per channel:   g_f = lambda * v;  accl += v * (f - u)  (accl from +0.0);  g_lambda = accl.
+ *     fixed pixel, per channel:  t = G; t += wN*vN; t += wW*vW; t += wE*vE; t += wS*vS  (absent edges skipped);  g_values = t.
+ * The last column of g_wx and g_gx, the last row of g_wy and g_gy, g_f and g_lambda at fixed pixels and g_values at free
+ * pixels are written +0.0.  An F32 output is the fp64 value rounded to nearest once. */
+typedef struct ccp_adjoint_inputs {
+    const ccp_device_array *u, *grad_x, *gx, *gy, *f, *wx, *wy, *lambda, *fixed;
+} ccp_adjoint_inputs;
+typedef struct ccp_adjoint_outputs {
+    const ccp_device_array *g_wx, *g_wy, *g_lambda, *g_gx, *g_gy, *g_f, *g_values;
+} ccp_adjoint_outputs;
+int ccp_grid_weighted_adjoint_device(ccp_grid *g, const ccp_adjoint_inputs *in, const ccp_adjoint_outputs *out);
+
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
 int ccp_grid_last_timing(ccp_grid *g, float *milliseconds, int32_t *kernel_launches);
