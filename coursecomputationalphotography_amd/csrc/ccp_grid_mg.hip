@@ -9,14 +9,46 @@
 #include <algorithm>
 #include <atomic>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 using namespace ccp;
 
 namespace ccp {
 
+// The work set of a PCG over C channels: z, r, p, ap (C x n doubles each, zero-filled), C slices of `ps` partial sums
+// and CgState[C].
+struct PcgWork {
+    DevBuf<double> z, r, p, ap, partial;
+    DevBuf<CgState> state;
+    long ps = 0;                     // partial sums per channel
+    // What is not there yet: the vectors; with partial_per_channel > 0 the partial sums and the states too (a V-cycle
+    // on row blocks needs the vectors alone).
+    int alloc(int C, long n, long partial_per_channel, hipStream_t s)
+    {
+        if (!ap.p)                                                  // (the last one made: all four are there or none is used)
+            for (DevBuf<double> *v : {&z, &r, &p, &ap}) {
+                CCP_TRY(v->alloc((size_t)(C * n)));
+                CCP_HIP(hipMemsetAsync(v->p, 0, sizeof(double) * C * n, s));
+            }
+        if (partial_per_channel > 0 && !state.p) {
+            ps = partial_per_channel;
+            CCP_TRY(partial.alloc((size_t)(C * ps)));
+            CCP_TRY(state.alloc((size_t)C));
+        }
+        return CCP_OK;
+    }
+    void release()
+    {
+        for (DevBuf<double> *v : {&z, &r, &p, &ap, &partial}) v->release();
+        state.release();
+        ps = 0;
+    }
+};
+
 // The hierarchy of one handle: level 0 is the handle's own operator and vectors; levels 1.. own d, we, ws, b, z in
-// one allocation (level layout, pads zero; a weighted hierarchy adds lambda).  The PCG work vectors (one channel) are allocated at the first solve.
+// one allocation (level layout, pads zero; a weighted hierarchy adds lambda).  The PCG work sets (`seq`: one channel,
+// `bat`: all of them) are allocated at the first solve of their mode.
 // Row blocks (ccp_grid_mg_conjugate_gradient_rowblocked): levels 0 .. dist-1 hold the block's own rows plus up to
 // kMgGhost ghost rows per neighbour side (level 0 in a layout of its own: the MG vectors do not depend on the
 // handle's ghost depth); every level from `dist` on is held whole by every rank.
@@ -32,8 +64,7 @@ struct MgHierarchy {
     std::vector<long> size;
     DevBuf<double> store;
     DevBuf<double> t0;               // level 0's pre-smoothed z (one channel): k_mg_tile reads it while it writes z
-    DevBuf<double> z, r, p, ap, partial;
-    DevBuf<CgState> state;
+    PcgWork seq;                     // the sequential mode and the row-block calls (there n is level 0's, ghost rows included)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int kind0 = kMgSolve;
     bool weighted = false;           // level 0 is a weighted handle's stored operator; every level carries lambda (arr 6)
@@ -50,13 +81,12 @@ struct MgHierarchy {
     float *farr(int k, int which) { return fstore.p + fbase[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t
     int lam_slot = 6;                // F32: 3 (the fp64 store then holds d, we, ws and lambda only)
     // CCP_MG_CHANNELS_BATCHED (ccp_grid_mgb.hpp): C of every vector, made at the first batched V-cycle (bt0: level 0's t;
-    // bstore: per coarse level b, z, t, each C x `size`) and at the first batched solve (the PCG vectors, CgState[C], the
-    // partial sums: C slices of bps).  The levels' coefficients are shared with the sequential mode.
+    // bstore: per coarse level b, z, t, each C x `size`) and at the first batched solve (the work set `bat`).  The levels'
+    // coefficients are shared with the sequential mode.
     int bC = 0;
-    long bps = 0;
     std::vector<long> bbase;
-    DevBuf<double> bt0, bstore, bz, br, bp, bap, bpartial;
-    DevBuf<CgState> bstate;
+    DevBuf<double> bt0, bstore;
+    PcgWork bat;
     double *barr(int k, int which) { return bstore.p + bbase[k] + (long)which * bC * size[k]; }   // 0 b, 1 z, 2 t: channel ch at + ch * size[k]
     // CCP_MG_SMOOTHER_LINE (ccp_grid_mgl.hpp): the smoother of the levels above the tail, taken from the handle at every
     // call (hierarchy), and the three work planes of the line solves, made at the first line V-cycle (line_planes): each
@@ -80,14 +110,31 @@ namespace {
 
 dim3 cells_grid(int w, int h) { return dim3((unsigned)((w + kBlock - 1) / kBlock), (unsigned)h); }
 
+// A level's run-time kind as a template argument: f(K) with decltype(K)::value == kind; returns what f returns.  A step
+// that takes a bool too goes through with_bool inside f.  (f is instantiated for all three kinds: where a kernel exists
+// for fewer, as the fp32 V-cycle's coarse levels do for kMgCoarse alone, name the kind and do not come here.)
+template <typename F>
+auto with_kind(int kind, F &&f)
+{
+    if (kind == kMgCoarse) return f(std::integral_constant<int, kMgCoarse>{});
+    else if (kind == kMgMasked) return f(std::integral_constant<int, kMgMasked>{});
+    else return f(std::integral_constant<int, kMgSolve>{});
+}
+
+template <typename F>
+auto with_bool(bool on, F &&f)
+{
+    if (on) return f(std::true_type{});
+    else return f(std::false_type{});
+}
+
 // coarse local rows [Y0, Y0 + rows) of c from f (kind: f's operator)
 void coarsen(int kind, hipStream_t s, const MgLevel &f, const MgLevel &c, int Y0, int rows, double *d, double *we, double *ws)
 {
     if (rows <= 0) return;
-    const dim3 grid = cells_grid(c.W, rows);
-    if (kind == kMgCoarse) hipLaunchKernelGGL((k_mg_coarsen<kMgCoarse>), grid, dim3(kBlock), 0, s, f, c, Y0, d, we, ws);
-    else if (kind == kMgMasked) hipLaunchKernelGGL((k_mg_coarsen<kMgMasked>), grid, dim3(kBlock), 0, s, f, c, Y0, d, we, ws);
-    else hipLaunchKernelGGL((k_mg_coarsen<kMgSolve>), grid, dim3(kBlock), 0, s, f, c, Y0, d, we, ws);
+    with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((k_mg_coarsen<decltype(K)::value>), cells_grid(c.W, rows), dim3(kBlock), 0, s, f, c, Y0, d, we, ws);
+    });
 }
 
 int level_kind(const MgHierarchy &h, int k) { return k ? kMgCoarse : h.kind0; }
@@ -194,19 +241,14 @@ int sweeps_arg(int32_t smoothing_sweeps, int *nu, int smoother = CCP_MG_SMOOTHER
 
 dim3 tiles(const MgLevel &f) { return dim3((unsigned)((f.W + kMgTileW - 1) / kMgTileW), (unsigned)((f.hi - f.lo + kMgTileH - 1) / kMgTileH)); }
 
-// t: the level's pre-smoothed z (restriction and the post-smoothing pass read it), z: its correction
-template <int KIND>
-void pre_t(hipStream_t s, const MgLevel &f, const double *b, double *t, int nu, const CgState *st)
+// t: the level's pre-smoothed z (restriction and the post-smoothing pass read it), z: its correction.  grid: tiles(f),
+// or one workgroup for a 1x1 image (there t = b/d, what red updates from z = 0 give, is the V-cycle's z).
+void pre(int kind, hipStream_t s, dim3 grid, const MgLevel &f, const double *b, double *t, int nu, const CgState *st)
 {
-    hipLaunchKernelGGL((k_mg_tile<KIND, false>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, static_cast<const double *>(nullptr), t,
-                       f, static_cast<const double *>(nullptr), 2.0, nu, st);
-}
-
-void pre(int kind, hipStream_t s, const MgLevel &f, const double *b, double *t, int nu, const CgState *st)
-{
-    if (kind == kMgCoarse) pre_t<kMgCoarse>(s, f, b, t, nu, st);
-    else if (kind == kMgMasked) pre_t<kMgMasked>(s, f, b, t, nu, st);
-    else pre_t<kMgSolve>(s, f, b, t, nu, st);
+    const double *none = nullptr;
+    with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((k_mg_tile<decltype(K)::value, false>), grid, dim3(kBlock), mg_tile_lds(nu), s, f, b, none, t, f, none, 2.0, nu, st);
+    });
 }
 
 // coarse local rows [Y0, Y0 + rows) of bc from f's residual
@@ -214,19 +256,18 @@ void restrict_rows(int kind, hipStream_t s, const MgLevel &f, const double *b, c
                    double *bc, const CgState *st)
 {
     if (rows <= 0) return;
-    const dim3 grid = cells_grid(c.W, rows);
-    if (kind == kMgCoarse) hipLaunchKernelGGL((k_mg_restrict<kMgCoarse>), grid, dim3(kBlock), 0, s, f, b, t, c, Y0, bc, st);
-    else if (kind == kMgMasked) hipLaunchKernelGGL((k_mg_restrict<kMgMasked>), grid, dim3(kBlock), 0, s, f, b, t, c, Y0, bc, st);
-    else hipLaunchKernelGGL((k_mg_restrict<kMgSolve>), grid, dim3(kBlock), 0, s, f, b, t, c, Y0, bc, st);
+    with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((k_mg_restrict<decltype(K)::value>), cells_grid(c.W, rows), dim3(kBlock), 0, s, f, b, t, c, Y0, bc, st);
+    });
 }
 
 // cs: the scale of the coarse correction (MgHierarchy::cs)
 void post(int kind, hipStream_t s, const MgLevel &f, const double *b, const double *t, double *z, const MgLevel &c, const double *ec, double cs,
           int nu, const CgState *st)
 {
-    if (kind == kMgCoarse) hipLaunchKernelGGL((k_mg_tile<kMgCoarse, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, cs, nu, st);
-    else if (kind == kMgMasked) hipLaunchKernelGGL((k_mg_tile<kMgMasked, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, cs, nu, st);
-    else hipLaunchKernelGGL((k_mg_tile<kMgSolve, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, cs, nu, st);
+    with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((k_mg_tile<decltype(K)::value, true>), tiles(f), dim3(kBlock), mg_tile_lds(nu), s, f, b, t, z, c, ec, cs, nu, st);
+    });
 }
 
 // ---- CCP_MG_SMOOTHER_LINE (ccp_grid_mgl.hpp) ---------------------------------------------------------------------------
@@ -292,6 +333,28 @@ void post_lines(MgHierarchy &h, hipStream_t s, const MgLevel &f, const double *b
     }
 }
 
+// The tail kernels' descriptor (MgTail of MgLevel, MgsTail of MgsLevel): the levels from `first` on, their cells packed
+// one level after the other.
+template <typename Tail, typename Level>
+Tail tail_of(const std::vector<Level> &lv, int first)
+{
+    Tail t{};
+    t.levels = (int)lv.size() - first;
+    int off = 0;
+    for (int i = 0; i < t.levels; ++i) {
+        const Level &l = lv[first + i];
+        t.W[i] = l.W;
+        t.H[i] = l.H;
+        t.pitch[i] = l.pitch;
+        t.off[i] = off;
+        t.d[i] = l.d;
+        t.we[i] = l.we;
+        t.ws[i] = l.ws;
+        off += l.W * l.H;
+    }
+    return t;
+}
+
 // The levels from `from` (held whole) down: tiles above the tail, then k_mg_tail, then back up to `from`.  Every launch
 // is a no-op once st->active is 0 (st may be null).
 int whole_levels(MgHierarchy &h, hipStream_t s, int from, const double *b0, double *z0, int nu, const CgState *st)
@@ -302,44 +365,15 @@ int whole_levels(MgHierarchy &h, hipStream_t s, int from, const double *b0, doub
     const bool line = h.smoother == CCP_MG_SMOOTHER_LINE;
     for (int k = from; k < h.tail; ++k) {
         if (line) pre_lines(h, s, h.lv[k], B(k), T(k), nu, st);
-        else pre(level_kind(h, k), s, h.lv[k], B(k), T(k), nu, st);
+        else pre(level_kind(h, k), s, tiles(h.lv[k]), h.lv[k], B(k), T(k), nu, st);
         restrict_rows(level_kind(h, k), s, h.lv[k], B(k), T(k), h.lv[k + 1], 0, h.lv[k + 1].H, h.arr(k + 1, 3), st);
     }
-    MgTail t{};
-    t.levels = h.levels - h.tail;
-    int off = 0;
-    for (int i = 0; i < t.levels; ++i) {
-        const MgLevel &l = h.lv[h.tail + i];
-        t.W[i] = l.W;
-        t.H[i] = l.H;
-        t.pitch[i] = l.pitch;
-        t.off[i] = off;
-        t.d[i] = l.d;
-        t.we[i] = l.we;
-        t.ws[i] = l.ws;
-        off += l.W * l.H;
-    }
+    const MgTail t = tail_of<MgTail>(h.lv, h.tail);
     hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(kBlock), 0, s, t, B(h.tail), Z(h.tail), h.cs, nu, st);
     for (int k = h.tail - 1; k >= from; --k) {
         if (line) post_lines(h, s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], h.arr(k + 1, 4), h.cs, nu, st);
         else post(level_kind(h, k), s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], h.arr(k + 1, 4), h.cs, nu, st);
     }
-    CCP_HIP(hipGetLastError());
-    return CCP_OK;
-}
-
-// 1x1 image: z = b/d, what red updates from z = 0 give
-int vcycle_1x1(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st)
-{
-    if (h.kind0 == kMgCoarse)
-        hipLaunchKernelGGL((k_mg_tile<kMgCoarse, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
-                           static_cast<const double *>(nullptr), 2.0, nu, st);
-    else if (h.kind0 == kMgMasked)
-        hipLaunchKernelGGL((k_mg_tile<kMgMasked, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
-                           static_cast<const double *>(nullptr), 2.0, nu, st);
-    else
-        hipLaunchKernelGGL((k_mg_tile<kMgSolve, false>), dim3(1), dim3(kBlock), mg_tile_lds(nu), s, h.lv[0], b0, static_cast<const double *>(nullptr), z0, h.lv[0],
-                           static_cast<const double *>(nullptr), 2.0, nu, st);
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 }
@@ -410,14 +444,12 @@ template <bool POST, typename Z>
 void tile32_top(int kind, hipStream_t s, dim3 grid, const MgsLevel &f, const double *b, const float *t, Z *z, const MgsLevel &c, const float *ec,
                 float cs, int nu, const CgState *st)
 {
-    if (kind == kMgCoarse) tile32<kMgCoarse, POST>(s, grid, f, b, t, z, c, ec, cs, nu, st);
-    else if (kind == kMgMasked) tile32<kMgMasked, POST>(s, grid, f, b, t, z, c, ec, cs, nu, st);
-    else tile32<kMgSolve, POST>(s, grid, f, b, t, z, c, ec, cs, nu, st);
+    with_kind(kind, [&](auto K) { tile32<decltype(K)::value, POST>(s, grid, f, b, t, z, c, ec, cs, nu, st); });
 }
 
 dim3 tiles32(const MgsLevel &f) { return dim3((unsigned)((f.W + kMgsTileW - 1) / kMgsTileW), (unsigned)((f.H + kMgsTileH - 1) / kMgsTileH)); }
 
-// vcycle in float: z0 := (double) M32^-1 (float) b0, the launch structure of whole_levels / vcycle_1x1
+// vcycle in float: z0 := (double) M32^-1 (float) b0, the launch structure of vcycle in fp64
 int vcycle32(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st)
 {
     const float *none = nullptr;
@@ -434,29 +466,16 @@ int vcycle32(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu
         const dim3 rgrid = cells_grid(c.W, c.H);
         if (k == 0) {
             tile32_top<false>(h.kind0, s, tiles32(f), f, b0, none, T(0), f, none, 2.0f, nu, st);
-            if (h.kind0 == kMgCoarse) hipLaunchKernelGGL((k_mgs_restrict<kMgCoarse, double>), rgrid, dim3(kBlock), 0, s, f, b0, T(0), c, h.farr(1, 3), st);
-            else if (h.kind0 == kMgMasked) hipLaunchKernelGGL((k_mgs_restrict<kMgMasked, double>), rgrid, dim3(kBlock), 0, s, f, b0, T(0), c, h.farr(1, 3), st);
-            else hipLaunchKernelGGL((k_mgs_restrict<kMgSolve, double>), rgrid, dim3(kBlock), 0, s, f, b0, T(0), c, h.farr(1, 3), st);
+            with_kind(h.kind0, [&](auto K) {
+                hipLaunchKernelGGL((k_mgs_restrict<decltype(K)::value, double>), rgrid, dim3(kBlock), 0, s, f, b0, T(0), c, h.farr(1, 3), st);
+            });
         } else {
             const float *b = h.farr(k, 3);
             tile32<kMgCoarse, false>(s, tiles32(f), f, b, none, T(k), f, none, 2.0f, nu, st);
             hipLaunchKernelGGL((k_mgs_restrict<kMgCoarse, float>), rgrid, dim3(kBlock), 0, s, f, b, T(k), c, h.farr(k + 1, 3), st);
         }
     }
-    MgsTail t{};
-    t.levels = h.levels - h.tail;
-    int off = 0;
-    for (int i = 0; i < t.levels; ++i) {
-        const MgsLevel &l = h.flv[h.tail + i];
-        t.W[i] = l.W;
-        t.H[i] = l.H;
-        t.pitch[i] = l.pitch;
-        t.off[i] = off;
-        t.d[i] = l.d;
-        t.we[i] = l.we;
-        t.ws[i] = l.ws;
-        off += l.W * l.H;
-    }
+    const MgsTail t = tail_of<MgsTail>(h.flv, h.tail);
     hipLaunchKernelGGL(k_mgs_tail, dim3(1), dim3(kBlock), 0, s, t, static_cast<const float *>(h.farr(h.tail, 3)), h.farr(h.tail, 4), cs, nu, st);
     for (int k = h.tail - 1; k >= 0; --k) {
         const MgsLevel &f = h.flv[k], &c = h.flv[k + 1];
@@ -472,7 +491,11 @@ int vcycle32(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu
 int vcycle(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st)
 {
     if (h.precision == CCP_MG_PRECISION_F32) return vcycle32(h, s, b0, z0, nu, st);
-    if (h.levels == 1) return vcycle_1x1(h, s, b0, z0, nu, st);
+    if (h.levels == 1) {                                            // a 1x1 image
+        pre(h.kind0, s, dim3(1), h.lv[0], b0, z0, nu, st);
+        CCP_HIP(hipGetLastError());
+        return CCP_OK;
+    }
     return whole_levels(h, s, 0, b0, z0, nu, st);
 }
 
@@ -480,15 +503,6 @@ int vcycle(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, 
 // The dynamic LDS a k_mgb_tile launch asks for: the one figure behind the launch, the limit below and
 // ccp_debug_mgb_tile_lds.
 int tile_b_lds(int kind, int nu) { return mgb_tile_lds(kind, nu); }
-
-template <int KIND>
-int tile_lds_limit_of()
-{
-    const int bytes = tile_b_lds(KIND, 4);                            // the largest nu
-    CCP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mgb_tile<KIND, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    CCP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mgb_tile<KIND, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    return CCP_OK;
-}
 
 // The stored-operator kind passes the 64 KiB a kernel may take without asking; the others come within 256 B of it
 // (65,280 B at nu = 4) and are given their size too.  Once per device and process.
@@ -499,9 +513,14 @@ int tile_lds_limit()
     CCP_HIP(hipGetDevice(&dev));
     const unsigned long long bit = dev < 64 ? 1ull << dev : 0;
     if (raised.load() & bit) return CCP_OK;
-    CCP_TRY(tile_lds_limit_of<kMgSolve>());
-    CCP_TRY(tile_lds_limit_of<kMgMasked>());
-    CCP_TRY(tile_lds_limit_of<kMgCoarse>());
+    for (int kind : {kMgSolve, kMgMasked, kMgCoarse})
+        CCP_TRY(with_kind(kind, [](auto K) -> int {
+            constexpr int KIND = decltype(K)::value;
+            const int bytes = tile_b_lds(KIND, 4);                        // the largest nu
+            CCP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mgb_tile<KIND, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+            CCP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mgb_tile<KIND, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+            return CCP_OK;
+        }));
     raised.fetch_or(bit);
     return CCP_OK;
 }
@@ -531,28 +550,23 @@ int batched_levels(const GridMgView &v, MgHierarchy &h)
 
 void batched_release(MgHierarchy &h)
 {
-    for (DevBuf<double> *b : {&h.bt0, &h.bstore, &h.bz, &h.br, &h.bp, &h.bap, &h.bpartial}) b->release();
-    h.bstate.release();
+    h.bt0.release();
+    h.bstore.release();
+    h.bat.release();
     h.bC = 0;
-}
-
-template <int KIND, bool POST>
-void tile_b(hipStream_t s, dim3 grid, const MgLevel &f, const double *b, const double *t, double *z, long fs, const MgLevel &c,
-            const double *ec, long es, double cs, int nu, int C, const CgState *st)
-{
-    hipLaunchKernelGGL((k_mgb_tile<KIND, POST>), grid, dim3(mgb_tile_threads(KIND)), tile_b_lds(KIND, nu), s, f, b, t, z, fs, c, ec, es, cs, nu, C, st);
 }
 
 template <bool POST>
 void tile_b(int kind, hipStream_t s, dim3 grid, const MgLevel &f, const double *b, const double *t, double *z, long fs, const MgLevel &c,
             const double *ec, long es, double cs, int nu, int C, const CgState *st)
 {
-    if (kind == kMgCoarse) tile_b<kMgCoarse, POST>(s, grid, f, b, t, z, fs, c, ec, es, cs, nu, C, st);
-    else if (kind == kMgMasked) tile_b<kMgMasked, POST>(s, grid, f, b, t, z, fs, c, ec, es, cs, nu, C, st);
-    else tile_b<kMgSolve, POST>(s, grid, f, b, t, z, fs, c, ec, es, cs, nu, C, st);
+    with_kind(kind, [&](auto K) {
+        constexpr int KIND = decltype(K)::value;
+        hipLaunchKernelGGL((k_mgb_tile<KIND, POST>), grid, dim3(mgb_tile_threads(KIND)), tile_b_lds(KIND, nu), s, f, b, t, z, fs, c, ec, es, cs, nu, C, st);
+    });
 }
 
-// z0 := M^-1 b0 for all C channels (n0 doubles apart in b0 and z0): whole_levels / vcycle_1x1 with every launch serving
+// z0 := M^-1 b0 for all C channels (n0 doubles apart in b0 and z0): the launches of vcycle in fp64, each serving
 // all channels; st: CgState[C] or null
 int vcycle_batched(MgHierarchy &h, hipStream_t s, int C, long n0, const double *b0, double *z0, int nu, const CgState *st)
 {
@@ -573,24 +587,12 @@ int vcycle_batched(MgHierarchy &h, hipStream_t s, int C, long n0, const double *
         tile_b<false>(kind, s, tiles(f), f, B(k), none, T(k), S(k), f, none, 0, 2.0, nu, C, st);
         dim3 grid = cells_grid(c.W, c.H);
         grid.z = groups;
-        if (kind == kMgCoarse) hipLaunchKernelGGL((k_mgb_restrict<kMgCoarse>), grid, dim3(kBlock), 0, s, f, B(k), static_cast<const double *>(T(k)), S(k), c, 0, h.barr(k + 1, 0), S(k + 1), C, st);
-        else if (kind == kMgMasked) hipLaunchKernelGGL((k_mgb_restrict<kMgMasked>), grid, dim3(kBlock), 0, s, f, B(k), static_cast<const double *>(T(k)), S(k), c, 0, h.barr(k + 1, 0), S(k + 1), C, st);
-        else hipLaunchKernelGGL((k_mgb_restrict<kMgSolve>), grid, dim3(kBlock), 0, s, f, B(k), static_cast<const double *>(T(k)), S(k), c, 0, h.barr(k + 1, 0), S(k + 1), C, st);
+        with_kind(kind, [&](auto K) {
+            hipLaunchKernelGGL((k_mgb_restrict<decltype(K)::value>), grid, dim3(kBlock), 0, s, f, B(k), static_cast<const double *>(T(k)), S(k), c, 0,
+                               h.barr(k + 1, 0), S(k + 1), C, st);
+        });
     }
-    MgTail t{};
-    t.levels = h.levels - h.tail;
-    int off = 0;
-    for (int i = 0; i < t.levels; ++i) {
-        const MgLevel &l = h.lv[h.tail + i];
-        t.W[i] = l.W;
-        t.H[i] = l.H;
-        t.pitch[i] = l.pitch;
-        t.off[i] = off;
-        t.d[i] = l.d;
-        t.we[i] = l.we;
-        t.ws[i] = l.ws;
-        off += l.W * l.H;
-    }
+    const MgTail t = tail_of<MgTail>(h.lv, h.tail);
     hipLaunchKernelGGL(k_mgb_tail, dim3((unsigned)C), dim3(kBlock), 0, s, t, B(h.tail), Z(h.tail), S(h.tail), S(h.tail), h.cs, nu, st);
     for (int k = h.tail - 1; k >= 0; --k)
         tile_b<true>(level_kind(h, k), s, tiles(h.lv[k]), h.lv[k], B(k), static_cast<const double *>(T(k)), Z(k), S(k), h.lv[k + 1],
@@ -599,103 +601,181 @@ int vcycle_batched(MgHierarchy &h, hipStream_t s, int C, long n0, const double *
     return CCP_OK;
 }
 
-// ccp_grid_mg_conjugate_gradient in batched mode: the sequential loop's launches, each for all channels
-int pcg_batched(const GridMgView &v, MgHierarchy &h, double epsilon, int max_iteration, int nu, ccp_gs_report *report)
+// ---- the PCG loop ----------------------------------------------------------------------------------------------------
+// One loop (pcg_loop) serves the three modes.  A mode is a "steps" object: the launches of every step of the recurrence,
+// and no control flow of the loop.  The wide passes (init, dot, update, direction) only launch; the products, the
+// V-cycle and the one-block steps that consume a sum (check, set_rlen, alpha, beta) return a status: on row blocks they
+// exchange ghost rows and all-reduce.  The loop itself reads s, st (the device's CgState[C]) and p, z, len (p = z copies
+// len doubles) from the object.
+
+// host: C states of the caller's (the read-backs land there); report: C entries or null.  `seconds` is the time of this
+// call in every entry: one channel's solve, or in batched mode the whole solve.
+template <typename Steps>
+int pcg_loop(const Steps &S, MgHierarchy &h, CgState *host, int C, int max_iteration, ccp_gs_report *report)
 {
-    const Geom &geo = v.geom;
-    const int C = v.channels;
-    const long n = geo.ch_stride;
-    const unsigned groups = (unsigned)((C + kMgbGroup - 1) / kMgbGroup);
-    const unsigned agx = cells_grid((geo.W + 1) / 2, 1).x;             // (the sequential loop's grids within a channel)
-    const dim3 agrid(agx, (unsigned)std::max(1, std::min(geo.H, (int)(1024 / agx))), 2 * groups);
-    const int apply_blocks = (int)(agrid.x * agrid.y * 2);
-    const int blocks = (int)std::max<long>(1, std::min<long>(2048, (n + kBlock - 1) / kBlock));
-    const dim3 vgrid((unsigned)blocks, (unsigned)C), sgrid((unsigned)C);
-    hipStream_t s = v.stream;
-    CCP_TRY(batched_levels(v, h));
-    if (!h.bz.p) {
-        h.bps = std::max(apply_blocks, blocks);
-        for (DevBuf<double> *b : {&h.bz, &h.br, &h.bp, &h.bap}) {
-            CCP_TRY(b->alloc((size_t)(C * n)));
-            CCP_HIP(hipMemsetAsync(b->p, 0, sizeof(double) * C * n, s));
-        }
-        CCP_TRY(h.bpartial.alloc((size_t)(C * h.bps)));
-        CCP_TRY(h.bstate.alloc((size_t)C));
-    }
-    CgState *st = h.bstate.p;
-    double *part = h.bpartial.p;
-    const long ps = h.bps;
-    const MgLevel &l0 = h.lv[0];
-    auto apply = [&](const double *in, double *out, bool dot) {
-        const CgState *a = dot ? st : nullptr;
-        if (v.weighted) {
-            if (dot) hipLaunchKernelGGL((k_mgb_apply<kMgCoarse, true>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
-            else hipLaunchKernelGGL((k_mgb_apply<kMgCoarse, false>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
-        } else if (v.masked) {
-            if (dot) hipLaunchKernelGGL((k_mgb_apply<kMgMasked, true>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
-            else hipLaunchKernelGGL((k_mgb_apply<kMgMasked, false>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
-        } else {
-            if (dot) hipLaunchKernelGGL((k_mgb_apply<kMgSolve, true>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
-            else hipLaunchKernelGGL((k_mgb_apply<kMgSolve, false>), agrid, dim3(kBlock), 0, s, l0, in, out, n, part, ps, C, a);
-        }
-    };
-    std::vector<CgState> host((size_t)C);
-    for (CgState &c : host) {
-        c = CgState{};
-        c.active = 1;
-    }
+    hipStream_t s = S.s;
     const size_t st_bytes = sizeof(CgState) * (size_t)C;
+    auto read_back = [&]() -> int {
+        CCP_HIP(hipMemcpyAsync(host, S.st, st_bytes, hipMemcpyDeviceToHost, s));
+        CCP_HIP(hipStreamSynchronize(s));
+        return CCP_OK;
+    };
     auto any_active = [&]() {
-        for (const CgState &c : host)
-            if (c.active) return true;
+        for (int c = 0; c < C; ++c)
+            if (host[c].active) return true;
         return false;
     };
-    CCP_HIP(hipMemcpyAsync(st, host.data(), st_bytes, hipMemcpyHostToDevice, s));
+    for (int c = 0; c < C; ++c) {
+        host[c] = CgState{};
+        host[c].active = 1;
+    }
+    CCP_HIP(hipMemcpyAsync(S.st, host, st_bytes, hipMemcpyHostToDevice, s));
     CCP_HIP(hipEventRecord(h.ev0, s));
-    apply(v.x, h.br.p, false);                                                                   // r = A x
-    hipLaunchKernelGGL(k_mgb_init, vgrid, dim3(kBlock), 0, s, static_cast<const double *>(v.b), h.br.p, h.bp.p, n, part, ps);   // r = b - r; r'r
-    hipLaunchKernelGGL(k_mgb_check, sgrid, dim3(kBlock), 0, s, part, ps, blocks, epsilon, st);
-    CCP_TRY(vcycle_batched(h, s, C, n, h.br.p, h.bz.p, nu, st));                                  // z = M r
-    hipLaunchKernelGGL(k_mgb_dot, vgrid, dim3(kBlock), 0, s, h.br.p, h.bz.p, n, part, ps, st);
-    hipLaunchKernelGGL(k_mgb_set_rlen, sgrid, dim3(kBlock), 0, s, part, ps, blocks, st);          // rlen = r'z
-    CCP_HIP(hipMemcpyAsync(h.bp.p, h.bz.p, sizeof(double) * C * n, hipMemcpyDeviceToDevice, s));  // p = z
+    CCP_TRY(S.residual());                                               // r = A x
+    S.init();                                                            // r = b - r; r'r
+    CCP_TRY(S.check());
+    CCP_TRY(S.precondition());                                           // z = M r
+    S.dot();
+    CCP_TRY(S.set_rlen());                                               // rlen = r'z
+    CCP_HIP(hipMemcpyAsync(S.p, S.z, sizeof(double) * S.len, hipMemcpyDeviceToDevice, s));   // p = z
     CCP_HIP(hipGetLastError());
-    CCP_HIP(hipMemcpyAsync(host.data(), st, st_bytes, hipMemcpyDeviceToHost, s));
-    CCP_HIP(hipStreamSynchronize(s));
+    CCP_TRY(read_back());
     int issued = 0;
     bool active = any_active() && max_iteration > 0;
     while (active && issued < max_iteration) {
         const int batch = std::min(16, max_iteration - issued);
-        for (int k = 0; k < batch; ++k) {
-            apply(h.bp.p, h.bap.p, true);                                                        // Ap, p'Ap partials
-            hipLaunchKernelGGL(k_mgb_alpha, sgrid, dim3(kBlock), 0, s, part, ps, apply_blocks, st);
-            hipLaunchKernelGGL(k_mgb_update, vgrid, dim3(kBlock), 0, s, v.x, h.bp.p, h.br.p, h.bap.p, n, part, ps, st);
-            hipLaunchKernelGGL(k_mgb_check, sgrid, dim3(kBlock), 0, s, part, ps, blocks, epsilon, st);
-            CCP_TRY(vcycle_batched(h, s, C, n, h.br.p, h.bz.p, nu, st));
-            hipLaunchKernelGGL(k_mgb_dot, vgrid, dim3(kBlock), 0, s, h.br.p, h.bz.p, n, part, ps, st);
-            hipLaunchKernelGGL(k_mgb_beta, sgrid, dim3(kBlock), 0, s, part, ps, blocks, st);
-            hipLaunchKernelGGL(k_mgb_direction, vgrid, dim3(kBlock), 0, s, h.bp.p, h.bz.p, n, st);   // p = z + beta p
+        for (int k = 0; k < batch; ++k) {                                // (the launches of an iteration are no-ops once st says so)
+            CCP_TRY(S.product());                                        // Ap, p'Ap partials
+            CCP_TRY(S.alpha());                                          // alpha = r'z / p'Ap
+            S.update();
+            CCP_TRY(S.check());
+            CCP_TRY(S.precondition());
+            S.dot();
+            CCP_TRY(S.beta());
+            S.direction();                                               // p = z + beta p
         }
         CCP_HIP(hipGetLastError());
         issued += batch;
-        CCP_HIP(hipMemcpyAsync(host.data(), st, st_bytes, hipMemcpyDeviceToHost, s));
-        CCP_HIP(hipStreamSynchronize(s));
+        CCP_TRY(read_back());
         active = any_active();
     }
     CCP_HIP(hipEventRecord(h.ev1, s));
-    CCP_HIP(hipMemcpyAsync(host.data(), st, st_bytes, hipMemcpyDeviceToHost, s));
-    CCP_HIP(hipStreamSynchronize(s));
+    CCP_TRY(read_back());
     if (report) {
         float ms = 0.f;
         CCP_HIP(hipEventElapsedTime(&ms, h.ev0, h.ev1));
-        for (int ch = 0; ch < C; ++ch) {
-            report[ch].iterations = host[ch].iterations;
-            report[ch].converged = host[ch].converged;
-            report[ch].last_l1_step = host[ch].r1norm;
-            report[ch].seconds = ms * 1e-3;                                                       // the whole batched solve
+        for (int c = 0; c < C; ++c) {
+            report[c].iterations = host[c].iterations;
+            report[c].converged = host[c].converged;
+            report[c].last_l1_step = host[c].r1norm;
+            report[c].seconds = ms * 1e-3;
         }
     }
     return CCP_OK;
+}
+
+// What the steps of every mode work on
+struct PcgArgs {
+    MgHierarchy *h;
+    hipStream_t s;
+    dim3 agrid;                      // of the product
+    int apply_blocks, blocks;        // the partial sums (per channel) a product / a wide pass leaves
+    long n, len, ps;                 // doubles of a channel, of p = z, of a channel's partial sums
+    double epsilon;
+    int nu;
+    const double *b;
+    double *x, *r, *z, *p, *ap, *part;
+    CgState *st;
+    // rows folded so that the product's grid has ~2,048 blocks per channel group (and as many partial sums for alpha)
+    void shape(int W, int rows, long count, unsigned groups = 1)
+    {
+        const unsigned agx = cells_grid((W + 1) / 2, 1).x;
+        agrid = dim3(agx, (unsigned)std::max(1, std::min(rows, (int)(1024 / agx))), 2 * groups);
+        apply_blocks = (int)(agrid.x * agrid.y * 2);
+        blocks = (int)std::max<long>(1, std::min<long>(2048, (count + kBlock - 1) / kBlock));
+        n = len = count;
+    }
+    void bind(PcgWork &w, long off)   // the vectors from `off` on
+    {
+        r = w.r.p + off, z = w.z.p + off, p = w.p.p + off, ap = w.ap.p + off;
+        part = w.partial.p, ps = w.ps, st = w.state.p;
+    }
+};
+
+// One channel of a one-block handle: k_cg_* / k_mg_*.  The caller sets b and x per channel.
+struct ChannelSteps : PcgArgs {
+    int apply(const double *in, double *out, bool dot) const              // the product of an iteration stops with the loop
+    {
+        const CgState *a = dot ? st : nullptr;
+        with_kind(h->kind0, [&](auto K) {
+            with_bool(dot, [&](auto D) {
+                hipLaunchKernelGGL((k_mg_apply<decltype(K)::value, decltype(D)::value>), agrid, dim3(kBlock), 0, s, h->lv[0], in, out, part, a);
+            });
+        });
+        return CCP_OK;
+    }
+    int residual() const { return apply(x, r, false); }
+    int product() const { return apply(p, ap, true); }
+    int precondition() const { return vcycle(*h, s, r, z, nu, st); }
+    void init() const { hipLaunchKernelGGL(k_cg_init, dim3(blocks), dim3(kBlock), 0, s, b, r, p, n, part); }
+    void dot() const { hipLaunchKernelGGL(k_cg_dot, dim3(blocks), dim3(kBlock), 0, s, r, z, n, part, st); }
+    void update() const { hipLaunchKernelGGL(k_cg_update, dim3(blocks), dim3(kBlock), 0, s, x, p, r, ap, n, part, st); }
+    void direction() const { hipLaunchKernelGGL(k_cg_direction, dim3(blocks), dim3(kBlock), 0, s, p, z, n, st); }
+    // the one-block steps read `count` sums at `sum`
+    int check(const double *sum, int count) const { hipLaunchKernelGGL(k_mg_check, dim3(1), dim3(kBlock), 0, s, sum, count, epsilon, st); return CCP_OK; }
+    int set_rlen(const double *sum, int count) const { hipLaunchKernelGGL(k_cg_set_rlen, dim3(1), dim3(kBlock), 0, s, sum, count, st); return CCP_OK; }
+    int alpha(const double *sum, int count) const { hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(kBlock), 0, s, sum, count, st); return CCP_OK; }
+    int beta(const double *sum, int count) const { hipLaunchKernelGGL(k_mg_beta, dim3(1), dim3(kBlock), 0, s, sum, count, st); return CCP_OK; }
+    int check() const { return check(part, blocks); }
+    int set_rlen() const { return set_rlen(part, blocks); }
+    int alpha() const { return alpha(part, apply_blocks); }
+    int beta() const { return beta(part, blocks); }
+};
+
+// All C channels of a one-block handle (n doubles apart in every vector): the sequential launches, each for all channels
+struct BatchedSteps : PcgArgs {
+    int C;
+    dim3 vgrid, sgrid;               // of a wide pass, of a one-block step (a block per channel)
+    int apply(const double *in, double *out, bool dot) const
+    {
+        const CgState *a = dot ? st : nullptr;
+        with_kind(h->kind0, [&](auto K) {
+            with_bool(dot, [&](auto D) {
+                hipLaunchKernelGGL((k_mgb_apply<decltype(K)::value, decltype(D)::value>), agrid, dim3(kBlock), 0, s, h->lv[0], in, out, n, part, ps, C, a);
+            });
+        });
+        return CCP_OK;
+    }
+    int residual() const { return apply(x, r, false); }
+    int product() const { return apply(p, ap, true); }
+    int precondition() const { return vcycle_batched(*h, s, C, n, r, z, nu, st); }
+    void init() const { hipLaunchKernelGGL(k_mgb_init, vgrid, dim3(kBlock), 0, s, b, r, p, n, part, ps); }
+    void dot() const { hipLaunchKernelGGL(k_mgb_dot, vgrid, dim3(kBlock), 0, s, r, z, n, part, ps, st); }
+    void update() const { hipLaunchKernelGGL(k_mgb_update, vgrid, dim3(kBlock), 0, s, x, p, r, ap, n, part, ps, st); }
+    void direction() const { hipLaunchKernelGGL(k_mgb_direction, vgrid, dim3(kBlock), 0, s, p, z, n, st); }
+    int check() const { hipLaunchKernelGGL(k_mgb_check, sgrid, dim3(kBlock), 0, s, part, ps, blocks, epsilon, st); return CCP_OK; }
+    int set_rlen() const { hipLaunchKernelGGL(k_mgb_set_rlen, sgrid, dim3(kBlock), 0, s, part, ps, blocks, st); return CCP_OK; }
+    int alpha() const { hipLaunchKernelGGL(k_mgb_alpha, sgrid, dim3(kBlock), 0, s, part, ps, apply_blocks, st); return CCP_OK; }
+    int beta() const { hipLaunchKernelGGL(k_mgb_beta, sgrid, dim3(kBlock), 0, s, part, ps, blocks, st); return CCP_OK; }
+};
+
+// ccp_grid_mg_conjugate_gradient in batched mode
+int pcg_batched(const GridMgView &v, MgHierarchy &h, double epsilon, int max_iteration, int nu, ccp_gs_report *report)
+{
+    const int C = v.channels;
+    const unsigned groups = (unsigned)((C + kMgbGroup - 1) / kMgbGroup);
+    BatchedSteps S{};
+    S.h = &h, S.s = v.stream, S.C = C, S.epsilon = epsilon, S.nu = nu;
+    S.shape(v.geom.W, v.geom.H, v.geom.ch_stride, groups);               // (the sequential loop's grids within a channel)
+    S.len = C * S.n;
+    S.vgrid = dim3((unsigned)S.blocks, (unsigned)C);
+    S.sgrid = dim3((unsigned)C);
+    CCP_TRY(batched_levels(v, h));
+    CCP_TRY(h.bat.alloc(C, S.n, std::max(S.apply_blocks, S.blocks), S.s));
+    S.bind(h.bat, 0);
+    S.b = v.b, S.x = v.x;
+    std::vector<CgState> host((size_t)C);
+    return pcg_loop(S, h, host.data(), C, max_iteration, report);
 }
 
 // ---- row blocks ----------------------------------------------------------------------------------------------------
@@ -871,14 +951,14 @@ int hierarchy_rowblocked(const GridMgView &v, const Net &n, MgHierarchy **out)
 // restriction of its own rows, summed.  COLLECTIVE: every rank issues the same messages whatever st says.
 int vcycle_rowblocked(MgHierarchy &h, const Net &n, const double *b0, double *z0, int nu, const CgState *st)
 {
-    if (h.levels == 1) return vcycle_1x1(h, n.s, b0, z0, nu, st);
+    if (h.levels == 1) return vcycle(h, n.s, b0, z0, nu, st);       // (nothing to exchange)
     auto B = [&](int k) -> double * { return k ? h.arr(k, 3) : const_cast<double *>(b0); };
     auto Z = [&](int k) -> double * { return k ? h.arr(k, 4) : z0; };
     auto T = [&](int k) -> double * { return k ? h.arr(k, 5) : h.t0.p; };
     for (int k = 0; k < h.dist; ++k) {
         const MgLevel &f = h.lv[k], &c = h.lv[k + 1];
         CCP_TRY(exchange_rows(h, n, k, B(k), 2 * nu));
-        pre(level_kind(h, k), n.s, f, B(k), T(k), nu, st);
+        pre(level_kind(h, k), n.s, tiles(f), f, B(k), T(k), nu, st);
         CCP_TRY(exchange_rows(h, n, k, T(k), 2 * nu));
         if (k + 1 < h.dist) {
             restrict_rows(level_kind(h, k), n.s, f, B(k), T(k), c, c.lo, c.hi - c.lo, B(k + 1), st);
@@ -899,6 +979,39 @@ int vcycle_rowblocked(MgHierarchy &h, const Net &n, const double *b0, double *z0
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 }
+
+// One channel of a row block, on the owned rows (r, z, p, ap point at them): a product fetches one ghost row of its
+// input first, and every partial sum is reduced to one double and all-reduced before the one-block step that consumes
+// it, so every rank takes the same decisions.  COLLECTIVE: every rank issues the same messages whatever st says.
+struct RowSteps : ChannelSteps {
+    const Net *net;
+    double *total;                   // the communicator's scratch: the sum over every rank
+    int sums(int count) const
+    {
+        hipLaunchKernelGGL(k_reduce_to_one, dim3(1), dim3(kBlock), 0, s, part, (long)count, total);
+        CCP_HIP(hipGetLastError());
+        CCP_RCCL(net->api->AllReduce(total, total, 1, ncclDouble, ncclSum, net->comm->comm, s));
+        return CCP_OK;
+    }
+    int apply(double *in, double *out, bool dot) const                    // in, out: whole vectors of level 0
+    {
+        CCP_TRY(exchange_rows(*h, *net, 0, in, 1));
+        ChannelSteps::apply(in, out, dot);
+        CCP_HIP(hipGetLastError());
+        return CCP_OK;
+    }
+    int residual() const
+    {
+        CCP_HIP(hipMemcpyAsync(p, x, sizeof(double) * n, hipMemcpyDeviceToDevice, s));   // x with ghost rows, in p
+        return apply(h->seq.p.p, h->seq.r.p, false);
+    }
+    int product() const { return apply(h->seq.p.p, h->seq.ap.p, true); }
+    int precondition() const { return vcycle_rowblocked(*h, *net, h->seq.r.p, h->seq.z.p, nu, st); }
+    int check() const { CCP_TRY(sums(blocks)); return ChannelSteps::check(total, 1); }
+    int set_rlen() const { CCP_TRY(sums(blocks)); return ChannelSteps::set_rlen(total, 1); }
+    int alpha() const { CCP_TRY(sums(apply_blocks)); return ChannelSteps::alpha(total, 1); }
+    int beta() const { CCP_TRY(sums(blocks)); return ChannelSteps::beta(total, 1); }
+};
 
 // The checks every rank makes alike, before any collective call, then the hierarchy (collective on its first use)
 int prepare_rowblocked(ccp_grid *g, int32_t smoothing_sweeps, bool need_nu, GridMgView *v, Net *n, int *nu, MgHierarchy **h)
@@ -1024,8 +1137,7 @@ try {
     if (*cache) {                                                  // the other mode's vectors go; the levels stay
         MgHierarchy &h = **cache;
         batched_release(h);
-        for (DevBuf<double> *b : {&h.z, &h.r, &h.p, &h.ap, &h.partial}) b->release();
-        h.state.release();
+        h.seq.release();
     }
     return CCP_OK;
 } CCP_ABI_CATCH
@@ -1133,86 +1245,17 @@ try {
     CCP_TRY(line_planes(v, *h));
     if (batched) return pcg_batched(v, *h, epsilon, max_iteration, nu, report);
     if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
-    const Geom &geo = v.geom;
-    const long n = geo.ch_stride;                                  // one channel incl. pads (pads stay 0 in every vector)
-    // k_mg_apply: rows folded so that the grid has ~2,048 blocks (and as many partial sums for k_cg_alpha)
-    const unsigned agx = cells_grid((geo.W + 1) / 2, 1).x;
-    const dim3 agrid(agx, (unsigned)std::max(1, std::min(geo.H, (int)(1024 / agx))), 2);
-    const int apply_blocks = (int)(agrid.x * agrid.y * agrid.z);
-    const int blocks = (int)std::max<long>(1, std::min<long>(2048, (n + kBlock - 1) / kBlock));
-    hipStream_t s = v.stream;
-    if (!h->z.p) {
-        CCP_TRY(h->z.alloc((size_t)n));
-        CCP_TRY(h->r.alloc((size_t)n));
-        CCP_TRY(h->p.alloc((size_t)n));
-        CCP_TRY(h->ap.alloc((size_t)n));
-        CCP_TRY(h->partial.alloc((size_t)std::max(apply_blocks, blocks)));
-        CCP_TRY(h->state.alloc(1));
-        for (DevBuf<double> *b : {&h->z, &h->r, &h->p, &h->ap}) CCP_HIP(hipMemsetAsync(b->p, 0, sizeof(double) * n, s));
-    }
-    CgState *st = h->state.p;
-    double *part = h->partial.p;
-    const MgLevel &l0 = h->lv[0];
-    auto apply = [&](const double *in, double *out, bool dot) {           // the product of an iteration stops with the loop
-        if (v.weighted) {
-            if (dot) hipLaunchKernelGGL((k_mg_apply<kMgCoarse, true>), agrid, dim3(kBlock), 0, s, l0, in, out, part, st);
-            else hipLaunchKernelGGL((k_mg_apply<kMgCoarse, false>), agrid, dim3(kBlock), 0, s, l0, in, out, part, static_cast<const CgState *>(nullptr));
-        } else if (v.masked) {
-            if (dot) hipLaunchKernelGGL((k_mg_apply<kMgMasked, true>), agrid, dim3(kBlock), 0, s, l0, in, out, part, st);
-            else hipLaunchKernelGGL((k_mg_apply<kMgMasked, false>), agrid, dim3(kBlock), 0, s, l0, in, out, part, static_cast<const CgState *>(nullptr));
-        } else {
-            if (dot) hipLaunchKernelGGL((k_mg_apply<kMgSolve, true>), agrid, dim3(kBlock), 0, s, l0, in, out, part, st);
-            else hipLaunchKernelGGL((k_mg_apply<kMgSolve, false>), agrid, dim3(kBlock), 0, s, l0, in, out, part, static_cast<const CgState *>(nullptr));
-        }
-    };
+    const long n = v.geom.ch_stride;                               // one channel incl. pads (pads stay 0 in every vector)
+    ChannelSteps S{};
+    S.h = h, S.s = v.stream, S.epsilon = epsilon, S.nu = nu;
+    S.shape(v.geom.W, v.geom.H, n);
+    CCP_TRY(h->seq.alloc(1, n, std::max(S.apply_blocks, S.blocks), S.s));
+    S.bind(h->seq, 0);
     for (int ch = 0; ch < v.channels; ++ch) {
-        const double *b = v.b + ch * n;
-        double *x = v.x + ch * n;
-        CgState host{};
-        host.active = 1;
-        CCP_HIP(hipMemcpyAsync(st, &host, sizeof(host), hipMemcpyHostToDevice, s));
-        CCP_HIP(hipEventRecord(h->ev0, s));
-        apply(x, h->r.p, false);                                                              // r = A x
-        hipLaunchKernelGGL(k_cg_init, dim3(blocks), dim3(kBlock), 0, s, b, h->r.p, h->p.p, n, part);   // r = b - r; r'r
-        hipLaunchKernelGGL(k_mg_check, dim3(1), dim3(kBlock), 0, s, part, blocks, epsilon, st);
-        CCP_TRY(vcycle(*h, s, h->r.p, h->z.p, nu, st));                                   // z = M r
-        hipLaunchKernelGGL(k_cg_dot, dim3(blocks), dim3(kBlock), 0, s, h->r.p, h->z.p, n, part, st);
-        hipLaunchKernelGGL(k_cg_set_rlen, dim3(1), dim3(kBlock), 0, s, part, blocks, st);   // rlen = r'z
-        CCP_HIP(hipMemcpyAsync(h->p.p, h->z.p, sizeof(double) * n, hipMemcpyDeviceToDevice, s));   // p = z
-        CCP_HIP(hipGetLastError());
-        CCP_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-        CCP_HIP(hipStreamSynchronize(s));
-        int issued = 0;
-        bool active = host.active != 0 && max_iteration > 0;
-        while (active && issued < max_iteration) {
-            const int batch = std::min(16, max_iteration - issued);
-            for (int k = 0; k < batch; ++k) {
-                apply(h->p.p, h->ap.p, true);                                                // Ap, p'Ap partials
-                hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(kBlock), 0, s, part, apply_blocks, st);   // alpha = r'z / p'Ap
-                hipLaunchKernelGGL(k_cg_update, dim3(blocks), dim3(kBlock), 0, s, x, h->p.p, h->r.p, h->ap.p, n, part, st);
-                hipLaunchKernelGGL(k_mg_check, dim3(1), dim3(kBlock), 0, s, part, blocks, epsilon, st);
-                CCP_TRY(vcycle(*h, s, h->r.p, h->z.p, nu, st));
-                hipLaunchKernelGGL(k_cg_dot, dim3(blocks), dim3(kBlock), 0, s, h->r.p, h->z.p, n, part, st);
-                hipLaunchKernelGGL(k_mg_beta, dim3(1), dim3(kBlock), 0, s, part, blocks, st);
-                hipLaunchKernelGGL(k_cg_direction, dim3(blocks), dim3(kBlock), 0, s, h->p.p, h->z.p, n, st);   // p = z + beta p
-            }
-            CCP_HIP(hipGetLastError());
-            issued += batch;
-            CCP_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-            CCP_HIP(hipStreamSynchronize(s));
-            active = host.active != 0;
-        }
-        CCP_HIP(hipEventRecord(h->ev1, s));
-        CCP_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-        CCP_HIP(hipStreamSynchronize(s));
-        if (report) {
-            float ms = 0.f;
-            CCP_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-            report[ch].iterations = host.iterations;
-            report[ch].converged = host.converged;
-            report[ch].last_l1_step = host.r1norm;
-            report[ch].seconds = ms * 1e-3;
-        }
+        S.b = v.b + ch * n;
+        S.x = v.x + ch * n;
+        CgState host;
+        CCP_TRY(pcg_loop(S, *h, &host, 1, max_iteration, report ? report + ch : nullptr));
     }
     return CCP_OK;
 } CCP_ABI_CATCH
@@ -1228,17 +1271,12 @@ try {
     CCP_TRY(prepare_rowblocked(g, smoothing_sweeps, true, &v, &net, &nu, &h));
     const MgLevel &l0 = h->lv[0];
     const long row = 2 * l0.pitch, n0 = (long)l0.H * row, n_own = (long)(l0.hi - l0.lo) * row;
-    if (!h->r.p) {                                        // (PCG work vectors in level 0's layout; zero beyond the owned rows)
-        for (DevBuf<double> *b : {&h->z, &h->r, &h->p, &h->ap}) {
-            CCP_TRY(b->alloc((size_t)n0));
-            CCP_HIP(hipMemsetAsync(b->p, 0, sizeof(double) * n0, net.s));
-        }
-    }
+    CCP_TRY(h->seq.alloc(1, n0, 0, net.s));               // (PCG work vectors in level 0's layout; zero beyond the owned rows)
     const long hoff = (long)v.geom.own_lo * row;
     for (int ch = 0; ch < v.channels; ++ch) {
-        CCP_HIP(hipMemcpyAsync(h->r.p + l0.lo * row, v.b + ch * v.geom.ch_stride + hoff, sizeof(double) * n_own, hipMemcpyDeviceToDevice, net.s));
-        CCP_TRY(vcycle_rowblocked(*h, net, h->r.p, h->z.p, nu, nullptr));
-        CCP_HIP(hipMemcpyAsync(v.x + ch * v.geom.ch_stride + hoff, h->z.p + l0.lo * row, sizeof(double) * n_own, hipMemcpyDeviceToDevice, net.s));
+        CCP_HIP(hipMemcpyAsync(h->seq.r.p + l0.lo * row, v.b + ch * v.geom.ch_stride + hoff, sizeof(double) * n_own, hipMemcpyDeviceToDevice, net.s));
+        CCP_TRY(vcycle_rowblocked(*h, net, h->seq.r.p, h->seq.z.p, nu, nullptr));
+        CCP_HIP(hipMemcpyAsync(v.x + ch * v.geom.ch_stride + hoff, h->seq.z.p + l0.lo * row, sizeof(double) * n_own, hipMemcpyDeviceToDevice, net.s));
     }
     CCP_HIP(hipStreamSynchronize(net.s));
     grid_mg_halo_stale(g);
@@ -1262,9 +1300,8 @@ try {
     return CCP_OK;
 } CCP_ABI_CATCH
 
-// The one-block PCG loop over the owned rows: A p fetches one ghost row of p first; every partial sum is reduced to one
-// double and all-reduced, so every rank takes the same decisions and issues the same collectives.  x is updated in
-// place on the handle's owned rows (the owned range of a plane is laid out alike in the handle and in level 0).
+// The one-block PCG loop over the owned rows (RowSteps).  x is updated in place on the handle's owned rows (the owned
+// range of a plane is laid out alike in the handle and in level 0).
 int ccp_grid_mg_conjugate_gradient_rowblocked(ccp_grid *g, double epsilon, int32_t max_iteration, int32_t smoothing_sweeps,
                                               ccp_gs_report *report)
 try {
@@ -1278,96 +1315,18 @@ try {
     const long row = 2 * l0.pitch, n0 = (long)l0.H * row, off = (long)l0.lo * row;
     const long n = (long)(l0.hi - l0.lo) * row;                       // the owned range (pads stay 0 in every vector)
     const long hoff = (long)v.geom.own_lo * row;
-    const int own_rows = l0.hi - l0.lo;
-    const unsigned agx = cells_grid((l0.W + 1) / 2, 1).x;
-    const dim3 agrid(agx, (unsigned)std::max(1, std::min(own_rows, (int)(1024 / agx))), 2);
-    const int apply_blocks = (int)(agrid.x * agrid.y * agrid.z);
-    const int blocks = (int)std::max<long>(1, std::min<long>(2048, (n + kBlock - 1) / kBlock));
-    hipStream_t s = net.s;
-    if (!h->r.p) {
-        for (DevBuf<double> *b : {&h->z, &h->r, &h->p, &h->ap}) {
-            CCP_TRY(b->alloc((size_t)n0));
-            CCP_HIP(hipMemsetAsync(b->p, 0, sizeof(double) * n0, s));
-        }
-    }
-    if (!h->partial.p) CCP_TRY(h->partial.alloc((size_t)std::max(apply_blocks, blocks)));
-    if (!h->state.p) CCP_TRY(h->state.alloc(1));
-    CgState *st = h->state.p;
-    double *part = h->partial.p;
-    double *total = reinterpret_cast<double *>(net.comm->scratch.p);
-    auto sums = [&](int count) -> int {                                   // total[0] := the partials summed over every rank
-        hipLaunchKernelGGL(k_reduce_to_one, dim3(1), dim3(kBlock), 0, s, part, (long)count, total);
-        CCP_HIP(hipGetLastError());
-        CCP_RCCL(net.api->AllReduce(total, total, 1, ncclDouble, ncclSum, net.comm->comm, s));
-        return CCP_OK;
-    };
-    auto apply = [&](double *in, double *out, bool dot) -> int {          // one ghost row of `in`, then out := A in
-        CCP_TRY(exchange_rows(*h, net, 0, in, 1));
-        if (v.masked) {
-            if (dot) hipLaunchKernelGGL((k_mg_apply<kMgMasked, true>), agrid, dim3(kBlock), 0, s, l0, in, out, part, st);
-            else hipLaunchKernelGGL((k_mg_apply<kMgMasked, false>), agrid, dim3(kBlock), 0, s, l0, in, out, part, static_cast<const CgState *>(nullptr));
-        } else {
-            if (dot) hipLaunchKernelGGL((k_mg_apply<kMgSolve, true>), agrid, dim3(kBlock), 0, s, l0, in, out, part, st);
-            else hipLaunchKernelGGL((k_mg_apply<kMgSolve, false>), agrid, dim3(kBlock), 0, s, l0, in, out, part, static_cast<const CgState *>(nullptr));
-        }
-        CCP_HIP(hipGetLastError());
-        return CCP_OK;
-    };
-    double *r = h->r.p + off, *z = h->z.p + off, *p = h->p.p + off, *ap = h->ap.p + off;
+    RowSteps S{};
+    S.h = h, S.s = net.s, S.epsilon = epsilon, S.nu = nu;
+    S.net = &net;
+    S.total = reinterpret_cast<double *>(net.comm->scratch.p);
+    S.shape(l0.W, l0.hi - l0.lo, n);
+    CCP_TRY(h->seq.alloc(1, n0, std::max(S.apply_blocks, S.blocks), S.s));
+    S.bind(h->seq, off);
     for (int ch = 0; ch < v.channels; ++ch) {
-        const double *b = v.b + ch * v.geom.ch_stride + hoff;
-        double *x = v.x + ch * v.geom.ch_stride + hoff;
-        CgState host{};
-        host.active = 1;
-        CCP_HIP(hipMemcpyAsync(st, &host, sizeof(host), hipMemcpyHostToDevice, s));
-        CCP_HIP(hipEventRecord(h->ev0, s));
-        CCP_HIP(hipMemcpyAsync(p, x, sizeof(double) * n, hipMemcpyDeviceToDevice, s));     // x with ghost rows, in p
-        CCP_TRY(apply(h->p.p, h->r.p, false));                                                // r = A x
-        hipLaunchKernelGGL(k_cg_init, dim3(blocks), dim3(kBlock), 0, s, b, r, p, n, part);    // r = b - r; r'r
-        CCP_TRY(sums(blocks));
-        hipLaunchKernelGGL(k_mg_check, dim3(1), dim3(kBlock), 0, s, total, 1, epsilon, st);
-        CCP_TRY(vcycle_rowblocked(*h, net, h->r.p, h->z.p, nu, st));                           // z = M r
-        hipLaunchKernelGGL(k_cg_dot, dim3(blocks), dim3(kBlock), 0, s, r, z, n, part, st);
-        CCP_TRY(sums(blocks));
-        hipLaunchKernelGGL(k_cg_set_rlen, dim3(1), dim3(kBlock), 0, s, total, 1, st);         // rlen = r'z
-        CCP_HIP(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, s));       // p = z
-        CCP_HIP(hipGetLastError());
-        CCP_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-        CCP_HIP(hipStreamSynchronize(s));
-        int issued = 0;
-        bool active = host.active != 0 && max_iteration > 0;
-        while (active && issued < max_iteration) {
-            const int batch = std::min(16, max_iteration - issued);
-            for (int k = 0; k < batch; ++k) {
-                CCP_TRY(apply(h->p.p, h->ap.p, true));                                         // Ap, p'Ap
-                CCP_TRY(sums(apply_blocks));
-                hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(kBlock), 0, s, total, 1, st);    // alpha = r'z / p'Ap
-                hipLaunchKernelGGL(k_cg_update, dim3(blocks), dim3(kBlock), 0, s, x, p, r, ap, n, part, st);
-                CCP_TRY(sums(blocks));
-                hipLaunchKernelGGL(k_mg_check, dim3(1), dim3(kBlock), 0, s, total, 1, epsilon, st);
-                CCP_TRY(vcycle_rowblocked(*h, net, h->r.p, h->z.p, nu, st));
-                hipLaunchKernelGGL(k_cg_dot, dim3(blocks), dim3(kBlock), 0, s, r, z, n, part, st);
-                CCP_TRY(sums(blocks));
-                hipLaunchKernelGGL(k_mg_beta, dim3(1), dim3(kBlock), 0, s, total, 1, st);
-                hipLaunchKernelGGL(k_cg_direction, dim3(blocks), dim3(kBlock), 0, s, p, z, n, st);   // p = z + beta p
-            }
-            CCP_HIP(hipGetLastError());
-            issued += batch;
-            CCP_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-            CCP_HIP(hipStreamSynchronize(s));
-            active = host.active != 0;
-        }
-        CCP_HIP(hipEventRecord(h->ev1, s));
-        CCP_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-        CCP_HIP(hipStreamSynchronize(s));
-        if (report) {
-            float ms = 0.f;
-            CCP_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-            report[ch].iterations = host.iterations;
-            report[ch].converged = host.converged;
-            report[ch].last_l1_step = host.r1norm;
-            report[ch].seconds = ms * 1e-3;
-        }
+        S.b = v.b + ch * v.geom.ch_stride + hoff;
+        S.x = v.x + ch * v.geom.ch_stride + hoff;
+        CgState host;
+        CCP_TRY(pcg_loop(S, *h, &host, 1, max_iteration, report ? report + ch : nullptr));
     }
     grid_mg_halo_stale(g);                                                // the ghost rows of x are stale now
     return CCP_OK;

@@ -117,13 +117,15 @@ def case_pcg(c):
     """The PCG loop across the blocks against the one-block call: x to rounding, the same report on every rank, the
     stop confirmed by the global residual.  bands: compare only these row bands (bounded host memory at full size).
     remask: after the first solve, set another mask on every rank and solve again (the hierarchy must follow it).
-    sweep_after: a row-blocked sweep after the solve must refresh the stale ghost rows itself."""
+    sweep_after: a row-blocked sweep after the solve must refresh the stale ghost rows itself.  x0: the start value of
+    x (0 without it); with it every rank also says whether its owned rows still hold x0, bit for bit (iters 0)."""
     W, H, C_, nu, iters = c["W"], c["H"], c.get("C", 1), c.get("nu", 2), c["iters"]
     mask = mask_of(c)
     bands = c.get("bands") or [[0, H]]
+    x0 = c.get("x0", 0.0)
     whole = capi.Grid(W, H, C_, mask=mask)
     system(whole)
-    whole.fill_x(0.0)
+    whole.fill_x(x0)
     eps = eps_of(c, whole)
     reps_w = whole.mg_conjugate_gradient(eps, iters, nu)
     want = [np.stack([whole.get_x(ch, lo, hi - lo) for ch in range(C_)]) for lo, hi in bands]
@@ -143,7 +145,7 @@ def case_pcg(c):
     def rank_fn(rank, comm):
         gb = block(c, cuts, rank, mask)
         system(gb)
-        gb.fill_x(0.0)
+        gb.fill_x(x0)
         gb.attach_comm(comm)
         reps = gb.mg_conjugate_gradient_rowblocked(eps, iters, nu)
         rr, _ = gb.residual_norm2_global()
@@ -153,6 +155,9 @@ def case_pcg(c):
             a, b = max(lo, blo), min(hi, bhi)
             mine.append(np.stack([gb.get_x(ch, a, b - a) for ch in range(C_)]) if a < b else None)
         res = {"reps": [(r.iterations, r.converged, r.last_l1_step) for r in reps], "rr": rr.tolist()}
+        if "x0" in c:
+            start = np.full((gb.get_x_owned(0).shape), x0).view(np.uint64)
+            res["x_is_start"] = all(np.array_equal(gb.get_x_owned(ch).view(np.uint64), start) for ch in range(C_))
         if c.get("sweep_after"):
             gb.sweep_rowblocked(2)
             res["after"] = np.stack([gb.get_x_owned(ch) for ch in range(C_)])
@@ -177,6 +182,8 @@ def case_pcg(c):
         den += float(np.sum(want[i] ** 2))
     res = {"ok": True, "eps": eps, "rel_diff": float(np.sqrt(num / den)), "report_one_block": rep_w,
            "report_ranks": [o[1]["reps"] for o in out], "rnorm_global": [list(np.sqrt(o[1]["rr"])) for o in out]}
+    if "x0" in c:
+        res["x_is_start"] = [o[1]["x_is_start"] for o in out]
     if c.get("sweep_after"):
         got_x = np.concatenate([o[0][0] for o in out], axis=1)
         ref = capi.Grid(W, H, C_, mask=mask)

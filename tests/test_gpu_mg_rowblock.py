@@ -5,7 +5,8 @@ tests/cpp/libfake_rccl.so, as in test_gpu_rccl_multirank.py; one rank also runs 
 The V-cycle across the blocks is bit-identical to the one-block V-cycle on every partition (aligned, ragged, blocks of
 2 nu rows, levels all in the tail, a mask region, nu 1..4, two channels); the distribution rule keeps aligned blocks
 distributed down to the tail; the PCG loop follows the one-block loop (x to rounding, iterations +-1, the same report
-on every rank) up to 16384^2 over 8 blocks; refusals are the same on every rank."""
+on every rank) up to 16384^2 over 8 blocks, and keeps to its iteration cap across the batch of 16 and at 0; refusals are
+the same on every rank."""
 import json
 import os
 import subprocess
@@ -102,6 +103,19 @@ def test_pcg_fixed_count_follows_one_block(fake_env):
         assert r["rel_diff"] < 1e-9, (r["case"], r["rel_diff"])
         for ch, (it, conv, _) in enumerate(rep):
             assert it == r["report_one_block"][ch][0] == 8 and conv == 0, (r["case"], rep)
+
+
+def test_pcg_iteration_caps(fake_env):
+    """The cap across the loop's batch of 16 iterations, and at zero (x = 3 at the start, so that it is not the zero a
+    cleared buffer holds)."""
+    size = {"kind": "pcg", "eps": 1e-30, "world": 2, "W": 100, "H": 60, "C": 2}
+    edge, zero = drive(fake_env, [{**size, "iters": 17}, {**size, "iters": 0, "x0": 3.0}])
+    assert edge["rel_diff"] < 1e-9, edge["rel_diff"]
+    for ch, (it, conv, _) in enumerate(same_reports(edge)):
+        assert it == edge["report_one_block"][ch][0] == 17 and conv == 0, (edge["report_ranks"], edge["report_one_block"])
+    for it, conv, _ in same_reports(zero):
+        assert it == 0 and conv == 0, zero["report_ranks"]
+    assert zero["x_is_start"] == [True, True]
 
 
 def check_converged(r):
