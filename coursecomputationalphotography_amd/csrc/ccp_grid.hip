@@ -683,6 +683,16 @@ int launch_fused(ccp_grid *g, int T, const double *xin, double *xout, const int 
     return CCP_OK;
 }
 
+// x_alt, the ping-pong partner of x, exists from its first use on (cleared once: passes read its pads)
+int ensure_x_alt(ccp_grid *g)
+{
+    if (g->x_alt.p) return CCP_OK;
+    const size_t elems = (size_t)g->geom.ch_stride * g->desc.channels;
+    CCP_TRY(g->x_alt.alloc(elems));
+    CCP_HIP(hipMemsetAsync(g->x_alt.p, 0, elems * sizeof(double), g->stream));
+    return CCP_OK;
+}
+
 // `iterations` unchecked sweeps: an even number of fused launches (so the result lands back
 // in g->x), a lone leftover iteration through the in-place half-sweep kernels.
 // l1_last: the last launch also accumulates the L1 step of the final iteration (fused check).
@@ -697,11 +707,7 @@ int run_unchecked(ccp_grid *g, int iterations, const int *active = nullptr, bool
         if (edge_rows > 0) CCP_TRY(edge_epoch_publish_after_pass(g));
         return CCP_OK;
     }
-    if (!g->x_alt.p) {
-        const size_t elems = (size_t)g->geom.ch_stride * g->desc.channels;
-        CCP_TRY(g->x_alt.alloc(elems));
-        CCP_HIP(hipMemsetAsync(g->x_alt.p, 0, elems * sizeof(double), g->stream));
-    }
+    CCP_TRY(ensure_x_alt(g));
     // The passes (fused_pass_split): measured per-depth launch times when the handle was tuned, otherwise "fewer, deeper
     // launches are cheaper"; an odd number of them only where x and x_alt may swap roles.
     double cost[kFusedMaxT + 1] = {0};
@@ -794,6 +800,153 @@ int end_timing(ccp_grid *g)
     CCP_HIP(hipEventRecord(g->ev1, g->stream));
     g->timing_pending = true;
     return CCP_OK;
+}
+
+// ---- Steps the solve entry points share (NOTES.md §R22.1).  The drivers around them stay apart: the one-block loop runs one
+// ---- pass ahead of the host, the row-block loop is synchronous, row-block CG fetches ghost rows and all-reduces.
+
+// The end of every solve: the end event, the wait, the time, then the reports.  per_channel(ch, r) fills report[ch]'s
+// converged / iterations / last_l1_step from wherever the caller keeps them.  state_out: the device's SolveState is read
+// back into it between the end event and the wait (the one-block solve's last look at it).
+template <class PerChannel>
+int finish_solve(ccp_grid *g, ccp_gs_report *report, PerChannel per_channel, SolveState *state_out = nullptr)
+{
+    CCP_TRY(end_timing(g));
+    if (state_out) CCP_HIP(hipMemcpyAsync(state_out, g->state.p, sizeof(*state_out), hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    float ms = 0.f;
+    CCP_HIP(hipEventElapsedTime(&ms, g->ev0, g->ev1));
+    g->last_ms = ms;
+    g->timing_pending = false;
+    for (int ch = 0; report && ch < g->desc.channels; ++ch) {
+        per_channel(ch, report[ch]);
+        report[ch].seconds = ms * 1e-3;
+    }
+    return CCP_OK;
+}
+
+// The step of one checked sweep from its block results (blocks[0/1]: per channel, red / black region) and, with st, the
+// stop rule on it; out != nullptr: the sums go there (row blocks all-reduce them)
+int launch_check(ccp_grid *g, const long *blocks, double epsilon, int sweep_index, SolveState *st, double *out)
+{
+    hipLaunchKernelGGL(k_check, dim3((unsigned)g->desc.channels), dim3(kBlock), 0, g->stream, g->partial.p, blocks[0],
+                       g->partial.p + g->partial_region, blocks[1], epsilon, sweep_index, st, out);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+// What the checked fused passes work in beside x: its partner, the one-channel mask of a re-run, the sums of a pass's sweeps
+int ensure_checked_work(ccp_grid *g)
+{
+    CCP_TRY(ensure_x_alt(g));
+    if (!g->redo_mask.p) CCP_TRY(g->redo_mask.alloc(kMaxChannels));
+    if (!g->sweep_sums.p) CCP_TRY(g->sweep_sums.alloc((size_t)kFusedMaxCheckedT * kMaxChannels));
+    return CCP_OK;
+}
+
+// `double eps = 10` (sparse-matrix.h:354), every channel iterating: on the host and (enqueued) on the device
+int start_solve_state(ccp_grid *g, SolveState &host)
+{
+    host = SolveState{};
+    for (int ch = 0; ch < g->desc.channels; ++ch) {
+        host.active[ch] = 1;
+        host.last_eps[ch] = 10.0;
+    }
+    CCP_HIP(hipMemcpyAsync(g->state.p, &host, sizeof(host), hipMemcpyHostToDevice, g->stream));
+    return CCP_OK;
+}
+
+// One checked pass of depth T, cur -> alt, over the channels still active: the step of each of its sweeps (a block per
+// channel and sweep), reduce(count) on those T * C sums in g->sweep_sums (row blocks: the all-reduce), then the rule on
+// them in sweep order (k0 + 1 is the first sweep's index).
+template <class Reduce>
+int checked_pass(ccp_grid *g, int T, const double *cur, double *alt, int k0, int check_every, double epsilon, Reduce reduce)
+{
+    const int C = g->desc.channels;
+    long blocks[2] = {0, 0};
+    CCP_TRY(launch_fused(g, T, cur, alt, reinterpret_cast<const int *>(g->state.p), 2, blocks));
+    hipLaunchKernelGGL(k_sweep_sums_wide, dim3((unsigned)C, (unsigned)T), dim3(kBlock), 0, g->stream, g->partial.p, blocks[0],
+                       g->partial.p + g->partial_region, blocks[1], g->sweep_sums.p);
+    CCP_HIP(hipGetLastError());
+    CCP_TRY(reduce((size_t)T * C));
+    hipLaunchKernelGGL(k_decide_sums, dim3(1), dim3(kMaxChannels), 0, g->stream, g->sweep_sums.p, C, T, k0 + 1, check_every, epsilon, g->state.p);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+// After the host has seen the state behind the pass (k0, T, cur -> alt): a channel that stopped inside it is re-run from
+// the pass's input buffer (still intact: passes ping-pong) for exactly the sweeps it wanted, then kept in BOTH buffers — a
+// frozen channel is never touched again.  since0: the ghost-row counter when the pass started; the re-run starts there.
+int settle_stopped(ccp_grid *g, const SolveState &host, int *was_active, int k0, int T, double *cur, double *alt, int since0, bool *any_active)
+{
+    const size_t plane = (size_t)g->geom.ch_stride * sizeof(double);
+    const int since1 = g->half_sweeps_since_refresh;
+    *any_active = false;
+    for (int ch = 0; ch < g->desc.channels; ++ch) {
+        *any_active |= host.active[ch] != 0;
+        if (!was_active[ch] || host.active[ch]) continue;
+        was_active[ch] = 0;                                   // stopped inside this pass
+        const int m = host.iterations[ch] - k0;               // sweeps of the pass it wanted: 1..T
+        double *have = alt;                                   // where the channel's x_k is
+        if (m < T) {
+            int mask[kMaxChannels] = {0};
+            mask[ch] = 1;
+            CCP_HIP(hipMemcpyAsync(g->redo_mask.p, mask, sizeof(mask), hipMemcpyHostToDevice, g->stream));
+            g->half_sweeps_since_refresh = since0;
+            double *p = cur, *q = alt;
+            for (int left = m; left > 0;) {
+                const int t = std::min(left, g->masked ? kMaskedMaxT : kFusedMaxT);
+                CCP_TRY(launch_fused(g, t, p, q, g->redo_mask.p));
+                std::swap(p, q);
+                left -= t;
+            }
+            CCP_HIP(hipStreamSynchronize(g->stream));          // `mask` lives on this stack frame
+            g->half_sweeps_since_refresh = since1;
+            have = p;
+        }
+        double *other = (have == cur) ? alt : cur;
+        CCP_HIP(hipMemcpyAsync(other + (size_t)ch * g->geom.ch_stride, have + (size_t)ch * g->geom.ch_stride, plane,
+                               hipMemcpyDeviceToDevice, g->stream));
+    }
+    return CCP_OK;
+}
+
+// Conjugate gradient: the work vectors (one channel each), the loop CCP_GS_CG_FUSED asks for — 0 the three-pass loop
+// (88 B), 2 the fused loop with the row-per-block pass A (one block only; its iterates are the three-pass loop's bit for
+// bit), otherwise the fused loop with the marching pass A (default) — and the masked / unmasked kernels (launches only: the
+// caller asks hipGetLastError its own way, CCP_HIP outside CG and a bare CCP_ERR_HIP in the CG lambdas, as before).
+int ensure_cg_work(ccp_grid *g)
+{
+    if (g->cg_r.p) return CCP_OK;
+    const size_t n = (size_t)g->geom.ch_stride;
+    CCP_TRY(g->cg_r.alloc(n));
+    CCP_TRY(g->cg_p.alloc(n));
+    CCP_TRY(g->cg_p2.alloc(n));
+    CCP_TRY(g->cg_ap.alloc(n));
+    CCP_TRY(g->cg_state.alloc(1));
+    return CCP_OK;
+}
+
+int cg_fused_mode() { return getenv("CCP_GS_CG_FUSED") ? atoi(getenv("CCP_GS_CG_FUSED")) : 1; }
+
+// k_apply<2, DOT> on rows l_lo + blockIdx.y: out := A in (DOT 0), the residual's sums of in against out (1), out := A in and in'(A in) (2)
+template <int DOT>
+void launch_apply(ccp_grid *g, dim3 grid, const double *in, double *out, int l_lo)
+{
+    if (g->masked) hipLaunchKernelGGL((k_apply<2, DOT, true>), grid, dim3(kBlock), 0, g->stream, in, out, out, g->geom, l_lo, g->partial.p, g->maskp.p);
+    else hipLaunchKernelGGL((k_apply<2, DOT>), grid, dim3(kBlock), 0, g->stream, in, out, out, g->geom, l_lo, g->partial.p, static_cast<const unsigned char *>(nullptr));
+}
+
+// Pass A of the fused loop, marching march_rows rows per block over rows [row_lo, row_hi)
+void launch_apply_march(ccp_grid *g, dim3 mgrid, double *xv, const double *rv, const double *p_in, double *p_out, double *apv, int march_rows,
+                       int row_lo, int row_hi)
+{
+    if (g->masked)
+        hipLaunchKernelGGL((k_cg_apply_march<true>), mgrid, dim3(kBlock), 0, g->stream, xv, rv, p_in, p_out, apv, g->geom, march_rows, g->partial.p,
+                           g->maskp.p, g->cg_state.p, row_lo, row_hi);
+    else
+        hipLaunchKernelGGL((k_cg_apply_march<false>), mgrid, dim3(kBlock), 0, g->stream, xv, rv, p_in, p_out, apv, g->geom, march_rows, g->partial.p,
+                           static_cast<const unsigned char *>(nullptr), g->cg_state.p, row_lo, row_hi);
 }
 
 // Host <-> device rows in natural order through the staging buffer.
@@ -1218,11 +1371,7 @@ try {
     const int l_lo = g->shrink_top ? 1 : 0;
     const int l_hi = geo.local_rows - (g->shrink_bottom ? 1 : 0);
     dim3 grid((unsigned)((geo.pitch + 2L * kBlock - 1) / (2L * kBlock)), (unsigned)(l_hi - l_lo), (unsigned)g->desc.channels * 2);
-    if (g->masked)
-        hipLaunchKernelGGL((k_apply<2, 0, true>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->b.p, g->b.p, geo, l_lo, g->partial.p, g->maskp.p);
-    else
-        hipLaunchKernelGGL((k_apply<2, 0>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->b.p, g->b.p, geo, l_lo, g->partial.p,
-                           static_cast<const unsigned char *>(nullptr));
+    launch_apply<0>(g, grid, g->x.p, g->b.p, l_lo);
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 } CCP_ABI_CATCH
@@ -1270,11 +1419,7 @@ try {
     CCP_TRY(bind(g));
     if (max_t < 1) return CCP_ERR_BAD_ARG;
     max_t = std::min<int>(max_t, g->masked ? kMaskedMaxT : kFusedMaxT);
-    if (!g->x_alt.p) {
-        const size_t elems = (size_t)g->geom.ch_stride * g->desc.channels;
-        CCP_TRY(g->x_alt.alloc(elems));
-        CCP_HIP(hipMemsetAsync(g->x_alt.p, 0, elems * sizeof(double), g->stream));
-    }
+    CCP_TRY(ensure_x_alt(g));
     const int saved_chunk = g->rows_per_chunk, saved_launches = g->last_launches;
     const bool saved_tuned = g->tuned;
     g->tuned = false;                                  // candidates below set rows_per_chunk directly
@@ -1428,9 +1573,7 @@ try {
     CCP_TRY(begin_timing(g));
     long blocks[2] = {0, 0};
     CCP_TRY(one_iteration(g, true, nullptr, blocks));
-    hipLaunchKernelGGL(k_check, dim3((unsigned)C), dim3(kBlock), 0, g->stream, g->partial.p, blocks[0],
-                       g->partial.p + g->partial_region, blocks[1], 0.0, 0, static_cast<SolveState *>(nullptr), g->small.p);
-    CCP_HIP(hipGetLastError());
+    CCP_TRY(launch_check(g, blocks, 0.0, 0, nullptr, g->small.p));
     CCP_TRY(end_timing(g));
     CCP_HIP(hipMemcpyAsync(l1_per_channel, g->small.p, sizeof(double) * C, hipMemcpyDeviceToHost, g->stream));
     CCP_HIP(hipStreamSynchronize(g->stream));
@@ -1444,13 +1587,9 @@ try {
     if (g->ghost_top || g->ghost_bottom) return CCP_ERR_STATE;   // row blocks are driven by the caller (halo exchange)
     if (check_every < 0) return CCP_ERR_BAD_ARG;
     const int C = g->desc.channels;
-    SolveState host{};
-    for (int ch = 0; ch < C; ++ch) {
-        host.active[ch] = 1;
-        host.last_eps[ch] = 10.0;            // sparse-matrix.h:354
-    }
-    CCP_HIP(hipMemcpyAsync(g->state.p, &host, sizeof(host), hipMemcpyHostToDevice, g->stream));
-    CCP_HIP(hipStreamSynchronize(g->stream));
+    SolveState host;
+    CCP_TRY(start_solve_state(g, host));
+    CCP_HIP(hipStreamSynchronize(g->stream));   // the upload read a stack variable; and nothing older runs into the timing
     CCP_TRY(begin_timing(g));
     int issued = 0;
     // `while (eps > epsilon && cnt < max_iteration)`: eps starts at 10
@@ -1471,12 +1610,7 @@ try {
         // that sweep is inside the pass, the channel is re-run from the pass's input buffer (still
         // intact: passes ping-pong) for exactly the missing sweeps — once per solve.
         const size_t elems = (size_t)g->geom.ch_stride * C;
-        if (!g->x_alt.p) {
-            CCP_TRY(g->x_alt.alloc(elems));
-            CCP_HIP(hipMemsetAsync(g->x_alt.p, 0, elems * sizeof(double), g->stream));
-        }
-        if (!g->redo_mask.p) CCP_TRY(g->redo_mask.alloc(kMaxChannels));
-        const size_t plane = (size_t)g->geom.ch_stride * sizeof(double);
+        CCP_TRY(ensure_checked_work(g));
         double *cur = g->x.p, *alt = g->x_alt.p;
         int was_active[kMaxChannels];
         for (int ch = 0; ch < C; ++ch) was_active[ch] = 1;
@@ -1484,7 +1618,6 @@ try {
         // back, so the chip does not idle through a host round trip per pass (a pass of 4096^2 x 3 takes 0.3 ms; the
         // round trip was a tenth of it).  That is safe because the rule is applied on the device, in stream order: a
         // channel that stops in pass n is frozen before pass n+1 starts, which then leaves it — and its buffers — alone.
-        if (!g->sweep_sums.p) CCP_TRY(g->sweep_sums.alloc((size_t)kFusedMaxCheckedT * kMaxChannels));
         struct Queued {
             SolveState st;
             int k0 = 0, T = 0;
@@ -1499,14 +1632,7 @@ try {
             q.T = std::min(g->masked ? kMaskedMaxCheckedT : kFusedMaxCheckedT, max_iteration - k0);
             q.cur = cur;
             q.alt = alt;
-            long blocks[2] = {0, 0};
-            CCP_TRY(launch_fused(g, q.T, cur, alt, active, 2, blocks));
-            // the step of each sweep (a block per channel and sweep), then the rule on them in sweep order
-            hipLaunchKernelGGL(k_sweep_sums_wide, dim3((unsigned)C, (unsigned)q.T), dim3(kBlock), 0, g->stream, g->partial.p, blocks[0],
-                               g->partial.p + g->partial_region, blocks[1], g->sweep_sums.p);
-            hipLaunchKernelGGL(k_decide_sums, dim3(1), dim3(kMaxChannels), 0, g->stream, g->sweep_sums.p, C, q.T, k0 + 1, check_every, epsilon,
-                               g->state.p);
-            CCP_HIP(hipGetLastError());
+            CCP_TRY(checked_pass(g, q.T, cur, alt, k0, check_every, epsilon, [](size_t) { return CCP_OK; }));   // one block: its sums are the sums
             CCP_HIP(hipMemcpyAsync(&q.st, g->state.p, sizeof(q.st), hipMemcpyDeviceToHost, g->stream));
             CCP_HIP(hipEventRecord(q.ev, g->stream));
             k0 += q.T;
@@ -1518,32 +1644,8 @@ try {
             Queued &q = ring[n_seen & 1];
             CCP_HIP(hipEventSynchronize(q.ev));
             host = q.st;
-            any_active = false;
-            for (int ch = 0; ch < C; ++ch) {
-                any_active |= host.active[ch] != 0;
-                if (!was_active[ch] || host.active[ch]) continue;
-                was_active[ch] = 0;                                   // stopped inside this pass
-                const int m = host.iterations[ch] - q.k0;             // sweeps of the pass it wanted: 1..T
-                double *have = q.alt;                                 // where the channel's x_k is
-                if (m < q.T) {
-                    int mask[kMaxChannels] = {0};
-                    mask[ch] = 1;
-                    CCP_HIP(hipMemcpyAsync(g->redo_mask.p, mask, sizeof(mask), hipMemcpyHostToDevice, g->stream));
-                    double *p = q.cur, *r = q.alt;
-                    for (int left = m; left > 0;) {
-                        const int t = std::min(left, g->masked ? kMaskedMaxT : kFusedMaxT);
-                        CCP_TRY(launch_fused(g, t, p, r, g->redo_mask.p));
-                        std::swap(p, r);
-                        left -= t;
-                    }
-                    CCP_HIP(hipStreamSynchronize(g->stream));          // `mask` lives on this stack frame
-                    have = p;
-                }
-                // a frozen channel is never touched again: keep its result in BOTH buffers
-                double *other = (have == q.cur) ? q.alt : q.cur;
-                CCP_HIP(hipMemcpyAsync(other + (size_t)ch * g->geom.ch_stride, have + (size_t)ch * g->geom.ch_stride, plane,
-                                       hipMemcpyDeviceToDevice, g->stream));
-            }
+            // (no ghost rows on this handle: the ghost-row counter never moves)
+            CCP_TRY(settle_stopped(g, host, was_active, q.k0, q.T, q.cur, q.alt, g->half_sweeps_since_refresh, &any_active));
             ++n_seen;
             return CCP_OK;
         };
@@ -1571,10 +1673,7 @@ try {
                 long blocks[2] = {0, 0};
                 CCP_TRY(run_unchecked(g, check_every, active, true, blocks));
                 issued += check_every;
-                hipLaunchKernelGGL(k_check, dim3((unsigned)C), dim3(kBlock), 0, g->stream, g->partial.p, blocks[0],
-                                   g->partial.p + g->partial_region, blocks[1], epsilon, issued, g->state.p,
-                                   static_cast<double *>(nullptr));
-                CCP_HIP(hipGetLastError());
+                CCP_TRY(launch_check(g, blocks, epsilon, issued, g->state.p, nullptr));
                 ++checks;
                 continue;
             }
@@ -1588,10 +1687,7 @@ try {
             long blocks[2] = {0, 0};
             CCP_TRY(one_iteration(g, true, active, blocks));
             ++issued;
-            hipLaunchKernelGGL(k_check, dim3((unsigned)C), dim3(kBlock), 0, g->stream, g->partial.p, blocks[0],
-                               g->partial.p + g->partial_region, blocks[1], epsilon, issued, g->state.p,
-                               static_cast<double *>(nullptr));
-            CCP_HIP(hipGetLastError());
+            CCP_TRY(launch_check(g, blocks, epsilon, issued, g->state.p, nullptr));
             ++checks;
         }
         CCP_HIP(hipMemcpyAsync(&host, g->state.p, sizeof(host), hipMemcpyDeviceToHost, g->stream));
@@ -1599,22 +1695,11 @@ try {
         any_active = false;
         for (int ch = 0; ch < C; ++ch) any_active |= host.active[ch] != 0;
     }
-    CCP_TRY(end_timing(g));
-    CCP_HIP(hipMemcpyAsync(&host, g->state.p, sizeof(host), hipMemcpyDeviceToHost, g->stream));
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    float ms = 0.f;
-    CCP_HIP(hipEventElapsedTime(&ms, g->ev0, g->ev1));
-    g->last_ms = ms;
-    g->timing_pending = false;
-    if (report) {
-        for (int ch = 0; ch < C; ++ch) {
-            report[ch].converged = host.converged[ch];
-            report[ch].iterations = host.converged[ch] ? host.iterations[ch] : issued;
-            report[ch].last_l1_step = host.last_eps[ch];
-            report[ch].seconds = ms * 1e-3;
-        }
-    }
-    return CCP_OK;
+    return finish_solve(g, report, [&](int ch, ccp_gs_report &r) {
+        r.converged = host.converged[ch];
+        r.iterations = host.converged[ch] ? host.iterations[ch] : issued;
+        r.last_l1_step = host.last_eps[ch];
+    }, &host);
 } CCP_ABI_CATCH
 
 namespace {
@@ -1948,21 +2033,11 @@ try {
     }
     hipLaunchKernelGGL((k_lex_convert_tiled<false>), tgrid, dim3(kBlock), 0, g->stream, g->x.p, lex_xd(g), g->geom, lg);
     CCP_HIP(hipGetLastError());
-    CCP_TRY(end_timing(g));
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    float ms = 0.f;
-    CCP_HIP(hipEventElapsedTime(&ms, g->ev0, g->ev1));
-    g->last_ms = ms;
-    g->timing_pending = false;
-    if (report) {
-        for (int ch = 0; ch < C; ++ch) {
-            report[ch].converged = converged[ch];
-            report[ch].iterations = iterations_of[ch];
-            report[ch].last_l1_step = last_eps[ch];
-            report[ch].seconds = ms * 1e-3;
-        }
-    }
-    return CCP_OK;
+    return finish_solve(g, report, [&](int ch, ccp_gs_report &r) {
+        r.converged = converged[ch];
+        r.iterations = iterations_of[ch];
+        r.last_l1_step = last_eps[ch];
+    });
 } CCP_ABI_CATCH
 
 int ccp_debug_lex_tickets(int32_t width, int32_t depth, int32_t groups, uint32_t *order, int64_t capacity, int32_t *strips, int64_t *count)
@@ -1987,13 +2062,7 @@ try {
     if (g->ghost_top || g->ghost_bottom || g->desc.row_count != g->desc.height) return CCP_ERR_STATE;
     const Geom &geo = g->geom;
     const long n = geo.ch_stride;                       // one channel incl. pads (pads stay 0 in b, r, p, Ap)
-    if (!g->cg_r.p) {
-        CCP_TRY(g->cg_r.alloc((size_t)n));
-        CCP_TRY(g->cg_p.alloc((size_t)n));
-        CCP_TRY(g->cg_p2.alloc((size_t)n));
-        CCP_TRY(g->cg_ap.alloc((size_t)n));
-        CCP_TRY(g->cg_state.alloc(1));
-    }
+    CCP_TRY(ensure_cg_work(g));
     hipStream_t s = g->stream;
     dim3 grid((unsigned)((geo.pitch + 2L * kBlock - 1) / (2L * kBlock)), (unsigned)geo.local_rows, 2);
     for (int ch = 0; ch < g->desc.channels; ++ch) {
@@ -2001,21 +2070,16 @@ try {
         CCP_HIP(hipMemsetAsync(g->cg_ap.p, 0, sizeof(double) * n, s));
         // matrix-free A*v on one channel: the kernel sees channel 0 of the offset pointers
         auto spmv = [&](const double *in, double *out) -> int {
-            if (g->masked) hipLaunchKernelGGL((k_apply<2, 0, true>), grid, dim3(kBlock), 0, s, in, out, out, geo, 0, g->partial.p, g->maskp.p);
-            else hipLaunchKernelGGL((k_apply<2, 0>), grid, dim3(kBlock), 0, s, in, out, out, geo, 0, g->partial.p, static_cast<const unsigned char *>(nullptr));
+            launch_apply<0>(g, grid, in, out, 0);
             return hipGetLastError() == hipSuccess ? CCP_OK : CCP_ERR_HIP;
         };
         auto spmv_dot = [&](const double *in, double *out, int *n_partials) -> int {
-            if (g->masked) hipLaunchKernelGGL((k_apply<2, 2, true>), grid, dim3(kBlock), 0, s, in, out, out, geo, 0, g->partial.p, g->maskp.p);
-            else hipLaunchKernelGGL((k_apply<2, 2>), grid, dim3(kBlock), 0, s, in, out, out, geo, 0, g->partial.p, static_cast<const unsigned char *>(nullptr));
             *n_partials = (int)(grid.x * grid.y * grid.z);
+            launch_apply<2>(g, grid, in, out, 0);
             return hipGetLastError() == hipSuccess ? CCP_OK : CCP_ERR_HIP;
         };
-        // CCP_GS_CG_FUSED: 0 the three-pass loop (88 B), 2 the fused loop with the row-per-block pass A (its iterates are
-        // the three-pass loop's bit for bit), otherwise the fused loop with the marching pass A (default)
-        const int fused_mode = getenv("CCP_GS_CG_FUSED") ? atoi(getenv("CCP_GS_CG_FUSED")) : 1;
-        const bool fused = fused_mode != 0;
-        if (!fused) {
+        const int fused_mode = cg_fused_mode();
+        if (fused_mode == 0) {
             CCP_TRY(cg_solve(spmv, spmv_dot, g->b.p + (long)ch * n, g->x.p + (long)ch * n, g->cg_r.p, g->cg_p.p, g->cg_ap.p, n, epsilon,
                              max_iteration, g->cg_state.p, g->partial.p, s, g->ev0, g->ev1, report ? report + ch : nullptr));
             continue;
@@ -2026,13 +2090,8 @@ try {
         const dim3 mgrid((unsigned)((geo.pitch + 2L * kBlock - 1) / (2L * kBlock)), (unsigned)((geo.local_rows + march_rows - 1) / march_rows));
         auto apply = [&](double *xv, const double *rv, const double *p_in, double *p_out, double *apv, int *n_partials) -> int {
             if (fused_mode != 2) {
-                if (g->masked)
-                    hipLaunchKernelGGL((k_cg_apply_march<true>), mgrid, dim3(kBlock), 0, s, xv, rv, p_in, p_out, apv, geo, march_rows, g->partial.p, g->maskp.p, g->cg_state.p,
-                                       0, geo.local_rows);
-                else
-                    hipLaunchKernelGGL((k_cg_apply_march<false>), mgrid, dim3(kBlock), 0, s, xv, rv, p_in, p_out, apv, geo, march_rows, g->partial.p,
-                                       static_cast<const unsigned char *>(nullptr), g->cg_state.p, 0, geo.local_rows);
                 *n_partials = (int)(mgrid.x * mgrid.y);
+                launch_apply_march(g, mgrid, xv, rv, p_in, p_out, apv, march_rows, 0, geo.local_rows);
                 return hipGetLastError() == hipSuccess ? CCP_OK : CCP_ERR_HIP;
             }
             if (g->masked)
@@ -2067,11 +2126,7 @@ int residual_to_small(ccp_grid *g)
     if ((g->shrink_top || g->shrink_bottom) && g->half_sweeps_since_refresh >= g->desc.ghost) return CCP_ERR_STATE;
     const Geom &geo = g->geom;
     dim3 grid((unsigned)((geo.pitch + 2L * kBlock - 1) / (2L * kBlock)), (unsigned)(geo.own_hi - geo.own_lo), (unsigned)C * 2);
-    if (g->masked)
-        hipLaunchKernelGGL((k_apply<2, 1, true>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->b.p, g->b.p, geo, geo.own_lo, g->partial.p, g->maskp.p);
-    else
-        hipLaunchKernelGGL((k_apply<2, 1>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->b.p, g->b.p, geo, geo.own_lo, g->partial.p,
-                           static_cast<const unsigned char *>(nullptr));
+    launch_apply<1>(g, grid, g->x.p, g->b.p, geo.own_lo);
     CCP_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_pair_reduce, dim3((unsigned)C), dim3(kBlock), 0, g->stream, g->partial.p, (long)grid.x * grid.y, g->small.p);
     CCP_HIP(hipGetLastError());
@@ -2329,21 +2384,10 @@ try {
         // step of each of its sweeps (as ccp_grid_gauss_seidel does on one block); the blocks' sums are all-reduced and
         // every rank takes the same decisions.  A channel freezes at the sweep its rule fired at (re-run from the pass's
         // input for the missing sweeps when that sweep lies inside a pass), exactly as on one block.
-        SolveState host{};
-        for (int ch = 0; ch < C; ++ch) {
-            host.active[ch] = 1;
-            host.last_eps[ch] = 10.0;
-        }
-        CCP_HIP(hipMemcpyAsync(g->state.p, &host, sizeof(host), hipMemcpyHostToDevice, g->stream));
+        SolveState host;
+        CCP_TRY(start_solve_state(g, host));
         const size_t elems = (size_t)g->geom.ch_stride * C;
-        if (!g->x_alt.p) {
-            CCP_TRY(g->x_alt.alloc(elems));
-            CCP_HIP(hipMemsetAsync(g->x_alt.p, 0, elems * sizeof(double), g->stream));
-        }
-        if (!g->redo_mask.p) CCP_TRY(g->redo_mask.alloc(kMaxChannels));
-        if (!g->sweep_sums.p) CCP_TRY(g->sweep_sums.alloc((size_t)kFusedMaxCheckedT * kMaxChannels));
-        const int *active = reinterpret_cast<const int *>(g->state.p);
-        const size_t plane = (size_t)g->geom.ch_stride * sizeof(double);
+        CCP_TRY(ensure_checked_work(g));
         const bool shrinking = g->shrink_top || g->shrink_bottom;
         const int max_checked = g->masked ? kMaskedMaxCheckedT : kFusedMaxCheckedT;
         double *cur = g->x.p, *alt = g->x_alt.p;
@@ -2361,45 +2405,13 @@ try {
             if (shrinking) T = std::min(T, (g->desc.ghost - g->half_sweeps_since_refresh) / 2);
             if (T < 1) return CCP_ERR_STATE;
             const int since0 = g->half_sweeps_since_refresh;
-            long blocks[2] = {0, 0};
-            CCP_TRY(launch_fused(g, T, cur, alt, active, 2, blocks));
-            hipLaunchKernelGGL(k_sweep_sums_wide, dim3((unsigned)C, (unsigned)T), dim3(kBlock), 0, g->stream, g->partial.p, blocks[0],
-                               g->partial.p + g->partial_region, blocks[1], g->sweep_sums.p);
-            CCP_HIP(hipGetLastError());
-            CCP_RCCL(api->AllReduce(g->sweep_sums.p, g->sweep_sums.p, (size_t)T * C, ncclDouble, ncclSum, g->comm->comm, g->stream));
-            hipLaunchKernelGGL(k_decide_sums, dim3(1), dim3(64), 0, g->stream, g->sweep_sums.p, C, T, k0 + 1, check_every, epsilon, g->state.p);
-            CCP_HIP(hipGetLastError());
+            CCP_TRY(checked_pass(g, T, cur, alt, k0, check_every, epsilon, [&](size_t count) -> int {
+                CCP_RCCL(api->AllReduce(g->sweep_sums.p, g->sweep_sums.p, count, ncclDouble, ncclSum, g->comm->comm, g->stream));
+                return CCP_OK;
+            }));
             CCP_HIP(hipMemcpyAsync(&host, g->state.p, sizeof(host), hipMemcpyDeviceToHost, g->stream));
             CCP_HIP(hipStreamSynchronize(g->stream));
-            const int since1 = g->half_sweeps_since_refresh;
-            any_active = false;
-            for (int ch = 0; ch < C; ++ch) {
-                any_active |= host.active[ch] != 0;
-                if (!was_active[ch] || host.active[ch]) continue;
-                was_active[ch] = 0;                                   // stopped inside this pass
-                const int m = host.iterations[ch] - k0;               // sweeps of the pass it wanted: 1..T
-                double *have = alt;
-                if (m < T) {
-                    int mask[kMaxChannels] = {0};
-                    mask[ch] = 1;
-                    CCP_HIP(hipMemcpyAsync(g->redo_mask.p, mask, sizeof(mask), hipMemcpyHostToDevice, g->stream));
-                    g->half_sweeps_since_refresh = since0;           // the re-run starts where the pass started
-                    double *p = cur, *q = alt;
-                    for (int left = m; left > 0;) {
-                        const int t = std::min(left, g->masked ? kMaskedMaxT : kFusedMaxT);
-                        CCP_TRY(launch_fused(g, t, p, q, g->redo_mask.p));
-                        std::swap(p, q);
-                        left -= t;
-                    }
-                    CCP_HIP(hipStreamSynchronize(g->stream));          // `mask` lives on this stack frame
-                    g->half_sweeps_since_refresh = since1;
-                    have = p;
-                }
-                // a frozen channel is never touched again: keep its result in BOTH buffers
-                double *other = (have == cur) ? alt : cur;
-                CCP_HIP(hipMemcpyAsync(other + (size_t)ch * g->geom.ch_stride, have + (size_t)ch * g->geom.ch_stride, plane,
-                                       hipMemcpyDeviceToDevice, g->stream));
-            }
+            CCP_TRY(settle_stopped(g, host, was_active, k0, T, cur, alt, since0, &any_active));
             k0 += T;
             std::swap(cur, alt);
         }
@@ -2422,9 +2434,7 @@ try {
             long blocks[2] = {0, 0};
             CCP_TRY(one_iteration(g, true, nullptr, blocks));
             ++cnt;
-            hipLaunchKernelGGL(k_check, dim3((unsigned)C), dim3(kBlock), 0, g->stream, g->partial.p, blocks[0],
-                               g->partial.p + g->partial_region, blocks[1], 0.0, 0, static_cast<SolveState *>(nullptr), g->small.p);
-            CCP_HIP(hipGetLastError());
+            CCP_TRY(launch_check(g, blocks, 0.0, 0, nullptr, g->small.p));
             CCP_RCCL(api->AllReduce(g->small.p, g->small.p, (size_t)C, ncclDouble, ncclSum, g->comm->comm, g->stream));
             double host[kMaxChannels];
             CCP_HIP(hipMemcpyAsync(host, g->small.p, sizeof(double) * C, hipMemcpyDeviceToHost, g->stream));
@@ -2437,21 +2447,11 @@ try {
             if (getenv("CCP_GS_DEBUG")) fprintf(stderr, "[ccp_gs] rowblocked sweep %d: step %.17g (channel 0), epsilon %.17g\n", cnt, eps[0], epsilon);
         }
     }
-    CCP_TRY(end_timing(g));
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    float ms = 0.f;
-    CCP_HIP(hipEventElapsedTime(&ms, g->ev0, g->ev1));
-    g->last_ms = ms;
-    g->timing_pending = false;
-    if (report) {
-        for (int ch = 0; ch < C; ++ch) {
-            report[ch].converged = stop_at[ch] ? 1 : 0;
-            report[ch].iterations = stop_at[ch] ? stop_at[ch] : cnt;
-            report[ch].last_l1_step = eps[ch];
-            report[ch].seconds = ms * 1e-3;
-        }
-    }
-    return CCP_OK;
+    return finish_solve(g, report, [&](int ch, ccp_gs_report &r) {
+        r.converged = stop_at[ch] ? 1 : 0;
+        r.iterations = stop_at[ch] ? stop_at[ch] : cnt;
+        r.last_l1_step = eps[ch];
+    });
 } CCP_ABI_CATCH
 
 // conjugateGradient (sparse-matrix.h:396-434) on a row block: the three-vector loop of ccp_cg.hpp on the OWNED rows (one
@@ -2470,13 +2470,7 @@ try {
     const long n = geo.ch_stride;
     const size_t row = (size_t)2 * geo.pitch;
     const long off = (long)geo.own_lo * (long)row, n_own = (long)(geo.own_hi - geo.own_lo) * (long)row;
-    if (!g->cg_r.p) {
-        CCP_TRY(g->cg_r.alloc((size_t)n));
-        CCP_TRY(g->cg_p.alloc((size_t)n));
-        CCP_TRY(g->cg_p2.alloc((size_t)n));
-        CCP_TRY(g->cg_ap.alloc((size_t)n));
-        CCP_TRY(g->cg_state.alloc(1));
-    }
+    CCP_TRY(ensure_cg_work(g));
     hipStream_t s = g->stream;
     dim3 grid((unsigned)((geo.pitch + 2L * kBlock - 1) / (2L * kBlock)), (unsigned)(geo.own_hi - geo.own_lo), 2);
     // one row of `plane` to each neighbour's ghost row next to its owned rows, theirs into ours
@@ -2516,16 +2510,14 @@ try {
             double *in = const_cast<double *>(in_own) - off;
             double *out = out_own - off;
             CCP_TRY(fetch_rows(in));
-            if (g->masked) hipLaunchKernelGGL((k_apply<2, 0, true>), grid, dim3(kBlock), 0, s, in, out, out, geo, geo.own_lo, g->partial.p, g->maskp.p);
-            else hipLaunchKernelGGL((k_apply<2, 0>), grid, dim3(kBlock), 0, s, in, out, out, geo, geo.own_lo, g->partial.p, static_cast<const unsigned char *>(nullptr));
+            launch_apply<0>(g, grid, in, out, geo.own_lo);
             return hipGetLastError() == hipSuccess ? CCP_OK : CCP_ERR_HIP;
         };
         auto spmv_dot = [&](const double *in_own, double *out_own, int *n_partials) -> int {
             *n_partials = 0;                             // (the loop runs its own dot pass over the owned range)
             return spmv(in_own, out_own);
         };
-        const int fused_mode = getenv("CCP_GS_CG_FUSED") ? atoi(getenv("CCP_GS_CG_FUSED")) : 1;
-        if (fused_mode == 0) {
+        if (cg_fused_mode() == 0) {
             CCP_TRY(cg_solve(spmv, spmv_dot, g->b.p + (long)ch * n + off, g->x.p + (long)ch * n + off, g->cg_r.p + off, g->cg_p.p + off,
                              g->cg_ap.p + off, n_own, epsilon, max_iteration, g->cg_state.p, g->partial.p, s, g->ev0, g->ev1,
                              report ? report + ch : nullptr, sums, true));
@@ -2541,13 +2533,8 @@ try {
             double *rv = const_cast<double *>(rv_own) - off, *p_in = const_cast<double *>(p_in_own) - off;
             CCP_TRY(fetch_rows(rv));
             CCP_TRY(fetch_rows(p_in));
-            if (g->masked)
-                hipLaunchKernelGGL((k_cg_apply_march<true>), mgrid, dim3(kBlock), 0, s, xv_own - off, rv, p_in, p_out_own - off, apv_own - off, geo, march_rows,
-                                   g->partial.p, g->maskp.p, g->cg_state.p, geo.own_lo, geo.own_hi);
-            else
-                hipLaunchKernelGGL((k_cg_apply_march<false>), mgrid, dim3(kBlock), 0, s, xv_own - off, rv, p_in, p_out_own - off, apv_own - off, geo, march_rows,
-                                   g->partial.p, static_cast<const unsigned char *>(nullptr), g->cg_state.p, geo.own_lo, geo.own_hi);
             *n_partials = (int)(mgrid.x * mgrid.y);
+            launch_apply_march(g, mgrid, xv_own - off, rv, p_in, p_out_own - off, apv_own - off, march_rows, geo.own_lo, geo.own_hi);
             return hipGetLastError() == hipSuccess ? CCP_OK : CCP_ERR_HIP;
         };
         CCP_TRY(cg_solve_fused(spmv, apply, g->b.p + (long)ch * n + off, g->x.p + (long)ch * n + off, g->cg_r.p + off, g->cg_p.p + off,
