@@ -77,6 +77,8 @@ ABI_SYMBOLS = (
     "ccp_grid_set_weights_constrained_host", "ccp_grid_set_weights_constrained_device", "ccp_grid_assemble_constrained_rhs",
     "ccp_grid_assemble_constrained_rhs_device", "ccp_grid_constraint_info",
     "ccp_grid_adjoint_begin_device", "ccp_grid_weighted_adjoint_device",
+    "ccp_grid_set_mask_device", "ccp_mask_erode_cross_device", "ccp_panorama_begin_device", "ccp_panorama_add_device",
+    "ccp_panorama_finish_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
     "ccp_grid_attach_comm", "ccp_grid_set_overlap", "ccp_grid_exchange_halos", "ccp_grid_sweep_rowblocked",
     "ccp_grid_gauss_seidel_rowblocked", "ccp_grid_conjugate_gradient_rowblocked", "ccp_grid_residual_norm2_global", "ccp_grid_comm_stats",
@@ -128,6 +130,12 @@ class AdjointInputs(C.Structure):
 class AdjointOutputs(C.Structure):
     """ccp_adjoint_outputs: one ccp_device_array pointer per gradient (NULL: not asked for)."""
     _fields_ = [(n, C.POINTER(DeviceArray)) for n in ADJOINT_OUTPUTS]
+
+
+class PanoramaState(C.Structure):
+    """ccp_panorama_state: the extents and the four views (dx, dy, raw, mask) of a panorama merge."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, C.POINTER(DeviceArray)) for n in ("dx", "dy", "raw", "mask")]
 
 
 _lib: Optional[C.CDLL] = None
@@ -290,6 +298,12 @@ def load() -> C.CDLL:
     L.ccp_grid_constraint_info.argtypes = [vp, vp, vp, vp]
     L.ccp_grid_adjoint_begin_device.argtypes = [vp, da]
     L.ccp_grid_weighted_adjoint_device.argtypes = [vp, C.POINTER(AdjointInputs), C.POINTER(AdjointOutputs)]
+    L.ccp_grid_set_mask_device.argtypes = [vp, da]
+    ps = C.POINTER(PanoramaState)
+    L.ccp_mask_erode_cross_device.argtypes = [i32, vp, i32, i32, da, da, i32]
+    L.ccp_panorama_begin_device.argtypes = [i32, vp, ps, da, da]
+    L.ccp_panorama_add_device.argtypes = [i32, vp, ps, da, da, da]
+    L.ccp_panorama_finish_device.argtypes = [i32, vp, ps]
     L.ccp_grid_last_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i32)]
     L.ccp_grid_region_begin.argtypes = [vp]
     L.ccp_grid_region_end.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i64), C.POINTER(i64)]
@@ -596,6 +610,9 @@ class Grid:
             self.set_mask(mask)
 
     def set_mask(self, mask):
+        """The region from an H x W host array, or from a CUDA tensor (set_mask_tensor: read on the device)."""
+        if getattr(mask, "is_cuda", False):
+            return self.set_mask_tensor(mask)
         mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
         if mask.shape != (self.H, self.W):
             raise ValueError("mask must be H x W")
@@ -1104,16 +1121,22 @@ class Grid:
         sy, sx = t.stride()
         return DeviceArray(t.data_ptr(), DTYPE_F64 if t.dtype == torch.float64 else DTYPE_F32, 0, 0, sy, sx, 0)
 
-    def _mask_array(self, fixed):
+    def _mask_array(self, fixed, name="fixed"):
         """ccp_device_array of an H x W uint8, bool, float32 or float64 mask tensor."""
         torch = self._torch()
         if isinstance(fixed, torch.Tensor) and fixed.dtype == torch.bool:
             fixed = fixed.view(torch.uint8)
         if isinstance(fixed, torch.Tensor) and fixed.dtype == torch.uint8:
             if tuple(fixed.shape) != (self.H, self.W):
-                raise ValueError(f"fixed must be {self.H} x {self.W}, not {tuple(fixed.shape)}")
+                raise ValueError(f"{name} must be {self.H} x {self.W}, not {tuple(fixed.shape)}")
             return DeviceArray(*self._label_array(fixed.unsqueeze(-1)))
-        return self._weight_array(fixed, "fixed")
+        return self._weight_array(fixed, name)
+
+    def set_mask_tensor(self, mask):
+        """set_mask from an H x W uint8, bool, float32 or float64 tensor of the whole canvas (!= 0: inside the region),
+        any strides, read on the device: the mask is never copied to the host.  Synchronises once (two counters)."""
+        m = self._mask_array(mask, "mask")
+        self._on_stream(lambda: self.L.ccp_grid_set_mask_device(self.h, C.byref(m)), "ccp_grid_set_mask_device")
 
     def set_weights_tensor(self, wx=None, wy=None, lam=None, fixed=None):
         """set_weights from H x W float32 / float64 tensors (expanded scalars broadcast); synchronises (the verdict).
@@ -1271,3 +1294,102 @@ class Grid:
         ms, n = C.c_float(), C.c_int32()
         check(self.L.ccp_grid_last_timing(self.h, C.byref(ms), C.byref(n)), "ccp_grid_last_timing")
         return ms.value, n.value
+
+
+# ---- lab8's panorama merge on torch tensors (ccp_panorama_*_device, ccp_mask_erode_cross_device) -----------------------
+# Free functions: every tensor lives on one GPU, any non-negative strides (interleaved, planar-permuted, a window of a
+# larger tensor); each call is enqueued on torch.cuda.current_stream() of that GPU with no host synchronisation.
+def _pano_array(t, name, dtype, shape, dev, output=False):
+    """Check tensor `t` (H x W x C, or H x W when shape[2] == 1) and return its ccp_device_array."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise ValueError(f"{name} must be a torch tensor on a GPU")
+    if t.device.index != dev:
+        raise ValueError(f"{name} must be on cuda:{dev}, not {t.device}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must have dtype {dtype}, not {t.dtype}")
+    if t.dim() == 2 and shape[2] == 1:
+        t = t.unsqueeze(-1)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {' x '.join(str(n) for n in shape)}, not {tuple(t.shape)}")
+    if any(s < 0 for s in t.stride()):
+        raise ValueError(f"{name} has a negative stride")
+    if output and not _no_overlap(t.shape, t.stride()):
+        raise ValueError(f"{name} is an output whose elements overlap")
+    sy, sx, sc = t.stride()
+    return DeviceArray(t.data_ptr(), DTYPE_F32 if dtype == torch.float32 else DTYPE_U8, 0, 0, sy, sx, sc)
+
+
+def _pano_stream(dev):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream)
+
+
+def _pano_state(state):
+    """(PanoramaState, device, H, W, C, the ccp_device_arrays kept alive) of a (dx, dy, raw, mask) tuple."""
+    import torch
+    dx, dy, raw, mask = state
+    if not isinstance(raw, torch.Tensor) or raw.device.type != "cuda" or raw.dim() not in (2, 3):
+        raise ValueError("raw must be an H x W x C torch tensor on a GPU")
+    dev = raw.device.index
+    H, W = raw.shape[0], raw.shape[1]
+    ch = raw.shape[2] if raw.dim() == 3 else 1
+    if ch not in (1, 3):
+        raise ValueError("the merge serves 1 or 3 channels")
+    arrs = [_pano_array(dx, "dx", torch.float32, (H, W, ch), dev, True), _pano_array(dy, "dy", torch.float32, (H, W, ch), dev, True),
+            _pano_array(raw, "raw", torch.uint8, (H, W, ch), dev, True), _pano_array(mask, "mask", torch.uint8, (H, W, 1), dev, True)]
+    return PanoramaState(W, H, ch, 0, *[C.pointer(a) for a in arrs]), dev, H, W, ch, arrs
+
+
+def mask_erode_cross_tensor(mask, times: int, out=None):
+    """`times` (1..8) cross erosions of a u8 H x W mask tensor in one launch (lab8_workload.erode_cross, repeated):
+    255 where every canvas pixel within L1 distance `times` is set, else 0."""
+    import torch
+    if not isinstance(mask, torch.Tensor) or mask.device.type != "cuda" or mask.dim() != 2:
+        raise ValueError("mask must be an H x W torch tensor on a GPU")
+    if not 1 <= int(times) <= 8:
+        raise ValueError("times must be 1..8")
+    dev = mask.device.index
+    H, W = mask.shape
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.uint8, device=mask.device)
+    a = _pano_array(mask, "mask", torch.uint8, (H, W, 1), dev)
+    b = _pano_array(out, "out", torch.uint8, (H, W, 1), dev, True)
+    check(load().ccp_mask_erode_cross_device(dev, _pano_stream(dev), W, H, C.byref(a), C.byref(b), int(times)),
+          "ccp_mask_erode_cross_device")
+    return out
+
+
+def panorama_begin_tensor(img0, mask0, out=None):
+    """The merge state (dx, dy, raw, mask) of the first image: u8 H x W x C colours and its u8 H x W footprint mask.
+    out: four tensors to write into (float32, float32, u8 H x W x C and u8 H x W), allocated when None."""
+    import torch
+    if not isinstance(img0, torch.Tensor) or img0.device.type != "cuda" or img0.dim() not in (2, 3):
+        raise ValueError("img0 must be an H x W x C torch tensor on a GPU")
+    if out is None:
+        shape = tuple(img0.shape)
+        out = (torch.empty(shape, dtype=torch.float32, device=img0.device), torch.empty(shape, dtype=torch.float32, device=img0.device),
+               torch.empty(shape, dtype=torch.uint8, device=img0.device), torch.empty(shape[:2], dtype=torch.uint8, device=img0.device))
+    st, dev, H, W, ch, _keep = _pano_state(out)
+    a = _pano_array(img0, "img0", torch.uint8, (H, W, ch), dev)
+    b = _pano_array(mask0, "mask0", torch.uint8, (H, W, 1), dev)
+    check(load().ccp_panorama_begin_device(dev, _pano_stream(dev), C.byref(st), C.byref(a), C.byref(b)), "ccp_panorama_begin_device")
+    return tuple(out)
+
+
+def panorama_add_tensor(state, img, outer, inner):
+    """One more image merged into `state` (dx, dy, raw, mask) in place, as the body of lab8_workload.merge does with
+    outer = erode_mask2 and inner = erode_mask (u8 H x W)."""
+    import torch
+    st, dev, H, W, ch, _keep = _pano_state(state)
+    a = _pano_array(img, "img", torch.uint8, (H, W, ch), dev)
+    b = _pano_array(outer, "outer", torch.uint8, (H, W, 1), dev)
+    c = _pano_array(inner, "inner", torch.uint8, (H, W, 1), dev)
+    check(load().ccp_panorama_add_device(dev, _pano_stream(dev), C.byref(st), C.byref(a), C.byref(b), C.byref(c)),
+          "ccp_panorama_add_device")
+
+
+def panorama_finish_tensor(state):
+    """EnforceGradientBound on `state` in place: dx, dy along the rim of the union mask recomputed from raw."""
+    st, dev, _H, _W, _ch, _keep = _pano_state(state)
+    check(load().ccp_panorama_finish_device(dev, _pano_stream(dev), C.byref(st)), "ccp_panorama_finish_device")

@@ -10,6 +10,8 @@
 #include "ccp_grid_weighted.hpp"
 #include "ccp_grid_adjoint.hpp"
 #include "ccp_comm.hpp"
+#include "ccp_view_check.hpp"
+#include "ccp_grid_mask.hpp"
 
 #include <algorithm>
 #include <functional>
@@ -74,10 +76,11 @@ struct ccp_grid {
     DevBuf<unsigned char> maskp, tile_live;
     DevBuf<int> tile_rows;       // ... and which of a live tile's own rows do (two ints per tile)
     // the region bytes of image rows y0-1 and y0+local_rows (2 x W, zero where a row does not exist): the blend
-    // assembly reads its neighbours there (ccp_grid_blend.hpp).  Known after ccp_grid_set_mask_host, and after the
-    // device twin on a handle that holds the whole canvas.  mask_border: the region touches the canvas's outer rows
-    // or columns (1 / 0; -1 not known yet, computed at the first clone call).
+    // assembly reads its neighbours there (ccp_grid_blend.hpp).  Known after ccp_grid_set_mask_host / _device, and
+    // after the internal split-layout twin on a handle that holds the whole canvas.  mask_border: the region touches the
+    // canvas's outer rows or columns (1 / 0; -1 not known yet -- the internal twin only -- computed at the first clone call).
     DevBuf<unsigned char> mask_edge;
+    DevBuf<unsigned long long> mask_counters;   // ccp_grid_set_mask_device: owned unknowns, border flag
     bool mask_edge_known = false;
     int mask_border = -1;
     int live_T = -1, live_R = -1, live_lo = -1, live_hi = -1;
@@ -780,6 +783,19 @@ int zero_unmasked(ccp_grid *g, double *plane)
     return CCP_OK;
 }
 
+// What every mask setter does once the new mask bytes are enqueued: what was derived from the old mask goes, and x, b
+// and x_alt are zeroed outside the new region.
+int mask_replaced(ccp_grid *g)
+{
+    g->live_T = -1;                                      // the tile census belongs to the old mask
+    mg_release(g->mg);                                   // ... and so does the multigrid hierarchy
+    g->mg = nullptr;
+    CCP_TRY(zero_unmasked(g, g->x.p));
+    CCP_TRY(zero_unmasked(g, g->b.p));
+    if (g->x_alt.p) CCP_TRY(zero_unmasked(g, g->x_alt.p));
+    return CCP_OK;
+}
+
 // k_weighted_apply: up to kWeightedApplyBlocks blocks per (channel, colour) striding over the colour's cells
 dim3 weighted_apply_grid(const ccp_grid *g)
 {
@@ -1051,6 +1067,7 @@ try {
         if (st == CCP_OK && hipMemset(g->maskp.p, 0, (size_t)geo.ch_stride) != hipSuccess) st = CCP_ERR_HIP;
         if (st == CCP_OK) st = g->mask_edge.alloc(2 * (size_t)d->width);
         if (st == CCP_OK && hipMemset(g->mask_edge.p, 0, 2 * (size_t)d->width) != hipSuccess) st = CCP_ERR_HIP;
+        if (st == CCP_OK) st = g->mask_counters.alloc(2);
     }
     if (st == CCP_OK) st = g->b.alloc(elems);
     g->weighted = (d->flags & CCP_GRID_WEIGHTED) != 0;
@@ -1223,12 +1240,7 @@ try {
     g->mask_edge_known = true;
     g->mask_border = border ? 1 : 0;
     g->unknowns = count;
-    g->live_T = -1;                                      // the tile census belongs to the old mask
-    mg_release(g->mg);                                   // ... and so does the multigrid hierarchy
-    g->mg = nullptr;
-    CCP_TRY(zero_unmasked(g, g->x.p));
-    CCP_TRY(zero_unmasked(g, g->b.p));
-    if (g->x_alt.p) CCP_TRY(zero_unmasked(g, g->x_alt.p));
+    CCP_TRY(mask_replaced(g));
     return CCP_OK;
 } CCP_ABI_CATCH
 
@@ -1320,12 +1332,7 @@ int ccp::grid_set_mask_split_device(ccp_grid *g, const unsigned char *split_mask
     g->mask_edge_known = g->geom.y0 == 0 && g->geom.local_rows == g->geom.H;
     g->mask_border = -1;
     g->unknowns = unknowns;
-    g->live_T = -1;                                      // the tile census belongs to the old mask
-    mg_release(g->mg);                                   // ... and so does the multigrid hierarchy
-    g->mg = nullptr;
-    CCP_TRY(zero_unmasked(g, g->x.p));
-    CCP_TRY(zero_unmasked(g, g->b.p));
-    if (g->x_alt.p) CCP_TRY(zero_unmasked(g, g->x_alt.p));
+    CCP_TRY(mask_replaced(g));
     CCP_HIP(hipStreamSynchronize(g->stream));            // the caller's buffer may go
     return CCP_OK;
 }
@@ -2608,55 +2615,9 @@ try {
 // ============================================================================================
 namespace {
 
-size_t dtype_bytes(int dtype) { return dtype == CCP_DTYPE_U8 ? 1 : dtype == CCP_DTYPE_F32 ? 4 : dtype == CCP_DTYPE_F64 ? 8 : 0; }
-
-// Refusals of a view with extents (n, y, x, c), checked on the host before anything is enqueued.  `dtypes`: bit
-// (1 << CCP_DTYPE_*) of every accepted dtype.  An output must not have two elements at one address.
 int check_view(const ccp_grid *g, const ccp_device_array *a, unsigned dtypes, bool output, long n, long y, long x, long c)
 {
-    if (!a || !a->data || a->reserved != 0) return CCP_ERR_BAD_ARG;
-    if (a->dtype < 0 || a->dtype > 31 || !(dtypes & (1u << a->dtype))) return CCP_ERR_BAD_ARG;
-    const long ext[4] = {n, y, x, c};
-    const long str[4] = {(long)a->stride_n, (long)a->stride_y, (long)a->stride_x, (long)a->stride_c};
-    for (int k = 0; k < 4; ++k)
-        if (str[k] < 0 || ext[k] < 0) return CCP_ERR_BAD_ARG;
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, a->data) != hipSuccess) {
-        (void)hipGetLastError();                            // pageable host memory: not a runtime allocation
-        return CCP_ERR_BAD_ARG;
-    }
-    if (attr.type != hipMemoryTypeDevice || attr.isManaged || attr.device != g->desc.device) return CCP_ERR_BAD_ARG;
-    if (n == 0 || y == 0 || x == 0 || c == 0) return CCP_OK;
-    const size_t es = dtype_bytes(a->dtype);
-    unsigned long long last = 0;                            // element offset of the last element
-    for (int k = 0; k < 4; ++k) last += (unsigned long long)(ext[k] - 1) * (unsigned long long)str[k];
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(a->data)) != hipSuccess) {
-        (void)hipGetLastError();
-        return CCP_ERR_BAD_ARG;
-    }
-    const unsigned long long lo = (unsigned long long)(uintptr_t)a->data, b0 = (unsigned long long)(uintptr_t)base;
-    if (lo < b0 || lo - b0 + (last + 1) * es > size) return CCP_ERR_BAD_ARG;
-    if (output) {
-        // sorted by stride, each stride >= stride * extent of the one below (dimensions of extent 1 do not count)
-        long s_[4], e_[4];
-        int m = 0;
-        for (int k = 0; k < 4; ++k)
-            if (ext[k] > 1) {
-                s_[m] = str[k];
-                e_[m] = ext[k];
-                ++m;
-            }
-        for (int i = 1; i < m; ++i)
-            for (int k = i; k > 0 && s_[k] < s_[k - 1]; --k) {
-                std::swap(s_[k], s_[k - 1]);
-                std::swap(e_[k], e_[k - 1]);
-            }
-        for (int i = 0; i < m; ++i)
-            if (s_[i] < (i ? s_[i - 1] * e_[i - 1] : 1)) return CCP_ERR_BAD_ARG;
-    }
-    return CCP_OK;
+    return check_view_on(g->desc.device, a, dtypes, output, n, y, x, c);
 }
 
 template <typename T>
@@ -3271,6 +3232,39 @@ try {
     if (!g->masked) return CCP_ERR_UNSUPPORTED;
     CCP_TRY(blend_composite(g, view_of<const uint8_t>(canvas), view_of<uint8_t>(out)));
     return edge_timeout_status(g);
+} CCP_ABI_CATCH
+
+int ccp_grid_set_mask_device(ccp_grid *g, const ccp_device_array *mask)
+try {
+    CCP_TRY(not_weighted(g));
+    CCP_TRY(bind(g));
+    if (!g->masked) return CCP_ERR_STATE;
+    CCP_TRY(check_view(g, mask, kF32F64 | kU8, false, 1, g->desc.height, g->desc.width, 1));
+    const Geom &geo = g->geom;
+    const dim3 grid((unsigned)((geo.pitch + kBlock - 1) / kBlock), (unsigned)geo.local_rows + 4);
+    CCP_HIP(hipMemsetAsync(g->mask_counters.p, 0, 2 * sizeof(unsigned long long), g->stream));
+    switch (mask->dtype) {
+    case CCP_DTYPE_U8:
+        hipLaunchKernelGGL(k_mask_split<uint8_t>, grid, dim3(kBlock), 0, g->stream, view_of<const uint8_t>(mask), g->maskp.p, g->mask_edge.p, geo,
+                           g->mask_counters.p);
+        break;
+    case CCP_DTYPE_F32:
+        hipLaunchKernelGGL(k_mask_split<float>, grid, dim3(kBlock), 0, g->stream, view_of<const float>(mask), g->maskp.p, g->mask_edge.p, geo,
+                           g->mask_counters.p);
+        break;
+    default:
+        hipLaunchKernelGGL(k_mask_split<double>, grid, dim3(kBlock), 0, g->stream, view_of<const double>(mask), g->maskp.p, g->mask_edge.p, geo,
+                           g->mask_counters.p);
+    }
+    CCP_HIP(hipGetLastError());
+    unsigned long long counters[2] = {0, 0};
+    CCP_HIP(hipMemcpyAsync(counters, g->mask_counters.p, sizeof counters, hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));            // the two counters, and the caller's mask may go (as the host twin)
+    g->mask_edge_known = true;
+    g->mask_border = counters[1] ? 1 : 0;
+    g->unknowns = (long)counters[0];
+    CCP_TRY(mask_replaced(g));
+    return CCP_OK;
 } CCP_ABI_CATCH
 
 int ccp_grid_assemble_weighted_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes, const float *f,

@@ -15,21 +15,11 @@
 #pragma once
 
 #include "ccp_grid_stencil.hpp"
+#include "ccp_view.hpp"          // View<T>, the one accessor
 
 #include <cstdint>
 
 namespace ccp {
-
-template <typename T>
-struct View {
-    T *p;
-    long sn, sy, sx, sc; // strides in elements
-    __device__ __forceinline__ T &operator()(int y, int x, int c) const { return p[(long)y * sy + (long)x * sx + (long)c * sc]; }
-    __device__ __forceinline__ T &at(int n, int y, int x, int c) const
-    {
-        return p[(long)n * sn + (long)y * sy + (long)x * sx + (long)c * sc];
-    }
-};
 
 // the pin values of k_assemble_rhs, passed by value
 struct Pins {

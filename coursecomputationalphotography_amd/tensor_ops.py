@@ -43,12 +43,19 @@ def _device_index(t) -> int:
 def _grid(W, H, C, dev, mask=None) -> "capi.Grid":
     """A handle whose every call, the solve included, is enqueued on torch's current stream of `dev`."""
     import torch
-    g = capi.Grid(W, H, C, device=dev, mask=None if mask is None else _host_mask(mask))
+    if isinstance(mask, torch.Tensor) and mask.device.type == "cuda":
+        if mask.dtype not in (torch.bool, torch.uint8, torch.float32, torch.float64):
+            mask = mask != 0
+        mask = mask.to(torch.device("cuda", dev))                 # (a mask on another GPU: one device-to-device copy)
+    elif mask is not None:
+        mask = _host_mask(mask)
+    g = capi.Grid(W, H, C, device=dev, mask=mask)
     g.set_stream(torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream)
     return g
 
 
 def _host_mask(mask) -> np.ndarray:
+    """A numpy or CPU-tensor mask as a host array (a CUDA tensor goes to the handle as it is: Grid.set_mask_tensor)."""
     import torch
     if isinstance(mask, torch.Tensor):
         mask = mask.detach().cpu().numpy()
@@ -89,8 +96,8 @@ def solve_channels(gx, gy, constraint, iterations: int, init=None, solver: str =
 def blend_region(gx, gy, canvas, mask, iterations: int, solver: str = "GaussSeidel"):
     """Region blend from a guidance field (ccp::BlendRegion): gx, gy float32 H x W x C tensors, canvas u8 H x W x C
     (the values outside the region and the start vector), mask H x W (non-zero = region).  Returns the composite,
-    a u8 H x W x C tensor.  The mask may be a tensor, but it is copied to the host once: the handle builds its
-    region layout on the host."""
+    a u8 H x W x C tensor.  A CUDA mask tensor is read on the device (capi.Grid.set_mask_tensor); a numpy or CPU
+    mask goes through the host setter."""
     _check_solver(solver)
     dev = _device_index(canvas)
     H, W = canvas.shape[0], canvas.shape[1]
@@ -107,7 +114,7 @@ def blend_region(gx, gy, canvas, mask, iterations: int, solver: str = "GaussSeid
 def seamless_clone(source, target, mask, iterations: int, mixed: bool = False, solver: str = "GaussSeidel"):
     """Seamless cloning (ccp::SeamlessClone) of the u8 H x W x C tensor `source`, already placed on the canvas, into
     `target`: imported (mixed False) or mixed gradients, boundary values and start vector from the target.  mask
-    H x W, copied to the host once (see blend_region); a region touching the canvas border raises CcpError.  Returns
+    H x W (see blend_region); a region touching the canvas border raises CcpError.  Returns
     the composite, a u8 H x W x C tensor."""
     _check_solver(solver)
     dev = _device_index(target)
@@ -118,6 +125,40 @@ def seamless_clone(source, target, mask, iterations: int, mixed: bool = False, s
         g.assemble_clone_tensor(source, target, mixed=mixed, init=1)
         _solve(g, solver, iterations)
         return g.store_u8_composite_tensor(target)
+    finally:
+        g.close()
+
+
+def panorama_merge(images, footprints):
+    """lab8's merge (hw8_pa.cc:749-799) of u8 H x W x C image tensors already warped onto one canvas, with their u8
+    H x W footprint masks: the first image starts the state, every further one is merged in under its footprint eroded
+    2 (outer) and 4 (inner) times with the 3 x 3 cross (:718-722), and the gradients along the rim of the union are
+    recomputed from the merged colours.  Returns (dx, dy, raw, mask): float32, float32, u8 H x W x C and u8 H x W
+    tensors, bit for bit what lab8_workload's numpy restatement computes.  Nothing leaves the device."""
+    if len(images) < 1 or len(images) != len(footprints):
+        raise ValueError("one footprint per image, at least one image")
+    state = capi.panorama_begin_tensor(images[0], footprints[0])
+    for img, foot in zip(images[1:], footprints[1:]):
+        capi.panorama_add_tensor(state, img, capi.mask_erode_cross_tensor(foot, 2), capi.mask_erode_cross_tensor(foot, 4))
+    capi.panorama_finish_tensor(state)
+    return state
+
+
+def panorama_blend(images, footprints, iterations: int = 50, solver: str = "GaussSeidel"):
+    """lab8's panorama blend from device tensors to a device result: panorama_merge, then the Poisson system of the
+    merged field on the union mask with the merged colours as boundary values and start vector (hw8_pa.cc:808-810,
+    50 iterations there), solved by `solver`; returns the composite, a u8 H x W x C tensor.  No image or mask is
+    copied to the host."""
+    _check_solver(solver)
+    dx, dy, raw, mask = panorama_merge(images, footprints)
+    dev = _device_index(raw)
+    H, W = raw.shape[0], raw.shape[1]
+    C = raw.shape[2] if raw.dim() == 3 else 1
+    g = _grid(W, H, C, dev, mask)
+    try:
+        g.assemble_region_rhs_tensor(dx, dy, raw, init_x=True)
+        _solve(g, solver, iterations)
+        return g.store_u8_composite_tensor(raw)
     finally:
         g.close()
 

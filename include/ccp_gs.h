@@ -710,6 +710,50 @@ int ccp_grid_assemble_region_rhs_device(ccp_grid *g, const ccp_device_array *gx,
 int ccp_grid_assemble_clone_device(ccp_grid *g, const ccp_device_array *source, const ccp_device_array *target,
                                    int32_t mode, int32_t init);
 int ccp_grid_store_u8_composite_device(ccp_grid *g, const ccp_device_array *canvas, const ccp_device_array *out);
+/* ccp_grid_set_mask_host from a mask in device memory: `mask` is an H x W view of the WHOLE canvas (stride_c unused),
+ * U8, F32 or F64, non-zero = inside the region.  One pass over the handle's local rows writes the region in the grid's
+ * layout, the rows just above and below the local rows, the count of owned unknowns and whether the region touches the
+ * canvas's outer rows or columns, and leaves the handle exactly as the host twin leaves it on the same mask (the tile
+ * census and the multigrid hierarchy dropped; x, b zeroed outside the region).  A row block dereferences only its local
+ * rows and one row either side, plus row 0, row H-1, column 0 and column W-1 of the whole view (every block reads these
+ * border lines and so finds the same verdict).  The mask is never copied to the host; the call reads back two
+ * counters and so SYNCHRONISES the stream once, as the host twin does.  Weighted handle: CCP_ERR_UNSUPPORTED; not a
+ * Dirichlet-mask grid: CCP_ERR_STATE; a refused view: CCP_ERR_BAD_ARG before anything is enqueued. */
+int ccp_grid_set_mask_device(ccp_grid *g, const ccp_device_array *mask);
+
+/* ---- lab8's panorama merge on the device (hw8_pa.cc:718-799) -----------------------------------------------------------
+ * Free functions on strided device views of device `device`, enqueued on `hip_stream` (a hipStream_t; NULL = the null
+ * stream) without host synchronisation and without device allocation; the views are refused as the _device calls above
+ * refuse them (CCP_ERR_BAD_ARG before anything is enqueued).  They restate, bit for bit, the functions of
+ * coursecomputationalphotography_amd/lab8_workload.py, whose searches are BOUNDED: "first x >= start where a condition
+ * holds" is W when nothing matches and a span that reaches the last column ends at W.  The reference's row loops have no
+ * bound there (hw8_pa.cc:364 reads past the end of a row); that is not reproduced.
+ *
+ * The merge state: dx, dy F32 H x W x channels, raw U8 H x W x channels, mask U8 H x W (stride_c unused); channels is 1
+ * or 3.  All four are outputs (no two elements at one address) and must not overlap each other or any input. */
+typedef struct ccp_panorama_state {
+    int32_t width, height, channels, reserved;   /* reserved: 0 */
+    const ccp_device_array *dx, *dy, *raw, *mask;
+} ccp_panorama_state;
+/* `times` (1..8) erosions with the 3 x 3 cross of a U8 H x W mask (non-zero = set) in ONE launch: out = 255 where every
+ * pixel of the canvas within L1 distance `times` is set, 0 elsewhere; outside the canvas counts as set (cv::erode's
+ * default border).  `out` must not overlap `in`. */
+int ccp_mask_erode_cross_device(int32_t device, void *hip_stream, int32_t width, int32_t height,
+                                const ccp_device_array *in, const ccp_device_array *out, int32_t times);
+/* The first image: dx, dy := forward differences of img0 (U8 H x W x channels) as float for y < H-1, x < W-1 and 0 in the
+ * last row and column (GradientAt), raw := img0, mask := mask0 (U8 H x W, copied as it is). */
+int ccp_panorama_begin_device(int32_t device, void *hip_stream, const ccp_panorama_state *state,
+                              const ccp_device_array *img0, const ccp_device_array *mask0);
+/* One more image merged in place, row by row, every span decided from the mask as it was BEFORE the call:
+ *   MergeImage2 (:338-383) of the gradients of MaskImage(img, outer) into dx and dy, with `inner` as inner mask;
+ *   MergeImage (:385-440) of img into raw under `inner`, skip 1;  MergeImage of `inner` into mask, skip 0.
+ * img U8 H x W x channels, outer and inner U8 H x W (hw8_pa.cc: erode_mask2 and erode_mask).  The masked image's
+ * gradients are formed inside the span copy; there is no H x W x channels temporary. */
+int ccp_panorama_add_device(int32_t device, void *hip_stream, const ccp_panorama_state *state,
+                            const ccp_device_array *img, const ccp_device_array *outer, const ccp_device_array *inner);
+/* EnforceGradientBound (:468-498) in gather form: with rim = mask & ~erode(mask), dx and dy at (x, y), y < H-1, x < W-1,
+ * are recomputed from raw iff rim is set at (x, y-1), (x, y) or (x, y+1). */
+int ccp_panorama_finish_device(int32_t device, void *hip_stream, const ccp_panorama_state *state);
 
 /* ---- Weighted grids (CCP_GRID_WEIGHTED) ------------------------------------------------------------------------------
  * The operator: wx, wy, lambda as H x W float32 host arrays with one row stride in bytes.  wx or wy NULL: 1 everywhere;

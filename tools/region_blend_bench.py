@@ -18,7 +18,16 @@ Byte model of the field assembly (C = 3, init_x): reads gx, gy 24 B, canvas 3 B,
 76 B per pixel (the clone form: source, target 6 B, mask 1 B, b, x 48 B: 55 B).  Kernel times come from a separate
 rocprofv3 --kernel-trace --stats run of this tool (--no-host), not from the host clock here.
 
-usage: region_blend_bench.py [--cases a,b] [--host-channels N] [--no-host] [--out FILE]
+--mask host|device|both adds a leg per case that times the region hand-off alone from a mask tensor ALREADY ON THE GPU,
+on one handle: "host" is the route before ccp_grid_set_mask_device (the tensor copied to the host, ccp_grid_set_mask_host),
+"device" is Grid.set_mask_tensor; "both" alternates the two in one process, `--reps` times each (host clock; both calls
+synchronise).  --merge 4096,8192 adds lab8's merge at those square sizes from images and footprints on the GPU to
+dx, dy, raw, mask on the GPU: the numpy restatement (download, erode, lab8_workload.merge, upload) and
+tensor_ops.panorama_merge, alternated likewise, and whether the two results are equal bit for bit.  --no-blend skips the
+end-to-end cases.
+
+usage: region_blend_bench.py [--cases a,b] [--host-channels N] [--no-host] [--no-blend] [--mask host|device|both]
+                             [--merge SIZES] [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -154,16 +163,95 @@ def host_route(mask, form, images, channels):
     return r, out
 
 
+def spread(ms):
+    return {"median": float(np.median(ms)), "min": float(np.min(ms)), "max": float(np.max(ms)), "n": len(ms)}
+
+
+def mask_leg(name, which, reps):
+    """The region hand-off alone, from a mask tensor on the GPU, alternating the routes on one handle."""
+    import torch
+    from coursecomputationalphotography_amd import tensor_ops
+    mask, _, images = case_inputs(name)
+    H, W = mask.shape
+    t = torch.from_numpy(mask).cuda()
+    g = capi.Grid(W, H, images[-1].shape[2], mask=mask)
+    routes = {"host": lambda: g.set_mask(tensor_ops._host_mask(t)), "device": lambda: g.set_mask_tensor(t)}
+    order = ("host", "device") if which == "both" else (which,)
+    for k in order:
+        routes[k]()                                          # warm-up: first-use costs of either route
+    ms = {k: [] for k in order}
+    for _ in range(reps):
+        for k in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            routes[k]()
+            ms[k].append(ms_since(t0))
+    g.close()
+    res = {"case": name, "leg": "mask", "width": W, "height": H, "region_pixels": int(mask.sum())}
+    res.update({f"set_mask_{k}_ms": spread(v) for k, v in ms.items()})
+    return res
+
+
+def merge_leg(size, reps):
+    """lab8's two-image merge, GPU tensors in, GPU tensors out: numpy restatement against tensor_ops.panorama_merge."""
+    import torch
+    from coursecomputationalphotography_amd import tensor_ops
+    inp = lab8_workload.inputs(size, size)
+    foot1 = inp["img1"].any(axis=2).astype(np.uint8) * 255
+    t_img = [torch.from_numpy(inp["img0"]).cuda(), torch.from_numpy(inp["img1"]).cuda()]
+    t_foot = [torch.from_numpy(inp["mask0"]).cuda(), torch.from_numpy(foot1).cuda()]
+
+    def numpy_route():
+        img0, img1 = (t.cpu().numpy() for t in t_img)
+        m0, f1 = (t.cpu().numpy() for t in t_foot)
+        e2 = lab8_workload.erode_cross(lab8_workload.erode_cross(f1))
+        e4 = lab8_workload.erode_cross(lab8_workload.erode_cross(e2))
+        mg = lab8_workload.merge({"img0": img0, "img1": img1, "mask0": m0, "erode_mask2": e2, "erode_mask": e4})
+        return tuple(torch.from_numpy(mg[k]).cuda() for k in ("dx", "dy", "raw", "mask"))
+
+    routes = {"numpy": numpy_route, "device": lambda: tensor_ops.panorama_merge(t_img, t_foot)}
+    out = {"device": routes["device"]()}                     # warm-up of the device route (module load)
+    ms = {k: [] for k in routes}
+    for _ in range(reps):
+        for k in routes:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out[k] = routes[k]()
+            torch.cuda.synchronize()
+            ms[k].append(ms_since(t0))
+    equal = all(torch.equal(a, b) for a, b in zip(out["numpy"], out["device"]))
+    res = {"leg": "merge", "width": size, "height": size, "channels": 3, "union_pixels": int((out["device"][3] != 0).sum().item()),
+           "results_equal": bool(equal)}
+    res.update({f"merge_{k}_ms": spread(v) for k, v in ms.items()})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="lab8_752x566,disc8192_field,disc8192_clone")
     ap.add_argument("--host-channels", type=int, default=1)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--no-blend", action="store_true")
+    ap.add_argument("--mask", choices=("host", "device", "both"), default=None)
+    ap.add_argument("--merge", default="")
+    ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if capi.device_count() < 1:
         raise SystemExit("region_blend_bench needs an MI355X")
-    for name in a.cases.split(","):
+
+    def emit(res):
+        line = json.dumps(res)
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+    for name in a.cases.split(",") if a.mask else ():
+        emit(mask_leg(name, a.mask, a.reps))
+    for size in [int(v) for v in a.merge.split(",") if v]:
+        emit(merge_leg(size, a.reps))
+    for name in () if a.no_blend else a.cases.split(","):
         mask, form, images = case_inputs(name)
         H, W = mask.shape
         C = images[-1].shape[2]
@@ -177,11 +265,7 @@ def main():
             host, out_host = host_route(mask, form, images, host_ch)
             res.update(host)
             res["composite_equal_on_measured_channels"] = bool(np.array_equal(out_dev[..., :host_ch], out_host[..., :host_ch]))
-        line = json.dumps(res)
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as f:
-                f.write(line + "\n")
+        emit(res)
 
 
 if __name__ == "__main__":
