@@ -14,7 +14,13 @@
 
 #include "ccp_common.hpp"
 
+#include <cstdlib>
+
 namespace ccp {
+
+// The loop CCP_GS_CG_FUSED asks for: 0 the three-pass loop, anything else a fused one (1 by default; the grid handles
+// know a second fused form, 2)
+inline int cg_fused_mode() { return getenv("CCP_GS_CG_FUSED") ? atoi(getenv("CCP_GS_CG_FUSED")) : 1; }
 
 struct CgState {
     int active;

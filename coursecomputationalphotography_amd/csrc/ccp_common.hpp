@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <new>
+#include <type_traits>
 
 #include "ccp_gs.h"
 
@@ -38,6 +39,15 @@ inline int hip_fail(hipError_t e, const char *what, const char *file, int line)
         int s_ = (expr);                 \
         if (s_ != CCP_OK) return s_;     \
     } while (0)
+
+// A run-time bool as a template argument: f(B) with decltype(B)::value == on; returns what f returns (host code that
+// picks between the <true> and the <false> form of a kernel).
+template <typename F>
+auto with_bool(bool on, F &&f)
+{
+    if (on) return f(std::true_type{});
+    else return f(std::false_type{});
+}
 
 // No C++ exception may cross the extern "C" boundary: every entry point is a function-try-block
 // ending in this handler (host allocations of multi-GB schedules, std::thread construction, ...).

@@ -1634,6 +1634,14 @@ int flush_edits(ccp_csr *m)
     return CCP_OK;
 }
 
+// What every entry point that reads the matrix starts with: the handle's device, an uploaded matrix, its edits applied.
+int ready(ccp_csr *m)
+{
+    CCP_TRY(bind(m));
+    if (!m->uploaded) return CCP_ERR_STATE;
+    return flush_edits(m);
+}
+
 // partial-sum scratch large enough for `blocks` block results of two doubles each
 int ensure_partial(ccp_csr *m, long blocks)
 {
@@ -1721,15 +1729,24 @@ int rb_exchange_natural(ccp_csr *m, double *x)
     return rb_messages(m, rb.nat_send_cnt.data(), rb.nat_send_off.data(), rb.nat_recv_cnt.data(), rb.nat_recv_pos.data(), x, m->stream);
 }
 
-// A vector of the block (n_local host values) into the extended natural order on the device: ghosts 0.
+// A row block: `count` device values added up over the ranks, in place and on every rank alike.  One GPU: nothing.
+int all_rank_sum(ccp_csr *m, double *v, int count)
+{
+    if (!m->rb.on) return CCP_OK;
+    const RcclApi *api = rccl_api();
+    if (!api) return CCP_ERR_RCCL;
+    CCP_RCCL(api->AllReduce(v, v, (size_t)count, ncclDouble, ncclSum, m->rb.comm->comm, m->stream));
+    return CCP_OK;
+}
+
+// A vector of the block (n_local host values; none: zeros) into the extended natural order on the device: ghosts 0.
 int rb_stage(ccp_csr *m, double *dst_dev, const double *host_local)
 {
     const ccp_csr::RowBlock &rb = m->rb;
     CCP_HIP(hipMemsetAsync(dst_dev, 0, sizeof(double) * (size_t)std::max(m->n_rows, 1), m->stream));
-    if (rb.n_local) CCP_HIP(hipMemcpyAsync(dst_dev + rb.n_lo, host_local, sizeof(double) * (size_t)rb.n_local, hipMemcpyHostToDevice, m->stream));
+    if (rb.n_local && host_local) CCP_HIP(hipMemcpyAsync(dst_dev + rb.n_lo, host_local, sizeof(double) * (size_t)rb.n_local, hipMemcpyHostToDevice, m->stream));
     return CCP_OK;
 }
-
 
 }  // namespace
 
@@ -2435,9 +2452,7 @@ try {
 
 int ccp_csr_get_colouring(ccp_csr *m, int32_t *colour, int32_t *n_colours)
 try {
-    CCP_TRY(bind(m));
-    if (!m->uploaded) return CCP_ERR_STATE;
-    CCP_TRY(flush_edits(m));
+    CCP_TRY(ready(m));
     if (!n_colours) return CCP_ERR_BAD_ARG;
     // (no colouring from the caller, nothing resolved yet: a raster region takes its canvas parity — detect_region)
     if (m->user_colour.empty() && m->allow_structured && m->allow_region && m->region_state < 0 && !m->multicolour.built && !m->rb.on)
@@ -2458,305 +2473,173 @@ try {
     return CCP_OK;
 } CCP_ABI_CATCH
 
-int ccp_csr_gauss_seidel(ccp_csr *m, const double *b, const double *x0, double *x_out, double epsilon,
-                         int32_t max_iteration, int32_t check_every, int32_t ordering, ccp_gs_report *report)
-try {
-    CCP_TRY(bind(m));
-    if (!m->uploaded) return CCP_ERR_STATE;
-    CCP_TRY(flush_edits(m));
-    if (!b || !x_out || check_every < 0) return CCP_ERR_BAD_ARG;
-    if (m->n_rows != m->n_cols) return CCP_ERR_UNSUPPORTED;   // the reference asserts len(b) == n_cols and sizes x from b
-    if (ordering != CCP_ORDER_LEXICOGRAPHIC && ordering != CCP_ORDER_MULTICOLOUR) return CCP_ERR_BAD_ARG;
-    // a row block: the index-order sweep is one dependence chain through all the blocks — only the colour order shards
-    if (m->rb.on && ordering != CCP_ORDER_MULTICOLOUR) return CCP_ERR_UNSUPPORTED;
-    const bool rowblock = m->rb.on;
-    if (ordering == CCP_ORDER_MULTICOLOUR && m->allow_structured) {
-        // The matrix SolveChannel builds (via Eigen, ConvertFromEigen) is recognised and solved
-        // matrix-free by the grid kernels: same sweep order, same arithmetic, same bits as the
-        // sliced-ELL path, ~20x its speed (temporally blocked sweep).
-        detect_poisson(m);
-        if (m->poisson_w > 0 && colouring_is_checkerboard(m)) {
-            if (!m->grid) {
-                ccp_grid_desc d{m->poisson_w, m->poisson_h, 1, 0, m->poisson_h, 0, m->device, 0};
-                CCP_TRY(ccp_grid_create(&d, &m->grid));
-                (void)grid_set_allow_swap(m->grid, true);  // (results leave through ccp_grid_get_x_host)
-                release_device_csr(m);                     // nothing on the device reads the stored matrix any more
-            }
-            CCP_TRY(ccp_grid_set_stream(m->grid, m->stream));
-            CCP_TRY(ccp_grid_set_b_host(m->grid, 0, b, 0, m->poisson_h));
-            if (x0) CCP_TRY(ccp_grid_set_x_host(m->grid, 0, x0, 0, m->poisson_h));
-            else CCP_TRY(ccp_grid_fill_x(m->grid, 1.0));                       // sparse-matrix.h:352
-            CCP_TRY(ccp_grid_gauss_seidel(m->grid, epsilon, max_iteration, check_every, report));
-            m->last_path = CCP_PATH_POISSON_GRID;
-            return ccp_grid_get_x_host(m->grid, 0, x_out, 0, m->poisson_h);
-        }
+}  // extern "C"
+
+// ---- the steps the solve, product and residual entry points share ----------------------------------------------------
+namespace {
+
+// The Poisson twin, made at first use and bound to the handle's stream; a solve (not a product or a residual) gives the stored device copy back.
+int poisson_twin(ccp_csr *m, bool drop_stored_matrix)
+{
+    if (!m->grid) {
+        ccp_grid_desc d{m->poisson_w, m->poisson_h, 1, 0, m->poisson_h, 0, m->device, 0};
+        CCP_TRY(ccp_grid_create(&d, &m->grid));
+        (void)grid_set_allow_swap(m->grid, true);              // (results leave through ccp_grid_get_x_host)
+        if (drop_stored_matrix) release_device_csr(m);         // nothing on the device reads the stored matrix any more
     }
-    if (m->allow_structured && m->allow_region) {
-        // The 5-point Laplacian of a raster region (a brush / label region of a blend; BASELINE configs[4]):
-        // swept matrix-free by the Dirichlet-mask grid kernels on a canvas the region is embedded in —
-        // 24 B per pixel per PASS of several iterations instead of 92 B per row per iteration.  Same colour
-        // order, same arithmetic, same bits as the sliced-ELL sweep (the step sums to summation order).
-        // In the reference's own order the canvas is swept in raster order (k_lex_wg, Dirichlet-mask variant):
-        // the unknowns are numbered in raster order and every piece of the region keeps its shape on the canvas,
-        // so two coupled unknowns are met in the order of their indices — the index-order sweep, bit for bit.
-        CCP_TRY(detect_region(m, ordering == CCP_ORDER_LEXICOGRAPHIC));
-        if (m->region_state == 1 || (m->region_state == 2 && ordering == CCP_ORDER_LEXICOGRAPHIC)) {
-            const long n = m->n_rows;
-            hipStream_t s = m->stream;
-            ccp_grid *g = m->region_grid;
-            CCP_TRY(ccp_grid_set_stream(g, s));
-            // the first solve runs on the default tiling of a mask grid; a matrix that is solved again gets its tiling
-            // timed once (speed only: ~0.1 s at 41.75 M unknowns, forty times a 50-sweep solve)
-            if (!m->region_tuned && ++m->region_solves >= 2) {
-                CCP_TRY(ccp_grid_tune(g, 8, nullptr, nullptr, nullptr));
-                m->region_tuned = true;
-            }
-            ccp_grid_layout lay{};
-            CCP_TRY(ccp_grid_get_layout(g, &lay));
-            double *gx = static_cast<double *>(lay.x_dev), *gb = static_cast<double *>(lay.b_dev);
-            CCP_HIP(hipMemcpyAsync(m->tmp.p, b, sizeof(double) * n, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL((k_canvas_move<0>), dim3(blocks_for(n)), dim3(kBlock), 0, s, gb, m->tmp.p, m->region_where.p, n, 0.0);
-            CCP_HIP(hipGetLastError());
-            if (x0) {
-                CCP_HIP(hipStreamSynchronize(s));
-                CCP_HIP(hipMemcpyAsync(m->tmp.p, x0, sizeof(double) * n, hipMemcpyHostToDevice, s));
-                hipLaunchKernelGGL((k_canvas_move<0>), dim3(blocks_for(n)), dim3(kBlock), 0, s, gx, m->tmp.p, m->region_where.p, n, 0.0);
-            } else {
-                hipLaunchKernelGGL((k_canvas_move<2>), dim3(blocks_for(n)), dim3(kBlock), 0, s, gx, m->tmp.p, m->region_where.p, n, 1.0);   // sparse-matrix.h:352
-            }
-            CCP_HIP(hipGetLastError());
-            bool swept = true;
-            if (ordering == CCP_ORDER_LEXICOGRAPHIC) {
-                const int st = ccp_grid_gauss_seidel_lexicographic(g, epsilon, max_iteration, check_every, report);
-                if (st == CCP_ERR_UNSUPPORTED) swept = false;     // (an engine chosen by CCP_GS_LEX_MODE that knows no masks)
-                else CCP_TRY(st);
-                m->last_launches = 0;
-            } else {
-                CCP_TRY(ccp_grid_region_begin(g));
-                CCP_TRY(ccp_grid_gauss_seidel(g, epsilon, max_iteration, check_every, report));
-                float region_ms = 0.f;
-                int64_t launches = 0, pass_iters = 0;
-                CCP_TRY(ccp_grid_region_end(g, &region_ms, &launches, &pass_iters));
-                m->last_launches = launches;
-            }
-            if (swept) {
-                CCP_TRY(ccp_grid_get_layout(g, &lay));             // (x and its ping-pong partner may have swapped roles)
-                gx = static_cast<double *>(lay.x_dev);
-                hipLaunchKernelGGL((k_canvas_move<1>), dim3(blocks_for(n)), dim3(kBlock), 0, s, gx, m->tmp.p, m->region_where.p, n, 0.0);
-                CCP_HIP(hipGetLastError());
-                CCP_HIP(hipMemcpyAsync(x_out, m->tmp.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-                CCP_HIP(hipStreamSynchronize(s));
-                m->last_path = CCP_PATH_REGION_GRID;
-                return CCP_OK;
-            }
-        }
-    }
-    if (ordering == CCP_ORDER_LEXICOGRAPHIC && m->allow_structured) {
-        // The reference's own order on the recognised Poisson matrix: the hyperplane pipeline of
-        // ccp_grid_lex.hpp — the same iterates as the level schedule below, without a launch per level
-        // and per sweep.
-        detect_poisson(m);
-        if (m->poisson_w > 1 && m->poisson_h > 1) {
-            if (!m->grid) {
-                ccp_grid_desc d{m->poisson_w, m->poisson_h, 1, 0, m->poisson_h, 0, m->device, 0};
-                CCP_TRY(ccp_grid_create(&d, &m->grid));
-                (void)grid_set_allow_swap(m->grid, true);  // (results leave through ccp_grid_get_x_host)
-                release_device_csr(m);                     // nothing on the device reads the stored matrix any more
-            }
-            CCP_TRY(ccp_grid_set_stream(m->grid, m->stream));
-            CCP_TRY(ccp_grid_set_b_host(m->grid, 0, b, 0, m->poisson_h));
-            if (x0) CCP_TRY(ccp_grid_set_x_host(m->grid, 0, x0, 0, m->poisson_h));
-            else CCP_TRY(ccp_grid_fill_x(m->grid, 1.0));                       // sparse-matrix.h:352
-            CCP_TRY(ccp_grid_gauss_seidel_lexicographic(m->grid, epsilon, max_iteration, check_every, report));
-            m->last_path = CCP_PATH_POISSON_GRID;
-            return ccp_grid_get_x_host(m->grid, 0, x_out, 0, m->poisson_h);
-        }
-    }
-    m->last_path = CCP_PATH_SLICED_ELL;
-    Schedule &sc = ordering == CCP_ORDER_MULTICOLOUR ? m->multicolour : m->lexicographic;
-    CCP_TRY(ordering == CCP_ORDER_MULTICOLOUR ? ensure_multicolour(m) : ensure_lexicographic(m));
+    return ccp_grid_set_stream(m->grid, m->stream);
+}
+
+// b and the start vector; none: the reference's fill (Gauss-Seidel 1, sparse-matrix.h:352; conjugate gradient 0, :397)
+int load_poisson_twin(ccp_csr *m, const double *b, const double *x, double fill)
+{
+    CCP_TRY(ccp_grid_set_b_host(m->grid, 0, b, 0, m->poisson_h));
+    if (x) return ccp_grid_set_x_host(m->grid, 0, x, 0, m->poisson_h);
+    return ccp_grid_fill_x(m->grid, fill);
+}
+
+int solve_on_poisson_twin(ccp_csr *m, const double *b, const double *x0, double *x_out, double epsilon, int max_iteration, int check_every, int ordering, ccp_gs_report *report)
+{
+    CCP_TRY(poisson_twin(m, true));
+    CCP_TRY(load_poisson_twin(m, b, x0, 1.0));
+    if (ordering == CCP_ORDER_LEXICOGRAPHIC) CCP_TRY(ccp_grid_gauss_seidel_lexicographic(m->grid, epsilon, max_iteration, check_every, report));
+    else CCP_TRY(ccp_grid_gauss_seidel(m->grid, epsilon, max_iteration, check_every, report));
+    m->last_path = CCP_PATH_POISSON_GRID;
+    return ccp_grid_get_x_host(m->grid, 0, x_out, 0, m->poisson_h);
+}
+
+// A raster-region Laplacian a solve has already recognised and no edit has touched: products and residuals run on its canvas.
+bool region_twin_stands(const ccp_csr *m) { return m->allow_region && m->region_state > 0 && m->region_grid && !m->edited; }
+
+// A host vector of the region's unknowns onto a plane of the twin's layout, through m->tmp (two in a row: wait in between).
+int to_canvas(ccp_csr *m, void *plane, const double *host)
+{
+    const long n = m->n_rows;
+    CCP_HIP(hipMemcpyAsync(m->tmp.p, host, sizeof(double) * n, hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL((k_canvas_move<0>), dim3(blocks_for(n)), dim3(kBlock), 0, m->stream, static_cast<double *>(plane), m->tmp.p, m->region_where.p, n, 0.0);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+// ... and the unknowns of a plane back to the host; returns once they have arrived.
+int from_canvas(ccp_csr *m, void *plane, double *host_out)
+{
+    const long n = m->n_rows;
+    hipLaunchKernelGGL((k_canvas_move<1>), dim3(blocks_for(n)), dim3(kBlock), 0, m->stream, static_cast<double *>(plane), m->tmp.p, m->region_where.p, n, 0.0);
+    CCP_HIP(hipGetLastError());
+    CCP_HIP(hipMemcpyAsync(host_out, m->tmp.p, sizeof(double) * n, hipMemcpyDeviceToHost, m->stream));
+    CCP_HIP(hipStreamSynchronize(m->stream));
+    return CCP_OK;
+}
+
+// The 5-point Laplacian of a raster region (a brush / label region of a blend; BASELINE configs[4]): swept matrix-free by the
+// Dirichlet-mask grid kernels on a canvas the region is embedded in — 24 B per pixel per PASS of several iterations instead
+// of 92 B per row per iteration.  Same colour order, same arithmetic, same bits as the sliced-ELL sweep (the step sums to
+// summation order).  In the reference's own order the canvas is swept in raster order (k_lex_wg, Dirichlet-mask variant): the
+// unknowns are numbered in raster order and every piece of the region keeps its shape on the canvas, so two coupled
+// unknowns are met in the order of their indices — the index-order sweep, bit for bit.
+// *swept = false: an index-order engine chosen by CCP_GS_LEX_MODE that knows no masks; the caller goes on to the stored matrix.
+int solve_on_region_twin(ccp_csr *m, const double *b, const double *x0, double *x_out, double epsilon, int max_iteration, int check_every, int ordering, ccp_gs_report *report, bool *swept)
+{
     const long n = m->n_rows;
     hipStream_t s = m->stream;
-    CCP_TRY(ensure_partial(m, std::max<long>(sc.group_block_off[sc.n_groups], (rowblock && m->rb.overlap) ? m->rb.part_off.back() : 0)));
-    // stage b (and x0) in natural order, gather into schedule order (a row block: b, x0 and x_out hold the block's
-    // own rows; the ghosts sit around them in the extended order and get their first values from their owners)
+    ccp_grid *g = m->region_grid;
+    CCP_TRY(ccp_grid_set_stream(g, s));
+    // the first solve runs on the default tiling of a mask grid; a matrix that is solved again gets its tiling
+    // timed once (speed only: ~0.1 s at 41.75 M unknowns, forty times a 50-sweep solve)
+    if (!m->region_tuned && ++m->region_solves >= 2) {
+        CCP_TRY(ccp_grid_tune(g, 8, nullptr, nullptr, nullptr));
+        m->region_tuned = true;
+    }
+    ccp_grid_layout lay{};
+    CCP_TRY(ccp_grid_get_layout(g, &lay));
+    CCP_TRY(to_canvas(m, lay.b_dev, b));
+    if (x0) {
+        CCP_HIP(hipStreamSynchronize(s));
+        CCP_TRY(to_canvas(m, lay.x_dev, x0));
+    } else {
+        hipLaunchKernelGGL((k_canvas_move<2>), dim3(blocks_for(n)), dim3(kBlock), 0, s, static_cast<double *>(lay.x_dev), m->tmp.p, m->region_where.p, n, 1.0);   // sparse-matrix.h:352
+        CCP_HIP(hipGetLastError());
+    }
+    *swept = true;
+    if (ordering == CCP_ORDER_LEXICOGRAPHIC) {
+        const int st = ccp_grid_gauss_seidel_lexicographic(g, epsilon, max_iteration, check_every, report);
+        if (st == CCP_ERR_UNSUPPORTED) *swept = false;
+        else CCP_TRY(st);
+        m->last_launches = 0;
+    } else {
+        CCP_TRY(ccp_grid_region_begin(g));
+        CCP_TRY(ccp_grid_gauss_seidel(g, epsilon, max_iteration, check_every, report));
+        float region_ms = 0.f;
+        int64_t launches = 0, pass_iters = 0;
+        CCP_TRY(ccp_grid_region_end(g, &region_ms, &launches, &pass_iters));
+        m->last_launches = launches;
+    }
+    if (!*swept) return CCP_OK;
+    CCP_TRY(ccp_grid_get_layout(g, &lay));             // (x and its ping-pong partner may have swapped roles)
+    CCP_TRY(from_canvas(m, lay.x_dev, x_out));
+    m->last_path = CCP_PATH_REGION_GRID;
+    return CCP_OK;
+}
+
+// A host vector in natural order onto the device: `count` values on one GPU, a row block's own rows (rb_stage, ghosts 0).
+// No host vector: zeros.
+int stage_vector(ccp_csr *m, double *dst, const double *host, long count)
+{
+    if (m->rb.on) return rb_stage(m, dst, host);
+    if (count && host) CCP_HIP(hipMemcpyAsync(dst, host, sizeof(double) * count, hipMemcpyHostToDevice, m->stream));
+    else if (count) CCP_HIP(hipMemsetAsync(dst, 0, sizeof(double) * count, m->stream));
+    return CCP_OK;
+}
+
+// The rows this handle owns, from a device vector in natural order, to the host: all n_rows on one GPU, a row block's own.
+int fetch_owned(ccp_csr *m, double *host_out, const double *src)
+{
+    const size_t at = m->rb.on ? (size_t)m->rb.n_lo : 0, count = m->rb.on ? (size_t)m->rb.n_local : (size_t)m->n_rows;
+    if (count) CCP_HIP(hipMemcpyAsync(host_out, src + at, sizeof(double) * count, hipMemcpyDeviceToHost, m->stream));
+    return CCP_OK;
+}
+
+// Gauss-Seidel on the stored matrix (sliced-ELL image in schedule order) begins: b, the start vector (x0 or 1), the start
+// state of the stop rule on the device and in `host`, the clock's start.
+int stage_sell_solve(ccp_csr *m, const Schedule &sc, const double *b, const double *x0, CsrSolveState &host)
+{
+    const long n = m->n_rows;
+    hipStream_t s = m->stream;
+    // natural order, gathered into schedule order (a row block: the ghosts get their first values from their owners)
     if (n) {
-        if (rowblock) CCP_TRY(rb_stage(m, m->tmp.p, b));
-        else CCP_HIP(hipMemcpyAsync(m->tmp.p, b, sizeof(double) * n, hipMemcpyHostToDevice, s));
+        CCP_TRY(stage_vector(m, m->tmp.p, b, n));
         hipLaunchKernelGGL((k_permute<true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, m->b.p, m->tmp.p, sc.perm.p, n);
         CCP_HIP(hipGetLastError());
         if (x0) {
             CCP_HIP(hipStreamSynchronize(s));
-            if (rowblock) CCP_TRY(rb_stage(m, m->tmp.p, x0));
-            else CCP_HIP(hipMemcpyAsync(m->tmp.p, x0, sizeof(double) * n, hipMemcpyHostToDevice, s));
+            CCP_TRY(stage_vector(m, m->tmp.p, x0, n));
             hipLaunchKernelGGL((k_permute<true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, m->x.p, m->tmp.p, sc.perm.p, n);
         } else {
             hipLaunchKernelGGL(k_fill_n, dim3(blocks_for(n)), dim3(kBlock), 0, s, m->x.p, n, 1.0);   // sparse-matrix.h:352
         }
         CCP_HIP(hipGetLastError());
     }
-    if (rowblock && x0)
+    if (m->rb.on && x0)
         for (int g = 0; g < m->rb.n_colours; ++g) CCP_TRY(rb_exchange_colour(m, g, s));
-    CsrSolveState host{};
     host.active = 1;
     host.last_eps = 10.0;                    // sparse-matrix.h:354
     CCP_HIP(hipMemcpyAsync(m->state.p, &host, sizeof(host), hipMemcpyHostToDevice, s));
     CCP_HIP(hipStreamSynchronize(s));
     CCP_HIP(hipEventRecord(m->ev0, s));
-    const SellView view = sc.view();
-    const int *active = reinterpret_cast<const int *>(m->state.p);
-    double *eps_accum = reinterpret_cast<double *>(reinterpret_cast<char *>(m->state.p) + offsetof(CsrSolveState, eps_accum));
-    int issued = 0;
-    bool any_active = (10.0 > epsilon) && max_iteration > 0 && (n > 0 || rowblock);   // (an empty block still takes part in the stop rule)
-    // narrow groups (<= 1024 rows: level schedules of grids up to ~1000 px wide, small matrices): the
-    // whole solve in one workgroup; wider groups keep one launch per group (one CU cannot feed them)
-    const bool one_block = m->allow_one_block && sc.n_groups > 0 && sc.max_group_slices <= 16;
-    if (any_active && one_block) {
-        hipLaunchKernelGGL(k_sell_gs_one_block, dim3(1), dim3(kSerialBlock), 0, s, view, sc.group_ptr_dev.p, sc.n_groups, m->x.p,
-                           m->b.p, m->state.p, epsilon, max_iteration, check_every);
-        CCP_HIP(hipGetLastError());
-        issued = max_iteration;
-        any_active = false;
-    }
-    if (any_active && ordering == CCP_ORDER_LEXICOGRAPHIC && m->allow_pipeline && sc.level_span >= 0 && sc.n_groups > 1) {
-        // level schedule pipelined over sweeps (k_sell_gs_pipe): n_levels + stride*K launches per batch
-        const int stride = sc.level_span + 1, n_levels = sc.n_groups;
-        unsigned max_blocks = 1;
-        for (int g = 0; g < n_levels; ++g)
-            max_blocks = std::max(max_blocks, (unsigned)(sc.group_block_off[g + 1] - sc.group_block_off[g]));
-        const long per_sweep = sc.group_block_off[n_levels];
-        auto run = [&](int sweeps, double *partial) -> int {
-            for (long tau = 0; tau <= (long)(n_levels - 1) + (long)stride * (sweeps - 1); ++tau) {
-                const long k_hi = std::min<long>(sweeps - 1, tau / stride);
-                const long k_lo = std::max<long>(0, (tau - (n_levels - 1) + stride - 1) / stride);
-                if (k_hi < k_lo) continue;
-                dim3 grid(max_blocks, (unsigned)(k_hi - k_lo + 1));
-                if (partial)
-                    hipLaunchKernelGGL((k_sell_gs_pipe<true>), grid, dim3(kBlock), 0, s, view, sc.group_ptr_dev.p,
-                                       sc.group_block_off_dev.p, (int)tau, stride, (int)k_lo, m->x.p, m->b.p, partial, per_sweep);
-                else
-                    hipLaunchKernelGGL((k_sell_gs_pipe<false>), grid, dim3(kBlock), 0, s, view, sc.group_ptr_dev.p,
-                                       sc.group_block_off_dev.p, (int)tau, stride, (int)k_lo, m->x.p, m->b.p,
-                                       static_cast<double *>(nullptr), per_sweep);
-            }
-            CCP_HIP(hipGetLastError());
-            return CCP_OK;
-        };
-        if (check_every == 0) {
-            while (issued < max_iteration) {               // gridDim.y carries the sweeps in flight: keep it small
-                const int kb = std::min(32768, max_iteration - issued);
-                CCP_TRY(run(kb, nullptr));
-                issued += kb;
-            }
-        } else {
-            const int batch_max = 128;
-            if (m->pipe_partial.n != (size_t)per_sweep * batch_max) CCP_TRY(m->pipe_partial.alloc((size_t)per_sweep * batch_max));
-            if (m->pipe_eps.n != (size_t)batch_max) CCP_TRY(m->pipe_eps.alloc(batch_max));
-            if (m->pipe_snap.n != (size_t)std::max<long>(n, 2)) CCP_TRY(m->pipe_snap.alloc((size_t)std::max<long>(n, 2)));
-            std::vector<double> eps_host(batch_max);
-            bool stopped = false;
-            while (!stopped && issued < max_iteration) {
-                const int kb = std::min(batch_max, max_iteration - issued);
-                CCP_HIP(hipMemcpyAsync(m->pipe_snap.p, m->x.p, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-                CCP_TRY(run(kb, m->pipe_partial.p));
-                hipLaunchKernelGGL(k_reduce_sweeps, dim3((unsigned)kb), dim3(kBlock), 0, s, m->pipe_partial.p, per_sweep, m->pipe_eps.p);
-                CCP_HIP(hipGetLastError());
-                CCP_HIP(hipMemcpyAsync(eps_host.data(), m->pipe_eps.p, sizeof(double) * kb, hipMemcpyDeviceToHost, s));
-                CCP_HIP(hipStreamSynchronize(s));
-                int stop = -1;
-                for (int k = 0; k < kb; ++k) {
-                    if ((issued + k + 1) % check_every != 0) continue;
-                    host.last_eps = eps_host[k];
-                    if (!(host.last_eps > epsilon)) {
-                        stop = k;
-                        break;
-                    }
-                }
-                if (stop >= 0) {
-                    stopped = true;
-                    host.converged = 1;
-                    host.iterations = issued + stop + 1;
-                    if (stop < kb - 1) {      // the pipeline ran past the stop sweep: redo exactly stop+1 sweeps from the snapshot
-                        CCP_HIP(hipMemcpyAsync(m->x.p, m->pipe_snap.p, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-                        CCP_TRY(run(stop + 1, nullptr));
-                    }
-                }
-                issued += kb;
-            }
-            host.active = stopped ? 0 : 1;
-            CCP_HIP(hipMemcpyAsync(m->state.p, &host, sizeof(host), hipMemcpyHostToDevice, s));
-        }
-        any_active = false;
-    }
-    while (any_active && issued < max_iteration) {
-        int checks = 0;
-        while (issued < max_iteration && checks < 8) {
-            const int k = issued + 1;
-            const bool check = check_every > 0 && (k % check_every == 0);
-            for (int g = 0; g < (rowblock ? m->rb.n_colours : sc.n_groups); ++g) {
-                const int s0 = g < sc.n_groups ? sc.group_slice_ptr[g] : 0, s1 = g < sc.n_groups ? sc.group_slice_ptr[g + 1] : 0;
-                if (rowblock && m->rb.overlap) {
-                    // edge slices, then their values on the way while the rest of the colour is swept
-                    ccp_csr::RowBlock &rb = m->rb;
-                    const int waves = kBlock / kWave;
-                    const int ne = rb.edge_cnt[(size_t)g], ni = rb.inner_cnt[(size_t)g];
-                    const unsigned be = (unsigned)((ne + waves - 1) / waves), bi = (unsigned)((ni + waves - 1) / waves);
-                    double *part = m->partial.p + rb.part_off[(size_t)g];
-                    if (ne) {
-                        if (check) hipLaunchKernelGGL((k_sell_gs_list<true>), dim3(be), dim3(kBlock), 0, s, view, rb.slice_list.p + rb.edge_off[(size_t)g], ne, m->x.p, m->b.p, part, active);
-                        else hipLaunchKernelGGL((k_sell_gs_list<false>), dim3(be), dim3(kBlock), 0, s, view, rb.slice_list.p + rb.edge_off[(size_t)g], ne, m->x.p, m->b.p, part, active);
-                    }
-                    CCP_HIP(hipEventRecord(rb.ev_edge, s));
-                    CCP_HIP(hipStreamWaitEvent(rb.stream_comm, rb.ev_edge, 0));
-                    CCP_TRY(rb_exchange_colour(m, g, rb.stream_comm));
-                    CCP_HIP(hipEventRecord(rb.ev_comm, rb.stream_comm));
-                    if (ni) {
-                        if (check) hipLaunchKernelGGL((k_sell_gs_list<true>), dim3(bi), dim3(kBlock), 0, s, view, rb.slice_list.p + rb.inner_off[(size_t)g], ni, m->x.p, m->b.p, part + be, active);
-                        else hipLaunchKernelGGL((k_sell_gs_list<false>), dim3(bi), dim3(kBlock), 0, s, view, rb.slice_list.p + rb.inner_off[(size_t)g], ni, m->x.p, m->b.p, part + be, active);
-                    }
-                    CCP_HIP(hipStreamWaitEvent(s, rb.ev_comm, 0));       // the next colour reads the ghosts
-                    continue;
-                }
-                if (s1 > s0) {
-                    const unsigned blocks = (unsigned)(sc.group_block_off[g + 1] - sc.group_block_off[g]);
-                    if (check)
-                        hipLaunchKernelGGL((k_sell_gs<true>), dim3(blocks), dim3(kBlock), 0, s, view, s0, s1, m->x.p, m->b.p,
-                                           m->partial.p + sc.group_block_off[g], active);
-                    else
-                        hipLaunchKernelGGL((k_sell_gs<false>), dim3(blocks), dim3(kBlock), 0, s, view, s0, s1, m->x.p, m->b.p,
-                                           m->partial.p, active);
-                }
-                // a row block: the colour's new values reach the blocks that reference them before the next colour runs
-                if (rowblock) CCP_TRY(rb_exchange_colour(m, g, s));
-            }
-            CCP_HIP(hipGetLastError());
-            if (check) {
-                const long n_part = (rowblock && m->rb.overlap) ? m->rb.part_off.back() : sc.group_block_off[sc.n_groups];
-                hipLaunchKernelGGL(k_reduce_to, dim3(1), dim3(kBlock), 0, s, m->partial.p, n_part, 1L, eps_accum, 0);
-                if (rowblock) {
-                    // sparse-matrix.h:376 over the whole matrix: the blocks' step sums added up, on every rank alike
-                    const RcclApi *api = rccl_api();
-                    if (!api) return CCP_ERR_RCCL;
-                    CCP_RCCL(api->AllReduce(eps_accum, eps_accum, 1, ncclDouble, ncclSum, m->rb.comm->comm, s));
-                }
-                hipLaunchKernelGGL(k_csr_check, dim3(1), dim3(64), 0, s, m->state.p, epsilon, k);
-                CCP_HIP(hipGetLastError());
-                ++checks;
-            }
-            ++issued;
-        }
-        if (check_every > 0) {
-            CCP_HIP(hipMemcpyAsync(&host, m->state.p, sizeof(host), hipMemcpyDeviceToHost, s));
-            CCP_HIP(hipStreamSynchronize(s));
-            any_active = host.active != 0;
-        }
-    }
+    return CCP_OK;
+}
+
+// The clock's stop, x back in natural order and out, the state the device holds now, the report.
+int finish_sell_solve(ccp_csr *m, const Schedule &sc, double *x_out, CsrSolveState &host, int issued, ccp_gs_report *report)
+{
+    const long n = m->n_rows;
+    hipStream_t s = m->stream;
     CCP_HIP(hipEventRecord(m->ev1, s));
     if (n) {
         hipLaunchKernelGGL((k_permute<false>), dim3(blocks_for(n)), dim3(kBlock), 0, s, m->tmp.p, m->x.p, sc.perm.p, n);
         CCP_HIP(hipGetLastError());
-        if (!rowblock) CCP_HIP(hipMemcpyAsync(x_out, m->tmp.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-        else if (m->rb.n_local) CCP_HIP(hipMemcpyAsync(x_out, m->tmp.p + m->rb.n_lo, sizeof(double) * (size_t)m->rb.n_local, hipMemcpyDeviceToHost, s));
+        CCP_TRY(fetch_owned(m, x_out, m->tmp.p));
     }
     CCP_HIP(hipMemcpyAsync(&host, m->state.p, sizeof(host), hipMemcpyDeviceToHost, s));
     CCP_HIP(hipStreamSynchronize(s));
@@ -2769,33 +2652,276 @@ try {
         report->seconds = ms * 1e-3;
     }
     return CCP_OK;
+}
+
+// Narrow groups (<= 1024 rows: level schedules of grids up to ~1000 px wide, small matrices): the whole solve, stop
+// rule included, in one workgroup; the device's state says where it stopped.
+int gs_one_block(ccp_csr *m, const Schedule &sc, double epsilon, int max_iteration, int check_every, int &issued)
+{
+    hipLaunchKernelGGL(k_sell_gs_one_block, dim3(1), dim3(kSerialBlock), 0, m->stream, sc.view(), sc.group_ptr_dev.p, sc.n_groups, m->x.p,
+                       m->b.p, m->state.p, epsilon, max_iteration, check_every);
+    CCP_HIP(hipGetLastError());
+    issued = max_iteration;
+    return CCP_OK;
+}
+
+// The index order on a level schedule, pipelined.  The stop rule is the host's: 128 sweeps at a time with their step
+// sums, and where the rule stops inside a batch, exactly those sweeps again from a snapshot of x.
+int gs_pipelined(ccp_csr *m, const Schedule &sc, double epsilon, int max_iteration, int check_every, CsrSolveState &host, int &issued)
+{
+    const long n = m->n_rows;
+    hipStream_t s = m->stream;
+    const SellView view = sc.view();
+    const int stride = sc.level_span + 1, n_levels = sc.n_groups;
+    unsigned max_blocks = 1;
+    for (int g = 0; g < n_levels; ++g)
+        max_blocks = std::max(max_blocks, (unsigned)(sc.group_block_off[g + 1] - sc.group_block_off[g]));
+    const long per_sweep = sc.group_block_off[n_levels];
+    // `sweeps` sweeps (k_sell_gs_pipe): n_levels + stride * (sweeps - 1) launches; partial: every sweep's step sums, or null
+    auto run = [&](int sweeps, double *partial) -> int {
+        for (long tau = 0; tau <= (long)(n_levels - 1) + (long)stride * (sweeps - 1); ++tau) {
+            const long k_hi = std::min<long>(sweeps - 1, tau / stride);
+            const long k_lo = std::max<long>(0, (tau - (n_levels - 1) + stride - 1) / stride);
+            if (k_hi < k_lo) continue;
+            dim3 grid(max_blocks, (unsigned)(k_hi - k_lo + 1));
+            with_bool(partial != nullptr, [&](auto L1) {
+                hipLaunchKernelGGL((k_sell_gs_pipe<decltype(L1)::value>), grid, dim3(kBlock), 0, s, view, sc.group_ptr_dev.p,
+                                   sc.group_block_off_dev.p, (int)tau, stride, (int)k_lo, m->x.p, m->b.p, partial, per_sweep);
+            });
+        }
+        CCP_HIP(hipGetLastError());
+        return CCP_OK;
+    };
+    if (check_every == 0) {
+        while (issued < max_iteration) {               // gridDim.y carries the sweeps in flight: keep it small
+            const int kb = std::min(32768, max_iteration - issued);
+            CCP_TRY(run(kb, nullptr));
+            issued += kb;
+        }
+        return CCP_OK;
+    }
+    const int batch_max = 128;
+    if (m->pipe_partial.n != (size_t)per_sweep * batch_max) CCP_TRY(m->pipe_partial.alloc((size_t)per_sweep * batch_max));
+    if (m->pipe_eps.n != (size_t)batch_max) CCP_TRY(m->pipe_eps.alloc(batch_max));
+    if (m->pipe_snap.n != (size_t)std::max<long>(n, 2)) CCP_TRY(m->pipe_snap.alloc((size_t)std::max<long>(n, 2)));
+    std::vector<double> eps_host(batch_max);
+    bool stopped = false;
+    while (!stopped && issued < max_iteration) {
+        const int kb = std::min(batch_max, max_iteration - issued);
+        CCP_HIP(hipMemcpyAsync(m->pipe_snap.p, m->x.p, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+        CCP_TRY(run(kb, m->pipe_partial.p));
+        hipLaunchKernelGGL(k_reduce_sweeps, dim3((unsigned)kb), dim3(kBlock), 0, s, m->pipe_partial.p, per_sweep, m->pipe_eps.p);
+        CCP_HIP(hipGetLastError());
+        CCP_HIP(hipMemcpyAsync(eps_host.data(), m->pipe_eps.p, sizeof(double) * kb, hipMemcpyDeviceToHost, s));
+        CCP_HIP(hipStreamSynchronize(s));
+        int stop = -1;
+        for (int k = 0; k < kb && stop < 0; ++k) {
+            if ((issued + k + 1) % check_every != 0) continue;
+            host.last_eps = eps_host[k];
+            if (!(host.last_eps > epsilon)) stop = k;
+        }
+        if (stop >= 0) {
+            stopped = true;
+            host.converged = 1;
+            host.iterations = issued + stop + 1;
+            if (stop < kb - 1) {      // the pipeline ran past the stop sweep: redo exactly stop+1 sweeps from the snapshot
+                CCP_HIP(hipMemcpyAsync(m->x.p, m->pipe_snap.p, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+                CCP_TRY(run(stop + 1, nullptr));
+            }
+        }
+        issued += kb;
+    }
+    host.active = stopped ? 0 : 1;
+    CCP_HIP(hipMemcpyAsync(m->state.p, &host, sizeof(host), hipMemcpyHostToDevice, s));
+    return CCP_OK;
+}
+
+// Colour g of a row block with its exchange hidden: the edge slices, then their values on the way on the block's
+// second stream while the rest of the colour is swept.
+int gs_overlapped_colour(ccp_csr *m, const SellView &view, int g, bool check, const int *active)
+{
+    ccp_csr::RowBlock &rb = m->rb;
+    hipStream_t s = m->stream;
+    const int waves = kBlock / kWave, ne = rb.edge_cnt[(size_t)g], ni = rb.inner_cnt[(size_t)g];
+    const unsigned be = (unsigned)((ne + waves - 1) / waves), bi = (unsigned)((ni + waves - 1) / waves);
+    double *part = m->partial.p + rb.part_off[(size_t)g];
+    auto sweep_list = [&](const int *list, int count, unsigned blocks, double *partial) {
+        with_bool(check, [&](auto L1) { hipLaunchKernelGGL((k_sell_gs_list<decltype(L1)::value>), dim3(blocks), dim3(kBlock), 0, s, view, list, count, m->x.p, m->b.p, partial, active); });
+    };
+    if (ne) sweep_list(rb.slice_list.p + rb.edge_off[(size_t)g], ne, be, part);
+    CCP_HIP(hipEventRecord(rb.ev_edge, s));
+    CCP_HIP(hipStreamWaitEvent(rb.stream_comm, rb.ev_edge, 0));
+    CCP_TRY(rb_exchange_colour(m, g, rb.stream_comm));
+    CCP_HIP(hipEventRecord(rb.ev_comm, rb.stream_comm));
+    if (ni) sweep_list(rb.slice_list.p + rb.inner_off[(size_t)g], ni, bi, part + be);
+    CCP_HIP(hipStreamWaitEvent(s, rb.ev_comm, 0));       // the next colour reads the ghosts
+    return CCP_OK;
+}
+
+// One launch per group and sweep (wide groups: one CU cannot feed them; every row block).  The stop rule is the device's: k_csr_check
+// clears the state's `active` word and the launches queued behind it do nothing; the host reads the word back after every 8 checks.
+int gs_by_groups(ccp_csr *m, const Schedule &sc, double epsilon, int max_iteration, int check_every, CsrSolveState &host, int &issued)
+{
+    hipStream_t s = m->stream;
+    const bool rowblock = m->rb.on;
+    const SellView view = sc.view();
+    const int *active = reinterpret_cast<const int *>(m->state.p);
+    double *eps_accum = reinterpret_cast<double *>(reinterpret_cast<char *>(m->state.p) + offsetof(CsrSolveState, eps_accum));
+    bool any_active = true;
+    while (any_active && issued < max_iteration) {
+        int checks = 0;
+        while (issued < max_iteration && checks < 8) {
+            const int k = issued + 1;
+            const bool check = check_every > 0 && (k % check_every == 0);
+            for (int g = 0; g < (rowblock ? m->rb.n_colours : sc.n_groups); ++g) {
+                if (rowblock && m->rb.overlap) {
+                    CCP_TRY(gs_overlapped_colour(m, view, g, check, active));
+                    continue;
+                }
+                const int s0 = g < sc.n_groups ? sc.group_slice_ptr[g] : 0, s1 = g < sc.n_groups ? sc.group_slice_ptr[g + 1] : 0;
+                if (s1 > s0) {
+                    const unsigned blocks = (unsigned)(sc.group_block_off[g + 1] - sc.group_block_off[g]);
+                    with_bool(check, [&](auto L1) {
+                        hipLaunchKernelGGL((k_sell_gs<decltype(L1)::value>), dim3(blocks), dim3(kBlock), 0, s, view, s0, s1, m->x.p, m->b.p,
+                                           m->partial.p + sc.group_block_off[g], active);
+                    });
+                }
+                // a row block: the colour's new values reach the blocks that reference them before the next colour runs
+                if (rowblock) CCP_TRY(rb_exchange_colour(m, g, s));
+            }
+            CCP_HIP(hipGetLastError());
+            if (check) {
+                const long n_part = (rowblock && m->rb.overlap) ? m->rb.part_off.back() : sc.group_block_off[sc.n_groups];
+                hipLaunchKernelGGL(k_reduce_to, dim3(1), dim3(kBlock), 0, s, m->partial.p, n_part, 1L, eps_accum, 0);
+                CCP_TRY(all_rank_sum(m, eps_accum, 1));   // (a row block: sparse-matrix.h:376 over the whole matrix)
+                hipLaunchKernelGGL(k_csr_check, dim3(1), dim3(64), 0, s, m->state.p, epsilon, k);
+                CCP_HIP(hipGetLastError());
+                ++checks;
+            }
+            ++issued;
+        }
+        if (check_every > 0) {
+            CCP_HIP(hipMemcpyAsync(&host, m->state.p, sizeof(host), hipMemcpyDeviceToHost, s));
+            CCP_HIP(hipStreamSynchronize(s));
+            any_active = host.active != 0;
+        }
+    }
+    return CCP_OK;
+}
+
+// The work vectors of conjugate gradient on the stored matrix (sliced-ELL image in natural order).
+int ensure_csr_cg_work(ccp_csr *m)
+{
+    const size_t need = (size_t)std::max<long>(m->n_rows, 2);
+    if (m->cg_state.p && m->cg_p.n >= need) return CCP_OK;    // (the state is allocated last: it stands for all three)
+    CCP_TRY(m->cg_p.alloc(need));
+    CCP_TRY(m->cg_ap.alloc(need));
+    return m->cg_state.alloc(1);
+}
+
+// out := A in over the natural image; DOT 2: with the block sums of in'(A in) in m->partial, *n_partials of them.  A row
+// block fetches the ghosts of `in` from their owners first.
+template <int DOT>
+struct NaturalSpmv {
+    ccp_csr *m;
+    SellView view;
+    int n_slices;
+    unsigned blocks;
+    explicit NaturalSpmv(ccp_csr *h) : m(h), view(h->natural.view()), n_slices(h->natural.n_slices),
+        blocks((unsigned)std::min<long>(2048, (n_slices + kBlock / kWave - 1) / (kBlock / kWave))) {}   // (k_sell_apply strides)
+    int operator()(const double *in, double *out, int *n_partials = nullptr) const
+    {
+        if (n_partials) *n_partials = 0;
+        if (m->rb.on) CCP_TRY(rb_exchange_natural(m, const_cast<double *>(in)));
+        if (n_slices == 0) return CCP_OK;
+        hipLaunchKernelGGL((k_sell_apply<DOT>), dim3(blocks), dim3(kBlock), 0, m->stream, view, n_slices, in, out, in, m->partial.p);
+        if (n_partials) *n_partials = (int)blocks;
+        return hipGetLastError() == hipSuccess ? CCP_OK : CCP_ERR_HIP;
+    }
+};
+
+// A row block's dot products: the partial sums reduced to one (the communicator's scratch words), then added up over the ranks.
+struct AllRankSums {
+    ccp_csr *m;
+    int operator()(double *partial, int *count, const double **sum_at, int slot) const
+    {
+        if (!m->rb.on) return CCP_OK;
+        double *total = reinterpret_cast<double *>(m->rb.comm->scratch.p) + slot;
+        hipLaunchKernelGGL(k_reduce_to, dim3(1), dim3(kBlock), 0, m->stream, partial, (long)*count, 1L, total, 0);
+        CCP_HIP(hipGetLastError());
+        *count = 1;
+        *sum_at = total;
+        return all_rank_sum(m, total, 1);
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int ccp_csr_gauss_seidel(ccp_csr *m, const double *b, const double *x0, double *x_out, double epsilon,
+                         int32_t max_iteration, int32_t check_every, int32_t ordering, ccp_gs_report *report)
+try {
+    CCP_TRY(ready(m));
+    if (!b || !x_out || check_every < 0) return CCP_ERR_BAD_ARG;
+    if (m->n_rows != m->n_cols) return CCP_ERR_UNSUPPORTED;   // the reference asserts len(b) == n_cols and sizes x from b
+    if (ordering != CCP_ORDER_LEXICOGRAPHIC && ordering != CCP_ORDER_MULTICOLOUR) return CCP_ERR_BAD_ARG;
+    // a row block: the index-order sweep is one dependence chain through all the blocks — only the colour order shards
+    if (m->rb.on && ordering != CCP_ORDER_MULTICOLOUR) return CCP_ERR_UNSUPPORTED;
+    const bool rowblock = m->rb.on;
+    if (ordering == CCP_ORDER_MULTICOLOUR && m->allow_structured) {
+        // The matrix SolveChannel builds (via Eigen, ConvertFromEigen) is recognised and solved matrix-free by the grid kernels:
+        // same sweep order, same arithmetic, same bits as the sliced-ELL path, ~20x its speed (temporally blocked sweep).
+        detect_poisson(m);
+        if (m->poisson_w > 0 && colouring_is_checkerboard(m))
+            return solve_on_poisson_twin(m, b, x0, x_out, epsilon, max_iteration, check_every, ordering, report);
+    }
+    if (m->allow_structured && m->allow_region) {
+        CCP_TRY(detect_region(m, ordering == CCP_ORDER_LEXICOGRAPHIC));
+        if (m->region_state == 1 || (m->region_state == 2 && ordering == CCP_ORDER_LEXICOGRAPHIC)) {
+            bool swept = false;
+            CCP_TRY(solve_on_region_twin(m, b, x0, x_out, epsilon, max_iteration, check_every, ordering, report, &swept));
+            if (swept) return CCP_OK;
+        }
+    }
+    if (ordering == CCP_ORDER_LEXICOGRAPHIC && m->allow_structured) {
+        // The reference's own order on the recognised Poisson matrix: the hyperplane pipeline of ccp_grid_lex.hpp — the same
+        // iterates as the level schedule below, without a launch per level and per sweep.
+        detect_poisson(m);
+        if (m->poisson_w > 1 && m->poisson_h > 1)
+            return solve_on_poisson_twin(m, b, x0, x_out, epsilon, max_iteration, check_every, ordering, report);
+    }
+    m->last_path = CCP_PATH_SLICED_ELL;
+    Schedule &sc = ordering == CCP_ORDER_MULTICOLOUR ? m->multicolour : m->lexicographic;
+    CCP_TRY(ordering == CCP_ORDER_MULTICOLOUR ? ensure_multicolour(m) : ensure_lexicographic(m));
+    const long n = m->n_rows;
+    CCP_TRY(ensure_partial(m, std::max<long>(sc.group_block_off[sc.n_groups], (rowblock && m->rb.overlap) ? m->rb.part_off.back() : 0)));
+    CsrSolveState host{};
+    CCP_TRY(stage_sell_solve(m, sc, b, x0, host));
+    int issued = 0;
+    const bool any_active = (10.0 > epsilon) && max_iteration > 0 && (n > 0 || rowblock);   // (an empty block still takes part in the stop rule)
+    const bool one_block = m->allow_one_block && sc.n_groups > 0 && sc.max_group_slices <= 16;
+    if (any_active && one_block) CCP_TRY(gs_one_block(m, sc, epsilon, max_iteration, check_every, issued));
+    else if (any_active && ordering == CCP_ORDER_LEXICOGRAPHIC && m->allow_pipeline && sc.level_span >= 0 && sc.n_groups > 1)
+        CCP_TRY(gs_pipelined(m, sc, epsilon, max_iteration, check_every, host, issued));
+    else if (any_active) CCP_TRY(gs_by_groups(m, sc, epsilon, max_iteration, check_every, host, issued));
+    return finish_sell_solve(m, sc, x_out, host, issued, report);
 } CCP_ABI_CATCH
 
 int ccp_csr_conjugate_gradient(ccp_csr *m, const double *b, const double *init, double *x_out, double epsilon,
                                int32_t max_iteration, ccp_gs_report *report)
 try {
-    CCP_TRY(bind(m));
-    if (!m->uploaded) return CCP_ERR_STATE;
-    CCP_TRY(flush_edits(m));
+    CCP_TRY(ready(m));
     const bool rowblock = m->rb.on;
     if ((!b || !x_out) && !(rowblock && m->rb.n_local == 0)) return CCP_ERR_BAD_ARG;
     if (m->n_rows != m->n_cols) return CCP_ERR_UNSUPPORTED;
     if (m->allow_structured) {
-        // SolveChannel's matrix at the unchanged call site (PhotoMontage.cpp:613): matrix-free SpMV of the
-        // grid path (16 B per pixel instead of ~92 B per row of the sliced-ELL image); same row order in
-        // the products, reductions tree-ordered either way
+        // SolveChannel's matrix at the unchanged call site (PhotoMontage.cpp:613): matrix-free SpMV of the grid path (16 B per pixel
+        // instead of ~92 B per row of the sliced-ELL image); same row order in the products, reductions tree-ordered either way
         detect_poisson(m);
         if (m->poisson_w > 1 && m->poisson_h > 1) {
-            if (!m->grid) {
-                ccp_grid_desc d{m->poisson_w, m->poisson_h, 1, 0, m->poisson_h, 0, m->device, 0};
-                CCP_TRY(ccp_grid_create(&d, &m->grid));
-                (void)grid_set_allow_swap(m->grid, true);  // (results leave through ccp_grid_get_x_host)
-                release_device_csr(m);                     // nothing on the device reads the stored matrix any more
-            }
-            CCP_TRY(ccp_grid_set_stream(m->grid, m->stream));
-            CCP_TRY(ccp_grid_set_b_host(m->grid, 0, b, 0, m->poisson_h));
-            if (init) CCP_TRY(ccp_grid_set_x_host(m->grid, 0, init, 0, m->poisson_h));
-            else CCP_TRY(ccp_grid_fill_x(m->grid, 0.0));                       // sparse-matrix.h:397
+            CCP_TRY(poisson_twin(m, true));
+            CCP_TRY(load_poisson_twin(m, b, init, 0.0));
             CCP_TRY(ccp_grid_conjugate_gradient(m->grid, epsilon, max_iteration, report));
             return ccp_grid_get_x_host(m->grid, 0, x_out, 0, m->poisson_h);
         }
@@ -2803,79 +2929,35 @@ try {
     CCP_TRY(ensure_natural(m));
     const long n = m->n_rows;
     hipStream_t s = m->stream;
-    if (!m->cg_p.p || m->cg_p.n < (size_t)std::max<long>(n, 2)) {
-        CCP_TRY(m->cg_p.alloc((size_t)std::max<long>(n, 2)));
-        CCP_TRY(m->cg_ap.alloc((size_t)std::max<long>(n, 2)));
-        CCP_TRY(m->cg_state.alloc(1));
-    }
-    const unsigned spmv_blocks = (unsigned)std::min<long>(2048, (m->natural.n_slices + kBlock / kWave - 1) / (kBlock / kWave));   // (k_sell_apply strides)
-    CCP_TRY(ensure_partial(m, std::max<long>(2048, spmv_blocks)));
-    if (rowblock) {
-        // b, init, x_out: the block's own rows.  The loop runs on the extended system: a ghost is an empty row, so its
-        // entries of A p and r are zero and take no part in the dot products; its entry of the vector A is applied to
-        // comes from its owner before every product, and every dot product is added up over the ranks.
-        CCP_TRY(rb_stage(m, m->b.p, b));
-        if (init) CCP_TRY(rb_stage(m, m->x.p, init));
-        else CCP_HIP(hipMemsetAsync(m->x.p, 0, sizeof(double) * (size_t)std::max<long>(n, 1), s));
-    } else if (n) {
-        CCP_HIP(hipMemcpyAsync(m->b.p, b, sizeof(double) * n, hipMemcpyHostToDevice, s));
-        if (init) CCP_HIP(hipMemcpyAsync(m->x.p, init, sizeof(double) * n, hipMemcpyHostToDevice, s));
-        else CCP_HIP(hipMemsetAsync(m->x.p, 0, sizeof(double) * n, s));                 // sparse-matrix.h:397
-    }
-    const SellView view = m->natural.view();
-    const int n_slices = m->natural.n_slices;
-    auto spmv = [&](const double *in, double *out) -> int {
-        if (rowblock) CCP_TRY(rb_exchange_natural(m, const_cast<double *>(in)));
-        if (n_slices == 0) return CCP_OK;
-        hipLaunchKernelGGL((k_sell_apply<0>), dim3(spmv_blocks), dim3(kBlock), 0, s, view, n_slices, in, out, in, m->partial.p);
-        return hipGetLastError() == hipSuccess ? CCP_OK : CCP_ERR_HIP;
-    };
-    auto spmv_dot = [&](const double *in, double *out, int *n_partials) -> int {
-        *n_partials = 0;
-        if (rowblock) CCP_TRY(rb_exchange_natural(m, const_cast<double *>(in)));
-        if (n_slices == 0) return CCP_OK;
-        hipLaunchKernelGGL((k_sell_apply<2>), dim3(spmv_blocks), dim3(kBlock), 0, s, view, n_slices, in, out, in, m->partial.p);
-        *n_partials = (int)spmv_blocks;
-        return hipGetLastError() == hipSuccess ? CCP_OK : CCP_ERR_HIP;
-    };
-    if (rowblock) {
-        const RcclApi *api = rccl_api();
-        if (!api) return CCP_ERR_RCCL;
-        double *total = reinterpret_cast<double *>(m->rb.comm->scratch.p);     // (the communicator's own scratch words)
-        auto sums = [&](double *partial, int *count, const double **sum_at, int slot) -> int {
-            hipLaunchKernelGGL(k_reduce_to, dim3(1), dim3(kBlock), 0, s, partial, (long)*count, 1L, total + slot, 0);
-            CCP_HIP(hipGetLastError());
-            CCP_RCCL(api->AllReduce(total + slot, total + slot, 1, ncclDouble, ncclSum, m->rb.comm->comm, s));
-            *count = 1;
-            *sum_at = total + slot;
-            return CCP_OK;
-        };
-        CCP_TRY(cg_solve(spmv, spmv_dot, m->b.p, m->x.p, m->tmp.p, m->cg_p.p, m->cg_ap.p, n, epsilon, max_iteration, m->cg_state.p,
-                         m->partial.p, s, m->ev0, m->ev1, report, sums, true));
-        if (m->rb.n_local) CCP_HIP(hipMemcpyAsync(x_out, m->x.p + m->rb.n_lo, sizeof(double) * (size_t)m->rb.n_local, hipMemcpyDeviceToHost, s));
-        CCP_HIP(hipStreamSynchronize(s));
-        return CCP_OK;
-    }
-    // One GPU: the fused loop (ccp_cg.hpp: 12 nnz + 72 B per row and iteration instead of 12 nnz + 88; the same iterates
-    // bit for bit).  CCP_GS_CG_FUSED=0: the three-pass loop (the tests run both).  A row block keeps the three-pass loop:
-    // the fused pass would need the ghost rows' r as well as their p before every product (two exchanges, not one).
-    const bool fused = !(getenv("CCP_GS_CG_FUSED") && atoi(getenv("CCP_GS_CG_FUSED")) == 0);
-    if (fused && n_slices > 0) {
-        if (m->cg_p2.n < (size_t)std::max<long>(n, 2)) CCP_TRY(m->cg_p2.alloc((size_t)std::max<long>(n, 2)));
-        CCP_HIP(hipMemsetAsync(m->cg_p2.p, 0, sizeof(double) * (size_t)std::max<long>(n, 2), s));
+    CCP_TRY(ensure_csr_cg_work(m));
+    const NaturalSpmv<0> spmv(m);
+    const NaturalSpmv<2> spmv_dot(m);
+    CCP_TRY(ensure_partial(m, std::max<long>(2048, spmv.blocks)));
+    // A row block: b, init, x_out hold the block's own rows and the loop runs on the extended system: a ghost is an empty row (its entries
+    // of A p and r are zero and take no part in the dot products), its entry of the vector A is applied to comes from its owner before
+    // every product, and every dot product is added up over the ranks.
+    CCP_TRY(stage_vector(m, m->b.p, b, n));
+    CCP_TRY(stage_vector(m, m->x.p, init, n));      // (no init: x = 0, sparse-matrix.h:397)
+    // One GPU: the fused loop (ccp_cg.hpp: 12 nnz + 72 B per row and iteration instead of 12 nnz + 88; the same iterates bit for bit);
+    // CCP_GS_CG_FUSED=0: the three-pass loop.  A row block keeps that one: fused, it would need the ghost rows' r as well as their p.
+    const AllRankSums sums{m};
+    if (!rowblock && cg_fused_mode() != 0 && spmv.n_slices > 0) {
+        const size_t n2 = (size_t)std::max<long>(n, 2);
+        if (m->cg_p2.n < n2) CCP_TRY(m->cg_p2.alloc(n2));
+        CCP_HIP(hipMemsetAsync(m->cg_p2.p, 0, sizeof(double) * n2, s));
         auto apply = [&](double *xv, const double *rv, const double *p_in, double *p_out, double *apv, int *n_partials) -> int {
-            hipLaunchKernelGGL(k_sell_cg_apply, dim3(spmv_blocks), dim3(kBlock), 0, s, view, n_slices, xv, rv, p_in, p_out, apv, m->partial.p,
-                               m->cg_state.p);
-            *n_partials = (int)spmv_blocks;
+            hipLaunchKernelGGL(k_sell_cg_apply, dim3(spmv.blocks), dim3(kBlock), 0, s, spmv.view, spmv.n_slices, xv, rv, p_in, p_out, apv,
+                               m->partial.p, m->cg_state.p);
+            *n_partials = (int)spmv.blocks;
             return hipGetLastError() == hipSuccess ? CCP_OK : CCP_ERR_HIP;
         };
         CCP_TRY(cg_solve_fused(spmv, apply, m->b.p, m->x.p, m->tmp.p, m->cg_p.p, m->cg_p2.p, m->cg_ap.p, n, epsilon, max_iteration,
                                m->cg_state.p, m->partial.p, s, m->ev0, m->ev1, report));
     } else {
         CCP_TRY(cg_solve(spmv, spmv_dot, m->b.p, m->x.p, m->tmp.p, m->cg_p.p, m->cg_ap.p, n, epsilon, max_iteration, m->cg_state.p,
-                         m->partial.p, s, m->ev0, m->ev1, report));
+                         m->partial.p, s, m->ev0, m->ev1, report, sums, rowblock));
     }
-    if (n) CCP_HIP(hipMemcpyAsync(x_out, m->x.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    CCP_TRY(fetch_owned(m, x_out, m->x.p));
     CCP_HIP(hipStreamSynchronize(s));
     return CCP_OK;
 } CCP_ABI_CATCH
@@ -2883,23 +2965,16 @@ try {
 int ccp_csr_conjugate_gradient_jacobi(ccp_csr *m, const double *b, double *x_out, double epsilon, int32_t max_iteration,
                                       ccp_gs_report *report)
 try {
-    CCP_TRY(bind(m));
-    if (!m->uploaded) return CCP_ERR_STATE;
-    CCP_TRY(flush_edits(m));
+    CCP_TRY(ready(m));
     const bool rowblock = m->rb.on;        // b, x_out: the block's own rows (see ccp_csr_conjugate_gradient)
     if ((!b || !x_out) && !(rowblock && m->rb.n_local == 0)) return CCP_ERR_BAD_ARG;
     if (m->n_rows != m->n_cols) return CCP_ERR_UNSUPPORTED;
     CCP_TRY(ensure_natural(m));
     const long n = m->n_rows;
     hipStream_t s = m->stream;
-    if (!m->cg_p.p || m->cg_p.n < (size_t)std::max<long>(n, 2)) {
-        CCP_TRY(m->cg_p.alloc((size_t)std::max<long>(n, 2)));
-        CCP_TRY(m->cg_ap.alloc((size_t)std::max<long>(n, 2)));
-        CCP_TRY(m->cg_state.alloc(1));
-    }
-    if (!m->cg_state.p) CCP_TRY(m->cg_state.alloc(1));
-    const unsigned spmv_blocks = (unsigned)std::min<long>(2048, (m->natural.n_slices + kBlock / kWave - 1) / (kBlock / kWave));   // (k_sell_apply strides)
-    CCP_TRY(ensure_partial(m, std::max<long>(2048, spmv_blocks)));
+    CCP_TRY(ensure_csr_cg_work(m));
+    const NaturalSpmv<2> spmv_dot(m);
+    CCP_TRY(ensure_partial(m, std::max<long>(2048, spmv_dot.blocks)));
     if (m->cg_partial2.n != 4096) CCP_TRY(m->cg_partial2.alloc(4096));
     // extractDiagnolColInv (sparse-matrix.h:472-491): 1/a_ii of the first stored diagonal entry, 1 if absent or 0
     CCP_TRY(materialise(m));
@@ -2915,102 +2990,52 @@ try {
     if (m->cg_inv.n != inv.size()) CCP_TRY(m->cg_inv.alloc(inv.size()));
     if (n) {
         CCP_HIP(hipMemcpyAsync(m->cg_inv.p, inv.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
-        if (rowblock) CCP_TRY(rb_stage(m, m->tmp.p, b));                                         // (a ghost: empty row, inverse diagonal 1, r = 0)
-        else CCP_HIP(hipMemcpyAsync(m->tmp.p, b, sizeof(double) * n, hipMemcpyHostToDevice, s));     // r = b - A 0 = b (:500-501)
-        CCP_HIP(hipMemsetAsync(m->x.p, 0, sizeof(double) * n, s));                               // :495
+        CCP_TRY(stage_vector(m, m->tmp.p, b, n));   // r = b - A 0 = b (:500-501; a ghost: empty row, inverse diagonal 1, r = 0)
+        CCP_TRY(stage_vector(m, m->x.p, nullptr, n));   // :495
     }
-    const SellView view = m->natural.view();
-    const int n_slices = m->natural.n_slices;
-    auto spmv_dot = [&](const double *in, double *out, int *n_partials) -> int {
-        *n_partials = 0;
-        if (rowblock) CCP_TRY(rb_exchange_natural(m, const_cast<double *>(in)));
-        if (n_slices == 0) return CCP_OK;
-        hipLaunchKernelGGL((k_sell_apply<2>), dim3(spmv_blocks), dim3(kBlock), 0, s, view, n_slices, in, out, in, m->partial.p);
-        *n_partials = (int)spmv_blocks;
-        return hipGetLastError() == hipSuccess ? CCP_OK : CCP_ERR_HIP;
-    };
-    if (rowblock) {
-        const RcclApi *api = rccl_api();
-        if (!api) return CCP_ERR_RCCL;
-        double *total = reinterpret_cast<double *>(m->rb.comm->scratch.p);
-        auto sums = [&](double *partial, int *count, const double **sum_at, int slot) -> int {
-            hipLaunchKernelGGL(k_reduce_to, dim3(1), dim3(kBlock), 0, s, partial, (long)*count, 1L, total + slot, 0);
-            CCP_HIP(hipGetLastError());
-            CCP_RCCL(api->AllReduce(total + slot, total + slot, 1, ncclDouble, ncclSum, m->rb.comm->comm, s));
-            *count = 1;
-            *sum_at = total + slot;
-            return CCP_OK;
-        };
-        CCP_TRY(pcg_solve(spmv_dot, m->x.p, m->tmp.p, m->cg_p.p, m->cg_ap.p, m->cg_inv.p, n, epsilon, max_iteration, m->cg_state.p,
-                          m->partial.p, m->cg_partial2.p, s, m->ev0, m->ev1, report, sums, true));
-        if (m->rb.n_local) CCP_HIP(hipMemcpyAsync(x_out, m->x.p + m->rb.n_lo, sizeof(double) * (size_t)m->rb.n_local, hipMemcpyDeviceToHost, s));
-        CCP_HIP(hipStreamSynchronize(s));    // `inv` lives on this stack frame
-        return CCP_OK;
-    }
+    const AllRankSums sums{m};
     CCP_TRY(pcg_solve(spmv_dot, m->x.p, m->tmp.p, m->cg_p.p, m->cg_ap.p, m->cg_inv.p, n, epsilon, max_iteration, m->cg_state.p,
-                      m->partial.p, m->cg_partial2.p, s, m->ev0, m->ev1, report));
-    if (n) CCP_HIP(hipMemcpyAsync(x_out, m->x.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+                      m->partial.p, m->cg_partial2.p, s, m->ev0, m->ev1, report, sums, rowblock));
+    CCP_TRY(fetch_owned(m, x_out, m->x.p));
     CCP_HIP(hipStreamSynchronize(s));        // `inv` lives on this stack frame
     return CCP_OK;
 } CCP_ABI_CATCH
 
 int ccp_csr_apply_to_vector(ccp_csr *m, const double *in, double *out)
 try {
-    CCP_TRY(bind(m));
-    if (!m->uploaded) return CCP_ERR_STATE;
-    CCP_TRY(flush_edits(m));
+    CCP_TRY(ready(m));
     if (m->rb.on ? (m->rb.n_local && (!in || !out)) : ((m->n_cols && !in) || (m->n_rows && !out))) return CCP_ERR_BAD_ARG;
     if (!m->rb.on && m->allow_structured && m->n_rows == m->n_cols) {
         // SolveChannel's matrix: b := A x matrix-free on the grid twin (the row's products in the stored order: same bits)
         // instead of a sliced-ELL image of the whole matrix (16 GB at 16384^2) that only this call would need
         detect_poisson(m);
         if (m->poisson_w > 1 && m->poisson_h > 1) {
-            if (!m->grid) {
-                ccp_grid_desc d{m->poisson_w, m->poisson_h, 1, 0, m->poisson_h, 0, m->device, 0};
-                CCP_TRY(ccp_grid_create(&d, &m->grid));
-                (void)grid_set_allow_swap(m->grid, true);
-            }
-            CCP_TRY(ccp_grid_set_stream(m->grid, m->stream));
+            CCP_TRY(poisson_twin(m, false));
             CCP_TRY(ccp_grid_set_x_host(m->grid, 0, in, 0, m->poisson_h));
             CCP_TRY(ccp_grid_b_from_x(m->grid));
             return ccp_grid_get_b_host(m->grid, 0, out, 0, m->poisson_h);
         }
-        if (m->allow_region && m->region_state > 0 && m->region_grid && !m->edited) {
-            // a raster-region Laplacian a solve has already recognised: b := A x on its canvas (Dirichlet-mask grid)
-            const long n = m->n_rows;
-            hipStream_t s = m->stream;
-            ccp_grid *g = m->region_grid;
-            CCP_TRY(ccp_grid_set_stream(g, s));
+        if (region_twin_stands(m)) {
             ccp_grid_layout lay{};
-            CCP_TRY(ccp_grid_get_layout(g, &lay));
-            CCP_HIP(hipMemcpyAsync(m->tmp.p, in, sizeof(double) * n, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL((k_canvas_move<0>), dim3(blocks_for(n)), dim3(kBlock), 0, s, static_cast<double *>(lay.x_dev), m->tmp.p, m->region_where.p, n, 0.0);
-            CCP_HIP(hipGetLastError());
-            CCP_TRY(ccp_grid_b_from_x(g));
-            hipLaunchKernelGGL((k_canvas_move<1>), dim3(blocks_for(n)), dim3(kBlock), 0, s, static_cast<double *>(lay.b_dev), m->tmp.p, m->region_where.p, n, 0.0);
-            CCP_HIP(hipGetLastError());
-            CCP_HIP(hipMemcpyAsync(out, m->tmp.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-            CCP_HIP(hipStreamSynchronize(s));
-            return CCP_OK;
+            CCP_TRY(ccp_grid_set_stream(m->region_grid, m->stream));
+            CCP_TRY(ccp_grid_get_layout(m->region_grid, &lay));
+            CCP_TRY(to_canvas(m, lay.x_dev, in));
+            CCP_TRY(ccp_grid_b_from_x(m->region_grid));
+            return from_canvas(m, lay.b_dev, out);
         }
     }
     CCP_TRY(ensure_natural(m));
     hipStream_t s = m->stream;
-    const bool rowblock = m->rb.on;        // in / out: the block's own rows; the ghosts of `in` come from their owners
-    if (rowblock) {
-        CCP_TRY(rb_stage(m, m->x.p, in));
-        CCP_TRY(rb_exchange_natural(m, m->x.p));
-    } else if (m->n_cols) {
-        CCP_HIP(hipMemcpyAsync(m->x.p, in, sizeof(double) * m->n_cols, hipMemcpyHostToDevice, s));
-    }
+    // a row block: in / out hold the block's own rows; the ghosts of `in` come from their owners
+    CCP_TRY(stage_vector(m, m->x.p, in, m->n_cols));
+    if (m->rb.on) CCP_TRY(rb_exchange_natural(m, m->x.p));
     if (m->n_rows) {
         const unsigned blocks = (unsigned)((m->natural.n_slices + kBlock / kWave - 1) / (kBlock / kWave));
         CCP_TRY(ensure_partial(m, blocks));
         hipLaunchKernelGGL((k_sell_apply<0>), dim3(blocks), dim3(kBlock), 0, s, m->natural.view(), m->natural.n_slices,
                            m->x.p, m->tmp.p, m->b.p, m->partial.p);
         CCP_HIP(hipGetLastError());
-        if (!rowblock) CCP_HIP(hipMemcpyAsync(out, m->tmp.p, sizeof(double) * m->n_rows, hipMemcpyDeviceToHost, s));
-        else if (m->rb.n_local) CCP_HIP(hipMemcpyAsync(out, m->tmp.p + m->rb.n_lo, sizeof(double) * (size_t)m->rb.n_local, hipMemcpyDeviceToHost, s));
+        CCP_TRY(fetch_owned(m, out, m->tmp.p));
     }
     CCP_HIP(hipStreamSynchronize(s));
     return CCP_OK;
@@ -3018,43 +3043,27 @@ try {
 
 int ccp_csr_residual_norm2(ccp_csr *m, const double *b, const double *x, double *rr, double *bb)
 try {
-    CCP_TRY(bind(m));
-    if (!m->uploaded) return CCP_ERR_STATE;
-    CCP_TRY(flush_edits(m));
+    CCP_TRY(ready(m));
     if (!rr || !bb || ((!b || !x) && !(m->rb.on && m->rb.n_local == 0))) return CCP_ERR_BAD_ARG;
     if (!m->rb.on && m->allow_structured && m->n_rows == m->n_cols && m->n_rows > 0) {
         detect_poisson(m);                   // (as ccp_csr_apply_to_vector: matrix-free on the grid twin)
+        ccp_grid *twin = nullptr;
         if (m->poisson_w > 1 && m->poisson_h > 1) {
-            if (!m->grid) {
-                ccp_grid_desc d{m->poisson_w, m->poisson_h, 1, 0, m->poisson_h, 0, m->device, 0};
-                CCP_TRY(ccp_grid_create(&d, &m->grid));
-                (void)grid_set_allow_swap(m->grid, true);
-            }
-            CCP_TRY(ccp_grid_set_stream(m->grid, m->stream));
-            CCP_TRY(ccp_grid_set_b_host(m->grid, 0, b, 0, m->poisson_h));
-            CCP_TRY(ccp_grid_set_x_host(m->grid, 0, x, 0, m->poisson_h));
-            double both[2] = {0.0, 0.0};
-            CCP_TRY(ccp_grid_residual_norm2(m->grid, both));
-            *rr = both[0];
-            *bb = both[1];
-            return CCP_OK;
-        }
-        if (m->allow_region && m->region_state > 0 && m->region_grid && !m->edited) {
-            const long n = m->n_rows;
-            hipStream_t s = m->stream;
-            ccp_grid *g = m->region_grid;
-            CCP_TRY(ccp_grid_set_stream(g, s));
+            CCP_TRY(poisson_twin(m, false));
+            CCP_TRY(load_poisson_twin(m, b, x, 0.0));
+            twin = m->grid;
+        } else if (region_twin_stands(m)) {
             ccp_grid_layout lay{};
-            CCP_TRY(ccp_grid_get_layout(g, &lay));
-            CCP_HIP(hipMemcpyAsync(m->tmp.p, b, sizeof(double) * n, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL((k_canvas_move<0>), dim3(blocks_for(n)), dim3(kBlock), 0, s, static_cast<double *>(lay.b_dev), m->tmp.p, m->region_where.p, n, 0.0);
-            CCP_HIP(hipGetLastError());
-            CCP_HIP(hipStreamSynchronize(s));            // (tmp is staged twice)
-            CCP_HIP(hipMemcpyAsync(m->tmp.p, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL((k_canvas_move<0>), dim3(blocks_for(n)), dim3(kBlock), 0, s, static_cast<double *>(lay.x_dev), m->tmp.p, m->region_where.p, n, 0.0);
-            CCP_HIP(hipGetLastError());
+            CCP_TRY(ccp_grid_set_stream(m->region_grid, m->stream));
+            CCP_TRY(ccp_grid_get_layout(m->region_grid, &lay));
+            CCP_TRY(to_canvas(m, lay.b_dev, b));
+            CCP_HIP(hipStreamSynchronize(m->stream));            // (tmp is staged twice)
+            CCP_TRY(to_canvas(m, lay.x_dev, x));
+            twin = m->region_grid;
+        }
+        if (twin) {
             double both[2] = {0.0, 0.0};
-            CCP_TRY(ccp_grid_residual_norm2(g, both));
+            CCP_TRY(ccp_grid_residual_norm2(twin, both));
             *rr = both[0];
             *bb = both[1];
             return CCP_OK;
@@ -3062,18 +3071,12 @@ try {
     }
     CCP_TRY(ensure_natural(m));
     hipStream_t s = m->stream;
-    *rr = 0.0;
-    *bb = 0.0;
+    *rr = *bb = 0.0;
     const bool rowblock = m->rb.on;        // b, x: the block's own rows; rr, bb: sums over the whole matrix, on every rank
     if (!m->n_rows && !rowblock) return CCP_OK;
-    if (rowblock) {
-        CCP_TRY(rb_stage(m, m->x.p, x));
-        CCP_TRY(rb_exchange_natural(m, m->x.p));
-        CCP_TRY(rb_stage(m, m->b.p, b));
-    } else {
-        CCP_HIP(hipMemcpyAsync(m->x.p, x, sizeof(double) * m->n_cols, hipMemcpyHostToDevice, s));
-        CCP_HIP(hipMemcpyAsync(m->b.p, b, sizeof(double) * m->n_rows, hipMemcpyHostToDevice, s));
-    }
+    CCP_TRY(stage_vector(m, m->x.p, x, m->n_cols));
+    if (rowblock) CCP_TRY(rb_exchange_natural(m, m->x.p));
+    CCP_TRY(stage_vector(m, m->b.p, b, m->n_rows));
     const unsigned blocks = (unsigned)((m->natural.n_slices + kBlock / kWave - 1) / (kBlock / kWave));
     CCP_TRY(ensure_partial(m, std::max(blocks, 1u)));
     if (blocks)
@@ -3083,11 +3086,7 @@ try {
     hipLaunchKernelGGL(k_reduce_to, dim3(1), dim3(kBlock), 0, s, m->partial.p, (long)blocks, 2L, res, 0);
     hipLaunchKernelGGL(k_reduce_to, dim3(1), dim3(kBlock), 0, s, m->partial.p + 1, (long)blocks, 2L, res + 1, 0);
     CCP_HIP(hipGetLastError());
-    if (rowblock) {
-        const RcclApi *api = rccl_api();
-        if (!api) return CCP_ERR_RCCL;
-        CCP_RCCL(api->AllReduce(res, res, 2, ncclDouble, ncclSum, m->rb.comm->comm, s));
-    }
+    CCP_TRY(all_rank_sum(m, res, 2));
     double host[2];
     CCP_HIP(hipMemcpyAsync(host, res, sizeof(host), hipMemcpyDeviceToHost, s));
     CCP_HIP(hipStreamSynchronize(s));

@@ -943,8 +943,6 @@ int ensure_cg_work(ccp_grid *g)
     return CCP_OK;
 }
 
-int cg_fused_mode() { return getenv("CCP_GS_CG_FUSED") ? atoi(getenv("CCP_GS_CG_FUSED")) : 1; }
-
 // k_apply<2, DOT> on rows l_lo + blockIdx.y: out := A in (DOT 0), the residual's sums of in against out (1), out := A in and in'(A in) (2)
 template <int DOT>
 void launch_apply(ccp_grid *g, dim3 grid, const double *in, double *out, int l_lo)

@@ -111,7 +111,7 @@ namespace {
 dim3 cells_grid(int w, int h) { return dim3((unsigned)((w + kBlock - 1) / kBlock), (unsigned)h); }
 
 // A level's run-time kind as a template argument: f(K) with decltype(K)::value == kind; returns what f returns.  A step
-// that takes a bool too goes through with_bool inside f.  (f is instantiated for all three kinds: where a kernel exists
+// that takes a bool too goes through with_bool (ccp_common.hpp) inside f.  (f is instantiated for all three kinds: where a kernel exists
 // for fewer, as the fp32 V-cycle's coarse levels do for kMgCoarse alone, name the kind and do not come here.)
 template <typename F>
 auto with_kind(int kind, F &&f)
@@ -119,13 +119,6 @@ auto with_kind(int kind, F &&f)
     if (kind == kMgCoarse) return f(std::integral_constant<int, kMgCoarse>{});
     else if (kind == kMgMasked) return f(std::integral_constant<int, kMgMasked>{});
     else return f(std::integral_constant<int, kMgSolve>{});
-}
-
-template <typename F>
-auto with_bool(bool on, F &&f)
-{
-    if (on) return f(std::true_type{});
-    else return f(std::false_type{});
 }
 
 // coarse local rows [Y0, Y0 + rows) of c from f (kind: f's operator)
