@@ -33,34 +33,95 @@ struct CgState {
     double r1norm;       // sqrt(r1'r1) of the last update
 };
 
+// ---- the passes' bodies ------------------------------------------------------------------------------------------------
+// Each pass of the loop is written once here and instantiated by two kernels: k_cg_* below (one vector, one CgState) and
+// the batched multigrid PCG's k_mgb_* (ccp_grid_mgb.hpp: the channel on grid y or x, st and the partial sums indexed by
+// it).  A vector body covers the grid-stride range of blockIdx.x within elements [o, o + n) of its vectors (o = 0, or
+// where the channel's slice begins) and returns the thread's partial sum; the kernel adds up (block_sum) and stores.  o
+// is an index and not an offset the caller has added to every pointer: that is what k_mgb_* did before they called
+// these bodies, and it keeps their machine code and k_cg_*'s (where o = 0 folds away) as it was.  A scalar step takes
+// the sum reduce_partials gave; thread 0 stores.
+
+// the thread's share of a'b
+__device__ __forceinline__ double cg_dot_body(const double *__restrict__ a, const double *__restrict__ b, long o, long n,
+                                              const CgState *__restrict__ st)
+{
+    double acc = 0.0;
+    if (st->active)
+        for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) acc += a[o + i] * b[o + i];
+    return acc;
+}
+
+// r := b - r  (r holds A x on entry; vecsub(b, r, r), sparse-matrix.h:407) and p := r (:410); the thread's share of r'r
+__device__ __forceinline__ double cg_init_body(const double *__restrict__ b, double *__restrict__ r, double *__restrict__ p, long o,
+                                               long n)
+{
+    double acc = 0.0;
+    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) {
+        const double v = b[o + i] - r[o + i];
+        r[o + i] = v;
+        p[o + i] = v;
+        acc += v * v;
+    }
+    return acc;
+}
+
+// x += alpha p (:421); r := r + (-alpha) Ap (:422, r1 stored over r); the thread's share of r1'r1 (:423)
+__device__ __forceinline__ double cg_update_body(double *__restrict__ x, const double *__restrict__ p, double *__restrict__ r,
+                                                 const double *__restrict__ ap, long o, long n, const CgState *__restrict__ st)
+{
+    double acc = 0.0;
+    if (st->active) {
+        const double alpha = st->alpha;
+        const double nalpha = -alpha;
+        for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) {
+            x[o + i] = x[o + i] + alpha * p[o + i];
+            const double v = r[o + i] + nalpha * ap[o + i];
+            r[o + i] = v;
+            acc += v * v;
+        }
+    }
+    return acc;
+}
+
+// p := r1 + beta p (:427; the multigrid PCG passes z for r1)
+__device__ __forceinline__ void cg_direction_body(double *__restrict__ p, const double *__restrict__ r, long o, long n,
+                                                  const CgState *__restrict__ st)
+{
+    if (!st->active) return;
+    const double beta = st->beta;
+    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock)
+        p[o + i] = r[o + i] + beta * p[o + i];
+}
+
+__device__ __forceinline__ void cg_set_rlen_step(double rlen, CgState *__restrict__ st)
+{
+    if (threadIdx.x == 0) st->rlen = rlen;
+}
+
+// alpha = r'r / p'Ap (sparse-matrix.h:420)
+__device__ __forceinline__ void cg_alpha_step(double pap, CgState *__restrict__ st)
+{
+    if (threadIdx.x == 0 && st->active) st->alpha = st->rlen / pap;
+}
+
+// ---- the kernels -----------------------------------------------------------------------------------------------------
 // partial[blockIdx.x] = sum over this block's grid-stride range of a[i]*b[i]
 static __global__ void __launch_bounds__(kBlock)
 k_cg_dot(const double *__restrict__ a, const double *__restrict__ b, long n, double *__restrict__ partial,
          const CgState *__restrict__ st)
 {
     __shared__ double scratch[kBlock / kWave];
-    double acc = 0.0;
-    if (st->active)
-        for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) acc += a[i] * b[i];
-    const double t = block_sum(acc, scratch);
+    const double t = block_sum(cg_dot_body(a, b, 0, n, st), scratch);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
-// r := b - r  (r holds A x on entry; vecsub(b, r, r), sparse-matrix.h:407) and p := r (:410);
-// partial sums of r'r.
 static __global__ void __launch_bounds__(kBlock)
 k_cg_init(const double *__restrict__ b, double *__restrict__ r, double *__restrict__ p, long n,
           double *__restrict__ partial)
 {
     __shared__ double scratch[kBlock / kWave];
-    double acc = 0.0;
-    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) {
-        const double v = b[i] - r[i];
-        r[i] = v;
-        p[i] = v;
-        acc += v * v;
-    }
-    const double t = block_sum(acc, scratch);
+    const double t = block_sum(cg_init_body(b, r, p, 0, n), scratch);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -85,37 +146,22 @@ static __global__ void __launch_bounds__(kBlock)
 k_cg_set_rlen(const double *__restrict__ partial, int count, CgState *__restrict__ st)
 {
     __shared__ double scratch[kBlock / kWave];
-    const double t = reduce_partials(partial, count, scratch);
-    if (threadIdx.x == 0) st->rlen = t;
+    cg_set_rlen_step(reduce_partials(partial, count, scratch), st);
 }
 
-// alpha = r'r / p'Ap (sparse-matrix.h:420)
 static __global__ void __launch_bounds__(kBlock)
 k_cg_alpha(const double *__restrict__ partial, int count, CgState *__restrict__ st)
 {
     __shared__ double scratch[kBlock / kWave];
-    const double pap = reduce_partials(partial, count, scratch);
-    if (threadIdx.x == 0 && st->active) st->alpha = st->rlen / pap;
+    cg_alpha_step(reduce_partials(partial, count, scratch), st);
 }
 
-// x += alpha p (:421); r := r + (-alpha) Ap (:422, r1 stored over r); partial sums of r1'r1 (:423)
 static __global__ void __launch_bounds__(kBlock)
 k_cg_update(double *__restrict__ x, const double *__restrict__ p, double *__restrict__ r,
             const double *__restrict__ ap, long n, double *__restrict__ partial, const CgState *__restrict__ st)
 {
     __shared__ double scratch[kBlock / kWave];
-    double acc = 0.0;
-    if (st->active) {
-        const double alpha = st->alpha;
-        const double nalpha = -alpha;
-        for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) {
-            x[i] = x[i] + alpha * p[i];
-            const double v = r[i] + nalpha * ap[i];
-            r[i] = v;
-            acc += v * v;
-        }
-    }
-    const double t = block_sum(acc, scratch);
+    const double t = block_sum(cg_update_body(x, p, r, ap, 0, n, st), scratch);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -138,14 +184,10 @@ k_cg_beta(const double *__restrict__ partial, int count, double epsilon, CgState
     }
 }
 
-// p := r1 + beta p (:427)
 static __global__ void __launch_bounds__(kBlock)
 k_cg_direction(double *__restrict__ p, const double *__restrict__ r, long n, const CgState *__restrict__ st)
 {
-    if (!st->active) return;
-    const double beta = st->beta;
-    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock)
-        p[i] = r[i] + beta * p[i];
+    cg_direction_body(p, r, 0, n, st);
 }
 
 // ---- fused loop (matrix-free grid path): 72 B per unknown and iteration instead of 88 -------------------------

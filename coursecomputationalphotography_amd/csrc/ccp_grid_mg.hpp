@@ -77,6 +77,47 @@ __device__ __forceinline__ double mg_ld(const double *__restrict__ v, const MgLe
     return (x >= 0 && x < lv.W && y >= 0 && y < lv.H) ? v[mg_at(lv.pitch, x, y)] : 0.0;
 }
 
+// ---- the per-cell formulas ---------------------------------------------------------------------------------------------
+// Each is written once, for T = double (this file, ccp_grid_mgb.hpp) and T = float (ccp_grid_mgs.hpp); level 0 of
+// SolveChannel's matrix uses gs_update / apply_row (ccp_grid_stencil.hpp) the same way.  The callers differ only in where
+// the operands come from (global memory, LDS, registers) and load them themselves; a missing neighbour is passed as 0.
+
+// the stored operator's neighbour sum: weight and value of the north, west, east and south neighbour, in this order
+template <typename T>
+__device__ __forceinline__ T mg_nb_sum(T wn, T xu, T ww, T xl, T we, T xr, T ws, T xd)
+{
+    T s = T(0);
+    s += wn * xu;
+    s += ww * xl;
+    s += we * xr;
+    s += ws * xd;
+    return s;
+}
+
+// Gauss-Seidel update and residual of a live cell of a stored operator, s its mg_nb_sum (the division is IEEE)
+template <typename T>
+__device__ __forceinline__ T mg_stored_update(T b, T s, T d) { return (b + s) / d; }
+
+template <typename T>
+__device__ __forceinline__ T mg_stored_residual(T b, T d, T xi, T s) { return b - (d * xi - s); }
+
+// a live cell of the Dirichlet-mask Laplacian: k_half_sweep's masked arithmetic, b - sigma with
+// sigma = (((-xu) + (-xl)) + (-xr)) + (-xd) and a_ii = 4; and its row of A x in applyToVector's order
+template <typename T>
+__device__ __forceinline__ T mg_masked_update(T b, T xu, T xl, T xr, T xd) { return (b + (((xu + xl) + xr) + xd)) * T(0.25); }
+
+template <typename T>
+__device__ __forceinline__ T mg_masked_row(T xi, T xu, T xl, T xr, T xd)
+{
+    T ax = T(0);
+    ax += T(-1) * xu;
+    ax += T(-1) * xl;
+    ax += T(4) * xi;
+    ax += T(-1) * xr;
+    ax += T(-1) * xd;
+    return ax;
+}
+
 template <int KIND>
 __device__ __forceinline__ bool mg_live(const MgLevel &lv, int x, int y)
 {
@@ -118,17 +159,12 @@ __device__ __forceinline__ double mg_update(const MgLevel &lv, double bv, double
         double out = 0.0;
         return gs_update(classify(lv.g0, x, lv.y0 + y, y), bv, xu, xl, xr, xd, out) ? out : 0.0;
     } else if (KIND == kMgMasked) {
-        // k_half_sweep's masked arithmetic: b - sigma with sigma = (((-xu) + (-xl)) + (-xr)) + (-xd); a_ii = 4
-        return lv.mask[at] ? (bv + (((xu + xl) + xr) + xd)) * 0.25 : 0.0;
+        return lv.mask[at] ? mg_masked_update(bv, xu, xl, xr, xd) : 0.0;
     } else {
         const double d = lv.d[at];
         if (d == 0.0) return 0.0;
-        double s = 0.0;
-        s += mg_ld(lv.ws, lv, x, y - 1) * xu;
-        s += mg_ld(lv.we, lv, x - 1, y) * xl;
-        s += lv.we[at] * xr;
-        s += lv.ws[at] * xd;
-        return (bv + s) / d;
+        const double s = mg_nb_sum(mg_ld(lv.ws, lv, x, y - 1), xu, mg_ld(lv.we, lv, x - 1, y), xl, lv.we[at], xr, lv.ws[at], xd);
+        return mg_stored_update(bv, s, d);
     }
 }
 
@@ -141,15 +177,7 @@ __device__ __forceinline__ double mg_row0(const MgLevel &lv, const double *__res
     const double xu = mg_ld(z, lv, x, y - 1), xl = mg_ld(z, lv, x - 1, y), xr = mg_ld(z, lv, x + 1, y), xd = mg_ld(z, lv, x, y + 1);
     if (KIND == kMgSolve) return apply_row(classify(lv.g0, x, lv.y0 + y, y), xi, xu, xl, xr, xd);
     if (KIND == kMgCoarse) return weighted_row(lv.d, lv.we, lv.ws, lv.pitch, lv.W, lv.H, z, x, y);   // a weighted handle's level 0
-    double ax = 0.0;
-    if (lv.mask[at]) {
-        ax += -1.0 * xu;
-        ax += -1.0 * xl;
-        ax += 4.0 * xi;
-        ax += -1.0 * xr;
-        ax += -1.0 * xd;
-    }
-    return ax;
+    return lv.mask[at] ? mg_masked_row(xi, xu, xl, xr, xd) : 0.0;
 }
 
 // b - A z at (x,y); 0 outside the level's owned rows and on dead pixels
@@ -165,12 +193,8 @@ __device__ __forceinline__ double mg_residual(const MgLevel &lv, const double *_
         if (d == 0.0) return 0.0;
         const double xi = z[at];
         const double xu = mg_ld(z, lv, x, y - 1), xl = mg_ld(z, lv, x - 1, y), xr = mg_ld(z, lv, x + 1, y), xd = mg_ld(z, lv, x, y + 1);
-        double s = 0.0;
-        s += mg_ld(lv.ws, lv, x, y - 1) * xu;
-        s += mg_ld(lv.we, lv, x - 1, y) * xl;
-        s += lv.we[at] * xr;
-        s += lv.ws[at] * xd;
-        return b[at] - (d * xi - s);
+        const double s = mg_nb_sum(mg_ld(lv.ws, lv, x, y - 1), xu, mg_ld(lv.we, lv, x - 1, y), xl, lv.we[at], xr, lv.ws[at], xd);
+        return mg_stored_residual(b[at], d, xi, s);
     }
 }
 
@@ -348,21 +372,23 @@ k_mg_tile(MgLevel lv, const double *__restrict__ b, const double *__restrict__ z
 }
 
 // ---- the tail: every level from `first` down to 1x1 in one workgroup, resident in LDS --------------------------------
-struct MgTail {
+template <typename T>
+struct MgTailT {
     int levels;
     int W[kMgTailLevels], H[kMgTailLevels], off[kMgTailLevels];   // off: first cell of the level in the LDS arrays (raster order)
     long pitch[kMgTailLevels];
-    const double *d[kMgTailLevels], *we[kMgTailLevels], *ws[kMgTailLevels];
+    const T *d[kMgTailLevels], *we[kMgTailLevels], *ws[kMgTailLevels];
 };
+using MgTail = MgTailT<double>;
 
-// b_top: right-hand side of the tail's first level (its level layout); z_top: its correction; cs: the correction scale
-// (2.0 or 1.0, as k_mg_tile's).  grid = 1 workgroup.  k_mgb_tail (ccp_grid_mgb.hpp) is this body once per channel and
-// must give the same bits: a change here is made there too.
-static __global__ void __launch_bounds__(kBlock)
-k_mg_tail(MgTail t, const double *__restrict__ b_top, double *__restrict__ z_top, double cs, int nu, const CgState *__restrict__ st)
+// The tail's V-cycle, the whole workgroup's work.  b_top: right-hand side of the tail's first level (its level layout);
+// z_top: its correction; cs: the correction scale (2.0 or 1.0, as k_mg_tile's).  Three kernels instantiate it: k_mg_tail
+// (below), k_mgb_tail (ccp_grid_mgb.hpp: one workgroup per channel, b_top and z_top offset to the channel) and
+// k_mgs_tail (ccp_grid_mgs.hpp: T = float).
+template <typename T>
+__device__ __forceinline__ void mg_tail_body(const MgTailT<T> &t, const T *__restrict__ b_top, T *__restrict__ z_top, T cs, int nu)
 {
-    if (st && !st->active) return;
-    __shared__ double sd[kMgTailCells], swe[kMgTailCells], sws[kMgTailCells], sb[kMgTailCells], sz[kMgTailCells];
+    __shared__ T sd[kMgTailCells], swe[kMgTailCells], sws[kMgTailCells], sb[kMgTailCells], sz[kMgTailCells];
     for (int k = 0; k < t.levels; ++k) {
         const int W = t.W[k], n = t.W[k] * t.H[k];
         for (int i = threadIdx.x; i < n; i += kBlock) {
@@ -375,40 +401,36 @@ k_mg_tail(MgTail t, const double *__restrict__ b_top, double *__restrict__ z_top
     }
     __syncthreads();
     // the coarse-level arithmetic of mg_update / mg_residual on the LDS copy
-    auto sum_nb = [&](int k, int X, int Y, double &xi) -> double {
+    auto sum_nb = [&](int k, int X, int Y, T &xi) -> T {
         const int W = t.W[k], H = t.H[k], o = t.off[k], i = o + Y * W + X;
         xi = sz[i];
-        double s = 0.0;
-        s += (Y > 0 ? sws[i - W] : 0.0) * (Y > 0 ? sz[i - W] : 0.0);
-        s += (X > 0 ? swe[i - 1] : 0.0) * (X > 0 ? sz[i - 1] : 0.0);
-        s += swe[i] * (X + 1 < W ? sz[i + 1] : 0.0);
-        s += sws[i] * (Y + 1 < H ? sz[i + W] : 0.0);
-        return s;
+        return mg_nb_sum(Y > 0 ? sws[i - W] : T(0), Y > 0 ? sz[i - W] : T(0), X > 0 ? swe[i - 1] : T(0), X > 0 ? sz[i - 1] : T(0),
+                         swe[i], X + 1 < W ? sz[i + 1] : T(0), sws[i], Y + 1 < H ? sz[i + W] : T(0));
     };
     auto sweep = [&](int k, int c, bool first) {
         const int W = t.W[k], n = t.W[k] * t.H[k], o = t.off[k];
         for (int i = threadIdx.x; i < n; i += kBlock) {
             const int X = i % W, Y = i / W;
             if (((X + Y) & 1) != c) continue;
-            const double d = sd[o + i];
-            double v = 0.0;
-            if (d != 0.0) {
-                double xi;
-                const double s = first ? 0.0 : sum_nb(k, X, Y, xi);
-                v = (sb[o + i] + s) / d;
+            const T d = sd[o + i];
+            T v = T(0);
+            if (d != T(0)) {
+                T xi;
+                const T s = first ? T(0) : sum_nb(k, X, Y, xi);
+                v = mg_stored_update(sb[o + i], s, d);
             }
             sz[o + i] = v;
         }
         __syncthreads();
     };
-    auto residual = [&](int k, int X, int Y) -> double {
-        if (X >= t.W[k] || Y >= t.H[k]) return 0.0;
+    auto residual = [&](int k, int X, int Y) -> T {
+        if (X >= t.W[k] || Y >= t.H[k]) return T(0);
         const int i = t.off[k] + Y * t.W[k] + X;
-        const double d = sd[i];
-        if (d == 0.0) return 0.0;
-        double xi;
-        const double s = sum_nb(k, X, Y, xi);
-        return sb[i] - (d * xi - s);
+        const T d = sd[i];
+        if (d == T(0)) return T(0);
+        T xi;
+        const T s = sum_nb(k, X, Y, xi);
+        return mg_stored_residual(sb[i], d, xi, s);
     };
     const int last = t.levels - 1;
     for (int k = 0; k < last; ++k) {
@@ -419,22 +441,22 @@ k_mg_tail(MgTail t, const double *__restrict__ b_top, double *__restrict__ z_top
         const int Wc = t.W[k + 1], nc = t.W[k + 1] * t.H[k + 1], oc = t.off[k + 1];
         for (int i = threadIdx.x; i < nc; i += kBlock) {
             const int X = i % Wc, Y = i / Wc;
-            const double r00 = residual(k, 2 * X, 2 * Y), r10 = residual(k, 2 * X + 1, 2 * Y);
-            const double r01 = residual(k, 2 * X, 2 * Y + 1), r11 = residual(k, 2 * X + 1, 2 * Y + 1);
+            const T r00 = residual(k, 2 * X, 2 * Y), r10 = residual(k, 2 * X + 1, 2 * Y);
+            const T r01 = residual(k, 2 * X, 2 * Y + 1), r11 = residual(k, 2 * X + 1, 2 * Y + 1);
             sb[oc + i] = (r00 + r10) + (r01 + r11);
         }
         __syncthreads();
     }
     {
         const int n = t.W[last] * t.H[last], o = t.off[last];
-        for (int i = threadIdx.x; i < n; i += kBlock) sz[o + i] = sd[o + i] != 0.0 ? sb[o + i] / sd[o + i] : 0.0;
+        for (int i = threadIdx.x; i < n; i += kBlock) sz[o + i] = sd[o + i] != T(0) ? sb[o + i] / sd[o + i] : T(0);
         __syncthreads();
     }
     for (int k = last - 1; k >= 0; --k) {
         const int W = t.W[k], n = t.W[k] * t.H[k], o = t.off[k], Wc = t.W[k + 1], oc = t.off[k + 1];
         for (int i = threadIdx.x; i < n; i += kBlock) {
             const int X = i % W, Y = i / W;
-            if (sd[o + i] != 0.0) sz[o + i] = sz[o + i] + cs * sz[oc + (Y >> 1) * Wc + (X >> 1)];
+            if (sd[o + i] != T(0)) sz[o + i] = sz[o + i] + cs * sz[oc + (Y >> 1) * Wc + (X >> 1)];
         }
         __syncthreads();
         for (int s = 0; s < nu; ++s) {
@@ -446,13 +468,19 @@ k_mg_tail(MgTail t, const double *__restrict__ b_top, double *__restrict__ z_top
     for (int i = threadIdx.x; i < n; i += kBlock) z_top[mg_at(t.pitch[0], i % W, i / W)] = sz[i];
 }
 
-// ---- PCG scalars (the vector passes are ccp_cg.hpp's: k_cg_update, k_cg_dot, k_cg_direction) -------------------------
-// r'r of the update just made: `if (sqrt(r'r) < epsilon) break;` before the V-cycle of the next direction runs
+// grid = 1 workgroup
 static __global__ void __launch_bounds__(kBlock)
-k_mg_check(const double *__restrict__ partial, int count, double epsilon, CgState *__restrict__ st)
+k_mg_tail(MgTail t, const double *__restrict__ b_top, double *__restrict__ z_top, double cs, int nu, const CgState *__restrict__ st)
 {
-    __shared__ double scratch[kBlock / kWave];
-    const double rr = reduce_partials(partial, count, scratch);
+    if (st && !st->active) return;
+    mg_tail_body(t, b_top, z_top, cs, nu);
+}
+
+// ---- PCG scalars (the vector passes are ccp_cg.hpp's: k_cg_update, k_cg_dot, k_cg_direction) -------------------------
+// The two steps (thread 0 stores), for k_mg_check / k_mg_beta and, per channel, k_mgb_check / k_mgb_beta (ccp_grid_mgb.hpp).
+// rr = r'r of the update just made: `if (sqrt(r'r) < epsilon) break;` before the V-cycle of the next direction runs
+__device__ __forceinline__ void mg_check_step(double rr, double epsilon, CgState *__restrict__ st)
+{
     if (threadIdx.x == 0 && st->active) {
         st->r1norm = sqrt(rr);
         if (st->r1norm < epsilon) {
@@ -463,16 +491,27 @@ k_mg_check(const double *__restrict__ partial, int count, double epsilon, CgStat
 }
 
 // beta = new r'z / old r'z; ++iterations (k_pcg_beta's count)
-static __global__ void __launch_bounds__(kBlock)
-k_mg_beta(const double *__restrict__ partial, int count, CgState *__restrict__ st)
+__device__ __forceinline__ void mg_beta_step(double rz, CgState *__restrict__ st)
 {
-    __shared__ double scratch[kBlock / kWave];
-    const double rz = reduce_partials(partial, count, scratch);
     if (threadIdx.x == 0 && st->active) {
         st->beta = rz / st->rlen;
         st->rlen = rz;
         st->iterations += 1;
     }
+}
+
+static __global__ void __launch_bounds__(kBlock)
+k_mg_check(const double *__restrict__ partial, int count, double epsilon, CgState *__restrict__ st)
+{
+    __shared__ double scratch[kBlock / kWave];
+    mg_check_step(reduce_partials(partial, count, scratch), epsilon, st);
+}
+
+static __global__ void __launch_bounds__(kBlock)
+k_mg_beta(const double *__restrict__ partial, int count, CgState *__restrict__ st)
+{
+    __shared__ double scratch[kBlock / kWave];
+    mg_beta_step(reduce_partials(partial, count, scratch), st);
 }
 
 }  // namespace ccp

@@ -3,10 +3,12 @@
 // handle, and whatever does not depend on the channel -- the operator's coefficients -- is fetched once per launch.
 //
 // Definition.  The channels never mix, so channel ch gets, bit for bit, what the sequential kernels (k_mg_*, k_cg_*) give
-// it: every kernel here performs, per channel, exactly their operations in their order with their grouping of every
-// partial sum (the same grid within a channel, block_sum, reduce_partials over the channel's slice of the partial sums),
-// the division (b + s) / d, no reciprocal, nothing contracted.  A channel whose st[ch].active is 0 is skipped as a whole
-// launch is there.
+// it.  The arithmetic is theirs by construction: the tail's cycle (mg_tail_body), the per-cell formulas (mg_nb_sum,
+// mg_stored_update, mg_stored_residual, mg_masked_update, mg_masked_row, gs_update, apply_row), the CG passes' bodies
+// (cg_*_body, cg_*_step, mg_check_step, mg_beta_step) are the functions the sequential kernels call, on a channel's slice.
+// What this file adds is where the operands come from and the grouping of every partial sum, which is the sequential
+// one (the same grid within a channel, block_sum, reduce_partials over the channel's slice of the partial sums).  A
+// channel whose st[ch].active is 0 is skipped as a whole launch is there.
 //
 // Vectors.  Channel ch of a vector sits `stride` doubles after channel 0 (the handle's x and b: ch_stride; the PCG
 // vectors and level 0's t likewise; a coarse level's b, z, t: the level's size).  CgState[C]; the partial sums are C
@@ -128,16 +130,12 @@ k_mgb_tile(MgLevel lv, const double *__restrict__ b, const double *__restrict__ 
                 if (KIND == kMgSolve) {
                     if (!gs_update(mgb_unpack(sf[i]), bv, xu, xl, xr, xd, out)) out = 0.0;
                 } else if (KIND == kMgMasked) {
-                    out = sf[i] ? (bv + (((xu + xl) + xr) + xd)) * 0.25 : 0.0;
+                    out = sf[i] ? mg_masked_update(bv, xu, xl, xr, xd) : 0.0;
                 } else {
                     const double d = sd[i];
                     if (d != 0.0) {
-                        double s = 0.0;
-                        s += (r > 0 ? sws[i - RW] : 0.0) * xu;
-                        s += (col > 0 ? swe[i - 1] : 0.0) * xl;
-                        s += swe[i] * xr;
-                        s += sws[i] * xd;
-                        out = (bv + s) / d;
+                        const double s = mg_nb_sum(r > 0 ? sws[i - RW] : 0.0, xu, col > 0 ? swe[i - 1] : 0.0, xl, swe[i], xr, sws[i], xd);
+                        out = mg_stored_update(bv, s, d);
                     }
                 }
                 sz[i] = out;
@@ -218,13 +216,7 @@ __device__ __forceinline__ double mgb_row0(const MgbCell<KIND> &c, const double 
     const double xr = c.f & kMgbRight ? z[c.ar] : 0.0, xd = c.f & kMgbDown ? z[c.ad] : 0.0;
     if (KIND == kMgSolve) return apply_row(mgb_unpack((unsigned char)(c.f >> 8)), xi, xu, xl, xr, xd);
     double ax = 0.0;
-    if (c.f & kMgbLive) {
-        ax += -1.0 * xu;
-        ax += -1.0 * xl;
-        ax += 4.0 * xi;
-        ax += -1.0 * xr;
-        ax += -1.0 * xd;
-    }
+    if (c.f & kMgbLive) ax = mg_masked_row(xi, xu, xl, xr, xd);
     return ax;
 }
 
@@ -239,12 +231,7 @@ __device__ __forceinline__ double mgb_residual(const MgbCell<KIND> &c, const dou
         const double xi = z[c.at];
         const double xu = c.f & kMgbUp ? z[c.au] : 0.0, xl = c.f & kMgbLeft ? z[c.al] : 0.0;
         const double xr = c.f & kMgbRight ? z[c.ar] : 0.0, xd = c.f & kMgbDown ? z[c.ad] : 0.0;
-        double s = 0.0;
-        s += c.wn * xu;
-        s += c.ww * xl;
-        s += c.we * xr;
-        s += c.ws * xd;
-        return b[c.at] - (c.d * xi - s);
+        return mg_stored_residual(b[c.at], c.d, xi, mg_nb_sum(c.wn, xu, c.ww, xl, c.we, xr, c.ws, xd));
     }
 }
 
@@ -320,114 +307,23 @@ k_mgb_apply(MgLevel lv, const double *__restrict__ in, double *__restrict__ out,
     }
 }
 
-// ---- the tail: k_mg_tail's body, one workgroup per channel (bs, zs: the channel strides of b_top, z_top) -------------------
-// A copy of k_mg_tail (ccp_grid_mg.hpp), which stays untouched, plus the two pointer offsets and the indexed st: the
-// two bodies are kept in step by hand, operation for operation, or the batched mode loses its bit equality.
+// ---- the tail: mg_tail_body (ccp_grid_mg.hpp), one workgroup per channel (bs, zs: the channel strides of b_top, z_top) -----
 static __global__ void __launch_bounds__(kBlock)
 k_mgb_tail(MgTail t, const double *__restrict__ b_top, double *__restrict__ z_top, long bs, long zs, double cs, int nu,
            const CgState *__restrict__ st)
 {
     if (st && !st[blockIdx.x].active) return;
-    b_top += blockIdx.x * bs;
-    z_top += blockIdx.x * zs;
-    __shared__ double sd[kMgTailCells], swe[kMgTailCells], sws[kMgTailCells], sb[kMgTailCells], sz[kMgTailCells];
-    for (int k = 0; k < t.levels; ++k) {
-        const int W = t.W[k], n = t.W[k] * t.H[k];
-        for (int i = threadIdx.x; i < n; i += kBlock) {
-            const long at = mg_at(t.pitch[k], i % W, i / W);
-            sd[t.off[k] + i] = t.d[k][at];
-            swe[t.off[k] + i] = t.we[k][at];
-            sws[t.off[k] + i] = t.ws[k][at];
-            if (k == 0) sb[i] = b_top[at];
-        }
-    }
-    __syncthreads();
-    auto sum_nb = [&](int k, int X, int Y, double &xi) -> double {
-        const int W = t.W[k], H = t.H[k], o = t.off[k], i = o + Y * W + X;
-        xi = sz[i];
-        double s = 0.0;
-        s += (Y > 0 ? sws[i - W] : 0.0) * (Y > 0 ? sz[i - W] : 0.0);
-        s += (X > 0 ? swe[i - 1] : 0.0) * (X > 0 ? sz[i - 1] : 0.0);
-        s += swe[i] * (X + 1 < W ? sz[i + 1] : 0.0);
-        s += sws[i] * (Y + 1 < H ? sz[i + W] : 0.0);
-        return s;
-    };
-    auto sweep = [&](int k, int c, bool first) {
-        const int W = t.W[k], n = t.W[k] * t.H[k], o = t.off[k];
-        for (int i = threadIdx.x; i < n; i += kBlock) {
-            const int X = i % W, Y = i / W;
-            if (((X + Y) & 1) != c) continue;
-            const double d = sd[o + i];
-            double v = 0.0;
-            if (d != 0.0) {
-                double xi;
-                const double s = first ? 0.0 : sum_nb(k, X, Y, xi);
-                v = (sb[o + i] + s) / d;
-            }
-            sz[o + i] = v;
-        }
-        __syncthreads();
-    };
-    auto residual = [&](int k, int X, int Y) -> double {
-        if (X >= t.W[k] || Y >= t.H[k]) return 0.0;
-        const int i = t.off[k] + Y * t.W[k] + X;
-        const double d = sd[i];
-        if (d == 0.0) return 0.0;
-        double xi;
-        const double s = sum_nb(k, X, Y, xi);
-        return sb[i] - (d * xi - s);
-    };
-    const int last = t.levels - 1;
-    for (int k = 0; k < last; ++k) {
-        for (int s = 0; s < nu; ++s) {
-            sweep(k, 0, s == 0);
-            sweep(k, 1, false);
-        }
-        const int Wc = t.W[k + 1], nc = t.W[k + 1] * t.H[k + 1], oc = t.off[k + 1];
-        for (int i = threadIdx.x; i < nc; i += kBlock) {
-            const int X = i % Wc, Y = i / Wc;
-            const double r00 = residual(k, 2 * X, 2 * Y), r10 = residual(k, 2 * X + 1, 2 * Y);
-            const double r01 = residual(k, 2 * X, 2 * Y + 1), r11 = residual(k, 2 * X + 1, 2 * Y + 1);
-            sb[oc + i] = (r00 + r10) + (r01 + r11);
-        }
-        __syncthreads();
-    }
-    {
-        const int n = t.W[last] * t.H[last], o = t.off[last];
-        for (int i = threadIdx.x; i < n; i += kBlock) sz[o + i] = sd[o + i] != 0.0 ? sb[o + i] / sd[o + i] : 0.0;
-        __syncthreads();
-    }
-    for (int k = last - 1; k >= 0; --k) {
-        const int W = t.W[k], n = t.W[k] * t.H[k], o = t.off[k], Wc = t.W[k + 1], oc = t.off[k + 1];
-        for (int i = threadIdx.x; i < n; i += kBlock) {
-            const int X = i % W, Y = i / W;
-            if (sd[o + i] != 0.0) sz[o + i] = sz[o + i] + cs * sz[oc + (Y >> 1) * Wc + (X >> 1)];
-        }
-        __syncthreads();
-        for (int s = 0; s < nu; ++s) {
-            sweep(k, 1, false);
-            sweep(k, 0, false);
-        }
-    }
-    const int W = t.W[0], n = t.W[0] * t.H[0];
-    for (int i = threadIdx.x; i < n; i += kBlock) z_top[mg_at(t.pitch[0], i % W, i / W)] = sz[i];
+    mg_tail_body(t, b_top + blockIdx.x * bs, z_top + blockIdx.x * zs, cs, nu);
 }
 
-// ---- the vector passes: k_cg_init, k_cg_dot, k_cg_update, k_cg_direction with the channel on grid y ------------------------
+// ---- the vector passes: the bodies of k_cg_init, k_cg_dot, k_cg_update, k_cg_direction (ccp_cg.hpp), the channel on grid y ----
 // grid = (the sequential pass's blocks, C).  Every vector has the channel stride n; partial: C slices ps apart.
 static __global__ void __launch_bounds__(kBlock)
 k_mgb_init(const double *__restrict__ b, double *__restrict__ r, double *__restrict__ p, long n, double *__restrict__ partial, long ps)
 {
     __shared__ double scratch[kBlock / kWave];
     const long o = (long)blockIdx.y * n;
-    double acc = 0.0;
-    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) {
-        const double v = b[o + i] - r[o + i];
-        r[o + i] = v;
-        p[o + i] = v;
-        acc += v * v;
-    }
-    const double t = block_sum(acc, scratch);
+    const double t = block_sum(cg_init_body(b, r, p, o, n), scratch);
     if (threadIdx.x == 0) partial[blockIdx.y * ps + blockIdx.x] = t;
 }
 
@@ -437,10 +333,7 @@ k_mgb_dot(const double *__restrict__ a, const double *__restrict__ b, long n, do
 {
     __shared__ double scratch[kBlock / kWave];
     const long o = (long)blockIdx.y * n;
-    double acc = 0.0;
-    if (st[blockIdx.y].active)
-        for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) acc += a[o + i] * b[o + i];
-    const double t = block_sum(acc, scratch);
+    const double t = block_sum(cg_dot_body(a, b, o, n, st + blockIdx.y), scratch);
     if (threadIdx.x == 0) partial[blockIdx.y * ps + blockIdx.x] = t;
 }
 
@@ -450,74 +343,43 @@ k_mgb_update(double *__restrict__ x, const double *__restrict__ p, double *__res
 {
     __shared__ double scratch[kBlock / kWave];
     const long o = (long)blockIdx.y * n;
-    double acc = 0.0;
-    if (st[blockIdx.y].active) {
-        const double alpha = st[blockIdx.y].alpha;
-        const double nalpha = -alpha;
-        for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) {
-            x[o + i] = x[o + i] + alpha * p[o + i];
-            const double v = r[o + i] + nalpha * ap[o + i];
-            r[o + i] = v;
-            acc += v * v;
-        }
-    }
-    const double t = block_sum(acc, scratch);
+    const double t = block_sum(cg_update_body(x, p, r, ap, o, n, st + blockIdx.y), scratch);
     if (threadIdx.x == 0) partial[blockIdx.y * ps + blockIdx.x] = t;
 }
 
 static __global__ void __launch_bounds__(kBlock)
 k_mgb_direction(double *__restrict__ p, const double *__restrict__ z, long n, const CgState *__restrict__ st)
 {
-    if (!st[blockIdx.y].active) return;
-    const long o = (long)blockIdx.y * n;
-    const double beta = st[blockIdx.y].beta;
-    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) p[o + i] = z[o + i] + beta * p[o + i];
+    cg_direction_body(p, z, (long)blockIdx.y * n, n, st + blockIdx.y);
 }
 
-// ---- the scalar passes: k_cg_set_rlen, k_cg_alpha, k_mg_check, k_mg_beta, one workgroup per channel ------------------------
+// ---- the scalar passes: the steps of k_cg_set_rlen, k_cg_alpha, k_mg_check, k_mg_beta, one workgroup per channel ----------
 static __global__ void __launch_bounds__(kBlock)
 k_mgb_set_rlen(const double *__restrict__ partial, long ps, int count, CgState *__restrict__ st)
 {
     __shared__ double scratch[kBlock / kWave];
-    const double t = reduce_partials(partial + blockIdx.x * ps, count, scratch);
-    if (threadIdx.x == 0) st[blockIdx.x].rlen = t;
+    cg_set_rlen_step(reduce_partials(partial + blockIdx.x * ps, count, scratch), st + blockIdx.x);
 }
 
 static __global__ void __launch_bounds__(kBlock)
 k_mgb_alpha(const double *__restrict__ partial, long ps, int count, CgState *__restrict__ st)
 {
     __shared__ double scratch[kBlock / kWave];
-    const double pap = reduce_partials(partial + blockIdx.x * ps, count, scratch);
-    CgState *s = st + blockIdx.x;
-    if (threadIdx.x == 0 && s->active) s->alpha = s->rlen / pap;
+    cg_alpha_step(reduce_partials(partial + blockIdx.x * ps, count, scratch), st + blockIdx.x);
 }
 
 static __global__ void __launch_bounds__(kBlock)
 k_mgb_check(const double *__restrict__ partial, long ps, int count, double epsilon, CgState *__restrict__ st)
 {
     __shared__ double scratch[kBlock / kWave];
-    const double rr = reduce_partials(partial + blockIdx.x * ps, count, scratch);
-    CgState *s = st + blockIdx.x;
-    if (threadIdx.x == 0 && s->active) {
-        s->r1norm = sqrt(rr);
-        if (s->r1norm < epsilon) {
-            s->active = 0;
-            s->converged = 1;
-        }
-    }
+    mg_check_step(reduce_partials(partial + blockIdx.x * ps, count, scratch), epsilon, st + blockIdx.x);
 }
 
 static __global__ void __launch_bounds__(kBlock)
 k_mgb_beta(const double *__restrict__ partial, long ps, int count, CgState *__restrict__ st)
 {
     __shared__ double scratch[kBlock / kWave];
-    const double rz = reduce_partials(partial + blockIdx.x * ps, count, scratch);
-    CgState *s = st + blockIdx.x;
-    if (threadIdx.x == 0 && s->active) {
-        s->beta = rz / s->rlen;
-        s->rlen = rz;
-        s->iterations += 1;
-    }
+    mg_beta_step(reduce_partials(partial + blockIdx.x * ps, count, scratch), st + blockIdx.x);
 }
 
 }  // namespace ccp

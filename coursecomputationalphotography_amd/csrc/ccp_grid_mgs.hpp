@@ -5,7 +5,10 @@
 // to nearest: k_mgs_narrow, which also gives the verdict of the narrowing) and a pixel is live if its float d != 0.
 // z := M^-1 r narrows r once on the way in, runs ccp_grid_mg.hpp's V-cycle with every value a float -- the same sweeps,
 // operation order, restriction order, cs, tile / tail / 1x1 structure -- and widens the result on the way out.  The
-// division is IEEE (correctly rounded, denormals kept) and nothing is contracted to an fma.
+// per-cell formulas and the tail's cycle are ccp_grid_mg.hpp's own templates (mg_nb_sum .., mg_tail_body) and
+// ccp_grid_stencil.hpp's gs_update / apply_row, instantiated for float; the level struct, the loads and the tile kernel
+// (colour-split LDS) are this file's.  The division is IEEE (correctly rounded, denormals kept) and nothing is
+// contracted to an fma.
 //
 // Where the conversions happen: in the level-0 kernels' loads and stores, never in a pass of their own.  B is the type
 // of a level's right-hand side in memory (double on level 0: the PCG's r; float below), Z the type the tile kernel
@@ -68,35 +71,26 @@ __device__ __forceinline__ bool mgs_live(const MgsLevel &lv, int x, int y)
     return lv.d[mg_at(lv.pitch, x, y)] != 0.0f;
 }
 
-// mg_update in float: one Gauss-Seidel update of (x,y) from b and the four neighbours' values (0 outside the level)
+// mg_update on floats: one Gauss-Seidel update of (x,y) from b and the four neighbours' values (0 outside the level), by
+// the formulas mg_update uses
 template <int KIND>
 __device__ __forceinline__ float mgs_update(const MgsLevel &lv, float bv, float xu, float xl, float xr, float xd, int x, int y)
 {
     const long at = mg_at(lv.pitch, x, y);
-    if (KIND == kMgSolve) {                                          // gs_update
-        const Stencil s = classify(lv.g0, x, y, y);
-        if (s.diag == 0) return 0.0f;
-        float sigma = 0.0f;
-        if (s.up) sigma += -1.0f * xu;
-        if (s.left) sigma += -1.0f * xl;
-        if (s.right) sigma += -1.0f * xr;
-        if (s.down) sigma += -1.0f * xd;
-        return (bv - sigma) / (float)s.diag;
+    if (KIND == kMgSolve) {
+        float out = 0.0f;
+        return gs_update(classify(lv.g0, x, y, y), bv, xu, xl, xr, xd, out) ? out : 0.0f;
     } else if (KIND == kMgMasked) {
-        return lv.mask[at] ? (bv + (((xu + xl) + xr) + xd)) * 0.25f : 0.0f;
+        return lv.mask[at] ? mg_masked_update(bv, xu, xl, xr, xd) : 0.0f;
     } else {
         const float d = lv.d[at];
         if (d == 0.0f) return 0.0f;
-        float s = 0.0f;
-        s += mgs_ld(lv.ws, lv, x, y - 1) * xu;
-        s += mgs_ld(lv.we, lv, x - 1, y) * xl;
-        s += lv.we[at] * xr;
-        s += lv.ws[at] * xd;
-        return (bv + s) / d;
+        const float s = mg_nb_sum(mgs_ld(lv.ws, lv, x, y - 1), xu, mgs_ld(lv.we, lv, x - 1, y), xl, lv.we[at], xr, lv.ws[at], xd);
+        return mg_stored_update(bv, s, d);
     }
 }
 
-// mg_residual in float: b - A z at (x,y), b narrowed on load; 0 outside the level and on dead pixels
+// mg_residual on floats: b - A z at (x,y), b narrowed on load; 0 outside the level and on dead pixels
 template <int KIND, typename B>
 __device__ __forceinline__ float mgs_residual(const MgsLevel &lv, const B *__restrict__ b, const float *__restrict__ z, int x, int y)
 {
@@ -104,34 +98,19 @@ __device__ __forceinline__ float mgs_residual(const MgsLevel &lv, const B *__res
     const long at = mg_at(lv.pitch, x, y);
     const float xi = z[at];
     const float xu = mgs_ld(z, lv, x, y - 1), xl = mgs_ld(z, lv, x - 1, y), xr = mgs_ld(z, lv, x + 1, y), xd = mgs_ld(z, lv, x, y + 1);
-    if (KIND == kMgSolve) {                                          // apply_row
+    if (KIND == kMgSolve) {
+        // apply_row adds the diagonal under `if (s.diag != 0)`; after the early return that is every time: the same bits
         const Stencil s = classify(lv.g0, x, y, y);
         if (s.diag == 0) return 0.0f;
-        float sum = 0.0f;
-        if (s.up) sum += -1.0f * xu;
-        if (s.left) sum += -1.0f * xl;
-        sum += (float)s.diag * xi;
-        if (s.right) sum += -1.0f * xr;
-        if (s.down) sum += -1.0f * xd;
-        return (float)b[at] - sum;
+        return (float)b[at] - apply_row(s, xi, xu, xl, xr, xd);
     } else if (KIND == kMgMasked) {
         if (!lv.mask[at]) return 0.0f;
-        float ax = 0.0f;
-        ax += -1.0f * xu;
-        ax += -1.0f * xl;
-        ax += 4.0f * xi;
-        ax += -1.0f * xr;
-        ax += -1.0f * xd;
-        return (float)b[at] - ax;
+        return (float)b[at] - mg_masked_row(xi, xu, xl, xr, xd);
     } else {
         const float d = lv.d[at];
         if (d == 0.0f) return 0.0f;
-        float s = 0.0f;
-        s += mgs_ld(lv.ws, lv, x, y - 1) * xu;
-        s += mgs_ld(lv.we, lv, x - 1, y) * xl;
-        s += lv.we[at] * xr;
-        s += lv.ws[at] * xd;
-        return (float)b[at] - (d * xi - s);
+        const float s = mg_nb_sum(mgs_ld(lv.ws, lv, x, y - 1), xu, mgs_ld(lv.we, lv, x - 1, y), xl, lv.we[at], xr, lv.ws[at], xd);
+        return mg_stored_residual((float)b[at], d, xi, s);
     }
 }
 
@@ -208,99 +187,14 @@ k_mgs_tile(MgsLevel lv, const B *__restrict__ b, const float *__restrict__ z_in,
     }
 }
 
-// ---- the tail: k_mg_tail in float (every level from the tail's first down to 1x1 in one workgroup, resident in LDS) ----
-struct MgsTail {
-    int levels;
-    int W[kMgTailLevels], H[kMgTailLevels], off[kMgTailLevels];
-    long pitch[kMgTailLevels];
-    const float *d[kMgTailLevels], *we[kMgTailLevels], *ws[kMgTailLevels];
-};
+// ---- the tail: mg_tail_body (ccp_grid_mg.hpp) on floats, every level from the tail's first down to 1x1 in one workgroup ----
+using MgsTail = MgTailT<float>;
 
 static __global__ void __launch_bounds__(kBlock)
 k_mgs_tail(MgsTail t, const float *__restrict__ b_top, float *__restrict__ z_top, float cs, int nu, const CgState *__restrict__ st)
 {
     if (st && !st->active) return;
-    __shared__ float sd[kMgTailCells], swe[kMgTailCells], sws[kMgTailCells], sb[kMgTailCells], sz[kMgTailCells];
-    for (int k = 0; k < t.levels; ++k) {
-        const int W = t.W[k], n = t.W[k] * t.H[k];
-        for (int i = threadIdx.x; i < n; i += kBlock) {
-            const long at = mg_at(t.pitch[k], i % W, i / W);
-            sd[t.off[k] + i] = t.d[k][at];
-            swe[t.off[k] + i] = t.we[k][at];
-            sws[t.off[k] + i] = t.ws[k][at];
-            if (k == 0) sb[i] = b_top[at];
-        }
-    }
-    __syncthreads();
-    auto sum_nb = [&](int k, int X, int Y, float &xi) -> float {
-        const int W = t.W[k], H = t.H[k], o = t.off[k], i = o + Y * W + X;
-        xi = sz[i];
-        float s = 0.0f;
-        s += (Y > 0 ? sws[i - W] : 0.0f) * (Y > 0 ? sz[i - W] : 0.0f);
-        s += (X > 0 ? swe[i - 1] : 0.0f) * (X > 0 ? sz[i - 1] : 0.0f);
-        s += swe[i] * (X + 1 < W ? sz[i + 1] : 0.0f);
-        s += sws[i] * (Y + 1 < H ? sz[i + W] : 0.0f);
-        return s;
-    };
-    auto sweep = [&](int k, int c, bool first) {
-        const int W = t.W[k], n = t.W[k] * t.H[k], o = t.off[k];
-        for (int i = threadIdx.x; i < n; i += kBlock) {
-            const int X = i % W, Y = i / W;
-            if (((X + Y) & 1) != c) continue;
-            const float d = sd[o + i];
-            float v = 0.0f;
-            if (d != 0.0f) {
-                float xi;
-                const float s = first ? 0.0f : sum_nb(k, X, Y, xi);
-                v = (sb[o + i] + s) / d;
-            }
-            sz[o + i] = v;
-        }
-        __syncthreads();
-    };
-    auto residual = [&](int k, int X, int Y) -> float {
-        if (X >= t.W[k] || Y >= t.H[k]) return 0.0f;
-        const int i = t.off[k] + Y * t.W[k] + X;
-        const float d = sd[i];
-        if (d == 0.0f) return 0.0f;
-        float xi;
-        const float s = sum_nb(k, X, Y, xi);
-        return sb[i] - (d * xi - s);
-    };
-    const int last = t.levels - 1;
-    for (int k = 0; k < last; ++k) {
-        for (int s = 0; s < nu; ++s) {
-            sweep(k, 0, s == 0);
-            sweep(k, 1, false);
-        }
-        const int Wc = t.W[k + 1], nc = t.W[k + 1] * t.H[k + 1], oc = t.off[k + 1];
-        for (int i = threadIdx.x; i < nc; i += kBlock) {
-            const int X = i % Wc, Y = i / Wc;
-            const float r00 = residual(k, 2 * X, 2 * Y), r10 = residual(k, 2 * X + 1, 2 * Y);
-            const float r01 = residual(k, 2 * X, 2 * Y + 1), r11 = residual(k, 2 * X + 1, 2 * Y + 1);
-            sb[oc + i] = (r00 + r10) + (r01 + r11);
-        }
-        __syncthreads();
-    }
-    {
-        const int n = t.W[last] * t.H[last], o = t.off[last];
-        for (int i = threadIdx.x; i < n; i += kBlock) sz[o + i] = sd[o + i] != 0.0f ? sb[o + i] / sd[o + i] : 0.0f;
-        __syncthreads();
-    }
-    for (int k = last - 1; k >= 0; --k) {
-        const int W = t.W[k], n = t.W[k] * t.H[k], o = t.off[k], Wc = t.W[k + 1], oc = t.off[k + 1];
-        for (int i = threadIdx.x; i < n; i += kBlock) {
-            const int X = i % W, Y = i / W;
-            if (sd[o + i] != 0.0f) sz[o + i] = sz[o + i] + cs * sz[oc + (Y >> 1) * Wc + (X >> 1)];
-        }
-        __syncthreads();
-        for (int s = 0; s < nu; ++s) {
-            sweep(k, 1, false);
-            sweep(k, 0, false);
-        }
-    }
-    const int W = t.W[0], n = t.W[0] * t.H[0];
-    for (int i = threadIdx.x; i < n; i += kBlock) z_top[mg_at(t.pitch[0], i % W, i / W)] = sz[i];
+    mg_tail_body(t, b_top, z_top, cs, nu);
 }
 
 }  // namespace ccp

@@ -67,31 +67,32 @@ __device__ __forceinline__ Stencil classify(const Geom &g, int x, int y, int l)
 }
 
 // (b - sigma) / a_ii with the reference's accumulation order.  Returns false when the row is
-// skipped (a_ii == 0, sparse-matrix.h:361-363).
-__device__ __forceinline__ bool gs_update(const Stencil &s, double bv, double xu, double xl,
-                                          double xr, double xd, double &out)
+// skipped (a_ii == 0, sparse-matrix.h:361-363).  T is deduced from the values: double everywhere
+// but in the fp32 V-cycle (ccp_grid_mgs.hpp), which runs the same statement on floats.
+template <typename T>
+__device__ __forceinline__ bool gs_update(const Stencil &s, T bv, T xu, T xl, T xr, T xd, T &out)
 {
     if (s.diag == 0) return false;
-    double sigma = 0.0;
-    if (s.up) sigma += -1.0 * xu;
-    if (s.left) sigma += -1.0 * xl;
-    if (s.right) sigma += -1.0 * xr;
-    if (s.down) sigma += -1.0 * xd;
-    out = (bv - sigma) / (double)s.diag;
+    T sigma = T(0);
+    if (s.up) sigma += T(-1) * xu;
+    if (s.left) sigma += T(-1) * xl;
+    if (s.right) sigma += T(-1) * xr;
+    if (s.down) sigma += T(-1) * xd;
+    out = (bv - sigma) / (T)s.diag;
     return true;
 }
 
 // A x for one pixel in applyToVector's order (sparse-matrix.h:382-393): up, left, diagonal,
-// right, down; empty rows give 0.
-__device__ __forceinline__ double apply_row(const Stencil &s, double xi, double xu, double xl,
-                                            double xr, double xd)
+// right, down; empty rows give 0.  T as gs_update's.
+template <typename T>
+__device__ __forceinline__ T apply_row(const Stencil &s, T xi, T xu, T xl, T xr, T xd)
 {
-    double sum = 0.0;
-    if (s.up) sum += -1.0 * xu;
-    if (s.left) sum += -1.0 * xl;
-    if (s.diag != 0) sum += (double)s.diag * xi;
-    if (s.right) sum += -1.0 * xr;
-    if (s.down) sum += -1.0 * xd;
+    T sum = T(0);
+    if (s.up) sum += T(-1) * xu;
+    if (s.left) sum += T(-1) * xl;
+    if (s.diag != 0) sum += (T)s.diag * xi;
+    if (s.right) sum += T(-1) * xr;
+    if (s.down) sum += T(-1) * xd;
     return sum;
 }
 

@@ -3,7 +3,8 @@
 The reference is the same handle in sequential mode, and equality is of bits: the raw float64 of x per channel, equal
 `iterations` and `converged`, `last_l1_step` equal as bits.  Kinds: structured, mask (disc and blob), weighted Galerkin,
 weighted rescaled, rescaled with 10 % fixed pixels (tests/test_gpu_mixed.py's constructions); shapes 1x1 (the one-level
-path), 5x3 (the tail directly under level 0), 70x40 (two tiles over one tile level, the halo crossing a tile edge),
+path), 5x3 (the tail directly under level 0), 64x64 and 63x33 (a full six-level tail from 32x32, all 1,365 LDS cells,
+and one from a non-square 32x17), 70x40 (two tiles over one tile level, the halo crossing a tile edge),
 257x131 (three tile levels, odd sizes, partial edge tiles); C = 1, 2, 3, and 5 once (a second channel group); nu = 2
 everywhere, 1 and 4 on 70x40.  Channels that stop at different iterations, the iteration cap across the 16-iteration
 batch edge, the mode's handling and what it survives, the refusals (f32, row-block calls, unknown values), tensor_ops
@@ -24,7 +25,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 BAD_ARG, UNSUPPORTED = 1, 6
 KINDS = ["structured", "mask", "galerkin", "rescaled", "rescaled_fixed"]
-SHAPES = [(1, 1), (5, 3), (70, 40), (257, 131)]
+SHAPES = [(1, 1), (5, 3), (63, 33), (64, 64), (70, 40), (257, 131)]
 
 
 def weights(W, H, seed):

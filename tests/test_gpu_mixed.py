@@ -3,7 +3,8 @@
 A fresh handle reports f64, and a round trip through f32 leaves its levels and its V-cycle bit for bit what a handle
 that was never switched gives.  In f32, one V-cycle (nu = 1, 2) equals tests/mixed_helpers.py's float32 V-cycle bit for
 bit on structured, mask, weighted (Galerkin, rescaled, rescaled with fixed pixels) handles, on the one-level path (1x1),
-the tail directly under level 0 (5x3), two tiles over one tile level (70x40) and three tile levels with odd sizes and
+the tail directly under level 0 (5x3), a full tail of six levels from 32x32 (64x64: all 1,365 LDS cells) and one whose
+first level is not square (63x33: 32x17), two tiles over one tile level (70x40) and three tile levels with odd sizes and
 partial edge tiles (257x131).  MG-PCG in f32 takes the model's fp32 count (+-1: the device's dot products are
 tree-ordered), converges, leaves an fp64 residual below epsilon, and on the screened system agrees with the f64 mode's x
 to 2 epsilon / min lambda.  Channels are independent, bad arguments, row blocks and weights a float cannot hold are
@@ -109,7 +110,7 @@ def test_default_is_f64_and_the_round_trip_keeps_its_bits(kind):
 
 # ---- 2. one V-cycle, bit for bit ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("W,H", [(1, 1), (5, 3), (70, 40), (257, 131)])
+@pytest.mark.parametrize("W,H", [(1, 1), (5, 3), (63, 33), (64, 64), (70, 40), (257, 131)])
 def test_f32_vcycle_bit_identical(W, H, kind):
     g, levels, cs = handle(kind, W, H)
     g.mg_set_precision("f32")
