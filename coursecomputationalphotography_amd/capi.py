@@ -77,6 +77,8 @@ ABI_SYMBOLS = (
     "ccp_grid_set_weights_constrained_host", "ccp_grid_set_weights_constrained_device", "ccp_grid_assemble_constrained_rhs",
     "ccp_grid_assemble_constrained_rhs_device", "ccp_grid_constraint_info",
     "ccp_grid_adjoint_begin_device", "ccp_grid_weighted_adjoint_device",
+    "ccp_grid_set_weights_per_channel_device", "ccp_grid_operator_channels", "ccp_grid_mg_level_channel",
+    "ccp_grid_constraint_info_channel",
     "ccp_grid_set_mask_device", "ccp_mask_erode_cross_device", "ccp_panorama_begin_device", "ccp_panorama_add_device",
     "ccp_panorama_finish_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
@@ -296,6 +298,10 @@ def load() -> C.CDLL:
     L.ccp_grid_assemble_constrained_rhs.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i32]
     L.ccp_grid_assemble_constrained_rhs_device.argtypes = [vp, da, da, da, da, i32]
     L.ccp_grid_constraint_info.argtypes = [vp, vp, vp, vp]
+    L.ccp_grid_set_weights_per_channel_device.argtypes = [vp, vp, vp, vp, vp]
+    L.ccp_grid_operator_channels.argtypes = [vp, C.POINTER(i32)]
+    L.ccp_grid_mg_level_channel.argtypes = [vp, i32, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
+    L.ccp_grid_constraint_info_channel.argtypes = [vp, i32, vp, vp, vp]
     L.ccp_grid_adjoint_begin_device.argtypes = [vp, da]
     L.ccp_grid_weighted_adjoint_device.argtypes = [vp, C.POINTER(AdjointInputs), C.POINTER(AdjointOutputs)]
     L.ccp_grid_set_mask_device.argtypes = [vp, da]
@@ -801,17 +807,22 @@ class Grid:
         check(self.L.ccp_grid_mg_get_smoother(self.h, C.byref(value)), "ccp_grid_mg_get_smoother")
         return next(name for name, v in MG_SMOOTHERS.items() if v == value.value)
 
-    def mg_levels(self):
-        """The multigrid hierarchy: one (diag, w_east, w_south) triple of H_k x W_k arrays per level, level 0 first."""
-        n, w, h = C.c_int32(), C.c_int32(), C.c_int32()
-        check(self.L.ccp_grid_mg_level(self.h, 0, C.byref(n), None, None, None, None, None), "ccp_grid_mg_level")
-        levels = []
-        for k in range(n.value):
-            check(self.L.ccp_grid_mg_level(self.h, k, None, C.byref(w), C.byref(h), None, None, None), "ccp_grid_mg_level")
-            d, we, ws = (np.empty((h.value, w.value), dtype=np.float64) for _ in range(3))
-            check(self.L.ccp_grid_mg_level(self.h, k, None, None, None, _ptr(d), _ptr(we), _ptr(ws)), "ccp_grid_mg_level")
-            levels.append((d, we, ws))
-        return levels
+    def mg_levels(self, channel: int = 0):
+        """The multigrid hierarchy: one (diag, w_east, w_south) triple of H_k x W_k arrays per level, level 0 first.
+        channel: whose hierarchy, on a handle with one operator per channel (set_weights_per_channel_tensor)."""
+        n = C.c_int32()
+        check(self.L.ccp_grid_mg_level_channel(self.h, channel, 0, C.byref(n), None, None, None, None, None), "ccp_grid_mg_level_channel")
+        return [self.mg_level(k, channel) for k in range(n.value)]
+
+    def mg_level(self, level: int, channel: int = 0):
+        """(diag, w_east, w_south) of one level of channel `channel`'s hierarchy."""
+        w, h = C.c_int32(), C.c_int32()
+        check(self.L.ccp_grid_mg_level_channel(self.h, channel, level, None, C.byref(w), C.byref(h), None, None, None),
+              "ccp_grid_mg_level_channel")
+        d, we, ws = (np.empty((h.value, w.value), dtype=np.float64) for _ in range(3))
+        check(self.L.ccp_grid_mg_level_channel(self.h, channel, level, None, None, None, _ptr(d), _ptr(we), _ptr(ws)),
+              "ccp_grid_mg_level_channel")
+        return d, we, ws
 
     def residual_norm2(self):
         out = np.empty(2 * self.C, dtype=np.float64)
@@ -1087,11 +1098,21 @@ class Grid:
         check(self.L.ccp_grid_assemble_constrained_rhs(self.h, _ptr(gx), _ptr(gy), row, _ptr(f), row, _ptr(values), row,
                                                        1 if init_x else 0), "ccp_grid_assemble_constrained_rhs")
 
-    def constraint_info(self):
-        """(fixed pixels, free pixels with a non-empty row, edges with exactly one fixed end) of the installed operator."""
+    def constraint_info(self, channel=None):
+        """(fixed pixels, free pixels with a non-empty row, edges with exactly one fixed end) of the installed operator;
+        channel: of that channel's operator (None: channel 0, the shared operator's call)."""
         n = [C.c_int64() for _ in range(3)]
-        check(self.L.ccp_grid_constraint_info(self.h, *[C.byref(v) for v in n]), "ccp_grid_constraint_info")
+        if channel is None:
+            check(self.L.ccp_grid_constraint_info(self.h, *[C.byref(v) for v in n]), "ccp_grid_constraint_info")
+        else:
+            check(self.L.ccp_grid_constraint_info_channel(self.h, channel, *[C.byref(v) for v in n]), "ccp_grid_constraint_info_channel")
         return tuple(v.value for v in n)
+
+    def operator_channels(self) -> int:
+        """1: one operator shared by all channels (set_weights*); channels: one per channel (set_weights_per_channel_tensor)."""
+        n = C.c_int32()
+        check(self.L.ccp_grid_operator_channels(self.h, C.byref(n)), "ccp_grid_operator_channels")
+        return n.value
 
     def assemble_weighted_rhs(self, gx=None, gy=None, f=None, init_x: bool = False):
         """b of every channel from float32 H x W x channels host arrays: guidance gx, gy (None: 0) and data f (None: 0);
@@ -1131,6 +1152,32 @@ class Grid:
                 raise ValueError(f"{name} must be {self.H} x {self.W}, not {tuple(fixed.shape)}")
             return DeviceArray(*self._label_array(fixed.unsqueeze(-1)))
         return self._weight_array(fixed, name)
+
+    def _channel_array(self, t, name, dtypes, output=False):
+        """ccp_device_array of an H x W x channels tensor of the per-channel calls; an H x W tensor (an expanded scalar
+        too) is passed with stride_c = 0: every channel reads the one plane.  bool is read as uint8."""
+        if t is None:
+            return None
+        torch = self._torch()
+        if isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+            t = t.view(torch.uint8)
+        if isinstance(t, torch.Tensor) and t.dim() == 2 and not output:
+            t = t.unsqueeze(-1).expand(-1, -1, self.C)
+        return self._hwc(t, name, dtypes, output=output)[0]
+
+    def set_weights_per_channel_tensor(self, wx=None, wy=None, lam=None, fixed=None):
+        """One operator PER CHANNEL from H x W x channels float32 / float64 tensors (an H x W tensor or an expanded scalar
+        serves every channel); fixed: H x W x channels uint8, bool, float32 or float64 (!= 0: fixed), None: no fixed
+        pixels.  Channel c then behaves, bit for bit, as a one-channel handle given channel c's slices through
+        set_weights_tensor.  Synchronises (the verdict); a bad weight in any channel raises CcpError (BAD_ARG) and leaves
+        the handle without an operator.  set_weights* returns to the shared operator."""
+        torch = self._torch()
+        floats = (torch.float32, torch.float64)
+        arrs = [self._channel_array(t, n, floats) for t, n in ((wx, "wx"), (wy, "wy"), (lam, "lam"))]
+        arrs.append(self._channel_array(fixed, "fixed", (torch.uint8,) + floats))
+        refs = [None if a is None else C.byref(a) for a in arrs]
+        self._on_stream(lambda: self.L.ccp_grid_set_weights_per_channel_device(self.h, *refs),
+                        "ccp_grid_set_weights_per_channel_device")
 
     def set_mask_tensor(self, mask):
         """set_mask from an H x W uint8, bool, float32 or float64 tensor of the whole canvas (!= 0: inside the region),
@@ -1195,9 +1242,18 @@ class Grid:
         gradients to compute, of "wx", "wy", "lam" (H x W) and "gx", "gy", "f", "values" (H x W x channels); "values"
         needs `grad` (dL/du).  Only those are computed, and only the inputs they need are read.  Returns {name: tensor};
         a tensor given in `out` ({name: tensor}, float32 or float64, any non-overlapping view) is filled, the others are
-        allocated as `dtype` (float64 by default)."""
+        allocated as `dtype` (float64 by default).  On a handle with one operator per channel
+        (set_weights_per_channel_tensor) wx, wy, lam, fixed are H x W x channels (H x W: every channel's) and the
+        gradients "wx", "wy", "lam" come back H x W x channels, channel c's from channel c alone."""
         torch = self._torch()
         want = tuple(want)
+        n_op = C.c_int32(1)                                          # (no operator, not weighted: the call below refuses)
+        per_channel = self.L.ccp_grid_operator_channels(self.h, C.byref(n_op)) == 0 and n_op.value > 1
+        if self.C == 1:
+            # one channel: the two layouts address the same elements, and ccp_grid_operator_channels cannot tell them apart
+            # (it says 1 for both), so the tensors decide: an H x W x 1 weight, mask or weight gradient is a stack of one
+            given = [wx, wy, lam, fixed] + [(out or {}).get(n) for n in ("wx", "wy", "lam")]
+            per_channel = any(isinstance(t, torch.Tensor) and t.dim() == 3 for t in given)
         planes, images = ("wx", "wy", "lam"), ("gx", "gy", "f", "values")
         unknown = [n for n in want if n not in planes + images] + [n for n in (out or {}) if n not in want]
         if unknown:
@@ -1209,17 +1265,22 @@ class Grid:
                "grad_x": None if grad is None else self._hwc(grad, "grad", floats)[0],
                "gx": None if gx is None else self._hwc(gx, "gx", (torch.float32,))[0],
                "gy": None if gy is None else self._hwc(gy, "gy", (torch.float32,))[0],
-               "f": None if f is None else self._hwc(f, "f", any_)[0],
-               "wx": self._weight_array(wx, "wx"), "wy": self._weight_array(wy, "wy"), "lambda": self._weight_array(lam, "lam"),
-               "fixed": None if fixed is None else self._mask_array(fixed)}
+               "f": None if f is None else self._hwc(f, "f", any_)[0]}
+        if per_channel:
+            ins.update({"wx": self._channel_array(wx, "wx", floats), "wy": self._channel_array(wy, "wy", floats),
+                        "lambda": self._channel_array(lam, "lam", floats), "fixed": self._channel_array(fixed, "fixed", any_)})
+        else:
+            ins.update({"wx": self._weight_array(wx, "wx"), "wy": self._weight_array(wy, "wy"), "lambda": self._weight_array(lam, "lam"),
+                        "fixed": None if fixed is None else self._mask_array(fixed)})
         result, outs = {}, {}
         for n in want:
             t = (out or {}).get(n)
             if t is None:
-                shape = (self.H, self.W) if n in planes else (self.H, self.W, self.C)
+                shape = (self.H, self.W) if n in planes and not per_channel else (self.H, self.W, self.C)
                 with torch.cuda.device(self._device()):
                     t = torch.empty(shape, dtype=dtype or torch.float64, device=self._device())
-            outs["g_lambda" if n == "lam" else "g_" + n] = self._plane_out(t, n) if n in planes else self._hwc(t, n, floats, output=True)[0]
+            plane = n in planes and not per_channel
+            outs["g_lambda" if n == "lam" else "g_" + n] = self._plane_out(t, n) if plane else self._hwc(t, n, floats, output=True)[0]
             result[n] = t
         a = AdjointInputs(*[None if ins[n] is None else C.pointer(ins[n]) for n in ADJOINT_INPUTS])
         b = AdjointOutputs(*[None if outs.get(n) is None else C.pointer(outs[n]) for n in ADJOINT_OUTPUTS])

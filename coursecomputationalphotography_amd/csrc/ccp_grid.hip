@@ -8,6 +8,7 @@
 #include "ccp_grid_mg_view.hpp"
 #include "ccp_grid_blend.hpp"
 #include "ccp_grid_weighted.hpp"
+#include "ccp_grid_pco_api.hpp"
 #include "ccp_grid_adjoint.hpp"
 #include "ccp_comm.hpp"
 #include "ccp_view_check.hpp"
@@ -151,6 +152,13 @@ struct ccp_grid {
     DevBuf<double> wcons;
     DevBuf<unsigned long long> wcount;
     long w_fixed = 0, w_live = -1, w_edges = 0;
+    // One operator per channel (ccp_grid_set_weights_per_channel_device, ccp_grid_pco.hpp): wop then holds `channels` sets
+    // of the four planes, 4 x ch_stride apart, and wcons (while any channel has a fixed pixel) `channels` sets of its three,
+    // 3 x ch_stride apart; pc_*: every channel's figures (w_fixed, w_live, w_edges are channel 0's).  op_sets: the sets wop
+    // holds now, 1 after the shared operator's setters.
+    bool per_channel = false;
+    int op_sets = 1;
+    long pc_fixed[kMaxChannels] = {}, pc_live[kMaxChannels] = {}, pc_edges[kMaxChannels] = {};
     int mg_kind = CCP_MG_HIERARCHY_GALERKIN;   // ccp_grid_mg_set_hierarchy (weighted handles; survives ccp_grid_set_weights_*)
     int mg_channels = CCP_MG_CHANNELS_SEQUENTIAL;   // ccp_grid_mg_set_channels (survives what mg_precision survives, and set_precision)
     int mg_smoother = CCP_MG_SMOOTHER_POINT;   // ccp_grid_mg_set_smoother (survives what mg_channels survives, and set_channels)
@@ -803,6 +811,28 @@ dim3 weighted_apply_grid(const ccp_grid *g)
     return dim3((unsigned)std::max<long>(1, std::min<long>(kWeightedApplyBlocks, (cells + kBlock - 1) / kBlock)), 1, 2 * (unsigned)g->desc.channels);
 }
 
+// b := A x (MODE 0) or the residual's partial sums (MODE 1) of every channel of a weighted handle.  With one operator
+// per channel the same kernel runs once per channel on that channel's planes, vectors and slice of the partial sums:
+// the launch a one-channel handle makes.
+template <int MODE>
+int weighted_apply(ccp_grid *g)
+{
+    dim3 grid = weighted_apply_grid(g);
+    const long n = g->geom.ch_stride;
+    if (!g->per_channel) {
+        hipLaunchKernelGGL((k_weighted_apply<MODE>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->b.p, g->geom, g->wop.p, n, g->wpart.p);
+        CCP_HIP(hipGetLastError());
+        return CCP_OK;
+    }
+    grid.z = 2;
+    for (int ch = 0; ch < g->desc.channels; ++ch) {
+        hipLaunchKernelGGL((k_weighted_apply<MODE>), grid, dim3(kBlock), 0, g->stream, g->x.p + ch * n, g->b.p + ch * n, g->geom,
+                           g->wop.p + 4 * ch * n, n, g->wpart.p + 4L * ch * grid.x);
+        CCP_HIP(hipGetLastError());
+    }
+    return CCP_OK;
+}
+
 int begin_timing(ccp_grid *g)
 {
     g->last_launches = 0;
@@ -1073,7 +1103,7 @@ try {
         st = g->wop.alloc(4 * (size_t)geo.ch_stride);
         if (st == CCP_OK && hipMemset(g->wop.p, 0, 4 * sizeof(double) * (size_t)geo.ch_stride) != hipSuccess) st = CCP_ERR_HIP;
         if (st == CCP_OK) st = g->wpart.alloc(4 * (size_t)d->channels * kWeightedApplyBlocks);
-        if (st == CCP_OK) st = g->wcount.alloc(4);
+        if (st == CCP_OK) st = g->wcount.alloc(1 + 3 * kMaxChannels);
     }
     // partial sums: the finest launch is one block per (x tile, row, channel*2) with 2 doubles
     const size_t part = (size_t)((geo.pitch + 2L * kBlock - 1) / (2L * kBlock)) * geo.local_rows * d->channels * 2 * 2 + 64;
@@ -1262,6 +1292,9 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     v->wwe = op ? op + n : nullptr;
     v->wws = op ? op + 2 * n : nullptr;
     v->wlam = !op ? nullptr : g->has_fixed ? g->wcons.p + 2 * n : op + 3 * n;   // with fixed pixels: lambda' (ccp_grid_weighted.hpp)
+    v->op_channels = g->weighted && g->has_op && g->per_channel ? g->desc.channels : 1;
+    v->op_stride = 4 * n;
+    v->lam_stride = g->has_fixed ? 3 * n : 4 * n;
     v->hierarchy_kind = g->mg_kind;
     v->precision = g->mg_precision;
     v->channels_mode = g->mg_channels;
@@ -1364,10 +1397,7 @@ try {
     CCP_TRY(bind(g));
     if (g->weighted) {
         if (!g->has_op) return CCP_ERR_STATE;
-        hipLaunchKernelGGL((k_weighted_apply<0>), weighted_apply_grid(g), dim3(kBlock), 0, g->stream, g->x.p, g->b.p, g->geom, g->wop.p,
-                           g->geom.ch_stride, g->wpart.p);
-        CCP_HIP(hipGetLastError());
-        return CCP_OK;
+        return weighted_apply<0>(g);
     }
     if ((g->shrink_top || g->shrink_bottom) && g->half_sweeps_since_refresh >= g->desc.ghost) return CCP_ERR_STATE;
     const Geom &geo = g->geom;
@@ -2122,8 +2152,7 @@ int residual_to_small(ccp_grid *g)
     if (g->weighted) {
         if (!g->has_op) return CCP_ERR_STATE;
         const dim3 wg = weighted_apply_grid(g);
-        hipLaunchKernelGGL((k_weighted_apply<1>), wg, dim3(kBlock), 0, g->stream, g->x.p, g->b.p, g->geom, g->wop.p, g->geom.ch_stride, g->wpart.p);
-        CCP_HIP(hipGetLastError());
+        CCP_TRY(weighted_apply<1>(g));
         hipLaunchKernelGGL(k_pair_reduce, dim3((unsigned)C), dim3(kBlock), 0, g->stream, g->wpart.p, (long)wg.x, g->small.p);
         CCP_HIP(hipGetLastError());
         return CCP_OK;
@@ -2922,9 +2951,23 @@ int weighted_rhs_host(ccp_grid *g, const float *gx, const float *gy, int64_t fie
         CCP_TRY(upload_window(g, dev[i], src[i], stride[i], 0, H));
         v[i] = staged_view<const float>(dev[i].p, W, C);
     }
-    CCP_TRY(weighted_rhs(g, v[0], v[1], v[2], has, init_x, v[3]));
+    if (g->per_channel) {
+        PcoView pv[4];
+        for (int i = 0; i < 4; ++i) pv[i] = PcoView{v[i].p, v[i].sy, v[i].sx, v[i].sc, CCP_DTYPE_F32, 0.0};
+        CCP_TRY(pco_rhs(g->stream, g->b.p, g->x.p, g->geom, C, g->wop.p, g->has_fixed ? g->wcons.p : nullptr, pv[0], pv[1], pv[2], pv[3], has,
+                        init_x));
+    } else {
+        CCP_TRY(weighted_rhs(g, v[0], v[1], v[2], has, init_x, v[3]));
+    }
     CCP_HIP(hipStreamSynchronize(g->stream));
     return CCP_OK;
+}
+
+// a caller's view (or none) as the per-channel kernels read it
+PcoView pco_view(const ccp_device_array *a, double dflt)
+{
+    if (!a) return PcoView{nullptr, 0, 0, 0, 0, dflt};
+    return PcoView{a->data, (long)a->stride_y, (long)a->stride_x, (long)a->stride_c, a->dtype, dflt};
 }
 
 int weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f,
@@ -2937,6 +2980,9 @@ int weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_devic
     if (values) CCP_TRY(check_view(g, values, kF32F64 | kU8, false, 1, H, W, C));
     if (!g->has_op) return CCP_ERR_STATE;
     const int has = (gx ? 1 : 0) | (gy ? 2 : 0) | (f ? 4 : 0) | (values ? 8 : 0);
+    if (g->per_channel)
+        return pco_rhs(g->stream, g->b.p, g->x.p, g->geom, C, g->wop.p, g->has_fixed ? g->wcons.p : nullptr, pco_view(gx, 0.0), pco_view(gy, 0.0),
+                       pco_view(f, 0.0), pco_view(values, 0.0), has, init);
     if (!values) return weighted_rhs_views(g, gx, gy, f, has, init, VF{nullptr, 0, 0, 0, 0});
     if (values->dtype == CCP_DTYPE_U8) return weighted_rhs_views(g, gx, gy, f, has, init, view_of<const uint8_t>(values));
     if (values->dtype == CCP_DTYPE_F32) return weighted_rhs_views(g, gx, gy, f, has, init, view_of<const float>(values));
@@ -3308,6 +3354,69 @@ void drop_operator(ccp_grid *g)
     g->has_op = g->has_fixed = false;
     g->w_fixed = g->w_edges = 0;
     g->w_live = -1;
+    g->per_channel = false;
+}
+
+// wop for `sets` operators (1: the shared one; channels: one per channel), pads zero; what it held is gone
+int operator_planes(ccp_grid *g, int sets)
+{
+    if (g->op_sets == sets) return CCP_OK;
+    const size_t count = 4 * (size_t)sets * (size_t)g->geom.ch_stride;
+    g->op_sets = 0;
+    CCP_TRY(g->wop.alloc(count));
+    CCP_HIP(hipMemsetAsync(g->wop.p, 0, sizeof(double) * count, g->stream));
+    g->op_sets = sets;
+    return CCP_OK;
+}
+
+// One operator per channel (ccp_grid_pco.hpp): all channels' planes in one launch, the verdict and, with a mask, every
+// channel's counts in one read.  The three extra planes stay only if some channel has a fixed pixel.
+int set_weights_per_channel(ccp_grid *g, const PcoView &wx, const PcoView &wy, const PcoView &lam, const PcoView *fixed)
+{
+    const Geom &geo = g->geom;
+    const long n = geo.ch_stride;
+    const int C = g->desc.channels;
+    drop_operator(g);
+    g->wcons.release();
+    CCP_TRY(operator_planes(g, C));
+    if (fixed) {
+        CCP_TRY(g->wcons.alloc(3 * (size_t)C * (size_t)n));
+        CCP_HIP(hipMemsetAsync(g->wcons.p, 0, 3 * sizeof(double) * (size_t)C * (size_t)n, g->stream));   // the pads
+    }
+    CCP_TRY(pco_coef(g->stream, wx, wy, lam, fixed, geo.W, geo.H, C, geo.pitch, g->wop.p, n, g->wcons.p, g->wcount.p));
+    unsigned long long count[1 + 3 * kMaxChannels] = {1};
+    CCP_HIP(hipMemcpyAsync(count, g->wcount.p, sizeof(unsigned long long) * (size_t)(1 + 3 * C), hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    bool any_fixed = false;
+    for (int c = 0; c < C && fixed; ++c) any_fixed = any_fixed || count[1 + 3 * c] != 0;
+    if (count[0] || !any_fixed) g->wcons.release();
+    if (count[0]) return CCP_ERR_BAD_ARG;
+    for (int c = 0; c < C; ++c) {
+        g->pc_fixed[c] = fixed ? (long)count[1 + 3 * c] : 0;
+        g->pc_live[c] = fixed ? (long)geo.W * geo.H - (long)count[1 + 3 * c] - (long)count[2 + 3 * c] : -1;
+        g->pc_edges[c] = fixed ? (long)count[3 + 3 * c] : 0;
+    }
+    g->has_op = true;
+    g->per_channel = true;
+    g->has_fixed = any_fixed;
+    g->w_fixed = g->pc_fixed[0];
+    g->w_live = g->pc_live[0];
+    g->w_edges = g->pc_edges[0];
+    return edge_timeout_status(g);
+}
+
+// a channel's dead pixels counted once (an operator formed without a mask)
+int count_live(ccp_grid *g, const double *d, long *live)
+{
+    const Geom &geo = g->geom;
+    unsigned long long dead = 0;
+    CCP_HIP(hipMemsetAsync(g->wcount.p, 0, sizeof(unsigned long long), g->stream));
+    hipLaunchKernelGGL(k_weighted_count_dead, pixel_grid(g, geo.H), dim3(kBlock), 0, g->stream, d, geo.W, geo.H, geo.pitch, g->wcount.p);
+    CCP_HIP(hipGetLastError());
+    CCP_HIP(hipMemcpyAsync(&dead, g->wcount.p, sizeof(dead), hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    *live = (long)geo.W * geo.H - (long)dead;
+    return CCP_OK;
 }
 
 // The operator from three weight views in one pass; the device's verdict on the weights is read back once.  The old
@@ -3318,6 +3427,7 @@ int set_weights(ccp_grid *g, const WeightView &wx, const WeightView &wy, const W
     const long n = geo.ch_stride;
     drop_operator(g);
     g->wcons.release();
+    CCP_TRY(operator_planes(g, 1));
     unsigned bad = 0;
     CCP_HIP(hipMemsetAsync(g->io_bad.p, 0, sizeof(unsigned), g->stream));
     hipLaunchKernelGGL(k_weighted_coef, dim3((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)geo.H), dim3(kBlock), 0, g->stream, wx, wy,
@@ -3339,6 +3449,7 @@ int set_weights_fixed(ccp_grid *g, const WeightView &wx, const WeightView &wy, c
     const Geom &geo = g->geom;
     const long n = geo.ch_stride;
     drop_operator(g);
+    CCP_TRY(operator_planes(g, 1));
     CCP_TRY(g->wcons.alloc(3 * (size_t)n));
     CCP_HIP(hipMemsetAsync(g->wcons.p, 0, 3 * sizeof(double) * (size_t)n, g->stream));   // the pads
     CCP_HIP(hipMemsetAsync(g->wcount.p, 0, 4 * sizeof(unsigned long long), g->stream));
@@ -3424,20 +3535,51 @@ int ccp_grid_constraint_info(ccp_grid *g, int64_t *fixed_pixels, int64_t *free_l
 try {
     CCP_TRY(weighted_handle(g));
     if (!g->has_op) return CCP_ERR_STATE;
-    if (g->w_live < 0) {                                   // an operator of ccp_grid_set_weights_*: its dead pixels counted once
-        const Geom &geo = g->geom;
-        unsigned long long dead = 0;
-        CCP_HIP(hipMemsetAsync(g->wcount.p, 0, sizeof(unsigned long long), g->stream));
-        hipLaunchKernelGGL(k_weighted_count_dead, pixel_grid(g, geo.H), dim3(kBlock), 0, g->stream, g->wop.p, geo.W, geo.H, geo.pitch,
-                           g->wcount.p);
-        CCP_HIP(hipGetLastError());
-        CCP_HIP(hipMemcpyAsync(&dead, g->wcount.p, sizeof(dead), hipMemcpyDeviceToHost, g->stream));
-        CCP_HIP(hipStreamSynchronize(g->stream));
-        g->w_live = (long)geo.W * geo.H - (long)dead;
-    }
+    if (g->w_live < 0) CCP_TRY(count_live(g, g->wop.p, &g->w_live));   // an operator of ccp_grid_set_weights_*: its dead pixels counted once
+    if (g->per_channel) g->pc_live[0] = g->w_live;
     if (fixed_pixels) *fixed_pixels = g->w_fixed;
     if (free_live_pixels) *free_live_pixels = g->w_live;
     if (boundary_edges) *boundary_edges = g->w_edges;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_constraint_info_channel(ccp_grid *g, int32_t channel, int64_t *fixed_pixels, int64_t *free_live_pixels, int64_t *boundary_edges)
+try {
+    CCP_TRY(weighted_handle(g));
+    if (channel < 0 || channel >= g->desc.channels) return CCP_ERR_BAD_ARG;
+    if (!g->has_op) return CCP_ERR_STATE;
+    if (!g->per_channel || channel == 0) return ccp_grid_constraint_info(g, fixed_pixels, free_live_pixels, boundary_edges);
+    if (g->pc_live[channel] < 0) CCP_TRY(count_live(g, g->wop.p + 4 * (long)channel * g->geom.ch_stride, &g->pc_live[channel]));
+    if (fixed_pixels) *fixed_pixels = g->pc_fixed[channel];
+    if (free_live_pixels) *free_live_pixels = g->pc_live[channel];
+    if (boundary_edges) *boundary_edges = g->pc_edges[channel];
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_set_weights_per_channel_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
+                                            const ccp_device_array *fixed)
+try {
+    CCP_TRY(weighted_handle(g));
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    const ccp_device_array *src[3] = {wx, wy, lambda};
+    const double dflt[3] = {1.0, 1.0, 0.0};
+    PcoView v[3];
+    for (int i = 0; i < 3; ++i) {
+        if (src[i]) CCP_TRY(check_view(g, src[i], kF32F64, false, 1, H, W, C));
+        v[i] = pco_view(src[i], dflt[i]);
+    }
+    if (!fixed) return set_weights_per_channel(g, v[0], v[1], v[2], nullptr);
+    CCP_TRY(check_view(g, fixed, kF32F64 | kU8, false, 1, H, W, C));
+    const PcoView m = pco_view(fixed, 0.0);
+    return set_weights_per_channel(g, v[0], v[1], v[2], &m);
+} CCP_ABI_CATCH
+
+int ccp_grid_operator_channels(ccp_grid *g, int32_t *n)
+try {
+    CCP_TRY(weighted_handle(g));
+    if (!n) return CCP_ERR_BAD_ARG;
+    if (!g->has_op) return CCP_ERR_STATE;
+    *n = g->per_channel ? g->desc.channels : 1;
     return CCP_OK;
 } CCP_ABI_CATCH
 
@@ -3460,6 +3602,15 @@ AdjOut adj_out(const ccp_device_array *a)
     return AdjOut{const_cast<void *>(a->data), (long)a->stride_y, (long)a->stride_x, (long)a->stride_c, a->dtype};
 }
 
+// channel c of a view as a one-channel view (one operator per channel: a launch per channel, each the launch of a
+// one-channel handle on the channel's slices)
+template <typename A>
+A adj_channel(A a, int c)
+{
+    if (a.p) a.p = (decltype(a.p))((const char *)a.p + (long)c * a.sc * (long)dtype_bytes(a.dtype));
+    return a;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3470,6 +3621,15 @@ try {
     const Geom &geo = g->geom;
     CCP_TRY(check_view(g, grad_x, kF32F64, false, 1, geo.H, geo.W, g->desc.channels));
     if (!g->has_op) return CCP_ERR_STATE;
+    if (g->per_channel) {                                                    // channel c's free / live set: its own d
+        const long n = geo.ch_stride;
+        for (int c = 0; c < g->desc.channels; ++c) {
+            hipLaunchKernelGGL(k_adjoint_begin, pixel_grid(g, geo.H), dim3(kBlock), 0, g->stream, g->b.p + c * n, g->x.p + c * n,
+                               g->wop.p + 4 * c * n, geo.pitch, n, geo.W, 1, adj_channel(adj_in(grad_x), c));
+            CCP_HIP(hipGetLastError());
+        }
+        return edge_timeout_status(g);
+    }
     hipLaunchKernelGGL(k_adjoint_begin, pixel_grid(g, geo.H), dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->wop.p, geo.pitch, geo.ch_stride,
                        geo.W, g->desc.channels, adj_in(grad_x));
     CCP_HIP(hipGetLastError());
@@ -3487,14 +3647,15 @@ try {
     if (in->gx) CCP_TRY(check_view(g, in->gx, kF32, false, 1, H, W, C));
     if (in->gy) CCP_TRY(check_view(g, in->gy, kF32, false, 1, H, W, C));
     if (in->f) CCP_TRY(check_view(g, in->f, kF32F64 | kU8, false, 1, H, W, C));
-    if (in->wx) CCP_TRY(check_view(g, in->wx, kF32F64, false, 1, H, W, 1));
-    if (in->wy) CCP_TRY(check_view(g, in->wy, kF32F64, false, 1, H, W, 1));
-    if (in->lambda) CCP_TRY(check_view(g, in->lambda, kF32F64, false, 1, H, W, 1));
-    if (in->fixed) CCP_TRY(check_view(g, in->fixed, kF32F64 | kU8, false, 1, H, W, 1));
+    const int PC = g->has_op && g->per_channel ? C : 1;                      // the extent of the weight views along c
+    if (in->wx) CCP_TRY(check_view(g, in->wx, kF32F64, false, 1, H, W, PC));
+    if (in->wy) CCP_TRY(check_view(g, in->wy, kF32F64, false, 1, H, W, PC));
+    if (in->lambda) CCP_TRY(check_view(g, in->lambda, kF32F64, false, 1, H, W, PC));
+    if (in->fixed) CCP_TRY(check_view(g, in->fixed, kF32F64 | kU8, false, 1, H, W, PC));
     const ccp_device_array *planes[3] = {out->g_wx, out->g_wy, out->g_lambda};
     const ccp_device_array *images[4] = {out->g_gx, out->g_gy, out->g_f, out->g_values};
     for (const ccp_device_array *a : planes)
-        if (a) CCP_TRY(check_view(g, a, kF32F64, true, 1, H, W, 1));
+        if (a) CCP_TRY(check_view(g, a, kF32F64, true, 1, H, W, PC));
     for (const ccp_device_array *a : images)
         if (a) CCP_TRY(check_view(g, a, kF32F64, true, 1, H, W, C));
     if (!g->has_op) return CCP_ERR_STATE;
@@ -3514,15 +3675,43 @@ try {
     a.wy = adj_in(in->wy);
     a.lam = adj_in(in->lambda);
     a.fixed = adj_in(in->fixed);
-    a.wx.sc = a.wy.sc = a.lam.sc = a.fixed.sc = 0;         // H x W: stride_c unused
     a.g_wx = adj_out(out->g_wx);
     a.g_wy = adj_out(out->g_wy);
     a.g_lam = adj_out(out->g_lambda);
-    a.g_wx.sc = a.g_wy.sc = a.g_lam.sc = 0;
     a.g_gx = adj_out(out->g_gx);
     a.g_gy = adj_out(out->g_gy);
     a.g_f = adj_out(out->g_f);
     a.g_val = adj_out(out->g_values);
+    if (g->per_channel) {
+        // H x W x C weights and weight gradients (their stride_c is used), no sum over channels: one launch per channel,
+        // each the launch of a one-channel handle on channel c's slice of every view
+        for (int c = 0; c < C; ++c) {
+            AdjointArgs k = a;
+            k.C = 1;
+            k.v = a.v + (long)c * geo.ch_stride;
+            k.u = adj_channel(a.u, c);
+            k.grad = adj_channel(a.grad, c);
+            k.gx = adj_channel(a.gx, c);
+            k.gy = adj_channel(a.gy, c);
+            k.f = adj_channel(a.f, c);
+            k.wx = adj_channel(a.wx, c);
+            k.wy = adj_channel(a.wy, c);
+            k.lam = adj_channel(a.lam, c);
+            k.fixed = adj_channel(a.fixed, c);
+            k.g_wx = adj_channel(a.g_wx, c);
+            k.g_wy = adj_channel(a.g_wy, c);
+            k.g_lam = adj_channel(a.g_lam, c);
+            k.g_gx = adj_channel(a.g_gx, c);
+            k.g_gy = adj_channel(a.g_gy, c);
+            k.g_f = adj_channel(a.g_f, c);
+            k.g_val = adj_channel(a.g_val, c);
+            hipLaunchKernelGGL(k_weighted_adjoint, pixel_grid(g, H), dim3(kBlock), 0, g->stream, k);
+            CCP_HIP(hipGetLastError());
+        }
+        return edge_timeout_status(g);
+    }
+    a.wx.sc = a.wy.sc = a.lam.sc = a.fixed.sc = 0;         // H x W: stride_c unused
+    a.g_wx.sc = a.g_wy.sc = a.g_lam.sc = 0;
     hipLaunchKernelGGL(k_weighted_adjoint, pixel_grid(g, H), dim3(kBlock), 0, g->stream, a);
     CCP_HIP(hipGetLastError());
     return edge_timeout_status(g);

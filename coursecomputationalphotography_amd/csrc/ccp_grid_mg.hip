@@ -4,6 +4,7 @@
 #include "ccp_grid_mgs.hpp"
 #include "ccp_grid_mgb.hpp"
 #include "ccp_grid_mgl.hpp"
+#include "ccp_grid_pco_api.hpp"
 #include "ccp_comm.hpp"
 
 #include <algorithm>
@@ -78,7 +79,8 @@ struct MgHierarchy {
     std::vector<long> fbase;
     DevBuf<float> fstore, w32, t0f;
     DevBuf<unsigned> fbad;
-    float *farr(int k, int which) { return fstore.p + fbase[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t
+    // one operator (opC == 1) only: 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t.  Code that may see opC > 1 asks fcoef() / fvec().
+    float *farr(int k, int which) { return fstore.p + fbase[k] + (long)which * size[k]; }
     int lam_slot = 6;                // F32: 3 (the fp64 store then holds d, we, ws and lambda only)
     // CCP_MG_CHANNELS_BATCHED (ccp_grid_mgb.hpp): C of every vector, made at the first batched V-cycle (bt0: level 0's t;
     // bstore: per coarse level b, z, t, each C x `size`) and at the first batched solve (the work set `bat`).  The levels'
@@ -94,7 +96,35 @@ struct MgHierarchy {
     int smoother = CCP_MG_SMOOTHER_POINT;
     long lplane = 0;
     DevBuf<double> lwork;
-    double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }   // 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda (lam_slot)
+    // one operator (opC == 1) only: 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda (lam_slot).  The one-block code, which may see
+    // opC > 1, asks coef() for a coefficient plane and vec() for a vector; the row-block code (never weighted) uses arr().
+    double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }
+    // One operator per channel (a weighted handle after ccp_grid_set_weights_per_channel_device, ccp_grid_pco.hpp): opC
+    // copies of the coefficient part of every level.  The coarse levels' d, we, ws, lambda of all channels live in cstore
+    // (level k, channel ch: at cbase[k] + 4 ch size[k], each `size[k]`), the float copies of d, we, ws in cfstore (3 per
+    // channel) and w32 (level 0, 3 n0 per channel); store and fstore then hold the vectors b, z, t alone (vec, fvec).
+    // clv / cflv: every channel's level descriptors -- the same structs with the channel's pointers; the sequential
+    // V-cycle and PCG are handed the channel and read levels_of(ch) / flevels_of(ch), nothing else.
+    int opC = 1;
+    long os0 = 0;                    // level 0's per-channel stride of d, we, ws (the handle's)
+    DevBuf<MgTail> ctails;           // batched mode: every channel's tail descriptor (k_pco_tail), made with batched_levels
+    std::vector<long> cbase;
+    DevBuf<double> cstore;
+    DevBuf<float> cfstore;
+    std::vector<std::vector<MgLevel>> clv;
+    std::vector<std::vector<MgsLevel>> cflv;
+    // which: 0 d, 1 we, 2 ws, 3 lambda
+    double *coef(int ch, int k, int which)
+    {
+        if (opC == 1) return arr(k, which == 3 ? lam_slot : which);
+        return cstore.p + cbase[k] + (4L * ch + which) * size[k];
+    }
+    float *fcoef(int ch, int k, int which) { return opC == 1 ? farr(k, which) : cfstore.p + 3 * cbase[k] / 4 + (3L * ch + which) * size[k]; }
+    // which: 0 b, 1 z, 2 t of coarse level k (one set: the sequential V-cycle's)
+    double *vec(int k, int which) { return store.p + base[k] + (long)(opC == 1 ? 3 + which : which) * size[k]; }
+    float *fvec(int k, int which) { return fstore.p + fbase[k] + (long)(opC == 1 ? 3 + which : which) * size[k]; }
+    const std::vector<MgLevel> &levels_of(int ch) const { return opC == 1 ? lv : clv[(size_t)ch]; }
+    const std::vector<MgsLevel> &flevels_of(int ch) const { return opC == 1 ? flv : cflv[(size_t)ch]; }
     ~MgHierarchy()
     {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -147,7 +177,10 @@ int build(const GridMgView &v, MgHierarchy **out)
     // narrowing reads
     const bool f32 = v.precision == CCP_MG_PRECISION_F32;
     h->lam_slot = f32 ? 3 : 6;
-    const int per_level = (f32 ? 3 : 6) + (v.weighted ? 1 : 0);
+    const int OC = v.weighted ? v.op_channels : 1;                  // operators: > 1 keeps the coefficients in cstore
+    h->opC = OC;
+    h->os0 = v.op_stride;
+    const int per_level = OC > 1 ? (f32 ? 0 : 3) : (f32 ? 3 : 6) + (v.weighted ? 1 : 0);
     MgLevel l0{};
     l0.W = v.geom.W;
     l0.H = v.geom.H;
@@ -163,7 +196,8 @@ int build(const GridMgView &v, MgHierarchy **out)
     h->lv.push_back(l0);
     h->base.push_back(0);
     h->size.push_back(0);
-    long total = 0;
+    h->cbase.push_back(0);
+    long total = 0, ctotal = 0;
     while (h->lv.back().W > 1 || h->lv.back().H > 1) {
         MgLevel c{};
         c.W = (h->lv.back().W + 1) / 2;
@@ -174,6 +208,8 @@ int build(const GridMgView &v, MgHierarchy **out)
         h->base.push_back(total);
         h->size.push_back((long)c.H * 2 * c.pitch);
         total += per_level * h->size.back();
+        h->cbase.push_back(ctotal);
+        ctotal += 4L * OC * h->size.back();
     }
     h->levels = (int)h->lv.size();
     h->tail = h->levels;
@@ -183,6 +219,10 @@ int build(const GridMgView &v, MgHierarchy **out)
             break;
         }
     if (h->levels - h->tail > kMgTailLevels) return CCP_ERR_STATE;     // (cannot happen: sides <= 32 leave <= 6 levels)
+    if (OC > 1 && ctotal > 0) {
+        CCP_TRY(h->cstore.alloc((size_t)ctotal));
+        CCP_HIP(hipMemsetAsync(h->cstore.p, 0, sizeof(double) * ctotal, v.stream));
+    }
     if (!f32) {                                                     // (the fp32 V-cycle keeps its own, in float: narrow_levels)
         CCP_TRY(h->t0.alloc((size_t)v.geom.ch_stride));
         CCP_HIP(hipMemsetAsync(h->t0.p, 0, sizeof(double) * v.geom.ch_stride, v.stream));
@@ -192,12 +232,30 @@ int build(const GridMgView &v, MgHierarchy **out)
         CCP_HIP(hipMemsetAsync(h->store.p, 0, sizeof(double) * total, v.stream));
     }
     for (int k = 1; k < h->levels; ++k) {
-        h->lv[k].d = h->arr(k, 0);
-        h->lv[k].we = h->arr(k, 1);
-        h->lv[k].ws = h->arr(k, 2);
+        h->lv[k].d = h->coef(0, k, 0);
+        h->lv[k].we = h->coef(0, k, 1);
+        h->lv[k].ws = h->coef(0, k, 2);
+    }
+    if (OC > 1) {                                                   // every channel's descriptors: lv with the channel's planes
+        for (int ch = 0; ch < OC; ++ch) {
+            h->clv.push_back(h->lv);
+            std::vector<MgLevel> &l = h->clv.back();
+            l[0].d = v.wd + ch * v.op_stride;
+            l[0].we = v.wwe + ch * v.op_stride;
+            l[0].ws = v.wws + ch * v.op_stride;
+            for (int k = 1; k < h->levels; ++k) {
+                l[k].d = h->coef(ch, k, 0);
+                l[k].we = h->coef(ch, k, 1);
+                l[k].ws = h->coef(ch, k, 2);
+            }
+        }
     }
     for (int k = 0; k + 1 < h->levels; ++k) {
-        if (v.weighted)
+        if (OC > 1)                                                 // all channels' level k + 1 in one launch
+            CCP_TRY(pco_coarsen(v.stream, OC, h->lv[k], k ? 4 * h->size[k] : v.op_stride, k ? static_cast<const double *>(h->coef(0, k, 3)) : v.wlam,
+                                k ? 4 * h->size[k] : v.lam_stride, h->lv[k + 1], h->coef(0, k + 1, 0), h->coef(0, k + 1, 1), h->coef(0, k + 1, 2),
+                                h->coef(0, k + 1, 3), 4 * h->size[k + 1], rescaled ? 0.5 : 1.0));
+        else if (v.weighted)
             hipLaunchKernelGGL(k_mg_coarsen_weighted, cells_grid(h->lv[k + 1].W, h->lv[k + 1].H), dim3(kBlock), 0, v.stream, h->lv[k],
                                k ? static_cast<const double *>(h->arr(k, h->lam_slot)) : v.wlam, h->lv[k + 1], h->arr(k + 1, 0), h->arr(k + 1, 1),
                                h->arr(k + 1, 2), h->arr(k + 1, h->lam_slot), rescaled ? 0.5 : 1.0);
@@ -212,7 +270,8 @@ int build(const GridMgView &v, MgHierarchy **out)
 
 int hierarchy(const GridMgView &v, MgHierarchy **out)
 {
-    if (*v.cache && ((*v.cache)->rowblocked || (*v.cache)->weighted != v.weighted || (*v.cache)->precision != v.precision)) {   // built for the row-block calls: this call needs its own
+    if (*v.cache && ((*v.cache)->rowblocked || (*v.cache)->weighted != v.weighted || (*v.cache)->precision != v.precision ||
+                     (*v.cache)->opC != (v.weighted ? v.op_channels : 1))) {   // built for the row-block calls: this call needs its own
         mg_release(*v.cache);
         *v.cache = nullptr;
     }
@@ -350,22 +409,24 @@ Tail tail_of(const std::vector<Level> &lv, int first)
 
 // The levels from `from` (held whole) down: tiles above the tail, then k_mg_tail, then back up to `from`.  Every launch
 // is a no-op once st->active is 0 (st may be null).
-int whole_levels(MgHierarchy &h, hipStream_t s, int from, const double *b0, double *z0, int nu, const CgState *st)
+// ch: whose operator (one operator per channel; 0 otherwise).
+int whole_levels(MgHierarchy &h, hipStream_t s, int from, const double *b0, double *z0, int nu, const CgState *st, int ch = 0)
 {
-    auto B = [&](int k) -> const double * { return k ? h.arr(k, 3) : b0; };
-    auto Z = [&](int k) -> double * { return k ? h.arr(k, 4) : z0; };
-    auto T = [&](int k) -> double * { return k ? h.arr(k, 5) : h.t0.p; };
+    const std::vector<MgLevel> &lv = h.levels_of(ch);
+    auto B = [&](int k) -> const double * { return k ? h.vec(k, 0) : b0; };
+    auto Z = [&](int k) -> double * { return k ? h.vec(k, 1) : z0; };
+    auto T = [&](int k) -> double * { return k ? h.vec(k, 2) : h.t0.p; };
     const bool line = h.smoother == CCP_MG_SMOOTHER_LINE;
     for (int k = from; k < h.tail; ++k) {
-        if (line) pre_lines(h, s, h.lv[k], B(k), T(k), nu, st);
-        else pre(level_kind(h, k), s, tiles(h.lv[k]), h.lv[k], B(k), T(k), nu, st);
-        restrict_rows(level_kind(h, k), s, h.lv[k], B(k), T(k), h.lv[k + 1], 0, h.lv[k + 1].H, h.arr(k + 1, 3), st);
+        if (line) pre_lines(h, s, lv[k], B(k), T(k), nu, st);
+        else pre(level_kind(h, k), s, tiles(lv[k]), lv[k], B(k), T(k), nu, st);
+        restrict_rows(level_kind(h, k), s, lv[k], B(k), T(k), lv[k + 1], 0, lv[k + 1].H, h.vec(k + 1, 0), st);
     }
-    const MgTail t = tail_of<MgTail>(h.lv, h.tail);
+    const MgTail t = tail_of<MgTail>(lv, h.tail);
     hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(kBlock), 0, s, t, B(h.tail), Z(h.tail), h.cs, nu, st);
     for (int k = h.tail - 1; k >= from; --k) {
-        if (line) post_lines(h, s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], h.arr(k + 1, 4), h.cs, nu, st);
-        else post(level_kind(h, k), s, h.lv[k], B(k), T(k), Z(k), h.lv[k + 1], h.arr(k + 1, 4), h.cs, nu, st);
+        if (line) post_lines(h, s, lv[k], B(k), T(k), Z(k), lv[k + 1], h.vec(k + 1, 1), h.cs, nu, st);
+        else post(level_kind(h, k), s, lv[k], B(k), T(k), Z(k), lv[k + 1], h.vec(k + 1, 1), h.cs, nu, st);
     }
     CCP_HIP(hipGetLastError());
     return CCP_OK;
@@ -383,7 +444,7 @@ int narrow_levels(const GridMgView &v, MgHierarchy &h)
     h.fbase.assign((size_t)h.levels, 0);
     for (int k = 1; k < h.levels; ++k) {
         h.fbase[k] = total;
-        total += 6 * h.size[k];
+        total += (h.opC > 1 ? 3 : 6) * h.size[k];          // one operator per channel: the vectors alone (cfstore has d, we, ws)
     }
     CCP_TRY(h.fbad.alloc(1));
     CCP_HIP(hipMemsetAsync(h.fbad.p, 0, sizeof(unsigned), s));
@@ -396,27 +457,36 @@ int narrow_levels(const GridMgView &v, MgHierarchy &h)
     auto narrow = [&](const double *src, float *dst, long n) {
         hipLaunchKernelGGL(k_mgs_narrow, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, src, dst, n, h.fbad.p);
     };
-    h.flv.assign((size_t)h.levels, MgsLevel{});
-    for (int k = 0; k < h.levels; ++k) {
-        MgsLevel &f = h.flv[k];
-        f.W = h.lv[k].W;
-        f.H = h.lv[k].H;
-        f.pitch = h.lv[k].pitch;
-        f.mask = h.lv[k].mask;
-        f.g0 = h.lv[k].g0;
-        if (k) {
-            narrow(h.arr(k, 0), h.farr(k, 0), 3 * h.size[k]);        // d, we, ws lie one after the other in both stores
-            f.d = h.farr(k, 0);
-            f.we = h.farr(k, 1);
-            f.ws = h.farr(k, 2);
-        } else if (h.weighted) {                                    // the handle's d, we, ws planes, n0 doubles apart
-            CCP_TRY(h.w32.alloc((size_t)(3 * n0)));
-            narrow(h.lv[0].d, h.w32.p, 3 * n0);
-            f.d = h.w32.p;
-            f.we = h.w32.p + n0;
-            f.ws = h.w32.p + 2 * n0;
-        }
+    if (h.opC > 1) {
+        const long ftotal = 3 * h.cbase.back() / 4 + 3L * h.opC * h.size.back();
+        CCP_TRY(h.cfstore.alloc((size_t)ftotal));
+        CCP_HIP(hipMemsetAsync(h.cfstore.p, 0, sizeof(float) * ftotal, s));
+        h.cflv.assign((size_t)h.opC, std::vector<MgsLevel>((size_t)h.levels, MgsLevel{}));
     }
+    h.flv.assign((size_t)h.levels, MgsLevel{});
+    if (h.weighted) CCP_TRY(h.w32.alloc((size_t)(3 * n0 * h.opC)));
+    for (int ch = 0; ch < h.opC; ++ch)
+        for (int k = 0; k < h.levels; ++k) {
+            const MgLevel &l = h.opC > 1 ? h.clv[(size_t)ch][k] : h.lv[k];
+            MgsLevel &f = h.opC > 1 ? h.cflv[(size_t)ch][k] : h.flv[k];
+            f.W = l.W;
+            f.H = l.H;
+            f.pitch = l.pitch;
+            f.mask = l.mask;
+            f.g0 = l.g0;
+            if (k) {
+                narrow(h.coef(ch, k, 0), h.fcoef(ch, k, 0), 3 * h.size[k]);   // d, we, ws lie one after the other in both stores
+                f.d = h.fcoef(ch, k, 0);
+                f.we = h.fcoef(ch, k, 1);
+                f.ws = h.fcoef(ch, k, 2);
+            } else if (h.weighted) {                                // the handle's d, we, ws planes, n0 doubles apart
+                float *w = h.w32.p + 3 * n0 * ch;
+                narrow(l.d, w, 3 * n0);
+                f.d = w;
+                f.we = w + n0;
+                f.ws = w + 2 * n0;
+            }
+        }
     CCP_HIP(hipGetLastError());
     unsigned bad = 0;
     CCP_HIP(hipMemcpyAsync(&bad, h.fbad.p, sizeof(bad), hipMemcpyDeviceToHost, s));
@@ -443,53 +513,55 @@ void tile32_top(int kind, hipStream_t s, dim3 grid, const MgsLevel &f, const dou
 dim3 tiles32(const MgsLevel &f) { return dim3((unsigned)((f.W + kMgsTileW - 1) / kMgsTileW), (unsigned)((f.H + kMgsTileH - 1) / kMgsTileH)); }
 
 // vcycle in float: z0 := (double) M32^-1 (float) b0, the launch structure of vcycle in fp64
-int vcycle32(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st)
+int vcycle32(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st, int ch)
 {
+    const std::vector<MgsLevel> &flv = h.flevels_of(ch);
     const float *none = nullptr;
     const float cs = (float)h.cs;
-    const MgsLevel &l0 = h.flv[0];
+    const MgsLevel &l0 = flv[0];
     if (h.levels == 1) {
         tile32_top<false>(h.kind0, s, dim3(1), l0, b0, none, z0, l0, none, 2.0f, nu, st);
         CCP_HIP(hipGetLastError());
         return CCP_OK;
     }
-    auto T = [&](int k) -> float * { return k ? h.farr(k, 5) : h.t0f.p; };
+    auto T = [&](int k) -> float * { return k ? h.fvec(k, 2) : h.t0f.p; };
     for (int k = 0; k < h.tail; ++k) {
-        const MgsLevel &f = h.flv[k], &c = h.flv[k + 1];
+        const MgsLevel &f = flv[k], &c = flv[k + 1];
         const dim3 rgrid = cells_grid(c.W, c.H);
         if (k == 0) {
             tile32_top<false>(h.kind0, s, tiles32(f), f, b0, none, T(0), f, none, 2.0f, nu, st);
             with_kind(h.kind0, [&](auto K) {
-                hipLaunchKernelGGL((k_mgs_restrict<decltype(K)::value, double>), rgrid, dim3(kBlock), 0, s, f, b0, T(0), c, h.farr(1, 3), st);
+                hipLaunchKernelGGL((k_mgs_restrict<decltype(K)::value, double>), rgrid, dim3(kBlock), 0, s, f, b0, T(0), c, h.fvec(1, 0), st);
             });
         } else {
-            const float *b = h.farr(k, 3);
+            const float *b = h.fvec(k, 0);
             tile32<kMgCoarse, false>(s, tiles32(f), f, b, none, T(k), f, none, 2.0f, nu, st);
-            hipLaunchKernelGGL((k_mgs_restrict<kMgCoarse, float>), rgrid, dim3(kBlock), 0, s, f, b, T(k), c, h.farr(k + 1, 3), st);
+            hipLaunchKernelGGL((k_mgs_restrict<kMgCoarse, float>), rgrid, dim3(kBlock), 0, s, f, b, T(k), c, h.fvec(k + 1, 0), st);
         }
     }
-    const MgsTail t = tail_of<MgsTail>(h.flv, h.tail);
-    hipLaunchKernelGGL(k_mgs_tail, dim3(1), dim3(kBlock), 0, s, t, static_cast<const float *>(h.farr(h.tail, 3)), h.farr(h.tail, 4), cs, nu, st);
+    const MgsTail t = tail_of<MgsTail>(flv, h.tail);
+    hipLaunchKernelGGL(k_mgs_tail, dim3(1), dim3(kBlock), 0, s, t, static_cast<const float *>(h.fvec(h.tail, 0)), h.fvec(h.tail, 1), cs, nu, st);
     for (int k = h.tail - 1; k >= 0; --k) {
-        const MgsLevel &f = h.flv[k], &c = h.flv[k + 1];
-        const float *ec = h.farr(k + 1, 4);
+        const MgsLevel &f = flv[k], &c = flv[k + 1];
+        const float *ec = h.fvec(k + 1, 1);
         if (k == 0) tile32_top<true>(h.kind0, s, tiles32(f), f, b0, static_cast<const float *>(T(0)), z0, c, ec, cs, nu, st);
-        else tile32<kMgCoarse, true>(s, tiles32(f), f, static_cast<const float *>(h.farr(k, 3)), static_cast<const float *>(T(k)), h.farr(k, 4), c, ec, cs, nu, st);
+        else tile32<kMgCoarse, true>(s, tiles32(f), f, static_cast<const float *>(h.fvec(k, 0)), static_cast<const float *>(T(k)), h.fvec(k, 1), c, ec, cs, nu, st);
     }
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 }
 
-// z0 := M^-1 b0 on level 0 (one channel); every launch is a no-op once st->active is 0 (st may be null)
-int vcycle(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st)
+// z0 := M^-1 b0 on level 0 (one channel, with channel ch's operator where the handle has one per channel); every launch
+// is a no-op once st->active is 0 (st may be null)
+int vcycle(MgHierarchy &h, hipStream_t s, const double *b0, double *z0, int nu, const CgState *st, int ch = 0)
 {
-    if (h.precision == CCP_MG_PRECISION_F32) return vcycle32(h, s, b0, z0, nu, st);
+    if (h.precision == CCP_MG_PRECISION_F32) return vcycle32(h, s, b0, z0, nu, st, ch);
     if (h.levels == 1) {                                            // a 1x1 image
-        pre(h.kind0, s, dim3(1), h.lv[0], b0, z0, nu, st);
+        pre(h.kind0, s, dim3(1), h.levels_of(ch)[0], b0, z0, nu, st);
         CCP_HIP(hipGetLastError());
         return CCP_OK;
     }
-    return whole_levels(h, s, 0, b0, z0, nu, st);
+    return whole_levels(h, s, 0, b0, z0, nu, st, ch);
 }
 
 // ---- CCP_MG_CHANNELS_BATCHED (ccp_grid_mgb.hpp) ----------------------------------------------------------------------
@@ -525,6 +597,14 @@ int batched_levels(const GridMgView &v, MgHierarchy &h)
     const int C = v.channels;
     const long n0 = v.geom.ch_stride;
     CCP_TRY(tile_lds_limit());
+    if (h.opC > 1) {                                                // one operator per channel: k_pco_* (ccp_grid_pco.hpp)
+        CCP_TRY(pco_tile_lds_limit());
+        std::vector<MgTail> tails;
+        for (int ch = 0; ch < h.opC; ++ch) tails.push_back(tail_of<MgTail>(h.clv[(size_t)ch], h.tail));
+        CCP_TRY(h.ctails.alloc(tails.size()));
+        CCP_HIP(hipMemcpyAsync(h.ctails.p, tails.data(), sizeof(MgTail) * tails.size(), hipMemcpyHostToDevice, v.stream));
+        CCP_HIP(hipStreamSynchronize(v.stream));                    // (tails goes out of scope)
+    }
     long total = 0;
     h.bbase.assign((size_t)h.levels, 0);
     for (int k = 1; k < h.levels; ++k) {
@@ -545,6 +625,7 @@ void batched_release(MgHierarchy &h)
 {
     h.bt0.release();
     h.bstore.release();
+    h.ctails.release();
     h.bat.release();
     h.bC = 0;
 }
@@ -564,6 +645,23 @@ void tile_b(int kind, hipStream_t s, dim3 grid, const MgLevel &f, const double *
 int vcycle_batched(MgHierarchy &h, hipStream_t s, int C, long n0, const double *b0, double *z0, int nu, const CgState *st)
 {
     const double *none = nullptr;
+    if (h.opC > 1) {                                                 // one operator per channel: the same launches, the channel on grid z
+        const std::vector<MgLevel> &lv = h.clv[0];                   // channel 0's descriptors; channel ch's coefficients OS(k) ch further
+        auto OS = [&](int k) -> long { return k ? 4 * h.size[k] : h.os0; };
+        auto S = [&](int k) -> long { return k ? h.size[k] : n0; };
+        auto B = [&](int k) -> const double * { return k ? h.barr(k, 0) : b0; };
+        auto Z = [&](int k) -> double * { return k ? h.barr(k, 1) : z0; };
+        auto T = [&](int k) -> double * { return k ? h.barr(k, 2) : h.bt0.p; };
+        if (h.levels == 1) return pco_tile(s, false, dim3(1), C, lv[0], OS(0), b0, none, z0, n0, lv[0], none, 0, 2.0, nu, st);
+        for (int k = 0; k < h.tail; ++k) {
+            CCP_TRY(pco_tile(s, false, tiles(lv[k]), C, lv[k], OS(k), B(k), none, T(k), S(k), lv[k], none, 0, 2.0, nu, st));
+            CCP_TRY(pco_restrict(s, C, lv[k], OS(k), B(k), T(k), S(k), lv[k + 1], h.barr(k + 1, 0), S(k + 1), st));
+        }
+        CCP_TRY(pco_tail(s, C, h.ctails.p, B(h.tail), Z(h.tail), S(h.tail), S(h.tail), h.cs, nu, st));
+        for (int k = h.tail - 1; k >= 0; --k)
+            CCP_TRY(pco_tile(s, true, tiles(lv[k]), C, lv[k], OS(k), B(k), T(k), Z(k), S(k), lv[k + 1], h.barr(k + 1, 1), S(k + 1), h.cs, nu, st));
+        return CCP_OK;
+    }
     if (h.levels == 1) {
         tile_b<false>(h.kind0, s, dim3(1), h.lv[0], b0, none, z0, n0, h.lv[0], none, 0, 2.0, nu, C, st);
         CCP_HIP(hipGetLastError());
@@ -697,19 +795,20 @@ struct PcgArgs {
 
 // One channel of a one-block handle: k_cg_* / k_mg_*.  The caller sets b and x per channel.
 struct ChannelSteps : PcgArgs {
+    int ch = 0;                      // whose operator (one operator per channel; 0 otherwise)
     int apply(const double *in, double *out, bool dot) const              // the product of an iteration stops with the loop
     {
         const CgState *a = dot ? st : nullptr;
         with_kind(h->kind0, [&](auto K) {
             with_bool(dot, [&](auto D) {
-                hipLaunchKernelGGL((k_mg_apply<decltype(K)::value, decltype(D)::value>), agrid, dim3(kBlock), 0, s, h->lv[0], in, out, part, a);
+                hipLaunchKernelGGL((k_mg_apply<decltype(K)::value, decltype(D)::value>), agrid, dim3(kBlock), 0, s, h->levels_of(ch)[0], in, out, part, a);
             });
         });
         return CCP_OK;
     }
     int residual() const { return apply(x, r, false); }
     int product() const { return apply(p, ap, true); }
-    int precondition() const { return vcycle(*h, s, r, z, nu, st); }
+    int precondition() const { return vcycle(*h, s, r, z, nu, st, ch); }
     void init() const { hipLaunchKernelGGL(k_cg_init, dim3(blocks), dim3(kBlock), 0, s, b, r, p, n, part); }
     void dot() const { hipLaunchKernelGGL(k_cg_dot, dim3(blocks), dim3(kBlock), 0, s, r, z, n, part, st); }
     void update() const { hipLaunchKernelGGL(k_cg_update, dim3(blocks), dim3(kBlock), 0, s, x, p, r, ap, n, part, st); }
@@ -732,6 +831,7 @@ struct BatchedSteps : PcgArgs {
     int apply(const double *in, double *out, bool dot) const
     {
         const CgState *a = dot ? st : nullptr;
+        if (h->opC > 1) return pco_apply(s, dot, agrid, C, h->clv[0][0], h->os0, in, out, n, part, ps, a);
         with_kind(h->kind0, [&](auto K) {
             with_bool(dot, [&](auto D) {
                 hipLaunchKernelGGL((k_mgb_apply<decltype(K)::value, decltype(D)::value>), agrid, dim3(kBlock), 0, s, h->lv[0], in, out, n, part, ps, C, a);
@@ -1062,7 +1162,7 @@ try {
         CCP_HIP(hipStreamSynchronize(v.stream));
         return CCP_OK;
     }
-    for (int ch = 0; ch < v.channels; ++ch) CCP_TRY(vcycle(*h, v.stream, v.b + ch * n, v.x + ch * n, nu, nullptr));
+    for (int ch = 0; ch < v.channels; ++ch) CCP_TRY(vcycle(*h, v.stream, v.b + ch * n, v.x + ch * n, nu, nullptr, ch));
     CCP_HIP(hipStreamSynchronize(v.stream));
     return CCP_OK;
 } CCP_ABI_CATCH
@@ -1181,13 +1281,21 @@ try {
 int ccp_grid_mg_level(ccp_grid *g, int32_t level, int32_t *n_levels, int32_t *width, int32_t *height, double *diag,
                       double *w_east, double *w_south)
 try {
+    return ccp_grid_mg_level_channel(g, 0, level, n_levels, width, height, diag, w_east, w_south);
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_level_channel(ccp_grid *g, int32_t channel, int32_t level, int32_t *n_levels, int32_t *width, int32_t *height, double *diag,
+                              double *w_east, double *w_south)
+try {
     GridMgView v{};
     CCP_TRY(check_handle(g, &v));
+    if (channel < 0 || channel >= v.channels) return CCP_ERR_BAD_ARG;
     MgHierarchy *h = nullptr;
     CCP_TRY(hierarchy(v, &h));
     if (n_levels) *n_levels = h->levels;
     if (level < 0 || level >= h->levels) return CCP_ERR_BAD_ARG;
-    const MgLevel &l = h->lv[level];
+    const int oc = h->opC > 1 ? channel : 0;                       // the shared operator is every channel's
+    const MgLevel &l = h->levels_of(oc)[level];
     if (width) *width = l.W;
     if (height) *height = l.H;
     if (!diag && !w_east && !w_south) return CCP_OK;
@@ -1208,7 +1316,7 @@ try {
         CCP_HIP(hipGetLastError());
         for (int i = 0; i < 3; ++i) src[i] = tmp.p + i * n;
     } else {
-        for (int i = 0; i < 3; ++i) src[i] = h->arr(level, i);
+        for (int i = 0; i < 3; ++i) src[i] = h->coef(oc, level, i);
     }
     double *dst[3] = {diag, w_east, w_south};
     std::vector<double> host((size_t)n);
@@ -1247,6 +1355,7 @@ try {
     for (int ch = 0; ch < v.channels; ++ch) {
         S.b = v.b + ch * n;
         S.x = v.x + ch * n;
+        S.ch = ch;                                                  // (one operator per channel: the channel's levels)
         CgState host;
         CCP_TRY(pcg_loop(S, *h, &host, 1, max_iteration, report ? report + ch : nullptr));
     }

@@ -257,12 +257,11 @@ k_mg_coarsen(MgLevel lv, MgLevel cv, int Y0, double *__restrict__ d, double *__r
 // coarse diagonal is never a difference.  `edge` (uniform) scales the four side sums: 1.0 for the Galerkin hierarchy,
 // 0.5 for the rescaled one (CCP_MG_HIERARCHY_RESCALED), whose correction is then added unscaled; both products are
 // exact, and lambda_c takes no factor.  grid = (ceil(Wc/kBlock), Hc).
-static __global__ void __launch_bounds__(kBlock)
-k_mg_coarsen_weighted(MgLevel lv, const double *__restrict__ lam, MgLevel cv, double *__restrict__ d, double *__restrict__ we,
-                      double *__restrict__ ws, double *__restrict__ lam_c, double edge)
+// The cell is written once (mg_coarsen_weighted_cell) for this kernel and the per-channel one (ccp_grid_pco.hpp).
+__device__ __forceinline__ void mg_coarsen_weighted_cell(const MgLevel &lv, const double *__restrict__ lam, const MgLevel &cv, int X, int Y,
+                                                         double *__restrict__ d, double *__restrict__ we, double *__restrict__ ws,
+                                                         double *__restrict__ lam_c, double edge)
 {
-    const int X = blockIdx.x * kBlock + threadIdx.x, Y = blockIdx.y;
-    if (X >= cv.W) return;
     const int x = 2 * X, y = 2 * Y;
     const double lc = (mg_ld(lam, lv, x, y) + mg_ld(lam, lv, x + 1, y)) + (mg_ld(lam, lv, x, y + 1) + mg_ld(lam, lv, x + 1, y + 1));
     const double n = edge * (mg_ld(lv.ws, lv, x, y - 1) + mg_ld(lv.ws, lv, x + 1, y - 1));
@@ -279,6 +278,15 @@ k_mg_coarsen_weighted(MgLevel lv, const double *__restrict__ lam, MgLevel cv, do
     we[at] = e;
     ws[at] = s;
     lam_c[at] = lc;
+}
+
+static __global__ void __launch_bounds__(kBlock)
+k_mg_coarsen_weighted(MgLevel lv, const double *__restrict__ lam, MgLevel cv, double *__restrict__ d, double *__restrict__ we,
+                      double *__restrict__ ws, double *__restrict__ lam_c, double edge)
+{
+    const int X = blockIdx.x * kBlock + threadIdx.x, Y = blockIdx.y;
+    if (X >= cv.W) return;
+    mg_coarsen_weighted_cell(lv, lam, cv, X, Y, d, we, ws, lam_c, edge);
 }
 
 // level 0's coefficients in the level layout (ccp_grid_mg_level only).  grid = (ceil(W/kBlock), H).

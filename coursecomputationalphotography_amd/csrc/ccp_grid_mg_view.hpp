@@ -20,6 +20,10 @@ struct GridMgView {
     // null while it has no operator
     bool weighted;
     const double *wd, *wwe, *wws, *wlam;
+    // one operator per channel (ccp_grid_set_weights_per_channel_device): op_channels == channels sets of those planes,
+    // channel ch's d, we, ws at + ch * op_stride and its lambda at + ch * lam_stride; the shared operator: op_channels 1
+    int op_channels;
+    long op_stride, lam_stride;
     int hierarchy_kind;              // CCP_MG_HIERARCHY_* (ccp_grid_mg_set_hierarchy; GALERKIN unless the handle is weighted)
     int precision;                   // CCP_MG_PRECISION_* (ccp_grid_mg_set_precision)
     int channels_mode;               // CCP_MG_CHANNELS_* (ccp_grid_mg_set_channels)

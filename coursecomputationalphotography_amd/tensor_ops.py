@@ -172,6 +172,20 @@ def _weight(w, H, W, dev):
     return torch.tensor(float(w), dtype=torch.float64, device=torch.device("cuda", dev)).expand(H, W)
 
 
+def _per_channel(*tensors):
+    """Does any of the operator's arguments carry a channel axis (H x W x C)?  Then the handle gets one operator per
+    channel (capi.Grid.set_weights_per_channel_tensor); otherwise exactly the shared operator's path."""
+    import torch
+    return any(isinstance(t, torch.Tensor) and t.dim() == 3 for t in tensors)
+
+
+def _set_operator(g, wx, wy, lam, fixed=None):
+    if _per_channel(wx, wy, lam, fixed):
+        g.set_weights_per_channel_tensor(wx, wy, lam, fixed)
+    else:
+        g.set_weights_tensor(wx, wy, lam, fixed=fixed)
+
+
 def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=None, out_dtype=None, epsilon: float = 1e-10,
                    hierarchy="galerkin", precision="f64", channels="sequential", smoother="point"):
     """Minimise  sum wx (u(x+1,y) - u(x,y) - gx)^2 + sum wy (u(x,y+1) - u(x,y) - gy)^2 + sum data_weight (u - f)^2
@@ -185,7 +199,12 @@ def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=Non
     epsilon; choose it together with "rescaled", the Galerkin hierarchy pays iterations for it).  channels: "sequential" (the
     default) or "batched" (capi.Grid.mg_set_channels: one PCG loop whose launches serve all channels; every channel gets
     the same bits; not together with "f32").  smoother: "point" (the default) or "line" (capi.Grid.mg_set_smoother:
-    alternating zebra line relaxation, for strongly anisotropic weights; fp64 and sequential channels only)."""
+    alternating zebra line relaxation, for strongly anisotropic weights; fp64 and sequential channels only).
+
+    One operator per channel.  If any of wx, wy, data_weight is H x W x C, channel c is solved with channel c's weights
+    (H x W arguments beside it serve every channel), and equals, bit for bit, the one-channel call on channel c's slices.
+    A mini-batch of N single-channel images with their own weights is H x W x N with channels="batched": one PCG loop
+    whose launches serve the whole batch, every image stopping at its own iteration."""
     import torch
     out_dtype = torch.uint8 if out_dtype is None else out_dtype
     ref = next((t for t in (f, gx, gy) if t is not None), None)
@@ -201,7 +220,7 @@ def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=Non
         g.mg_set_precision(precision)
         g.mg_set_channels(channels)
         g.mg_set_smoother(smoother)
-        g.set_weights_tensor(_weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev))
+        _set_operator(g, _weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev))
         g.assemble_weighted_rhs_tensor(gx, gy, f, init_x=f is not None)
         if f is None:
             g.fill_x(0.0)
@@ -255,7 +274,8 @@ def constrained_solve(gx, gy, f, values, fixed, iterations: int, wx=None, wy=Non
     to the host.  The start vector is f on the free pixels (0 without f).  Returns the composite -- the solution on the
     free pixels, `values` on the fixed ones -- as out_dtype (torch.uint8 by default: clamped).  With data_weight None or
     0 every connected set of free pixels needs a fixed neighbour, or the system is singular there.  precision, channels, smoother: as
-    weighted_solve's."""
+    weighted_solve's.  wx, wy, data_weight or fixed given as H x W x C: one operator (and one fixed set) per channel, as
+    in weighted_solve."""
     import torch
     out_dtype = torch.uint8 if out_dtype is None else out_dtype
     dev = _device_index(fixed)
@@ -269,7 +289,7 @@ def constrained_solve(gx, gy, f, values, fixed, iterations: int, wx=None, wy=Non
         g.mg_set_precision(precision)
         g.mg_set_channels(channels)
         g.mg_set_smoother(smoother)
-        g.set_weights_tensor(_weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev), fixed=fixed)
+        _set_operator(g, _weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev), fixed)
         if f is None:
             g.fill_x(0.0)
         g.assemble_constrained_rhs_tensor(gx, gy, f, values, init_x=f is not None)
@@ -366,7 +386,7 @@ def _solve_function():
                 g.mg_set_precision(cfg["precision"])
                 g.mg_set_channels(cfg["channels"])
                 g.mg_set_smoother(cfg["smoother"])
-                g.set_weights_tensor(wx, wy, lam, fixed=fixed)
+                _set_operator(g, wx, wy, lam, fixed)
                 if f is None:
                     g.fill_x(0.0)
                 g.assemble_constrained_rhs_tensor(gx, gy, f, values, init_x=f is not None)
@@ -438,6 +458,13 @@ def weighted_solve_grad(gx, gy, f, iterations: int, wx=None, wy=None, data_weigh
     graph is dropped); it is released as soon as autograd releases the node's saved tensors.  Under torch.no_grad(), or
     when no input requires a gradient, use weighted_solve / constrained_solve, which release it at once.
 
+    One operator per channel.  If any of wx, wy, data_weight, fixed is H x W x C the handle gets one operator per channel
+    (weighted_solve): an H x W x C weight gets an H x W x C gradient, channel c's from channel c alone (no sum over
+    channels), equal to the gradient of the one-channel call on channel c's slices; an H x W weight or a scalar passed
+    beside it is expanded to H x W x C here, outside the autograd function, so that torch sums its gradient over the
+    channels through the broadcast.  A mini-batch of N single-channel images with their own weights is H x W x N with
+    channels="batched".
+
     strict (the default): a forward or adjoint solve that does not report `converged` within `iterations` raises
     RuntimeError -- these are the gradients of the converged solution, and an unconverged solve's are not them."""
     import torch
@@ -447,10 +474,16 @@ def weighted_solve_grad(gx, gy, f, iterations: int, wx=None, wy=None, data_weigh
     dev = _device_index(ref)
     H, W = ref.shape[0], ref.shape[1]
 
+    C = ref.shape[2] if ref.dim() == 3 else 1
+    stacked = _per_channel(wx, wy, data_weight, fixed)
+
     def plane(w):
         if isinstance(w, torch.Tensor) and w.dim() == 0:
-            return w.expand(H, W)
-        return _weight(w, H, W, dev)
+            w = w.expand(H, W)
+        w = _weight(w, H, W, dev)
+        if stacked and w is not None and w.dim() == 2:
+            w = w.unsqueeze(-1).expand(H, W, C)
+        return w
 
     cfg = dict(iterations=int(iterations), epsilon=float(epsilon), hierarchy=hierarchy, precision=precision, channels=channels,
                smoother=smoother, strict=bool(strict))

@@ -243,6 +243,7 @@ typedef struct ccp_grid_desc {
 /* flags: a weighted grid.  Instead of SolveChannel's matrix the handle carries the normal equations of
  *     E(u) = sum wx (u(x+1,y) - u(x,y) - gx)^2 + sum wy (u(x,y+1) - u(x,y) - gy)^2 + sum lambda (u - f)^2,
  * one operator shared by all channels: screened Poisson fusion, WLS edge-preserving smoothing, soft constraints.
+ * (ccp_grid_set_weights_per_channel_device, below, gives every channel its own operator instead.)
  * wx(x,y) weighs the edge (x,y)-(x+1,y) (read for x < W-1 only), wy(x,y) the edge (x,y)-(x,y+1) (y < H-1 only),
  * lambda(x,y) is the data weight; each is widened to fp64 on the device.  Coefficients, in this order:
  *     d = lambda; d += wN; d += wW; d += wE; d += wS       (wN = wy(x,y-1), wW = wx(x-1,y), wE = wx(x,y), wS = wy(x,y))
@@ -886,6 +887,68 @@ typedef struct ccp_adjoint_outputs {
     const ccp_device_array *g_wx, *g_wy, *g_lambda, *g_gx, *g_gy, *g_f, *g_values;
 } ccp_adjoint_outputs;
 int ccp_grid_weighted_adjoint_device(ccp_grid *g, const ccp_adjoint_inputs *in, const ccp_adjoint_outputs *out);
+
+/* ---- One operator per channel on a weighted grid -------------------------------------------------------------------------
+ * ccp_grid_set_weights_* / _constrained_* install ONE operator that every channel shares.  This call installs one per
+ * channel: a stack of images with their own edge weights, data weights and fixed pixels (a mini-batch of single-channel
+ * images, colour channels smoothed along their own edges, per-channel confidence maps or anchor sets) on ONE handle.
+ *
+ * Definition.  Channel c's planes -- d, we, ws, lambda and, where a fixed mask came, ce, cs and lambda' -- are those that
+ * ccp_grid_set_weights_constrained_device forms on a ONE-CHANNEL handle from channel c's slices of the views, in the
+ * arithmetic order stated above, unchanged; and every call below gives channel c, bit for bit, what that one-channel
+ * handle gives.  wx, wy, lambda: F32 or F64, H x W x channels, stride_c USED (0 broadcasts one plane to every channel;
+ * an H x W array is passed that way); fixed: U8, F32 or F64, same shape, or NULL.  NULL views keep their defaults:
+ * weights 1, lambda 0, no fixed pixels.
+ *
+ * All channels are formed and validated in one launch (k_pco_coef / k_pco_coef_fixed, ccp_grid_pco.hpp); the call
+ * synchronises once and reads the verdict plus, when `fixed` is given, every channel's counts.  A weight that is negative,
+ * NaN or infinite in ANY channel: CCP_ERR_BAD_ARG, and the handle is left with no operator.  Views are checked as in every
+ * _device call, with the extent `channels` along c (a view too short for it: CCP_ERR_BAD_ARG before anything is enqueued).
+ * Not a weighted handle: CCP_ERR_UNSUPPORTED.  Installing drops the cached hierarchy.  ccp_grid_set_weights_* and
+ * _constrained_* go back to the shared operator and release the per-channel planes.  The ABI version does not change.
+ *
+ * While a per-channel operator is installed:
+ *   ccp_grid_assemble_weighted_rhs[_device], _constrained_rhs[_device]: channel c's b (and x at its fixed pixels, or with
+ *       init) from channel c's weights, lambda and fixed set; all channels in one launch (k_pco_rhs).
+ *   ccp_grid_b_from_x, ccp_grid_residual_norm2: channel c's operator (one launch per channel).
+ *   ccp_grid_mg_apply, ccp_grid_mg_conjugate_gradient: every channel with its own hierarchy (all channels' coarse levels
+ *       are formed by one launch per level, k_pco_coarsen).
+ *   ccp_grid_mg_level, ccp_grid_constraint_info: channel 0; their _channel forms: any channel (on a shared operator every
+ *       channel reports the shared one).
+ *   ccp_grid_adjoint_begin_device: channel c's free / live set.
+ *   ccp_grid_weighted_adjoint_device: wx, wy, lambda, fixed are read as H x W x channels (stride_c used), and g_wx, g_wy,
+ *       g_lambda are written as H x W x channels with NO sum over channels: channel c's accumulator starts at +0.0 and
+ *       takes that channel's one term, so g_wx[:, :, c] is what a one-channel handle writes.  g_gx, g_gy, g_f, g_values
+ *       are as above with channel c's weights.  One launch per channel, each the launch of a one-channel handle.
+ *
+ * Modes (CCP_MG_HIERARCHY_*, CCP_MG_PRECISION_*, CCP_MG_SMOOTHER_*, CCP_MG_CHANNELS_*):
+ *   sequential channels: both hierarchy kinds, F64 and F32, the point and the line smoother -- the existing k_mg_*, k_mgs_*,
+ *       k_mgl_* and k_cg_* kernels run unchanged on channel c's level descriptors, which is what makes channel c's x,
+ *       iterations, converged and last_l1_step those of the one-channel handle by construction;
+ *   batched channels: F64 with the point smoother, both hierarchy kinds (k_pco_tile, k_pco_restrict, k_pco_tail,
+ *       k_pco_apply: the channel on grid z, the sequential kernels' arithmetic and grouping of partial sums; the vector
+ *       and scalar passes are k_mgb_*'s); every channel gets the sequential call's bits and counts.  Timings: NOTES R26.1;
+ *   batched with F32, batched with the line smoother, the row-block calls: CCP_ERR_UNSUPPORTED with x and b untouched, as
+ *       on every weighted handle.
+ * One exception to "channel c behaves as the one-channel handle": with CCP_MG_PRECISION_F32 the narrowing of all
+ * channels' coefficients has ONE verdict, so a coefficient that narrows to inf (or a non-zero one to 0) in any channel makes
+ * every solve on the handle CCP_ERR_UNSUPPORTED, where one-channel handles on the other channels' slices would solve.
+ *
+ * Memory per pixel and channel: 32 B (d, we, ws, lambda); plus 24 B while any channel has a fixed pixel (ce, cs, lambda'
+ * for every channel); plus 12 B with CCP_MG_PRECISION_F32 (the float copies of d, we, ws); plus one third of each for the
+ * coarse levels of the hierarchy.  The V-cycle's vectors stay one set in sequential mode and `channels` sets in batched
+ * mode, as on a shared operator. */
+int ccp_grid_set_weights_per_channel_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy,
+                                            const ccp_device_array *lambda, const ccp_device_array *fixed);
+/* 1: the shared operator; channels: one per channel.  Not a weighted handle: CCP_ERR_UNSUPPORTED; no operator:
+ * CCP_ERR_STATE. */
+int ccp_grid_operator_channels(ccp_grid *g, int32_t *n);
+/* ccp_grid_mg_level of channel `channel`'s hierarchy (0 <= channel < channels, else CCP_ERR_BAD_ARG). */
+int ccp_grid_mg_level_channel(ccp_grid *g, int32_t channel, int32_t level, int32_t *n_levels, int32_t *width, int32_t *height,
+                              double *diag, double *w_east, double *w_south);
+/* ccp_grid_constraint_info of channel `channel`'s operator. */
+int ccp_grid_constraint_info_channel(ccp_grid *g, int32_t channel, int64_t *fixed_pixels, int64_t *free_live_pixels,
+                                     int64_t *boundary_edges);
 
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
