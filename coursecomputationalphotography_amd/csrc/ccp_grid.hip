@@ -7,8 +7,7 @@
 #include "ccp_grid_cg.hpp"
 #include "ccp_grid_mg_view.hpp"
 #include "ccp_grid_blend.hpp"
-#include "ccp_grid_weighted.hpp"
-#include "ccp_grid_pco_api.hpp"
+#include "ccp_grid_weighted_api.hpp"
 #include "ccp_grid_adjoint.hpp"
 #include "ccp_comm.hpp"
 #include "ccp_view_check.hpp"
@@ -146,16 +145,14 @@ struct ccp_grid {
     bool has_op = false;
     DevBuf<double> wop, wpart;
     // Fixed pixels (ccp_grid_set_weights_constrained_*): wcons holds the planes ce, cs and lambda' (ccp_grid_weighted.hpp)
-    // while the operator has any (has_fixed), and is released otherwise.  wcount: the formation pass's verdict and counts;
-    // w_fixed / w_live / w_edges: ccp_grid_constraint_info's figures (w_live < 0: not counted yet)
+    // while the operator has any (has_fixed), and is released otherwise.  wcount: the formation pass's verdict and counts
     bool has_fixed = false;
     DevBuf<double> wcons;
     DevBuf<unsigned long long> wcount;
-    long w_fixed = 0, w_live = -1, w_edges = 0;
-    // One operator per channel (ccp_grid_set_weights_per_channel_device, ccp_grid_pco.hpp): wop then holds `channels` sets
-    // of the four planes, 4 x ch_stride apart, and wcons (while any channel has a fixed pixel) `channels` sets of its three,
-    // 3 x ch_stride apart; pc_*: every channel's figures (w_fixed, w_live, w_edges are channel 0's).  op_sets: the sets wop
-    // holds now, 1 after the shared operator's setters.
+    // One operator per channel (ccp_grid_set_weights_per_channel_device): wop then holds `channels` sets of the four planes,
+    // 4 x ch_stride apart, and wcons (while any channel has a fixed pixel) `channels` sets of its three, 3 x ch_stride
+    // apart.  op_sets: the sets wop holds now, 1 after the shared operator's setters.  pc_*: ccp_grid_constraint_info's
+    // figures of every set, index 0 the shared operator's (pc_live < 0: not counted yet).
     bool per_channel = false;
     int op_sets = 1;
     long pc_fixed[kMaxChannels] = {}, pc_live[kMaxChannels] = {}, pc_edges[kMaxChannels] = {};
@@ -2886,47 +2883,20 @@ int blend_composite(ccp_grid *g, const VU &canvas, const View<uint8_t> &out)
     return CCP_OK;
 }
 
-// F: the view of the data term f, float, double or u8; an absent input is a null view (guarded by its `has` bit).
-// V: the view of the prescribed values (has & 8), read only where the operator has fixed pixels.
-template <typename F, typename V>
-int weighted_rhs(ccp_grid *g, const VF &gx, const VF &gy, const F &f, int has, bool init_x, const V &values)
+// a caller's view (or none) as the weighted handle's operator kernels read it
+ImageView image_view(const ccp_device_array *a, double dflt)
 {
-    const Geom &geo = g->geom;
-    const dim3 grid = pixel_grid(g, geo.H);
-    const double *op = g->wop.p;
-    const int C = g->desc.channels;
-    if (g->has_fixed) {
-        if (init_x)
-            hipLaunchKernelGGL((k_weighted_rhs<true, true, VF, F, V>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx,
-                               gy, f, has, C, g->wcons.p, values);
-        else
-            hipLaunchKernelGGL((k_weighted_rhs<false, true, VF, F, V>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx,
-                               gy, f, has, C, g->wcons.p, values);
-    } else {
-        const VF none{nullptr, 0, 0, 0, 0};
-        const double *no_planes = nullptr;
-        if (init_x)
-            hipLaunchKernelGGL((k_weighted_rhs<true, false, VF, F, VF>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx,
-                               gy, f, has & 7, C, no_planes, none);
-        else
-            hipLaunchKernelGGL((k_weighted_rhs<false, false, VF, F, VF>), grid, dim3(kBlock), 0, g->stream, g->b.p, g->x.p, geo, op, geo.ch_stride, gx,
-                               gy, f, has & 7, C, no_planes, none);
-    }
-    CCP_HIP(hipGetLastError());
-    return CCP_OK;
+    if (!a) return ImageView{nullptr, 0, 0, 0, 0, dflt};
+    return ImageView{a->data, (long)a->stride_y, (long)a->stride_x, (long)a->stride_c, a->dtype, dflt};
 }
 
-// the dispatch over f's dtype (NULL: no data term)
-template <typename V>
-int weighted_rhs_views(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f, int has, bool init,
-                       const V &values)
+// b of every channel from the handle's operator, the shared one or every channel's own, in one launch; v: gx, gy, f and
+// the prescribed values (has & 1, 2, 4, 8: which of them are there)
+int weighted_rhs_launch(ccp_grid *g, const ImageView v[4], int has, bool init_x)
 {
-    const VF none{nullptr, 0, 0, 0, 0};
-    const VF vgx = gx ? view_of<const float>(gx) : none, vgy = gy ? view_of<const float>(gy) : none;
-    if (!f) return weighted_rhs(g, vgx, vgy, none, has, init, values);
-    if (f->dtype == CCP_DTYPE_U8) return weighted_rhs(g, vgx, vgy, view_of<const uint8_t>(f), has, init, values);
-    if (f->dtype == CCP_DTYPE_F32) return weighted_rhs(g, vgx, vgy, view_of<const float>(f), has, init, values);
-    return weighted_rhs(g, vgx, vgy, view_of<const double>(f), has, init, values);
+    const int C = g->desc.channels;
+    return weighted_rhs(g->stream, g->b.p, g->x.p, g->geom, C, g->per_channel ? C : 1, g->wop.p, g->has_fixed ? g->wcons.p : nullptr, v[0], v[1],
+                        v[2], v[3], has, init_x);
 }
 
 // ccp_grid_assemble_weighted_rhs and ccp_grid_assemble_constrained_rhs: the host arrays staged, one launch, one wait
@@ -2942,32 +2912,18 @@ int weighted_rhs_host(ccp_grid *g, const float *gx, const float *gy, int64_t fie
     const float *src[4] = {gx, gy, f, values};
     const int64_t stride[4] = {field_stride_bytes, field_stride_bytes, f_stride_bytes, values_stride_bytes};
     DevBuf<float> dev[4];
-    VF v[4];
+    ImageView v[4];
     int has = 0;
     for (int i = 0; i < 4; ++i) {
-        v[i] = VF{nullptr, 0, 0, 0, 0};
+        v[i] = ImageView{nullptr, 0, 0, 0, 0, 0.0};
         if (!src[i]) continue;
         has |= 1 << i;
         CCP_TRY(upload_window(g, dev[i], src[i], stride[i], 0, H));
-        v[i] = staged_view<const float>(dev[i].p, W, C);
+        v[i] = ImageView{dev[i].p, (long)W * C, (long)C, 1, CCP_DTYPE_F32, 0.0};   // the staging buffer: packed H x W x C
     }
-    if (g->per_channel) {
-        PcoView pv[4];
-        for (int i = 0; i < 4; ++i) pv[i] = PcoView{v[i].p, v[i].sy, v[i].sx, v[i].sc, CCP_DTYPE_F32, 0.0};
-        CCP_TRY(pco_rhs(g->stream, g->b.p, g->x.p, g->geom, C, g->wop.p, g->has_fixed ? g->wcons.p : nullptr, pv[0], pv[1], pv[2], pv[3], has,
-                        init_x));
-    } else {
-        CCP_TRY(weighted_rhs(g, v[0], v[1], v[2], has, init_x, v[3]));
-    }
+    CCP_TRY(weighted_rhs_launch(g, v, has, init_x));
     CCP_HIP(hipStreamSynchronize(g->stream));
     return CCP_OK;
-}
-
-// a caller's view (or none) as the per-channel kernels read it
-PcoView pco_view(const ccp_device_array *a, double dflt)
-{
-    if (!a) return PcoView{nullptr, 0, 0, 0, 0, dflt};
-    return PcoView{a->data, (long)a->stride_y, (long)a->stride_x, (long)a->stride_c, a->dtype, dflt};
 }
 
 int weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f,
@@ -2980,13 +2936,8 @@ int weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_devic
     if (values) CCP_TRY(check_view(g, values, kF32F64 | kU8, false, 1, H, W, C));
     if (!g->has_op) return CCP_ERR_STATE;
     const int has = (gx ? 1 : 0) | (gy ? 2 : 0) | (f ? 4 : 0) | (values ? 8 : 0);
-    if (g->per_channel)
-        return pco_rhs(g->stream, g->b.p, g->x.p, g->geom, C, g->wop.p, g->has_fixed ? g->wcons.p : nullptr, pco_view(gx, 0.0), pco_view(gy, 0.0),
-                       pco_view(f, 0.0), pco_view(values, 0.0), has, init);
-    if (!values) return weighted_rhs_views(g, gx, gy, f, has, init, VF{nullptr, 0, 0, 0, 0});
-    if (values->dtype == CCP_DTYPE_U8) return weighted_rhs_views(g, gx, gy, f, has, init, view_of<const uint8_t>(values));
-    if (values->dtype == CCP_DTYPE_F32) return weighted_rhs_views(g, gx, gy, f, has, init, view_of<const float>(values));
-    return weighted_rhs_views(g, gx, gy, f, has, init, view_of<const double>(values));
+    const ImageView v[4] = {image_view(gx, 0.0), image_view(gy, 0.0), image_view(f, 0.0), image_view(values, 0.0)};
+    return weighted_rhs_launch(g, v, has, init);
 }
 
 }  // namespace
@@ -3352,8 +3303,6 @@ void drop_operator(ccp_grid *g)
     mg_release(g->mg);
     g->mg = nullptr;
     g->has_op = g->has_fixed = false;
-    g->w_fixed = g->w_edges = 0;
-    g->w_live = -1;
     g->per_channel = false;
 }
 
@@ -3369,39 +3318,39 @@ int operator_planes(ccp_grid *g, int sets)
     return CCP_OK;
 }
 
-// One operator per channel (ccp_grid_pco.hpp): all channels' planes in one launch, the verdict and, with a mask, every
-// channel's counts in one read.  The three extra planes stay only if some channel has a fixed pixel.
-int set_weights_per_channel(ccp_grid *g, const PcoView &wx, const PcoView &wy, const PcoView &lam, const PcoView *fixed)
+// The handle's operators (one that all channels share, the views H x W; or per_channel: one per channel, the views
+// H x W x C) from three weight views and, with `fixed`, a mask of fixed pixels: all planes in one launch, the verdict
+// and, with a mask, every set's counts in one read.  The old operator and the hierarchy built on it are gone either
+// way: a refusal leaves the handle with none.  The three extra planes stay only if some set has a fixed pixel: with
+// none the four planes are what the call without a mask forms, bit for bit.
+int form_operator(ccp_grid *g, bool per_channel, const ImageView &wx, const ImageView &wy, const ImageView &lam, const ImageView *fixed)
 {
     const Geom &geo = g->geom;
     const long n = geo.ch_stride;
-    const int C = g->desc.channels;
+    const int sets = per_channel ? g->desc.channels : 1;
     drop_operator(g);
     g->wcons.release();
-    CCP_TRY(operator_planes(g, C));
+    CCP_TRY(operator_planes(g, sets));
     if (fixed) {
-        CCP_TRY(g->wcons.alloc(3 * (size_t)C * (size_t)n));
-        CCP_HIP(hipMemsetAsync(g->wcons.p, 0, 3 * sizeof(double) * (size_t)C * (size_t)n, g->stream));   // the pads
+        CCP_TRY(g->wcons.alloc(3 * (size_t)sets * (size_t)n));
+        CCP_HIP(hipMemsetAsync(g->wcons.p, 0, 3 * sizeof(double) * (size_t)sets * (size_t)n, g->stream));   // the pads
     }
-    CCP_TRY(pco_coef(g->stream, wx, wy, lam, fixed, geo.W, geo.H, C, geo.pitch, g->wop.p, n, g->wcons.p, g->wcount.p));
+    CCP_TRY(weighted_coef(g->stream, wx, wy, lam, fixed, geo.W, geo.H, sets, geo.pitch, g->wop.p, n, g->wcons.p, g->wcount.p));
     unsigned long long count[1 + 3 * kMaxChannels] = {1};
-    CCP_HIP(hipMemcpyAsync(count, g->wcount.p, sizeof(unsigned long long) * (size_t)(1 + 3 * C), hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipMemcpyAsync(count, g->wcount.p, sizeof(unsigned long long) * (size_t)(1 + 3 * sets), hipMemcpyDeviceToHost, g->stream));
     CCP_HIP(hipStreamSynchronize(g->stream));
     bool any_fixed = false;
-    for (int c = 0; c < C && fixed; ++c) any_fixed = any_fixed || count[1 + 3 * c] != 0;
+    for (int c = 0; c < sets && fixed; ++c) any_fixed = any_fixed || count[1 + 3 * c] != 0;
     if (count[0] || !any_fixed) g->wcons.release();
     if (count[0]) return CCP_ERR_BAD_ARG;
-    for (int c = 0; c < C; ++c) {
+    for (int c = 0; c < sets; ++c) {
         g->pc_fixed[c] = fixed ? (long)count[1 + 3 * c] : 0;
         g->pc_live[c] = fixed ? (long)geo.W * geo.H - (long)count[1 + 3 * c] - (long)count[2 + 3 * c] : -1;
         g->pc_edges[c] = fixed ? (long)count[3 + 3 * c] : 0;
     }
     g->has_op = true;
-    g->per_channel = true;
+    g->per_channel = per_channel;
     g->has_fixed = any_fixed;
-    g->w_fixed = g->pc_fixed[0];
-    g->w_live = g->pc_live[0];
-    g->w_edges = g->pc_edges[0];
     return edge_timeout_status(g);
 }
 
@@ -3419,55 +3368,24 @@ int count_live(ccp_grid *g, const double *d, long *live)
     return CCP_OK;
 }
 
-// The operator from three weight views in one pass; the device's verdict on the weights is read back once.  The old
-// operator and the hierarchy built on it are gone either way: a refusal leaves the handle with none.
-int set_weights(ccp_grid *g, const WeightView &wx, const WeightView &wy, const WeightView &lam)
+// ccp_grid_set_weights_[constrained_]device and ccp_grid_set_weights_per_channel_device: the views are H x W for the
+// shared operator and H x W x channels for one operator per channel
+int set_weights_device(ccp_grid *g, bool per_channel, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
+                       const ccp_device_array *fixed)
 {
-    const Geom &geo = g->geom;
-    const long n = geo.ch_stride;
-    drop_operator(g);
-    g->wcons.release();
-    CCP_TRY(operator_planes(g, 1));
-    unsigned bad = 0;
-    CCP_HIP(hipMemsetAsync(g->io_bad.p, 0, sizeof(unsigned), g->stream));
-    hipLaunchKernelGGL(k_weighted_coef, dim3((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)geo.H), dim3(kBlock), 0, g->stream, wx, wy,
-                       lam, geo.W, geo.H, geo.pitch, g->wop.p, g->wop.p + n, g->wop.p + 2 * n, g->wop.p + 3 * n, g->io_bad.p);
-    CCP_HIP(hipGetLastError());
-    CCP_HIP(hipMemcpyAsync(&bad, g->io_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    if (bad) return CCP_ERR_BAD_ARG;
-    g->has_op = true;
-    return edge_timeout_status(g);
-}
-
-// set_weights with a mask of fixed pixels (M: its view): the planes of ccp_grid_weighted.hpp in one pass, whose verdict
-// and counts come back in one read.  The three extra planes stay only if any pixel is fixed: with none the four planes
-// are what set_weights forms, bit for bit.
-template <typename M>
-int set_weights_fixed(ccp_grid *g, const WeightView &wx, const WeightView &wy, const WeightView &lam, const M &fixed)
-{
-    const Geom &geo = g->geom;
-    const long n = geo.ch_stride;
-    drop_operator(g);
-    CCP_TRY(operator_planes(g, 1));
-    CCP_TRY(g->wcons.alloc(3 * (size_t)n));
-    CCP_HIP(hipMemsetAsync(g->wcons.p, 0, 3 * sizeof(double) * (size_t)n, g->stream));   // the pads
-    CCP_HIP(hipMemsetAsync(g->wcount.p, 0, 4 * sizeof(unsigned long long), g->stream));
-    hipLaunchKernelGGL((k_weighted_coef_fixed<M>), dim3((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)geo.H), dim3(kBlock), 0, g->stream,
-                       wx, wy, lam, fixed, geo.W, geo.H, geo.pitch, g->wop.p, g->wop.p + n, g->wop.p + 2 * n, g->wop.p + 3 * n, g->wcons.p,
-                       g->wcons.p + n, g->wcons.p + 2 * n, g->wcount.p);
-    CCP_HIP(hipGetLastError());
-    unsigned long long count[4] = {1, 0, 0, 0};
-    CCP_HIP(hipMemcpyAsync(count, g->wcount.p, sizeof(count), hipMemcpyDeviceToHost, g->stream));
-    CCP_HIP(hipStreamSynchronize(g->stream));
-    if (count[0] || !count[1]) g->wcons.release();
-    if (count[0]) return CCP_ERR_BAD_ARG;
-    g->has_op = true;
-    g->has_fixed = count[1] != 0;
-    g->w_fixed = (long)count[1];
-    g->w_live = (long)geo.W * geo.H - (long)count[1] - (long)count[2];
-    g->w_edges = (long)count[3];
-    return edge_timeout_status(g);
+    CCP_TRY(weighted_handle(g));
+    const int W = g->desc.width, H = g->desc.height, C = per_channel ? g->desc.channels : 1;
+    const ccp_device_array *src[3] = {wx, wy, lambda};
+    const double dflt[3] = {1.0, 1.0, 0.0};
+    ImageView v[3];
+    for (int i = 0; i < 3; ++i) {
+        if (src[i]) CCP_TRY(check_view(g, src[i], kF32F64, false, 1, H, W, C));
+        v[i] = image_view(src[i], dflt[i]);
+    }
+    if (!fixed) return form_operator(g, per_channel, v[0], v[1], v[2], nullptr);
+    CCP_TRY(check_view(g, fixed, kF32F64 | kU8, false, 1, H, W, C));
+    const ImageView m = image_view(fixed, 0.0);
+    return form_operator(g, per_channel, v[0], v[1], v[2], &m);
 }
 
 }  // namespace
@@ -3495,52 +3413,31 @@ try {
     const double dflt[3] = {1.0, 1.0, 0.0};
     DevBuf<float> dev[3];
     DevBuf<uint8_t> dfix;
-    WeightView v[3];
+    ImageView v[3];
     for (int i = 0; i < 3; ++i) {
-        v[i] = WeightView{nullptr, 0, 0, 0, dflt[i]};
+        v[i] = ImageView{nullptr, 0, 0, 0, 0, dflt[i]};
         if (!src[i]) continue;
         CCP_TRY(dev[i].alloc((size_t)W * H));
         CCP_HIP(hipMemcpy2DAsync(dev[i].p, (size_t)W * sizeof(float), src[i], (size_t)row_stride_bytes, (size_t)W * sizeof(float), (size_t)H,
                                  hipMemcpyHostToDevice, g->stream));
-        v[i] = WeightView{dev[i].p, (long)W, 1, 0, dflt[i]};
+        v[i] = ImageView{dev[i].p, (long)W, 1, 0, CCP_DTYPE_F32, dflt[i]};
     }
-    if (!fixed) return set_weights(g, v[0], v[1], v[2]);
+    if (!fixed) return form_operator(g, false, v[0], v[1], v[2], nullptr);
     CCP_TRY(dfix.alloc((size_t)W * H));
     CCP_HIP(hipMemcpy2DAsync(dfix.p, (size_t)W, fixed, (size_t)fixed_stride_bytes, (size_t)W, (size_t)H, hipMemcpyHostToDevice, g->stream));
-    return set_weights_fixed(g, v[0], v[1], v[2], View<const uint8_t>{dfix.p, 0, (long)W, 1, 0});
+    const ImageView m{dfix.p, (long)W, 1, 0, CCP_DTYPE_U8, 0.0};
+    return form_operator(g, false, v[0], v[1], v[2], &m);
 } CCP_ABI_CATCH
 
 int ccp_grid_set_weights_constrained_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
                                             const ccp_device_array *fixed)
 try {
-    CCP_TRY(weighted_handle(g));
-    const int W = g->desc.width, H = g->desc.height;
-    const ccp_device_array *src[3] = {wx, wy, lambda};
-    const double dflt[3] = {1.0, 1.0, 0.0};
-    WeightView v[3];
-    for (int i = 0; i < 3; ++i) {
-        v[i] = WeightView{nullptr, 0, 0, 0, dflt[i]};
-        if (!src[i]) continue;
-        CCP_TRY(check_view(g, src[i], kF32F64, false, 1, H, W, 1));
-        v[i] = WeightView{src[i]->data, (long)src[i]->stride_y, (long)src[i]->stride_x, src[i]->dtype == CCP_DTYPE_F64 ? 1 : 0, dflt[i]};
-    }
-    if (!fixed) return set_weights(g, v[0], v[1], v[2]);
-    CCP_TRY(check_view(g, fixed, kF32F64 | kU8, false, 1, H, W, 1));
-    if (fixed->dtype == CCP_DTYPE_U8) return set_weights_fixed(g, v[0], v[1], v[2], view_of<const uint8_t>(fixed));
-    if (fixed->dtype == CCP_DTYPE_F32) return set_weights_fixed(g, v[0], v[1], v[2], view_of<const float>(fixed));
-    return set_weights_fixed(g, v[0], v[1], v[2], view_of<const double>(fixed));
+    return set_weights_device(g, false, wx, wy, lambda, fixed);
 } CCP_ABI_CATCH
 
 int ccp_grid_constraint_info(ccp_grid *g, int64_t *fixed_pixels, int64_t *free_live_pixels, int64_t *boundary_edges)
 try {
-    CCP_TRY(weighted_handle(g));
-    if (!g->has_op) return CCP_ERR_STATE;
-    if (g->w_live < 0) CCP_TRY(count_live(g, g->wop.p, &g->w_live));   // an operator of ccp_grid_set_weights_*: its dead pixels counted once
-    if (g->per_channel) g->pc_live[0] = g->w_live;
-    if (fixed_pixels) *fixed_pixels = g->w_fixed;
-    if (free_live_pixels) *free_live_pixels = g->w_live;
-    if (boundary_edges) *boundary_edges = g->w_edges;
-    return CCP_OK;
+    return ccp_grid_constraint_info_channel(g, 0, fixed_pixels, free_live_pixels, boundary_edges);
 } CCP_ABI_CATCH
 
 int ccp_grid_constraint_info_channel(ccp_grid *g, int32_t channel, int64_t *fixed_pixels, int64_t *free_live_pixels, int64_t *boundary_edges)
@@ -3548,30 +3445,19 @@ try {
     CCP_TRY(weighted_handle(g));
     if (channel < 0 || channel >= g->desc.channels) return CCP_ERR_BAD_ARG;
     if (!g->has_op) return CCP_ERR_STATE;
-    if (!g->per_channel || channel == 0) return ccp_grid_constraint_info(g, fixed_pixels, free_live_pixels, boundary_edges);
-    if (g->pc_live[channel] < 0) CCP_TRY(count_live(g, g->wop.p + 4 * (long)channel * g->geom.ch_stride, &g->pc_live[channel]));
-    if (fixed_pixels) *fixed_pixels = g->pc_fixed[channel];
-    if (free_live_pixels) *free_live_pixels = g->pc_live[channel];
-    if (boundary_edges) *boundary_edges = g->pc_edges[channel];
+    const int k = g->per_channel ? channel : 0;                            // the shared operator is every channel's
+    // an operator formed without a mask: its dead pixels counted once
+    if (g->pc_live[k] < 0) CCP_TRY(count_live(g, g->wop.p + 4 * (long)k * g->geom.ch_stride, &g->pc_live[k]));
+    if (fixed_pixels) *fixed_pixels = g->pc_fixed[k];
+    if (free_live_pixels) *free_live_pixels = g->pc_live[k];
+    if (boundary_edges) *boundary_edges = g->pc_edges[k];
     return CCP_OK;
 } CCP_ABI_CATCH
 
 int ccp_grid_set_weights_per_channel_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
                                             const ccp_device_array *fixed)
 try {
-    CCP_TRY(weighted_handle(g));
-    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
-    const ccp_device_array *src[3] = {wx, wy, lambda};
-    const double dflt[3] = {1.0, 1.0, 0.0};
-    PcoView v[3];
-    for (int i = 0; i < 3; ++i) {
-        if (src[i]) CCP_TRY(check_view(g, src[i], kF32F64, false, 1, H, W, C));
-        v[i] = pco_view(src[i], dflt[i]);
-    }
-    if (!fixed) return set_weights_per_channel(g, v[0], v[1], v[2], nullptr);
-    CCP_TRY(check_view(g, fixed, kF32F64 | kU8, false, 1, H, W, C));
-    const PcoView m = pco_view(fixed, 0.0);
-    return set_weights_per_channel(g, v[0], v[1], v[2], &m);
+    return set_weights_device(g, true, wx, wy, lambda, fixed);
 } CCP_ABI_CATCH
 
 int ccp_grid_operator_channels(ccp_grid *g, int32_t *n)

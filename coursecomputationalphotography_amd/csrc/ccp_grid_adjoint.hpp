@@ -38,7 +38,7 @@
 #define CCP_ADJ_FN inline
 #include "adjoint_host_real.inc"       // kBlock and w_at, as text from the real headers
 #else
-#include "ccp_grid_weighted.hpp"       // w_at
+#include "ccp_grid_stencil.hpp"        // w_at
 #define CCP_ADJ_FN __host__ __device__ __forceinline__
 #endif
 

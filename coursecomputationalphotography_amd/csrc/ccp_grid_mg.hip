@@ -4,7 +4,7 @@
 #include "ccp_grid_mgs.hpp"
 #include "ccp_grid_mgb.hpp"
 #include "ccp_grid_mgl.hpp"
-#include "ccp_grid_pco_api.hpp"
+#include "ccp_grid_weighted_api.hpp"
 #include "ccp_comm.hpp"
 
 #include <algorithm>
@@ -99,7 +99,7 @@ struct MgHierarchy {
     // one operator (opC == 1) only: 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda (lam_slot).  The one-block code, which may see
     // opC > 1, asks coef() for a coefficient plane and vec() for a vector; the row-block code (never weighted) uses arr().
     double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }
-    // One operator per channel (a weighted handle after ccp_grid_set_weights_per_channel_device, ccp_grid_pco.hpp): opC
+    // One operator per channel (a weighted handle after ccp_grid_set_weights_per_channel_device): opC
     // copies of the coefficient part of every level.  The coarse levels' d, we, ws, lambda of all channels live in cstore
     // (level k, channel ch: at cbase[k] + 4 ch size[k], each `size[k]`), the float copies of d, we, ws in cfstore (3 per
     // channel) and w32 (level 0, 3 n0 per channel); store and fstore then hold the vectors b, z, t alone (vec, fvec).
@@ -251,14 +251,11 @@ int build(const GridMgView &v, MgHierarchy **out)
         }
     }
     for (int k = 0; k + 1 < h->levels; ++k) {
-        if (OC > 1)                                                 // all channels' level k + 1 in one launch
-            CCP_TRY(pco_coarsen(v.stream, OC, h->lv[k], k ? 4 * h->size[k] : v.op_stride, k ? static_cast<const double *>(h->coef(0, k, 3)) : v.wlam,
-                                k ? 4 * h->size[k] : v.lam_stride, h->lv[k + 1], h->coef(0, k + 1, 0), h->coef(0, k + 1, 1), h->coef(0, k + 1, 2),
-                                h->coef(0, k + 1, 3), 4 * h->size[k + 1], rescaled ? 0.5 : 1.0));
-        else if (v.weighted)
-            hipLaunchKernelGGL(k_mg_coarsen_weighted, cells_grid(h->lv[k + 1].W, h->lv[k + 1].H), dim3(kBlock), 0, v.stream, h->lv[k],
-                               k ? static_cast<const double *>(h->arr(k, h->lam_slot)) : v.wlam, h->lv[k + 1], h->arr(k + 1, 0), h->arr(k + 1, 1),
-                               h->arr(k + 1, 2), h->arr(k + 1, h->lam_slot), rescaled ? 0.5 : 1.0);
+        if (v.weighted)                                             // level k + 1 of all OC operators in one launch
+            CCP_TRY(weighted_coarsen(v.stream, OC, h->lv[k], k ? 4 * h->size[k] : v.op_stride,
+                                     k ? static_cast<const double *>(h->coef(0, k, 3)) : v.wlam, k ? 4 * h->size[k] : v.lam_stride, h->lv[k + 1],
+                                     h->coef(0, k + 1, 0), h->coef(0, k + 1, 1), h->coef(0, k + 1, 2), h->coef(0, k + 1, 3), 4 * h->size[k + 1],
+                                     rescaled ? 0.5 : 1.0));
         else
             coarsen(level_kind(*h, k), v.stream, h->lv[k], h->lv[k + 1], 0, h->lv[k + 1].H, h->arr(k + 1, 0), h->arr(k + 1, 1), h->arr(k + 1, 2));
         CCP_HIP(hipGetLastError());

@@ -7,7 +7,7 @@
 // (2X..2X+1, 2Y..2Y+1), down to 1x1.  A_{k+1} = P^T A_k P with P piecewise constant over the aggregates is again a
 // 5-point operator, stored per cell as d (diagonal), we (weight to the east cell), ws (weight to the south cell);
 // the weights are the positive couplings (A_ij = -w).  Every value is a small integer: exact in fp64.  A weighted
-// hierarchy carries the data weight lambda on every level too and forms d without cancellation (k_mg_coarsen_weighted):
+// hierarchy carries the data weight lambda on every level too and forms d without cancellation (k_weighted_coarsen):
 // its weights are real numbers, and d - 2 x internal edges could round to a tiny or negative diagonal.
 //
 // Layout.  Every level uses the fine grid's colour-split layout: cell (X,Y) sits in colour plane (X+Y)&1 of row Y at
@@ -39,7 +39,6 @@
 #include "ccp_cg.hpp"
 #include "ccp_grid_mg_view.hpp"
 #include "ccp_grid_stencil.hpp"
-#include "ccp_grid_weighted.hpp"
 
 namespace ccp {
 
@@ -256,8 +255,7 @@ k_mg_coarsen(MgLevel lv, MgLevel cv, int Y0, double *__restrict__ d, double *__r
 // the we of the column to the left, upper child first); we / ws as k_mg_coarsen forms them.  Every term is >= 0, so a
 // coarse diagonal is never a difference.  `edge` (uniform) scales the four side sums: 1.0 for the Galerkin hierarchy,
 // 0.5 for the rescaled one (CCP_MG_HIERARCHY_RESCALED), whose correction is then added unscaled; both products are
-// exact, and lambda_c takes no factor.  grid = (ceil(Wc/kBlock), Hc).
-// The cell is written once (mg_coarsen_weighted_cell) for this kernel and the per-channel one (ccp_grid_pco.hpp).
+// exact, and lambda_c takes no factor.
 __device__ __forceinline__ void mg_coarsen_weighted_cell(const MgLevel &lv, const double *__restrict__ lam, const MgLevel &cv, int X, int Y,
                                                          double *__restrict__ d, double *__restrict__ we, double *__restrict__ ws,
                                                          double *__restrict__ lam_c, double edge)
@@ -278,15 +276,6 @@ __device__ __forceinline__ void mg_coarsen_weighted_cell(const MgLevel &lv, cons
     we[at] = e;
     ws[at] = s;
     lam_c[at] = lc;
-}
-
-static __global__ void __launch_bounds__(kBlock)
-k_mg_coarsen_weighted(MgLevel lv, const double *__restrict__ lam, MgLevel cv, double *__restrict__ d, double *__restrict__ we,
-                      double *__restrict__ ws, double *__restrict__ lam_c, double edge)
-{
-    const int X = blockIdx.x * kBlock + threadIdx.x, Y = blockIdx.y;
-    if (X >= cv.W) return;
-    mg_coarsen_weighted_cell(lv, lam, cv, X, Y, d, we, ws, lam_c, edge);
 }
 
 // level 0's coefficients in the level layout (ccp_grid_mg_level only).  grid = (ceil(W/kBlock), H).

@@ -25,6 +25,8 @@
 
 #include "ccp_grid_mg.hpp"
 
+#include <cfloat>
+
 namespace ccp {
 
 constexpr int kMgsTileW = 64, kMgsTileH = 32;                     // output tile of k_mgs_tile (halo 2 nu around it), as k_mg_tile's

@@ -1,6 +1,7 @@
 // ccp_grid_stencil.hpp — the grid layout (Geom, row_off), 16-byte lane vectors and the 5-point stencil of
 // SolveChannel's matrix (classify, gs_update, apply_row): the device helpers of ccp_grid_kernels.hpp, which explains
-// the layout and the arithmetic.  No kernels here, so that more than one translation unit may include it.
+// the layout and the arithmetic; and the layout and the row of a weighted handle's stored operator (w_at, weighted_row).
+// No kernels here, so that more than one translation unit may include it.
 #pragma once
 
 #include "ccp_common.hpp"
@@ -94,6 +95,35 @@ __device__ __forceinline__ T apply_row(const Stencil &s, T xi, T xu, T xl, T xr,
     if (s.right) sum += T(-1) * xr;
     if (s.down) sum += T(-1) * xd;
     return sum;
+}
+
+// ---- the weighted handles' stored operator (ccp_grid_weighted.hpp explains the planes) ---------------------------------
+// cell (x,y) of a plane in the colour-split layout of x, b and the operator's planes
+__host__ __device__ __forceinline__ long w_at(long pitch, int x, int y)
+{
+    return ((long)y * 2 + ((x + y) & 1)) * pitch + (x >> 1);
+}
+
+// (A z)(x,y) of the stored operator on a W x H single-block level (the PCG's product on level 0 as well)
+__device__ __forceinline__ double weighted_row(const double *__restrict__ d, const double *__restrict__ we, const double *__restrict__ ws,
+                                               long pitch, int W, int H, const double *__restrict__ z, int x, int y)
+{
+    const long at = w_at(pitch, x, y);
+    const double dd = d[at];
+    if (dd == 0.0) return 0.0;
+    double a = 0.0;
+    if (y >= 1) {
+        const long n = w_at(pitch, x, y - 1);
+        a += -(ws[n] * z[n]);
+    }
+    if (x >= 1) {
+        const long w = w_at(pitch, x - 1, y);
+        a += -(we[w] * z[w]);
+    }
+    a += dd * z[at];
+    if (x + 1 < W) a += -(we[at] * z[w_at(pitch, x + 1, y)]);
+    if (y + 1 < H) a += -(ws[at] * z[w_at(pitch, x, y + 1)]);
+    return a;
 }
 
 }  // namespace ccp

@@ -1,6 +1,7 @@
-// ccp_grid_pco.hip — the kernels of a weighted handle's per-channel operator (ccp_grid_pco.hpp) in a translation unit
-// of their own, behind the launchers ccp_grid.hip and ccp_grid_mg.hip call.
+// ccp_grid_weighted.hip — the weighted handle's operator kernels (ccp_grid_weighted.hpp) and the per-channel batched
+// mode's (ccp_grid_pco.hpp) in a translation unit of their own, behind the launchers ccp_grid.hip and ccp_grid_mg.hip call.
 #include "ccp_grid_pco.hpp"
+#include "ccp_grid_weighted.hpp"
 
 #include <atomic>
 
@@ -12,38 +13,38 @@ dim3 pixels(int W, int H, int C) { return dim3((unsigned)((W + kBlock - 1) / kBl
 
 }  // namespace
 
-int ccp::pco_coef(hipStream_t s, const PcoView &wx, const PcoView &wy, const PcoView &lam, const PcoView *fixed, int W, int H, int C, long pitch,
-                  double *op, long plane, double *cons, unsigned long long *count)
+int ccp::weighted_coef(hipStream_t s, const ImageView &wx, const ImageView &wy, const ImageView &lam, const ImageView *fixed, int W, int H,
+                       int sets, long pitch, double *op, long plane, double *cons, unsigned long long *count)
 {
-    CCP_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long) * (size_t)(1 + 3 * C), s));
+    CCP_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long) * (size_t)(1 + 3 * sets), s));
     if (fixed)
-        hipLaunchKernelGGL(k_pco_coef_fixed, pixels(W, H, C), dim3(kBlock), 0, s, wx, wy, lam, *fixed, W, H, pitch, op, plane, 4 * plane, cons,
-                           3 * plane, count);
+        hipLaunchKernelGGL(k_weighted_coef_fixed, pixels(W, H, sets), dim3(kBlock), 0, s, wx, wy, lam, *fixed, W, H, pitch, op, plane, 4 * plane,
+                           cons, 3 * plane, count);
     else
-        hipLaunchKernelGGL(k_pco_coef, pixels(W, H, C), dim3(kBlock), 0, s, wx, wy, lam, W, H, pitch, op, plane, 4 * plane, count);
+        hipLaunchKernelGGL(k_weighted_coef, pixels(W, H, sets), dim3(kBlock), 0, s, wx, wy, lam, W, H, pitch, op, plane, 4 * plane, count);
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 }
 
-int ccp::pco_rhs(hipStream_t s, double *b, double *x, const Geom &g, int C, const double *op, const double *cons, const PcoView &gx,
-                 const PcoView &gy, const PcoView &f, const PcoView &v, int has, bool init)
+int ccp::weighted_rhs(hipStream_t s, double *b, double *x, const Geom &g, int C, int sets, const double *op, const double *cons,
+                      const ImageView &gx, const ImageView &gy, const ImageView &f, const ImageView &v, int has, bool init)
 {
     const long plane = g.ch_stride;
-    const dim3 grid = pixels(g.W, g.H, C);
+    const dim3 grid = pixels(g.W, g.H, sets);
     with_bool(init, [&](auto I) {
         with_bool(cons != nullptr, [&](auto F) {
-            hipLaunchKernelGGL((k_pco_rhs<decltype(I)::value, decltype(F)::value>), grid, dim3(kBlock), 0, s, b, x, g, op, plane, 4 * plane, cons,
-                               3 * plane, gx, gy, f, v, cons ? has : has & 7);
+            hipLaunchKernelGGL((k_weighted_rhs<decltype(I)::value, decltype(F)::value>), grid, dim3(kBlock), 0, s, b, x, g, op, plane, 4 * plane,
+                               cons, 3 * plane, gx, gy, f, v, cons ? has : has & 7, C / sets);
         });
     });
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 }
 
-int ccp::pco_coarsen(hipStream_t s, int C, const MgLevel &lv, long fs, const double *lam, long ls, const MgLevel &cv, double *d, double *we,
-                     double *ws, double *lam_c, long cstride, double edge)
+int ccp::weighted_coarsen(hipStream_t s, int sets, const MgLevel &lv, long fs, const double *lam, long ls, const MgLevel &cv, double *d,
+                          double *we, double *ws, double *lam_c, long cstride, double edge)
 {
-    hipLaunchKernelGGL(k_pco_coarsen, pixels(cv.W, cv.H, C), dim3(kBlock), 0, s, lv, fs, lam, ls, cv, d, we, ws, lam_c, cstride, edge);
+    hipLaunchKernelGGL(k_weighted_coarsen, pixels(cv.W, cv.H, sets), dim3(kBlock), 0, s, lv, fs, lam, ls, cv, d, we, ws, lam_c, cstride, edge);
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 }

@@ -900,7 +900,8 @@ int ccp_grid_weighted_adjoint_device(ccp_grid *g, const ccp_adjoint_inputs *in, 
  * an H x W array is passed that way); fixed: U8, F32 or F64, same shape, or NULL.  NULL views keep their defaults:
  * weights 1, lambda 0, no fixed pixels.
  *
- * All channels are formed and validated in one launch (k_pco_coef / k_pco_coef_fixed, ccp_grid_pco.hpp); the call
+ * All channels are formed and validated in one launch (k_weighted_coef / k_weighted_coef_fixed, ccp_grid_weighted.hpp: the
+ * kernels that form the shared operator, with the channel on a grid axis); the call
  * synchronises once and reads the verdict plus, when `fixed` is given, every channel's counts.  A weight that is negative,
  * NaN or infinite in ANY channel: CCP_ERR_BAD_ARG, and the handle is left with no operator.  Views are checked as in every
  * _device call, with the extent `channels` along c (a view too short for it: CCP_ERR_BAD_ARG before anything is enqueued).
@@ -909,10 +910,10 @@ int ccp_grid_weighted_adjoint_device(ccp_grid *g, const ccp_adjoint_inputs *in, 
  *
  * While a per-channel operator is installed:
  *   ccp_grid_assemble_weighted_rhs[_device], _constrained_rhs[_device]: channel c's b (and x at its fixed pixels, or with
- *       init) from channel c's weights, lambda and fixed set; all channels in one launch (k_pco_rhs).
+ *       init) from channel c's weights, lambda and fixed set; all channels in one launch (k_weighted_rhs).
  *   ccp_grid_b_from_x, ccp_grid_residual_norm2: channel c's operator (one launch per channel).
  *   ccp_grid_mg_apply, ccp_grid_mg_conjugate_gradient: every channel with its own hierarchy (all channels' coarse levels
- *       are formed by one launch per level, k_pco_coarsen).
+ *       are formed by one launch per level, k_weighted_coarsen).
  *   ccp_grid_mg_level, ccp_grid_constraint_info: channel 0; their _channel forms: any channel (on a shared operator every
  *       channel reports the shared one).
  *   ccp_grid_adjoint_begin_device: channel c's free / live set.

@@ -1,7 +1,7 @@
 """Test-side expectations of the rescaled hierarchy of weighted grid handles (include/ccp_gs.h,
 CCP_MG_HIERARCHY_RESCALED), NOT product code.
 
-A numpy restatement of k_mg_coarsen_weighted with the edge factor 0.5 and of the V-cycle with the unscaled coarse
+A numpy restatement of k_weighted_coarsen with the edge factor 0.5 and of the V-cycle with the unscaled coarse
 correction, in the device's operation order (as weighted_helpers.py and mg_helpers.py, which this file imports):
 
 * level 0 is weighted_helpers' level 0 (d, we, ws, lam), unchanged;
@@ -18,7 +18,7 @@ import weighted_helpers as wh
 
 
 def coarsen(level):
-    """k_mg_coarsen_weighted with edge = 0.5: the edge weights halved, lam summed."""
+    """k_weighted_coarsen with edge = 0.5: the edge weights halved, lam summed."""
     lam, we, ws = (mg._pad_even(a) for a in (level.lam, level.we, level.ws))
     wsp = np.zeros((lam.shape[0] + 1, lam.shape[1]))
     wsp[1:, :] = ws

@@ -21,7 +21,7 @@ def test_kernel_bodies_on_the_host_under_sanitizers(tmp_path):
     shutil.copy(os.path.join(csrc, "ccp_grid_adjoint.hpp"), d)
     shutil.copy(os.path.join(ROOT, "tests", "cpp", "adjoint_host_check.cpp"), d)
     # the real kBlock and w_at, as text: the host build restates neither
-    common, weighted = open(os.path.join(csrc, "ccp_common.hpp")).read(), open(os.path.join(csrc, "ccp_grid_weighted.hpp")).read()
+    common, weighted = open(os.path.join(csrc, "ccp_common.hpp")).read(), open(os.path.join(csrc, "ccp_grid_stencil.hpp")).read()
     parts = [re.search(r"^constexpr int kBlock = \d+;", common, re.M),
              re.search(r"^__host__ __device__ __forceinline__ long w_at\(.*?^\}", weighted, re.M | re.S)]
     assert all(parts), [bool(m) for m in parts]

@@ -18,6 +18,7 @@ import scipy.sparse.linalg as sla
 import torch
 
 import constrained_helpers as ch
+import per_channel_helpers as pch
 import test_gpu_weighted as tgw
 import weighted_helpers as wh
 from coursecomputationalphotography_amd import capi
@@ -220,6 +221,61 @@ def test_device_twins_equal_host_twins(W, H, Cn):
                 torch.cuda.current_stream().synchronize()
                 states_equal(state(d), want[init], (mname, vname, init))
     d.close()
+
+
+RHS_DTYPES = (None, "u8", "f32", "f64")
+
+
+@pytest.mark.parametrize("per_channel", [False, True], ids=["shared", "per_channel"])
+@pytest.mark.parametrize("W,H", [(9, 7), (257, 5)])        # odd both ways; a second block in x that holds one pixel
+def test_every_dtype_pair_of_f_and_values(W, H, per_channel):
+    """The dtypes of f and of values are run-time fields of the right-hand-side kernel's views: every pair from
+    {absent, u8, f32, f64}^2 with gx, gy present, with and without init, on a shared operator with a random mask and on
+    one operator per channel with a mask per channel.  f and values are integers in [0, 255], so every dtype carries
+    the same numbers and one reference per (f present, values present, init) serves all pairs: b and x bit for bit."""
+    Cn = 3
+    gx, gy = field(W, H, Cn, 1), field(W, H, Cn, 2)
+    f8 = rng(3).integers(0, 256, (H, W, Cn), dtype=np.uint8)
+    v8 = rng(4).integers(0, 256, (H, W, Cn), dtype=np.uint8)
+    x0 = [rng(6 + c).uniform(-9, 9, (H, W)) for c in range(Cn)]
+    zero = np.zeros((H, W, Cn), np.float32)
+    g = capi.Grid(W, H, Cn, weighted=True)
+    if per_channel:
+        ws = [random_weights(W, H, 80 + W + c) for c in range(Cn)]
+        wx, wy, lam = (np.stack([w[i] for w in ws], axis=-1) for i in range(3))
+        fixed = np.stack([random_fixed(W, H, 9 + W + c) for c in range(Cn)], axis=-1)
+        assert all(fixed[..., c].any() for c in range(Cn))
+        g.set_weights_per_channel_tensor(*[torch.from_numpy(a).to(DEV) for a in (wx, wy, lam, fixed)])
+        lv = [pch.channel_levels((wx, wy, lam, fixed), c)[0] for c in range(Cn)]
+    else:
+        wx, wy, lam = random_weights(W, H, 77 + W)
+        fixed = random_fixed(W, H, 5 + W)
+        g.set_weights_tensor(*[torch.from_numpy(a).to(DEV) for a in (wx, wy, lam)], fixed=torch.from_numpy(fixed).to(DEV))
+        lv = [ch.level0(W, H, wx, wy, lam, fixed)] * Cn
+    want = {}
+    for hf in (False, True):
+        for hv in (False, True):
+            ins = (gx, gy, f8 if hf else zero, v8 if hv else zero)            # an absent input reads 0
+            b = [pch.channel_rhs([lv[c]], ins, c) if per_channel else ch.rhs(lv[c], gx[..., c], gy[..., c], ins[2][..., c], ins[3][..., c])
+                 for c in range(Cn)]
+            for init in (False, True):
+                want[hf, hv, init] = (b, [ch.x_after(lv[c], x0[c], ins[2][..., c], ins[3][..., c], init) for c in range(Cn)])
+    tgx, tgy = torch.from_numpy(gx).to(DEV), torch.from_numpy(gy).to(DEV)
+    to = {None: lambda a: None, "u8": lambda a: torch.from_numpy(a).to(DEV), "f32": lambda a: torch.from_numpy(a).to(DEV).to(torch.float32),
+          "f64": lambda a: torch.from_numpy(a).to(DEV).to(torch.float64)}
+    for fd in RHS_DTYPES:
+        for vd in RHS_DTYPES:
+            for init in (False, True):
+                for c in range(Cn):
+                    g.set_x(x0[c], c)
+                    g.set_b(np.full((H, W), 7.0), c)
+                g.assemble_constrained_rhs_tensor(tgx, tgy, to[fd](f8), to[vd](v8), init_x=init)
+                torch.cuda.current_stream().synchronize()
+                b, x = want[fd is not None, vd is not None, init]
+                for c in range(Cn):
+                    assert np.array_equal(g.get_b(c), b[c]), ("b", fd, vd, init, c)
+                    assert np.array_equal(g.get_x(c), x[c]), ("x", fd, vd, init, c)
+    g.close()
 
 
 def test_broadcast_mask_and_values():

@@ -338,7 +338,7 @@ def test_switching_between_the_shared_and_the_per_channel_operator():
 
 
 # ---- 7. refusals ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("with_mask", [False, True])               # k_pco_coef's verdict and k_pco_coef_fixed's
+@pytest.mark.parametrize("with_mask", [False, True])               # k_weighted_coef's verdict and k_weighted_coef_fixed's
 @pytest.mark.parametrize("bad", [float("nan"), -1.0, float("inf")])
 @pytest.mark.parametrize("which", [0, 1, 2])
 def test_a_bad_weight_in_one_channel_only(which, bad, with_mask):

@@ -44,7 +44,7 @@ def notes(tmp_path_factory):
 # (kernel name fragment, instantiations expected at least)
 KERNELS = [("k_io_scatter", 12), ("k_io_gather", 6), ("k_io_label_check", 1)]
 VIEW_KERNELS = ["k_assemble_rhs", "k_assemble_from_images", "k_store_u8", "k_load_u8", "k_blend_field_rhs",
-                "k_blend_clone_rhs", "k_blend_composite", "k_weighted_rhs"]
+                "k_blend_clone_rhs", "k_blend_composite"]
 
 
 def _named(notes, frag):

@@ -1,7 +1,8 @@
 """CPU: the multigrid kernels after the correction scale and the coarsening's edge factor became kernel arguments
 (csrc/ccp_grid_mg.hpp; CCP_MG_HIERARCHY_RESCALED), in the BUILT gfx950 code object: every k_mg_* kernel still has no
 VGPR/SGPR spills and no scratch, k_mg_tail's static LDS is still exactly its five arrays of kMgTailCells doubles, and
-k_mg_coarsen_weighted is there once (the edge factor is an argument, not a template parameter)."""
+the weighted coarsening (k_weighted_coarsen, which serves the shared operator and the per-channel ones) is there once (the
+edge factor is an argument, not a template parameter)."""
 import os
 import re
 import shutil
@@ -28,13 +29,13 @@ def mg_kernels(tmp_path_factory):
         notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", o], check=True, capture_output=True, text=True).stdout
         for block in notes.split("  - .agpr_count")[1:]:
             name = re.search(r"\.name:\s+(\S+)", block)
-            if name and "k_mg_" in name.group(1):
+            if name and ("k_mg_" in name.group(1) or "k_weighted_coarsen" in name.group(1)):
                 kernels[name.group(1)] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", block, re.M)}
     return kernels
 
 
 def test_kernels_present(mg_kernels):
-    assert sum(1 for n in mg_kernels if "k_mg_coarsen_weighted" in n) == 1
+    assert sum(1 for n in mg_kernels if "k_weighted_coarsen" in n) == 1
     assert sum(1 for n in mg_kernels if "k_mg_tail" in n) == 1
     # k_mg_tile: three operator kinds x (pre, post)
     assert sum(1 for n in mg_kernels if "k_mg_tile" in n) == 6

@@ -86,7 +86,7 @@ class Coarse(mg.Coarse):
 
 
 def coarsen(level):
-    """The cancellation-free Galerkin coarsening (k_mg_coarsen_weighted)."""
+    """The cancellation-free Galerkin coarsening (k_weighted_coarsen)."""
     H, W = level.d.shape
     lam, we, ws = (mg._pad_even(a) for a in (level.lam, level.we, level.ws))
     # one more row / column of zeros above and to the left: the edges that enter an aggregate from the north / west
