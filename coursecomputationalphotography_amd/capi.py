@@ -49,6 +49,22 @@ def mg_smoother_value(kind):
     if int(kind) not in MG_SMOOTHERS.values():
         raise ValueError(f"smoother must be one of {sorted(MG_SMOOTHERS.values())}, not {kind!r}")
     return int(kind)
+
+
+MG_NULLSPACES = {"none": 0, "constant": 1}
+
+
+def mg_nullspace_value(kind):
+    """The CCP_MG_NULLSPACE_* integer of "none" / "constant" (or of an integer of MG_NULLSPACES): ValueError otherwise."""
+    if isinstance(kind, str):
+        if kind not in MG_NULLSPACES:
+            raise ValueError(f"nullspace must be one of {sorted(MG_NULLSPACES)}, not {kind!r}")
+        return MG_NULLSPACES[kind]
+    if int(kind) not in MG_NULLSPACES.values():
+        raise ValueError(f"nullspace must be one of {sorted(MG_NULLSPACES.values())}, not {kind!r}")
+    return int(kind)
+
+
 ORDER_LEXICOGRAPHIC = 0
 ORDER_MULTICOLOUR = 1
 CLONE_IMPORT = 0
@@ -67,6 +83,7 @@ ABI_SYMBOLS = (
     "ccp_grid_mg_set_hierarchy", "ccp_grid_mg_get_hierarchy", "ccp_grid_mg_set_precision", "ccp_grid_mg_get_precision",
     "ccp_grid_mg_set_channels", "ccp_grid_mg_get_channels", "ccp_debug_mgb_tile_lds",
     "ccp_grid_mg_set_smoother", "ccp_grid_mg_get_smoother",
+    "ccp_grid_mg_set_nullspace", "ccp_grid_mg_get_nullspace", "ccp_grid_mg_nullspace_info",
     "ccp_grid_residual_norm2", "ccp_grid_abs_sum", "ccp_grid_assemble_rhs", "ccp_grid_assemble_from_images", "ccp_grid_store_u8",
     "ccp_grid_set_x_u8", "ccp_grid_assemble_region_rhs", "ccp_grid_assemble_clone", "ccp_grid_store_u8_composite",
     "ccp_grid_last_timing", "ccp_grid_region_begin", "ccp_grid_region_end",
@@ -245,6 +262,9 @@ def load() -> C.CDLL:
     L.ccp_grid_mg_get_channels.argtypes = [vp, C.POINTER(i32)]
     L.ccp_grid_mg_set_smoother.argtypes = [vp, i32]
     L.ccp_grid_mg_get_smoother.argtypes = [vp, C.POINTER(i32)]
+    L.ccp_grid_mg_set_nullspace.argtypes = [vp, i32]
+    L.ccp_grid_mg_get_nullspace.argtypes = [vp, C.POINTER(i32)]
+    L.ccp_grid_mg_nullspace_info.argtypes = [vp, i32, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int64)]
     L.ccp_debug_mgb_tile_lds.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.ccp_csr_apply_to_vector.argtypes = [vp, vp, vp]
     L.ccp_csr_residual_norm2.argtypes = [vp, vp, vp, C.POINTER(dbl), C.POINTER(dbl)]
@@ -806,6 +826,26 @@ class Grid:
         value = C.c_int32()
         check(self.L.ccp_grid_mg_get_smoother(self.h, C.byref(value)), "ccp_grid_mg_get_smoother")
         return next(name for name, v in MG_SMOOTHERS.items() if v == value.value)
+
+    def mg_set_nullspace(self, kind):
+        """The null space the multigrid PCG accounts for (weighted handles): "none" (the default) or "constant" -- a
+        floating operator (lambda = 0 everywhere, no fixed pixel, every in-canvas edge weight > 0) is solved on the
+        mean-free vectors, and x keeps the mean it came with; anything else is refused at the solve, as are batched
+        channels and the line smoother on a canvas whose hierarchy has a line-smoothed level (level 0, or a coarse level
+        with a side > 32) of one row or one column -- or the integers of MG_NULLSPACES."""
+        check(self.L.ccp_grid_mg_set_nullspace(self.h, mg_nullspace_value(kind)), "ccp_grid_mg_set_nullspace")
+
+    def mg_get_nullspace(self):
+        """The handle's null-space mode: "none" or "constant"."""
+        value = C.c_int32()
+        check(self.L.ccp_grid_mg_get_nullspace(self.h, C.byref(value)), "ccp_grid_mg_get_nullspace")
+        return next(name for name, v in MG_NULLSPACES.items() if v == value.value)
+
+    def mg_nullspace_info(self, channel: int = 0):
+        """(mean(b), mean of the returned x, W * H) of the last "constant"-mode solve of channel `channel`."""
+        bm, xm, n = C.c_double(), C.c_double(), C.c_int64()
+        check(self.L.ccp_grid_mg_nullspace_info(self.h, channel, C.byref(bm), C.byref(xm), C.byref(n)), "ccp_grid_mg_nullspace_info")
+        return bm.value, xm.value, n.value
 
     def mg_levels(self, channel: int = 0):
         """The multigrid hierarchy: one (diag, w_east, w_south) triple of H_k x W_k arrays per level, level 0 first.

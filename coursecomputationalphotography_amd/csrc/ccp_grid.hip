@@ -160,6 +160,7 @@ struct ccp_grid {
     int mg_channels = CCP_MG_CHANNELS_SEQUENTIAL;   // ccp_grid_mg_set_channels (survives what mg_precision survives, and set_precision)
     int mg_smoother = CCP_MG_SMOOTHER_POINT;   // ccp_grid_mg_set_smoother (survives what mg_channels survives, and set_channels)
     int mg_precision = CCP_MG_PRECISION_F64;   // ccp_grid_mg_set_precision (survives set_weights, set_mask and set_hierarchy)
+    MgNullspace mg_nullspace;                  // ccp_grid_mg_set_nullspace (the value survives what mg_smoother survives; the rest goes with the operator)
 };
 
 namespace {
@@ -1296,6 +1297,7 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     v->precision = g->mg_precision;
     v->channels_mode = g->mg_channels;
     v->smoother = g->mg_smoother;
+    v->ns = &g->mg_nullspace;
     v->stream = g->stream;
     v->cache = &g->mg;
     v->comm = g->comm;
@@ -1335,6 +1337,14 @@ int ccp::grid_mg_smoother_slot(ccp_grid *g, int **kind, MgHierarchy ***cache)
     CCP_TRY(bind(g));
     *kind = &g->mg_smoother;
     *cache = &g->mg;
+    return CCP_OK;
+}
+
+int ccp::grid_mg_nullspace_slot(ccp_grid *g, bool *weighted, MgNullspace **ns)
+{
+    CCP_TRY(bind(g));
+    *weighted = g->weighted;
+    *ns = &g->mg_nullspace;
     return CCP_OK;
 }
 
@@ -3304,6 +3314,7 @@ void drop_operator(ccp_grid *g)
     g->mg = nullptr;
     g->has_op = g->has_fixed = false;
     g->per_channel = false;
+    g->mg_nullspace.forget();
 }
 
 // wop for `sets` operators (1: the shared one; channels: one per channel), pads zero; what it held is gone

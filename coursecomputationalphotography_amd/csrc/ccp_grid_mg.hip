@@ -4,6 +4,7 @@
 #include "ccp_grid_mgs.hpp"
 #include "ccp_grid_mgb.hpp"
 #include "ccp_grid_mgl.hpp"
+#include "ccp_grid_mgn.hpp"
 #include "ccp_grid_weighted_api.hpp"
 #include "ccp_comm.hpp"
 
@@ -96,6 +97,11 @@ struct MgHierarchy {
     int smoother = CCP_MG_SMOOTHER_POINT;
     long lplane = 0;
     DevBuf<double> lwork;
+    // CCP_MG_NULLSPACE_CONSTANT (ccp_grid_mgn.hpp), made at the first call in that mode: the census counts (one word per
+    // operator), the solve's device scalars and the partial sums of its three-sum reduction (3 x 2,048)
+    DevBuf<unsigned> nscount;
+    DevBuf<MgnState> nsstate;        // one per channel: read back once, after the last channel's solve
+    DevBuf<double> nspart;
     // one operator (opC == 1) only: 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda (lam_slot).  The one-block code, which may see
     // opC > 1, asks coef() for a coefficient plane and vec() for a vector; the row-block code (never weighted) uses arr().
     double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }
@@ -725,7 +731,7 @@ int pcg_loop(const Steps &S, MgHierarchy &h, CgState *host, int C, int max_itera
     CCP_TRY(S.precondition());                                           // z = M r
     S.dot();
     CCP_TRY(S.set_rlen());                                               // rlen = r'z
-    CCP_HIP(hipMemcpyAsync(S.p, S.z, sizeof(double) * S.len, hipMemcpyDeviceToDevice, s));   // p = z
+    CCP_TRY(S.start_direction());                                        // p = z
     CCP_HIP(hipGetLastError());
     CCP_TRY(read_back());
     int issued = 0;
@@ -747,6 +753,7 @@ int pcg_loop(const Steps &S, MgHierarchy &h, CgState *host, int C, int max_itera
         CCP_TRY(read_back());
         active = any_active();
     }
+    CCP_TRY(S.finish());                                                 // (nothing, but in CCP_MG_NULLSPACE_CONSTANT mode)
     CCP_HIP(hipEventRecord(h.ev1, s));
     CCP_TRY(read_back());
     if (report) {
@@ -788,6 +795,13 @@ struct PcgArgs {
         r = w.r.p + off, z = w.z.p + off, p = w.p.p + off, ap = w.ap.p + off;
         part = w.partial.p, ps = w.ps, st = w.state.p;
     }
+    // the first direction, p = z, and what a mode still owes x when the loop ends
+    int start_direction() const
+    {
+        CCP_HIP(hipMemcpyAsync(p, z, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
+        return CCP_OK;
+    }
+    int finish() const { return CCP_OK; }
 };
 
 // One channel of a one-block handle: k_cg_* / k_mg_*.  The caller sets b and x per channel.
@@ -819,6 +833,44 @@ struct ChannelSteps : PcgArgs {
     int set_rlen() const { return set_rlen(part, blocks); }
     int alpha() const { return alpha(part, apply_blocks); }
     int beta() const { return beta(part, blocks); }
+};
+
+// One channel of a weighted handle in CCP_MG_NULLSPACE_CONSTANT mode (ccp_grid_mgn.hpp; the loop: include/ccp_gs.h): the
+// product, the V-cycle, the update and the checks are ChannelSteps'; the sums carry sum(z) and sum(r) along and the
+// directions subtract mean(z).
+struct NullspaceSteps : ChannelSteps {
+    MgnLay lay;
+    double pixels;                   // W H
+    MgnState *ns;
+    double *npart;                   // 3 x `blocks` partial sums
+    void means(const double *a, const double *b2, int which) const
+    {
+        hipLaunchKernelGGL(k_mgn_sums, dim3(blocks), dim3(kBlock), 0, s, a, b2, lay, npart);
+        hipLaunchKernelGGL(k_mgn_means, dim3(1), dim3(kBlock), 0, s, static_cast<const double *>(npart), blocks, pixels, which, ns);
+    }
+    void shift() const { hipLaunchKernelGGL(k_mgn_shift, dim3(blocks), dim3(kBlock), 0, s, x, lay, static_cast<const MgnState *>(ns)); }
+    int residual() const                                                 // bm, m0; r = A x
+    {
+        means(b, x, kMgnStart);
+        return apply(x, r, false);
+    }
+    void init() const { hipLaunchKernelGGL(k_mgn_init, dim3(blocks), dim3(kBlock), 0, s, b, r, lay, static_cast<const MgnState *>(ns), part); }
+    void dot() const { hipLaunchKernelGGL(k_mgn_dot, dim3(blocks), dim3(kBlock), 0, s, r, z, n, npart, st); }
+    int set_rlen() const { hipLaunchKernelGGL(k_mgn_rz<true>, dim3(1), dim3(kBlock), 0, s, static_cast<const double *>(npart), blocks, pixels, st, ns); return CCP_OK; }
+    int beta() const { hipLaunchKernelGGL(k_mgn_rz<false>, dim3(1), dim3(kBlock), 0, s, static_cast<const double *>(npart), blocks, pixels, st, ns); return CCP_OK; }
+    void direction() const { hipLaunchKernelGGL(k_mgn_direction<false>, dim3(blocks), dim3(kBlock), 0, s, p, z, lay, st, static_cast<const MgnState *>(ns)); }
+    int start_direction() const
+    {
+        hipLaunchKernelGGL(k_mgn_direction<true>, dim3(blocks), dim3(kBlock), 0, s, p, z, lay, st, static_cast<const MgnState *>(ns));
+        return CCP_OK;
+    }
+    int finish() const                                                   // x += m0 - mean(x); the mean it then has
+    {
+        means(x, nullptr, kMgnClose);
+        shift();
+        means(x, nullptr, kMgnReport);
+        return CCP_OK;
+    }
 };
 
 // All C channels of a one-block handle (n doubles apart in every vector): the sequential launches, each for all channels
@@ -1135,6 +1187,55 @@ int check_handle(ccp_grid *g, GridMgView *v)
     return CCP_OK;
 }
 
+// ---- CCP_MG_NULLSPACE_CONSTANT (ccp_grid_mgn.hpp) ----------------------------------------------------------------------
+bool constant_mode(const GridMgView &v) { return v.weighted && v.ns->kind == CCP_MG_NULLSPACE_CONSTANT; }
+
+// What the mode does not serve, before anything is built
+int nullspace_check(const GridMgView &v)
+{
+    if (!constant_mode(v)) return CCP_OK;
+    if (v.channels_mode != CCP_MG_CHANNELS_SEQUENTIAL) return CCP_ERR_UNSUPPORTED;
+    // A line-smoothed level of one row or one column: its one line along that direction has no neighbour across and no
+    // lambda (the coarse operators of a floating operator are floating too), so the exact line solve would be a solve of
+    // the singular operator itself.  Lines run on level 0 and on every coarse level above the tail, the levels with a side
+    // > kMgTailSide (build): 33x1 at level 0, 129x2 at its level 1 (65x1), 2048x32 at its level 5 (64x1).
+    if (v.smoother == CCP_MG_SMOOTHER_LINE)
+        for (int k = 0, W = v.geom.W, H = v.geom.H; k == 0 || W > kMgTailSide || H > kMgTailSide; ++k, W = (W + 1) / 2, H = (H + 1) / 2)
+            if (W == 1 || H == 1) return CCP_ERR_UNSUPPORTED;
+    return CCP_OK;
+}
+
+// The mode's buffers, once per hierarchy, and the census of the handle's operators, once per installed operator (one
+// read-back): CCP_ERR_UNSUPPORTED unless every one is floating
+int nullspace_ready(const GridMgView &v, MgHierarchy &h)
+{
+    if (!constant_mode(v)) return CCP_OK;
+    if (!h.nspart.p) {
+        CCP_TRY(h.nscount.alloc((size_t)kMaxChannels));
+        CCP_TRY(h.nsstate.alloc((size_t)kMaxChannels));
+        CCP_TRY(h.nspart.alloc((size_t)(3 * 2048)));
+    }
+    MgNullspace &ns = *v.ns;
+    if (ns.floating < 0) {
+        const int sets = v.op_channels;
+        unsigned bad[kMaxChannels] = {};
+        CCP_HIP(hipMemsetAsync(h.nscount.p, 0, sizeof(unsigned) * kMaxChannels, v.stream));
+        dim3 grid = cells_grid(v.geom.W, v.geom.H);
+        grid.z = (unsigned)sets;
+        hipLaunchKernelGGL(k_mgn_census, grid, dim3(kBlock), 0, v.stream, v.wd, v.op_stride, (long)v.geom.ch_stride, v.geom.W, v.geom.H,
+                           (long)v.geom.pitch, h.nscount.p);
+        CCP_HIP(hipGetLastError());
+        CCP_HIP(hipMemcpyAsync(bad, h.nscount.p, sizeof(unsigned) * (size_t)sets, hipMemcpyDeviceToHost, v.stream));
+        CCP_HIP(hipStreamSynchronize(v.stream));
+        ns.floating = 1;
+        for (int k = 0; k < sets; ++k)
+            if (bad[k]) ns.floating = 0;
+    }
+    return ns.floating ? CCP_OK : CCP_ERR_UNSUPPORTED;
+}
+
+MgnLay nullspace_layout(const GridMgView &v) { return MgnLay{v.geom.W, 2 * v.geom.H, (int)v.geom.pitch}; }
+
 }  // namespace
 
 extern "C" {
@@ -1148,11 +1249,31 @@ try {
     const bool batched = v.channels_mode == CCP_MG_CHANNELS_BATCHED;
     if (batched && v.precision == CCP_MG_PRECISION_F32) return CCP_ERR_UNSUPPORTED;
     CCP_TRY(line_check(v));
+    CCP_TRY(nullspace_check(v));
     MgHierarchy *h = nullptr;
     CCP_TRY(hierarchy(v, &h));
     if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
     CCP_TRY(line_planes(v, *h));
+    CCP_TRY(nullspace_ready(v, *h));
     const long n = v.geom.ch_stride;
+    if (constant_mode(v)) {                                        // x := z - mean(z), z = M (b - mean(b))
+        NullspaceSteps S{};
+        S.h = h, S.s = v.stream, S.nu = nu;
+        S.shape(v.geom.W, v.geom.H, n);
+        S.lay = nullspace_layout(v), S.pixels = (double)v.geom.W * (double)v.geom.H;
+        S.ns = h->nsstate.p, S.npart = h->nspart.p;
+        CCP_TRY(h->seq.alloc(1, n, 0, S.s));
+        for (int ch = 0; ch < v.channels; ++ch) {
+            S.b = v.b + ch * n, S.x = v.x + ch * n;
+            S.means(S.b, nullptr, kMgnStart);                      // (m0 = 0)
+            hipLaunchKernelGGL(k_mgn_center, dim3(S.blocks), dim3(kBlock), 0, S.s, S.b, h->seq.r.p, S.lay, static_cast<const MgnState *>(S.ns));
+            CCP_TRY(vcycle(*h, S.s, h->seq.r.p, S.x, nu, nullptr, ch));
+            CCP_TRY(S.finish());
+        }
+        CCP_HIP(hipGetLastError());
+        CCP_HIP(hipStreamSynchronize(v.stream));
+        return CCP_OK;
+    }
     if (batched) {
         CCP_TRY(batched_levels(v, *h));
         CCP_TRY(vcycle_batched(*h, v.stream, v.channels, n, v.b, v.x, nu, nullptr));
@@ -1267,6 +1388,40 @@ try {
     return CCP_OK;
 } CCP_ABI_CATCH
 
+int ccp_grid_mg_set_nullspace(ccp_grid *g, int32_t kind)
+try {
+    bool weighted = false;
+    MgNullspace *ns = nullptr;
+    CCP_TRY(grid_mg_nullspace_slot(g, &weighted, &ns));
+    if (kind != CCP_MG_NULLSPACE_NONE && kind != CCP_MG_NULLSPACE_CONSTANT) return CCP_ERR_BAD_ARG;
+    if (!weighted) return CCP_ERR_UNSUPPORTED;
+    ns->kind = kind;                                               // (the hierarchy and the PCG vectors serve both modes)
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_get_nullspace(ccp_grid *g, int32_t *kind)
+try {
+    bool weighted = false;
+    MgNullspace *ns = nullptr;
+    CCP_TRY(grid_mg_nullspace_slot(g, &weighted, &ns));
+    if (!kind) return CCP_ERR_BAD_ARG;
+    *kind = weighted ? ns->kind : CCP_MG_NULLSPACE_NONE;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_nullspace_info(ccp_grid *g, int32_t channel, double *b_mean, double *x_mean, int64_t *pixels)
+try {
+    GridMgView v{};
+    CCP_TRY(grid_mg_view(g, &v));
+    if (channel < 0 || channel >= v.channels) return CCP_ERR_BAD_ARG;
+    if (!v.weighted) return CCP_ERR_UNSUPPORTED;
+    if (!v.ns->solved[channel]) return CCP_ERR_STATE;
+    if (b_mean) *b_mean = v.ns->b_mean[channel];
+    if (x_mean) *x_mean = v.ns->x_mean[channel];
+    if (pixels) *pixels = (int64_t)v.geom.W * (int64_t)v.geom.H;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
 int ccp_debug_mgb_tile_lds(int32_t level_kind, int32_t smoothing_sweeps, int32_t *bytes, int32_t *threads)
 try {
     if (level_kind < kMgSolve || level_kind > kMgCoarse || smoothing_sweeps < 1 || smoothing_sweeps > 4) return CCP_ERR_BAD_ARG;
@@ -1338,12 +1493,41 @@ try {
     const bool batched = v.channels_mode == CCP_MG_CHANNELS_BATCHED;
     if (batched && v.precision == CCP_MG_PRECISION_F32) return CCP_ERR_UNSUPPORTED;
     CCP_TRY(line_check(v));
+    CCP_TRY(nullspace_check(v));
     MgHierarchy *h = nullptr;
     CCP_TRY(hierarchy(v, &h));
     CCP_TRY(line_planes(v, *h));
     if (batched) return pcg_batched(v, *h, epsilon, max_iteration, nu, report);
     if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
+    CCP_TRY(nullspace_ready(v, *h));
     const long n = v.geom.ch_stride;                               // one channel incl. pads (pads stay 0 in every vector)
+    if (constant_mode(v)) {
+        NullspaceSteps S{};
+        S.h = h, S.s = v.stream, S.epsilon = epsilon, S.nu = nu;
+        S.shape(v.geom.W, v.geom.H, n);
+        S.lay = nullspace_layout(v), S.pixels = (double)v.geom.W * (double)v.geom.H;
+        S.ns = h->nsstate.p, S.npart = h->nspart.p;
+        CCP_TRY(h->seq.alloc(1, n, std::max(S.apply_blocks, S.blocks), S.s));
+        S.bind(h->seq, 0);
+        for (int ch = 0; ch < v.channels; ++ch) {
+            S.b = v.b + ch * n;
+            S.x = v.x + ch * n;
+            S.ch = ch;
+            S.ns = h->nsstate.p + ch;
+            v.ns->solved[ch] = false;
+            CgState host;
+            CCP_TRY(pcg_loop(S, *h, &host, 1, max_iteration, report ? report + ch : nullptr));
+        }
+        MgnState means[kMaxChannels] = {};                          // one read-back for all channels, after the last solve
+        CCP_HIP(hipMemcpyAsync(means, h->nsstate.p, sizeof(MgnState) * (size_t)v.channels, hipMemcpyDeviceToHost, S.s));
+        CCP_HIP(hipStreamSynchronize(S.s));
+        for (int ch = 0; ch < v.channels; ++ch) {
+            v.ns->solved[ch] = true;
+            v.ns->b_mean[ch] = means[ch].b_mean;
+            v.ns->x_mean[ch] = means[ch].x_mean;
+        }
+        return CCP_OK;
+    }
     ChannelSteps S{};
     S.h = h, S.s = v.stream, S.epsilon = epsilon, S.nu = nu;
     S.shape(v.geom.W, v.geom.H, n);

@@ -9,6 +9,21 @@ namespace ccp {
 struct MgHierarchy;
 void mg_release(MgHierarchy *h);
 
+// CCP_MG_NULLSPACE_* (ccp_grid_mg_set_nullspace) and what the handle remembers for it: the census verdict of the
+// installed operators (-1: not taken yet, 0: one is not floating, 1: all are) and ccp_grid_mg_nullspace_info's figures of
+// every channel's last CONSTANT-mode solve.  A new operator forgets the verdict and the figures.
+struct MgNullspace {
+    int kind = 0;
+    int floating = -1;
+    bool solved[kMaxChannels] = {};
+    double b_mean[kMaxChannels] = {}, x_mean[kMaxChannels] = {};
+    void forget()
+    {
+        floating = -1;
+        for (bool &s : solved) s = false;
+    }
+};
+
 struct GridMgView {
     Geom geom;
     int channels;
@@ -28,6 +43,7 @@ struct GridMgView {
     int precision;                   // CCP_MG_PRECISION_* (ccp_grid_mg_set_precision)
     int channels_mode;               // CCP_MG_CHANNELS_* (ccp_grid_mg_set_channels)
     int smoother;                    // CCP_MG_SMOOTHER_* (ccp_grid_mg_set_smoother)
+    MgNullspace *ns;                 // ccp_grid_mg_set_nullspace's value, the census verdict and the last solves' means
     hipStream_t stream;
     MgHierarchy **cache;             // the handle's cached hierarchy (built on first use, dropped with the mask and the partition)
     // row blocks (ccp_grid_attach_comm): the communicator, every rank's first image row then the image height
@@ -45,6 +61,8 @@ int grid_mg_precision_slot(ccp_grid *g, int **precision, MgHierarchy ***cache, b
 int grid_mg_channels_slot(ccp_grid *g, int **mode, MgHierarchy ***cache);
 // the handle's smoother (ccp_grid_mg_set_smoother / _get_smoother)
 int grid_mg_smoother_slot(ccp_grid *g, int **kind, MgHierarchy ***cache);
+// the handle's null-space record (ccp_grid_mg_set_nullspace / _get_nullspace) and whether the handle is weighted
+int grid_mg_nullspace_slot(ccp_grid *g, bool *weighted, MgNullspace **ns);
 void grid_mg_halo_stale(ccp_grid *g);   // after a row-block solve: the next sweep refreshes the ghost rows first
 
 }  // namespace ccp

@@ -187,7 +187,7 @@ def _set_operator(g, wx, wy, lam, fixed=None):
 
 
 def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=None, out_dtype=None, epsilon: float = 1e-10,
-                   hierarchy="galerkin", precision="f64", channels="sequential", smoother="point"):
+                   hierarchy="galerkin", precision="f64", channels="sequential", smoother="point", nullspace="none"):
     """Minimise  sum wx (u(x+1,y) - u(x,y) - gx)^2 + sum wy (u(x,y+1) - u(x,y) - gy)^2 + sum data_weight (u - f)^2
     for every channel on a weighted grid handle (CCP_GRID_WEIGHTED), by multigrid-preconditioned CG (at most
     `iterations` iterations to sqrt(r'r) < epsilon) from x = f.  gx, gy: float32 H x W x C tensors or None (zero
@@ -200,6 +200,10 @@ def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=Non
     default) or "batched" (capi.Grid.mg_set_channels: one PCG loop whose launches serve all channels; every channel gets
     the same bits; not together with "f32").  smoother: "point" (the default) or "line" (capi.Grid.mg_set_smoother:
     alternating zebra line relaxation, for strongly anisotropic weights; fp64 and sequential channels only).
+    nullspace: "none" (the default) or "constant" (capi.Grid.mg_set_nullspace): the floating system -- data_weight None or
+    0 everywhere and every in-canvas weight > 0, whose solution is free up to a constant per channel -- is solved on the
+    mean-free vectors and the result keeps the mean of the start vector (f, or 0 without f); sequential channels only;
+    any other operator is refused (capi.CcpError, UNSUPPORTED).  integrate_gradients is the front end for it.
 
     One operator per channel.  If any of wx, wy, data_weight is H x W x C, channel c is solved with channel c's weights
     (H x W arguments beside it serve every channel), and equals, bit for bit, the one-channel call on channel c's slices.
@@ -220,11 +224,67 @@ def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=Non
         g.mg_set_precision(precision)
         g.mg_set_channels(channels)
         g.mg_set_smoother(smoother)
+        g.mg_set_nullspace(nullspace)
         _set_operator(g, _weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev))
         g.assemble_weighted_rhs_tensor(gx, gy, f, init_x=f is not None)
         if f is None:
             g.fill_x(0.0)
         g.mg_conjugate_gradient(epsilon, iterations, 2)
+        if out_dtype == torch.uint8:
+            return g.store_u8_tensor()
+        return g.get_x_tensor(dtype=out_dtype)
+    finally:
+        g.close()
+
+
+def _no_nullspace(nullspace, who):
+    if capi.mg_nullspace_value(nullspace) != capi.MG_NULLSPACES["none"]:
+        raise ValueError(f"{who} does not take nullspace={nullspace!r}: a floating system has no fixed pixel, and the adjoint of "
+                         "a floating solve is not implemented; use weighted_solve or integrate_gradients")
+
+
+def integrate_gradients(gx, gy, wx=None, wy=None, mean=0.0, iterations: int = 200, epsilon: float = 1e-10, out_dtype=None,
+                        hierarchy="galerkin", precision="f64", smoother="point"):
+    """The image whose forward differences are closest to a gradient field: u minimises
+    sum wx (u(x+1,y) - u(x,y) - gx)^2 + sum wy (u(x,y+1) - u(x,y) - gy)^2 per channel over the whole canvas with a free
+    border (pure Neumann), which fixes u up to a constant; the constant is chosen so that mean(u) = `mean`.  gx, gy:
+    float32 H x W x C (or H x W) device tensors, one may be None; wx, wy: H x W (or H x W x C: one operator per channel)
+    float32 / float64 tensors or scalars, every in-canvas weight > 0 (None: 1); mean: a number, or one value per channel (a
+    sequence or a tensor of C entries).  Solved on a weighted grid handle in its "constant" null-space mode
+    (capi.Grid.mg_set_nullspace) by multigrid-preconditioned CG from u = mean: at most `iterations` iterations, to
+    sqrt(r'r) < epsilon * |b| of the channel with the largest |b| (b = -div(w g), the mean of b removed); a field whose b is
+    zero in every channel gives the constant image `mean` without a solve.  smoother="line" is refused on elongated
+    canvases whose hierarchy has a line-smoothed level of one row or one column (capi.Grid.mg_set_nullspace).  Returns a device
+    tensor of gx's shape, float64 unless out_dtype says otherwise (torch.uint8: clamped).  hierarchy, precision, smoother: as
+    weighted_solve's; the channels are solved one after the other."""
+    import torch
+    ref = next((t for t in (gx, gy) if t is not None), None)
+    if ref is None:
+        raise ValueError("integrate_gradients needs at least one of gx, gy")
+    if ref.dim() == 2:
+        u = integrate_gradients(None if gx is None else gx.unsqueeze(-1), None if gy is None else gy.unsqueeze(-1), wx, wy, mean, iterations,
+                                epsilon, out_dtype, hierarchy, precision, smoother)
+        return u[..., 0]
+    out_dtype = torch.float64 if out_dtype is None else out_dtype
+    dev = _device_index(ref)
+    H, W, C = ref.shape
+    device = torch.device("cuda", dev)
+    m = torch.as_tensor(mean, dtype=torch.float64, device=device).reshape(-1)
+    if m.numel() not in (1, C):
+        raise ValueError(f"mean must be a number or have one entry per channel ({C}), not {m.numel()}")
+    g = capi.Grid(W, H, C, device=dev, weighted=True)
+    g.set_stream(torch.cuda.current_stream(device).cuda_stream)
+    try:
+        g.mg_set_hierarchy(hierarchy)
+        g.mg_set_precision(precision)
+        g.mg_set_smoother(smoother)
+        g.mg_set_nullspace("constant")
+        _set_operator(g, _weight(wx, H, W, dev), _weight(wy, H, W, dev), None)
+        g.assemble_weighted_rhs_tensor(gx, gy, None, init_x=False)
+        g.set_x_tensor(m.reshape(1, 1, -1).expand(H, W, C).contiguous())
+        _, bb = g.residual_norm2()
+        if float(bb.max()) > 0.0:                          # b = 0 (a zero field, or every weighted gradient 0): u = mean as it stands
+            g.mg_conjugate_gradient(epsilon * float(bb.max()) ** 0.5, iterations, 0)
         if out_dtype == torch.uint8:
             return g.store_u8_tensor()
         return g.get_x_tensor(dtype=out_dtype)
@@ -266,7 +326,7 @@ def wls_smooth(image, iterations: int, lam: float = 1.0, alpha: float = 1.2, eps
 
 def constrained_solve(gx, gy, f, values, fixed, iterations: int, wx=None, wy=None, data_weight=None, out_dtype=None,
                       epsilon: float = 1e-10, hierarchy="rescaled", precision="f64", channels="sequential",
-                      smoother="point"):
+                      smoother="point", nullspace="none"):
     """weighted_solve with hard constraints: the pixels where `fixed` (an H x W uint8, bool, float32 or float64 tensor) is
     non-zero keep the value `values` prescribes (u8 / float32 / float64 H x W x C, None: 0) and the energy of
     weighted_solve is minimised over the others; edges that leave the canvas are absent, so the free region may touch
@@ -275,8 +335,9 @@ def constrained_solve(gx, gy, f, values, fixed, iterations: int, wx=None, wy=Non
     free pixels, `values` on the fixed ones -- as out_dtype (torch.uint8 by default: clamped).  With data_weight None or
     0 every connected set of free pixels needs a fixed neighbour, or the system is singular there.  precision, channels, smoother: as
     weighted_solve's.  wx, wy, data_weight or fixed given as H x W x C: one operator (and one fixed set) per channel, as
-    in weighted_solve."""
+    in weighted_solve.  nullspace: "none" only (ValueError otherwise: a floating system has no fixed pixel)."""
     import torch
+    _no_nullspace(nullspace, "constrained_solve")
     out_dtype = torch.uint8 if out_dtype is None else out_dtype
     dev = _device_index(fixed)
     H, W = fixed.shape[0], fixed.shape[1]
@@ -319,7 +380,7 @@ def clone_gradients(source, target=None):
 
 
 def seamless_clone_constrained(source, target, mask, iterations: int, mixed: bool = False, data_weight=None, precision="f64",
-                               channels="sequential", smoother="point"):
+                               channels="sequential", smoother="point", nullspace="none"):
     """Seamless cloning (Perez et al. 2003) on a weighted handle with fixed pixels: inside `mask` (H x W, non-zero = region)
     the result follows the gradients of the u8 H x W x C tensor `source` (mixed: the stronger of source's and target's),
     outside it is `target`.  Unlike seamless_clone the region may touch the canvas border (no condition is imposed there)
@@ -327,8 +388,9 @@ def seamless_clone_constrained(source, target, mask, iterations: int, mixed: boo
     source's colours (screened cloning).  The start vector is the target; multigrid-preconditioned CG, at most
     `iterations` iterations (precision: "f64" or "f32", the V-cycle's: capi.Grid.mg_set_precision; channels: "sequential" or
     "batched", capi.Grid.mg_set_channels; smoother: "point" or "line", capi.Grid.mg_set_smoother).  Returns the composite,
-    a u8 H x W x C tensor."""
+    a u8 H x W x C tensor.  nullspace: "none" only (ValueError otherwise)."""
     import torch
+    _no_nullspace(nullspace, "seamless_clone_constrained")
     if source.dim() == 2:
         return seamless_clone_constrained(source.unsqueeze(-1), target.unsqueeze(-1), mask, iterations, mixed, data_weight, precision, channels, smoother)[..., 0]
     dev = _device_index(target)
@@ -437,7 +499,7 @@ _WeightedSolve = None
 
 def weighted_solve_grad(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=None, values=None, fixed=None,
                         epsilon: float = 1e-10, hierarchy="rescaled", precision="f64", channels="sequential", smoother="point",
-                        strict: bool = True):
+                        strict: bool = True, nullspace="none"):
     """weighted_solve / constrained_solve as a differentiable torch function: returns x, a float64 H x W x C tensor (the
     composite: the minimiser on the free pixels, `values` on the fixed ones) with a grad_fn, so that a loss of x can be
     differentiated with respect to gx, gy, f, wx, wy, data_weight and values.  Inputs as constrained_solve's (`fixed` None:
@@ -466,8 +528,11 @@ def weighted_solve_grad(gx, gy, f, iterations: int, wx=None, wy=None, data_weigh
     channels="batched".
 
     strict (the default): a forward or adjoint solve that does not report `converged` within `iterations` raises
-    RuntimeError -- these are the gradients of the converged solution, and an unconverged solve's are not them."""
+    RuntimeError -- these are the gradients of the converged solution, and an unconverged solve's are not them.
+
+    nullspace: "none" only (ValueError otherwise): the adjoint of a floating solve is out of scope."""
     import torch
+    _no_nullspace(nullspace, "weighted_solve_grad")
     ref = next((t for t in (values, f, gx, gy) if t is not None), None)
     if ref is None:
         raise ValueError("weighted_solve_grad needs at least one of gx, gy, f, values")

@@ -267,12 +267,18 @@ enum class Channels { Sequential = CCP_MG_CHANNELS_SEQUENTIAL, Batched = CCP_MG_
 // strongly anisotropic weights (edge-aware smoothing, sparse fixed pixels); the default, Smoother::Point, is red-black
 // Gauss-Seidel.  Not together with Precision::Single or Channels::Batched: that solve throws.
 enum class Smoother { Point = CCP_MG_SMOOTHER_POINT, Line = CCP_MG_SMOOTHER_LINE };
+// nullspace: the null space the solve accounts for (ccp_grid_mg_set_nullspace).  Nullspace::Constant solves the floating
+// system -- lambda null or 0 everywhere, every in-canvas weight > 0: integrating a gradient field over the whole canvas --
+// whose solution is free up to a constant per channel: the result keeps the mean of the start vector (f; 0 without it).
+// Any other operator makes that solve throw, as does Channels::Batched.  The default, Nullspace::None, is the loop as it was.
+enum class Nullspace { None = CCP_MG_NULLSPACE_NONE, Constant = CCP_MG_NULLSPACE_CONSTANT };
 
 inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageView *f, const ImageView *wx, const ImageView *wy,
                           const ImageView *lambda, ImageView &out, int iterations,
                           Solver solver = Solver::MultigridConjugateGradient, int device = 0,
                           Hierarchy hierarchy = Hierarchy::Galerkin, Precision precision = Precision::Double,
-                          Channels channels = Channels::Sequential, Smoother smoother = Smoother::Point)
+                          Channels channels = Channels::Sequential, Smoother smoother = Smoother::Point,
+                          Nullspace nullspace = Nullspace::None)
 {
     if (solver != Solver::MultigridConjugateGradient)
         throw std::invalid_argument("SolveWeighted: only Solver::MultigridConjugateGradient solves a weighted system");
@@ -297,6 +303,7 @@ inline void SolveWeighted(const ImageView *gx, const ImageView *gy, const ImageV
     detail::check(ccp_grid_mg_set_precision(h.g, (int32_t)precision), "ccp_grid_mg_set_precision");
     detail::check(ccp_grid_mg_set_channels(h.g, (int32_t)channels), "ccp_grid_mg_set_channels");
     detail::check(ccp_grid_mg_set_smoother(h.g, (int32_t)smoother), "ccp_grid_mg_set_smoother");
+    detail::check(ccp_grid_mg_set_nullspace(h.g, (int32_t)nullspace), "ccp_grid_mg_set_nullspace");
     detail::check(ccp_grid_set_weights_host(h.g, fp(wx), fp(wy), fp(lambda), (int64_t)wstep), "ccp_grid_set_weights_host");
     const int64_t gstep = gx ? (int64_t)gx->step : gy ? (int64_t)gy->step : 0;
     detail::check(ccp_grid_assemble_weighted_rhs(h.g, fp(gx), fp(gy), gstep, fp(f), f ? (int64_t)f->step : 0, f ? 1 : 0),

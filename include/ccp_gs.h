@@ -509,6 +509,48 @@ int ccp_grid_mg_get_channels(ccp_grid *g, int32_t *mode);
 #define CCP_MG_SMOOTHER_LINE  1   /* alternating zebra line relaxation (weighted handles) */
 int ccp_grid_mg_set_smoother(ccp_grid *g, int32_t kind);
 int ccp_grid_mg_get_smoother(ccp_grid *g, int32_t *kind);
+/* The null space the multigrid PCG of a WEIGHTED handle accounts for, per handle.  NONE, the default, is the loop above,
+ * bit for bit and launch for launch.  CONSTANT solves a FLOATING operator -- lambda = 0 at every pixel, no fixed pixel,
+ * every in-canvas edge weight > 0 (pure Neumann: integrating a gradient field, a fusion with a free border) -- whose
+ * matrix is singular with exactly the constants as its null space: the solve runs on the mean-free vectors and returns
+ * the solution whose mean is the initial guess's mean (with init_x_from_f: the mean of f).  With n = W * H,
+ * mean(v) = (sum of v) / n, every sum by the handle's deterministic reductions (block partials in a fixed order), and
+ * pitch padding never entering a sum or taking a value:
+ *   bm = mean(b);  m0 = mean(x);  r = (b - bm) - A x                      (b itself is not modified)
+ *   stop with 0 iterations if sqrt(r'r) < epsilon
+ *   z = M r;  zm = mean(z);  rz = r'z - zm * sum(r);  p = z - zm
+ *   loop: alpha = rz / p'Ap;  x += alpha p;  r += (-alpha) Ap;  stop if sqrt(r'r) < epsilon
+ *         z = M r;  zm = mean(z);  rz' = r'z - zm * sum(r);  beta = rz' / rz;  p = (z - zm) + beta p
+ *   end:  x += m0 - mean(x)        (on every exit: converged, the iteration cap, 0 iterations)
+ * r'z, sum(z) and sum(r) come from one pass over r and z; zm stays on the device and the direction update reads it there,
+ * so an iteration makes the passes and the host synchronisations of the NONE loop.  iterations, converged and
+ * last_l1_step mean what they mean above, for the projected system: a right-hand side that is not consistent (sum(b) != 0:
+ * a lambda f term, a user's own b, rounding) is solved for its consistent part b - bm.  ccp_grid_mg_apply gives
+ * x := z - mean(z) with z = M (b - bm).
+ * With CONSTANT set, ccp_grid_mg_conjugate_gradient and ccp_grid_mg_apply first require every operator of the handle
+ * (the shared one, or each channel's own) to be floating; a census kernel decides that once per installed operator, at
+ * the first such call (one read-back).  Refused with CCP_ERR_UNSUPPORTED, x and b untouched: an operator that is not
+ * floating (a 1x1 canvas, which has no edge, counts as not floating); CONSTANT with CCP_MG_CHANNELS_BATCHED; CONSTANT with
+ * CCP_MG_SMOOTHER_LINE when a level the V-cycle smooths by lines -- level 0, and every coarse level with a side > 32,
+ * level k being ceil(W / 2^k) x ceil(H / 2^k) -- has one row or one column: 33x1, but also the elongated 129x2 (its level 1
+ * is 65x1), 257x3, 2048x32 (its level 5 is 64x1); 64x2 and 2048x33 are served.  The line along such a level has no
+ * neighbour across and no lambda (the coarse operators of a floating operator are floating too), so the exact line solve
+ * would be a solve of the singular operator itself.  (The _rowblocked calls refuse every weighted handle.)  Served: the
+ * sequential channel mode, both hierarchy kinds, F64 and F32, the point smoother on every canvas and the line smoother on
+ * every other one, shared and per-channel operators.
+ * The setter takes weighted handles only (others: CCP_ERR_UNSUPPORTED); a NULL handle or an unknown kind:
+ * CCP_ERR_BAD_ARG.  Setting the current value does nothing; a change keeps the cached hierarchy, which both modes share.
+ * The value survives ccp_grid_set_weights_* and the other mode setters.  The getter gives NONE on every handle that is
+ * not weighted. */
+#define CCP_MG_NULLSPACE_NONE     0   /* the default: today's loop, bit for bit */
+#define CCP_MG_NULLSPACE_CONSTANT 1   /* floating operator: solve on the mean-free vectors */
+int ccp_grid_mg_set_nullspace(ccp_grid *g, int32_t kind);
+int ccp_grid_mg_get_nullspace(ccp_grid *g, int32_t *kind);
+/* Of the last CONSTANT-mode solve (ccp_grid_mg_conjugate_gradient) of channel `channel`: bm = mean(b), the mean of the x
+ * it returned, and n = W * H.  Any output may be NULL.  CCP_ERR_STATE before such a solve of that channel (a new operator
+ * forgets the last one); not a weighted handle: CCP_ERR_UNSUPPORTED; a NULL handle or a channel out of range:
+ * CCP_ERR_BAD_ARG. */
+int ccp_grid_mg_nullspace_info(ccp_grid *g, int32_t channel, double *b_mean, double *x_mean, int64_t *pixels);
 
 /* Diagnostic (host only, no device needed): the dynamic LDS in bytes and the workgroup size of a BATCHED tile-pass launch
  * on a level of kind `level_kind` -- 0 structured, 1 Dirichlet mask, 2 stored operator (level 0 of a weighted handle and
