@@ -96,6 +96,7 @@ ABI_SYMBOLS = (
     "ccp_grid_adjoint_begin_device", "ccp_grid_weighted_adjoint_device",
     "ccp_grid_set_weights_per_channel_device", "ccp_grid_operator_channels", "ccp_grid_mg_level_channel",
     "ccp_grid_constraint_info_channel",
+    "ccp_grid_mg_prepare", "ccp_grid_mg_conjugate_gradient_enqueue",
     "ccp_grid_set_mask_device", "ccp_mask_erode_cross_device", "ccp_panorama_begin_device", "ccp_panorama_add_device",
     "ccp_panorama_finish_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
@@ -253,6 +254,8 @@ def load() -> C.CDLL:
     L.ccp_grid_conjugate_gradient.argtypes = [vp, dbl, i32, C.POINTER(Report)]
     L.ccp_grid_mg_conjugate_gradient.argtypes = [vp, dbl, i32, i32, C.POINTER(Report)]
     L.ccp_grid_mg_apply.argtypes = [vp, i32]
+    L.ccp_grid_mg_prepare.argtypes = [vp, i32]
+    L.ccp_grid_mg_conjugate_gradient_enqueue.argtypes = [vp, dbl, i32, i32, C.POINTER(DeviceArray)]
     L.ccp_grid_mg_level.argtypes = [vp, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
     L.ccp_grid_mg_set_hierarchy.argtypes = [vp, i32]
     L.ccp_grid_mg_get_hierarchy.argtypes = [vp, C.POINTER(i32)]
@@ -765,6 +768,36 @@ class Grid:
         check(self.L.ccp_grid_mg_conjugate_gradient(self.h, epsilon, max_iteration, smoothing_sweeps, reps),
               "ccp_grid_mg_conjugate_gradient")
         return list(reps)
+
+    def mg_prepare(self, sweeps=0):
+        """Everything mg_conjugate_gradient would do before its first launch in the handle's present configuration -- the
+        checks, the hierarchy, every allocation and one-off read-back -- with the status the solve would return (CcpError).
+        May synchronise; x and b are untouched.  Needed before mg_conjugate_gradient_enqueue, with the same `sweeps`, and
+        again after a call that drops what it built: the operator and mask setters, the mg_set_* mode setters."""
+        check(self.L.ccp_grid_mg_prepare(self.h, sweeps), "ccp_grid_mg_prepare")
+
+    def mg_conjugate_gradient_enqueue(self, epsilon, max_iteration, sweeps=0, report=None):
+        """mg_conjugate_gradient without the host: the start-up steps and exactly `max_iteration` iterations (<= 4096; a
+        channel that has stopped costs no-op launches) are enqueued on torch's current stream of the handle's device, with no
+        allocation and no host synchronisation, so the call may be recorded by torch.cuda.graph.  x and the figures of the
+        report equal mg_conjugate_gradient's bit for bit.  Needs mg_prepare(sweeps) (CcpError STATE otherwise).
+        report: a CUDA float64 tensor of channels x 6 (any non-overlapping strides), or None; a kernel fills row ch with
+        iterations, converged (0.0 / 1.0), last_l1_step, b_mean, x_mean ("constant" null-space mode; 0.0 otherwise) and
+        0.0 when the stream gets there.  Returns `report`."""
+        arr = None
+        if report is not None:
+            torch = self._torch()
+            if not isinstance(report, torch.Tensor) or report.device.type != "cuda" or report.device.index != self.desc.device:
+                raise ValueError(f"report must be a tensor on cuda:{self.desc.device}")
+            if report.dtype != torch.float64 or tuple(report.shape) != (self.C, 6):
+                raise ValueError(f"report must be a float64 tensor of {self.C} x 6, not {report.dtype} {tuple(report.shape)}")
+            if any(s < 0 for s in report.stride()) or not _no_overlap(report.shape, report.stride()):
+                raise ValueError("report is an output whose elements overlap or has a negative stride")
+            arr = DeviceArray(report.data_ptr(), DTYPE_F64, 0, 0, report.stride(0), report.stride(1), 0)
+        ref = None if arr is None else C.byref(arr)
+        self._on_stream(lambda: self.L.ccp_grid_mg_conjugate_gradient_enqueue(self.h, epsilon, max_iteration, sweeps, ref),
+                        "ccp_grid_mg_conjugate_gradient_enqueue")
+        return report
 
     def mg_apply(self, smoothing_sweeps=2):
         """x := M^-1 b (one V-cycle per channel; diagnostic)."""

@@ -1299,6 +1299,7 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     v->smoother = g->mg_smoother;
     v->ns = &g->mg_nullspace;
     v->stream = g->stream;
+    v->device = g->device;
     v->cache = &g->mg;
     v->comm = g->comm;
     v->part = g->part.empty() ? nullptr : g->part.data();

@@ -5,6 +5,8 @@
 #include "ccp_grid_mgb.hpp"
 #include "ccp_grid_mgl.hpp"
 #include "ccp_grid_mgn.hpp"
+#include "ccp_grid_mge.hpp"
+#include "ccp_view_check.hpp"
 #include "ccp_grid_weighted_api.hpp"
 #include "ccp_comm.hpp"
 
@@ -102,6 +104,13 @@ struct MgHierarchy {
     DevBuf<unsigned> nscount;
     DevBuf<MgnState> nsstate;        // one per channel: read back once, after the last channel's solve
     DevBuf<double> nspart;
+    // ccp_grid_mg_prepare / ccp_grid_mg_conjugate_gradient_enqueue (ccp_grid_mge.hpp): the enqueue solve's states, one per
+    // channel in either channel mode (the report kernel reads them all after the last channel), and what the last
+    // successful prepare built for -- the enqueue call runs only on exactly that.  Everything else prepare builds is what
+    // the synchronous solve builds at its first call; a setter that frees part of it clears `prepared`.
+    DevBuf<CgState> estate;
+    bool prepared = false;
+    int prep_nu = 0, prep_channels = 0, prep_mode = 0, prep_smoother = 0, prep_nullspace = 0;
     // one operator (opC == 1) only: 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda (lam_slot).  The one-block code, which may see
     // opC > 1, asks coef() for a coefficient plane and vec() for a vector; the row-block code (never weighted) uses arr().
     double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }
@@ -702,6 +711,51 @@ int vcycle_batched(MgHierarchy &h, hipStream_t s, int C, long n0, const double *
 // exchange ghost rows and all-reduce.  The loop itself reads s, st (the device's CgState[C]) and p, z, len (p = z copies
 // len doubles) from the object.
 
+// The step calls of the recurrence, written once for the two forms of the loop below: the start-up steps, and `count`
+// iterations (the launches of an iteration are no-ops once st says so).
+template <typename Steps>
+int pcg_start(const Steps &S)
+{
+    CCP_TRY(S.residual());                                               // r = A x
+    S.init();                                                            // r = b - r; r'r
+    CCP_TRY(S.check());
+    CCP_TRY(S.precondition());                                           // z = M r
+    S.dot();
+    CCP_TRY(S.set_rlen());                                               // rlen = r'z
+    CCP_TRY(S.start_direction());                                        // p = z
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+template <typename Steps>
+int pcg_iterate(const Steps &S, int count)
+{
+    for (int k = 0; k < count; ++k) {
+        CCP_TRY(S.product());                                            // Ap, p'Ap partials
+        CCP_TRY(S.alpha());                                              // alpha = r'z / p'Ap
+        S.update();
+        CCP_TRY(S.check());
+        CCP_TRY(S.precondition());
+        S.dot();
+        CCP_TRY(S.beta());
+        S.direction();                                                   // p = z + beta p
+    }
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+// The enqueue-only form (ccp_grid_mg_conjugate_gradient_enqueue): S.st has been initialised on the device (k_mge_init);
+// the start-up steps, exactly max_iteration iterations and the mode's finish go onto the stream, and nothing comes back.
+template <typename Steps>
+int pcg_enqueue(const Steps &S, int max_iteration)
+{
+    CCP_TRY(pcg_start(S));
+    CCP_TRY(pcg_iterate(S, max_iteration));
+    return S.finish();
+}
+
+// The synchronous form: the states go up from the host, and come back after the start-up steps, after every batch of 16
+// iterations (the loop stops issuing once no channel is active) and at the end.
 // host: C states of the caller's (the read-backs land there); report: C entries or null.  `seconds` is the time of this
 // call in every entry: one channel's solve, or in batched mode the whole solve.
 template <typename Steps>
@@ -725,30 +779,13 @@ int pcg_loop(const Steps &S, MgHierarchy &h, CgState *host, int C, int max_itera
     }
     CCP_HIP(hipMemcpyAsync(S.st, host, st_bytes, hipMemcpyHostToDevice, s));
     CCP_HIP(hipEventRecord(h.ev0, s));
-    CCP_TRY(S.residual());                                               // r = A x
-    S.init();                                                            // r = b - r; r'r
-    CCP_TRY(S.check());
-    CCP_TRY(S.precondition());                                           // z = M r
-    S.dot();
-    CCP_TRY(S.set_rlen());                                               // rlen = r'z
-    CCP_TRY(S.start_direction());                                        // p = z
-    CCP_HIP(hipGetLastError());
+    CCP_TRY(pcg_start(S));
     CCP_TRY(read_back());
     int issued = 0;
     bool active = any_active() && max_iteration > 0;
     while (active && issued < max_iteration) {
         const int batch = std::min(16, max_iteration - issued);
-        for (int k = 0; k < batch; ++k) {                                // (the launches of an iteration are no-ops once st says so)
-            CCP_TRY(S.product());                                        // Ap, p'Ap partials
-            CCP_TRY(S.alpha());                                          // alpha = r'z / p'Ap
-            S.update();
-            CCP_TRY(S.check());
-            CCP_TRY(S.precondition());
-            S.dot();
-            CCP_TRY(S.beta());
-            S.direction();                                               // p = z + beta p
-        }
-        CCP_HIP(hipGetLastError());
+        CCP_TRY(pcg_iterate(S, batch));
         issued += batch;
         CCP_TRY(read_back());
         active = any_active();
@@ -901,8 +938,9 @@ struct BatchedSteps : PcgArgs {
     int beta() const { hipLaunchKernelGGL(k_mgb_beta, sgrid, dim3(kBlock), 0, s, part, ps, blocks, st); return CCP_OK; }
 };
 
-// ccp_grid_mg_conjugate_gradient in batched mode
-int pcg_batched(const GridMgView &v, MgHierarchy &h, double epsilon, int max_iteration, int nu, ccp_gs_report *report)
+// ccp_grid_mg_conjugate_gradient in batched mode, on the levels and the work set pcg_ready made.  enqueue: the host-free
+// form, on the states at h.estate
+int pcg_batched(const GridMgView &v, MgHierarchy &h, double epsilon, int max_iteration, int nu, ccp_gs_report *report, bool enqueue)
 {
     const int C = v.channels;
     const unsigned groups = (unsigned)((C + kMgbGroup - 1) / kMgbGroup);
@@ -912,10 +950,12 @@ int pcg_batched(const GridMgView &v, MgHierarchy &h, double epsilon, int max_ite
     S.len = C * S.n;
     S.vgrid = dim3((unsigned)S.blocks, (unsigned)C);
     S.sgrid = dim3((unsigned)C);
-    CCP_TRY(batched_levels(v, h));
-    CCP_TRY(h.bat.alloc(C, S.n, std::max(S.apply_blocks, S.blocks), S.s));
     S.bind(h.bat, 0);
     S.b = v.b, S.x = v.x;
+    if (enqueue) {
+        S.st = h.estate.p;
+        return pcg_enqueue(S, max_iteration);
+    }
     std::vector<CgState> host((size_t)C);
     return pcg_loop(S, h, host.data(), C, max_iteration, report);
 }
@@ -1236,6 +1276,97 @@ int nullspace_ready(const GridMgView &v, MgHierarchy &h)
 
 MgnLay nullspace_layout(const GridMgView &v) { return MgnLay{v.geom.W, 2 * v.geom.H, (int)v.geom.pitch}; }
 
+// ---- one solve, three entry points -------------------------------------------------------------------------------------
+// ccp_grid_mg_conjugate_gradient is pcg_ready then pcg_solve; ccp_grid_mg_prepare is pcg_ready alone, and
+// ccp_grid_mg_conjugate_gradient_enqueue is pcg_solve alone in its enqueue form.
+
+// Everything the solve does before its first launch, in the handle's present configuration: the refusals, the hierarchy,
+// and whatever of the mode allocates or reads back, the PCG work set included.  Every step is a no-op once it is done.
+int pcg_ready(ccp_grid *g, int32_t max_iteration, int32_t smoothing_sweeps, GridMgView *v, int *nu, MgHierarchy **out)
+{
+    CCP_TRY(check_handle(g, v));
+    CCP_TRY(sweeps_arg(smoothing_sweeps, nu, v->smoother));
+    if (max_iteration < 0) return CCP_ERR_BAD_ARG;
+    const bool batched = v->channels_mode == CCP_MG_CHANNELS_BATCHED;
+    if (batched && v->precision == CCP_MG_PRECISION_F32) return CCP_ERR_UNSUPPORTED;
+    CCP_TRY(line_check(*v));
+    CCP_TRY(nullspace_check(*v));
+    MgHierarchy *h = nullptr;
+    CCP_TRY(hierarchy(*v, &h));
+    CCP_TRY(line_planes(*v, *h));
+    PcgArgs a{};                                                   // (the solve's shape: how many partial sums a channel needs)
+    const long n = v->geom.ch_stride;                              // one channel incl. pads (pads stay 0 in every vector)
+    if (batched) {
+        a.shape(v->geom.W, v->geom.H, n, (unsigned)((v->channels + kMgbGroup - 1) / kMgbGroup));
+        CCP_TRY(batched_levels(*v, *h));
+        CCP_TRY(h->bat.alloc(v->channels, n, std::max(a.apply_blocks, a.blocks), v->stream));
+    } else {
+        if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(*v, *h));
+        CCP_TRY(nullspace_ready(*v, *h));
+        a.shape(v->geom.W, v->geom.H, n);
+        CCP_TRY(h->seq.alloc(1, n, std::max(a.apply_blocks, a.blocks), v->stream));
+    }
+    *out = h;
+    return CCP_OK;
+}
+
+// The solve itself on what pcg_ready left: the mode's steps object, and its loop once (batched) or per channel.
+// enqueue: the host-free form of the loop (pcg_enqueue), channel ch on the state h.estate[ch]; report is not used then.
+int pcg_solve(const GridMgView &v, MgHierarchy &h, double epsilon, int max_iteration, int nu, ccp_gs_report *report, bool enqueue)
+{
+    if (v.channels_mode == CCP_MG_CHANNELS_BATCHED) return pcg_batched(v, h, epsilon, max_iteration, nu, report, enqueue);
+    const long n = v.geom.ch_stride;
+    // one channel after the other: b, x, the channel's operator and, on the enqueue form, the channel's own state
+    auto channels = [&](auto &S, auto &&each) -> int {
+        S.h = &h, S.s = v.stream, S.epsilon = epsilon, S.nu = nu;
+        S.shape(v.geom.W, v.geom.H, n);
+        S.bind(h.seq, 0);
+        for (int ch = 0; ch < v.channels; ++ch) {
+            S.b = v.b + ch * n;
+            S.x = v.x + ch * n;
+            S.ch = ch;                                              // (one operator per channel: the channel's levels)
+            each(ch);
+            if (enqueue) {
+                S.st = h.estate.p + ch;
+                CCP_TRY(pcg_enqueue(S, max_iteration));
+            } else {
+                CgState host;
+                CCP_TRY(pcg_loop(S, h, &host, 1, max_iteration, report ? report + ch : nullptr));
+            }
+        }
+        return CCP_OK;
+    };
+    if (constant_mode(v)) {
+        NullspaceSteps S{};
+        S.lay = nullspace_layout(v), S.pixels = (double)v.geom.W * (double)v.geom.H;
+        S.npart = h.nspart.p;
+        CCP_TRY(channels(S, [&](int ch) {
+            S.ns = h.nsstate.p + ch;
+            v.ns->solved[ch] = false;
+        }));
+        if (enqueue) return CCP_OK;                                 // (the means stay on the device: k_mge_report reads them there)
+        MgnState means[kMaxChannels] = {};                          // one read-back for all channels, after the last solve
+        CCP_HIP(hipMemcpyAsync(means, h.nsstate.p, sizeof(MgnState) * (size_t)v.channels, hipMemcpyDeviceToHost, v.stream));
+        CCP_HIP(hipStreamSynchronize(v.stream));
+        for (int ch = 0; ch < v.channels; ++ch) {
+            v.ns->solved[ch] = true;
+            v.ns->b_mean[ch] = means[ch].b_mean;
+            v.ns->x_mean[ch] = means[ch].x_mean;
+        }
+        return CCP_OK;
+    }
+    ChannelSteps S{};
+    return channels(S, [](int) {});
+}
+
+// Is what the last ccp_grid_mg_prepare built what a solve of this view with `nu` sweeps runs on?
+bool prepared_for(const GridMgView &v, const MgHierarchy *h, int nu)
+{
+    return h && h->prepared && !h->rowblocked && h->estate.p && h->weighted == v.weighted && h->precision == v.precision &&
+           h->opC == (v.weighted ? v.op_channels : 1) && h->prep_nu == nu && h->prep_channels == v.channels &&
+           h->prep_mode == v.channels_mode && h->prep_smoother == v.smoother && h->prep_nullspace == (constant_mode(v) ? 1 : 0);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1349,6 +1480,7 @@ try {
         MgHierarchy &h = **cache;
         batched_release(h);
         h.seq.release();
+        h.prepared = false;
     }
     return CCP_OK;
 } CCP_ABI_CATCH
@@ -1374,6 +1506,7 @@ try {
     if (*cache) {                                                  // the line solves' work planes go; everything else is shared
         (*cache)->lwork.release();
         (*cache)->lplane = 0;
+        (*cache)->prepared = false;
     }
     return CCP_OK;
 } CCP_ABI_CATCH
@@ -1486,60 +1619,46 @@ int ccp_grid_mg_conjugate_gradient(ccp_grid *g, double epsilon, int32_t max_iter
                                    ccp_gs_report *report)
 try {
     GridMgView v{};
+    int nu = 2;
+    MgHierarchy *h = nullptr;
+    CCP_TRY(pcg_ready(g, max_iteration, smoothing_sweeps, &v, &nu, &h));
+    return pcg_solve(v, *h, epsilon, max_iteration, nu, report, false);
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_prepare(ccp_grid *g, int32_t smoothing_sweeps)
+try {
+    GridMgView v{};
+    int nu = 2;
+    MgHierarchy *h = nullptr;
+    CCP_TRY(pcg_ready(g, 0, smoothing_sweeps, &v, &nu, &h));
+    h->prepared = false;
+    if (!h->estate.p) CCP_TRY(h->estate.alloc((size_t)kMaxChannels));
+    CCP_HIP(hipStreamSynchronize(v.stream));                       // what building enqueued has run: a failure shows here
+    h->prep_nu = nu, h->prep_channels = v.channels, h->prep_mode = v.channels_mode, h->prep_smoother = v.smoother;
+    h->prep_nullspace = constant_mode(v) ? 1 : 0;
+    h->prepared = true;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_conjugate_gradient_enqueue(ccp_grid *g, double epsilon, int32_t max_iteration, int32_t smoothing_sweeps,
+                                           const ccp_device_array *report)
+try {
+    GridMgView v{};
     CCP_TRY(check_handle(g, &v));
     int nu = 2;
     CCP_TRY(sweeps_arg(smoothing_sweeps, &nu, v.smoother));
-    if (max_iteration < 0) return CCP_ERR_BAD_ARG;
-    const bool batched = v.channels_mode == CCP_MG_CHANNELS_BATCHED;
-    if (batched && v.precision == CCP_MG_PRECISION_F32) return CCP_ERR_UNSUPPORTED;
-    CCP_TRY(line_check(v));
-    CCP_TRY(nullspace_check(v));
-    MgHierarchy *h = nullptr;
-    CCP_TRY(hierarchy(v, &h));
-    CCP_TRY(line_planes(v, *h));
-    if (batched) return pcg_batched(v, *h, epsilon, max_iteration, nu, report);
-    if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
-    CCP_TRY(nullspace_ready(v, *h));
-    const long n = v.geom.ch_stride;                               // one channel incl. pads (pads stay 0 in every vector)
-    if (constant_mode(v)) {
-        NullspaceSteps S{};
-        S.h = h, S.s = v.stream, S.epsilon = epsilon, S.nu = nu;
-        S.shape(v.geom.W, v.geom.H, n);
-        S.lay = nullspace_layout(v), S.pixels = (double)v.geom.W * (double)v.geom.H;
-        S.ns = h->nsstate.p, S.npart = h->nspart.p;
-        CCP_TRY(h->seq.alloc(1, n, std::max(S.apply_blocks, S.blocks), S.s));
-        S.bind(h->seq, 0);
-        for (int ch = 0; ch < v.channels; ++ch) {
-            S.b = v.b + ch * n;
-            S.x = v.x + ch * n;
-            S.ch = ch;
-            S.ns = h->nsstate.p + ch;
-            v.ns->solved[ch] = false;
-            CgState host;
-            CCP_TRY(pcg_loop(S, *h, &host, 1, max_iteration, report ? report + ch : nullptr));
-        }
-        MgnState means[kMaxChannels] = {};                          // one read-back for all channels, after the last solve
-        CCP_HIP(hipMemcpyAsync(means, h->nsstate.p, sizeof(MgnState) * (size_t)v.channels, hipMemcpyDeviceToHost, S.s));
-        CCP_HIP(hipStreamSynchronize(S.s));
-        for (int ch = 0; ch < v.channels; ++ch) {
-            v.ns->solved[ch] = true;
-            v.ns->b_mean[ch] = means[ch].b_mean;
-            v.ns->x_mean[ch] = means[ch].x_mean;
-        }
-        return CCP_OK;
+    if (max_iteration < 0 || max_iteration > CCP_MG_ENQUEUE_MAX_ITERATION) return CCP_ERR_BAD_ARG;
+    if (report) CCP_TRY(check_view_on(v.device, report, 1u << CCP_DTYPE_F64, true, 1, v.channels, kMgeReportFields, 1));
+    MgHierarchy *h = *v.cache;
+    if (!prepared_for(v, h, nu)) return CCP_ERR_STATE;
+    hipLaunchKernelGGL(k_mge_init, dim3(1), dim3(kBlock), 0, v.stream, h->estate.p, v.channels);
+    CCP_TRY(pcg_solve(v, *h, epsilon, max_iteration, nu, nullptr, true));
+    if (report) {
+        const MgeReport out{static_cast<double *>(const_cast<void *>(report->data)), (long)report->stride_y, (long)report->stride_x};
+        const MgnState *ns = constant_mode(v) ? h->nsstate.p : nullptr;
+        hipLaunchKernelGGL(k_mge_report, dim3(1), dim3(kBlock), 0, v.stream, static_cast<const CgState *>(h->estate.p), ns, v.channels, out);
     }
-    ChannelSteps S{};
-    S.h = h, S.s = v.stream, S.epsilon = epsilon, S.nu = nu;
-    S.shape(v.geom.W, v.geom.H, n);
-    CCP_TRY(h->seq.alloc(1, n, std::max(S.apply_blocks, S.blocks), S.s));
-    S.bind(h->seq, 0);
-    for (int ch = 0; ch < v.channels; ++ch) {
-        S.b = v.b + ch * n;
-        S.x = v.x + ch * n;
-        S.ch = ch;                                                  // (one operator per channel: the channel's levels)
-        CgState host;
-        CCP_TRY(pcg_loop(S, *h, &host, 1, max_iteration, report ? report + ch : nullptr));
-    }
+    CCP_HIP(hipGetLastError());
     return CCP_OK;
 } CCP_ABI_CATCH
 

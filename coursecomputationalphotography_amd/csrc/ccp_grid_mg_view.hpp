@@ -45,7 +45,8 @@ struct GridMgView {
     int smoother;                    // CCP_MG_SMOOTHER_* (ccp_grid_mg_set_smoother)
     MgNullspace *ns;                 // ccp_grid_mg_set_nullspace's value, the census verdict and the last solves' means
     hipStream_t stream;
-    MgHierarchy **cache;             // the handle's cached hierarchy (built on first use, dropped with the mask and the partition)
+    int device;                      // the handle's device (what a ccp_device_array argument is checked against)
+    MgHierarchy **cache;            // the handle's cached hierarchy (built on first use, dropped with the mask and the partition)
     // row blocks (ccp_grid_attach_comm): the communicator, every rank's first image row then the image height
     // (world + 1 entries), and the handle's ghost depth; comm is null when none is attached
     ccp_comm *comm;

@@ -7,6 +7,7 @@ of that device; the solvers themselves wait for their own reports, so the call r
 `solver` takes the names of the facade's ccp::Solver: "GaussSeidel" (red-black), "ConjugateGradient",
 "GaussSeidelReferenceOrder" and "MultigridConjugateGradient"; `iterations` means what it means there (fixed sweep
 count for the Gauss-Seidel solvers, the iteration cap at epsilon 1e-10 for the CG solvers).
+WeightedSolver is the exception to "the solvers wait": a persistent weighted handle whose solves only enqueue.
 """
 from __future__ import annotations
 
@@ -553,3 +554,146 @@ def weighted_solve_grad(gx, gy, f, iterations: int, wx=None, wy=None, data_weigh
     cfg = dict(iterations=int(iterations), epsilon=float(epsilon), hierarchy=hierarchy, precision=precision, channels=channels,
                smoother=smoother, strict=bool(strict))
     return _solve_function().apply(gx, gy, f, plane(wx), plane(wy), plane(data_weight), values, fixed, cfg)
+
+
+# ---- a persistent weighted handle: prepare once, then only enqueue ------------------------------------------------------
+class WeightedSolver:
+    """A weighted grid handle that lives across solves, for loops that solve many right-hand sides on ONE operator (a
+    training loop, a video, the replays of a torch.cuda.graph).  The functions above create a handle per call, and their
+    solve waits for the host; here set_operator pays for everything that allocates or synchronises -- the operator's
+    validation, the multigrid hierarchy, the PCG vectors (capi.Grid.mg_prepare) -- and solve / solve_grad then only
+    enqueue on torch's current stream (capi.Grid.mg_conjugate_gradient_enqueue): no host synchronisation and no
+    allocation on the handle, so a solve may be recorded by torch.cuda.graph together with whatever produces its inputs
+    and consumes its result.
+
+    H, W, C: the canvas and its channels; device: a torch device or a GPU index.  iterations: every solve enqueues
+    exactly this many PCG iterations (<= 4096); a channel that reaches sqrt(r'r) < epsilon earlier stops there and the
+    remaining launches are no-ops for it, so x and the report are those of the synchronous solve with the same cap, bit
+    for bit (`iterations` in a report counts completed iterations, and the update that passes epsilon is one more: a system
+    that reports 6 needs iterations >= 7 here).  epsilon is absolute.  hierarchy, precision, channels, smoother, nullspace: as weighted_solve's (the
+    hierarchy defaults to "rescaled", as in weighted_solve_grad).  Two smoothing sweeps, as everywhere in this module.
+
+    Nothing checks convergence for you -- that would be a read-back: pass `report` (a float64 C x 6 tensor: iterations,
+    converged, last_l1_step, b_mean, x_mean, 0 per channel) and look at it when the stream has passed."""
+
+    SWEEPS = 2
+
+    def __init__(self, H, W, C, device, *, iterations, epsilon, hierarchy="rescaled", precision="f64", channels="sequential",
+                 smoother="point", nullspace="none"):
+        import torch
+        device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("WeightedSolver needs a GPU device")
+        dev = device.index if device.index is not None else torch.cuda.current_device()
+        if not 0 <= int(iterations) <= 4096:
+            raise ValueError(f"iterations must be 0 .. 4096 (one call queues exactly that many), not {iterations}")
+        self.H, self.W, self.C, self.device = int(H), int(W), int(C), torch.device("cuda", dev)
+        self.iterations, self.epsilon = int(iterations), float(epsilon)
+        self.nullspace = capi.mg_nullspace_value(nullspace)
+        self._operator = None
+        self._zero = torch.zeros((), dtype=torch.float64, device=self.device).expand(self.H, self.W, self.C)
+        self.grid = capi.Grid(self.W, self.H, self.C, device=dev, weighted=True)
+        try:
+            self.grid.mg_set_hierarchy(hierarchy)
+            self.grid.mg_set_precision(precision)
+            self.grid.mg_set_channels(channels)
+            self.grid.mg_set_smoother(smoother)
+            self.grid.mg_set_nullspace(nullspace)
+        except BaseException:
+            self.grid.close()
+            raise
+
+    def set_operator(self, wx, wy, data_weight=None, fixed=None):
+        """Install the operator (wx, wy, data_weight: H x W tensors or scalars, None: 1, 1, 0; fixed: an H x W mask of
+        prescribed pixels or None; any of them H x W x C: one operator per channel, chosen as weighted_solve chooses)
+        and prepare the solve for it.  Synchronises; raises capi.CcpError for a refused operator or mode combination.
+        Not to be called while a stream is being captured."""
+        dev = self.device.index
+        wx, wy, lam = (_weight(w, self.H, self.W, dev) for w in (wx, wy, data_weight))
+        self._operator = None
+        _set_operator(self.grid, wx, wy, lam, fixed)
+        self.grid.mg_prepare(self.SWEEPS)
+        self._operator = (wx, wy, lam, fixed)
+
+    def _enqueue_solve(self, gx, gy, f, values, x0, out, report):
+        if self._operator is None:
+            raise RuntimeError("WeightedSolver: set_operator first")
+        g = self.grid
+        g.set_x_tensor(self._zero if x0 is None else x0)
+        g.assemble_constrained_rhs_tensor(gx, gy, f, values, init_x=False)   # (puts `values` on the fixed pixels of x)
+        g.mg_conjugate_gradient_enqueue(self.epsilon, self.iterations, self.SWEEPS, report)
+        return g.get_x_tensor(out=out)
+
+    def solve(self, gx, gy, f, values=None, x0=None, out=None, report=None):
+        """Minimise weighted_solve's / constrained_solve's energy for the installed operator: the right-hand side from gx,
+        gy (float32 H x W x C or None), f and values (u8 / float32 / float64 or None), x from x0 (float32 / float64
+        H x W x C) or 0, the solve, and x copied into `out` (float32 / float64 H x W x C; a new float64 tensor when None).
+        Returns (out, report).  Enqueue only."""
+        return self._enqueue_solve(gx, gy, f, values, x0, out, report), report
+
+    def solve_grad(self, gx, gy, f, values=None, x0=None, report=None, adjoint_report=None):
+        """solve as a differentiable function of gx, gy, f and values (weighted_solve_grad's formulas; no gradients for the
+        weights: weighted_solve_grad is for those).  Returns (u, report), u a new float64 H x W x C tensor with a grad_fn.
+        Backward is the adjoint right-hand side, one more enqueue solve and the gradient pass on this same handle; it
+        needs only the saved u and inputs, so several forwards may precede their backwards.  No `strict` check: the
+        adjoint solve's figures land in `adjoint_report` if given."""
+        if self.nullspace != capi.MG_NULLSPACES["none"]:
+            _no_nullspace("constant", "WeightedSolver.solve_grad")
+        return _persistent_function().apply(gx, gy, f, values, x0, self, report, adjoint_report), report
+
+    def close(self):
+        self.grid.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+_PersistentSolve = None
+
+
+def _persistent_function():
+    """The torch.autograd.Function behind WeightedSolver.solve_grad (built on first use, as _solve_function)."""
+    global _PersistentSolve
+    if _PersistentSolve is not None:
+        return _PersistentSolve
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    names = ("gx", "gy", "f", "values")
+
+    class PersistentSolve(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, gx, gy, f, values, x0, solver, report, adjoint_report):
+            u = solver._enqueue_solve(gx, gy, f, values, x0, None, report)
+            ctx.solver, ctx.adjoint_report = solver, adjoint_report
+            ctx.present = [t is not None for t in (gx, gy, f, values)]
+            ctx.save_for_backward(*[t for t in (gx, gy, f, values) if t is not None], u)
+            return u
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad):
+            saved = list(ctx.saved_tensors)
+            u = saved[-1]
+            it = iter(saved[:-1])
+            inputs = {n: next(it) if p else None for n, p in zip(names, ctx.present)}
+            solver = ctx.solver
+            g = solver.grid
+            wx, wy, lam, fixed = solver._operator
+            want = tuple(n for n, need in zip(names, ctx.needs_input_grad[:4]) if need)
+            grad = grad.reshape(u.shape)
+            if grad.dtype not in (torch.float32, torch.float64):
+                grad = grad.to(torch.float64)
+            g.adjoint_begin_tensor(grad)
+            g.mg_conjugate_gradient_enqueue(solver.epsilon, solver.iterations, solver.SWEEPS, ctx.adjoint_report)
+            out = {n: torch.empty(inputs[n].shape, dtype=inputs[n].dtype, device=inputs[n].device) for n in want}
+            got = g.weighted_adjoint_tensor(u, grad if "values" in want else None, inputs["gx"], inputs["gy"], inputs["f"], wx, wy, lam,
+                                            fixed, want=want, out=out)
+            return tuple(got.get(n) for n in names) + (None, None, None, None)
+
+    _PersistentSolve = PersistentSolve
+    return PersistentSolve

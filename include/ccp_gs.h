@@ -993,6 +993,63 @@ int ccp_grid_mg_level_channel(ccp_grid *g, int32_t channel, int32_t level, int32
 int ccp_grid_constraint_info_channel(ccp_grid *g, int32_t channel, int64_t *fixed_pixels, int64_t *free_live_pixels,
                                      int64_t *boundary_edges);
 
+/* ---- The multigrid PCG without the host: prepare once, then only enqueue -------------------------------------------------
+ * ccp_grid_mg_conjugate_gradient synchronises with the host after its start-up steps, after every 16 iterations and at the
+ * end, uploads its loop states, and at the first solve of a configuration builds the hierarchy and allocates its vectors.
+ * The two calls below split that: ccp_grid_mg_prepare does, once, everything that allocates or reads back, and
+ * ccp_grid_mg_conjugate_gradient_enqueue then only enqueues -- no allocation, no host synchronisation (no
+ * hipStreamSynchronize, no event wait or timing) and no copy to or from host memory -- so it may be issued while the
+ * handle's stream is being captured (hipStreamBeginCapture, torch.cuda.graph), between the _device calls that assemble the
+ * right-hand side and read x out.  ccp_grid_mg_prepare, the operator and mask setters and ccp_grid_mg_conjugate_gradient
+ * itself may NOT be issued during a capture: they synchronise.  Across the replays of a captured graph the operator is
+ * fixed; right-hand sides, initial guesses and adjoint right-hand sides may change.
+ *
+ * ccp_grid_mg_prepare: everything ccp_grid_mg_conjugate_gradient would do before its first launch in the handle's present
+ * configuration -- the checks, the hierarchy, the float copies of CCP_MG_PRECISION_F32, the work planes of
+ * CCP_MG_SMOOTHER_LINE, the vectors of CCP_MG_CHANNELS_BATCHED, the census of CCP_MG_NULLSPACE_CONSTANT, the PCG vectors and
+ * partial sums for the handle's channel count, and the enqueue solve's own loop states.  It returns exactly the status the
+ * solve would return for that configuration (CCP_ERR_UNSUPPORTED for every refused combination, CCP_ERR_STATE without an
+ * operator or on a row block, CCP_ERR_BAD_ARG for a NULL handle or smoothing_sweeps outside 0..4) and leaves x and b
+ * untouched.  It may synchronise.  Single-block handles of all three kinds: structured, Dirichlet-mask, weighted.  Calling
+ * it twice is harmless: what is there is kept. */
+int ccp_grid_mg_prepare(ccp_grid *g, int32_t smoothing_sweeps);
+
+/* ccp_grid_mg_conjugate_gradient_enqueue: the recurrence, kernels, launch geometry and operation order of
+ * ccp_grid_mg_conjugate_gradient in every mode that call serves -- sequential and batched channels, both hierarchy kinds,
+ * F64 and F32, the point and the line smoother, CCP_MG_NULLSPACE_CONSTANT, shared and per-channel operators.  It
+ * initialises the loop states on the device, enqueues the start-up steps and EXACTLY max_iteration iterations (per channel
+ * in sequential mode, once in batched mode) on the handle's stream, and returns.  Every launch of an iteration is a no-op
+ * for a channel that has stopped, exactly as inside the synchronous call's batches of 16; so with the same handle state,
+ * epsilon, max_iteration and smoothing_sweeps, x and the report's iterations, converged and last_l1_step equal the
+ * synchronous call's BIT FOR BIT on every channel and in every mode, and in CONSTANT mode the two means do as well.  A
+ * solve that converges early still pays the launches of the remaining iterations: choose max_iteration close to what the
+ * system needs -- `iterations` counts the completed iterations and the update whose residual passes epsilon is one more, so
+ * a solve that reports 6 iterations needs max_iteration >= 7 to report converged, here as in the synchronous call.
+ *   Precondition: ccp_grid_mg_prepare succeeded on this handle with the same smoothing_sweeps, after the last call that
+ *   drops what it built.  Those calls are: the operator setters (ccp_grid_set_weights_host / _device,
+ *   ccp_grid_set_weights_constrained_host / _device, ccp_grid_set_weights_per_channel_device), the mask setters
+ *   (ccp_grid_set_mask_host / _device), the mode setters when they change the value (ccp_grid_mg_set_precision,
+ *   ccp_grid_mg_set_channels, ccp_grid_mg_set_smoother, ccp_grid_mg_set_nullspace), the hierarchy kind setter
+ *   (ccp_grid_mg_set_hierarchy), and ccp_grid_attach_comm and the _rowblocked multigrid calls.  Otherwise the call returns
+ *   CCP_ERR_STATE with nothing enqueued and x, b and the report untouched: prepare again.  The synchronous solve,
+ *   ccp_grid_mg_apply and the I/O and assembly calls keep a prepared handle prepared.
+ *   max_iteration < 0: CCP_ERR_BAD_ARG.  max_iteration > CCP_MG_ENQUEUE_MAX_ITERATION (4096): CCP_ERR_BAD_ARG -- a stated
+ *   cap on the number of launches one call may queue.  smoothing_sweeps as in the synchronous call.
+ *   report: NULL, or an F64 view of `channels` x 6 in device memory, any non-overlapping strides: channel ch's field k at
+ *   data + ch * stride_y + k * stride_x elements (stride_n and stride_c unused), checked like every _device view (a wrong
+ *   dtype, a view too short, memory of another device: CCP_ERR_BAD_ARG before anything is enqueued).  A kernel fills it at
+ *   the end of the stream work: [0] iterations, [1] converged (0.0 or 1.0), [2] last_l1_step, [3] b_mean and [4] x_mean --
+ *   the values ccp_grid_mg_nullspace_info gives after a synchronous solve in CONSTANT mode, +0.0 in NONE mode -- and [5]
+ *   +0.0, reserved.  There is no `seconds`: time the stream.  After a CONSTANT-mode enqueue solve
+ *   ccp_grid_mg_nullspace_info returns CCP_ERR_STATE: the means are in the report, not on the host.
+ *   There is no `strict` flag and no error for a solve that did not converge: read `converged` when the stream has passed.
+ * Out of scope, each a possible follow-up: the _rowblocked calls; ccp_grid_mg_apply; a stop test relative to |b| computed
+ * on the device (one more reduction per solve: epsilon is absolute, as in the synchronous call); refreshing an installed
+ * operator without the setters' validation read-back.  Additive: the ABI version does not change. */
+#define CCP_MG_ENQUEUE_MAX_ITERATION 4096
+int ccp_grid_mg_conjugate_gradient_enqueue(ccp_grid *g, double epsilon, int32_t max_iteration, int32_t smoothing_sweeps,
+                                           const ccp_device_array *report);
+
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
 int ccp_grid_last_timing(ccp_grid *g, float *milliseconds, int32_t *kernel_launches);

@@ -1,0 +1,398 @@
+"""GPU: the host-free multigrid PCG (include/ccp_gs.h, ccp_grid_mg_prepare + ccp_grid_mg_conjugate_gradient_enqueue).
+
+The reference is the synchronous call on a second handle built from identical inputs, and equality is of bits: the raw
+float64 of x per channel, the report's iterations and converged equal, last_l1_step equal as bits, and in CONSTANT mode
+the two means equal as bits to ccp_grid_mg_nullspace_info of the synchronous twin.  No tolerance anywhere: the enqueue
+call issues the synchronous call's launches plus no-op launches, so nothing may differ.
+
+Cases: structured 64x48 and 257x131x3; a Dirichlet mask 257x131 with an elliptical region; weighted 257x131x3 on a
+screened system (lambda = 1e-2) in fp64 / point / sequential on both hierarchy kinds, f32 + rescaled, batched, line, one
+operator per channel (sequential and batched), an ellipse of fixed pixels; weighted 33x1 and 3x2 (the whole hierarchy is
+the tail kernel); floating 64x48 and 257x131x3 in CONSTANT mode with b + 1e-3.  Stops on channels scaled by 1, 1e-6
+and 0 (tests/test_gpu_mg_batched.py's construction): a cap of 3, a cap of 40 past every channel's own stop, a cap of 0,
+an x0 that already satisfies epsilon.  The statuses, and tensor_ops.WeightedSolver against weighted_solve and
+weighted_solve_grad."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import mixed_helpers as mh
+from coursecomputationalphotography_amd import capi, tensor_ops
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda", 0)
+BAD_ARG, STATE, UNSUPPORTED = 1, 5, 6
+SENTINEL = -7.25
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def tbits(t):
+    return t.detach().contiguous().view(torch.int64)
+
+
+def screened(W, H, seed, lam=1e-2):
+    """float32 edge weights in [0.5, 2] and lambda = 1e-2 everywhere: the screened system"""
+    g = mh.rng(seed)
+    wx, wy = (g.uniform(0.5, 2.0, (H, W)).astype(np.float32) for _ in range(2))
+    return wx, wy, np.full((H, W), lam, dtype=np.float32)
+
+
+def ellipse(W, H):
+    return 1 - mh.ellipse_fixed(W, H)                        # the region: inside the ellipse
+
+
+def make(kind, W, H, Cn):
+    """A fresh handle of `kind`; two calls give two handles with identical operators and modes."""
+    if kind == "structured":
+        return capi.Grid(W, H, Cn)
+    if kind == "mask":
+        return capi.Grid(W, H, Cn, mask=ellipse(W, H))
+    g = capi.Grid(W, H, Cn, weighted=True)
+    wx, wy, lam = screened(W, H, 31 * W + H)
+    if kind == "floating":                                   # lambda = 0, every weight > 0: CONSTANT mode's operator
+        g.mg_set_hierarchy("rescaled")
+        g.mg_set_nullspace("constant")
+        g.set_weights(wx, wy, None)
+        return g
+    g.mg_set_hierarchy("galerkin" if kind == "galerkin" else "rescaled")
+    if kind == "f32":
+        g.mg_set_precision("f32")
+    if kind in ("batched", "per_channel_batched"):
+        g.mg_set_channels("batched")
+    if kind == "line":
+        g.mg_set_smoother("line")
+    if kind in ("per_channel", "per_channel_batched"):
+        ws = [screened(W, H, 1000 * c + W) for c in range(Cn)]
+        stack = lambda i: torch.from_numpy(np.stack([w[i] for w in ws], axis=-1)).to(DEV)
+        g.set_weights_per_channel_tensor(stack(0), stack(1), stack(2))
+    else:
+        g.set_weights(wx, wy, lam, fixed=mh.ellipse_fixed(W, H) if kind == "fixed" else None)
+    return g
+
+
+def load(g, seed, scales=None, shift=0.0, zero_x=False):
+    """b = A x* of a random x* per channel (channel c then scales[c][1] x channel scales[c][0]'s), + shift; x0 random or 0"""
+    g.randomize_x(seed, 0.0, 255.0)
+    g.b_from_x()
+    bs = [g.get_b(c) for c in range(g.C)]
+    if scales is not None:
+        bs = [bs[src] * s for src, s in scales]
+    if scales is not None or shift:
+        for c, b in enumerate(bs):
+            g.set_b(b + shift, c)
+    if zero_x:
+        g.fill_x(0.0)
+    else:
+        g.randomize_x(seed + 1, 0.0, 255.0)
+    return float(np.linalg.norm(g.get_b(0)))
+
+
+def enqueue(g, eps, cap, sweeps):
+    report = torch.full((g.C, 6), SENTINEL, dtype=torch.float64, device=DEV)
+    g.mg_prepare(sweeps)
+    g.mg_prepare(sweeps)                                     # twice is harmless
+    assert g.mg_conjugate_gradient_enqueue(eps, cap, sweeps, report) is report
+    torch.cuda.synchronize()
+    return report.cpu().numpy()
+
+
+def compare(gs, ge, reps, rep, what, constant=False):
+    for c in range(gs.C):
+        assert np.array_equal(bits(ge.get_x(c)), bits(gs.get_x(c))), (what, c, "x")
+        assert rep[c, 0] == reps[c].iterations and rep[c, 1] == float(reps[c].converged), (what, c, rep[c], reps[c].iterations, reps[c].converged)
+        assert rep[c, 1] in (0.0, 1.0)
+        assert bits(rep[c, 2]) == bits(reps[c].last_l1_step), (what, c, rep[c, 2], reps[c].last_l1_step)
+        if constant:
+            bm, xm, n = gs.mg_nullspace_info(c)
+            assert bits(rep[c, 3]) == bits(bm) and bits(rep[c, 4]) == bits(xm), (what, c, rep[c], bm, xm)
+            assert n == gs.W * gs.H
+        else:
+            assert bits(rep[c, 3]) == 0 and bits(rep[c, 4]) == 0, (what, c, rep[c])
+        assert bits(rep[c, 5]) == 0, (what, c, rep[c])
+
+
+def pair(kind, W, H, Cn, seed, cap=40, sweeps=0, eps_rel=1e-10, eps=None, **system):
+    """The synchronous call on one handle, prepare + enqueue on its twin: (reports, the enqueue report, both handles)"""
+    gs, ge = make(kind, W, H, Cn), make(kind, W, H, Cn)
+    norm = [load(g, seed, **system) for g in (gs, ge)]
+    assert norm[0] == norm[1]
+    eps = eps_rel * norm[0] if eps is None else eps
+    reps = gs.mg_conjugate_gradient(eps, cap, sweeps)
+    rep = enqueue(ge, eps, cap, sweeps)
+    print(f"{kind} {W}x{H}x{Cn} cap {cap}: iterations {[r.iterations for r in reps]}, converged {[r.converged for r in reps]}")
+    compare(gs, ge, reps, rep, f"{kind} {W}x{H}x{Cn}", constant=kind == "floating")
+    return reps, rep, gs, ge
+
+
+# ---- 1. every kind and mode: the bits of the synchronous call ------------------------------------------------------------
+CASES = [("structured", 64, 48, 1), ("structured", 257, 131, 3), ("mask", 257, 131, 1),
+         ("galerkin", 257, 131, 3), ("rescaled", 257, 131, 3), ("f32", 257, 131, 3), ("batched", 257, 131, 3),
+         ("line", 257, 131, 3), ("per_channel", 257, 131, 3), ("per_channel_batched", 257, 131, 3), ("fixed", 257, 131, 3),
+         ("rescaled", 33, 1, 1), ("rescaled", 3, 2, 1)]
+
+
+@pytest.mark.parametrize("kind,W,H,Cn", CASES)
+def test_enqueue_equals_the_synchronous_call(kind, W, H, Cn):
+    reps, rep, gs, ge = pair(kind, W, H, Cn, 100 + W)
+    assert all(r.iterations > 0 for r in reps)
+    gs.close(), ge.close()
+
+
+@pytest.mark.parametrize("W,H,Cn", [(64, 48, 1), (257, 131, 3)])
+def test_floating_system_in_constant_mode(W, H, Cn):
+    """b + 1e-3 is not consistent: the mode solves its mean-free part; the report carries the two means"""
+    reps, rep, gs, ge = pair("floating", W, H, Cn, 200 + W, cap=100, shift=1e-3)
+    assert all(r.converged and r.iterations > 0 for r in reps)
+    for c in range(Cn):
+        with pytest.raises(capi.CcpError) as err:             # the means of an enqueue solve are in the report, not on the host
+            ge.mg_nullspace_info(c)
+        assert err.value.status == STATE
+    gs.close(), ge.close()
+
+
+def test_explicit_sweep_counts():
+    for sweeps in (1, 4):
+        _, _, gs, ge = pair("rescaled", 70, 40, 2, 300 + sweeps, sweeps=sweeps)
+        gs.close(), ge.close()
+
+
+# ---- 2. the stops --------------------------------------------------------------------------------------------------------
+SCALES = [(0, 1.0), (0, 1e-6), (0, 0.0)]
+
+
+@pytest.mark.parametrize("kind", ["rescaled", "batched"])
+def test_stops(kind):
+    W, H, Cn = 257, 131, 3
+    # a cap of 3 from a random x0 (every channel's residual is large, the zero channel's too): nothing has converged
+    reps, rep, gs, ge = pair(kind, W, H, Cn, 700, cap=3, scales=SCALES)
+    assert [r.iterations for r in reps] == [3] * Cn and not any(r.converged for r in reps)
+    gs.close(), ge.close()
+    # a cap of 40: every channel stops earlier, at its own iteration; the launches after that are no-ops
+    reps, rep, gs, ge = pair(kind, W, H, Cn, 700, cap=40, scales=SCALES, zero_x=True)
+    its = [r.iterations for r in reps]
+    assert all(r.converged for r in reps) and its[2] == 0 and 0 < its[1] < its[0] < 40, its
+    assert not np.any(ge.get_x(2))
+    # an x0 that already satisfies epsilon (the solution just found, against a looser epsilon so that the residual formed
+    # afresh from x passes it whatever the recurrence's last one was): 0 iterations, converged, x untouched
+    eps = 1e-6 * float(np.linalg.norm(gs.get_b(0)))
+    solved = [gs.get_x(c) for c in range(Cn)]
+    again = gs.mg_conjugate_gradient(eps, 40, 0)
+    rep = torch.full((Cn, 6), SENTINEL, dtype=torch.float64, device=DEV)
+    ge.mg_conjugate_gradient_enqueue(eps, 40, 0, rep)        # still prepared: the solve before changed nothing of that
+    torch.cuda.synchronize()
+    assert [r.iterations for r in again] == [0] * Cn and all(r.converged for r in again)
+    compare(gs, ge, again, rep.cpu().numpy(), f"{kind} solved start")
+    for c in range(Cn):
+        assert np.array_equal(bits(ge.get_x(c)), bits(solved[c]))
+    gs.close(), ge.close()
+    # max_iteration = 0: the start-up steps alone
+    reps, rep, gs, ge = pair(kind, W, H, Cn, 700, cap=0, scales=SCALES)
+    assert [r.iterations for r in reps] == [0] * Cn and not any(r.converged for r in reps)
+    assert np.array_equal(bits(ge.get_x(0)), bits(gs.get_x(0)))
+    gs.close(), ge.close()
+
+
+# ---- 3. the statuses -----------------------------------------------------------------------------------------------------
+def snapshot(g):
+    return [bits(g.get_x(c)).copy() for c in range(g.C)] + [bits(g.get_b(c)).copy() for c in range(g.C)]
+
+
+def refused(g, status, cap=10, sweeps=0):
+    """The enqueue call returns `status` and leaves x, b and the report as they were"""
+    before = snapshot(g)
+    report = torch.full((g.C, 6), SENTINEL, dtype=torch.float64, device=DEV)
+    with pytest.raises(capi.CcpError) as err:
+        g.mg_conjugate_gradient_enqueue(1e-3, cap, sweeps, report)
+    torch.cuda.synchronize()
+    assert err.value.status == status
+    assert bool((report == SENTINEL).all())
+    for a, b in zip(snapshot(g), before):
+        assert np.array_equal(a, b)
+
+
+def test_enqueue_needs_a_matching_prepare():
+    W, H, Cn = 70, 40, 2
+    g = make("rescaled", W, H, Cn)
+    load(g, 5)
+    refused(g, STATE)                                        # never prepared
+    g.mg_prepare(0)
+    refused(g, STATE, sweeps=3)                              # prepared with other sweeps (0 means 2)
+    refused(g, BAD_ARG, cap=4097)
+    refused(g, BAD_ARG, cap=-1)
+    g.mg_set_precision("f32")
+    refused(g, STATE)                                        # the mode setter dropped what prepare built
+    g.mg_prepare(0)
+    wx, wy, lam = screened(W, H, 9)
+    g.set_weights(wx, wy, lam)
+    refused(g, STATE)                                        # ... and so does an operator setter
+    g.mg_prepare(0)
+    g.mg_set_channels("batched")
+    g.mg_set_channels("sequential")
+    refused(g, STATE)                                        # back at the prepared mode, but its vectors are gone
+    g.mg_prepare(0)
+    report = torch.full((Cn, 6), SENTINEL, dtype=torch.float64, device=DEV)
+    g.mg_conjugate_gradient_enqueue(1e-3, 30, 0, report)     # and prepared again it solves
+    g.mg_conjugate_gradient_enqueue(1e-3, 30, 0, None)       # report is optional
+    torch.cuda.synchronize()
+    assert bool((report[:, 1] == 1.0).all())
+    g.close()
+
+
+def test_prepare_returns_the_solves_refusals():
+    W, H, Cn = 70, 40, 2
+    g = make("rescaled", W, H, Cn)
+    load(g, 6)
+    before = snapshot(g)
+    g.mg_set_channels("batched")
+    g.mg_set_precision("f32")
+    with pytest.raises(capi.CcpError) as err:
+        g.mg_prepare(0)
+    assert err.value.status == UNSUPPORTED
+    refused(g, STATE)
+    g.mg_set_precision("f64")                                # repaired: it solves again
+    rep = enqueue(g, 1e-3, 30, 0)
+    assert (rep[:, 1] == 1.0).all()
+    g.close()
+    s = make("structured", W, H, 1)
+    load(s, 7)
+    before = snapshot(s)
+    s.mg_set_smoother("line")
+    with pytest.raises(capi.CcpError) as err:
+        s.mg_prepare(0)
+    assert err.value.status == UNSUPPORTED
+    for a, b in zip(snapshot(s), before):
+        assert np.array_equal(a, b)
+    s.mg_set_smoother("point")
+    rep = enqueue(s, 1e-3, 30, 0)
+    assert rep[0, 1] == 1.0
+    s.close()
+    w = capi.Grid(W, H, 1, weighted=True)                    # no operator
+    with pytest.raises(capi.CcpError) as err:
+        w.mg_prepare(0)
+    assert err.value.status == STATE
+    with pytest.raises(capi.CcpError) as err:
+        w.mg_prepare(5)
+    assert err.value.status in (STATE, BAD_ARG)
+    w.close()
+
+
+def test_report_views_are_checked_before_anything_is_enqueued():
+    W, H, Cn = 70, 40, 2
+    g = make("rescaled", W, H, Cn)
+    load(g, 8)
+    g.mg_prepare(0)
+    before = snapshot(g)
+    good = torch.full((Cn, 6), SENTINEL, dtype=torch.float64, device=DEV)
+    call = lambda arr: g.L.ccp_grid_mg_conjugate_gradient_enqueue(g.h, 1e-3, 10, 0, C.byref(arr))
+    assert call(capi.DeviceArray(good.data_ptr(), capi.DTYPE_F32, 0, 0, 6, 1, 0)) == BAD_ARG          # dtype
+    assert call(capi.DeviceArray(good.data_ptr(), capi.DTYPE_F64, 0, 0, 1 << 40, 1, 0)) == BAD_ARG    # channel 1 beyond the allocation
+    assert call(capi.DeviceArray(good.data_ptr(), capi.DTYPE_F64, 0, 0, 3, 1, 0)) == BAD_ARG          # rows overlap
+    assert call(capi.DeviceArray(good.data_ptr(), capi.DTYPE_F64, 1, 0, 6, 1, 0)) == BAD_ARG          # reserved
+    assert call(capi.DeviceArray(None, capi.DTYPE_F64, 0, 0, 6, 1, 0)) == BAD_ARG
+    host = torch.zeros((Cn, 6), dtype=torch.float64)
+    assert call(capi.DeviceArray(host.data_ptr(), capi.DTYPE_F64, 0, 0, 6, 1, 0)) == BAD_ARG          # host memory
+    with pytest.raises(ValueError):
+        g.mg_conjugate_gradient_enqueue(1e-3, 10, 0, good[:1])
+    with pytest.raises(ValueError):
+        g.mg_conjugate_gradient_enqueue(1e-3, 10, 0, good.to(torch.float32))
+    torch.cuda.synchronize()
+    assert bool((good == SENTINEL).all())
+    for a, b in zip(snapshot(g), before):
+        assert np.array_equal(a, b)
+    # a transposed (strided) report is as good as a contiguous one
+    wide = torch.full((6, Cn), SENTINEL, dtype=torch.float64, device=DEV)
+    g.mg_conjugate_gradient_enqueue(1e-3, 30, 0, wide.t())
+    g.fill_x(0.0)
+    g.mg_conjugate_gradient_enqueue(1e-3, 30, 0, good)
+    torch.cuda.synchronize()
+    assert bool((wide[1] == 1.0).all()) and bool((good[:, 1] == 1.0).all()) and bool((wide[5] == 0.0).all())
+    g.close()
+
+
+# ---- 4. tensor_ops.WeightedSolver ----------------------------------------------------------------------------------------
+def images(W, H, Cn, seed):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    gx, gy = (torch.randn(H, W, Cn, generator=g, dtype=torch.float32).to(DEV) for _ in range(2))
+    f = (255.0 * torch.rand(H, W, Cn, generator=g, dtype=torch.float64)).to(DEV)
+    return gx, gy, f
+
+
+def test_weighted_solver_equals_weighted_solve():
+    W, H, Cn = 257, 131, 3
+    wx, wy, lam = (torch.from_numpy(a).to(DEV) for a in screened(W, H, 77))
+    gx, gy, f = images(W, H, Cn, 1)
+    eps = 1e-6
+    want = tensor_ops.weighted_solve(gx, gy, f, 40, wx=wx, wy=wy, data_weight=lam, out_dtype=torch.float64, epsilon=eps, hierarchy="rescaled")
+    with tensor_ops.WeightedSolver(H, W, Cn, DEV, iterations=40, epsilon=eps) as solver:
+        solver.set_operator(wx, wy, lam)
+        report = torch.full((Cn, 6), SENTINEL, dtype=torch.float64, device=DEV)
+        got, rep = solver.solve(gx, gy, f, x0=f, report=report)
+        assert rep is report
+        out = torch.empty(H, W, Cn, dtype=torch.float64, device=DEV)
+        again, _ = solver.solve(gx, gy, f, x0=f, out=out)    # the handle lives on: a second solve, into `out`
+        torch.cuda.synchronize()
+        assert again is out
+        assert torch.equal(tbits(got), tbits(want)) and torch.equal(tbits(out), tbits(want))
+        assert bool((report[:, 1] == 1.0).all()) and bool((report[:, 0] > 0).all()) and bool((report[:, 0] < 40).all())
+        zero, _ = solver.solve(gx, gy, f)                    # from x = 0: the same system, another path to its solution
+        assert float((zero - want).abs().max()) < 1e-3
+
+
+def constrained_inputs(W, H, Cn):
+    wx, wy, lam = (torch.from_numpy(a).to(torch.float64).to(DEV) for a in screened(W, H, 78))
+    fixed = torch.from_numpy(mh.ellipse_fixed(W, H)).to(DEV)
+    gx, gy, f = images(W, H, Cn, 2)
+    values = images(W, H, Cn, 3)[2]
+    return wx, wy, lam, fixed, gx, gy, f, values
+
+
+def leaves(*ts):
+    return [t.clone().requires_grad_(True) for t in ts]
+
+
+def test_weighted_solver_gradients_equal_weighted_solve_grad():
+    W, H, Cn = 64, 48, 2
+    wx, wy, lam, fixed, gx, gy, f, values = constrained_inputs(W, H, Cn)
+    weight = images(W, H, Cn, 4)[2]
+    weight2 = images(W, H, Cn, 5)[2]
+    eps, cap = 1e-8, 60
+
+    def reference(wgt):
+        a = leaves(gx, gy, f, values)
+        u = tensor_ops.weighted_solve_grad(a[0], a[1], a[2], cap, wx=wx, wy=wy, data_weight=lam, values=a[3], fixed=fixed, epsilon=eps)
+        (u * wgt).sum().backward()
+        return u.detach(), [t.grad for t in a]
+
+    u_ref, g_ref = reference(weight)
+    u_ref2, g_ref2 = reference(weight2)
+    with tensor_ops.WeightedSolver(H, W, Cn, DEV, iterations=cap, epsilon=eps) as solver:
+        solver.set_operator(wx, wy, lam, fixed)
+        a = leaves(gx, gy, f, values)
+        rep, arep = (torch.full((Cn, 6), SENTINEL, dtype=torch.float64, device=DEV) for _ in range(2))
+        u, r = solver.solve_grad(a[0], a[1], a[2], a[3], x0=f, report=rep, adjoint_report=arep)
+        assert r is rep and u.grad_fn is not None
+        (u * weight).sum().backward()
+        torch.cuda.synchronize()
+        assert torch.equal(tbits(u), tbits(u_ref))
+        assert bool((rep[:, 1] == 1.0).all()) and bool((arep[:, 1] == 1.0).all())
+        for t, want, name in zip(a, g_ref, ("gx", "gy", "f", "values")):
+            assert t.grad is not None and t.grad.dtype == want.dtype, name
+            assert torch.equal(t.grad.contiguous().view(torch.uint8), want.contiguous().view(torch.uint8)), name
+        # two forwards, then both backwards: each pair's gradients are those of the pair run alone
+        a1, a2 = leaves(gx, gy, f, values), leaves(gx, gy, f, values)
+        u1, _ = solver.solve_grad(a1[0], a1[1], a1[2], a1[3], x0=f)
+        u2, _ = solver.solve_grad(a2[0], a2[1], a2[2], a2[3], x0=f)
+        (u1 * weight).sum().backward()
+        (u2 * weight2).sum().backward()
+        torch.cuda.synchronize()
+        for got, want in ((a1, g_ref), (a2, g_ref2)):
+            for t, w, name in zip(got, want, ("gx", "gy", "f", "values")):
+                assert torch.equal(t.grad.contiguous().view(torch.uint8), w.contiguous().view(torch.uint8)), name
+    with pytest.raises(RuntimeError):
+        tensor_ops.WeightedSolver(H, W, Cn, DEV, iterations=5, epsilon=eps).solve(gx, gy, f)   # no operator yet
