@@ -26,43 +26,40 @@ MG_HIERARCHY_GALERKIN, MG_HIERARCHY_RESCALED = 0, 1
 MG_HIERARCHIES = {"galerkin": MG_HIERARCHY_GALERKIN, "rescaled": MG_HIERARCHY_RESCALED}
 MG_PRECISIONS = {"f64": 0, "f32": 1}
 MG_CHANNELS = {"sequential": 0, "batched": 1}
+MG_SMOOTHERS = {"point": 0, "line": 1}
+MG_NULLSPACES = {"none": 0, "constant": 1}
+# The multigrid options of a grid handle, in the order Grid.mg_configure applies them: option -> (its names and their
+# CCP_MG_* integers, whether an integer that is none of them is left to the library -- CcpError, not ValueError).  The
+# C functions are ccp_grid_mg_set_<option> and ccp_grid_mg_get_<option>.
+MG_OPTIONS = {"hierarchy": (MG_HIERARCHIES, True), "precision": (MG_PRECISIONS, True), "channels": (MG_CHANNELS, False),
+              "smoother": (MG_SMOOTHERS, False), "nullspace": (MG_NULLSPACES, False)}
+
+
+def _mg_value(option, value):
+    """The CCP_MG_* integer of a name of `option` (or of one of its integers): ValueError otherwise."""
+    names, any_integer = MG_OPTIONS[option]
+    if isinstance(value, str):
+        if value not in names:
+            raise ValueError(f"{option} must be one of {sorted(names)}, not {value!r}")
+        return names[value]
+    if not any_integer and int(value) not in names.values():
+        raise ValueError(f"{option} must be one of {sorted(names.values())}, not {value!r}")
+    return int(value)
 
 
 def mg_channels_value(mode):
     """The CCP_MG_CHANNELS_* integer of "sequential" / "batched" (or of an integer of MG_CHANNELS): ValueError otherwise."""
-    if isinstance(mode, str):
-        if mode not in MG_CHANNELS:
-            raise ValueError(f"channels must be one of {sorted(MG_CHANNELS)}, not {mode!r}")
-        return MG_CHANNELS[mode]
-    if int(mode) not in MG_CHANNELS.values():
-        raise ValueError(f"channels must be one of {sorted(MG_CHANNELS.values())}, not {mode!r}")
-    return int(mode)
-MG_SMOOTHERS = {"point": 0, "line": 1}
+    return _mg_value("channels", mode)
 
 
 def mg_smoother_value(kind):
     """The CCP_MG_SMOOTHER_* integer of "point" / "line" (or of an integer of MG_SMOOTHERS): ValueError otherwise."""
-    if isinstance(kind, str):
-        if kind not in MG_SMOOTHERS:
-            raise ValueError(f"smoother must be one of {sorted(MG_SMOOTHERS)}, not {kind!r}")
-        return MG_SMOOTHERS[kind]
-    if int(kind) not in MG_SMOOTHERS.values():
-        raise ValueError(f"smoother must be one of {sorted(MG_SMOOTHERS.values())}, not {kind!r}")
-    return int(kind)
-
-
-MG_NULLSPACES = {"none": 0, "constant": 1}
+    return _mg_value("smoother", kind)
 
 
 def mg_nullspace_value(kind):
     """The CCP_MG_NULLSPACE_* integer of "none" / "constant" (or of an integer of MG_NULLSPACES): ValueError otherwise."""
-    if isinstance(kind, str):
-        if kind not in MG_NULLSPACES:
-            raise ValueError(f"nullspace must be one of {sorted(MG_NULLSPACES)}, not {kind!r}")
-        return MG_NULLSPACES[kind]
-    if int(kind) not in MG_NULLSPACES.values():
-        raise ValueError(f"nullspace must be one of {sorted(MG_NULLSPACES.values())}, not {kind!r}")
-    return int(kind)
+    return _mg_value("nullspace", kind)
 
 
 ORDER_LEXICOGRAPHIC = 0
@@ -257,16 +254,9 @@ def load() -> C.CDLL:
     L.ccp_grid_mg_prepare.argtypes = [vp, i32]
     L.ccp_grid_mg_conjugate_gradient_enqueue.argtypes = [vp, dbl, i32, i32, C.POINTER(DeviceArray)]
     L.ccp_grid_mg_level.argtypes = [vp, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
-    L.ccp_grid_mg_set_hierarchy.argtypes = [vp, i32]
-    L.ccp_grid_mg_get_hierarchy.argtypes = [vp, C.POINTER(i32)]
-    L.ccp_grid_mg_set_precision.argtypes = [vp, i32]
-    L.ccp_grid_mg_get_precision.argtypes = [vp, C.POINTER(i32)]
-    L.ccp_grid_mg_set_channels.argtypes = [vp, i32]
-    L.ccp_grid_mg_get_channels.argtypes = [vp, C.POINTER(i32)]
-    L.ccp_grid_mg_set_smoother.argtypes = [vp, i32]
-    L.ccp_grid_mg_get_smoother.argtypes = [vp, C.POINTER(i32)]
-    L.ccp_grid_mg_set_nullspace.argtypes = [vp, i32]
-    L.ccp_grid_mg_get_nullspace.argtypes = [vp, C.POINTER(i32)]
+    for option in MG_OPTIONS:
+        getattr(L, f"ccp_grid_mg_set_{option}").argtypes = [vp, i32]
+        getattr(L, f"ccp_grid_mg_get_{option}").argtypes = [vp, C.POINTER(i32)]
     L.ccp_grid_mg_nullspace_info.argtypes = [vp, i32, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int64)]
     L.ccp_debug_mgb_tile_lds.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.ccp_csr_apply_to_vector.argtypes = [vp, vp, vp]
@@ -803,62 +793,63 @@ class Grid:
         """x := M^-1 b (one V-cycle per channel; diagnostic)."""
         check(self.L.ccp_grid_mg_apply(self.h, smoothing_sweeps), "ccp_grid_mg_apply")
 
+    def _mg_set(self, option, value):
+        name = f"ccp_grid_mg_set_{option}"
+        check(getattr(self.L, name)(self.h, _mg_value(option, value)), name)
+
+    def _mg_get(self, option):
+        value, name = C.c_int32(), f"ccp_grid_mg_get_{option}"
+        check(getattr(self.L, name)(self.h, C.byref(value)), name)
+        return next(n for n, v in MG_OPTIONS[option][0].items() if v == value.value)
+
+    def mg_configure(self, *, hierarchy=None, precision=None, channels=None, smoother=None, nullspace=None):
+        """mg_set_hierarchy, _precision, _channels, _smoother and _nullspace, in that order, each for an option that is
+        given.  An option left at None is not set: its setter is not called, so hierarchy and nullspace, which only a
+        weighted handle takes, can be left out on any other."""
+        for option, value in zip(MG_OPTIONS, (hierarchy, precision, channels, smoother, nullspace)):
+            if value is not None:
+                self._mg_set(option, value)
+
     def mg_set_hierarchy(self, kind):
         """The hierarchy kind of a weighted handle: "galerkin" (the default: coarse correction scaled by 2) or "rescaled"
         (edge weights halved per level, correction unscaled: the one to choose with data weights > 0), or the integers
         MG_HIERARCHY_*.  A change drops the cached hierarchy."""
-        if isinstance(kind, str):
-            if kind not in MG_HIERARCHIES:
-                raise ValueError(f"hierarchy must be one of {sorted(MG_HIERARCHIES)}, not {kind!r}")
-            kind = MG_HIERARCHIES[kind]
-        check(self.L.ccp_grid_mg_set_hierarchy(self.h, int(kind)), "ccp_grid_mg_set_hierarchy")
+        self._mg_set("hierarchy", kind)
 
     @property
     def mg_hierarchy(self):
         """The handle's hierarchy kind: "galerkin" or "rescaled"."""
-        kind = C.c_int32()
-        check(self.L.ccp_grid_mg_get_hierarchy(self.h, C.byref(kind)), "ccp_grid_mg_get_hierarchy")
-        return next(name for name, value in MG_HIERARCHIES.items() if value == kind.value)
+        return self._mg_get("hierarchy")
 
     def mg_set_precision(self, precision):
         """The precision of the multigrid preconditioner: "f64" (the default) or "f32" (the V-cycle in float, the outer
         PCG loop and its stop test in fp64: same answer, for weighted handles best with the "rescaled" hierarchy), or the
         integers of MG_PRECISIONS.  A change drops the cached hierarchy."""
-        if isinstance(precision, str):
-            if precision not in MG_PRECISIONS:
-                raise ValueError(f"precision must be one of {sorted(MG_PRECISIONS)}, not {precision!r}")
-            precision = MG_PRECISIONS[precision]
-        check(self.L.ccp_grid_mg_set_precision(self.h, int(precision)), "ccp_grid_mg_set_precision")
+        self._mg_set("precision", precision)
 
     def mg_precision(self):
         """The handle's preconditioner precision: "f64" or "f32"."""
-        value = C.c_int32()
-        check(self.L.ccp_grid_mg_get_precision(self.h, C.byref(value)), "ccp_grid_mg_get_precision")
-        return next(name for name, v in MG_PRECISIONS.items() if v == value.value)
+        return self._mg_get("precision")
 
     def mg_set_channels(self, mode):
         """How the multigrid PCG goes through the handle's channels: "sequential" (the default: one loop per channel) or
         "batched" (one loop, every launch serves all channels; every channel gets the sequential call's bits), or the
         integers of MG_CHANNELS.  A change drops the cached PCG vectors and keeps the hierarchy."""
-        check(self.L.ccp_grid_mg_set_channels(self.h, mg_channels_value(mode)), "ccp_grid_mg_set_channels")
+        self._mg_set("channels", mode)
 
     def mg_channels(self):
         """The handle's channel mode: "sequential" or "batched"."""
-        value = C.c_int32()
-        check(self.L.ccp_grid_mg_get_channels(self.h, C.byref(value)), "ccp_grid_mg_get_channels")
-        return next(name for name, v in MG_CHANNELS.items() if v == value.value)
+        return self._mg_get("channels")
 
     def mg_set_smoother(self, kind):
         """The V-cycle's smoother: "point" (the default: red-black Gauss-Seidel) or "line" (alternating zebra line
         relaxation on the levels above the tail; weighted handles, fp64, sequential channels: anything else is refused
         at the solve), or the integers of MG_SMOOTHERS.  With "line" smoothing_sweeps 0 means 1 sweep."""
-        check(self.L.ccp_grid_mg_set_smoother(self.h, mg_smoother_value(kind)), "ccp_grid_mg_set_smoother")
+        self._mg_set("smoother", kind)
 
     def mg_smoother(self):
         """The handle's smoother: "point" or "line"."""
-        value = C.c_int32()
-        check(self.L.ccp_grid_mg_get_smoother(self.h, C.byref(value)), "ccp_grid_mg_get_smoother")
-        return next(name for name, v in MG_SMOOTHERS.items() if v == value.value)
+        return self._mg_get("smoother")
 
     def mg_set_nullspace(self, kind):
         """The null space the multigrid PCG accounts for (weighted handles): "none" (the default) or "constant" -- a
@@ -866,13 +857,11 @@ class Grid:
         mean-free vectors, and x keeps the mean it came with; anything else is refused at the solve, as are batched
         channels and the line smoother on a canvas whose hierarchy has a line-smoothed level (level 0, or a coarse level
         with a side > 32) of one row or one column -- or the integers of MG_NULLSPACES."""
-        check(self.L.ccp_grid_mg_set_nullspace(self.h, mg_nullspace_value(kind)), "ccp_grid_mg_set_nullspace")
+        self._mg_set("nullspace", kind)
 
     def mg_get_nullspace(self):
         """The handle's null-space mode: "none" or "constant"."""
-        value = C.c_int32()
-        check(self.L.ccp_grid_mg_get_nullspace(self.h, C.byref(value)), "ccp_grid_mg_get_nullspace")
-        return next(name for name, v in MG_NULLSPACES.items() if v == value.value)
+        return self._mg_get("nullspace")
 
     def mg_nullspace_info(self, channel: int = 0):
         """(mean(b), mean of the returned x, W * H) of the last "constant"-mode solve of channel `channel`."""

@@ -156,11 +156,8 @@ struct ccp_grid {
     bool per_channel = false;
     int op_sets = 1;
     long pc_fixed[kMaxChannels] = {}, pc_live[kMaxChannels] = {}, pc_edges[kMaxChannels] = {};
-    int mg_kind = CCP_MG_HIERARCHY_GALERKIN;   // ccp_grid_mg_set_hierarchy (weighted handles; survives ccp_grid_set_weights_*)
-    int mg_channels = CCP_MG_CHANNELS_SEQUENTIAL;   // ccp_grid_mg_set_channels (survives what mg_precision survives, and set_precision)
-    int mg_smoother = CCP_MG_SMOOTHER_POINT;   // ccp_grid_mg_set_smoother (survives what mg_channels survives, and set_channels)
-    int mg_precision = CCP_MG_PRECISION_F64;   // ccp_grid_mg_set_precision (survives set_weights, set_mask and set_hierarchy)
-    MgNullspace mg_nullspace;                  // ccp_grid_mg_set_nullspace (the value survives what mg_smoother survives; the rest goes with the operator)
+    MgConfig mg_cfg;                           // ccp_grid_mg_set_* (ccp_grid_mg_view.hpp)
+    MgNullspace mg_nullspace;                  // goes with the operator (drop_operator)
 };
 
 namespace {
@@ -794,8 +791,7 @@ int zero_unmasked(ccp_grid *g, double *plane)
 int mask_replaced(ccp_grid *g)
 {
     g->live_T = -1;                                      // the tile census belongs to the old mask
-    mg_release(g->mg);                                   // ... and so does the multigrid hierarchy
-    g->mg = nullptr;
+    mg_release(&g->mg);                                  // ... and so does the multigrid hierarchy
     CCP_TRY(zero_unmasked(g, g->x.p));
     CCP_TRY(zero_unmasked(g, g->b.p));
     if (g->x_alt.p) CCP_TRY(zero_unmasked(g, g->x_alt.p));
@@ -1169,7 +1165,7 @@ try {
     if (g->edge_flag) (void)hipFree(g->edge_flag);
     if (g->edge_timeout) (void)hipHostFree(g->edge_timeout);
     if (g->lex_order_pin) (void)hipHostFree(g->lex_order_pin);
-    mg_release(g->mg);
+    mg_release(&g->mg);
     delete g;
     return CCP_OK;
 } CCP_ABI_CATCH
@@ -1293,10 +1289,7 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     v->op_channels = g->weighted && g->has_op && g->per_channel ? g->desc.channels : 1;
     v->op_stride = 4 * n;
     v->lam_stride = g->has_fixed ? 3 * n : 4 * n;
-    v->hierarchy_kind = g->mg_kind;
-    v->precision = g->mg_precision;
-    v->channels_mode = g->mg_channels;
-    v->smoother = g->mg_smoother;
+    v->cfg = g->mg_cfg;
     v->ns = &g->mg_nullspace;
     v->stream = g->stream;
     v->device = g->device;
@@ -1307,45 +1300,13 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     return CCP_OK;
 }
 
-int ccp::grid_mg_hierarchy_slot(ccp_grid *g, bool *weighted, int **kind, MgHierarchy ***cache)
+int ccp::grid_mg_slot(ccp_grid *g, GridMgSlot *s)
 {
     CCP_TRY(bind(g));
-    *weighted = g->weighted;
-    *kind = &g->mg_kind;
-    *cache = &g->mg;
-    return CCP_OK;
-}
-
-int ccp::grid_mg_precision_slot(ccp_grid *g, int **precision, MgHierarchy ***cache, bool *row_block)
-{
-    CCP_TRY(bind(g));
-    *precision = &g->mg_precision;
-    *cache = &g->mg;
-    *row_block = g->desc.ghost != 0 || g->desc.row_count < g->desc.height;
-    return CCP_OK;
-}
-
-int ccp::grid_mg_channels_slot(ccp_grid *g, int **mode, MgHierarchy ***cache)
-{
-    CCP_TRY(bind(g));
-    *mode = &g->mg_channels;
-    *cache = &g->mg;
-    return CCP_OK;
-}
-
-int ccp::grid_mg_smoother_slot(ccp_grid *g, int **kind, MgHierarchy ***cache)
-{
-    CCP_TRY(bind(g));
-    *kind = &g->mg_smoother;
-    *cache = &g->mg;
-    return CCP_OK;
-}
-
-int ccp::grid_mg_nullspace_slot(ccp_grid *g, bool *weighted, MgNullspace **ns)
-{
-    CCP_TRY(bind(g));
-    *weighted = g->weighted;
-    *ns = &g->mg_nullspace;
+    s->cfg = &g->mg_cfg;
+    s->cache = &g->mg;
+    s->weighted = g->weighted;
+    s->row_block = g->desc.ghost != 0 || g->desc.row_count < g->desc.height;
     return CCP_OK;
 }
 
@@ -2304,8 +2265,7 @@ int ccp_grid_attach_comm(ccp_grid *g, ccp_comm *c)
 try {
     CCP_TRY(not_weighted(g));
     CCP_TRY(bind(g));
-    mg_release(g->mg);                               // the multigrid hierarchy belongs to the partition
-    g->mg = nullptr;
+    mg_release(&g->mg);                              // the multigrid hierarchy belongs to the partition
     if (!c) {                                        // detach
         g->comm = nullptr;
         g->part.clear();
@@ -3311,8 +3271,7 @@ namespace {
 // a new operator is coming: the old one, its counts and the hierarchy built on it go
 void drop_operator(ccp_grid *g)
 {
-    mg_release(g->mg);
-    g->mg = nullptr;
+    mg_release(&g->mg);
     g->has_op = g->has_fixed = false;
     g->per_channel = false;
     g->mg_nullspace.forget();

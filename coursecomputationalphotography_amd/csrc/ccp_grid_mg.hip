@@ -94,8 +94,9 @@ struct MgHierarchy {
     PcgWork bat;
     double *barr(int k, int which) { return bstore.p + bbase[k] + (long)which * bC * size[k]; }   // 0 b, 1 z, 2 t: channel ch at + ch * size[k]
     // CCP_MG_SMOOTHER_LINE (ccp_grid_mgl.hpp): the smoother of the levels above the tail, taken from the handle at every
-    // call (hierarchy), and the three work planes of the line solves, made at the first line V-cycle (line_planes): each
-    // as long as the largest level above the tail, lwork holds them one after the other.
+    // call (hierarchy: whole_levels is handed the hierarchy by the steps objects, which know no view), and the three work
+    // planes of the line solves, made at the first line V-cycle (line_planes): each as long as the largest level above
+    // the tail, lwork holds them one after the other.
     int smoother = CCP_MG_SMOOTHER_POINT;
     long lplane = 0;
     DevBuf<double> lwork;
@@ -106,11 +107,13 @@ struct MgHierarchy {
     DevBuf<double> nspart;
     // ccp_grid_mg_prepare / ccp_grid_mg_conjugate_gradient_enqueue (ccp_grid_mge.hpp): the enqueue solve's states, one per
     // channel in either channel mode (the report kernel reads them all after the last channel), and what the last
-    // successful prepare built for -- the enqueue call runs only on exactly that.  Everything else prepare builds is what
-    // the synchronous solve builds at its first call; a setter that frees part of it clears `prepared`.
+    // successful prepare built for (prepared_for) -- the enqueue call runs only on exactly that.  Everything else prepare
+    // builds is what the synchronous solve builds at its first call; a setter that frees part of it clears `prepared`
+    // (kOptions).
     DevBuf<CgState> estate;
     bool prepared = false;
-    int prep_nu = 0, prep_channels = 0, prep_mode = 0, prep_smoother = 0, prep_nullspace = 0;
+    MgConfig prep_cfg;
+    int prep_nu = 0, prep_channels = 0;
     // one operator (opC == 1) only: 0 d, 1 we, 2 ws, 3 b, 4 z, 5 t, 6 lambda (lam_slot).  The one-block code, which may see
     // opC > 1, asks coef() for a coefficient plane and vec() for a vector; the row-block code (never weighted) uses arr().
     double *arr(int k, int which) { return store.p + base[k] + (long)which * size[k]; }
@@ -147,7 +150,11 @@ struct MgHierarchy {
     }
 };
 
-void mg_release(MgHierarchy *h) { delete h; }
+void mg_release(MgHierarchy **cache)
+{
+    delete *cache;
+    *cache = nullptr;
+}
 
 }  // namespace ccp
 
@@ -183,14 +190,14 @@ int build(const GridMgView &v, MgHierarchy **out)
     std::unique_ptr<MgHierarchy> own(h);
     h->kind0 = v.weighted ? kMgCoarse : v.masked ? kMgMasked : kMgSolve;
     h->weighted = v.weighted;
-    h->precision = v.precision;
+    h->precision = v.cfg.precision;
     // (ccp_grid_mg_set_hierarchy drops the cached hierarchy when the kind changes: a cached one is of the handle's kind)
-    const bool rescaled = v.weighted && v.hierarchy_kind == CCP_MG_HIERARCHY_RESCALED;
+    const bool rescaled = v.weighted && v.cfg.hierarchy == CCP_MG_HIERARCHY_RESCALED;
     h->cs = rescaled ? 1.0 : 2.0;
     // per coarse level d, we, ws, the V-cycle's b, z, t, and a weighted handle's lambda; the fp32 V-cycle keeps its vectors
     // in float (narrow_levels), so its fp64 store holds the coefficients alone: what ccp_grid_mg_level returns and the
     // narrowing reads
-    const bool f32 = v.precision == CCP_MG_PRECISION_F32;
+    const bool f32 = v.cfg.precision == CCP_MG_PRECISION_F32;
     h->lam_slot = f32 ? 3 : 6;
     const int OC = v.weighted ? v.op_channels : 1;                  // operators: > 1 keeps the coefficients in cstore
     h->opC = OC;
@@ -280,16 +287,19 @@ int build(const GridMgView &v, MgHierarchy **out)
     return CCP_OK;
 }
 
+// Does the cached hierarchy h serve the one-block calls on this view?  (Not one built for the row-block calls, for
+// another precision or for another set of operators; a change of the hierarchy kind has deleted it: kOptions.)
+bool cache_serves(const GridMgView &v, const MgHierarchy &h)
+{
+    return !h.rowblocked && h.weighted == v.weighted && h.precision == v.cfg.precision && h.opC == (v.weighted ? v.op_channels : 1);
+}
+
 int hierarchy(const GridMgView &v, MgHierarchy **out)
 {
-    if (*v.cache && ((*v.cache)->rowblocked || (*v.cache)->weighted != v.weighted || (*v.cache)->precision != v.precision ||
-                     (*v.cache)->opC != (v.weighted ? v.op_channels : 1))) {   // built for the row-block calls: this call needs its own
-        mg_release(*v.cache);
-        *v.cache = nullptr;
-    }
+    if (*v.cache && !cache_serves(v, **v.cache)) mg_release(v.cache);
     if (!*v.cache) CCP_TRY(build(v, v.cache));
     *out = *v.cache;
-    (*out)->smoother = v.smoother;
+    (*out)->smoother = v.cfg.smoother;
     return CCP_OK;
 }
 
@@ -335,19 +345,10 @@ void post(int kind, hipStream_t s, const MgLevel &f, const double *b, const doub
 }
 
 // ---- CCP_MG_SMOOTHER_LINE (ccp_grid_mgl.hpp) ---------------------------------------------------------------------------
-// What the line mode serves: a weighted handle, the fp64 V-cycle, the sequential channel mode (the row-block calls refuse
-// it in prepare_rowblocked).
-int line_check(const GridMgView &v)
-{
-    if (v.smoother != CCP_MG_SMOOTHER_LINE) return CCP_OK;
-    if (!v.weighted || v.precision != CCP_MG_PRECISION_F64 || v.channels_mode != CCP_MG_CHANNELS_SEQUENTIAL) return CCP_ERR_UNSUPPORTED;
-    return CCP_OK;
-}
-
-// the work planes of the line solves, once per hierarchy
+// the work planes of the line solves, once per hierarchy (what the line mode serves: config_check)
 int line_planes(const GridMgView &v, MgHierarchy &h)
 {
-    if (h.smoother != CCP_MG_SMOOTHER_LINE || h.lwork.p) return CCP_OK;
+    if (v.cfg.smoother != CCP_MG_SMOOTHER_LINE || h.lwork.p) return CCP_OK;
     long n = 0;
     // level 0 is indexed by mg_at(pitch, x, y) < H * 2 * pitch, which is ch_stride on a weighted handle (one block, no ghost rows)
     for (int k = 0; k < h.tail && k < h.levels; ++k) n = std::max(n, k ? h.size[k] : (long)v.geom.ch_stride);
@@ -1118,10 +1119,7 @@ int build_rowblocked(const GridMgView &v, const Net &n, MgHierarchy **out)
 
 int hierarchy_rowblocked(const GridMgView &v, const Net &n, MgHierarchy **out)
 {
-    if (*v.cache && !(*v.cache)->rowblocked) {
-        mg_release(*v.cache);
-        *v.cache = nullptr;
-    }
+    if (*v.cache && !(*v.cache)->rowblocked) mg_release(v.cache);
     if (!*v.cache) CCP_TRY(build_rowblocked(v, n, v.cache));
     *out = *v.cache;
     return CCP_OK;
@@ -1200,9 +1198,9 @@ int prepare_rowblocked(ccp_grid *g, int32_t smoothing_sweeps, bool need_nu, Grid
 {
     CCP_TRY(grid_mg_view(g, v));
     if (v->weighted) return CCP_ERR_UNSUPPORTED;                   // weighted handles are single blocks
-    if (v->precision != CCP_MG_PRECISION_F64) return CCP_ERR_UNSUPPORTED;   // the fp32 V-cycle too (a world-1 communicator on a whole image)
-    if (v->channels_mode != CCP_MG_CHANNELS_SEQUENTIAL) return CCP_ERR_UNSUPPORTED;   // ... and the batched mode
-    if (v->smoother != CCP_MG_SMOOTHER_POINT) return CCP_ERR_UNSUPPORTED;   // ... and the line smoother
+    if (v->cfg.precision != CCP_MG_PRECISION_F64) return CCP_ERR_UNSUPPORTED;   // the fp32 V-cycle too (a world-1 communicator on a whole image)
+    if (v->cfg.channels != CCP_MG_CHANNELS_SEQUENTIAL) return CCP_ERR_UNSUPPORTED;   // ... and the batched mode
+    if (v->cfg.smoother != CCP_MG_SMOOTHER_POINT) return CCP_ERR_UNSUPPORTED;   // ... and the line smoother
     if (!v->comm) return CCP_ERR_STATE;
     n->api = rccl_api();
     if (!n->api) return CCP_ERR_RCCL;
@@ -1228,22 +1226,8 @@ int check_handle(ccp_grid *g, GridMgView *v)
 }
 
 // ---- CCP_MG_NULLSPACE_CONSTANT (ccp_grid_mgn.hpp) ----------------------------------------------------------------------
-bool constant_mode(const GridMgView &v) { return v.weighted && v.ns->kind == CCP_MG_NULLSPACE_CONSTANT; }
-
-// What the mode does not serve, before anything is built
-int nullspace_check(const GridMgView &v)
-{
-    if (!constant_mode(v)) return CCP_OK;
-    if (v.channels_mode != CCP_MG_CHANNELS_SEQUENTIAL) return CCP_ERR_UNSUPPORTED;
-    // A line-smoothed level of one row or one column: its one line along that direction has no neighbour across and no
-    // lambda (the coarse operators of a floating operator are floating too), so the exact line solve would be a solve of
-    // the singular operator itself.  Lines run on level 0 and on every coarse level above the tail, the levels with a side
-    // > kMgTailSide (build): 33x1 at level 0, 129x2 at its level 1 (65x1), 2048x32 at its level 5 (64x1).
-    if (v.smoother == CCP_MG_SMOOTHER_LINE)
-        for (int k = 0, W = v.geom.W, H = v.geom.H; k == 0 || W > kMgTailSide || H > kMgTailSide; ++k, W = (W + 1) / 2, H = (H + 1) / 2)
-            if (W == 1 || H == 1) return CCP_ERR_UNSUPPORTED;
-    return CCP_OK;
-}
+// (only a weighted handle can hold the value: kOptions)
+bool constant_mode(const GridMgView &v) { return v.cfg.nullspace == CCP_MG_NULLSPACE_CONSTANT; }
 
 // The mode's buffers, once per hierarchy, and the census of the handle's operators, once per installed operator (one
 // read-back): CCP_ERR_UNSUPPORTED unless every one is floating
@@ -1280,41 +1264,71 @@ MgnLay nullspace_layout(const GridMgView &v) { return MgnLay{v.geom.W, 2 * v.geo
 // ccp_grid_mg_conjugate_gradient is pcg_ready then pcg_solve; ccp_grid_mg_prepare is pcg_ready alone, and
 // ccp_grid_mg_conjugate_gradient_enqueue is pcg_solve alone in its enqueue form.
 
-// Everything the solve does before its first launch, in the handle's present configuration: the refusals, the hierarchy,
-// and whatever of the mode allocates or reads back, the PCG work set included.  Every step is a no-op once it is done.
-int pcg_ready(ccp_grid *g, int32_t max_iteration, int32_t smoothing_sweeps, GridMgView *v, int *nu, MgHierarchy **out)
+// The combinations of options that the one-block calls refuse, before anything is built (the row-block calls:
+// prepare_rowblocked).  The line smoother serves a weighted handle, the fp64 V-cycle and the sequential channel mode;
+// the constant null space the sequential channel mode.
+int config_check(const GridMgView &v)
 {
-    CCP_TRY(check_handle(g, v));
-    CCP_TRY(sweeps_arg(smoothing_sweeps, nu, v->smoother));
-    if (max_iteration < 0) return CCP_ERR_BAD_ARG;
-    const bool batched = v->channels_mode == CCP_MG_CHANNELS_BATCHED;
-    if (batched && v->precision == CCP_MG_PRECISION_F32) return CCP_ERR_UNSUPPORTED;
-    CCP_TRY(line_check(*v));
-    CCP_TRY(nullspace_check(*v));
+    const MgConfig &c = v.cfg;
+    const bool sequential = c.channels == CCP_MG_CHANNELS_SEQUENTIAL, line = c.smoother == CCP_MG_SMOOTHER_LINE;
+    if (!sequential && c.precision == CCP_MG_PRECISION_F32) return CCP_ERR_UNSUPPORTED;
+    if (line && (!v.weighted || c.precision != CCP_MG_PRECISION_F64 || !sequential)) return CCP_ERR_UNSUPPORTED;
+    if (!constant_mode(v)) return CCP_OK;
+    if (!sequential) return CCP_ERR_UNSUPPORTED;
+    // A line-smoothed level of one row or one column: its one line along that direction has no neighbour across and no
+    // lambda (the coarse operators of a floating operator are floating too), so the exact line solve would be a solve of
+    // the singular operator itself.  Lines run on level 0 and on every coarse level above the tail, the levels with a side
+    // > kMgTailSide (build): 33x1 at level 0, 129x2 at its level 1 (65x1), 2048x32 at its level 5 (64x1).
+    if (line)
+        for (int k = 0, W = v.geom.W, H = v.geom.H; k == 0 || W > kMgTailSide || H > kMgTailSide; ++k, W = (W + 1) / 2, H = (H + 1) / 2)
+            if (W == 1 || H == 1) return CCP_ERR_UNSUPPORTED;
+    return CCP_OK;
+}
+
+// Everything a V-cycle in the view's configuration needs that allocates or reads back.  Every step is a no-op once it is done.
+int vcycle_ready(const GridMgView &v, MgHierarchy **out)
+{
     MgHierarchy *h = nullptr;
-    CCP_TRY(hierarchy(*v, &h));
-    CCP_TRY(line_planes(*v, *h));
-    PcgArgs a{};                                                   // (the solve's shape: how many partial sums a channel needs)
-    const long n = v->geom.ch_stride;                              // one channel incl. pads (pads stay 0 in every vector)
-    if (batched) {
-        a.shape(v->geom.W, v->geom.H, n, (unsigned)((v->channels + kMgbGroup - 1) / kMgbGroup));
-        CCP_TRY(batched_levels(*v, *h));
-        CCP_TRY(h->bat.alloc(v->channels, n, std::max(a.apply_blocks, a.blocks), v->stream));
+    CCP_TRY(hierarchy(v, &h));
+    CCP_TRY(line_planes(v, *h));
+    if (v.cfg.channels == CCP_MG_CHANNELS_BATCHED) {
+        CCP_TRY(batched_levels(v, *h));
     } else {
-        if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(*v, *h));
-        CCP_TRY(nullspace_ready(*v, *h));
-        a.shape(v->geom.W, v->geom.H, n);
-        CCP_TRY(h->seq.alloc(1, n, std::max(a.apply_blocks, a.blocks), v->stream));
+        if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
+        CCP_TRY(nullspace_ready(v, *h));
     }
     *out = h;
     return CCP_OK;
+}
+
+// What ccp_grid_mg_apply (max_iteration 0) and the solve do alike before their first launch, in the handle's present
+// configuration: the refusals, then vcycle_ready.
+int call_ready(ccp_grid *g, int32_t max_iteration, int32_t smoothing_sweeps, GridMgView *v, int *nu, MgHierarchy **out)
+{
+    CCP_TRY(check_handle(g, v));
+    CCP_TRY(sweeps_arg(smoothing_sweeps, nu, v->cfg.smoother));
+    if (max_iteration < 0) return CCP_ERR_BAD_ARG;
+    CCP_TRY(config_check(*v));
+    return vcycle_ready(*v, out);
+}
+
+// Everything the solve does before its first launch: call_ready and the PCG work set of the channel mode.
+int pcg_ready(ccp_grid *g, int32_t max_iteration, int32_t smoothing_sweeps, GridMgView *v, int *nu, MgHierarchy **out)
+{
+    CCP_TRY(call_ready(g, max_iteration, smoothing_sweeps, v, nu, out));
+    const bool batched = v->cfg.channels == CCP_MG_CHANNELS_BATCHED;
+    PcgArgs a{};                                                   // (the solve's shape: how many partial sums a channel needs)
+    const long n = v->geom.ch_stride;                              // one channel incl. pads (pads stay 0 in every vector)
+    a.shape(v->geom.W, v->geom.H, n, batched ? (unsigned)((v->channels + kMgbGroup - 1) / kMgbGroup) : 1);
+    PcgWork &work = batched ? (*out)->bat : (*out)->seq;
+    return work.alloc(batched ? v->channels : 1, n, std::max(a.apply_blocks, a.blocks), v->stream);
 }
 
 // The solve itself on what pcg_ready left: the mode's steps object, and its loop once (batched) or per channel.
 // enqueue: the host-free form of the loop (pcg_enqueue), channel ch on the state h.estate[ch]; report is not used then.
 int pcg_solve(const GridMgView &v, MgHierarchy &h, double epsilon, int max_iteration, int nu, ccp_gs_report *report, bool enqueue)
 {
-    if (v.channels_mode == CCP_MG_CHANNELS_BATCHED) return pcg_batched(v, h, epsilon, max_iteration, nu, report, enqueue);
+    if (v.cfg.channels == CCP_MG_CHANNELS_BATCHED) return pcg_batched(v, h, epsilon, max_iteration, nu, report, enqueue);
     const long n = v.geom.ch_stride;
     // one channel after the other: b, x, the channel's operator and, on the enqueue form, the channel's own state
     auto channels = [&](auto &S, auto &&each) -> int {
@@ -1362,9 +1376,68 @@ int pcg_solve(const GridMgView &v, MgHierarchy &h, double epsilon, int max_itera
 // Is what the last ccp_grid_mg_prepare built what a solve of this view with `nu` sweeps runs on?
 bool prepared_for(const GridMgView &v, const MgHierarchy *h, int nu)
 {
-    return h && h->prepared && !h->rowblocked && h->estate.p && h->weighted == v.weighted && h->precision == v.precision &&
-           h->opC == (v.weighted ? v.op_channels : 1) && h->prep_nu == nu && h->prep_channels == v.channels &&
-           h->prep_mode == v.channels_mode && h->prep_smoother == v.smoother && h->prep_nullspace == (constant_mode(v) ? 1 : 0);
+    return h && h->prepared && h->estate.p && cache_serves(v, *h) && h->prep_cfg == v.cfg && h->prep_nu == nu && h->prep_channels == v.channels;
+}
+
+// ---- the options (ccp_grid_mg_set_* / _get_*) ---------------------------------------------------------------------------
+// Every option takes the values 0 and 1 (CCP_MG_*_*, include/ccp_gs.h).  Per option: its place in MgConfig; when the
+// setter returns CCP_ERR_UNSUPPORTED (null: never); what a change of value frees of a cached hierarchy (null: nothing).
+// ccp_grid_mg_conjugate_gradient_enqueue rests on the last column: whatever is freed here is rebuilt by the next solve or
+// prepare alone, so a change either deletes the hierarchy, or clears `prepared` with what it frees, or -- the null
+// space, whose buffers serve both values -- frees nothing and leaves prepared_for to see that the options differ.
+struct MgOption {
+    int MgConfig::*field;
+    bool (*unsupported)(const GridMgSlot &s, int value);
+    void (*changed)(MgHierarchy **cache);
+};
+enum { kOptHierarchy, kOptPrecision, kOptChannels, kOptSmoother, kOptNullspace };
+
+bool not_weighted(const GridMgSlot &s, int) { return !s.weighted; }
+
+const MgOption kOptions[] = {
+    // the cached levels belong to the other kind
+    {&MgConfig::hierarchy, not_weighted, mg_release},
+    // the cached vectors belong to the other precision; row blocks run the fp64 V-cycle only (local: nothing collective happens here)
+    {&MgConfig::precision, [](const GridMgSlot &s, int value) { return value == CCP_MG_PRECISION_F32 && s.row_block; }, mg_release},
+    // the other mode's vectors go; the levels stay
+    {&MgConfig::channels, nullptr,
+     [](MgHierarchy **cache) {
+         batched_release(**cache);
+         (*cache)->seq.release();
+         (*cache)->prepared = false;
+     }},
+    // the line solves' work planes go; everything else is shared
+    {&MgConfig::smoother, nullptr,
+     [](MgHierarchy **cache) {
+         (*cache)->lwork.release();
+         (*cache)->lplane = 0;
+         (*cache)->prepared = false;
+     }},
+    // the hierarchy and the PCG vectors serve both modes
+    {&MgConfig::nullspace, not_weighted, nullptr},
+};
+
+// In this order: the handle, the value's range, the refusal (also of the value the handle holds), the same value (nothing happens)
+int set_option(ccp_grid *g, int which, int32_t value)
+{
+    const MgOption &o = kOptions[which];
+    GridMgSlot s{};
+    CCP_TRY(grid_mg_slot(g, &s));
+    if (value != 0 && value != 1) return CCP_ERR_BAD_ARG;
+    if (o.unsupported && o.unsupported(s, value)) return CCP_ERR_UNSUPPORTED;
+    if (s.cfg->*o.field == value) return CCP_OK;
+    s.cfg->*o.field = value;
+    if (o.changed && *s.cache) o.changed(s.cache);
+    return CCP_OK;
+}
+
+int get_option(ccp_grid *g, int which, int32_t *value)
+{
+    GridMgSlot s{};
+    CCP_TRY(grid_mg_slot(g, &s));
+    if (!value) return CCP_ERR_BAD_ARG;
+    *value = s.cfg->*kOptions[which].field;
+    return CCP_OK;
 }
 
 }  // namespace
@@ -1374,18 +1447,9 @@ extern "C" {
 int ccp_grid_mg_apply(ccp_grid *g, int32_t smoothing_sweeps)
 try {
     GridMgView v{};
-    CCP_TRY(check_handle(g, &v));
     int nu = 2;
-    CCP_TRY(sweeps_arg(smoothing_sweeps, &nu, v.smoother));
-    const bool batched = v.channels_mode == CCP_MG_CHANNELS_BATCHED;
-    if (batched && v.precision == CCP_MG_PRECISION_F32) return CCP_ERR_UNSUPPORTED;
-    CCP_TRY(line_check(v));
-    CCP_TRY(nullspace_check(v));
     MgHierarchy *h = nullptr;
-    CCP_TRY(hierarchy(v, &h));
-    if (h->precision == CCP_MG_PRECISION_F32) CCP_TRY(narrow_levels(v, *h));
-    CCP_TRY(line_planes(v, *h));
-    CCP_TRY(nullspace_ready(v, *h));
+    CCP_TRY(call_ready(g, 0, smoothing_sweeps, &v, &nu, &h));
     const long n = v.geom.ch_stride;
     if (constant_mode(v)) {                                        // x := z - mean(z), z = M (b - mean(b))
         NullspaceSteps S{};
@@ -1405,8 +1469,7 @@ try {
         CCP_HIP(hipStreamSynchronize(v.stream));
         return CCP_OK;
     }
-    if (batched) {
-        CCP_TRY(batched_levels(v, *h));
+    if (v.cfg.channels == CCP_MG_CHANNELS_BATCHED) {
         CCP_TRY(vcycle_batched(*h, v.stream, v.channels, n, v.b, v.x, nu, nullptr));
         CCP_HIP(hipStreamSynchronize(v.stream));
         return CCP_OK;
@@ -1416,131 +1479,16 @@ try {
     return CCP_OK;
 } CCP_ABI_CATCH
 
-int ccp_grid_mg_set_hierarchy(ccp_grid *g, int32_t kind)
-try {
-    bool weighted = false;
-    int *slot = nullptr;
-    MgHierarchy **cache = nullptr;
-    CCP_TRY(grid_mg_hierarchy_slot(g, &weighted, &slot, &cache));
-    if (kind != CCP_MG_HIERARCHY_GALERKIN && kind != CCP_MG_HIERARCHY_RESCALED) return CCP_ERR_BAD_ARG;
-    if (!weighted) return CCP_ERR_UNSUPPORTED;
-    if (*slot == kind) return CCP_OK;
-    *slot = kind;
-    mg_release(*cache);                                            // the cached levels belong to the other kind
-    *cache = nullptr;
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_mg_get_hierarchy(ccp_grid *g, int32_t *kind)
-try {
-    bool weighted = false;
-    int *slot = nullptr;
-    MgHierarchy **cache = nullptr;
-    CCP_TRY(grid_mg_hierarchy_slot(g, &weighted, &slot, &cache));
-    if (!kind) return CCP_ERR_BAD_ARG;
-    *kind = *slot;
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_mg_set_precision(ccp_grid *g, int32_t precision)
-try {
-    int *slot = nullptr;
-    MgHierarchy **cache = nullptr;
-    bool row_block = false;
-    CCP_TRY(grid_mg_precision_slot(g, &slot, &cache, &row_block));
-    if (precision != CCP_MG_PRECISION_F64 && precision != CCP_MG_PRECISION_F32) return CCP_ERR_BAD_ARG;
-    if (precision == CCP_MG_PRECISION_F32 && row_block) return CCP_ERR_UNSUPPORTED;   // (local: nothing collective happens here)
-    if (*slot == precision) return CCP_OK;
-    *slot = precision;
-    mg_release(*cache);                                            // the cached vectors belong to the other precision
-    *cache = nullptr;
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_mg_get_precision(ccp_grid *g, int32_t *precision)
-try {
-    int *slot = nullptr;
-    MgHierarchy **cache = nullptr;
-    bool row_block = false;
-    CCP_TRY(grid_mg_precision_slot(g, &slot, &cache, &row_block));
-    if (!precision) return CCP_ERR_BAD_ARG;
-    *precision = *slot;
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_mg_set_channels(ccp_grid *g, int32_t mode)
-try {
-    int *slot = nullptr;
-    MgHierarchy **cache = nullptr;
-    CCP_TRY(grid_mg_channels_slot(g, &slot, &cache));
-    if (mode != CCP_MG_CHANNELS_SEQUENTIAL && mode != CCP_MG_CHANNELS_BATCHED) return CCP_ERR_BAD_ARG;
-    if (*slot == mode) return CCP_OK;
-    *slot = mode;
-    if (*cache) {                                                  // the other mode's vectors go; the levels stay
-        MgHierarchy &h = **cache;
-        batched_release(h);
-        h.seq.release();
-        h.prepared = false;
-    }
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_mg_get_channels(ccp_grid *g, int32_t *mode)
-try {
-    int *slot = nullptr;
-    MgHierarchy **cache = nullptr;
-    CCP_TRY(grid_mg_channels_slot(g, &slot, &cache));
-    if (!mode) return CCP_ERR_BAD_ARG;
-    *mode = *slot;
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_mg_set_smoother(ccp_grid *g, int32_t kind)
-try {
-    int *slot = nullptr;
-    MgHierarchy **cache = nullptr;
-    CCP_TRY(grid_mg_smoother_slot(g, &slot, &cache));
-    if (kind != CCP_MG_SMOOTHER_POINT && kind != CCP_MG_SMOOTHER_LINE) return CCP_ERR_BAD_ARG;
-    if (*slot == kind) return CCP_OK;
-    *slot = kind;
-    if (*cache) {                                                  // the line solves' work planes go; everything else is shared
-        (*cache)->lwork.release();
-        (*cache)->lplane = 0;
-        (*cache)->prepared = false;
-    }
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_mg_get_smoother(ccp_grid *g, int32_t *kind)
-try {
-    int *slot = nullptr;
-    MgHierarchy **cache = nullptr;
-    CCP_TRY(grid_mg_smoother_slot(g, &slot, &cache));
-    if (!kind) return CCP_ERR_BAD_ARG;
-    *kind = *slot;
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_mg_set_nullspace(ccp_grid *g, int32_t kind)
-try {
-    bool weighted = false;
-    MgNullspace *ns = nullptr;
-    CCP_TRY(grid_mg_nullspace_slot(g, &weighted, &ns));
-    if (kind != CCP_MG_NULLSPACE_NONE && kind != CCP_MG_NULLSPACE_CONSTANT) return CCP_ERR_BAD_ARG;
-    if (!weighted) return CCP_ERR_UNSUPPORTED;
-    ns->kind = kind;                                               // (the hierarchy and the PCG vectors serve both modes)
-    return CCP_OK;
-} CCP_ABI_CATCH
-
-int ccp_grid_mg_get_nullspace(ccp_grid *g, int32_t *kind)
-try {
-    bool weighted = false;
-    MgNullspace *ns = nullptr;
-    CCP_TRY(grid_mg_nullspace_slot(g, &weighted, &ns));
-    if (!kind) return CCP_ERR_BAD_ARG;
-    *kind = weighted ? ns->kind : CCP_MG_NULLSPACE_NONE;
-    return CCP_OK;
-} CCP_ABI_CATCH
+int ccp_grid_mg_set_hierarchy(ccp_grid *g, int32_t kind) try { return set_option(g, kOptHierarchy, kind); } CCP_ABI_CATCH
+int ccp_grid_mg_get_hierarchy(ccp_grid *g, int32_t *kind) try { return get_option(g, kOptHierarchy, kind); } CCP_ABI_CATCH
+int ccp_grid_mg_set_precision(ccp_grid *g, int32_t precision) try { return set_option(g, kOptPrecision, precision); } CCP_ABI_CATCH
+int ccp_grid_mg_get_precision(ccp_grid *g, int32_t *precision) try { return get_option(g, kOptPrecision, precision); } CCP_ABI_CATCH
+int ccp_grid_mg_set_channels(ccp_grid *g, int32_t mode) try { return set_option(g, kOptChannels, mode); } CCP_ABI_CATCH
+int ccp_grid_mg_get_channels(ccp_grid *g, int32_t *mode) try { return get_option(g, kOptChannels, mode); } CCP_ABI_CATCH
+int ccp_grid_mg_set_smoother(ccp_grid *g, int32_t kind) try { return set_option(g, kOptSmoother, kind); } CCP_ABI_CATCH
+int ccp_grid_mg_get_smoother(ccp_grid *g, int32_t *kind) try { return get_option(g, kOptSmoother, kind); } CCP_ABI_CATCH
+int ccp_grid_mg_set_nullspace(ccp_grid *g, int32_t kind) try { return set_option(g, kOptNullspace, kind); } CCP_ABI_CATCH
+int ccp_grid_mg_get_nullspace(ccp_grid *g, int32_t *kind) try { return get_option(g, kOptNullspace, kind); } CCP_ABI_CATCH
 
 int ccp_grid_mg_nullspace_info(ccp_grid *g, int32_t channel, double *b_mean, double *x_mean, int64_t *pixels)
 try {
@@ -1634,8 +1582,7 @@ try {
     h->prepared = false;
     if (!h->estate.p) CCP_TRY(h->estate.alloc((size_t)kMaxChannels));
     CCP_HIP(hipStreamSynchronize(v.stream));                       // what building enqueued has run: a failure shows here
-    h->prep_nu = nu, h->prep_channels = v.channels, h->prep_mode = v.channels_mode, h->prep_smoother = v.smoother;
-    h->prep_nullspace = constant_mode(v) ? 1 : 0;
+    h->prep_cfg = v.cfg, h->prep_nu = nu, h->prep_channels = v.channels;
     h->prepared = true;
     return CCP_OK;
 } CCP_ABI_CATCH
@@ -1646,7 +1593,7 @@ try {
     GridMgView v{};
     CCP_TRY(check_handle(g, &v));
     int nu = 2;
-    CCP_TRY(sweeps_arg(smoothing_sweeps, &nu, v.smoother));
+    CCP_TRY(sweeps_arg(smoothing_sweeps, &nu, v.cfg.smoother));
     if (max_iteration < 0 || max_iteration > CCP_MG_ENQUEUE_MAX_ITERATION) return CCP_ERR_BAD_ARG;
     if (report) CCP_TRY(check_view_on(v.device, report, 1u << CCP_DTYPE_F64, true, 1, v.channels, kMgeReportFields, 1));
     MgHierarchy *h = *v.cache;

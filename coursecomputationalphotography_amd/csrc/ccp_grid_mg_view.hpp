@@ -7,13 +7,26 @@
 namespace ccp {
 
 struct MgHierarchy;
-void mg_release(MgHierarchy *h);
+void mg_release(MgHierarchy **cache);   // deletes the cached hierarchy, if any, and leaves null
 
-// CCP_MG_NULLSPACE_* (ccp_grid_mg_set_nullspace) and what the handle remembers for it: the census verdict of the
-// installed operators (-1: not taken yet, 0: one is not floating, 1: all are) and ccp_grid_mg_nullspace_info's figures of
-// every channel's last CONSTANT-mode solve.  A new operator forgets the verdict and the figures.
+// The multigrid options of a handle, CCP_MG_*_* each (ccp_grid_mg_set_* / _get_*).  They outlive every operator, mask and
+// communicator the handle is given; what a change of one frees of the cached hierarchy: kOptions (ccp_grid_mg.hip).
+struct MgConfig {
+    int hierarchy = CCP_MG_HIERARCHY_GALERKIN;   // (weighted handles only: the others keep the default)
+    int precision = CCP_MG_PRECISION_F64;
+    int channels = CCP_MG_CHANNELS_SEQUENTIAL;
+    int smoother = CCP_MG_SMOOTHER_POINT;
+    int nullspace = CCP_MG_NULLSPACE_NONE;       // (weighted handles only)
+    bool operator==(const MgConfig &o) const
+    {
+        return hierarchy == o.hierarchy && precision == o.precision && channels == o.channels && smoother == o.smoother && nullspace == o.nullspace;
+    }
+};
+
+// What the handle remembers for CCP_MG_NULLSPACE_CONSTANT: the census verdict of the installed operators (-1: not taken
+// yet, 0: one is not floating, 1: all are) and ccp_grid_mg_nullspace_info's figures of every channel's last solve in that
+// mode.  A new operator forgets the verdict and the figures.
 struct MgNullspace {
-    int kind = 0;
     int floating = -1;
     bool solved[kMaxChannels] = {};
     double b_mean[kMaxChannels] = {}, x_mean[kMaxChannels] = {};
@@ -39,11 +52,8 @@ struct GridMgView {
     // channel ch's d, we, ws at + ch * op_stride and its lambda at + ch * lam_stride; the shared operator: op_channels 1
     int op_channels;
     long op_stride, lam_stride;
-    int hierarchy_kind;              // CCP_MG_HIERARCHY_* (ccp_grid_mg_set_hierarchy; GALERKIN unless the handle is weighted)
-    int precision;                   // CCP_MG_PRECISION_* (ccp_grid_mg_set_precision)
-    int channels_mode;               // CCP_MG_CHANNELS_* (ccp_grid_mg_set_channels)
-    int smoother;                    // CCP_MG_SMOOTHER_* (ccp_grid_mg_set_smoother)
-    MgNullspace *ns;                 // ccp_grid_mg_set_nullspace's value, the census verdict and the last solves' means
+    MgConfig cfg;                    // the handle's options, by value
+    MgNullspace *ns;                 // the census verdict and the last CONSTANT-mode solves' means
     hipStream_t stream;
     int device;                      // the handle's device (what a ccp_device_array argument is checked against)
     MgHierarchy **cache;            // the handle's cached hierarchy (built on first use, dropped with the mask and the partition)
@@ -54,16 +64,14 @@ struct GridMgView {
     int ghost;
 };
 int grid_mg_view(ccp_grid *g, GridMgView *v);
-// the handle's hierarchy kind (ccp_grid_mg_set_hierarchy / _get_hierarchy) and whether the handle is weighted
-int grid_mg_hierarchy_slot(ccp_grid *g, bool *weighted, int **kind, MgHierarchy ***cache);
-// the handle's V-cycle precision (ccp_grid_mg_set_precision / _get_precision) and whether the handle is a row block
-int grid_mg_precision_slot(ccp_grid *g, int **precision, MgHierarchy ***cache, bool *row_block);
-// the handle's channel mode (ccp_grid_mg_set_channels / _get_channels)
-int grid_mg_channels_slot(ccp_grid *g, int **mode, MgHierarchy ***cache);
-// the handle's smoother (ccp_grid_mg_set_smoother / _get_smoother)
-int grid_mg_smoother_slot(ccp_grid *g, int **kind, MgHierarchy ***cache);
-// the handle's null-space record (ccp_grid_mg_set_nullspace / _get_nullspace) and whether the handle is weighted
-int grid_mg_nullspace_slot(ccp_grid *g, bool *weighted, MgNullspace **ns);
+// What the option setters and getters work on: the options themselves, the cached hierarchy, and the two facts a setter
+// may refuse on (row_block: the handle has ghost rows or holds fewer rows than the image)
+struct GridMgSlot {
+    MgConfig *cfg;
+    MgHierarchy **cache;
+    bool weighted, row_block;
+};
+int grid_mg_slot(ccp_grid *g, GridMgSlot *s);
 void grid_mg_halo_stale(ccp_grid *g);   // after a row-block solve: the next sweep refreshes the ghost rows first
 
 }  // namespace ccp

@@ -81,8 +81,7 @@ def solve_channels(gx, gy, constraint, iterations: int, init=None, solver: str =
     C = gx.shape[2] if gx.dim() == 3 else 1
     g = _grid(W, H, C, dev)
     try:
-        g.mg_set_precision(precision)
-        g.mg_set_channels(channels)
+        g.mg_configure(precision=precision, channels=channels)
         g.assemble_rhs_tensor(gx, gy, constraint)
         if init is not None:
             g.set_x_u8_tensor(init)
@@ -221,11 +220,7 @@ def weighted_solve(gx, gy, f, iterations: int, wx=None, wy=None, data_weight=Non
     g = capi.Grid(W, H, C, device=dev, weighted=True)
     g.set_stream(torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream)
     try:
-        g.mg_set_hierarchy(hierarchy)
-        g.mg_set_precision(precision)
-        g.mg_set_channels(channels)
-        g.mg_set_smoother(smoother)
-        g.mg_set_nullspace(nullspace)
+        g.mg_configure(hierarchy=hierarchy, precision=precision, channels=channels, smoother=smoother, nullspace=nullspace)
         _set_operator(g, _weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev))
         g.assemble_weighted_rhs_tensor(gx, gy, f, init_x=f is not None)
         if f is None:
@@ -276,10 +271,7 @@ def integrate_gradients(gx, gy, wx=None, wy=None, mean=0.0, iterations: int = 20
     g = capi.Grid(W, H, C, device=dev, weighted=True)
     g.set_stream(torch.cuda.current_stream(device).cuda_stream)
     try:
-        g.mg_set_hierarchy(hierarchy)
-        g.mg_set_precision(precision)
-        g.mg_set_smoother(smoother)
-        g.mg_set_nullspace("constant")
+        g.mg_configure(hierarchy=hierarchy, precision=precision, smoother=smoother, nullspace="constant")
         _set_operator(g, _weight(wx, H, W, dev), _weight(wy, H, W, dev), None)
         g.assemble_weighted_rhs_tensor(gx, gy, None, init_x=False)
         g.set_x_tensor(m.reshape(1, 1, -1).expand(H, W, C).contiguous())
@@ -347,10 +339,7 @@ def constrained_solve(gx, gy, f, values, fixed, iterations: int, wx=None, wy=Non
     g = capi.Grid(W, H, C, device=dev, weighted=True)
     g.set_stream(torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream)
     try:
-        g.mg_set_hierarchy(hierarchy)
-        g.mg_set_precision(precision)
-        g.mg_set_channels(channels)
-        g.mg_set_smoother(smoother)
+        g.mg_configure(hierarchy=hierarchy, precision=precision, channels=channels, smoother=smoother)
         _set_operator(g, _weight(wx, H, W, dev), _weight(wy, H, W, dev), _weight(data_weight, H, W, dev), fixed)
         if f is None:
             g.fill_x(0.0)
@@ -401,10 +390,7 @@ def seamless_clone_constrained(source, target, mask, iterations: int, mixed: boo
     g = capi.Grid(W, H, C, device=dev, weighted=True)
     g.set_stream(torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream)
     try:
-        g.mg_set_hierarchy("rescaled")
-        g.mg_set_precision(precision)
-        g.mg_set_channels(channels)
-        g.mg_set_smoother(smoother)
+        g.mg_configure(hierarchy="rescaled", precision=precision, channels=channels, smoother=smoother)
         g.set_weights_tensor(None, None, _weight(data_weight, H, W, dev), fixed=fixed)
         g.set_x_u8_tensor(target)
         g.assemble_constrained_rhs_tensor(gx, gy, None if data_weight is None else source, target, init_x=False)
@@ -445,10 +431,7 @@ def _solve_function():
             g = capi.Grid(W, H, C, device=dev, weighted=True)
             try:
                 g.set_stream(torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream)
-                g.mg_set_hierarchy(cfg["hierarchy"])
-                g.mg_set_precision(cfg["precision"])
-                g.mg_set_channels(cfg["channels"])
-                g.mg_set_smoother(cfg["smoother"])
+                g.mg_configure(hierarchy=cfg["hierarchy"], precision=cfg["precision"], channels=cfg["channels"], smoother=cfg["smoother"])
                 _set_operator(g, wx, wy, lam, fixed)
                 if f is None:
                     g.fill_x(0.0)
@@ -594,11 +577,7 @@ class WeightedSolver:
         self._zero = torch.zeros((), dtype=torch.float64, device=self.device).expand(self.H, self.W, self.C)
         self.grid = capi.Grid(self.W, self.H, self.C, device=dev, weighted=True)
         try:
-            self.grid.mg_set_hierarchy(hierarchy)
-            self.grid.mg_set_precision(precision)
-            self.grid.mg_set_channels(channels)
-            self.grid.mg_set_smoother(smoother)
-            self.grid.mg_set_nullspace(nullspace)
+            self.grid.mg_configure(hierarchy=hierarchy, precision=precision, channels=channels, smoother=smoother, nullspace=nullspace)
         except BaseException:
             self.grid.close()
             raise
