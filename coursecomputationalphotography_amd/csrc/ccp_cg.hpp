@@ -22,17 +22,6 @@ namespace ccp {
 // know a second fused form, 2)
 inline int cg_fused_mode() { return getenv("CCP_GS_CG_FUSED") ? atoi(getenv("CCP_GS_CG_FUSED")) : 1; }
 
-struct CgState {
-    int active;
-    int converged;
-    int iterations;      // the reference's `cnt`
-    int pcur;            // fused loop: which of the two direction buffers holds the current p
-    double rlen;         // r'r of the current residual
-    double alpha;
-    double beta;
-    double r1norm;       // sqrt(r1'r1) of the last update
-};
-
 // ---- the passes' bodies ------------------------------------------------------------------------------------------------
 // Each pass of the loop is written once here and instantiated by two kernels: k_cg_* below (one vector, one CgState) and
 // the batched multigrid PCG's k_mgb_* (ccp_grid_mgb.hpp: the channel on grid y or x, st and the partial sums indexed by

@@ -84,10 +84,22 @@ struct DevBuf {
     }
 };
 
+// The scalars of a device-side conjugate-gradient loop (ccp_cg.hpp), one per vector being solved for
+struct CgState {
+    int active;
+    int converged;
+    int iterations;      // the reference's `cnt`
+    int pcur;            // fused loop: which of the two direction buffers holds the current p
+    double rlen;         // r'r of the current residual
+    double alpha;
+    double beta;
+    double r1norm;       // sqrt(r1'r1) of the last update
+};
+
 }  // namespace ccp
 struct ccp_grid;
 namespace ccp {
-// Library-internal (not part of the C ABI): install the mask of a Dirichlet-mask grid from a DEVICE buffer that is
+// Library-internal (not part of the C ABI; ccp_grid_io.hip): install the mask of a Dirichlet-mask grid from a DEVICE buffer that is
 // already in the grid's layout (one byte per element of a channel plane, colour half-rows of `pitch` bytes).
 int grid_set_mask_split_device(ccp_grid *g, const unsigned char *split_mask_dev, long unknowns);
 // Library-internal: the handle's owner asks for the layout (ccp_grid_get_layout) at every use, so x and its ping-pong

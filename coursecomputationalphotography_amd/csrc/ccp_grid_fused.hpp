@@ -33,14 +33,10 @@
 
 #include "ccp_fused_plan.hpp"      // the chunk and strip arithmetic, shared with the host's pass planner
 #include "ccp_grid_kernels.hpp"
+#include "ccp_grid_types.hpp"     // kFusedMaxT, kFusedMaxCheckedT
 
 namespace ccp {
 
-#ifndef CCP_FUSED_MAX_T
-#define CCP_FUSED_MAX_T 8
-#endif
-constexpr int kFusedMaxT = CCP_FUSED_MAX_T;          // deepest pass instantiated
-constexpr int kFusedMaxCheckedT = 8;     // deepest pass that also reports the step of each of its sweeps (+2T+4 VGPRs)
 #ifndef CCP_FUSED_UNROLL
 #define CCP_FUSED_UNROLL 2
 #endif
@@ -54,24 +50,6 @@ constexpr int kFusedUnroll = CCP_FUSED_UNROLL;          // march steps unrolled 
 // +2-3 % at 16384^2 and 4096^2 x 3 over one trip.
 constexpr int kFusedLand = CCP_FUSED_LAND;
 static_assert(kStripLanes == kWave && kTileWaves == kBlock / kWave, "ccp_fused_plan.hpp plans for one half-column per lane, one wave per SIMD");
-
-// lane i <- lane i-1 (lane 0 gets 0) / lane i <- lane i+1 (lane 63 gets 0): the strip-edge lanes
-// have no neighbour inside the wave; their pixels are halo (never stored) or image-edge pixels
-// whose stencil has no such neighbour.
-__device__ __forceinline__ double lane_prev(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0x138, 0xf, 0xf, true);   // wave_shr:1
-    hi = __builtin_amdgcn_update_dpp(0, hi, 0x138, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double lane_next(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0x130, 0xf, 0xf, true);   // wave_shl:1
-    hi = __builtin_amdgcn_update_dpp(0, hi, 0x130, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
 
 struct FusedParams {
     const double *__restrict__ xin;

@@ -12,6 +12,9 @@
 // each colour half-row.  KIND picks how the natural side is read: kPairs when stride_x == 1 and a pair is one
 // aligned 2-element vector (channel-planar C x H x W, and any C = 1 row), kRgb when the view is interleaved with
 // C == 3 (the 6 values of a pair are contiguous: three 2-element vectors), kGeneral for any other strides.
+//
+// Below them: the layout conversion of the host row calls (k_convert) and the assembly, u8 store and u8 load kernels.
+// Included by ccp_grid_io.hip alone (k_io_label_check is neither a template nor static).
 #pragma once
 
 #include "ccp_grid_stencil.hpp"
@@ -173,6 +176,118 @@ k_io_label_check(View<const uint8_t> label, int W, int H, int n_images, unsigned
         any |= label(y, x, 0) >= n_images;
     }
     if (any) atomicOr(bad, 1u);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Layout conversion between natural raster rows (what std::vector<double> holds in the
+// reference) and the row-split colour planes.  grid = (ceil(W/kBlock), rows).
+template <bool TO_SPLIT>
+__global__ void __launch_bounds__(kBlock)
+k_convert(double *__restrict__ split, double *__restrict__ natural, Geom g, int ch, int l_first,
+          int W)
+{
+    const int x = blockIdx.x * kBlock + threadIdx.x;
+    const int r = blockIdx.y;
+    if (x >= W) return;
+    const int l = l_first + r;
+    const int c = (x + g.y0 + l) & 1;
+    const long s = (long)ch * g.ch_stride + row_off(g, l, c) + (x >> 1);
+    const long n = (long)r * W + x;
+    if (TO_SPLIT) split[s] = natural[n];
+    else natural[n] = split[s];
+}
+
+// ---------------------------------------------------------------------------------------------
+// Poisson right-hand side ATb for all channels (PhotoMontage.cpp:563-572,579-581,592), Eigen's
+// row-major sparse*dense accumulation order: gy above, gx left, -gx here, -gy here, pin.
+// gx, gy: H x W x C float32 on device through accessor F (ccp_grid_io.hpp), the pins through PIN (Pins by
+// value).  grid = (ceil(W/kBlock), H, C).
+template <typename F, typename PIN>
+__global__ void __launch_bounds__(kBlock)
+k_assemble_rhs(double *__restrict__ b, Geom g, F gx, F gy, PIN constraint)
+{
+    const int x = blockIdx.x * kBlock + threadIdx.x;
+    const int y = blockIdx.y;
+    const int ch = blockIdx.z;
+    if (x >= g.W) return;
+    double acc = 0.0;
+    if (y >= 1 && x < g.W - 1) acc += 1.0 * (double)gy(y - 1, x, ch);
+    if (x >= 1 && y < g.H - 1) acc += 1.0 * (double)gx(y, x - 1, ch);
+    if (x < g.W - 1 && y < g.H - 1) {
+        acc += -1.0 * (double)gx(y, x, ch);
+        acc += -1.0 * (double)gy(y, x, ch);
+    }
+    if ((x | y) == 0) acc += 1.0 * (double)constraint[ch];
+    const int l = y - g.y0;
+    b[(long)ch * g.ch_stride + row_off(g, l, (x + y) & 1) + (x >> 1)] = acc;
+}
+
+// Gradient field + right-hand side in one pass, straight from the source images and the label
+// map (BuildSolveGradientFusion, PhotoMontage.cpp:419-433): the forward differences of
+// GradientAt (:399-408: integer subtraction of the label-selected image, then float) feed the
+// same ATb accumulation as k_assemble_rhs, with the pin value Images[0](0,0)[ch] (:428).
+// INIT: also write the composite image as the start vector (PhotoMontage.cpp:599-610).
+// images: K stacked H x W x 3 u8 images (accessor IMG, image k = img.at(k, ...)), label: H x W u8 (accessor LAB).
+// grid = (ceil(W/kBlock), H, 3).
+template <bool INIT, typename IMG, typename LAB>
+__global__ void __launch_bounds__(kBlock)
+k_assemble_from_images(double *__restrict__ b, double *__restrict__ x, Geom g, IMG images, LAB label)
+{
+    const int xi = blockIdx.x * kBlock + threadIdx.x;
+    const int y = blockIdx.y;
+    const int ch = blockIdx.z;
+    if (xi >= g.W) return;
+    auto pix = [&](int k, int yy, int xx) -> int { return (int)images.at(k, yy, xx, ch); };
+    auto lab = [&](int yy, int xx) -> int { return (int)label(yy, xx, 0); };
+    double acc = 0.0;
+    if (y >= 1 && xi < g.W - 1) {                       // gy(y-1, x) of the cell above
+        const int k = lab(y - 1, xi);
+        acc += 1.0 * (double)(float)(pix(k, y, xi) - pix(k, y - 1, xi));
+    }
+    if (xi >= 1 && y < g.H - 1) {                       // gx(y, x-1) of the cell to the left
+        const int k = lab(y, xi - 1);
+        acc += 1.0 * (double)(float)(pix(k, y, xi) - pix(k, y, xi - 1));
+    }
+    if (xi < g.W - 1 && y < g.H - 1) {                  // -gx(y,x) - gy(y,x) of this cell
+        const int k = lab(y, xi);
+        const int here = pix(k, y, xi);
+        acc += -1.0 * (double)(float)(pix(k, y, xi + 1) - here);
+        acc += -1.0 * (double)(float)(pix(k, y + 1, xi) - here);
+    }
+    if ((xi | y) == 0) acc += 1.0 * (double)pix(0, 0, 0);
+    const long at = (long)ch * g.ch_stride + row_off(g, y - g.y0, (xi + y) & 1) + (xi >> 1);
+    b[at] = acc;
+    if (INIT) x[at] = (double)pix(lab(y, xi), y, xi);
+}
+
+// Solve epilogue: out(y,x)[ch] = uchar(max(min(sol,255),0)) (PhotoMontage.cpp:617-626).  out: accessor OUT.
+template <typename OUT>
+__global__ void __launch_bounds__(kBlock)
+k_store_u8(const double *__restrict__ x, Geom g, OUT out)
+{
+    const int xi = blockIdx.x * kBlock + threadIdx.x;
+    const int y = blockIdx.y;
+    const int ch = blockIdx.z;
+    if (xi >= g.W) return;
+    const int l = y - g.y0;
+    double v = x[(long)ch * g.ch_stride + row_off(g, l, (xi + y) & 1) + (xi >> 1)];
+    v = v < 255.0 ? v : 255.0;
+    v = v > 0.0 ? v : 0.0;
+    out(y, xi, ch) = (uint8_t)v;
+}
+
+// Composite initial guess: x(y,x)[ch] = image(y,x)[ch] (PhotoMontage.cpp:599-610).  img: accessor IMG.
+template <typename IMG>
+__global__ void __launch_bounds__(kBlock)
+k_load_u8(double *__restrict__ x, Geom g, IMG img)
+{
+    const int xi = blockIdx.x * kBlock + threadIdx.x;
+    const int y = blockIdx.y;
+    const int ch = blockIdx.z;
+    if (xi >= g.W) return;
+    const int l = y - g.y0;
+    x[(long)ch * g.ch_stride + row_off(g, l, (xi + y) & 1) + (xi >> 1)] =
+        (double)img(y, xi, ch);
 }
 
 }  // namespace ccp

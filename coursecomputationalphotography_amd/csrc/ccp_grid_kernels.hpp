@@ -17,8 +17,8 @@
 // -ffp-contract=off (no FMA contraction) — the build enforces it.
 #pragma once
 
-#include "ccp_grid_io.hpp"
 #include "ccp_grid_stencil.hpp"
+#include "ccp_grid_types.hpp"       // SolveState
 
 namespace ccp {
 
@@ -141,14 +141,6 @@ k_half_sweep(const double *__restrict__ xr, double *__restrict__ xw, const doubl
             partial[((long)ch * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = total;
     }
 }
-
-// Per-channel solver state kept on the device so the stop rule needs no host round trip.
-struct SolveState {
-    int active[kMaxChannels];       // 1 while the channel still iterates
-    int converged[kMaxChannels];
-    int iterations[kMaxChannels];   // sweep index at which the stop rule fired
-    double last_eps[kMaxChannels];
-};
 
 // eps = sum of the red and black partials of one checked sweep; apply the reference stop rule
 // `while (eps > epsilon && cnt < max_iteration)` (sparse-matrix.h:356).  grid = channels.
@@ -355,25 +347,6 @@ k_sum_reduce(const double *__restrict__ partial, long count, double *__restrict_
     if (threadIdx.x == 0) out[ch] = t;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Layout conversion between natural raster rows (what std::vector<double> holds in the
-// reference) and the row-split colour planes.  grid = (ceil(W/kBlock), rows).
-template <bool TO_SPLIT>
-__global__ void __launch_bounds__(kBlock)
-k_convert(double *__restrict__ split, double *__restrict__ natural, Geom g, int ch, int l_first,
-          int W)
-{
-    const int x = blockIdx.x * kBlock + threadIdx.x;
-    const int r = blockIdx.y;
-    if (x >= W) return;
-    const int l = l_first + r;
-    const int c = (x + g.y0 + l) & 1;
-    const long s = (long)ch * g.ch_stride + row_off(g, l, c) + (x >> 1);
-    const long n = (long)r * W + x;
-    if (TO_SPLIT) split[s] = natural[n];
-    else natural[n] = split[s];
-}
-
 __global__ void __launch_bounds__(kBlock) k_fill(double *__restrict__ p, long n, double v)
 {
     for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) p[i] = v;
@@ -403,154 +376,6 @@ k_randomize(double *__restrict__ x, Geom g, uint64_t seed, double lo, double hi)
     double v = 0.0;
     if (xi < g.W) v = lo + (hi - lo) * hash_uniform(seed, ch, xi, y);
     x[(long)ch * g.ch_stride + row_off(g, l, c) + j] = v;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Poisson right-hand side ATb for all channels (PhotoMontage.cpp:563-572,579-581,592), Eigen's
-// row-major sparse*dense accumulation order: gy above, gx left, -gx here, -gy here, pin.
-// gx, gy: H x W x C float32 on device through accessor F (ccp_grid_io.hpp), the pins through PIN (Pins by
-// value).  grid = (ceil(W/kBlock), H, C).
-template <typename F, typename PIN>
-__global__ void __launch_bounds__(kBlock)
-k_assemble_rhs(double *__restrict__ b, Geom g, F gx, F gy, PIN constraint)
-{
-    const int x = blockIdx.x * kBlock + threadIdx.x;
-    const int y = blockIdx.y;
-    const int ch = blockIdx.z;
-    if (x >= g.W) return;
-    double acc = 0.0;
-    if (y >= 1 && x < g.W - 1) acc += 1.0 * (double)gy(y - 1, x, ch);
-    if (x >= 1 && y < g.H - 1) acc += 1.0 * (double)gx(y, x - 1, ch);
-    if (x < g.W - 1 && y < g.H - 1) {
-        acc += -1.0 * (double)gx(y, x, ch);
-        acc += -1.0 * (double)gy(y, x, ch);
-    }
-    if ((x | y) == 0) acc += 1.0 * (double)constraint[ch];
-    const int l = y - g.y0;
-    b[(long)ch * g.ch_stride + row_off(g, l, (x + y) & 1) + (x >> 1)] = acc;
-}
-
-// Gradient field + right-hand side in one pass, straight from the source images and the label
-// map (BuildSolveGradientFusion, PhotoMontage.cpp:419-433): the forward differences of
-// GradientAt (:399-408: integer subtraction of the label-selected image, then float) feed the
-// same ATb accumulation as k_assemble_rhs, with the pin value Images[0](0,0)[ch] (:428).
-// INIT: also write the composite image as the start vector (PhotoMontage.cpp:599-610).
-// images: K stacked H x W x 3 u8 images (accessor IMG, image k = img.at(k, ...)), label: H x W u8 (accessor LAB).
-// grid = (ceil(W/kBlock), H, 3).
-template <bool INIT, typename IMG, typename LAB>
-__global__ void __launch_bounds__(kBlock)
-k_assemble_from_images(double *__restrict__ b, double *__restrict__ x, Geom g, IMG images, LAB label)
-{
-    const int xi = blockIdx.x * kBlock + threadIdx.x;
-    const int y = blockIdx.y;
-    const int ch = blockIdx.z;
-    if (xi >= g.W) return;
-    auto pix = [&](int k, int yy, int xx) -> int { return (int)images.at(k, yy, xx, ch); };
-    auto lab = [&](int yy, int xx) -> int { return (int)label(yy, xx, 0); };
-    double acc = 0.0;
-    if (y >= 1 && xi < g.W - 1) {                       // gy(y-1, x) of the cell above
-        const int k = lab(y - 1, xi);
-        acc += 1.0 * (double)(float)(pix(k, y, xi) - pix(k, y - 1, xi));
-    }
-    if (xi >= 1 && y < g.H - 1) {                       // gx(y, x-1) of the cell to the left
-        const int k = lab(y, xi - 1);
-        acc += 1.0 * (double)(float)(pix(k, y, xi) - pix(k, y, xi - 1));
-    }
-    if (xi < g.W - 1 && y < g.H - 1) {                  // -gx(y,x) - gy(y,x) of this cell
-        const int k = lab(y, xi);
-        const int here = pix(k, y, xi);
-        acc += -1.0 * (double)(float)(pix(k, y, xi + 1) - here);
-        acc += -1.0 * (double)(float)(pix(k, y + 1, xi) - here);
-    }
-    if ((xi | y) == 0) acc += 1.0 * (double)pix(0, 0, 0);
-    const long at = (long)ch * g.ch_stride + row_off(g, y - g.y0, (xi + y) & 1) + (xi >> 1);
-    b[at] = acc;
-    if (INIT) x[at] = (double)pix(lab(y, xi), y, xi);
-}
-
-// Solve epilogue: out(y,x)[ch] = uchar(max(min(sol,255),0)) (PhotoMontage.cpp:617-626).  out: accessor OUT.
-template <typename OUT>
-__global__ void __launch_bounds__(kBlock)
-k_store_u8(const double *__restrict__ x, Geom g, OUT out)
-{
-    const int xi = blockIdx.x * kBlock + threadIdx.x;
-    const int y = blockIdx.y;
-    const int ch = blockIdx.z;
-    if (xi >= g.W) return;
-    const int l = y - g.y0;
-    double v = x[(long)ch * g.ch_stride + row_off(g, l, (xi + y) & 1) + (xi >> 1)];
-    v = v < 255.0 ? v : 255.0;
-    v = v > 0.0 ? v : 0.0;
-    out(y, xi, ch) = (uint8_t)v;
-}
-
-// Composite initial guess: x(y,x)[ch] = image(y,x)[ch] (PhotoMontage.cpp:599-610).  img: accessor IMG.
-template <typename IMG>
-__global__ void __launch_bounds__(kBlock)
-k_load_u8(double *__restrict__ x, Geom g, IMG img)
-{
-    const int xi = blockIdx.x * kBlock + threadIdx.x;
-    const int y = blockIdx.y;
-    const int ch = blockIdx.z;
-    if (xi >= g.W) return;
-    const int l = y - g.y0;
-    x[(long)ch * g.ch_stride + row_off(g, l, (xi + y) & 1) + (xi >> 1)] =
-        (double)img(y, xi, ch);
-}
-
-// ---- weighted handles (ccp_grid_weighted.hpp explains the operator's planes) ----------------------------------------------
-
-// pixels with d = 0 of an operator without fixed pixels (ccp_grid_constraint_info): one atomic per block that has any
-static __global__ void __launch_bounds__(kBlock)
-k_weighted_count_dead(const double *__restrict__ d, int W, int H, long pitch, unsigned long long *__restrict__ count)
-{
-    __shared__ unsigned tally;
-    if (threadIdx.x == 0) tally = 0;
-    __syncthreads();
-    const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y;
-    if (x < W && d[w_at(pitch, x, y)] == 0.0) atomicAdd(&tally, 1u);
-    __syncthreads();
-    if (threadIdx.x == 0 && tally) atomicAdd(count, (unsigned long long)tally);
-}
-
-// MODE 0: b := A x; MODE 1: per (channel, colour) block partial sums of (b - A x)^2 and b^2 at
-// partial[2 ((ch * 2 + c) * gridDim.x + blockIdx.x) + {0, 1}] (k_pair_reduce's layout, gridDim.x blocks per group).
-// grid = (blocks, 1, 2 channels); a block strides over the cells of colour c.
-template <int MODE>
-__global__ void __launch_bounds__(kBlock)
-k_weighted_apply(const double *__restrict__ x, double *__restrict__ b, Geom g, const double *__restrict__ op, long plane,
-                 double *__restrict__ partial)
-{
-    __shared__ double scratch[kBlock / kWave];
-    const int ch = blockIdx.z >> 1, c = blockIdx.z & 1;
-    const double *__restrict__ d = op, *__restrict__ we = op + plane, *__restrict__ ws = op + 2 * plane;
-    const double *__restrict__ xc = x + (long)ch * g.ch_stride;
-    double *__restrict__ bc = b + (long)ch * g.ch_stride;
-    const int hw = (g.W + 1) / 2;
-    const long cells = (long)g.H * hw;
-    double rr = 0.0, bb = 0.0;
-    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < cells; i += (long)gridDim.x * kBlock) {
-        const int y = (int)(i / hw), xi = 2 * (int)(i - (long)y * hw) + ((y + c) & 1);
-        if (xi >= g.W) continue;
-        const double ax = weighted_row(d, we, ws, g.pitch, g.W, g.H, xc, xi, y);
-        const long at = w_at(g.pitch, xi, y);
-        if (MODE == 0) {
-            bc[at] = ax;
-        } else {
-            const double bv = bc[at], r = bv - ax;
-            rr += r * r;
-            bb += bv * bv;
-        }
-    }
-    if (MODE == 1) {
-        const double t0 = block_sum(rr, scratch);
-        const double t1 = block_sum(bb, scratch);
-        if (threadIdx.x == 0) {
-            const long k = 2 * ((long)blockIdx.z * gridDim.x + blockIdx.x);
-            partial[k] = t0;
-            partial[k + 1] = t1;
-        }
-    }
 }
 
 }  // namespace ccp

@@ -6,7 +6,7 @@
 // hyperplane tau - 1:  (x,y-1,k) and (x-1,y,k) trivially, (x+1,y,k-1) and (x,y+1,k-1) because
 // x+y+1 + 2(k-1) = tau - 1.  All points of one hyperplane are therefore independent, any order that
 // walks tau upwards reproduces the sequential sweep exactly, and one hyperplane holds pixels of many
-// iterations at once — the pipeline never drains between sweeps.  Two engines walk it (ccp_grid.hip):
+// iterations at once — the pipeline never drains between sweeps.  Two engines walk it (ccp_grid_lex.hip):
 // k_lex_wg, the default — time-skewed strips (x' = x + 2t, y' = y + 2t), the T sweeps of a pass on the T waves of a
 // workgroup, rows exchanged through LDS, all passes in one launch — and k_lex_plane (CCP_GS_LEX_MODE=planes), one
 // launch per tau, anti-diagonal d = tau - 2k of every iteration k in flight (a launch writes diagonals of one parity
@@ -18,25 +18,17 @@
 //   (x,y-1) -> [d-1][x]   (x-1,y) -> [d-1][x-1]   (x+1,y) -> [d+1][x+1]   (x,y+1) -> [d+1][x]
 // every access of a launch is unit-stride along x.  Twice the memory of the image, none of the traffic.
 //
-// Arithmetic per pixel: classify()/gs_update() (ccp_grid_kernels.hpp) — the reference's accumulation
+// Arithmetic per pixel: classify()/gs_update() (ccp_grid_stencil.hpp) — the reference's accumulation
 // order and its true division; interior pixels take (b + (((up+left)+right)+down)) * 0.25, the same bits.
 #pragma once
 
-#include "ccp_grid_kernels.hpp"
-#include "ccp_grid_fused.hpp"      // lane_prev / lane_next (DPP)
+#include "ccp_grid_stencil.hpp"    // classify / gs_update, lane_prev / lane_next (DPP)
+#include "ccp_grid_types.hpp"      // LexGeom
 
 namespace ccp {
 
 constexpr int kLexPPT = 4;                         // pixels per thread along a diagonal
 constexpr int kLexTile = kBlock * kLexPPT;         // pixels per block
-
-struct LexGeom {
-    int W, H;
-    long P;          // doubles per diagonal row (>= W)
-    long plane;      // doubles per channel = (W+H-1) * P
-    int n_diag;      // W + H - 1
-    int nbx;         // blocks along the longest diagonal
-};
 
 // split colour planes <-> diagonal-major through a 64 x 64 tile in LDS, so that BOTH sides move in runs: image rows of the tile on the split side (two
 // runs of 32 doubles, one per colour plane), pieces of anti-diagonals on the diagonal-major side (1 to 64 doubles).  (A

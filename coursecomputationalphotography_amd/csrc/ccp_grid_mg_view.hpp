@@ -1,4 +1,4 @@
-// ccp_grid_mg_view.hpp — what the multigrid solver (ccp_grid_mg.hip) needs of a grid handle (ccp_grid.hip owns the
+// ccp_grid_mg_view.hpp — what the multigrid solver (ccp_grid_mg.hip) needs of a grid handle (ccp_grid_handle.hpp defines the
 // handle, ccp_grid_mg.hip the hierarchy cached on it).  Declarations only: no kernels.
 #pragma once
 

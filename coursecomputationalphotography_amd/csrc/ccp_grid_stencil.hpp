@@ -126,4 +126,22 @@ __device__ __forceinline__ double weighted_row(const double *__restrict__ d, con
     return a;
 }
 
+// lane i <- lane i-1 (lane 0 gets 0) / lane i <- lane i+1 (lane 63 gets 0): the strip-edge lanes
+// have no neighbour inside the wave; their pixels are halo (never stored) or image-edge pixels
+// whose stencil has no such neighbour.
+__device__ __forceinline__ double lane_prev(double v)
+{
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(0, lo, 0x138, 0xf, 0xf, true);   // wave_shr:1
+    hi = __builtin_amdgcn_update_dpp(0, hi, 0x138, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double lane_next(double v)
+{
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(0, lo, 0x130, 0xf, 0xf, true);   // wave_shl:1
+    hi = __builtin_amdgcn_update_dpp(0, hi, 0x130, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+
 }  // namespace ccp

@@ -1,7 +1,12 @@
-// ccp_grid_weighted.hip — the weighted handle's operator kernels (ccp_grid_weighted.hpp) and the per-channel batched
-// mode's (ccp_grid_pco.hpp) in a translation unit of their own, behind the launchers ccp_grid.hip and ccp_grid_mg.hip call.
+// ccp_grid_weighted.hip — everything only a weighted handle (CCP_GRID_WEIGHTED) accepts: its operator, right-hand side,
+// constraint counts, product and adjoint, with the operator kernels (ccp_grid_weighted.hpp, ccp_grid_adjoint.hpp); and the
+// launchers of the coarsening and of the per-channel batched mode's kernels (ccp_grid_pco.hpp) that ccp_grid_mg.hip calls
+// (ccp_grid_weighted_api.hpp).
+#include "ccp_grid_handle.hpp"
 #include "ccp_grid_pco.hpp"
 #include "ccp_grid_weighted.hpp"
+#include "ccp_grid_adjoint.hpp"
+#include "ccp_view_check.hpp"
 
 #include <atomic>
 
@@ -11,10 +16,10 @@ namespace {
 
 dim3 pixels(int W, int H, int C) { return dim3((unsigned)((W + kBlock - 1) / kBlock), (unsigned)H, (unsigned)C); }
 
-}  // namespace
-
-int ccp::weighted_coef(hipStream_t s, const ImageView &wx, const ImageView &wy, const ImageView &lam, const ImageView *fixed, int W, int H,
-                       int sets, long pitch, double *op, long plane, double *cons, unsigned long long *count)
+// The planes of `sets` operators (1: the one all channels share, from H x W views; C: one per channel) in one launch;
+// fixed: null for none (cons is not touched then).  count: 1 + 3 sets words, zeroed here.
+int weighted_coef(hipStream_t s, const ImageView &wx, const ImageView &wy, const ImageView &lam, const ImageView *fixed, int W, int H,
+                  int sets, long pitch, double *op, long plane, double *cons, unsigned long long *count)
 {
     CCP_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long) * (size_t)(1 + 3 * sets), s));
     if (fixed)
@@ -26,8 +31,10 @@ int ccp::weighted_coef(hipStream_t s, const ImageView &wx, const ImageView &wy, 
     return CCP_OK;
 }
 
-int ccp::weighted_rhs(hipStream_t s, double *b, double *x, const Geom &g, int C, int sets, const double *op, const double *cons,
-                      const ImageView &gx, const ImageView &gy, const ImageView &f, const ImageView &v, int has, bool init)
+// b (and x at fixed pixels, or everywhere with init) of all C channels from `sets` operators in one launch; cons: null
+// without fixed pixels
+int weighted_rhs(hipStream_t s, double *b, double *x, const Geom &g, int C, int sets, const double *op, const double *cons,
+                 const ImageView &gx, const ImageView &gy, const ImageView &f, const ImageView &v, int has, bool init)
 {
     const long plane = g.ch_stride;
     const dim3 grid = pixels(g.W, g.H, sets);
@@ -40,6 +47,8 @@ int ccp::weighted_rhs(hipStream_t s, double *b, double *x, const Geom &g, int C,
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 }
+
+}  // namespace
 
 int ccp::weighted_coarsen(hipStream_t s, int sets, const MgLevel &lv, long fs, const double *lam, long ls, const MgLevel &cv, double *d,
                           double *we, double *ws, double *lam_c, long cstride, double edge)
@@ -102,3 +111,425 @@ int ccp::pco_apply(hipStream_t s, bool dot, dim3 grid, int C, const MgLevel &lv,
     CCP_HIP(hipGetLastError());
     return CCP_OK;
 }
+
+// ============================================================================================
+// Weighted grids (include/ccp_gs.h, CCP_GRID_WEIGHTED; kernels: ccp_grid_weighted.hpp)
+// ============================================================================================
+namespace {
+
+// every entry point here begins with this: bind, then CCP_ERR_UNSUPPORTED on a handle that is not weighted
+int weighted_handle(ccp_grid *g)
+{
+    CCP_TRY(bind(g));
+    return g->weighted ? CCP_OK : CCP_ERR_UNSUPPORTED;
+}
+
+// b of every channel from the handle's operator, the shared one or every channel's own, in one launch; v: gx, gy, f and
+// the prescribed values (has & 1, 2, 4, 8: which of them are there)
+int weighted_rhs_launch(ccp_grid *g, const ImageView v[4], int has, bool init_x)
+{
+    const int C = g->desc.channels;
+    return weighted_rhs(g->stream, g->b.p, g->x.p, g->geom, C, g->per_channel ? C : 1, g->wop.p, g->has_fixed ? g->wcons.p : nullptr, v[0], v[1],
+                        v[2], v[3], has, init_x);
+}
+
+// ccp_grid_assemble_weighted_rhs and ccp_grid_assemble_constrained_rhs: the host arrays staged, one launch, one wait
+int weighted_rhs_host(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes, const float *f, int64_t f_stride_bytes,
+                      const float *values, int64_t values_stride_bytes, bool init_x)
+{
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    const int64_t row = (int64_t)W * C * (int64_t)sizeof(float);
+    if ((gx || gy) && field_stride_bytes < row) return CCP_ERR_BAD_ARG;
+    if (f && f_stride_bytes < row) return CCP_ERR_BAD_ARG;
+    if (values && values_stride_bytes < row) return CCP_ERR_BAD_ARG;
+    if (!g->has_op) return CCP_ERR_STATE;
+    const float *src[4] = {gx, gy, f, values};
+    const int64_t stride[4] = {field_stride_bytes, field_stride_bytes, f_stride_bytes, values_stride_bytes};
+    DevBuf<float> dev[4];
+    ImageView v[4];
+    int has = 0;
+    for (int i = 0; i < 4; ++i) {
+        v[i] = ImageView{nullptr, 0, 0, 0, 0, 0.0};
+        if (!src[i]) continue;
+        has |= 1 << i;
+        CCP_TRY(upload_window(g, dev[i], src[i], stride[i], 0, H));
+        v[i] = ImageView{dev[i].p, (long)W * C, (long)C, 1, CCP_DTYPE_F32, 0.0};   // the staging buffer: packed H x W x C
+    }
+    CCP_TRY(weighted_rhs_launch(g, v, has, init_x));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    return CCP_OK;
+}
+
+int weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f,
+                        const ccp_device_array *values, bool init)
+{
+    const int W = g->desc.width, H = g->desc.height, C = g->desc.channels;
+    if (gx) CCP_TRY(check_view(g, gx, kF32, false, 1, H, W, C));
+    if (gy) CCP_TRY(check_view(g, gy, kF32, false, 1, H, W, C));
+    if (f) CCP_TRY(check_view(g, f, kF32F64 | kU8, false, 1, H, W, C));
+    if (values) CCP_TRY(check_view(g, values, kF32F64 | kU8, false, 1, H, W, C));
+    if (!g->has_op) return CCP_ERR_STATE;
+    const int has = (gx ? 1 : 0) | (gy ? 2 : 0) | (f ? 4 : 0) | (values ? 8 : 0);
+    const ImageView v[4] = {image_view(gx, 0.0), image_view(gy, 0.0), image_view(f, 0.0), image_view(values, 0.0)};
+    return weighted_rhs_launch(g, v, has, init);
+}
+
+// a new operator is coming: the old one, its counts and the hierarchy built on it go
+void drop_operator(ccp_grid *g)
+{
+    mg_release(&g->mg);
+    g->has_op = g->has_fixed = false;
+    g->per_channel = false;
+    g->mg_nullspace.forget();
+}
+
+// wop for `sets` operators (1: the shared one; channels: one per channel), pads zero; what it held is gone
+int operator_planes(ccp_grid *g, int sets)
+{
+    if (g->op_sets == sets) return CCP_OK;
+    const size_t count = 4 * (size_t)sets * (size_t)g->geom.ch_stride;
+    g->op_sets = 0;
+    CCP_TRY(g->wop.alloc(count));
+    CCP_HIP(hipMemsetAsync(g->wop.p, 0, sizeof(double) * count, g->stream));
+    g->op_sets = sets;
+    return CCP_OK;
+}
+
+// The handle's operators (one that all channels share, the views H x W; or per_channel: one per channel, the views
+// H x W x C) from three weight views and, with `fixed`, a mask of fixed pixels: all planes in one launch, the verdict
+// and, with a mask, every set's counts in one read.  The old operator and the hierarchy built on it are gone either
+// way: a refusal leaves the handle with none.  The three extra planes stay only if some set has a fixed pixel: with
+// none the four planes are what the call without a mask forms, bit for bit.
+int form_operator(ccp_grid *g, bool per_channel, const ImageView &wx, const ImageView &wy, const ImageView &lam, const ImageView *fixed)
+{
+    const Geom &geo = g->geom;
+    const long n = geo.ch_stride;
+    const int sets = per_channel ? g->desc.channels : 1;
+    drop_operator(g);
+    g->wcons.release();
+    CCP_TRY(operator_planes(g, sets));
+    if (fixed) {
+        CCP_TRY(g->wcons.alloc(3 * (size_t)sets * (size_t)n));
+        CCP_HIP(hipMemsetAsync(g->wcons.p, 0, 3 * sizeof(double) * (size_t)sets * (size_t)n, g->stream));   // the pads
+    }
+    CCP_TRY(weighted_coef(g->stream, wx, wy, lam, fixed, geo.W, geo.H, sets, geo.pitch, g->wop.p, n, g->wcons.p, g->wcount.p));
+    unsigned long long count[1 + 3 * kMaxChannels] = {1};
+    CCP_HIP(hipMemcpyAsync(count, g->wcount.p, sizeof(unsigned long long) * (size_t)(1 + 3 * sets), hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    bool any_fixed = false;
+    for (int c = 0; c < sets && fixed; ++c) any_fixed = any_fixed || count[1 + 3 * c] != 0;
+    if (count[0] || !any_fixed) g->wcons.release();
+    if (count[0]) return CCP_ERR_BAD_ARG;
+    for (int c = 0; c < sets; ++c) {
+        g->pc_fixed[c] = fixed ? (long)count[1 + 3 * c] : 0;
+        g->pc_live[c] = fixed ? (long)geo.W * geo.H - (long)count[1 + 3 * c] - (long)count[2 + 3 * c] : -1;
+        g->pc_edges[c] = fixed ? (long)count[3 + 3 * c] : 0;
+    }
+    g->has_op = true;
+    g->per_channel = per_channel;
+    g->has_fixed = any_fixed;
+    return edge_timeout_status(g);
+}
+
+// a channel's dead pixels counted once (an operator formed without a mask)
+int count_live(ccp_grid *g, const double *d, long *live)
+{
+    const Geom &geo = g->geom;
+    unsigned long long dead = 0;
+    CCP_HIP(hipMemsetAsync(g->wcount.p, 0, sizeof(unsigned long long), g->stream));
+    hipLaunchKernelGGL(k_weighted_count_dead, pixel_grid(g, geo.H), dim3(kBlock), 0, g->stream, d, geo.W, geo.H, geo.pitch, g->wcount.p);
+    CCP_HIP(hipGetLastError());
+    CCP_HIP(hipMemcpyAsync(&dead, g->wcount.p, sizeof(dead), hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    *live = (long)geo.W * geo.H - (long)dead;
+    return CCP_OK;
+}
+
+// ccp_grid_set_weights_[constrained_]device and ccp_grid_set_weights_per_channel_device: the views are H x W for the
+// shared operator and H x W x channels for one operator per channel
+int set_weights_device(ccp_grid *g, bool per_channel, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
+                       const ccp_device_array *fixed)
+{
+    CCP_TRY(weighted_handle(g));
+    const int W = g->desc.width, H = g->desc.height, C = per_channel ? g->desc.channels : 1;
+    const ccp_device_array *src[3] = {wx, wy, lambda};
+    const double dflt[3] = {1.0, 1.0, 0.0};
+    ImageView v[3];
+    for (int i = 0; i < 3; ++i) {
+        if (src[i]) CCP_TRY(check_view(g, src[i], kF32F64, false, 1, H, W, C));
+        v[i] = image_view(src[i], dflt[i]);
+    }
+    if (!fixed) return form_operator(g, per_channel, v[0], v[1], v[2], nullptr);
+    CCP_TRY(check_view(g, fixed, kF32F64 | kU8, false, 1, H, W, C));
+    const ImageView m = image_view(fixed, 0.0);
+    return form_operator(g, per_channel, v[0], v[1], v[2], &m);
+}
+
+// b := A x (MODE 0) or the residual's partial sums (MODE 1) of every channel of a weighted handle.  With one operator
+// per channel the same kernel runs once per channel on that channel's planes, vectors and slice of the partial sums:
+// the launch a one-channel handle makes.
+template <int MODE>
+int weighted_apply_mode(ccp_grid *g)
+{
+    dim3 grid = weighted_apply_grid(g);
+    const long n = g->geom.ch_stride;
+    if (!g->per_channel) {
+        hipLaunchKernelGGL((k_weighted_apply<MODE>), grid, dim3(kBlock), 0, g->stream, g->x.p, g->b.p, g->geom, g->wop.p, n, g->wpart.p);
+        CCP_HIP(hipGetLastError());
+        return CCP_OK;
+    }
+    grid.z = 2;
+    for (int ch = 0; ch < g->desc.channels; ++ch) {
+        hipLaunchKernelGGL((k_weighted_apply<MODE>), grid, dim3(kBlock), 0, g->stream, g->x.p + ch * n, g->b.p + ch * n, g->geom,
+                           g->wop.p + 4 * ch * n, n, g->wpart.p + 4L * ch * grid.x);
+        CCP_HIP(hipGetLastError());
+    }
+    return CCP_OK;
+}
+
+}  // namespace
+
+int ccp::weighted_apply(ccp_grid *g, int mode) { return mode == 0 ? weighted_apply_mode<0>(g) : weighted_apply_mode<1>(g); }
+
+extern "C" {
+
+int ccp_grid_assemble_weighted_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes, const float *f,
+                                   int64_t f_stride_bytes, int32_t init_x_from_f)
+try {
+    CCP_TRY(weighted_handle(g));
+    return weighted_rhs_host(g, gx, gy, field_stride_bytes, f, f_stride_bytes, nullptr, 0, init_x_from_f != 0);
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_weighted_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f,
+                                          int32_t init_x_from_f)
+try {
+    CCP_TRY(weighted_handle(g));
+    return weighted_rhs_device(g, gx, gy, f, nullptr, init_x_from_f != 0);
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_constrained_rhs(ccp_grid *g, const float *gx, const float *gy, int64_t field_stride_bytes, const float *f,
+                                      int64_t f_stride_bytes, const float *values, int64_t values_stride_bytes, int32_t init)
+try {
+    CCP_TRY(weighted_handle(g));
+    return weighted_rhs_host(g, gx, gy, field_stride_bytes, f, f_stride_bytes, values, values_stride_bytes, init != 0);
+} CCP_ABI_CATCH
+
+int ccp_grid_assemble_constrained_rhs_device(ccp_grid *g, const ccp_device_array *gx, const ccp_device_array *gy, const ccp_device_array *f,
+                                             const ccp_device_array *values, int32_t init)
+try {
+    CCP_TRY(weighted_handle(g));
+    return weighted_rhs_device(g, gx, gy, f, values, init != 0);
+} CCP_ABI_CATCH
+
+int ccp_grid_set_weights_host(ccp_grid *g, const float *wx, const float *wy, const float *lambda, int64_t row_stride_bytes)
+try {
+    return ccp_grid_set_weights_constrained_host(g, wx, wy, lambda, row_stride_bytes, nullptr, 0);
+} CCP_ABI_CATCH
+
+int ccp_grid_set_weights_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda)
+try {
+    return ccp_grid_set_weights_constrained_device(g, wx, wy, lambda, nullptr);
+} CCP_ABI_CATCH
+
+int ccp_grid_set_weights_constrained_host(ccp_grid *g, const float *wx, const float *wy, const float *lambda, int64_t row_stride_bytes,
+                                          const uint8_t *fixed, int64_t fixed_stride_bytes)
+try {
+    CCP_TRY(weighted_handle(g));
+    const int W = g->desc.width, H = g->desc.height;
+    const float *src[3] = {wx, wy, lambda};
+    if ((wx || wy || lambda) && row_stride_bytes < (int64_t)W * (int64_t)sizeof(float)) return CCP_ERR_BAD_ARG;
+    if (fixed && fixed_stride_bytes < (int64_t)W) return CCP_ERR_BAD_ARG;
+    const double dflt[3] = {1.0, 1.0, 0.0};
+    DevBuf<float> dev[3];
+    DevBuf<uint8_t> dfix;
+    ImageView v[3];
+    for (int i = 0; i < 3; ++i) {
+        v[i] = ImageView{nullptr, 0, 0, 0, 0, dflt[i]};
+        if (!src[i]) continue;
+        CCP_TRY(dev[i].alloc((size_t)W * H));
+        CCP_HIP(hipMemcpy2DAsync(dev[i].p, (size_t)W * sizeof(float), src[i], (size_t)row_stride_bytes, (size_t)W * sizeof(float), (size_t)H,
+                                 hipMemcpyHostToDevice, g->stream));
+        v[i] = ImageView{dev[i].p, (long)W, 1, 0, CCP_DTYPE_F32, dflt[i]};
+    }
+    if (!fixed) return form_operator(g, false, v[0], v[1], v[2], nullptr);
+    CCP_TRY(dfix.alloc((size_t)W * H));
+    CCP_HIP(hipMemcpy2DAsync(dfix.p, (size_t)W, fixed, (size_t)fixed_stride_bytes, (size_t)W, (size_t)H, hipMemcpyHostToDevice, g->stream));
+    const ImageView m{dfix.p, (long)W, 1, 0, CCP_DTYPE_U8, 0.0};
+    return form_operator(g, false, v[0], v[1], v[2], &m);
+} CCP_ABI_CATCH
+
+int ccp_grid_set_weights_constrained_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
+                                            const ccp_device_array *fixed)
+try {
+    return set_weights_device(g, false, wx, wy, lambda, fixed);
+} CCP_ABI_CATCH
+
+int ccp_grid_constraint_info(ccp_grid *g, int64_t *fixed_pixels, int64_t *free_live_pixels, int64_t *boundary_edges)
+try {
+    return ccp_grid_constraint_info_channel(g, 0, fixed_pixels, free_live_pixels, boundary_edges);
+} CCP_ABI_CATCH
+
+int ccp_grid_constraint_info_channel(ccp_grid *g, int32_t channel, int64_t *fixed_pixels, int64_t *free_live_pixels, int64_t *boundary_edges)
+try {
+    CCP_TRY(weighted_handle(g));
+    if (channel < 0 || channel >= g->desc.channels) return CCP_ERR_BAD_ARG;
+    if (!g->has_op) return CCP_ERR_STATE;
+    const int k = g->per_channel ? channel : 0;                            // the shared operator is every channel's
+    // an operator formed without a mask: its dead pixels counted once
+    if (g->pc_live[k] < 0) CCP_TRY(count_live(g, g->wop.p + 4 * (long)k * g->geom.ch_stride, &g->pc_live[k]));
+    if (fixed_pixels) *fixed_pixels = g->pc_fixed[k];
+    if (free_live_pixels) *free_live_pixels = g->pc_live[k];
+    if (boundary_edges) *boundary_edges = g->pc_edges[k];
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+int ccp_grid_set_weights_per_channel_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
+                                            const ccp_device_array *fixed)
+try {
+    return set_weights_device(g, true, wx, wy, lambda, fixed);
+} CCP_ABI_CATCH
+
+int ccp_grid_operator_channels(ccp_grid *g, int32_t *n)
+try {
+    CCP_TRY(weighted_handle(g));
+    if (!n) return CCP_ERR_BAD_ARG;
+    if (!g->has_op) return CCP_ERR_STATE;
+    *n = g->per_channel ? g->desc.channels : 1;
+    return CCP_OK;
+} CCP_ABI_CATCH
+
+}  // extern "C"
+
+// ============================================================================================
+// The backward pass of a weighted solve (include/ccp_gs.h, "Differentiating a weighted solve"; kernels: ccp_grid_adjoint.hpp)
+// ============================================================================================
+namespace {
+
+AdjIn adj_in(const ccp_device_array *a)
+{
+    if (!a) return AdjIn{nullptr, 0, 0, 0, 0};
+    return AdjIn{a->data, (long)a->stride_y, (long)a->stride_x, (long)a->stride_c, a->dtype};
+}
+
+AdjOut adj_out(const ccp_device_array *a)
+{
+    if (!a) return AdjOut{nullptr, 0, 0, 0, 0};
+    return AdjOut{const_cast<void *>(a->data), (long)a->stride_y, (long)a->stride_x, (long)a->stride_c, a->dtype};
+}
+
+// channel c of a view as a one-channel view (one operator per channel: a launch per channel, each the launch of a
+// one-channel handle on the channel's slices)
+template <typename A>
+A adj_channel(A a, int c)
+{
+    if (a.p) a.p = (decltype(a.p))((const char *)a.p + (long)c * a.sc * (long)dtype_bytes(a.dtype));
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ccp_grid_adjoint_begin_device(ccp_grid *g, const ccp_device_array *grad_x)
+try {
+    CCP_TRY(weighted_handle(g));
+    const Geom &geo = g->geom;
+    CCP_TRY(check_view(g, grad_x, kF32F64, false, 1, geo.H, geo.W, g->desc.channels));
+    if (!g->has_op) return CCP_ERR_STATE;
+    if (g->per_channel) {                                                    // channel c's free / live set: its own d
+        const long n = geo.ch_stride;
+        for (int c = 0; c < g->desc.channels; ++c) {
+            hipLaunchKernelGGL(k_adjoint_begin, pixel_grid(g, geo.H), dim3(kBlock), 0, g->stream, g->b.p + c * n, g->x.p + c * n,
+                               g->wop.p + 4 * c * n, geo.pitch, n, geo.W, 1, adj_channel(adj_in(grad_x), c));
+            CCP_HIP(hipGetLastError());
+        }
+        return edge_timeout_status(g);
+    }
+    hipLaunchKernelGGL(k_adjoint_begin, pixel_grid(g, geo.H), dim3(kBlock), 0, g->stream, g->b.p, g->x.p, g->wop.p, geo.pitch, geo.ch_stride,
+                       geo.W, g->desc.channels, adj_in(grad_x));
+    CCP_HIP(hipGetLastError());
+    return edge_timeout_status(g);
+} CCP_ABI_CATCH
+
+int ccp_grid_weighted_adjoint_device(ccp_grid *g, const ccp_adjoint_inputs *in, const ccp_adjoint_outputs *out)
+try {
+    CCP_TRY(weighted_handle(g));
+    if (!in || !out) return CCP_ERR_BAD_ARG;
+    const Geom &geo = g->geom;
+    const int W = geo.W, H = geo.H, C = g->desc.channels;
+    CCP_TRY(check_view(g, in->u, 1u << CCP_DTYPE_F64, false, 1, H, W, C));
+    if (in->grad_x || out->g_values) CCP_TRY(check_view(g, in->grad_x, kF32F64, false, 1, H, W, C));
+    if (in->gx) CCP_TRY(check_view(g, in->gx, kF32, false, 1, H, W, C));
+    if (in->gy) CCP_TRY(check_view(g, in->gy, kF32, false, 1, H, W, C));
+    if (in->f) CCP_TRY(check_view(g, in->f, kF32F64 | kU8, false, 1, H, W, C));
+    const int PC = g->has_op && g->per_channel ? C : 1;                      // the extent of the weight views along c
+    if (in->wx) CCP_TRY(check_view(g, in->wx, kF32F64, false, 1, H, W, PC));
+    if (in->wy) CCP_TRY(check_view(g, in->wy, kF32F64, false, 1, H, W, PC));
+    if (in->lambda) CCP_TRY(check_view(g, in->lambda, kF32F64, false, 1, H, W, PC));
+    if (in->fixed) CCP_TRY(check_view(g, in->fixed, kF32F64 | kU8, false, 1, H, W, PC));
+    const ccp_device_array *planes[3] = {out->g_wx, out->g_wy, out->g_lambda};
+    const ccp_device_array *images[4] = {out->g_gx, out->g_gy, out->g_f, out->g_values};
+    for (const ccp_device_array *a : planes)
+        if (a) CCP_TRY(check_view(g, a, kF32F64, true, 1, H, W, PC));
+    for (const ccp_device_array *a : images)
+        if (a) CCP_TRY(check_view(g, a, kF32F64, true, 1, H, W, C));
+    if (!g->has_op) return CCP_ERR_STATE;
+    AdjointArgs a{};
+    a.v = g->x.p;
+    a.pitch = geo.pitch;
+    a.ch_stride = geo.ch_stride;
+    a.W = W;
+    a.H = H;
+    a.C = C;
+    a.u = adj_in(in->u);
+    a.grad = adj_in(in->grad_x);
+    a.gx = adj_in(in->gx);
+    a.gy = adj_in(in->gy);
+    a.f = adj_in(in->f);
+    a.wx = adj_in(in->wx);
+    a.wy = adj_in(in->wy);
+    a.lam = adj_in(in->lambda);
+    a.fixed = adj_in(in->fixed);
+    a.g_wx = adj_out(out->g_wx);
+    a.g_wy = adj_out(out->g_wy);
+    a.g_lam = adj_out(out->g_lambda);
+    a.g_gx = adj_out(out->g_gx);
+    a.g_gy = adj_out(out->g_gy);
+    a.g_f = adj_out(out->g_f);
+    a.g_val = adj_out(out->g_values);
+    if (g->per_channel) {
+        // H x W x C weights and weight gradients (their stride_c is used), no sum over channels: one launch per channel,
+        // each the launch of a one-channel handle on channel c's slice of every view
+        for (int c = 0; c < C; ++c) {
+            AdjointArgs k = a;
+            k.C = 1;
+            k.v = a.v + (long)c * geo.ch_stride;
+            k.u = adj_channel(a.u, c);
+            k.grad = adj_channel(a.grad, c);
+            k.gx = adj_channel(a.gx, c);
+            k.gy = adj_channel(a.gy, c);
+            k.f = adj_channel(a.f, c);
+            k.wx = adj_channel(a.wx, c);
+            k.wy = adj_channel(a.wy, c);
+            k.lam = adj_channel(a.lam, c);
+            k.fixed = adj_channel(a.fixed, c);
+            k.g_wx = adj_channel(a.g_wx, c);
+            k.g_wy = adj_channel(a.g_wy, c);
+            k.g_lam = adj_channel(a.g_lam, c);
+            k.g_gx = adj_channel(a.g_gx, c);
+            k.g_gy = adj_channel(a.g_gy, c);
+            k.g_f = adj_channel(a.g_f, c);
+            k.g_val = adj_channel(a.g_val, c);
+            hipLaunchKernelGGL(k_weighted_adjoint, pixel_grid(g, H), dim3(kBlock), 0, g->stream, k);
+            CCP_HIP(hipGetLastError());
+        }
+        return edge_timeout_status(g);
+    }
+    a.wx.sc = a.wy.sc = a.lam.sc = a.fixed.sc = 0;         // H x W: stride_c unused
+    a.g_wx.sc = a.g_wy.sc = a.g_lam.sc = 0;
+    hipLaunchKernelGGL(k_weighted_adjoint, pixel_grid(g, H), dim3(kBlock), 0, g->stream, a);
+    CCP_HIP(hipGetLastError());
+    return edge_timeout_status(g);
+} CCP_ABI_CATCH
+
+}  // extern "C"

@@ -32,9 +32,8 @@
 // handle without the three extra planes.
 //
 // This file holds the operator kernels and is included by ccp_grid_weighted.hip alone (a static __global__ function is
-// compiled into every translation unit that sees it), behind the launchers of ccp_grid_weighted_api.hpp.  w_at and
-// weighted_row are in ccp_grid_stencil.hpp; k_weighted_apply and k_weighted_count_dead, which ccp_grid.hip launches, in
-// ccp_grid_kernels.hpp.
+// compiled into every translation unit that sees it), which holds every call that launches them; ccp_grid_mg.hip reaches
+// the coarsening through a launcher of ccp_grid_weighted_api.hpp.  w_at and weighted_row are in ccp_grid_stencil.hpp.
 #pragma once
 
 #include "ccp_grid_mg.hpp"
@@ -208,6 +207,61 @@ k_weighted_coarsen(MgLevel lv, long fs, const double *__restrict__ lam, long ls,
     lv.ws += ch * fs;
     const long co = ch * cstride;
     mg_coarsen_weighted_cell(lv, lam + ch * ls, cv, X, Y, d + co, we + co, ws + co, lam_c + co, edge);
+}
+
+// ---- weighted handles (ccp_grid_weighted.hpp explains the operator's planes) ----------------------------------------------
+
+// pixels with d = 0 of an operator without fixed pixels (ccp_grid_constraint_info): one atomic per block that has any
+static __global__ void __launch_bounds__(kBlock)
+k_weighted_count_dead(const double *__restrict__ d, int W, int H, long pitch, unsigned long long *__restrict__ count)
+{
+    __shared__ unsigned tally;
+    if (threadIdx.x == 0) tally = 0;
+    __syncthreads();
+    const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y;
+    if (x < W && d[w_at(pitch, x, y)] == 0.0) atomicAdd(&tally, 1u);
+    __syncthreads();
+    if (threadIdx.x == 0 && tally) atomicAdd(count, (unsigned long long)tally);
+}
+
+// MODE 0: b := A x; MODE 1: per (channel, colour) block partial sums of (b - A x)^2 and b^2 at
+// partial[2 ((ch * 2 + c) * gridDim.x + blockIdx.x) + {0, 1}] (k_pair_reduce's layout, gridDim.x blocks per group).
+// grid = (blocks, 1, 2 channels); a block strides over the cells of colour c.
+template <int MODE>
+__global__ void __launch_bounds__(kBlock)
+k_weighted_apply(const double *__restrict__ x, double *__restrict__ b, Geom g, const double *__restrict__ op, long plane,
+                 double *__restrict__ partial)
+{
+    __shared__ double scratch[kBlock / kWave];
+    const int ch = blockIdx.z >> 1, c = blockIdx.z & 1;
+    const double *__restrict__ d = op, *__restrict__ we = op + plane, *__restrict__ ws = op + 2 * plane;
+    const double *__restrict__ xc = x + (long)ch * g.ch_stride;
+    double *__restrict__ bc = b + (long)ch * g.ch_stride;
+    const int hw = (g.W + 1) / 2;
+    const long cells = (long)g.H * hw;
+    double rr = 0.0, bb = 0.0;
+    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < cells; i += (long)gridDim.x * kBlock) {
+        const int y = (int)(i / hw), xi = 2 * (int)(i - (long)y * hw) + ((y + c) & 1);
+        if (xi >= g.W) continue;
+        const double ax = weighted_row(d, we, ws, g.pitch, g.W, g.H, xc, xi, y);
+        const long at = w_at(g.pitch, xi, y);
+        if (MODE == 0) {
+            bc[at] = ax;
+        } else {
+            const double bv = bc[at], r = bv - ax;
+            rr += r * r;
+            bb += bv * bv;
+        }
+    }
+    if (MODE == 1) {
+        const double t0 = block_sum(rr, scratch);
+        const double t1 = block_sum(bb, scratch);
+        if (threadIdx.x == 0) {
+            const long k = 2 * ((long)blockIdx.z * gridDim.x + blockIdx.x);
+            partial[k] = t0;
+            partial[k + 1] = t1;
+        }
+    }
 }
 
 }  // namespace ccp

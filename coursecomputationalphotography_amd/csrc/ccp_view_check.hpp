@@ -1,5 +1,5 @@
 // ccp_view_check.hpp — the host-side refusals of a ccp_device_array (include/ccp_gs.h, "Device hand-off"), shared by
-// the grid handles' _device calls (ccp_grid.hip) and the free panorama calls (ccp_panorama.hip).  Host code only.
+// the grid handles' _device calls (ccp_grid_io.hip, ccp_grid_weighted.hip) and the free panorama calls (ccp_panorama.hip).  Host code only.
 #pragma once
 
 #include "ccp_common.hpp"

@@ -1,4 +1,4 @@
-"""CPU: the ticket order of the reference-order sweep (k_lex_wg, csrc/ccp_grid.hip: lex_ticket_order) through the host-only
+"""CPU: the ticket order of the reference-order sweep (k_lex_wg, csrc/ccp_grid_lex.hip: lex_ticket_order) through the host-only
 diagnostic entry point ccp_debug_lex_tickets — no GPU needed.
 
 The launch holds as many persistent workgroups as the chip has room for; each takes the next ticket and WAITS inside the
