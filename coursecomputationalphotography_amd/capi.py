@@ -94,6 +94,7 @@ ABI_SYMBOLS = (
     "ccp_grid_set_weights_per_channel_device", "ccp_grid_operator_channels", "ccp_grid_mg_level_channel",
     "ccp_grid_constraint_info_channel",
     "ccp_grid_mg_prepare", "ccp_grid_mg_conjugate_gradient_enqueue",
+    "ccp_grid_refresh_weights_device", "ccp_grid_operator_status",
     "ccp_grid_set_mask_device", "ccp_mask_erode_cross_device", "ccp_panorama_begin_device", "ccp_panorama_add_device",
     "ccp_panorama_finish_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
@@ -313,6 +314,8 @@ def load() -> C.CDLL:
     L.ccp_grid_constraint_info.argtypes = [vp, vp, vp, vp]
     L.ccp_grid_set_weights_per_channel_device.argtypes = [vp, vp, vp, vp, vp]
     L.ccp_grid_operator_channels.argtypes = [vp, C.POINTER(i32)]
+    L.ccp_grid_refresh_weights_device.argtypes = [vp, vp, vp, vp]
+    L.ccp_grid_operator_status.argtypes = [vp, C.POINTER(i32)]
     L.ccp_grid_mg_level_channel.argtypes = [vp, i32, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
     L.ccp_grid_constraint_info_channel.argtypes = [vp, i32, vp, vp, vp]
     L.ccp_grid_adjoint_begin_device.argtypes = [vp, da]
@@ -1258,6 +1261,30 @@ class Grid:
         m = self._mask_array(fixed)
         self._on_stream(lambda: self.L.ccp_grid_set_weights_constrained_device(self.h, *refs, C.byref(m)),
                         "ccp_grid_set_weights_constrained_device")
+
+    def refresh_weights_tensor(self, wx=None, wy=None, lam=None):
+        """New VALUES for the installed operator and everything mg_prepare derived from it, enqueued on torch's current
+        stream: no allocation and no synchronisation, so torch.cuda.graph may record it.  The operator's kind (shared:
+        H x W tensors; per channel: H x W x channels, an H x W tensor serves every channel), the fixed pixels, the
+        hierarchy kind and every mode stay; None takes the setters' defaults.  Needs an installed operator and mg_prepare
+        (CcpError STATE otherwise).  The verdict stays on the device: operator_status(), or field 5 of the enqueue solve's
+        report.  A refused refresh poisons the operator until the next good one; it never drops it."""
+        torch = self._torch()
+        named = ((wx, "wx"), (wy, "wy"), (lam, "lam"))
+        per_channel = self.operator_channels() > 1 or (self.C == 1 and any(isinstance(t, torch.Tensor) and t.dim() == 3 for t, _ in named))
+        if per_channel:
+            arrs = [self._channel_array(t, n, (torch.float32, torch.float64)) for t, n in named]
+        else:
+            arrs = [self._weight_array(t, n) for t, n in named]
+        refs = [None if a is None else C.byref(a) for a in arrs]
+        self._on_stream(lambda: self.L.ccp_grid_refresh_weights_device(self.h, *refs), "ccp_grid_refresh_weights_device")
+
+    def operator_status(self) -> int:
+        """The operator status word of the last refresh_weights_tensor (0: good; 1: a bad weight, 2: out of float range in
+        "f32" precision, 4: not floating in "constant" null-space mode, summed); 0 after a setter.  Synchronises."""
+        word = C.c_int32()
+        self._on_stream(lambda: self.L.ccp_grid_operator_status(self.h, C.byref(word)), "ccp_grid_operator_status")
+        return word.value
 
     def assemble_constrained_rhs_tensor(self, gx=None, gy=None, f=None, values=None, init_x: bool = False):
         """assemble_constrained_rhs from H x W x channels tensors: gx, gy float32; f and values u8, float32 or float64."""

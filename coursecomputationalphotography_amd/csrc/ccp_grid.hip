@@ -871,6 +871,8 @@ try {
         if (st == CCP_OK && hipMemset(g->wop.p, 0, 4 * sizeof(double) * (size_t)geo.ch_stride) != hipSuccess) st = CCP_ERR_HIP;
         if (st == CCP_OK) st = g->wpart.alloc(4 * (size_t)d->channels * kWeightedApplyBlocks);
         if (st == CCP_OK) st = g->wcount.alloc(1 + 3 * kMaxChannels);
+        if (st == CCP_OK) st = g->rcount.alloc(1 + 3 * kMaxChannels);
+        if (st == CCP_OK) st = g->op_status.alloc(1);
     }
     // partial sums: the finest launch is one block per (x tile, row, channel*2) with 2 doubles
     const size_t part = (size_t)((geo.pitch + 2L * kBlock - 1) / (2L * kBlock)) * geo.local_rows * d->channels * 2 * 2 + 64;
@@ -995,6 +997,9 @@ int ccp::grid_mg_view(ccp_grid *g, GridMgView *v)
     v->lam_stride = g->has_fixed ? 3 * n : 4 * n;
     v->cfg = g->mg_cfg;
     v->ns = &g->mg_nullspace;
+    v->refreshed = g->refreshed;
+    v->op_status = g->op_status.p;
+    v->op_verdict = g->rcount.p;
     v->stream = g->stream;
     v->device = g->device;
     v->cache = &g->mg;

@@ -184,7 +184,8 @@ void coarsen(int kind, hipStream_t s, const MgLevel &f, const MgLevel &c, int Y0
 
 int level_kind(const MgHierarchy &h, int k) { return k ? kMgCoarse : h.kind0; }
 
-int build(const GridMgView &v, MgHierarchy **out)
+// The hierarchy of a view laid out and allocated, every buffer zeroed, its coarse levels not filled yet: build's first half
+int lay_out(const GridMgView &v, MgHierarchy **out)
 {
     MgHierarchy *h = new MgHierarchy();
     std::unique_ptr<MgHierarchy> own(h);
@@ -272,18 +273,38 @@ int build(const GridMgView &v, MgHierarchy **out)
             }
         }
     }
-    for (int k = 0; k + 1 < h->levels; ++k) {
-        if (v.weighted)                                             // level k + 1 of all OC operators in one launch
-            CCP_TRY(weighted_coarsen(v.stream, OC, h->lv[k], k ? 4 * h->size[k] : v.op_stride,
-                                     k ? static_cast<const double *>(h->coef(0, k, 3)) : v.wlam, k ? 4 * h->size[k] : v.lam_stride, h->lv[k + 1],
-                                     h->coef(0, k + 1, 0), h->coef(0, k + 1, 1), h->coef(0, k + 1, 2), h->coef(0, k + 1, 3), 4 * h->size[k + 1],
-                                     rescaled ? 0.5 : 1.0));
-        else
-            coarsen(level_kind(*h, k), v.stream, h->lv[k], h->lv[k + 1], 0, h->lv[k + 1].H, h->arr(k + 1, 0), h->arr(k + 1, 1), h->arr(k + 1, 2));
-        CCP_HIP(hipGetLastError());
-    }
     if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return CCP_ERR_HIP;
     *out = own.release();
+    return CCP_OK;
+}
+
+// The coarse levels' coefficients from level 0, every cell of every level: launches only.  build's second half, and
+// all the hierarchy's fp64 coefficients need of ccp_grid_refresh_weights_device.
+int fill_levels(const GridMgView &v, MgHierarchy &h)
+{
+    const double edge = v.weighted && v.cfg.hierarchy == CCP_MG_HIERARCHY_RESCALED ? 0.5 : 1.0;
+    for (int k = 0; k + 1 < h.levels; ++k) {
+        if (v.weighted)                                             // level k + 1 of all opC operators in one launch
+            CCP_TRY(weighted_coarsen(v.stream, h.opC, h.lv[k], k ? 4 * h.size[k] : v.op_stride,
+                                     k ? static_cast<const double *>(h.coef(0, k, 3)) : v.wlam, k ? 4 * h.size[k] : v.lam_stride, h.lv[k + 1],
+                                     h.coef(0, k + 1, 0), h.coef(0, k + 1, 1), h.coef(0, k + 1, 2), h.coef(0, k + 1, 3), 4 * h.size[k + 1], edge));
+        else
+            coarsen(level_kind(h, k), v.stream, h.lv[k], h.lv[k + 1], 0, h.lv[k + 1].H, h.arr(k + 1, 0), h.arr(k + 1, 1), h.arr(k + 1, 2));
+        CCP_HIP(hipGetLastError());
+    }
+    return CCP_OK;
+}
+
+int build(const GridMgView &v, MgHierarchy **out)
+{
+    MgHierarchy *h = nullptr;
+    CCP_TRY(lay_out(v, &h));
+    const int st = fill_levels(v, *h);
+    if (st != CCP_OK) {
+        delete h;
+        return st;
+    }
+    *out = h;
     return CCP_OK;
 }
 
@@ -446,8 +467,28 @@ int whole_levels(MgHierarchy &h, hipStream_t s, int from, const double *b0, doub
 }
 
 // ---- CCP_MG_PRECISION_F32 (ccp_grid_mgs.hpp) -------------------------------------------------------------------------
-// The float copies of every level's coefficients and the float vectors, once per hierarchy: CCP_ERR_UNSUPPORTED (now
-// and at every later V-cycle of this hierarchy) if a coefficient narrows to inf or a non-zero one to 0.  One read-back.
+// The narrowing itself: every level's d, we, ws of every operator into its float copy, every launch ORing into h.fbad,
+// which the caller has cleared (narrow_levels by a memset; ccp_grid_refresh_weights_device, which runs these launches
+// again on new values, in k_mge_clear).  Launches only.
+int narrow_launch(const GridMgView &v, MgHierarchy &h)
+{
+    hipStream_t s = v.stream;
+    const long n0 = v.geom.ch_stride;
+    auto narrow = [&](const double *src, float *dst, long n) {
+        hipLaunchKernelGGL(k_mgs_narrow, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, src, dst, n, h.fbad.p);
+    };
+    for (int ch = 0; ch < h.opC; ++ch)
+        for (int k = 0; k < h.levels; ++k) {
+            if (k) narrow(h.coef(ch, k, 0), h.fcoef(ch, k, 0), 3 * h.size[k]);   // d, we, ws lie one after the other in both stores
+            else if (h.weighted) narrow(h.levels_of(ch)[0].d, h.w32.p + 3 * n0 * ch, 3 * n0);   // the handle's planes, n0 doubles apart
+        }
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+// The float copies of every level's coefficients and the float vectors, once per hierarchy: allocated and described
+// here, filled by narrow_launch.  CCP_ERR_UNSUPPORTED (now and at every later V-cycle of this hierarchy) if a coefficient
+// narrows to inf or a non-zero one to 0.  One read-back.
 int narrow_levels(const GridMgView &v, MgHierarchy &h)
 {
     if (h.narrowed) return h.narrowed > 0 ? CCP_OK : CCP_ERR_UNSUPPORTED;
@@ -467,9 +508,6 @@ int narrow_levels(const GridMgView &v, MgHierarchy &h)
         CCP_TRY(h.fstore.alloc((size_t)total));
         CCP_HIP(hipMemsetAsync(h.fstore.p, 0, sizeof(float) * total, s));
     }
-    auto narrow = [&](const double *src, float *dst, long n) {
-        hipLaunchKernelGGL(k_mgs_narrow, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, src, dst, n, h.fbad.p);
-    };
     if (h.opC > 1) {
         const long ftotal = 3 * h.cbase.back() / 4 + 3L * h.opC * h.size.back();
         CCP_TRY(h.cfstore.alloc((size_t)ftotal));
@@ -488,19 +526,17 @@ int narrow_levels(const GridMgView &v, MgHierarchy &h)
             f.mask = l.mask;
             f.g0 = l.g0;
             if (k) {
-                narrow(h.coef(ch, k, 0), h.fcoef(ch, k, 0), 3 * h.size[k]);   // d, we, ws lie one after the other in both stores
                 f.d = h.fcoef(ch, k, 0);
                 f.we = h.fcoef(ch, k, 1);
                 f.ws = h.fcoef(ch, k, 2);
-            } else if (h.weighted) {                                // the handle's d, we, ws planes, n0 doubles apart
+            } else if (h.weighted) {                                // the copy of the handle's d, we, ws planes
                 float *w = h.w32.p + 3 * n0 * ch;
-                narrow(l.d, w, 3 * n0);
                 f.d = w;
                 f.we = w + n0;
                 f.ws = w + 2 * n0;
             }
         }
-    CCP_HIP(hipGetLastError());
+    CCP_TRY(narrow_launch(v, h));
     unsigned bad = 0;
     CCP_HIP(hipMemcpyAsync(&bad, h.fbad.p, sizeof(bad), hipMemcpyDeviceToHost, s));
     CCP_HIP(hipStreamSynchronize(s));
@@ -881,10 +917,11 @@ struct NullspaceSteps : ChannelSteps {
     double pixels;                   // W H
     MgnState *ns;
     double *npart;                   // 3 x `blocks` partial sums
+    const unsigned *hold = nullptr;  // the enqueue solve on a refreshed operator: its status word (k_mgn_means)
     void means(const double *a, const double *b2, int which) const
     {
         hipLaunchKernelGGL(k_mgn_sums, dim3(blocks), dim3(kBlock), 0, s, a, b2, lay, npart);
-        hipLaunchKernelGGL(k_mgn_means, dim3(1), dim3(kBlock), 0, s, static_cast<const double *>(npart), blocks, pixels, which, ns);
+        hipLaunchKernelGGL(k_mgn_means, dim3(1), dim3(kBlock), 0, s, static_cast<const double *>(npart), blocks, pixels, which, ns, hold);
     }
     void shift() const { hipLaunchKernelGGL(k_mgn_shift, dim3(blocks), dim3(kBlock), 0, s, x, lay, static_cast<const MgnState *>(ns)); }
     int residual() const                                                 // bm, m0; r = A x
@@ -1229,6 +1266,18 @@ int check_handle(ccp_grid *g, GridMgView *v)
 // (only a weighted handle can hold the value: kOptions)
 bool constant_mode(const GridMgView &v) { return v.cfg.nullspace == CCP_MG_NULLSPACE_CONSTANT; }
 
+// The census of the handle's operators into h.nscount, one word per operator, which the caller has cleared (nullspace_ready
+// by a memset, the refresh in k_mge_clear): one launch
+int census_launch(const GridMgView &v, MgHierarchy &h)
+{
+    dim3 grid = cells_grid(v.geom.W, v.geom.H);
+    grid.z = (unsigned)v.op_channels;
+    hipLaunchKernelGGL(k_mgn_census, grid, dim3(kBlock), 0, v.stream, v.wd, v.op_stride, (long)v.geom.ch_stride, v.geom.W, v.geom.H,
+                       (long)v.geom.pitch, h.nscount.p);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
 // The mode's buffers, once per hierarchy, and the census of the handle's operators, once per installed operator (one
 // read-back): CCP_ERR_UNSUPPORTED unless every one is floating
 int nullspace_ready(const GridMgView &v, MgHierarchy &h)
@@ -1244,11 +1293,7 @@ int nullspace_ready(const GridMgView &v, MgHierarchy &h)
         const int sets = v.op_channels;
         unsigned bad[kMaxChannels] = {};
         CCP_HIP(hipMemsetAsync(h.nscount.p, 0, sizeof(unsigned) * kMaxChannels, v.stream));
-        dim3 grid = cells_grid(v.geom.W, v.geom.H);
-        grid.z = (unsigned)sets;
-        hipLaunchKernelGGL(k_mgn_census, grid, dim3(kBlock), 0, v.stream, v.wd, v.op_stride, (long)v.geom.ch_stride, v.geom.W, v.geom.H,
-                           (long)v.geom.pitch, h.nscount.p);
-        CCP_HIP(hipGetLastError());
+        CCP_TRY(census_launch(v, h));
         CCP_HIP(hipMemcpyAsync(bad, h.nscount.p, sizeof(unsigned) * (size_t)sets, hipMemcpyDeviceToHost, v.stream));
         CCP_HIP(hipStreamSynchronize(v.stream));
         ns.floating = 1;
@@ -1301,6 +1346,17 @@ int vcycle_ready(const GridMgView &v, MgHierarchy **out)
     return CCP_OK;
 }
 
+// An operator that ccp_grid_refresh_weights_device installed has its verdict on the device: the synchronous calls read it
+// (one wait) and refuse a poisoned operator before they touch x or b.  A setter's operator was validated on the host.
+int refreshed_operator_ok(const GridMgView &v)
+{
+    if (!v.refreshed) return CCP_OK;
+    unsigned word = 1;
+    CCP_HIP(hipMemcpyAsync(&word, v.op_status, sizeof(word), hipMemcpyDeviceToHost, v.stream));
+    CCP_HIP(hipStreamSynchronize(v.stream));
+    return word ? CCP_ERR_STATE : CCP_OK;
+}
+
 // What ccp_grid_mg_apply (max_iteration 0) and the solve do alike before their first launch, in the handle's present
 // configuration: the refusals, then vcycle_ready.
 int call_ready(ccp_grid *g, int32_t max_iteration, int32_t smoothing_sweeps, GridMgView *v, int *nu, MgHierarchy **out)
@@ -1309,6 +1365,7 @@ int call_ready(ccp_grid *g, int32_t max_iteration, int32_t smoothing_sweeps, Gri
     CCP_TRY(sweeps_arg(smoothing_sweeps, nu, v->cfg.smoother));
     if (max_iteration < 0) return CCP_ERR_BAD_ARG;
     CCP_TRY(config_check(*v));
+    CCP_TRY(refreshed_operator_ok(*v));
     return vcycle_ready(*v, out);
 }
 
@@ -1354,6 +1411,7 @@ int pcg_solve(const GridMgView &v, MgHierarchy &h, double epsilon, int max_itera
         NullspaceSteps S{};
         S.lay = nullspace_layout(v), S.pixels = (double)v.geom.W * (double)v.geom.H;
         S.npart = h.nspart.p;
+        S.hold = enqueue && v.refreshed ? v.op_status : nullptr;
         CCP_TRY(channels(S, [&](int ch) {
             S.ns = h.nsstate.p + ch;
             v.ns->solved[ch] = false;
@@ -1441,6 +1499,57 @@ int get_option(ccp_grid *g, int which, int32_t *value)
 }
 
 }  // namespace
+
+// ---- the hierarchy's half of ccp_grid_refresh_weights_device (ccp_grid_weighted.hip; ccp_grid_weighted_api.hpp) ---------
+namespace {
+
+// which of the mode-dependent verdicts a refresh of this view forms (config_check: batched channels are fp64, no null space)
+struct RefreshPlan {
+    bool f32, census;
+};
+
+RefreshPlan refresh_plan(const GridMgView &v, const MgHierarchy &h)
+{
+    const bool batched = v.cfg.channels == CCP_MG_CHANNELS_BATCHED;
+    return RefreshPlan{!batched && h.precision == CCP_MG_PRECISION_F32, !batched && constant_mode(v)};
+}
+
+}  // namespace
+
+// Is the handle one block with an operator, and is what the last ccp_grid_mg_prepare built still there and built for the
+// handle's present options?  (Any smoothing_sweeps: no coefficient depends on them.)  CCP_ERR_STATE with nothing enqueued
+// otherwise.  If so, the refresh's first launch: every word its kernels OR or count into, zeroed (n_counts of op_verdict).
+int ccp::mg_refresh_begin(ccp_grid *g, int n_counts)
+{
+    GridMgView v{};
+    CCP_TRY(check_handle(g, &v));
+    MgHierarchy *h = *v.cache;
+    const bool ready = h && h->prepared && h->estate.p && cache_serves(v, *h) && h->prep_cfg == v.cfg && h->prep_channels == v.channels;
+    if (!ready) return CCP_ERR_STATE;
+    const RefreshPlan plan = refresh_plan(v, *h);
+    hipLaunchKernelGGL(k_mge_clear, dim3(1), dim3(kBlock), 0, v.stream, v.op_status, v.op_verdict, n_counts, plan.f32 ? h->fbad.p : nullptr,
+                       plan.census ? h->nscount.p : nullptr);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
+// Level 0's planes hold new values (k_weighted_refresh is on the stream): everything derived from them again, by the
+// launches that built it -- the coarse levels, the float copies, the census -- and the three verdicts folded into the
+// status word.  Launches only; call after mg_refresh_begin said yes.
+int ccp::mg_refresh(ccp_grid *g)
+{
+    GridMgView v{};
+    CCP_TRY(check_handle(g, &v));
+    MgHierarchy &h = **v.cache;
+    const bool f32 = refresh_plan(v, h).f32, census = refresh_plan(v, h).census;
+    CCP_TRY(fill_levels(v, h));
+    if (f32) CCP_TRY(narrow_launch(v, h));
+    if (census) CCP_TRY(census_launch(v, h));
+    hipLaunchKernelGGL(k_mge_status, dim3(1), dim3(kBlock), 0, v.stream, v.op_verdict, f32 ? static_cast<const unsigned *>(h.fbad.p) : nullptr,
+                       census ? static_cast<const unsigned *>(h.nscount.p) : nullptr, v.op_channels, v.op_status);
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
 
 extern "C" {
 
@@ -1598,12 +1707,14 @@ try {
     if (report) CCP_TRY(check_view_on(v.device, report, 1u << CCP_DTYPE_F64, true, 1, v.channels, kMgeReportFields, 1));
     MgHierarchy *h = *v.cache;
     if (!prepared_for(v, h, nu)) return CCP_ERR_STATE;
-    hipLaunchKernelGGL(k_mge_init, dim3(1), dim3(kBlock), 0, v.stream, h->estate.p, v.channels);
+    const unsigned *status = v.refreshed ? v.op_status : nullptr;   // (a setter's operator was validated on the host)
+    hipLaunchKernelGGL(k_mge_init, dim3(1), dim3(kBlock), 0, v.stream, h->estate.p, v.channels, status);
     CCP_TRY(pcg_solve(v, *h, epsilon, max_iteration, nu, nullptr, true));
     if (report) {
         const MgeReport out{static_cast<double *>(const_cast<void *>(report->data)), (long)report->stride_y, (long)report->stride_x};
         const MgnState *ns = constant_mode(v) ? h->nsstate.p : nullptr;
-        hipLaunchKernelGGL(k_mge_report, dim3(1), dim3(kBlock), 0, v.stream, static_cast<const CgState *>(h->estate.p), ns, v.channels, out);
+        hipLaunchKernelGGL(k_mge_report, dim3(1), dim3(kBlock), 0, v.stream, static_cast<const CgState *>(h->estate.p), ns, v.channels, out,
+                           status);
     }
     CCP_HIP(hipGetLastError());
     return CCP_OK;

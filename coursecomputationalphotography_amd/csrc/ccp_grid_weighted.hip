@@ -6,6 +6,7 @@
 #include "ccp_grid_pco.hpp"
 #include "ccp_grid_weighted.hpp"
 #include "ccp_grid_adjoint.hpp"
+#include "ccp_grid_weighted_api.hpp"
 #include "ccp_view_check.hpp"
 
 #include <atomic>
@@ -180,7 +181,23 @@ void drop_operator(ccp_grid *g)
     mg_release(&g->mg);
     g->has_op = g->has_fixed = false;
     g->per_channel = false;
+    g->refreshed = g->counts_pending = false;
     g->mg_nullspace.forget();
+}
+
+// ccp_grid_constraint_info after a refresh: the counts the refresh pass left on the device, read once (one wait)
+int refreshed_counts(ccp_grid *g)
+{
+    const int sets = g->per_channel ? g->desc.channels : 1;
+    unsigned long long count[1 + 3 * kMaxChannels] = {};
+    CCP_HIP(hipMemcpyAsync(count, g->rcount.p, sizeof(unsigned long long) * (size_t)(1 + 3 * sets), hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    for (int c = 0; c < sets; ++c) {
+        g->pc_live[c] = (long)g->geom.W * g->geom.H - g->pc_fixed[c] - (long)count[2 + 3 * c];
+        g->pc_edges[c] = (long)count[3 + 3 * c];
+    }
+    g->counts_pending = false;
+    return CCP_OK;
 }
 
 // wop for `sets` operators (1: the shared one; channels: one per channel), pads zero; what it held is gone
@@ -375,6 +392,7 @@ try {
     if (channel < 0 || channel >= g->desc.channels) return CCP_ERR_BAD_ARG;
     if (!g->has_op) return CCP_ERR_STATE;
     const int k = g->per_channel ? channel : 0;                            // the shared operator is every channel's
+    if (g->counts_pending) CCP_TRY(refreshed_counts(g));
     // an operator formed without a mask: its dead pixels counted once
     if (g->pc_live[k] < 0) CCP_TRY(count_live(g, g->wop.p + 4 * (long)k * g->geom.ch_stride, &g->pc_live[k]));
     if (fixed_pixels) *fixed_pixels = g->pc_fixed[k];
@@ -387,6 +405,42 @@ int ccp_grid_set_weights_per_channel_device(ccp_grid *g, const ccp_device_array 
                                             const ccp_device_array *fixed)
 try {
     return set_weights_device(g, true, wx, wy, lambda, fixed);
+} CCP_ABI_CATCH
+
+int ccp_grid_refresh_weights_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda)
+try {
+    CCP_TRY(weighted_handle(g));
+    if (!g->has_op) return CCP_ERR_STATE;                                  // (the operator's kind decides the views' extents)
+    const Geom &geo = g->geom;
+    const int sets = g->per_channel ? g->desc.channels : 1;
+    const ccp_device_array *src[3] = {wx, wy, lambda};
+    const double dflt[3] = {1.0, 1.0, 0.0};
+    ImageView v[3];
+    for (int i = 0; i < 3; ++i) {
+        if (src[i]) CCP_TRY(check_view(g, src[i], kF32F64, false, 1, geo.H, geo.W, sets));
+        v[i] = image_view(src[i], dflt[i]);
+    }
+    // from here on: launches on the handle's stream, nothing else.  The first clears the status word and rcount.
+    CCP_TRY(mg_refresh_begin(g, 1 + 3 * sets));
+    const long n = geo.ch_stride;
+    hipLaunchKernelGGL(k_weighted_refresh, pixels(geo.W, geo.H, sets), dim3(kBlock), 0, g->stream, v[0], v[1], v[2], geo.W, geo.H, geo.pitch,
+                       g->wop.p, n, 4 * n, g->has_fixed ? g->wcons.p : nullptr, 3 * n, g->rcount.p);
+    CCP_HIP(hipGetLastError());
+    g->refreshed = g->counts_pending = true;
+    g->mg_nullspace.floating = -1;      // the census verdict the host remembers is the old values': a later prepare or solve asks again
+    return mg_refresh(g);
+} CCP_ABI_CATCH
+
+int ccp_grid_operator_status(ccp_grid *g, int32_t *status)
+try {
+    CCP_TRY(weighted_handle(g));
+    if (!status) return CCP_ERR_BAD_ARG;
+    if (!g->has_op) return CCP_ERR_STATE;
+    unsigned word = 0;
+    if (g->refreshed) CCP_HIP(hipMemcpyAsync(&word, g->op_status.p, sizeof(word), hipMemcpyDeviceToHost, g->stream));
+    CCP_HIP(hipStreamSynchronize(g->stream));
+    *status = (int32_t)word;
+    return CCP_OK;
 } CCP_ABI_CATCH
 
 int ccp_grid_operator_channels(ccp_grid *g, int32_t *n)

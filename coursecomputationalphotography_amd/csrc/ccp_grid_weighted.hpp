@@ -1,6 +1,7 @@
 // ccp_grid_weighted.hpp — the weighted grid handles (include/ccp_gs.h, CCP_GRID_WEIGHTED), hand-written for gfx950:
-// the stored operator's planes and arithmetic, and the operator kernels: the formation with its validation, the
-// right-hand side of every channel and the coarsening.
+// the stored operator's planes and arithmetic, and the operator kernels: the formation with its validation, its
+// enqueue-only twin that refreshes the values of an installed operator, the right-hand side of every channel and the
+// coarsening.
 //
 // Operator.  A weighted handle stores its level-0 operator in four planes of the grid's colour-split layout (w_at,
 // the layout of x and b and of the multigrid levels' mg_at): d, we, ws and lambda, pads zero.  we / ws are the weights
@@ -122,6 +123,69 @@ k_weighted_coef_fixed(ImageView wx, ImageView wy, ImageView lam, ImageView fixed
     if (n_edges) atomicAdd(&tally[2], n_edges);
     __syncthreads();
     if (threadIdx.x < 3 && tally[threadIdx.x]) atomicAdd(count + 1 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
+}
+
+// ccp_grid_refresh_weights_device: new values for the installed operators, the fixed set kept.  The planes of every set
+// are rewritten as k_weighted_coef_fixed forms them (which, where no pixel is fixed, are k_weighted_coef's: the same
+// sums in the same order), with one difference in where the fixed flags come from: the sign of the stored lambda plane
+// (< 0 on a fixed pixel) instead of a mask view.  cons: null when the handle has no fixed pixel (no plane is negative
+// then, and the three extra planes do not exist).
+// The lambda plane is rewritten in place while the neighbours' threads read it.  That is sound because the SIGN of an
+// entry never changes here: a fixed pixel's entry is stored as the -1 it holds, a free pixel's as a value that is >= 0 and
+// not NaN -- a lambda that fails the check is stored as +0.0, so a refused refresh poisons the operator's values but
+// never its fixed marks -- and an aligned 8-byte load returns the old or the new entry, never a mix of the two.
+// count[0]: the verdict of all sets, as k_weighted_coef's; count[2 + 3 k], count[3 + 3 k]: set k's free pixels with
+// d = 0 and edges with exactly one fixed end (count[1 + 3 k], the fixed pixels, is not touched: they do not change) --
+// per block in LDS, then one atomic per non-zero count.  grid = (ceil(W/kBlock), H, sets).
+static __global__ void __launch_bounds__(kBlock)
+k_weighted_refresh(ImageView wx, ImageView wy, ImageView lam, int W, int H, long pitch, double *op, long plane, long op_stride, double *cons,
+                   long cons_stride, unsigned long long *__restrict__ count)
+{
+    __shared__ unsigned tally[2];
+    if (threadIdx.x < 2) tally[threadIdx.x] = 0;
+    __syncthreads();
+    const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y, ch = blockIdx.z;
+    unsigned n_dead = 0, n_edges = 0;
+    if (x < W) {
+        const double l = lam(y, x, ch);
+        const double e = x + 1 < W ? wx(y, x, ch) : 0.0;
+        const double s = y + 1 < H ? wy(y, x, ch) : 0.0;
+        if (!(weight_ok(l) && weight_ok(e) && weight_ok(s))) atomicOr(count, 1ull);
+        double *o = op + (long)ch * op_stride;
+        const double *mark = o + 3 * plane;
+        const long at = w_at(pitch, x, y);
+        const bool fp = mark[at] < 0.0;
+        const bool fN = y >= 1 && mark[w_at(pitch, x, y - 1)] < 0.0, fW = x >= 1 && mark[w_at(pitch, x - 1, y)] < 0.0;
+        const bool fE = x + 1 < W && mark[w_at(pitch, x + 1, y)] < 0.0, fS = y + 1 < H && mark[w_at(pitch, x, y + 1)] < 0.0;
+        const double wN = y >= 1 ? wy(y - 1, x, ch) : 0.0, wW = x >= 1 ? wx(y, x - 1, ch) : 0.0;
+        double dd = l;
+        if (y >= 1) dd += wN;
+        if (x >= 1) dd += wW;
+        if (x + 1 < W) dd += e;
+        if (y + 1 < H) dd += s;
+        double lp = l;
+        if (fN) lp += wN;
+        if (fW) lp += wW;
+        if (fE) lp += e;
+        if (fS) lp += s;
+        const bool be = x + 1 < W && fp != fE, bs = y + 1 < H && fp != fS;   // edges with exactly one fixed end
+        o[at] = fp ? 0.0 : dd;
+        o[plane + at] = fp || fE ? 0.0 : e;
+        o[2 * plane + at] = fp || fS ? 0.0 : s;
+        o[3 * plane + at] = fp ? -1.0 : weight_ok(l) ? l : 0.0;
+        if (cons) {
+            double *k = cons + (long)ch * cons_stride;
+            k[at] = be ? e : 0.0;
+            k[plane + at] = bs ? s : 0.0;
+            k[2 * plane + at] = fp ? 0.0 : lp;
+        }
+        n_dead = !fp && dd == 0.0;
+        n_edges = (unsigned)be + (unsigned)bs;
+    }
+    if (n_dead) atomicAdd(&tally[0], n_dead);
+    if (n_edges) atomicAdd(&tally[1], n_edges);
+    __syncthreads();
+    if (threadIdx.x < 2 && tally[threadIdx.x]) atomicAdd(count + 2 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
 }
 
 // b of `cpb` channels per block from one set of the stored operator: block z takes channels [z cpb, (z + 1) cpb) and the

@@ -1,6 +1,7 @@
 // ccp_grid_weighted_api.hpp — what ccp_grid_mg.hip needs of the weighted handle's coarsening kernel
 // (ccp_grid_weighted.hpp) and of the per-channel batched mode's kernels (ccp_grid_pco.hpp), all compiled in
-// ccp_grid_weighted.hip alone: the launchers.  No kernels here, so that including it adds nothing to a
+// ccp_grid_weighted.hip alone: the launchers; and, the other way, what ccp_grid_weighted.hip's refresh entry point needs of
+// the hierarchy.  No kernels here, so that including it adds nothing to a
 // translation unit's device code.
 #pragma once
 
@@ -29,5 +30,11 @@ int pco_tail(hipStream_t s, int C, const MgTailT<double> *tails, const double *b
              const CgState *st);
 int pco_apply(hipStream_t s, bool dot, dim3 grid, int C, const MgLevel &lv, long os, const double *in, double *out, long vs, double *partial,
               long ps, const CgState *st);
+
+// ---- the other way (ccp_grid_mg.hip): the hierarchy's half of ccp_grid_refresh_weights_device --------------------------
+// CCP_ERR_STATE with nothing enqueued unless ccp_grid_mg_prepare's work stands; else one launch: the status word, n_counts
+// words of the refresh pass's counts and the mode's verdict words zeroed
+int mg_refresh_begin(ccp_grid *g, int n_counts);
+int mg_refresh(ccp_grid *g);         // the coarse levels, float copies, census and status word from the new level 0: launches only
 
 }  // namespace ccp

@@ -547,7 +547,8 @@ class WeightedSolver:
     validation, the multigrid hierarchy, the PCG vectors (capi.Grid.mg_prepare) -- and solve / solve_grad then only
     enqueue on torch's current stream (capi.Grid.mg_conjugate_gradient_enqueue): no host synchronisation and no
     allocation on the handle, so a solve may be recorded by torch.cuda.graph together with whatever produces its inputs
-    and consumes its result.
+    and consumes its result.  refresh_operator gives the installed operator new values the same way, enqueue only, so
+    weights that a network or a reweighting step produces every step can sit in the same graph.
 
     H, W, C: the canvas and its channels; device: a torch device or a GPU index.  iterations: every solve enqueues
     exactly this many PCG iterations (<= 4096); a channel that reaches sqrt(r'r) < epsilon earlier stops there and the
@@ -574,6 +575,7 @@ class WeightedSolver:
         self.iterations, self.epsilon = int(iterations), float(epsilon)
         self.nullspace = capi.mg_nullspace_value(nullspace)
         self._operator = None
+        self._generation = 0                               # refreshes of the handle's operator so far (solve_grad's backward)
         self._zero = torch.zeros((), dtype=torch.float64, device=self.device).expand(self.H, self.W, self.C)
         self.grid = capi.Grid(self.W, self.H, self.C, device=dev, weighted=True)
         try:
@@ -610,15 +612,58 @@ class WeightedSolver:
         Returns (out, report).  Enqueue only."""
         return self._enqueue_solve(gx, gy, f, values, x0, out, report), report
 
-    def solve_grad(self, gx, gy, f, values=None, x0=None, report=None, adjoint_report=None):
-        """solve as a differentiable function of gx, gy, f and values (weighted_solve_grad's formulas; no gradients for the
-        weights: weighted_solve_grad is for those).  Returns (u, report), u a new float64 H x W x C tensor with a grad_fn.
-        Backward is the adjoint right-hand side, one more enqueue solve and the gradient pass on this same handle; it
-        needs only the saved u and inputs, so several forwards may precede their backwards.  No `strict` check: the
-        adjoint solve's figures land in `adjoint_report` if given."""
+    def refresh_operator(self, wx, wy, data_weight=None):
+        """New values for the installed operator (wx, wy, data_weight as set_operator's; None: 1, 1, 0), enqueued on torch's
+        current stream (capi.Grid.refresh_weights_tensor): no synchronisation and no allocation on the handle, so it may
+        be recorded by torch.cuda.graph in front of a solve.  The fixed pixels, the kind of the operator (an H x W x C weight
+        needs an operator installed per channel; H x W weights serve either kind) and every mode stay: set_operator remains
+        the synchronising call and the only one that changes those.  (A python scalar becomes a new device tensor here: inside
+        a capture pass tensors.)  Bad weights are not raised here -- that would be a
+        read-back: the solves then leave x alone and field 5 of their report carries the status
+        (capi.Grid.operator_status reads it, synchronising)."""
+        if self._operator is None:
+            raise RuntimeError("WeightedSolver: set_operator first")
+        dev = self.device.index
+        wx, wy, lam = (_weight(w, self.H, self.W, dev) for w in (wx, wy, data_weight))
+        self.grid.refresh_weights_tensor(wx, wy, lam)
+        self._operator = (wx, wy, lam, self._operator[3])
+        self._generation += 1
+
+    def solve_grad(self, gx, gy, f, values=None, x0=None, report=None, adjoint_report=None, *, wx=None, wy=None, data_weight=None):
+        """solve as a differentiable function of gx, gy, f and values (weighted_solve_grad's formulas).  Returns (u, report),
+        u a new float64 H x W x C tensor with a grad_fn.  Backward is the adjoint right-hand side, one more enqueue solve and
+        the gradient pass on this same handle; it needs only the saved u and inputs, so several forwards may precede their
+        backwards.  No `strict` check: the adjoint solve's figures land in `adjoint_report` if given.
+
+        wx, wy, data_weight (keyword only): when any is given, forward first refreshes the operator with them
+        (refresh_operator; the ones not given keep the installed operator's values) and backward also returns their
+        gradients, by weighted_solve_grad's formulas and rules: each in its input's dtype and shape, python scalars get
+        none, a 0-dim tensor is expanded to H x W outside the autograd function so that torch sums its gradient, and on an
+        operator per channel an H x W weight is expanded to H x W x C the same way.  If the handle's operator has been
+        refreshed again since this forward, backward first refreshes it with the weights it saved, so forwards on
+        different weights may precede their backwards.  Without the three the function is what it was, bit for bit (no
+        gradients for the installed weights: weighted_solve_grad or these keywords are for those)."""
         if self.nullspace != capi.MG_NULLSPACES["none"]:
             _no_nullspace("constant", "WeightedSolver.solve_grad")
-        return _persistent_function().apply(gx, gy, f, values, x0, self, report, adjoint_report), report
+        weights = (None, None, None)
+        if wx is not None or wy is not None or data_weight is not None:
+            import torch
+            if self._operator is None:
+                raise RuntimeError("WeightedSolver: set_operator first")
+            stacked = self.grid.operator_channels() > 1 or _per_channel(wx, wy, data_weight)
+
+            def plane(w, installed):
+                if w is None:                              # (no gradient for a weight the caller did not hand in)
+                    return installed.detach() if isinstance(installed, torch.Tensor) else installed
+                if isinstance(w, torch.Tensor) and w.dim() == 0:
+                    w = w.expand(self.H, self.W)
+                w = _weight(w, self.H, self.W, self.device.index)
+                if stacked and w.dim() == 2:
+                    w = w.unsqueeze(-1).expand(self.H, self.W, self.C)
+                return w
+
+            weights = tuple(plane(w, old) for w, old in zip((wx, wy, data_weight), self._operator[:3]))
+        return _persistent_function().apply(gx, gy, f, values, x0, *weights, self, report, adjoint_report, weights != (None, None, None)), report
 
     def close(self):
         self.grid.close()
@@ -642,15 +687,21 @@ def _persistent_function():
     import torch
     from torch.autograd.function import once_differentiable
 
-    names = ("gx", "gy", "f", "values")
+    names = ("gx", "gy", "f", "values", "wx", "wy", "lam")
 
     class PersistentSolve(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, gx, gy, f, values, x0, solver, report, adjoint_report):
+        def forward(ctx, gx, gy, f, values, x0, wx, wy, lam, solver, report, adjoint_report, refresh):
+            if refresh:                                    # (a weight the caller did not give arrives as the installed one)
+                solver.refresh_operator(wx, wy, lam)
             u = solver._enqueue_solve(gx, gy, f, values, x0, None, report)
             ctx.solver, ctx.adjoint_report = solver, adjoint_report
-            ctx.present = [t is not None for t in (gx, gy, f, values)]
-            ctx.save_for_backward(*[t for t in (gx, gy, f, values) if t is not None], u)
+            ctx.generation = solver._generation
+            # the operator this solve ran on: what backward hands the gradient pass, and refreshes the handle with if
+            # another refresh has happened in between
+            wx, wy, lam, ctx.fixed = solver._operator
+            ctx.present = [t is not None for t in (gx, gy, f, values, wx, wy, lam)]
+            ctx.save_for_backward(*[t for t in (gx, gy, f, values, wx, wy, lam) if t is not None], u)
             return u
 
         @staticmethod
@@ -662,8 +713,12 @@ def _persistent_function():
             inputs = {n: next(it) if p else None for n, p in zip(names, ctx.present)}
             solver = ctx.solver
             g = solver.grid
-            wx, wy, lam, fixed = solver._operator
-            want = tuple(n for n, need in zip(names, ctx.needs_input_grad[:4]) if need)
+            wx, wy, lam, fixed = inputs["wx"], inputs["wy"], inputs["lam"], ctx.fixed
+            if solver._generation != ctx.generation:       # the handle holds a later refresh's values: back to this solve's
+                solver.refresh_operator(wx, wy, lam)
+                ctx.generation = solver._generation
+            need = list(ctx.needs_input_grad[:4]) + list(ctx.needs_input_grad[5:8])
+            want = tuple(n for n, yes in zip(names, need) if yes)
             grad = grad.reshape(u.shape)
             if grad.dtype not in (torch.float32, torch.float64):
                 grad = grad.to(torch.float64)
@@ -672,7 +727,7 @@ def _persistent_function():
             out = {n: torch.empty(inputs[n].shape, dtype=inputs[n].dtype, device=inputs[n].device) for n in want}
             got = g.weighted_adjoint_tensor(u, grad if "values" in want else None, inputs["gx"], inputs["gy"], inputs["f"], wx, wy, lam,
                                             fixed, want=want, out=out)
-            return tuple(got.get(n) for n in names) + (None, None, None, None)
+            return tuple(got.get(n) for n in names[:4]) + (None,) + tuple(got.get(n) for n in names[4:]) + (None, None, None, None)
 
     _PersistentSolve = PersistentSolve
     return PersistentSolve

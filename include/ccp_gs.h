@@ -1045,10 +1045,52 @@ int ccp_grid_mg_prepare(ccp_grid *g, int32_t smoothing_sweeps);
  *   There is no `strict` flag and no error for a solve that did not converge: read `converged` when the stream has passed.
  * Out of scope, each a possible follow-up: the _rowblocked calls; ccp_grid_mg_apply; a stop test relative to |b| computed
  * on the device (one more reduction per solve: epsilon is absolute, as in the synchronous call); refreshing an installed
- * operator without the setters' validation read-back.  Additive: the ABI version does not change. */
+ * operator without the setters' validation read-back.  Additive: the ABI version does not change.
+ * (That last follow-up is ccp_grid_refresh_weights_device below: with it the operator's VALUES may change between the
+ * replays too, and report field [5] is +0.0 or the operator status it leaves.) */
 #define CCP_MG_ENQUEUE_MAX_ITERATION 4096
 int ccp_grid_mg_conjugate_gradient_enqueue(ccp_grid *g, double epsilon, int32_t max_iteration, int32_t smoothing_sweeps,
                                            const ccp_device_array *report);
+
+/* ---- Refreshing a weighted operator by enqueue only -------------------------------------------------------------------------
+ * Edge weights, lambda or a confidence map that come out of a network or a reweighting step change at every training step
+ * or frame, on a canvas that does not.  ccp_grid_refresh_weights_device replaces the VALUES of the installed operator and of
+ * everything derived from them -- the coarse levels of the hierarchy, the float copies of CCP_MG_PRECISION_F32, the census
+ * of CCP_MG_NULLSPACE_CONSTANT -- on the handle's stream: no allocation, no host synchronisation and no copy to or from host
+ * memory, so it may be issued while the stream is being captured, before the assembly and the enqueue solve.
+ *   What it keeps: the kind of the operator (shared: the views are H x W; one per channel: H x W x channels; stride_c 0
+ *   broadcasts, NULL takes the setters' defaults 1, 1, 0), the set of fixed pixels, whether the three constraint planes
+ *   exist, the hierarchy kind and every mode.  The handle stays prepared.  Afterwards it holds, bit for bit, the planes,
+ *   coarse levels, float copies and census verdict that the matching setter (ccp_grid_set_weights_constrained_device or
+ *   ccp_grid_set_weights_per_channel_device with the same fixed mask, the new weights and the same options) followed by
+ *   ccp_grid_mg_prepare forms on a fresh handle.  Only ccp_grid_set_weights_* changes the fixed set or the kind.
+ *   Precondition: a single-block weighted handle with an operator installed, and a successful ccp_grid_mg_prepare (any
+ *   smoothing_sweeps) since the last call that drops what prepare built (the list above).  Otherwise CCP_ERR_STATE with
+ *   nothing enqueued.  The views are checked as the setters check them: CCP_ERR_BAD_ARG before anything is enqueued.  A
+ *   NULL handle: CCP_ERR_BAD_ARG; a handle that is not weighted: CCP_ERR_UNSUPPORTED, as from the setters.
+ *   The verdict stays on the device.  The setters and prepare read theirs back and refuse; the refresh returns CCP_OK and
+ *   leaves the operator status in a device word of the handle, the sum of
+ *     CCP_OPERATOR_BAD_WEIGHT (1)    a weight or lambda is not finite or is < 0,
+ *     CCP_OPERATOR_F32_RANGE (2)     CCP_MG_PRECISION_F32: a coefficient narrows to inf or a non-zero one to 0,
+ *     CCP_OPERATOR_NOT_FLOATING (4)  CCP_MG_NULLSPACE_CONSTANT: the census fails,
+ *   or 0.  While the word is non-zero ccp_grid_mg_conjugate_gradient_enqueue starts every channel stopped: x and b stay
+ *   untouched bit for bit in every mode, and the report reads iterations 0, converged 0 and [5] = the status ([5] is +0.0
+ *   after a good refresh and on a handle that was never refreshed).  After a refused refresh the operator is poisoned, not
+ *   dropped: its values are unusable, its fixed set and the handle's preparation are intact, and the next refresh with good
+ *   weights restores it fully.
+ * ccp_grid_operator_status synchronises and returns the word (0 while the last change of the operator was a setter's;
+ * CCP_ERR_STATE without an operator).  While the last change was a refresh, ccp_grid_mg_conjugate_gradient,
+ * ccp_grid_mg_apply and ccp_grid_mg_prepare read the word first -- they synchronise anyway -- and return CCP_ERR_STATE with
+ * x and b untouched when it is non-zero.  ccp_grid_constraint_info[_channel] reports the refreshed operator's counts: the
+ * fixed pixels are unchanged, the free live pixels and boundary edges are recounted on the device by the refresh and read
+ * back on demand.  Out of scope: changing the fixed set or the kind, the row-block calls.  Additive: the ABI version does
+ * not change. */
+#define CCP_OPERATOR_BAD_WEIGHT   1
+#define CCP_OPERATOR_F32_RANGE    2
+#define CCP_OPERATOR_NOT_FLOATING 4
+int ccp_grid_refresh_weights_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy,
+                                    const ccp_device_array *lambda);
+int ccp_grid_operator_status(ccp_grid *g, int32_t *status);
 
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
