@@ -873,6 +873,7 @@ try {
         if (st == CCP_OK) st = g->wcount.alloc(1 + 3 * kMaxChannels);
         if (st == CCP_OK) st = g->rcount.alloc(1 + 3 * kMaxChannels);
         if (st == CCP_OK) st = g->op_status.alloc(1);
+        if (st == CCP_OK && hipMemset(g->op_status.p, 0, sizeof(unsigned)) != hipSuccess) st = CCP_ERR_HIP;   // no refresh yet: good
     }
     // partial sums: the finest launch is one block per (x tile, row, channel*2) with 2 doubles
     const size_t part = (size_t)((geo.pitch + 2L * kBlock - 1) / (2L * kBlock)) * geo.local_rows * d->channels * 2 * 2 + 64;

@@ -154,12 +154,13 @@ struct ccp_grid {
     int op_sets = 1;
     long pc_fixed[kMaxChannels] = {}, pc_live[kMaxChannels] = {}, pc_edges[kMaxChannels] = {};
     // ccp_grid_refresh_weights_device (made with the handle: the refresh allocates nothing).  rcount: the refresh pass's
-    // verdict and counts in wcount's layout, which stay on the device until ccp_grid_constraint_info asks (counts_pending);
-    // op_status: the CCP_OPERATOR_* word of the last refresh, meaningful while `refreshed` (the last change of the operator
-    // was a refresh; a setter clears it).
+    // verdict and counts in wcount's layout, which stay on the device and are read whenever ccp_grid_constraint_info asks
+    // while `refreshed` (the last change of the operator was a refresh; a setter clears it); op_status: the CCP_OPERATOR_*
+    // word of the last refresh, 0 from the handle's creation and again after a setter, so that the enqueue solve can read it
+    // on every handle: neither may depend on what the host knew when a graph was recorded, a replayed refresh moves both.
     DevBuf<unsigned long long> rcount;
     DevBuf<unsigned> op_status;
-    bool refreshed = false, counts_pending = false;
+    bool refreshed = false;
     MgConfig mg_cfg;                           // ccp_grid_mg_set_* (ccp_grid_mg_view.hpp)
     MgNullspace mg_nullspace;                  // goes with the operator (drop_operator)
 };

@@ -917,7 +917,7 @@ struct NullspaceSteps : ChannelSteps {
     double pixels;                   // W H
     MgnState *ns;
     double *npart;                   // 3 x `blocks` partial sums
-    const unsigned *hold = nullptr;  // the enqueue solve on a refreshed operator: its status word (k_mgn_means)
+    const unsigned *hold = nullptr;  // the enqueue solve: the operator's status word (k_mgn_means)
     void means(const double *a, const double *b2, int which) const
     {
         hipLaunchKernelGGL(k_mgn_sums, dim3(blocks), dim3(kBlock), 0, s, a, b2, lay, npart);
@@ -1411,7 +1411,7 @@ int pcg_solve(const GridMgView &v, MgHierarchy &h, double epsilon, int max_itera
         NullspaceSteps S{};
         S.lay = nullspace_layout(v), S.pixels = (double)v.geom.W * (double)v.geom.H;
         S.npart = h.nspart.p;
-        S.hold = enqueue && v.refreshed ? v.op_status : nullptr;
+        S.hold = enqueue ? v.op_status : nullptr;
         CCP_TRY(channels(S, [&](int ch) {
             S.ns = h.nsstate.p + ch;
             v.ns->solved[ch] = false;
@@ -1707,7 +1707,9 @@ try {
     if (report) CCP_TRY(check_view_on(v.device, report, 1u << CCP_DTYPE_F64, true, 1, v.channels, kMgeReportFields, 1));
     MgHierarchy *h = *v.cache;
     if (!prepared_for(v, h, nu)) return CCP_ERR_STATE;
-    const unsigned *status = v.refreshed ? v.op_status : nullptr;   // (a setter's operator was validated on the host)
+    // The word and not what the host knows of it (v.refreshed): a recorded solve must see a refresh that follows the
+    // recording, an eager one too.  0 while a setter's operator, validated on the host, is installed; null: not weighted.
+    const unsigned *status = v.op_status;
     hipLaunchKernelGGL(k_mge_init, dim3(1), dim3(kBlock), 0, v.stream, h->estate.p, v.channels, status);
     CCP_TRY(pcg_solve(v, *h, epsilon, max_iteration, nu, nullptr, true));
     if (report) {

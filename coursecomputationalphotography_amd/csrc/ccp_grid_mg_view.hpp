@@ -54,9 +54,9 @@ struct GridMgView {
     long op_stride, lam_stride;
     MgConfig cfg;                    // the handle's options, by value
     MgNullspace *ns;                 // the census verdict and the last CONSTANT-mode solves' means
-    // ccp_grid_refresh_weights_device: was the last change of the operator a refresh; if so, *op_status (device) is its
-    // CCP_OPERATOR_* word, which the fold kernel forms from op_verdict[0] (device: the refresh pass's weight verdict), the
-    // narrowing's flag and the census counts
+    // ccp_grid_refresh_weights_device: was the last change of the operator a refresh; *op_status (device; null unless the
+    // handle is weighted) is its CCP_OPERATOR_* word, 0 while the last change was a setter's, which the fold kernel forms
+    // from op_verdict[0] (device: the refresh pass's weight verdict), the narrowing's flag and the census counts
     bool refreshed;
     unsigned *op_status;
     unsigned long long *op_verdict;

@@ -21,8 +21,9 @@ namespace ccp {
 constexpr int kMgeReportFields = 6;   // iterations, converged, last_l1_step, b_mean, x_mean, reserved
 
 // st[c] := a state about to start (active, every count and scalar 0: what pcg_loop uploads), c < C.  status: the
-// operator status word of ccp_grid_refresh_weights_device, or null on a handle whose operator a setter installed; while
-// it is non-zero every channel starts stopped (active 0), so every later launch of the solve is a no-op.
+// operator status word of ccp_grid_refresh_weights_device (0 while a setter's operator is installed), or null on a handle
+// that is not weighted; while it is non-zero every channel starts stopped (active 0), so every later launch of the solve
+// is a no-op.
 static __global__ void __launch_bounds__(kBlock)
 k_mge_init(CgState *__restrict__ st, int C, const unsigned *__restrict__ status)
 {

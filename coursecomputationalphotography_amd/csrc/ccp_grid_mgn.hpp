@@ -106,7 +106,7 @@ k_mgn_sums(const double *__restrict__ a, const double *__restrict__ b, MgnLay l,
 
 // one block, after k_mgn_sums left `count` partials of each sum; n = W H as a double.  kMgnStart: b_mean = sum0 / n,
 // m0 = sum1 / n.  kMgnClose: shift = m0 - sum0 / n.  kMgnReport: x_mean = sum0 / n.
-// hold (the enqueue solve on a refreshed operator: its status word; null otherwise): while it is non-zero the solve never
+// hold (the enqueue solve: the operator's status word; null otherwise): while it is non-zero the solve never
 // started and must leave x alone bit for bit, so kMgnClose stores -0.0, the one shift k_mgn_shift's x + shift returns
 // every x unchanged for (+0.0 would turn a -0.0 of x into +0.0).
 static __global__ void __launch_bounds__(kBlock)

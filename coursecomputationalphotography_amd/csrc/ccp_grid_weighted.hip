@@ -181,11 +181,12 @@ void drop_operator(ccp_grid *g)
     mg_release(&g->mg);
     g->has_op = g->has_fixed = false;
     g->per_channel = false;
-    g->refreshed = g->counts_pending = false;
+    g->refreshed = false;
     g->mg_nullspace.forget();
 }
 
-// ccp_grid_constraint_info after a refresh: the counts the refresh pass left on the device, read once (one wait)
+// ccp_grid_constraint_info after a refresh: the counts the refresh pass left on the device (one wait).  Read at every call
+// and not once per refresh: a refresh that a captured graph replays changes them without the host taking part.
 int refreshed_counts(ccp_grid *g)
 {
     const int sets = g->per_channel ? g->desc.channels : 1;
@@ -196,7 +197,6 @@ int refreshed_counts(ccp_grid *g)
         g->pc_live[c] = (long)g->geom.W * g->geom.H - g->pc_fixed[c] - (long)count[2 + 3 * c];
         g->pc_edges[c] = (long)count[3 + 3 * c];
     }
-    g->counts_pending = false;
     return CCP_OK;
 }
 
@@ -222,6 +222,9 @@ int form_operator(ccp_grid *g, bool per_channel, const ImageView &wx, const Imag
     const Geom &geo = g->geom;
     const long n = geo.ch_stride;
     const int sets = per_channel ? g->desc.channels : 1;
+    // a setter's operator is validated on the host: the status word of an earlier refresh goes, since the enqueue solve
+    // reads the word whoever installed the operator (a handle that was never refreshed launches what it launched)
+    if (g->refreshed) CCP_HIP(hipMemsetAsync(g->op_status.p, 0, sizeof(unsigned), g->stream));
     drop_operator(g);
     g->wcons.release();
     CCP_TRY(operator_planes(g, sets));
@@ -392,7 +395,7 @@ try {
     if (channel < 0 || channel >= g->desc.channels) return CCP_ERR_BAD_ARG;
     if (!g->has_op) return CCP_ERR_STATE;
     const int k = g->per_channel ? channel : 0;                            // the shared operator is every channel's
-    if (g->counts_pending) CCP_TRY(refreshed_counts(g));
+    if (g->refreshed) CCP_TRY(refreshed_counts(g));
     // an operator formed without a mask: its dead pixels counted once
     if (g->pc_live[k] < 0) CCP_TRY(count_live(g, g->wop.p + 4 * (long)k * g->geom.ch_stride, &g->pc_live[k]));
     if (fixed_pixels) *fixed_pixels = g->pc_fixed[k];
@@ -426,7 +429,7 @@ try {
     hipLaunchKernelGGL(k_weighted_refresh, pixels(geo.W, geo.H, sets), dim3(kBlock), 0, g->stream, v[0], v[1], v[2], geo.W, geo.H, geo.pitch,
                        g->wop.p, n, 4 * n, g->has_fixed ? g->wcons.p : nullptr, 3 * n, g->rcount.p);
     CCP_HIP(hipGetLastError());
-    g->refreshed = g->counts_pending = true;
+    g->refreshed = true;
     g->mg_nullspace.floating = -1;      // the census verdict the host remembers is the old values': a later prepare or solve asks again
     return mg_refresh(g);
 } CCP_ABI_CATCH

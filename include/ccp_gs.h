@@ -1077,14 +1077,16 @@ int ccp_grid_mg_conjugate_gradient_enqueue(ccp_grid *g, double epsilon, int32_t 
  *   untouched bit for bit in every mode, and the report reads iterations 0, converged 0 and [5] = the status ([5] is +0.0
  *   after a good refresh and on a handle that was never refreshed).  After a refused refresh the operator is poisoned, not
  *   dropped: its values are unusable, its fixed set and the handle's preparation are intact, and the next refresh with good
- *   weights restores it fully.
+ *   weights restores it fully.  The solve's kernels read the word when they run, on every weighted handle: a solve recorded
+ *   in a graph obeys the refreshes that run before each replay, recorded with it or issued eagerly after the recording, the
+ *   first refresh of the handle included.
  * ccp_grid_operator_status synchronises and returns the word (0 while the last change of the operator was a setter's;
  * CCP_ERR_STATE without an operator).  While the last change was a refresh, ccp_grid_mg_conjugate_gradient,
  * ccp_grid_mg_apply and ccp_grid_mg_prepare read the word first -- they synchronise anyway -- and return CCP_ERR_STATE with
  * x and b untouched when it is non-zero.  ccp_grid_constraint_info[_channel] reports the refreshed operator's counts: the
  * fixed pixels are unchanged, the free live pixels and boundary edges are recounted on the device by the refresh and read
- * back on demand.  Out of scope: changing the fixed set or the kind, the row-block calls.  Additive: the ABI version does
- * not change. */
+ * back on demand: at every call (one wait), so that they are those of the last refresh that ran, a replayed one too.
+ * Out of scope: changing the fixed set or the kind, the row-block calls.  Additive: the ABI version does not change. */
 #define CCP_OPERATOR_BAD_WEIGHT   1
 #define CCP_OPERATOR_F32_RANGE    2
 #define CCP_OPERATOR_NOT_FLOATING 4

@@ -17,13 +17,12 @@ import torch
 
 import mixed_helpers as mh
 from coursecomputationalphotography_amd import capi, tensor_ops
+from replay_helpers import SENTINEL, fixed_mask, handle, images, weights
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
 BAD_ARG, STATE, UNSUPPORTED = 1, 5, 6
-SENTINEL = -7.25
-PER_CHANNEL = ("per_channel", "per_channel_batched")
 
 
 def bits(a):
@@ -34,54 +33,12 @@ def tbits(t):
     return t.detach().contiguous().view(torch.int64)
 
 
-def weights(kind, W, H, Cn, seed, dtype=np.float32):
-    """wx, wy in [0.5, 2] and lambda = 1e-2 (0 for the floating system) as device tensors: H x W, or H x W x C for a kind
-    with one operator per channel"""
-    g = mh.rng(seed)
-    shape = (H, W, Cn) if kind in PER_CHANNEL else (H, W)
-    wx, wy = (g.uniform(0.5, 2.0, shape).astype(dtype) for _ in range(2))
-    lam = np.full(shape, 0.0 if kind == "floating" else 1e-2, dtype=dtype)
-    return [torch.from_numpy(a).to(DEV) for a in (wx, wy, lam)]
-
-
 def island(w, y0, y1, x0, x1):
     """pixels [y0, y1) x [x0, x1) lose every edge and their lambda: dead (x0, y0 >= 1)"""
     wx, wy, lam = w
     wx[y0:y1, x0 - 1:x1] = 0
     wy[y0 - 1:y1, x0:x1] = 0
     lam[y0:y1, x0:x1] = 0
-
-
-def fixed_mask(kind, W, H):
-    return torch.from_numpy(mh.ellipse_fixed(W, H)).to(DEV) if kind == "fixed" else None
-
-
-def handle(kind, W, H, Cn, w, sweeps=0, prepare=True):
-    """a fresh weighted handle in the modes of `kind` holding the operator w (the matching setter), prepared"""
-    g = capi.Grid(W, H, Cn, weighted=True)
-    g.mg_set_hierarchy("galerkin" if kind == "galerkin" else "rescaled")
-    if kind == "floating":
-        g.mg_set_nullspace("constant")
-    if kind == "f32":
-        g.mg_set_precision("f32")
-    if kind in ("batched", "per_channel_batched"):
-        g.mg_set_channels("batched")
-    if kind == "line":
-        g.mg_set_smoother("line")
-    if kind in PER_CHANNEL:
-        g.set_weights_per_channel_tensor(*w)
-    else:
-        g.set_weights_tensor(*w, fixed=fixed_mask(kind, W, H))
-    if prepare:
-        g.mg_prepare(sweeps)
-    return g
-
-
-def images(W, H, Cn, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    gx, gy = (torch.randn(H, W, Cn, generator=g, dtype=torch.float32).to(DEV) for _ in range(2))
-    f, values = ((255.0 * torch.rand(H, W, Cn, generator=g, dtype=torch.float64)).to(DEV) for _ in range(2))
-    return gx, gy, f, values
 
 
 def assemble(g, kind, img, seed):
