@@ -93,7 +93,7 @@ ABI_SYMBOLS = (
     "ccp_grid_adjoint_begin_device", "ccp_grid_weighted_adjoint_device",
     "ccp_grid_set_weights_per_channel_device", "ccp_grid_operator_channels", "ccp_grid_mg_level_channel",
     "ccp_grid_constraint_info_channel",
-    "ccp_grid_mg_prepare", "ccp_grid_mg_conjugate_gradient_enqueue",
+    "ccp_grid_mg_prepare", "ccp_grid_mg_conjugate_gradient_enqueue", "ccp_grid_mg_conjugate_gradient_enqueue_relative",
     "ccp_grid_refresh_weights_device", "ccp_grid_operator_status",
     "ccp_grid_set_mask_device", "ccp_mask_erode_cross_device", "ccp_panorama_begin_device", "ccp_panorama_add_device",
     "ccp_panorama_finish_device",
@@ -254,6 +254,7 @@ def load() -> C.CDLL:
     L.ccp_grid_mg_apply.argtypes = [vp, i32]
     L.ccp_grid_mg_prepare.argtypes = [vp, i32]
     L.ccp_grid_mg_conjugate_gradient_enqueue.argtypes = [vp, dbl, i32, i32, C.POINTER(DeviceArray)]
+    L.ccp_grid_mg_conjugate_gradient_enqueue_relative.argtypes = [vp, dbl, dbl, i32, i32, C.POINTER(DeviceArray)]
     L.ccp_grid_mg_level.argtypes = [vp, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
     for option in MG_OPTIONS:
         getattr(L, f"ccp_grid_mg_set_{option}").argtypes = [vp, i32]
@@ -777,19 +778,37 @@ class Grid:
         report: a CUDA float64 tensor of channels x 6 (any non-overlapping strides), or None; a kernel fills row ch with
         iterations, converged (0.0 / 1.0), last_l1_step, b_mean, x_mean ("constant" null-space mode; 0.0 otherwise) and
         0.0 when the stream gets there.  Returns `report`."""
-        arr = None
-        if report is not None:
-            torch = self._torch()
-            if not isinstance(report, torch.Tensor) or report.device.type != "cuda" or report.device.index != self.desc.device:
-                raise ValueError(f"report must be a tensor on cuda:{self.desc.device}")
-            if report.dtype != torch.float64 or tuple(report.shape) != (self.C, 6):
-                raise ValueError(f"report must be a float64 tensor of {self.C} x 6, not {report.dtype} {tuple(report.shape)}")
-            if any(s < 0 for s in report.stride()) or not _no_overlap(report.shape, report.stride()):
-                raise ValueError("report is an output whose elements overlap or has a negative stride")
-            arr = DeviceArray(report.data_ptr(), DTYPE_F64, 0, 0, report.stride(0), report.stride(1), 0)
+        arr = self._enqueue_report(report, 6)
         ref = None if arr is None else C.byref(arr)
         self._on_stream(lambda: self.L.ccp_grid_mg_conjugate_gradient_enqueue(self.h, epsilon, max_iteration, sweeps, ref),
                         "ccp_grid_mg_conjugate_gradient_enqueue")
+        return report
+
+    def _enqueue_report(self, report, fields):
+        """The view of an enqueue solve's report (a CUDA float64 tensor of channels x `fields`), or None for None."""
+        if report is None:
+            return None
+        torch = self._torch()
+        if not isinstance(report, torch.Tensor) or report.device.type != "cuda" or report.device.index != self.desc.device:
+            raise ValueError(f"report must be a tensor on cuda:{self.desc.device}")
+        if report.dtype != torch.float64 or tuple(report.shape) != (self.C, fields):
+            raise ValueError(f"report must be a float64 tensor of {self.C} x {fields}, not {report.dtype} {tuple(report.shape)}")
+        if any(s < 0 for s in report.stride()) or not _no_overlap(report.shape, report.stride()):
+            raise ValueError("report is an output whose elements overlap or has a negative stride")
+        return DeviceArray(report.data_ptr(), DTYPE_F64, 0, 0, report.stride(0), report.stride(1), 0)
+
+    def mg_conjugate_gradient_enqueue_relative(self, epsilon_abs, epsilon_rel, max_iteration, sweeps=0, report=None):
+        """mg_conjugate_gradient_enqueue with a stop test relative to |b| that the device forms: channel c stops when
+        sqrt(r'r) < max(epsilon_abs, epsilon_rel * |b_c|) or the residual is exactly 0, |b_c| summed inside the init pass that
+        reads b anyway (in "constant" null-space mode: |b_c - mean(b_c)|).  The threshold lives in device memory, so a
+        recorded solve follows each replay's right-hand side.  epsilon_rel = 0 is mg_conjugate_gradient_enqueue at
+        epsilon_abs, bit for bit.  Negative, NaN or infinite tolerances: CcpError BAD_ARG.  Needs mg_prepare(sweeps).
+        report: a CUDA float64 tensor of channels x 8, or None: the six fields of mg_conjugate_gradient_enqueue's report,
+        then |b_c| and the threshold channel c stopped against.  Returns `report`."""
+        arr = self._enqueue_report(report, 8)
+        ref = None if arr is None else C.byref(arr)
+        self._on_stream(lambda: self.L.ccp_grid_mg_conjugate_gradient_enqueue_relative(self.h, epsilon_abs, epsilon_rel, max_iteration, sweeps, ref),
+                        "ccp_grid_mg_conjugate_gradient_enqueue_relative")
         return report
 
     def mg_apply(self, smoothing_sweeps=2):

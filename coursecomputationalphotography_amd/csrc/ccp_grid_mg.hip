@@ -6,12 +6,14 @@
 #include "ccp_grid_mgl.hpp"
 #include "ccp_grid_mgn.hpp"
 #include "ccp_grid_mge.hpp"
+#include "ccp_grid_mgr.hpp"
 #include "ccp_view_check.hpp"
 #include "ccp_grid_weighted_api.hpp"
 #include "ccp_comm.hpp"
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <memory>
 #include <type_traits>
 #include <vector>
@@ -111,6 +113,9 @@ struct MgHierarchy {
     // builds is what the synchronous solve builds at its first call; a setter that frees part of it clears `prepared`
     // (kOptions).
     DevBuf<CgState> estate;
+    // ccp_grid_mg_conjugate_gradient_enqueue_relative (ccp_grid_mgr.hpp), made by every prepare: kMaxChannels thresholds,
+    // kMaxChannels norms of b, then the partial sums of b'b (the solve's own count: one channel's, or C of them in batched mode)
+    DevBuf<double> erel;
     bool prepared = false;
     MgConfig prep_cfg;
     int prep_nu = 0, prep_channels = 0;
@@ -855,6 +860,12 @@ struct PcgArgs {
     const double *b;
     double *x, *r, *z, *p, *ap, *part;
     CgState *st;
+    // The stop test relative to |b| (ccp_grid_mgr.hpp; eps null: the absolute one, against `epsilon`): the device words of
+    // the channel's threshold and norm (batched: of channel 0, the others follow), the partial sums of b'b laid out as
+    // `part`, and what the threshold step reads beside `epsilon` -- epsilon_rel and the operator's status word (or null)
+    double *eps = nullptr, *bnorm = nullptr, *bpart = nullptr;
+    double epsilon_rel = 0.0;
+    const unsigned *status = nullptr;
     // rows folded so that the product's grid has ~2,048 blocks per channel group (and as many partial sums for alpha)
     void shape(int W, int rows, long count, unsigned groups = 1)
     {
@@ -894,12 +905,31 @@ struct ChannelSteps : PcgArgs {
     int residual() const { return apply(x, r, false); }
     int product() const { return apply(p, ap, true); }
     int precondition() const { return vcycle(*h, s, r, z, nu, st, ch); }
-    void init() const { hipLaunchKernelGGL(k_cg_init, dim3(blocks), dim3(kBlock), 0, s, b, r, p, n, part); }
+    // the relative stop test's one-block step after its init pass: bnorm and eps from the partial sums of b'b
+    void threshold() const
+    {
+        hipLaunchKernelGGL(k_mgr_threshold, dim3(1), dim3(kBlock), 0, s, static_cast<const double *>(bpart), blocks, epsilon, epsilon_rel, status,
+                           bnorm, eps);
+    }
+    void init() const
+    {
+        if (!eps) {
+            hipLaunchKernelGGL(k_cg_init, dim3(blocks), dim3(kBlock), 0, s, b, r, p, n, part);
+            return;
+        }
+        hipLaunchKernelGGL(k_mgr_init, dim3(blocks), dim3(kBlock), 0, s, b, r, p, n, part, bpart);
+        threshold();
+    }
     void dot() const { hipLaunchKernelGGL(k_cg_dot, dim3(blocks), dim3(kBlock), 0, s, r, z, n, part, st); }
     void update() const { hipLaunchKernelGGL(k_cg_update, dim3(blocks), dim3(kBlock), 0, s, x, p, r, ap, n, part, st); }
     void direction() const { hipLaunchKernelGGL(k_cg_direction, dim3(blocks), dim3(kBlock), 0, s, p, z, n, st); }
     // the one-block steps read `count` sums at `sum`
-    int check(const double *sum, int count) const { hipLaunchKernelGGL(k_mg_check, dim3(1), dim3(kBlock), 0, s, sum, count, epsilon, st); return CCP_OK; }
+    int check(const double *sum, int count) const
+    {
+        if (eps) hipLaunchKernelGGL(k_mgr_check, dim3(1), dim3(kBlock), 0, s, sum, count, static_cast<const double *>(eps), st);
+        else hipLaunchKernelGGL(k_mg_check, dim3(1), dim3(kBlock), 0, s, sum, count, epsilon, st);
+        return CCP_OK;
+    }
     int set_rlen(const double *sum, int count) const { hipLaunchKernelGGL(k_cg_set_rlen, dim3(1), dim3(kBlock), 0, s, sum, count, st); return CCP_OK; }
     int alpha(const double *sum, int count) const { hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(kBlock), 0, s, sum, count, st); return CCP_OK; }
     int beta(const double *sum, int count) const { hipLaunchKernelGGL(k_mg_beta, dim3(1), dim3(kBlock), 0, s, sum, count, st); return CCP_OK; }
@@ -929,7 +959,15 @@ struct NullspaceSteps : ChannelSteps {
         means(b, x, kMgnStart);
         return apply(x, r, false);
     }
-    void init() const { hipLaunchKernelGGL(k_mgn_init, dim3(blocks), dim3(kBlock), 0, s, b, r, lay, static_cast<const MgnState *>(ns), part); }
+    void init() const
+    {
+        if (!eps) {
+            hipLaunchKernelGGL(k_mgn_init, dim3(blocks), dim3(kBlock), 0, s, b, r, lay, static_cast<const MgnState *>(ns), part);
+            return;
+        }
+        hipLaunchKernelGGL(k_mgr_init_constant, dim3(blocks), dim3(kBlock), 0, s, b, r, lay, static_cast<const MgnState *>(ns), part, bpart);
+        threshold();
+    }
     void dot() const { hipLaunchKernelGGL(k_mgn_dot, dim3(blocks), dim3(kBlock), 0, s, r, z, n, npart, st); }
     int set_rlen() const { hipLaunchKernelGGL(k_mgn_rz<true>, dim3(1), dim3(kBlock), 0, s, static_cast<const double *>(npart), blocks, pixels, st, ns); return CCP_OK; }
     int beta() const { hipLaunchKernelGGL(k_mgn_rz<false>, dim3(1), dim3(kBlock), 0, s, static_cast<const double *>(npart), blocks, pixels, st, ns); return CCP_OK; }
@@ -966,19 +1004,48 @@ struct BatchedSteps : PcgArgs {
     int residual() const { return apply(x, r, false); }
     int product() const { return apply(p, ap, true); }
     int precondition() const { return vcycle_batched(*h, s, C, n, r, z, nu, st); }
-    void init() const { hipLaunchKernelGGL(k_mgb_init, vgrid, dim3(kBlock), 0, s, b, r, p, n, part, ps); }
+    void init() const
+    {
+        if (!eps) {
+            hipLaunchKernelGGL(k_mgb_init, vgrid, dim3(kBlock), 0, s, b, r, p, n, part, ps);
+            return;
+        }
+        hipLaunchKernelGGL(k_mgr_init_batched, vgrid, dim3(kBlock), 0, s, b, r, p, n, part, bpart, ps);
+        hipLaunchKernelGGL(k_mgr_threshold_batched, sgrid, dim3(kBlock), 0, s, static_cast<const double *>(bpart), ps, blocks, epsilon, epsilon_rel,
+                           status, bnorm, eps);
+    }
     void dot() const { hipLaunchKernelGGL(k_mgb_dot, vgrid, dim3(kBlock), 0, s, r, z, n, part, ps, st); }
     void update() const { hipLaunchKernelGGL(k_mgb_update, vgrid, dim3(kBlock), 0, s, x, p, r, ap, n, part, ps, st); }
     void direction() const { hipLaunchKernelGGL(k_mgb_direction, vgrid, dim3(kBlock), 0, s, p, z, n, st); }
-    int check() const { hipLaunchKernelGGL(k_mgb_check, sgrid, dim3(kBlock), 0, s, part, ps, blocks, epsilon, st); return CCP_OK; }
+    int check() const
+    {
+        if (eps) hipLaunchKernelGGL(k_mgr_check_batched, sgrid, dim3(kBlock), 0, s, part, ps, blocks, static_cast<const double *>(eps), st);
+        else hipLaunchKernelGGL(k_mgb_check, sgrid, dim3(kBlock), 0, s, part, ps, blocks, epsilon, st);
+        return CCP_OK;
+    }
     int set_rlen() const { hipLaunchKernelGGL(k_mgb_set_rlen, sgrid, dim3(kBlock), 0, s, part, ps, blocks, st); return CCP_OK; }
     int alpha() const { hipLaunchKernelGGL(k_mgb_alpha, sgrid, dim3(kBlock), 0, s, part, ps, apply_blocks, st); return CCP_OK; }
     int beta() const { hipLaunchKernelGGL(k_mgb_beta, sgrid, dim3(kBlock), 0, s, part, ps, blocks, st); return CCP_OK; }
 };
 
+// The relative stop test of one enqueue solve (ccp_grid_mg_conjugate_gradient_enqueue_relative): epsilon_rel and where in
+// h.erel the thresholds, the norms and the partial sums of b'b live.  `epsilon` of the solve is epsilon_abs then.
+struct PcgRelative {
+    double epsilon_rel;
+    double *eps, *bnorm, *bpart;
+    const unsigned *status;
+    // into a steps object: channel ch's words (batched: ch = 0)
+    void bind(PcgArgs &a, int ch) const
+    {
+        a.eps = eps + ch, a.bnorm = bnorm + ch, a.bpart = bpart;
+        a.epsilon_rel = epsilon_rel, a.status = status;
+    }
+};
+
 // ccp_grid_mg_conjugate_gradient in batched mode, on the levels and the work set pcg_ready made.  enqueue: the host-free
-// form, on the states at h.estate
-int pcg_batched(const GridMgView &v, MgHierarchy &h, double epsilon, int max_iteration, int nu, ccp_gs_report *report, bool enqueue)
+// form, on the states at h.estate; rel: its relative stop test, or null
+int pcg_batched(const GridMgView &v, MgHierarchy &h, double epsilon, int max_iteration, int nu, ccp_gs_report *report, bool enqueue,
+                const PcgRelative *rel)
 {
     const int C = v.channels;
     const unsigned groups = (unsigned)((C + kMgbGroup - 1) / kMgbGroup);
@@ -992,6 +1059,7 @@ int pcg_batched(const GridMgView &v, MgHierarchy &h, double epsilon, int max_ite
     S.b = v.b, S.x = v.x;
     if (enqueue) {
         S.st = h.estate.p;
+        if (rel) rel->bind(S, 0);
         return pcg_enqueue(S, max_iteration);
     }
     std::vector<CgState> host((size_t)C);
@@ -1307,7 +1375,8 @@ MgnLay nullspace_layout(const GridMgView &v) { return MgnLay{v.geom.W, 2 * v.geo
 
 // ---- one solve, three entry points -------------------------------------------------------------------------------------
 // ccp_grid_mg_conjugate_gradient is pcg_ready then pcg_solve; ccp_grid_mg_prepare is pcg_ready alone, and
-// ccp_grid_mg_conjugate_gradient_enqueue is pcg_solve alone in its enqueue form.
+// ccp_grid_mg_conjugate_gradient_enqueue is pcg_solve alone in its enqueue form (enqueue_solve; _enqueue_relative is the
+// same with the stop test of ccp_grid_mgr.hpp).
 
 // The combinations of options that the one-block calls refuse, before anything is built (the row-block calls:
 // prepare_rowblocked).  The line smoother serves a weighted handle, the fp64 V-cycle and the sequential channel mode;
@@ -1383,9 +1452,11 @@ int pcg_ready(ccp_grid *g, int32_t max_iteration, int32_t smoothing_sweeps, Grid
 
 // The solve itself on what pcg_ready left: the mode's steps object, and its loop once (batched) or per channel.
 // enqueue: the host-free form of the loop (pcg_enqueue), channel ch on the state h.estate[ch]; report is not used then.
-int pcg_solve(const GridMgView &v, MgHierarchy &h, double epsilon, int max_iteration, int nu, ccp_gs_report *report, bool enqueue)
+// rel (enqueue only): the stop test relative to |b|, or null.
+int pcg_solve(const GridMgView &v, MgHierarchy &h, double epsilon, int max_iteration, int nu, ccp_gs_report *report, bool enqueue,
+              const PcgRelative *rel = nullptr)
 {
-    if (v.cfg.channels == CCP_MG_CHANNELS_BATCHED) return pcg_batched(v, h, epsilon, max_iteration, nu, report, enqueue);
+    if (v.cfg.channels == CCP_MG_CHANNELS_BATCHED) return pcg_batched(v, h, epsilon, max_iteration, nu, report, enqueue, rel);
     const long n = v.geom.ch_stride;
     // one channel after the other: b, x, the channel's operator and, on the enqueue form, the channel's own state
     auto channels = [&](auto &S, auto &&each) -> int {
@@ -1399,6 +1470,7 @@ int pcg_solve(const GridMgView &v, MgHierarchy &h, double epsilon, int max_itera
             each(ch);
             if (enqueue) {
                 S.st = h.estate.p + ch;
+                if (rel) rel->bind(S, ch);
                 CCP_TRY(pcg_enqueue(S, max_iteration));
             } else {
                 CgState host;
@@ -1434,7 +1506,46 @@ int pcg_solve(const GridMgView &v, MgHierarchy &h, double epsilon, int max_itera
 // Is what the last ccp_grid_mg_prepare built what a solve of this view with `nu` sweeps runs on?
 bool prepared_for(const GridMgView &v, const MgHierarchy *h, int nu)
 {
-    return h && h->prepared && h->estate.p && cache_serves(v, *h) && h->prep_cfg == v.cfg && h->prep_nu == nu && h->prep_channels == v.channels;
+    return h && h->prepared && h->estate.p && h->erel.p && cache_serves(v, *h) && h->prep_cfg == v.cfg && h->prep_nu == nu && h->prep_channels == v.channels;
+}
+
+// The two enqueue solves.  epsilon_rel null: ccp_grid_mg_conjugate_gradient_enqueue, the stop test against `epsilon` and
+// the report of kMgeReportFields; otherwise ccp_grid_mg_conjugate_gradient_enqueue_relative, `epsilon` its epsilon_abs, the
+// thresholds in h.erel and the report of kMgrReportFields.
+int enqueue_solve(ccp_grid *g, double epsilon, const double *epsilon_rel, int32_t max_iteration, int32_t smoothing_sweeps,
+                  const ccp_device_array *report)
+{
+    GridMgView v{};
+    CCP_TRY(check_handle(g, &v));
+    int nu = 2;
+    CCP_TRY(sweeps_arg(smoothing_sweeps, &nu, v.cfg.smoother));
+    if (max_iteration < 0 || max_iteration > CCP_MG_ENQUEUE_MAX_ITERATION) return CCP_ERR_BAD_ARG;
+    if (epsilon_rel)                                               // (the absolute call takes any epsilon, as the synchronous one)
+        for (double e : {epsilon, *epsilon_rel})
+            if (!(e >= 0.0) || std::isinf(e)) return CCP_ERR_BAD_ARG;
+    const int fields = epsilon_rel ? kMgrReportFields : kMgeReportFields;
+    if (report) CCP_TRY(check_view_on(v.device, report, 1u << CCP_DTYPE_F64, true, 1, v.channels, fields, 1));
+    MgHierarchy *h = *v.cache;
+    if (!prepared_for(v, h, nu)) return CCP_ERR_STATE;
+    // The word and not what the host knows of it (v.refreshed): a recorded solve must see a refresh that follows the
+    // recording, an eager one too.  0 while a setter's operator, validated on the host, is installed; null: not weighted.
+    const unsigned *status = v.op_status;
+    hipLaunchKernelGGL(k_mge_init, dim3(1), dim3(kBlock), 0, v.stream, h->estate.p, v.channels, status);
+    double *const eps = h->erel.p, *const bnorm = eps + kMaxChannels;
+    const PcgRelative rel{epsilon_rel ? *epsilon_rel : 0.0, eps, bnorm, bnorm + kMaxChannels, status};
+    CCP_TRY(pcg_solve(v, *h, epsilon, max_iteration, nu, nullptr, true, epsilon_rel ? &rel : nullptr));
+    if (report) {
+        const MgeReport out{static_cast<double *>(const_cast<void *>(report->data)), (long)report->stride_y, (long)report->stride_x};
+        const MgnState *ns = constant_mode(v) ? h->nsstate.p : nullptr;
+        const CgState *st = h->estate.p;
+        if (epsilon_rel)
+            hipLaunchKernelGGL(k_mgr_report, dim3(1), dim3(kBlock), 0, v.stream, st, ns, v.channels, out, status, static_cast<const double *>(bnorm),
+                               static_cast<const double *>(eps));
+        else
+            hipLaunchKernelGGL(k_mge_report, dim3(1), dim3(kBlock), 0, v.stream, st, ns, v.channels, out, status);
+    }
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
 }
 
 // ---- the options (ccp_grid_mg_set_* / _get_*) ---------------------------------------------------------------------------
@@ -1690,6 +1801,9 @@ try {
     CCP_TRY(pcg_ready(g, 0, smoothing_sweeps, &v, &nu, &h));
     h->prepared = false;
     if (!h->estate.p) CCP_TRY(h->estate.alloc((size_t)kMaxChannels));
+    const bool batched = v.cfg.channels == CCP_MG_CHANNELS_BATCHED;
+    const size_t rel_words = 2 * (size_t)kMaxChannels + (size_t)((batched ? v.channels : 1) * (batched ? h->bat : h->seq).ps);
+    if (!h->erel.p || h->erel.n != rel_words) CCP_TRY(h->erel.alloc(rel_words));
     CCP_HIP(hipStreamSynchronize(v.stream));                       // what building enqueued has run: a failure shows here
     h->prep_cfg = v.cfg, h->prep_nu = nu, h->prep_channels = v.channels;
     h->prepared = true;
@@ -1699,27 +1813,13 @@ try {
 int ccp_grid_mg_conjugate_gradient_enqueue(ccp_grid *g, double epsilon, int32_t max_iteration, int32_t smoothing_sweeps,
                                            const ccp_device_array *report)
 try {
-    GridMgView v{};
-    CCP_TRY(check_handle(g, &v));
-    int nu = 2;
-    CCP_TRY(sweeps_arg(smoothing_sweeps, &nu, v.cfg.smoother));
-    if (max_iteration < 0 || max_iteration > CCP_MG_ENQUEUE_MAX_ITERATION) return CCP_ERR_BAD_ARG;
-    if (report) CCP_TRY(check_view_on(v.device, report, 1u << CCP_DTYPE_F64, true, 1, v.channels, kMgeReportFields, 1));
-    MgHierarchy *h = *v.cache;
-    if (!prepared_for(v, h, nu)) return CCP_ERR_STATE;
-    // The word and not what the host knows of it (v.refreshed): a recorded solve must see a refresh that follows the
-    // recording, an eager one too.  0 while a setter's operator, validated on the host, is installed; null: not weighted.
-    const unsigned *status = v.op_status;
-    hipLaunchKernelGGL(k_mge_init, dim3(1), dim3(kBlock), 0, v.stream, h->estate.p, v.channels, status);
-    CCP_TRY(pcg_solve(v, *h, epsilon, max_iteration, nu, nullptr, true));
-    if (report) {
-        const MgeReport out{static_cast<double *>(const_cast<void *>(report->data)), (long)report->stride_y, (long)report->stride_x};
-        const MgnState *ns = constant_mode(v) ? h->nsstate.p : nullptr;
-        hipLaunchKernelGGL(k_mge_report, dim3(1), dim3(kBlock), 0, v.stream, static_cast<const CgState *>(h->estate.p), ns, v.channels, out,
-                           status);
-    }
-    CCP_HIP(hipGetLastError());
-    return CCP_OK;
+    return enqueue_solve(g, epsilon, nullptr, max_iteration, smoothing_sweeps, report);
+} CCP_ABI_CATCH
+
+int ccp_grid_mg_conjugate_gradient_enqueue_relative(ccp_grid *g, double epsilon_abs, double epsilon_rel, int32_t max_iteration,
+                                                    int32_t smoothing_sweeps, const ccp_device_array *report)
+try {
+    return enqueue_solve(g, epsilon_abs, &epsilon_rel, max_iteration, smoothing_sweeps, report);
 } CCP_ABI_CATCH
 
 // ---- row blocks ----------------------------------------------------------------------------------------------------

@@ -554,11 +554,14 @@ class WeightedSolver:
     exactly this many PCG iterations (<= 4096); a channel that reaches sqrt(r'r) < epsilon earlier stops there and the
     remaining launches are no-ops for it, so x and the report are those of the synchronous solve with the same cap, bit
     for bit (`iterations` in a report counts completed iterations, and the update that passes epsilon is one more: a system
-    that reports 6 needs iterations >= 7 here).  epsilon is absolute.  hierarchy, precision, channels, smoother, nullspace: as weighted_solve's (the
-    hierarchy defaults to "rescaled", as in weighted_solve_grad).  Two smoothing sweeps, as everywhere in this module.
+    that reports 6 needs iterations >= 7 here).  epsilon is absolute until set_stop gives a relative tolerance: then every
+    solve, forward or adjoint, stops channel c at sqrt(r'r) < max(epsilon, relative * |b_c|), |b_c| of the right-hand side
+    that solve finds on the device (capi.Grid.mg_conjugate_gradient_enqueue_relative).
+    hierarchy, precision, channels, smoother, nullspace: as weighted_solve's (the hierarchy defaults to "rescaled", as in weighted_solve_grad).  Two smoothing sweeps, as everywhere in this module.
 
     Nothing checks convergence for you -- that would be a read-back: pass `report` (a float64 C x 6 tensor: iterations,
-    converged, last_l1_step, b_mean, x_mean, 0 per channel) and look at it when the stream has passed."""
+    converged, last_l1_step, b_mean, x_mean, 0 per channel; C x 8 with a relative tolerance set: then |b_c| and the
+    threshold follow) and look at it when the stream has passed."""
 
     SWEEPS = 2
 
@@ -573,6 +576,7 @@ class WeightedSolver:
             raise ValueError(f"iterations must be 0 .. 4096 (one call queues exactly that many), not {iterations}")
         self.H, self.W, self.C, self.device = int(H), int(W), int(C), torch.device("cuda", dev)
         self.iterations, self.epsilon = int(iterations), float(epsilon)
+        self.relative = None                               # set_stop: the tolerance relative to |b|, or None (epsilon alone)
         self.nullspace = capi.mg_nullspace_value(nullspace)
         self._operator = None
         self._generation = 0                               # refreshes of the handle's operator so far (solve_grad's backward)
@@ -596,13 +600,31 @@ class WeightedSolver:
         self.grid.mg_prepare(self.SWEEPS)
         self._operator = (wx, wy, lam, fixed)
 
+    def set_stop(self, epsilon=None, relative=None):
+        """The stop test of every later solve, solve_grad's forward and backward included.  epsilon: the absolute tolerance
+        (None: keep the present one).  relative: None -- the state after __init__ -- stops at sqrt(r'r) < epsilon and
+        reports C x 6, as ever; a number stops channel c at sqrt(r'r) < max(epsilon, relative * |b_c|), with |b_c| the norm
+        of the right-hand side of THAT solve, formed on the device: of the assembled system in a forward solve, of dL/du
+        in a backward one, whatever the scale of the loss.  Reports and adjoint reports are then C x 8 (|b_c| and the
+        threshold follow the six fields).  Give epsilon a floor where a right-hand side may vanish.  Host state only:
+        nothing is enqueued, and a solve already recorded in a graph keeps the test it was recorded with."""
+        if epsilon is not None:
+            self.epsilon = float(epsilon)
+        self.relative = None if relative is None else float(relative)
+
+    def _enqueue_pcg(self, report):
+        """The enqueue solve on what the handle holds, by the stop test set_stop chose."""
+        if self.relative is None:
+            return self.grid.mg_conjugate_gradient_enqueue(self.epsilon, self.iterations, self.SWEEPS, report)
+        return self.grid.mg_conjugate_gradient_enqueue_relative(self.epsilon, self.relative, self.iterations, self.SWEEPS, report)
+
     def _enqueue_solve(self, gx, gy, f, values, x0, out, report):
         if self._operator is None:
             raise RuntimeError("WeightedSolver: set_operator first")
         g = self.grid
         g.set_x_tensor(self._zero if x0 is None else x0)
         g.assemble_constrained_rhs_tensor(gx, gy, f, values, init_x=False)   # (puts `values` on the fixed pixels of x)
-        g.mg_conjugate_gradient_enqueue(self.epsilon, self.iterations, self.SWEEPS, report)
+        self._enqueue_pcg(report)
         return g.get_x_tensor(out=out)
 
     def solve(self, gx, gy, f, values=None, x0=None, out=None, report=None):
@@ -723,7 +745,7 @@ def _persistent_function():
             if grad.dtype not in (torch.float32, torch.float64):
                 grad = grad.to(torch.float64)
             g.adjoint_begin_tensor(grad)
-            g.mg_conjugate_gradient_enqueue(solver.epsilon, solver.iterations, solver.SWEEPS, ctx.adjoint_report)
+            solver._enqueue_pcg(ctx.adjoint_report)
             out = {n: torch.empty(inputs[n].shape, dtype=inputs[n].dtype, device=inputs[n].device) for n in want}
             got = g.weighted_adjoint_tensor(u, grad if "values" in want else None, inputs["gx"], inputs["gy"], inputs["f"], wx, wy, lam,
                                             fixed, want=want, out=out)

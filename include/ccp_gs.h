@@ -1047,10 +1047,51 @@ int ccp_grid_mg_prepare(ccp_grid *g, int32_t smoothing_sweeps);
  * on the device (one more reduction per solve: epsilon is absolute, as in the synchronous call); refreshing an installed
  * operator without the setters' validation read-back.  Additive: the ABI version does not change.
  * (That last follow-up is ccp_grid_refresh_weights_device below: with it the operator's VALUES may change between the
- * replays too, and report field [5] is +0.0 or the operator status it leaves.) */
+ * replays too, and report field [5] is +0.0 or the operator status it leaves.)
+ * (The stop test relative to |b| is ccp_grid_mg_conjugate_gradient_enqueue_relative below.) */
 #define CCP_MG_ENQUEUE_MAX_ITERATION 4096
 int ccp_grid_mg_conjugate_gradient_enqueue(ccp_grid *g, double epsilon, int32_t max_iteration, int32_t smoothing_sweeps,
                                            const ccp_device_array *report);
+
+/* ccp_grid_mg_conjugate_gradient_enqueue_relative: the enqueue solve above with a stop test relative to |b|, formed on the
+ * device.  An absolute epsilon that the host passes by value is baked into a captured graph, while the right-hand side --
+ * and its scale -- changes from replay to replay; an adjoint solve's right-hand side dL/du has a scale of its own; and a
+ * caller who wants a relative tolerance would have to read |b| back.  Here every channel stops against its own threshold,
+ * which the solve computes from the right-hand side it finds when it runs.
+ *   The solve: recurrence, kernels, launch geometry and operation order are those of
+ *   ccp_grid_mg_conjugate_gradient_enqueue in every mode that call serves (sequential and batched channels, both
+ *   hierarchy kinds, F64 and F32, point and line smoother, CCP_MG_NULLSPACE_CONSTANT, shared and per-channel operators).
+ *   Same precondition (ccp_grid_mg_prepare with the same smoothing_sweeps; a prepared handle serves either enqueue
+ *   call), same statuses, same calls that drop the preparation, same EXACTLY max_iteration iterations enqueued.
+ *   The threshold of channel c:  eps_c = fmax(epsilon_abs, epsilon_rel * bnorm_c),  bnorm_c = sqrt(bb_c),
+ *   in this operation order: one multiply, then fmax.  bb_c is what the solve's init pass would sum as r'r if r were the
+ *   right-hand side itself: the sum of b b over the elements of channel c; in CONSTANT mode the sum of
+ *   (b - mean(b)) (b - mean(b)) over the pixels, with the b_mean the solve uses.  It is formed inside the init pass
+ *   that already reads b for r = b - A x -- no extra pass over the image -- over the same ranges and in the same
+ *   deterministic summation order as r'r, so with x = 0 on entry bb_c equals the initial r'r BIT FOR BIT.  One one-workgroup
+ *   launch per solve (per channel in sequential mode) then forms bnorm_c and eps_c.  Both live in device memory and the
+ *   check steps read eps_c from there: a recorded solve follows each replay's right-hand side.
+ *   The stop rule of channel c:  r1norm < eps_c || r1norm == 0.0.  For eps_c > 0 this is the rule of the absolute call.
+ *   The second term makes a zero right-hand side from x = 0 stop at 0 iterations, converged, with x untouched and no 0/0,
+ *   also when epsilon_abs is 0.  Caveat: a zero right-hand side with epsilon_abs == 0 and a non-zero x on entry has
+ *   eps_c = 0 and runs to the cap unless a residual is exactly 0: give epsilon_abs a floor (the absolute accuracy you
+ *   would accept for a vanishing b) whenever b may vanish.
+ *   epsilon_abs or epsilon_rel negative, NaN or infinite: CCP_ERR_BAD_ARG with nothing enqueued.  epsilon_rel == 0: x and
+ *   report fields [0] .. [5] equal ccp_grid_mg_conjugate_gradient_enqueue(g, epsilon_abs, ...) bit for bit, and
+ *   eps_c = epsilon_abs.  max_iteration and smoothing_sweeps as above.
+ *   report: NULL, or an F64 view of `channels` x 8 (CCP_MG_RELATIVE_REPORT_FIELDS), laid out and checked like the report
+ *   above (a `channels` x 6 view is too short: CCP_ERR_BAD_ARG).  Fields [0] .. [5] as above; [6] bnorm_c; [7] eps_c.
+ *   While the operator status word is non-zero every channel starts stopped, as above: x and b are untouched, [5] carries
+ *   the status and [6] = [7] = +0.0.
+ *   No allocation, no host synchronisation, no copy to or from host memory: the thresholds, the norms and the second set
+ *   of partial sums are allocated by ccp_grid_mg_prepare, always, and nothing on this path rests on host state that a
+ *   replay cannot see.
+ * Out of scope: a synchronous relative twin; the _rowblocked calls; ccp_grid_mg_apply; the C++ facades; a stop test
+ * relative to the initial residual rather than b.  Additive: the ABI version does not change. */
+#define CCP_MG_RELATIVE_REPORT_FIELDS 8
+int ccp_grid_mg_conjugate_gradient_enqueue_relative(ccp_grid *g, double epsilon_abs, double epsilon_rel,
+                                                    int32_t max_iteration, int32_t smoothing_sweeps,
+                                                    const ccp_device_array *report);
 
 /* ---- Refreshing a weighted operator by enqueue only -------------------------------------------------------------------------
  * Edge weights, lambda or a confidence map that come out of a network or a reweighting step change at every training step
