@@ -95,6 +95,7 @@ ABI_SYMBOLS = (
     "ccp_grid_constraint_info_channel",
     "ccp_grid_mg_prepare", "ccp_grid_mg_conjugate_gradient_enqueue", "ccp_grid_mg_conjugate_gradient_enqueue_relative",
     "ccp_grid_refresh_weights_device", "ccp_grid_operator_status",
+    "ccp_grid_reserve_constraints", "ccp_grid_refresh_constrained_device",
     "ccp_grid_set_mask_device", "ccp_mask_erode_cross_device", "ccp_panorama_begin_device", "ccp_panorama_add_device",
     "ccp_panorama_finish_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
@@ -317,6 +318,8 @@ def load() -> C.CDLL:
     L.ccp_grid_operator_channels.argtypes = [vp, C.POINTER(i32)]
     L.ccp_grid_refresh_weights_device.argtypes = [vp, vp, vp, vp]
     L.ccp_grid_operator_status.argtypes = [vp, C.POINTER(i32)]
+    L.ccp_grid_reserve_constraints.argtypes = [vp, i32]
+    L.ccp_grid_refresh_constrained_device.argtypes = [vp, vp, vp, vp, vp]
     L.ccp_grid_mg_level_channel.argtypes = [vp, i32, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
     L.ccp_grid_constraint_info_channel.argtypes = [vp, i32, vp, vp, vp]
     L.ccp_grid_adjoint_begin_device.argtypes = [vp, da]
@@ -1297,6 +1300,33 @@ class Grid:
             arrs = [self._weight_array(t, n) for t, n in named]
         refs = [None if a is None else C.byref(a) for a in arrs]
         self._on_stream(lambda: self.L.ccp_grid_refresh_weights_device(self.h, *refs), "ccp_grid_refresh_weights_device")
+
+    def reserve_constraints(self, on=True):
+        """Keep the three constraint planes of every operator the setters install from now on, fixed pixels or none, so
+        that refresh_constrained_tensor can give the handle a fixed set later.  Host state only; takes effect at the
+        next set_weights*; every result of the handle stays what it was, bit for bit.  24 bytes per pixel and operator."""
+        check(self.L.ccp_grid_reserve_constraints(self.h, 1 if on else 0), "ccp_grid_reserve_constraints")
+
+    def refresh_constrained_tensor(self, wx=None, wy=None, lam=None, fixed=None):
+        """refresh_weights_tensor with a new set of fixed pixels: `fixed` as the setters read it (uint8, bool, float32 or
+        float64, != 0: fixed; H x W, or H x W x channels on an operator per channel; None: no pixel fixed).  Enqueued on
+        torch's current stream: no allocation and no synchronisation, so torch.cuda.graph may record it.  Needs what
+        refresh_weights_tensor needs and the constraint planes: reserve_constraints() before the setter, or a setter's
+        mask with a fixed pixel (CcpError STATE otherwise).  Afterwards the handle holds what the setter with the same
+        four tensors and mg_prepare form on a fresh reserved handle, bit for bit; constraint_info reports the new set."""
+        torch = self._torch()
+        named = ((wx, "wx"), (wy, "wy"), (lam, "lam"))
+        per_channel = self.operator_channels() > 1 or (self.C == 1 and any(isinstance(t, torch.Tensor) and t.dim() == 3
+                                                                           for t in (wx, wy, lam, fixed)))
+        if per_channel:
+            floats = (torch.float32, torch.float64)
+            arrs = [self._channel_array(t, n, floats) for t, n in named]
+            arrs.append(self._channel_array(fixed, "fixed", (torch.uint8,) + floats))
+        else:
+            arrs = [self._weight_array(t, n) for t, n in named]
+            arrs.append(None if fixed is None else self._mask_array(fixed))
+        refs = [None if a is None else C.byref(a) for a in arrs]
+        self._on_stream(lambda: self.L.ccp_grid_refresh_constrained_device(self.h, *refs), "ccp_grid_refresh_constrained_device")
 
     def operator_status(self) -> int:
         """The operator status word of the last refresh_weights_tensor (0: good; 1: a bad weight, 2: out of float range in

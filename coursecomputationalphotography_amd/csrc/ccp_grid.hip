@@ -871,7 +871,7 @@ try {
         if (st == CCP_OK && hipMemset(g->wop.p, 0, 4 * sizeof(double) * (size_t)geo.ch_stride) != hipSuccess) st = CCP_ERR_HIP;
         if (st == CCP_OK) st = g->wpart.alloc(4 * (size_t)d->channels * kWeightedApplyBlocks);
         if (st == CCP_OK) st = g->wcount.alloc(1 + 3 * kMaxChannels);
-        if (st == CCP_OK) st = g->rcount.alloc(1 + 3 * kMaxChannels);
+        if (st == CCP_OK) st = g->rcount.alloc(kRefreshCounts);
         if (st == CCP_OK) st = g->op_status.alloc(1);
         if (st == CCP_OK && hipMemset(g->op_status.p, 0, sizeof(unsigned)) != hipSuccess) st = CCP_ERR_HIP;   // no refresh yet: good
     }

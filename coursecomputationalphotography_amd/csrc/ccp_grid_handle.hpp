@@ -142,7 +142,8 @@ struct ccp_grid {
     bool has_op = false;
     DevBuf<double> wop, wpart;
     // Fixed pixels (ccp_grid_set_weights_constrained_*): wcons holds the planes ce, cs and lambda' (ccp_grid_weighted.hpp)
-    // while the operator has any (has_fixed), and is released otherwise.  wcount: the formation pass's verdict and counts
+    // while the operator has any or the handle reserves them (has_fixed: the planes exist), and is released otherwise.
+    // wcount: the formation pass's verdict and counts
     bool has_fixed = false;
     DevBuf<double> wcons;
     DevBuf<unsigned long long> wcount;
@@ -161,11 +162,22 @@ struct ccp_grid {
     DevBuf<unsigned long long> rcount;
     DevBuf<unsigned> op_status;
     bool refreshed = false;
+    // ccp_grid_reserve_constraints / ccp_grid_refresh_constrained_device.  reserve_cons: the setters keep wcons whether or
+    // not a pixel is fixed (has_fixed then says "the three planes exist", which is all its readers ask).  The fixed set a
+    // constrained refresh installs is counted into words of its own, rcount[kRefreshFixedAt + k] for set k, which only that
+    // call clears and counts into (a value refresh clears rcount[1 + 3 k] and does not recount it); fixed_on_device: those
+    // words, not pc_fixed, hold the fixed counts -- from the first constrained refresh until a setter.
+    bool reserve_cons = false;
+    bool fixed_on_device = false;
     MgConfig mg_cfg;                           // ccp_grid_mg_set_* (ccp_grid_mg_view.hpp)
     MgNullspace mg_nullspace;                  // goes with the operator (drop_operator)
 };
 
 namespace ccp {
+
+// rcount: wcount's 1 + 3 sets words of up to kMaxChannels sets, then one fixed-pixel count per set
+constexpr int kRefreshFixedAt = 1 + 3 * kMaxChannels;
+constexpr int kRefreshCounts = kRefreshFixedAt + kMaxChannels;
 
 // The weighted product's launch geometry: ccp_grid.hip sizes wpart by it and reduces what ccp_grid_weighted.hip launched
 constexpr int kWeightedApplyBlocks = 1024;   // blocks per (channel, colour) of k_weighted_apply

@@ -182,6 +182,7 @@ void drop_operator(ccp_grid *g)
     g->has_op = g->has_fixed = false;
     g->per_channel = false;
     g->refreshed = false;
+    g->fixed_on_device = false;
     g->mg_nullspace.forget();
 }
 
@@ -190,10 +191,13 @@ void drop_operator(ccp_grid *g)
 int refreshed_counts(ccp_grid *g)
 {
     const int sets = g->per_channel ? g->desc.channels : 1;
-    unsigned long long count[1 + 3 * kMaxChannels] = {};
-    CCP_HIP(hipMemcpyAsync(count, g->rcount.p, sizeof(unsigned long long) * (size_t)(1 + 3 * sets), hipMemcpyDeviceToHost, g->stream));
+    unsigned long long count[kRefreshCounts] = {};
+    // (after a constrained refresh the fixed pixels are the device's too: the words behind the others, in the same copy)
+    const int words = g->fixed_on_device ? kRefreshFixedAt + sets : 1 + 3 * sets;
+    CCP_HIP(hipMemcpyAsync(count, g->rcount.p, sizeof(unsigned long long) * (size_t)words, hipMemcpyDeviceToHost, g->stream));
     CCP_HIP(hipStreamSynchronize(g->stream));
     for (int c = 0; c < sets; ++c) {
+        if (g->fixed_on_device) g->pc_fixed[c] = (long)count[kRefreshFixedAt + c];
         g->pc_live[c] = (long)g->geom.W * g->geom.H - g->pc_fixed[c] - (long)count[2 + 3 * c];
         g->pc_edges[c] = (long)count[3 + 3 * c];
     }
@@ -215,8 +219,9 @@ int operator_planes(ccp_grid *g, int sets)
 // The handle's operators (one that all channels share, the views H x W; or per_channel: one per channel, the views
 // H x W x C) from three weight views and, with `fixed`, a mask of fixed pixels: all planes in one launch, the verdict
 // and, with a mask, every set's counts in one read.  The old operator and the hierarchy built on it are gone either
-// way: a refusal leaves the handle with none.  The three extra planes stay only if some set has a fixed pixel: with
-// none the four planes are what the call without a mask forms, bit for bit.
+// way: a refusal leaves the handle with none.  The three extra planes stay only if some set has a fixed pixel or the
+// handle reserves them (ccp_grid_reserve_constraints; no mask is the all-zero mask then): with no fixed pixel the four
+// planes are what the call without a mask forms, bit for bit.
 int form_operator(ccp_grid *g, bool per_channel, const ImageView &wx, const ImageView &wy, const ImageView &lam, const ImageView *fixed)
 {
     const Geom &geo = g->geom;
@@ -228,6 +233,8 @@ int form_operator(ccp_grid *g, bool per_channel, const ImageView &wx, const Imag
     drop_operator(g);
     g->wcons.release();
     CCP_TRY(operator_planes(g, sets));
+    const ImageView none{nullptr, 0, 0, 0, CCP_DTYPE_U8, 0.0};
+    if (!fixed && g->reserve_cons) fixed = &none;
     if (fixed) {
         CCP_TRY(g->wcons.alloc(3 * (size_t)sets * (size_t)n));
         CCP_HIP(hipMemsetAsync(g->wcons.p, 0, 3 * sizeof(double) * (size_t)sets * (size_t)n, g->stream));   // the pads
@@ -238,7 +245,8 @@ int form_operator(ccp_grid *g, bool per_channel, const ImageView &wx, const Imag
     CCP_HIP(hipStreamSynchronize(g->stream));
     bool any_fixed = false;
     for (int c = 0; c < sets && fixed; ++c) any_fixed = any_fixed || count[1 + 3 * c] != 0;
-    if (count[0] || !any_fixed) g->wcons.release();
+    const bool keep = !count[0] && (any_fixed || g->reserve_cons);
+    if (!keep) g->wcons.release();
     if (count[0]) return CCP_ERR_BAD_ARG;
     for (int c = 0; c < sets; ++c) {
         g->pc_fixed[c] = fixed ? (long)count[1 + 3 * c] : 0;
@@ -247,7 +255,7 @@ int form_operator(ccp_grid *g, bool per_channel, const ImageView &wx, const Imag
     }
     g->has_op = true;
     g->per_channel = per_channel;
-    g->has_fixed = any_fixed;
+    g->has_fixed = keep;                                                   // the three planes exist
     return edge_timeout_status(g);
 }
 
@@ -305,6 +313,43 @@ int weighted_apply_mode(ccp_grid *g)
         CCP_HIP(hipGetLastError());
     }
     return CCP_OK;
+}
+
+// ccp_grid_refresh_weights_device (with_mask false: the fixed set the lambda plane marks is kept) and
+// ccp_grid_refresh_constrained_device (the fixed set of `fixed`, NULL: the empty one): one check of the views, one
+// mg_refresh_begin / mg_refresh pair around the pass over level 0
+int refresh_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
+                   const ccp_device_array *fixed, bool with_mask)
+{
+    CCP_TRY(weighted_handle(g));
+    if (!g->has_op) return CCP_ERR_STATE;                                  // (the operator's kind decides the views' extents)
+    const Geom &geo = g->geom;
+    const int sets = g->per_channel ? g->desc.channels : 1;
+    const ccp_device_array *src[3] = {wx, wy, lambda};
+    const double dflt[3] = {1.0, 1.0, 0.0};
+    ImageView v[3];
+    for (int i = 0; i < 3; ++i) {
+        if (src[i]) CCP_TRY(check_view(g, src[i], kF32F64, false, 1, geo.H, geo.W, sets));
+        v[i] = image_view(src[i], dflt[i]);
+    }
+    if (fixed) CCP_TRY(check_view(g, fixed, kF32F64 | kU8, false, 1, geo.H, geo.W, sets));
+    if (with_mask && !g->has_fixed) return CCP_ERR_STATE;                  // the three planes: reserved, or a setter's mask had a fixed pixel
+    // from here on: launches on the handle's stream, nothing else.  The first clears the status word and rcount (a new
+    // fixed set: the fixed-pixel words behind it too, which a value refresh leaves as they are).
+    CCP_TRY(mg_refresh_begin(g, with_mask ? kRefreshFixedAt + sets : 1 + 3 * sets));
+    const long n = geo.ch_stride;
+    if (with_mask)
+        hipLaunchKernelGGL(k_weighted_fixed_refresh, pixels(geo.W, geo.H, sets), dim3(kBlock), 0, g->stream, v[0], v[1], v[2],
+                           image_view(fixed, 0.0), geo.W, geo.H, geo.pitch, g->wop.p, n, 4 * n, g->wcons.p, 3 * n, g->rcount.p,
+                           g->rcount.p + kRefreshFixedAt);
+    else
+        hipLaunchKernelGGL(k_weighted_refresh, pixels(geo.W, geo.H, sets), dim3(kBlock), 0, g->stream, v[0], v[1], v[2], geo.W, geo.H, geo.pitch,
+                           g->wop.p, n, 4 * n, g->has_fixed ? g->wcons.p : nullptr, 3 * n, g->rcount.p);
+    CCP_HIP(hipGetLastError());
+    g->refreshed = true;
+    if (with_mask) g->fixed_on_device = true;   // the host's pc_fixed is the old set's: ccp_grid_constraint_info reads the device's from now on
+    g->mg_nullspace.floating = -1;      // the census verdict the host remembers is the old values': a later prepare or solve asks again
+    return mg_refresh(g);
 }
 
 }  // namespace
@@ -412,26 +457,21 @@ try {
 
 int ccp_grid_refresh_weights_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda)
 try {
+    return refresh_device(g, wx, wy, lambda, nullptr, false);
+} CCP_ABI_CATCH
+
+int ccp_grid_refresh_constrained_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
+                                        const ccp_device_array *fixed)
+try {
+    return refresh_device(g, wx, wy, lambda, fixed, true);
+} CCP_ABI_CATCH
+
+int ccp_grid_reserve_constraints(ccp_grid *g, int32_t on)
+try {
     CCP_TRY(weighted_handle(g));
-    if (!g->has_op) return CCP_ERR_STATE;                                  // (the operator's kind decides the views' extents)
-    const Geom &geo = g->geom;
-    const int sets = g->per_channel ? g->desc.channels : 1;
-    const ccp_device_array *src[3] = {wx, wy, lambda};
-    const double dflt[3] = {1.0, 1.0, 0.0};
-    ImageView v[3];
-    for (int i = 0; i < 3; ++i) {
-        if (src[i]) CCP_TRY(check_view(g, src[i], kF32F64, false, 1, geo.H, geo.W, sets));
-        v[i] = image_view(src[i], dflt[i]);
-    }
-    // from here on: launches on the handle's stream, nothing else.  The first clears the status word and rcount.
-    CCP_TRY(mg_refresh_begin(g, 1 + 3 * sets));
-    const long n = geo.ch_stride;
-    hipLaunchKernelGGL(k_weighted_refresh, pixels(geo.W, geo.H, sets), dim3(kBlock), 0, g->stream, v[0], v[1], v[2], geo.W, geo.H, geo.pitch,
-                       g->wop.p, n, 4 * n, g->has_fixed ? g->wcons.p : nullptr, 3 * n, g->rcount.p);
-    CCP_HIP(hipGetLastError());
-    g->refreshed = true;
-    g->mg_nullspace.floating = -1;      // the census verdict the host remembers is the old values': a later prepare or solve asks again
-    return mg_refresh(g);
+    if (g->desc.ghost != 0 || g->desc.row_count < g->desc.height) return CCP_ERR_UNSUPPORTED;   // a row block
+    g->reserve_cons = on != 0;                                             // the next setter's business: nothing changes now
+    return CCP_OK;
 } CCP_ABI_CATCH
 
 int ccp_grid_operator_status(ccp_grid *g, int32_t *status)

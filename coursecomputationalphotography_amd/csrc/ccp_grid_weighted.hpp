@@ -1,7 +1,7 @@
 // ccp_grid_weighted.hpp — the weighted grid handles (include/ccp_gs.h, CCP_GRID_WEIGHTED), hand-written for gfx950:
 // the stored operator's planes and arithmetic, and the operator kernels: the formation with its validation, its
-// enqueue-only twin that refreshes the values of an installed operator, the right-hand side of every channel and the
-// coarsening.
+// enqueue-only twins that refresh the values of an installed operator or its values and fixed set, the right-hand side of
+// every channel and the coarsening.
 //
 // Operator.  A weighted handle stores its level-0 operator in four planes of the grid's colour-split layout (w_at,
 // the layout of x and b and of the multigrid levels' mg_at): d, we, ws and lambda, pads zero.  we / ws are the weights
@@ -24,7 +24,8 @@
 // values); a fixed pixel gets b = 0 and x := v.
 //
 // One operator or one per channel.  The handle keeps `sets` sets of the four planes, 4 x ch_stride doubles apart (d, we,
-// ws, lambda of a set one after the other), and, while any set has a fixed pixel, `sets` sets of ce, cs, lambda',
+// ws, lambda of a set one after the other), and, while any set has a fixed pixel or the handle reserves them
+// (ccp_grid_reserve_constraints, for ccp_grid_refresh_constrained_device to fill later), `sets` sets of ce, cs, lambda',
 // 3 x ch_stride apart: sets = 1 is the operator every channel shares (ccp_grid_set_weights_*), sets = channels gives
 // every channel its own (ccp_grid_set_weights_per_channel_device).  A shared operator is a per-channel one with a single
 // set that all channels read, and the operator kernels below serve both: the set lies on grid z.  A set without fixed
@@ -186,6 +187,67 @@ k_weighted_refresh(ImageView wx, ImageView wy, ImageView lam, int W, int H, long
     if (n_edges) atomicAdd(&tally[1], n_edges);
     __syncthreads();
     if (threadIdx.x < 2 && tally[threadIdx.x]) atomicAdd(count + 2 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
+}
+
+// ccp_grid_refresh_constrained_device: new values AND a new fixed set for the installed operators, on a handle whose
+// three extra planes exist.  k_weighted_coef_fixed's arithmetic in its order -- the flags from the mask view, dd and lp
+// summed over the same operands, every weight checked, a fixed pixel's too -- so that the planes have the bits the setter
+// forms from the same four views; nothing that is read here is written here, so there is no in-place question.  What
+// differs is the refresh's: a lambda that fails the check is stored as +0.0 (a refused refresh poisons the values and
+// leaves the marks those of the mask), and the counts go where the refresh keeps them: count[0] the verdict of all sets,
+// count[2 + 3 k], count[3 + 3 k] set k's free pixels with d = 0 and edges with exactly one fixed end, as
+// k_weighted_refresh leaves them, and nfixed[k] set k's fixed pixels, words that only this kernel counts into (a value
+// refresh clears count[1 + 3 k] and does not recount it) -- per block in LDS, then one atomic per non-zero count.
+// grid = (ceil(W/kBlock), H, sets).
+static __global__ void __launch_bounds__(kBlock)
+k_weighted_fixed_refresh(ImageView wx, ImageView wy, ImageView lam, ImageView fixed, int W, int H, long pitch, double *__restrict__ op,
+                         long plane, long op_stride, double *__restrict__ cons, long cons_stride, unsigned long long *__restrict__ count,
+                         unsigned long long *__restrict__ nfixed)
+{
+    __shared__ unsigned tally[3];
+    if (threadIdx.x < 3) tally[threadIdx.x] = 0;
+    __syncthreads();
+    const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y, ch = blockIdx.z;
+    unsigned n_fixed = 0, n_dead = 0, n_edges = 0;
+    if (x < W) {
+        const double l = lam(y, x, ch);
+        const double e = x + 1 < W ? wx(y, x, ch) : 0.0;
+        const double s = y + 1 < H ? wy(y, x, ch) : 0.0;
+        if (!(weight_ok(l) && weight_ok(e) && weight_ok(s))) atomicOr(count, 1ull);
+        const bool fp = fixed(y, x, ch) != 0;
+        const bool fN = y >= 1 && fixed(y - 1, x, ch) != 0, fW = x >= 1 && fixed(y, x - 1, ch) != 0;
+        const bool fE = x + 1 < W && fixed(y, x + 1, ch) != 0, fS = y + 1 < H && fixed(y + 1, x, ch) != 0;
+        const double wN = y >= 1 ? wy(y - 1, x, ch) : 0.0, wW = x >= 1 ? wx(y, x - 1, ch) : 0.0;
+        double dd = l;
+        if (y >= 1) dd += wN;
+        if (x >= 1) dd += wW;
+        if (x + 1 < W) dd += e;
+        if (y + 1 < H) dd += s;
+        double lp = l;
+        if (fN) lp += wN;
+        if (fW) lp += wW;
+        if (fE) lp += e;
+        if (fS) lp += s;
+        const bool be = x + 1 < W && fp != fE, bs = y + 1 < H && fp != fS;   // edges with exactly one fixed end
+        double *__restrict__ o = op + (long)ch * op_stride, *__restrict__ k = cons + (long)ch * cons_stride;
+        const long at = w_at(pitch, x, y);
+        o[at] = fp ? 0.0 : dd;
+        o[plane + at] = fp || fE ? 0.0 : e;
+        o[2 * plane + at] = fp || fS ? 0.0 : s;
+        o[3 * plane + at] = fp ? -1.0 : weight_ok(l) ? l : 0.0;
+        k[at] = be ? e : 0.0;
+        k[plane + at] = bs ? s : 0.0;
+        k[2 * plane + at] = fp ? 0.0 : lp;
+        n_fixed = fp;
+        n_dead = !fp && dd == 0.0;
+        n_edges = (unsigned)be + (unsigned)bs;
+    }
+    if (n_fixed) atomicAdd(&tally[0], n_fixed);
+    if (n_dead) atomicAdd(&tally[1], n_dead);
+    if (n_edges) atomicAdd(&tally[2], n_edges);
+    __syncthreads();
+    if (threadIdx.x == 0 && tally[0]) atomicAdd(nfixed + ch, (unsigned long long)tally[0]);
+    if ((threadIdx.x == 1 || threadIdx.x == 2) && tally[threadIdx.x]) atomicAdd(count + 1 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
 }
 
 // b of `cpb` channels per block from one set of the stored operator: block z takes channels [z cpb, (z + 1) cpb) and the

@@ -548,7 +548,8 @@ class WeightedSolver:
     enqueue on torch's current stream (capi.Grid.mg_conjugate_gradient_enqueue): no host synchronisation and no
     allocation on the handle, so a solve may be recorded by torch.cuda.graph together with whatever produces its inputs
     and consumes its result.  refresh_operator gives the installed operator new values the same way, enqueue only, so
-    weights that a network or a reweighting step produces every step can sit in the same graph.
+    weights that a network or a reweighting step produces every step can sit in the same graph; refresh_constraints does the
+    same with a new mask of fixed pixels, on a handle whose constraint planes exist (reserve_constraints before set_operator).
 
     H, W, C: the canvas and its channels; device: a torch device or a GPU index.  iterations: every solve enqueues
     exactly this many PCG iterations (<= 4096); a channel that reaches sqrt(r'r) < epsilon earlier stops there and the
@@ -579,6 +580,7 @@ class WeightedSolver:
         self.relative = None                               # set_stop: the tolerance relative to |b|, or None (epsilon alone)
         self.nullspace = capi.mg_nullspace_value(nullspace)
         self._operator = None
+        self._planes = False                               # refresh_constraints has run: the constraint planes exist
         self._generation = 0                               # refreshes of the handle's operator so far (solve_grad's backward)
         self._zero = torch.zeros((), dtype=torch.float64, device=self.device).expand(self.H, self.W, self.C)
         self.grid = capi.Grid(self.W, self.H, self.C, device=dev, weighted=True)
@@ -596,6 +598,7 @@ class WeightedSolver:
         dev = self.device.index
         wx, wy, lam = (_weight(w, self.H, self.W, dev) for w in (wx, wy, data_weight))
         self._operator = None
+        self._planes = False
         _set_operator(self.grid, wx, wy, lam, fixed)
         self.grid.mg_prepare(self.SWEEPS)
         self._operator = (wx, wy, lam, fixed)
@@ -649,6 +652,27 @@ class WeightedSolver:
         wx, wy, lam = (_weight(w, self.H, self.W, dev) for w in (wx, wy, data_weight))
         self.grid.refresh_weights_tensor(wx, wy, lam)
         self._operator = (wx, wy, lam, self._operator[3])
+        self._generation += 1
+
+    def reserve_constraints(self):
+        """Before set_operator: keep the handle's constraint planes whether or not the operator fixes a pixel
+        (capi.Grid.reserve_constraints), so that refresh_constraints may give it a fixed set later.  Results are unchanged
+        bit for bit; 24 bytes per pixel and operator.  Host state only."""
+        self.grid.reserve_constraints(True)
+
+    def refresh_constraints(self, wx, wy, data_weight=None, fixed=None):
+        """refresh_operator with a new set of fixed pixels (fixed: as set_operator's, None: no pixel fixed), enqueued on
+        torch's current stream (capi.Grid.refresh_constrained_tensor): no synchronisation and no allocation on the handle,
+        so a mask per frame, sample or brush stroke can sit in the same torch.cuda.graph as the solve.  Needs the
+        constraint planes: reserve_constraints() before set_operator, or a set_operator whose mask fixed a pixel.  The kind
+        of the operator and every mode stay.  Nothing is raised for bad weights, as in refresh_operator."""
+        if self._operator is None:
+            raise RuntimeError("WeightedSolver: set_operator first")
+        dev = self.device.index
+        wx, wy, lam = (_weight(w, self.H, self.W, dev) for w in (wx, wy, data_weight))
+        self.grid.refresh_constrained_tensor(wx, wy, lam, fixed)
+        self._operator = (wx, wy, lam, fixed)
+        self._planes = True
         self._generation += 1
 
     def solve_grad(self, gx, gy, f, values=None, x0=None, report=None, adjoint_report=None, *, wx=None, wy=None, data_weight=None):
@@ -737,7 +761,10 @@ def _persistent_function():
             g = solver.grid
             wx, wy, lam, fixed = inputs["wx"], inputs["wy"], inputs["lam"], ctx.fixed
             if solver._generation != ctx.generation:       # the handle holds a later refresh's values: back to this solve's
-                solver.refresh_operator(wx, wy, lam)
+                if solver._planes:                         # ... and perhaps a later mask: weights and mask
+                    solver.refresh_constraints(wx, wy, lam, fixed)
+                else:
+                    solver.refresh_operator(wx, wy, lam)
                 ctx.generation = solver._generation
             need = list(ctx.needs_input_grad[:4]) + list(ctx.needs_input_grad[5:8])
             want = tuple(n for n, yes in zip(names, need) if yes)

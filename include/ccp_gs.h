@@ -1135,6 +1135,50 @@ int ccp_grid_refresh_weights_device(ccp_grid *g, const ccp_device_array *wx, con
                                     const ccp_device_array *lambda);
 int ccp_grid_operator_status(ccp_grid *g, int32_t *status);
 
+/* ---- Changing the fixed pixels of a weighted operator by enqueue only ----------------------------------------------------------
+ * Sparse anchors that differ per frame, a random hole per training sample, a brush that pins pixels, a mask per image of a
+ * mini-batch: the SET of fixed pixels changes as often as the weights do.  It lives only in values -- the sign of the stored
+ * lambda plane, the dead rows of the fixed pixels, the three constraint planes ce, cs, lambda' -- and the hierarchy's shape
+ * depends on the canvas alone, so it can be replaced as the weights are: by launches.
+ *
+ * ccp_grid_reserve_constraints(g, on): a sticky flag of a single-block weighted handle, off by default.  Host state only:
+ * nothing is enqueued, it takes effect at the next ccp_grid_set_weights_* call and does not drop an installed operator.
+ * While it is on, every setter allocates and KEEPS the three constraint planes of every set -- shared or per-channel
+ * operators, with a mask or without one (no mask is the all-zero mask), and even when no pixel is fixed -- and the handle
+ * runs as one with fixed pixels: lambda' feeds the hierarchy, the right-hand side takes the path that reads ce and cs.
+ *   Contract: every result of a reserved handle equals the unreserved handle's bit for bit -- the planes d, we, ws, lambda,
+ *   the levels, b, x, iterations, the report, the adjoint outputs, ccp_grid_constraint_info -- by the argument made above for
+ *   a set without fixed pixels beside one that has some (ce = cs = 0, lambda' = lambda).  Cost: 24 bytes per pixel and set.
+ *   A NULL handle: CCP_ERR_BAD_ARG; a handle that is not weighted, or a row block: CCP_ERR_UNSUPPORTED.
+ *
+ * ccp_grid_refresh_constrained_device is ccp_grid_refresh_weights_device with a new fixed set.  fixed: U8, F32 or F64,
+ * != 0 is fixed, as the setters read it; H x W for a shared operator, H x W x channels for one operator per channel
+ * (stride_c 0 broadcasts); NULL is the empty set.  Launches on the handle's stream only: no allocation, no host
+ * synchronisation, no copy to or from host memory and no memset, so it may be issued while the stream is being captured.
+ * It returns CCP_OK and leaves its verdict in the operator status word, the same three CCP_OPERATOR_* bits: the census runs
+ * on the new planes, so a fixed pixel under CCP_MG_NULLSPACE_CONSTANT yields CCP_OPERATOR_NOT_FLOATING.  A refused call
+ * poisons the values, never the marks (a failed lambda is stored +0.0 at a free pixel, a fixed pixel holds -1): the next
+ * good refresh of either kind restores the operator.
+ *   Precondition: that of ccp_grid_refresh_weights_device, plus: the three constraint planes exist, because they were
+ *   reserved or because the setter's mask had a fixed pixel.  Otherwise CCP_ERR_STATE with nothing enqueued.  The views
+ *   are checked as the setters check them: CCP_ERR_BAD_ARG before anything is enqueued.
+ *   Postcondition, bit for bit: the handle holds everything that ccp_grid_set_weights_constrained_device (or
+ *   ccp_grid_set_weights_per_channel_device) with the same four views followed by ccp_grid_mg_prepare forms on a fresh
+ *   reserved handle with the same options -- the level-0 planes, ce, cs, lambda', every coarse level, the float copies, the
+ *   line smoother's inputs, the census verdict -- so every later call equals that handle's bit for bit: the assembly, the
+ *   enqueue, relative and synchronous solves, ccp_grid_mg_apply, ccp_grid_b_from_x, ccp_grid_residual_norm2, the adjoint
+ *   begin and the adjoint pass.  A following ccp_grid_refresh_weights_device keeps the NEW set: it reads the marks this
+ *   call wrote.
+ *   Counts: ccp_grid_constraint_info[_channel] then reports all three counts of the last refresh that ran, a replayed one
+ *   included: the fixed pixels too are counted on the device, in words that only this call clears and counts into and
+ *   that a setter invalidates, and all are read back at every call (one wait).
+ *   Which planes exist does not change under a refresh, nor does the operator's kind or any mode: a recorded
+ *   ccp_grid_assemble_constrained_rhs_device has its path chosen at record time by whether the planes exist.
+ * Out of scope: the kind, the row-block calls, the C++ facades.  Additive: the ABI version does not change. */
+int ccp_grid_reserve_constraints(ccp_grid *g, int32_t on);
+int ccp_grid_refresh_constrained_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy,
+                                        const ccp_device_array *lambda, const ccp_device_array *fixed);
+
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
 int ccp_grid_last_timing(ccp_grid *g, float *milliseconds, int32_t *kernel_launches);

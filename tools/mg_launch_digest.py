@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Launch digest of the multigrid PCG in its five modes, to compare two builds of the library (NOTES §R30.1).
 
-  mg_launch_digest.py --list                   the 10 case names
+  mg_launch_digest.py --list                   the 14 case names
   mg_launch_digest.py run CASE OUT.json        one call with the library CCP_GS_LIB names; sha256 of x per channel and the
                                                reports' bytes go to OUT.json.  Run it under `rocprofv3 --kernel-trace
                                                --output-format csv -d ROOT/trace/CASE/{parent,new} -o t --`, in a fresh
@@ -10,7 +10,10 @@
                                                the result bytes of the two libraries
 
 Cases: weighted 70x40, C = 3, rescaled, screened weights (floating ones in the constant mode); ccp_grid_mg_conjugate_gradient
-with cap 17 and epsilon 0, and ccp_grid_mg_apply, in the modes f64 (sequential, point), f32, batched, line and constant."""
+with cap 17 and epsilon 0, and ccp_grid_mg_apply, in the modes f64 (sequential, point), f32, batched, line and constant; and,
+in the modes f64 and f32, `refresh` (ccp_grid_mg_prepare, ccp_grid_refresh_weights_device with other weights, then the same
+synchronous solve) and `enqueue` (ccp_grid_mg_prepare, then ccp_grid_mg_conjugate_gradient_enqueue with cap 17).  These two
+need torch for their device tensors."""
 import csv, glob, hashlib, json, os, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
@@ -21,7 +24,7 @@ MODES = {"f64": {}, "f32": {"precision": "f32"}, "batched": {"channels": "batche
 
 
 def cases():
-    return [f"{m}_{op}" for m in MODES for op in ("pcg", "apply")]
+    return [f"{m}_{op}" for m in MODES for op in ("pcg", "apply")] + [f"{m}_{op}" for m in ("f64", "f32") for op in ("refresh", "enqueue")]
 
 
 def run(name, out_path):
@@ -39,9 +42,24 @@ def run(name, out_path):
     g.randomize_x(1234, 0.0, 255.0)
     g.b_from_x()
     g.randomize_x(1235, 0.0, 255.0)
-    reps = g.mg_conjugate_gradient(0.0, 17, 0) if op == "pcg" else g.mg_apply(0)
+    if op in ("refresh", "enqueue"):
+        import torch
+        g.mg_prepare(0)
+    if op == "refresh":
+        w2 = [torch.from_numpy(rng.uniform(0.5, 2.0, (H, W))).cuda() for _ in range(2)]
+        g.refresh_weights_tensor(w2[0], w2[1], torch.full((H, W), 1e-2, dtype=torch.float64, device="cuda"))
+    if op == "enqueue":
+        report = torch.zeros(C, 6, dtype=torch.float64, device="cuda")
+        g.mg_conjugate_gradient_enqueue(0.0, 17, 0, report)
+        torch.cuda.synchronize()
+        reps = None
+        enqueue_report = report.cpu().numpy()[:, :3]
+    else:
+        reps = g.mg_conjugate_gradient(0.0, 17, 0) if op in ("pcg", "refresh") else g.mg_apply(0)
     xs = [g.get_x(c) for c in range(C)]
     rep = np.array([[r.iterations, r.converged, r.last_l1_step] for r in reps or []], dtype=np.float64)
+    if op == "enqueue":
+        rep = np.ascontiguousarray(enqueue_report, dtype=np.float64)
     g.close()
     with open(out_path, "w") as f:
         json.dump({"case": name, "lib": os.environ.get("CCP_GS_LIB", "default"), "x_sha256": [hashlib.sha256(x.tobytes()).hexdigest() for x in xs],
