@@ -302,7 +302,10 @@ inline FusedPlan fused_plan(const FusedPlanInput &in, const FusedPassKind &k)
         P.wx0 = P.ns_left * U;
         P.wx1 = (P.n_strips - P.ns_right) * U;
         P.n_wide = (T == kWideT && P.any_plain) ? (P.wx1 - P.wx0 + wide_useful_px(T) - 1) / wide_useful_px(T) : 0;
-        P.wide = !k.multi && T == kWideT && in.wide && k.l1 == 0 && !P.edge && P.any_plain && P.n_wide > 0;
+        // (a row stride the wide march cannot step by — wide_rows_stride_ok, an image millions of pixels wide — keeps the
+        // 128-px strips and their descriptor per row)
+        P.wide = !k.multi && T == kWideT && in.wide && k.l1 == 0 && !P.edge && P.any_plain && P.n_wide > 0 &&
+                 wide_rows_stride_ok(in.g.pitch * 16L);
         if (P.wide) fused_wide_interior(in, P);
     }
     P.grid_x = (unsigned)((P.n_strips + kTileWaves - 1) / kTileWaves);

@@ -10,7 +10,10 @@
 //     The ring is indexed by row, so b is never shifted.  LDS instructions of one wave complete in order: no barrier,
 //     no wait on another wave — one wavefront is still one worker;
 //   * the ring's slot of a row is (row - base) mod kWideRing, a compile-time constant in every unrolled step because
-//     the trip loop is unrolled over one whole turn of the ring (kWideRing / G trips).
+//     the trip loop is unrolled over one whole turn of the ring (kWideRing / G trips);
+//   * for the same reason a turn's rows are compile-time multiples of the row stride away from the turn's first row:
+//     the wave builds its buffer descriptors once per turn and plane, not once per row (WideTurn below).  It runs alone
+//     on its SIMD, where every scalar instruction of a descriptor per row was issue time nothing else filled.
 // It runs only the interior: the columns [wx0, wx1) that the narrow ordinary strips would store (the narrow side
 // strips stay border tiles in k_fused_border) and the rows between the top and bottom border chunks.  Those rows are one
 // contiguous range, and nothing here needs the chunk height: the host cuts them into row SEGMENTS sized to the device's
@@ -49,7 +52,8 @@ struct WideCtx {
     d2 *ring;              // this lane's pair in slot 0, red half: ring[slot * 2 * kWave + c * kWave]
 };
 
-// row q: x red, x black, b red, b black (pairs); rows outside [m0, m1) read 0
+// row q: x red, x black, b red, b black (pairs); rows outside [m0, m1) read 0.  One descriptor per row (row_rsrc): the
+// four rows the march starts with, before its first turn.
 __device__ __forceinline__ void wide_load_row(const WideCtx &cx, const Geom &g, int q, d2 (&dst)[4])
 {
     const bool exists = q >= cx.m0 && q < cx.m1;
@@ -60,12 +64,92 @@ __device__ __forceinline__ void wide_load_row(const WideCtx &cx, const Geom &g, 
     dst[3] = buf_load2(rbb, cx.ld_k);
 }
 
+// The rows of one ring turn (ccp_wide_plan.hpp, wide_turn_rows): one descriptor per plane for the whole turn, rebuilt
+// between turns from wave-uniform values, instead of one per row.  A row of the turn is a compile-time number of row
+// strides from the descriptor's base, added to the lane's offset by one v_add_u32.
+struct WideTurn {
+    __amdgpu_buffer_rsrc_t rx, rbb, ro;   // x in and b over the rows the turn loads, x out over the rows it stores
+    unsigned stride;                      // bytes per row (both colours)
+    int st_skip;                          // rows of the store window before ra
+};
+
+// descriptor of `records` bytes at row `row` of `plane`; the inputs go through readfirstlane, so that the compiler
+// knows the descriptor to be wave-uniform and puts no waterfall loop around the memory instructions that use it
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wide_window_rsrc(const double *plane, const Geom &g, int row, unsigned records)
+{
+    const unsigned long long a = (unsigned long long)(plane + (long)row * 2 * g.pitch);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
+    const int n = __builtin_amdgcn_readfirstlane((int)records);
+    return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, n, 0x00020000);
+}
+
+// the turn whose first step has newest row fb: it loads rows [fb + 2G, fb + 2G + kWideRing) and stores rows
+// [fb - 2T, fb - 2T + kWideRing).  A loaded row is never before m0 (fb >= base >= m0 - 1), so only the stores skip rows.
+template <int T>
+__device__ __forceinline__ WideTurn wide_turn_begin(const WideCtx &cx, const Geom &g, int fb)
+{
+    constexpr int G = 2;
+    static_assert(kWideLoadAhead == 2 * G, "ccp_wide_plan.hpp describes this march");
+    WideTurn t;
+    t.stride = (unsigned)g.pitch * 16u;
+    // The stride is the same in every turn, and the compiler, seeing that, would form lane offset + k x stride for all
+    // k once, ahead of the march, in 40 registers the window needs.  Taken through an empty asm it is a new value per
+    // turn: each sum is formed where it is used and dies with its memory instruction.
+    asm volatile("" : "+s"(t.stride));
+#if defined(CCP_WIDE_PROBE_DESC)
+    // timing-only experiment (results are wrong): every row of the turn is the turn's first row, clamped into the
+    // rows that exist, and exists; the per-row scalar work is gone from the instruction stream
+    const int ql = min(max(fb + 2 * G, cx.m0), cx.m1 - 1), qs = min(max(fb - 2 * T, cx.ra), cx.rb - 1);
+    t.rx = wide_window_rsrc(cx.xin, g, ql, t.stride);
+    t.rbb = wide_window_rsrc(cx.bb, g, ql, t.stride);
+    t.ro = wide_window_rsrc(cx.xout, g, qs, t.stride);
+    t.st_skip = 0;
+#else
+    const WideTurnRows ld = wide_turn_rows(fb + 2 * G, cx.m0, cx.m1, t.stride);
+    const WideTurnRows st = wide_turn_rows(fb - 2 * T, cx.ra, cx.rb, t.stride);
+    t.rx = wide_window_rsrc(cx.xin, g, ld.first, ld.records);
+    t.rbb = wide_window_rsrc(cx.bb, g, ld.first, ld.records);
+    t.ro = wide_window_rsrc(cx.xout, g, st.first, st.records);
+    t.st_skip = st.skip;
+#endif
+    return t;
+}
+
+// byte offset of the turn's k-th loaded / stored row from its descriptor's base
+__device__ __forceinline__ unsigned wide_ld_row(const WideTurn &t, int k)
+{
+#if defined(CCP_WIDE_PROBE_DESC)
+    return 0u;
+#else
+    return wide_row_offset(k, 0, t.stride);      // (no loaded row of a turn is before m0: wide_turn_begin)
+#endif
+}
+__device__ __forceinline__ unsigned wide_st_row(const WideTurn &t, int k)
+{
+#if defined(CCP_WIDE_PROBE_DESC)
+    return 0u;
+#else
+    return wide_row_offset(k, t.st_skip, t.stride);
+#endif
+}
+
+// the k-th row of the turn's load window: x red, x black, b red, b black (pairs); rows from m1 on read 0
+__device__ __forceinline__ void wide_load_turn_row(const WideCtx &cx, const WideTurn &t, int k, d2 (&dst)[4])
+{
+    const unsigned row = wide_ld_row(t, k);
+    dst[0] = buf_load2(t.rx, cx.ld_r + row);
+    dst[1] = buf_load2(t.rx, cx.ld_k + row);
+    dst[2] = buf_load2(t.rbb, cx.ld_r + row);
+    dst[3] = buf_load2(t.rbb, cx.ld_k + row);
+}
+
 __host__ __device__ constexpr int wide_slot(int k) { return ((k % kWideRing) + kWideRing) % kWideRing; }
 
 // One march step (fused_step's kStepFast): newest row f = fb + i, half-sweep h on row f - h, then the store of row
-// f - 2T.  PH: ring slot of row fb.
+// f - 2T, the (PH + i)-th row of the turn's store window.  PH: ring slot of row fb.
 template <int T, bool STORE_RED, int NT, int PH>
-__device__ __forceinline__ void wide_step(d2 (&wr)[NT], d2 (&wk)[NT], const WideCtx &cx, const Geom &g, int f, int i)
+__device__ __forceinline__ void wide_step(d2 (&wr)[NT], d2 (&wk)[NT], const WideCtx &cx, const WideTurn &t, int i)
 {
     using Win = FusedWindow<T, 2>;
     constexpr int HS = Win::HS;
@@ -90,11 +174,10 @@ __device__ __forceinline__ void wide_step(d2 (&wr)[NT], d2 (&wk)[NT], const Wide
         if (c) wk[sr] = nv; else wr[sr] = nv;
     }
     {
-        const int r = f - HS;
         const int sr = Win::slot(i, HS);
-        const __amdgpu_buffer_rsrc_t ro = row_rsrc(cx.xout, g, r, r >= cx.ra && r < cx.rb);
-        if constexpr (STORE_RED) buf_store2(wr[sr], ro, cx.st_r);
-        buf_store2(wk[sr], ro, cx.st_k);
+        const unsigned row = wide_st_row(t, PH + i);
+        if constexpr (STORE_RED) buf_store2(wr[sr], t.ro, cx.st_r + row);
+        buf_store2(wk[sr], t.ro, cx.st_k + row);
     }
     __builtin_amdgcn_sched_barrier(0);
 }
@@ -110,20 +193,21 @@ __device__ __forceinline__ void wide_place(d2 (&wr)[NT], d2 (&wk)[NT], const Wid
 }
 
 // One trip (G = 2 steps) of the two-landing-pair march (fused_wave, kFusedLand = 2): issue the loads of the rows two
-// trips ahead into LANDING, run the steps, shift the window, move the rows of ARRIVED in.  PH: ring slot of row fb.
+// trips ahead into LANDING, run the steps, shift the window, move the rows of ARRIVED in.  PH: ring slot of row fb,
+// and the place of the trip's rows in the turn's load and store windows.
 template <int T, bool STORE_RED, int NT, int PH>
-__device__ __forceinline__ void wide_trip(d2 (&wr)[NT], d2 (&wk)[NT], const WideCtx &cx, const Geom &g, int fb,
+__device__ __forceinline__ void wide_trip(d2 (&wr)[NT], d2 (&wk)[NT], const WideCtx &cx, const WideTurn &t,
                                           d2 (&landing)[2][4], const d2 (&arrived)[2][4])
 {
     constexpr int G = 2;
     using Win = FusedWindow<T, G>;
 #pragma unroll
-    for (int i = 0; i < G; ++i) wide_load_row(cx, g, fb + 2 * G + i, landing[i]);
+    for (int i = 0; i < G; ++i) wide_load_turn_row(cx, t, PH + i, landing[i]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < G; ++i) {
-        if (i == 0) wide_step<T, STORE_RED, NT, PH>(wr, wk, cx, g, fb, 0);
-        else wide_step<T, STORE_RED, NT, PH>(wr, wk, cx, g, fb + 1, 1);
+        if (i == 0) wide_step<T, STORE_RED, NT, PH>(wr, wk, cx, t, 0);
+        else wide_step<T, STORE_RED, NT, PH>(wr, wk, cx, t, 1);
     }
 #pragma unroll
     for (int s = 0; s + G < NT; ++s) {
@@ -139,13 +223,13 @@ __device__ __forceinline__ void wide_trip(d2 (&wr)[NT], d2 (&wk)[NT], const Wide
 // are used, and the wave waits for every row it loads.  Trips past the end of the march store nothing (the rows are
 // outside [ra, rb)) and load zeros (outside [m0, m1)).
 template <int T, bool STORE_RED, int NT, int PH>
-__device__ __forceinline__ void wide_turn(d2 (&wr)[NT], d2 (&wk)[NT], const WideCtx &cx, const Geom &g, int fb,
+__device__ __forceinline__ void wide_turn(d2 (&wr)[NT], d2 (&wk)[NT], const WideCtx &cx, const WideTurn &t,
                                           d2 (&la)[2][4], d2 (&lb)[2][4])
 {
     if constexpr (PH < kWideRing) {
-        if constexpr ((PH / 2) % 2 == 0) wide_trip<T, STORE_RED, NT, PH>(wr, wk, cx, g, fb, la, lb);
-        else wide_trip<T, STORE_RED, NT, PH>(wr, wk, cx, g, fb, lb, la);
-        wide_turn<T, STORE_RED, NT, PH + 2>(wr, wk, cx, g, fb + 2, la, lb);
+        if constexpr ((PH / 2) % 2 == 0) wide_trip<T, STORE_RED, NT, PH>(wr, wk, cx, t, la, lb);
+        else wide_trip<T, STORE_RED, NT, PH>(wr, wk, cx, t, lb, la);
+        wide_turn<T, STORE_RED, NT, PH + 2>(wr, wk, cx, t, la, lb);
     }
 }
 
@@ -174,10 +258,11 @@ __device__ __forceinline__ void fused_wave_wide(const double *__restrict__ xin, 
     cx.st_r = (STORE_RED && col_store) ? cx.ld_r : kLaneOut;
     cx.st_k = col_store ? cx.ld_k : kLaneOut;
     cx.ra = ra; cx.rb = rb;
-    cx.m0 = max(ra - HS, 0);
-    cx.m1 = min(rb + HS, g.local_rows);
-    const int base = cx.m0 - ((g.y0 + cx.m0) & 1);          // even image row: compile-time colour parity per step
-    const int f_end = rb - 1 + HS;
+    const WideMarch mar = wide_march(ra, rb, g.local_rows, g.y0, T);
+    cx.m0 = mar.m0;
+    cx.m1 = mar.m1;
+    const int base = mar.base;                               // even image row: compile-time colour parity per step
+    const int f_end = mar.f_end;
 
     d2 wr[NT], wk[NT];
     d2 la[G][4], lb[G][4];
@@ -194,7 +279,10 @@ __device__ __forceinline__ void fused_wave_wide(const double *__restrict__ xin, 
     for (int i = 0; i < G; ++i) wide_load_row(cx, g, base + G + i, lb[i]);
 #pragma unroll
     for (int i = 0; i < G; ++i) wide_place(wr, wk, cx, Win::slot(i, 0), i, la[i]);
-    for (int fb = base; fb <= f_end; fb += kWideRing) wide_turn<T, STORE_RED, NT, 0>(wr, wk, cx, g, fb, la, lb);
+    for (int fb = base; fb <= f_end; fb += kWideRing) {
+        const WideTurn t = wide_turn_begin<T>(cx, g, fb);
+        wide_turn<T, STORE_RED, NT, 0>(wr, wk, cx, t, la, lb);
+    }
 }
 
 // grid = ceil(wide_tiles / 4) blocks; block = 4 waves = 4 consecutive tiles.  Tile t = (channel * wide_nseg + segment) *

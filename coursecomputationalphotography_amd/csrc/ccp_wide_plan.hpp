@@ -1,5 +1,6 @@
 // ccp_wide_plan.hpp — how the interior rows of a wide depth-8 pass (ccp_grid_fused_wide.hpp) are cut into row
-// segments.  Host-only arithmetic, no HIP: tests/cpp/wide_plan_check.cpp includes this header alone.
+// segments, and how a tile reaches its rows (the rows of one ring turn, at the end).  Host-only arithmetic, no HIP:
+// tests/cpp/wide_plan_check.cpp and tests/cpp/wide_rows_check.cpp include this header alone.
 //
 // One wave of k_fused_sweep_wide marches one (wide strip, row segment) tile, and its 40 KB ring of b/4 rows leaves room
 // for one wave per SIMD: the device runs `slots` = 4 x CUs tiles at a time.  A tile of h stored rows marches h + 4T
@@ -92,6 +93,66 @@ CCP_WIDE_PLAN_FN void wide_segment_rows(int y0, int y1, int h, int s, int &ra, i
 {
     ra = y0 + s * h;
     rb = ra + h < y1 ? ra + h : y1;
+}
+
+// ---- the rows of one ring turn --------------------------------------------------------------------------------------
+// A turn of the march (kWideRing steps, fully unrolled) touches one WINDOW of kWideRing consecutive rows per plane:
+// it loads rows [fb + 2G, fb + 2G + kWideRing) of x and b and stores rows [fb - 2T, fb - 2T + kWideRing) of x, fb the
+// newest row of its first step.  One buffer descriptor per plane and turn covers the window: its base is the window's
+// first row w0 (never dereferenced where that row does not exist), and its num_records ends at the last row that exists.
+// The window's k-th row (k a compile-time constant of the unrolled step) is reached by the byte offset k x stride; a row
+// before the first existing one gets kWideRowOut instead, which no descriptor reaches.  So the range check alone selects
+// exactly the rows of [lo, hi), as one descriptor per row did.
+//
+// A lane adds its own offset inside the row (< stride) or kLaneOut = 2^31 (ccp_grid_fused.hpp).  With
+// (kWideRing + 4) x stride <= 2^30 (wide_rows_stride_ok) every sum stays below 2^32 and every num_records at or below
+// kWideRowOut: nothing wraps, whatever the segment height, because the offsets restart from 0 every turn.
+struct WideMarch {
+    int m0, m1;    // rows the tile loads: its rows and 2T rows of halo either side, clipped to the rows of the block
+    int base;      // newest row of the first step: m0, or m0 - 1 where that is the even image row (it does not exist then)
+    int f_end;     // newest row of the step that stores row rb - 1; turns begin at base, base + kWideRing, ... <= f_end
+};
+// the march of a tile that stores rows [ra, rb) of a block of local_rows rows whose row 0 is image row y0, depth T
+CCP_WIDE_PLAN_FN WideMarch wide_march(int ra, int rb, int local_rows, int y0, int T)
+{
+    WideMarch m;
+    m.m0 = ra - 2 * T > 0 ? ra - 2 * T : 0;
+    m.m1 = rb + 2 * T < local_rows ? rb + 2 * T : local_rows;
+    m.base = m.m0 - ((y0 + m.m0) & 1);
+    m.f_end = rb - 1 + 2 * T;
+    return m;
+}
+constexpr int kWideLoadAhead = 4;               // a turn loads the rows [fb + 4, fb + 4 + kWideRing): two trips of G = 2 ahead
+
+constexpr unsigned kWideRowOut = 0x40000000u;
+constexpr int kWideRowSpan = kWideRing + 4;     // row strides the guard allows for: the window and the rows in flight around it
+
+CCP_WIDE_PLAN_FN bool wide_rows_stride_ok(long stride_bytes)
+{
+    return stride_bytes >= 0 && stride_bytes <= (long)(kWideRowOut / kWideRowSpan);
+}
+
+struct WideTurnRows {
+    int first;          // row at the descriptor's base: the window's first row
+    int skip;           // rows of the window before the first one that exists: they take kWideRowOut
+    unsigned records;   // bytes from the base to the end of the last row of the window that exists (0: none)
+};
+
+// window [w0, w0 + kWideRing), existing rows [lo, hi), stride in bytes (wide_rows_stride_ok)
+CCP_WIDE_PLAN_FN WideTurnRows wide_turn_rows(int w0, int lo, int hi, unsigned stride)
+{
+    const int below = lo - w0, upto = hi - w0;
+    WideTurnRows r;
+    r.first = w0;
+    r.skip = below < 0 ? 0 : below > kWideRing ? kWideRing : below;
+    r.records = (unsigned)(upto < 0 ? 0 : upto > kWideRing ? kWideRing : upto) * stride;
+    return r;
+}
+
+// byte offset of the window's k-th row from the descriptor's base
+CCP_WIDE_PLAN_FN unsigned wide_row_offset(int k, int skip, unsigned stride)
+{
+    return k >= skip ? (unsigned)k * stride : kWideRowOut;
 }
 
 }  // namespace ccp
