@@ -95,7 +95,7 @@ ABI_SYMBOLS = (
     "ccp_grid_constraint_info_channel",
     "ccp_grid_mg_prepare", "ccp_grid_mg_conjugate_gradient_enqueue", "ccp_grid_mg_conjugate_gradient_enqueue_relative",
     "ccp_grid_refresh_weights_device", "ccp_grid_operator_status",
-    "ccp_grid_reserve_constraints", "ccp_grid_refresh_constrained_device",
+    "ccp_grid_reserve_constraints", "ccp_grid_refresh_constrained_device", "ccp_grid_reweight_device",
     "ccp_grid_set_mask_device", "ccp_mask_erode_cross_device", "ccp_panorama_begin_device", "ccp_panorama_add_device",
     "ccp_panorama_finish_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
@@ -149,6 +149,27 @@ class AdjointInputs(C.Structure):
 class AdjointOutputs(C.Structure):
     """ccp_adjoint_outputs: one ccp_device_array pointer per gradient (NULL: not asked for)."""
     _fields_ = [(n, C.POINTER(DeviceArray)) for n in ADJOINT_OUTPUTS]
+
+
+# ccp_grid_reweight_device (ccp_gs.h, "Reweighting a weighted operator from the solution"): names -> CCP_REWEIGHT_*
+REWEIGHT_PENALTIES = {"charbonnier": 0, "huber": 1, "reciprocal": 2}
+REWEIGHT_COUPLINGS = {"edge": 0, "pixel": 1}
+REWEIGHT_VIEWS = ("u", "gx", "gy", "base_wx", "base_wy", "lambda", "out_wx", "out_wy")
+
+
+def reweight_ids(penalty, coupling):
+    """(CCP_REWEIGHT_* penalty, coupling) of "charbonnier" | "huber" | "reciprocal" and "edge" | "pixel": ValueError otherwise."""
+    if penalty not in REWEIGHT_PENALTIES:
+        raise ValueError(f"penalty must be one of {sorted(REWEIGHT_PENALTIES)}, not {penalty!r}")
+    if coupling not in REWEIGHT_COUPLINGS:
+        raise ValueError(f"coupling must be one of {sorted(REWEIGHT_COUPLINGS)}, not {coupling!r}")
+    return REWEIGHT_PENALTIES[penalty], REWEIGHT_COUPLINGS[coupling]
+
+
+class Reweight(C.Structure):
+    """ccp_reweight: the penalty, the coupling, scale, epsilon and one ccp_device_array pointer per view (NULL: absent)."""
+    _fields_ = [("penalty", C.c_int32), ("coupling", C.c_int32), ("scale", C.c_double), ("epsilon", C.c_double)] + \
+               [(n, C.POINTER(DeviceArray)) for n in REWEIGHT_VIEWS]
 
 
 class PanoramaState(C.Structure):
@@ -320,6 +341,7 @@ def load() -> C.CDLL:
     L.ccp_grid_operator_status.argtypes = [vp, C.POINTER(i32)]
     L.ccp_grid_reserve_constraints.argtypes = [vp, i32]
     L.ccp_grid_refresh_constrained_device.argtypes = [vp, vp, vp, vp, vp]
+    L.ccp_grid_reweight_device.argtypes = [vp, C.POINTER(Reweight)]
     L.ccp_grid_mg_level_channel.argtypes = [vp, i32, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
     L.ccp_grid_constraint_info_channel.argtypes = [vp, i32, vp, vp, vp]
     L.ccp_grid_adjoint_begin_device.argtypes = [vp, da]
@@ -1327,6 +1349,37 @@ class Grid:
             arrs.append(None if fixed is None else self._mask_array(fixed))
         refs = [None if a is None else C.byref(a) for a in arrs]
         self._on_stream(lambda: self.L.ccp_grid_refresh_constrained_device(self.h, *refs), "ccp_grid_refresh_constrained_device")
+
+    def reweight_tensor(self, penalty, coupling, scale, epsilon, u=None, gx=None, gy=None, base_wx=None, base_wy=None, lam=None,
+                        out_wx=None, out_wy=None):
+        """refresh_weights_tensor with weights formed on the device from the solution (ccp_grid_reweight_device): per edge
+        w = base * (scale * phi(q)), q the squared residual gx - (uE - u) (gy, uS to the south) summed over the channels --
+        all of them on a shared operator, channel c alone on an operator per channel.  penalty: "charbonnier"
+        (phi = 1 / sqrt(q + epsilon^2)), "huber" (1 / max(sqrt(q), epsilon)) or "reciprocal" (1 / (sqrt(q) + epsilon));
+        coupling: "edge" (each edge from its own q) or "pixel" (both forward edges of a pixel from q_x + q_y); an unknown
+        name is a ValueError before any tensor is looked at.  u: None reads the handle's x, else a uint8 / float32 / float64
+        H x W x channels tensor (H x W: every channel's); gx, gy: float32 H x W x channels or None (0); base_wx, base_wy,
+        lam: as refresh_weights_tensor's wx, wy, lam (None: 1, 1, 0); out_wx, out_wy: float32 / float64 tensors, H x W on a
+        shared operator and H x W x channels on one per channel, that receive the weights formed (not overlapping any
+        input).  Enqueued on torch's current stream: no allocation, no synchronisation; the verdict is operator_status()."""
+        ids = reweight_ids(penalty, coupling)
+        torch = self._torch()
+        floats, any_ = (torch.float32, torch.float64), (torch.uint8, torch.float32, torch.float64)
+        named = ((base_wx, "base_wx"), (base_wy, "base_wy"), (lam, "lam"))
+        per_channel = self.operator_channels() > 1 or (self.C == 1 and any(isinstance(t, torch.Tensor) and t.dim() == 3
+                                                                           for t in (base_wx, base_wy, lam, out_wx, out_wy)))
+        arrs = {"u": self._channel_array(u, "u", any_),
+                "gx": None if gx is None else self._hwc(gx, "gx", (torch.float32,))[0],
+                "gy": None if gy is None else self._hwc(gy, "gy", (torch.float32,))[0]}
+        if per_channel:
+            arrs.update({n: self._channel_array(t, n, floats) for t, n in named})
+            arrs.update({n: self._channel_array(t, n, floats, output=True) for t, n in ((out_wx, "out_wx"), (out_wy, "out_wy"))})
+        else:
+            arrs.update({n: self._weight_array(t, n) for t, n in named})
+            arrs.update({n: None if t is None else self._plane_out(t, n) for t, n in ((out_wx, "out_wx"), (out_wy, "out_wy"))})
+        arrs["lambda"] = arrs.pop("lam")
+        how = Reweight(ids[0], ids[1], float(scale), float(epsilon), *[None if arrs[n] is None else C.pointer(arrs[n]) for n in REWEIGHT_VIEWS])
+        self._on_stream(lambda: self.L.ccp_grid_reweight_device(self.h, C.byref(how)), "ccp_grid_reweight_device")
 
     def operator_status(self) -> int:
         """The operator status word of the last refresh_weights_tensor (0: good; 1: a bad weight, 2: out of float range in

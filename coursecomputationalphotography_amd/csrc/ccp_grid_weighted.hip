@@ -352,6 +352,85 @@ int refresh_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_arr
     return mg_refresh(g);
 }
 
+AdjOut adj_out(const ccp_device_array *a);                               // (with the adjoint pass, below)
+
+static_assert(kPhiCharbonnier == CCP_REWEIGHT_CHARBONNIER && kPhiHuber == CCP_REWEIGHT_HUBER && kPhiReciprocal == CCP_REWEIGHT_RECIPROCAL,
+              "k_weighted_reweight's PHI is the header's penalty id");
+
+// the bytes [lo, hi) a view of extents H x W x C spans
+void view_span(const ccp_device_array *a, long H, long W, long C, uintptr_t *lo, uintptr_t *hi)
+{
+    const unsigned long long last = (unsigned long long)(H - 1) * (unsigned long long)a->stride_y +
+                                    (unsigned long long)(W - 1) * (unsigned long long)a->stride_x +
+                                    (unsigned long long)(C - 1) * (unsigned long long)a->stride_c;
+    *lo = (uintptr_t)a->data;
+    *hi = *lo + (uintptr_t)((last + 1) * dtype_bytes(a->dtype));
+}
+
+// ccp_grid_reweight_device: refresh_device without a mask, the level-0 pass forming the weights instead of reading them
+int reweight_device(ccp_grid *g, const ccp_reweight *how)
+{
+    CCP_TRY(weighted_handle(g));
+    if (!how) return CCP_ERR_BAD_ARG;
+    if (how->penalty < CCP_REWEIGHT_CHARBONNIER || how->penalty > CCP_REWEIGHT_RECIPROCAL) return CCP_ERR_BAD_ARG;
+    if (how->coupling != CCP_REWEIGHT_EDGE && how->coupling != CCP_REWEIGHT_PIXEL) return CCP_ERR_BAD_ARG;
+    if (!(how->epsilon > 0.0 && how->epsilon <= DBL_MAX) || !(how->scale >= 0.0 && how->scale <= DBL_MAX)) return CCP_ERR_BAD_ARG;
+    if (!g->has_op) return CCP_ERR_STATE;                                  // (the operator's kind decides the views' extents)
+    const Geom &geo = g->geom;
+    const int C = g->desc.channels, sets = g->per_channel ? C : 1;
+    struct {
+        const ccp_device_array *a;
+        unsigned dtypes;
+        bool output;
+        int c;
+    } views[8] = {{how->u, kF32F64 | kU8, false, C}, {how->gx, kF32, false, C},          {how->gy, kF32, false, C},
+                  {how->base_wx, kF32F64, false, sets}, {how->base_wy, kF32F64, false, sets}, {how->lambda, kF32F64, false, sets},
+                  {how->out_wx, kF32F64, true, sets},   {how->out_wy, kF32F64, true, sets}};
+    for (const auto &v : views)
+        if (v.a) CCP_TRY(check_view(g, v.a, v.dtypes, v.output, 1, geo.H, geo.W, v.c));
+    // an output that shares bytes with an input would be read by the neighbours' threads while its owner writes it
+    for (int o = 6; o < 8; ++o)
+        for (int i = 0; i < 6 && views[o].a; ++i) {
+            if (!views[i].a) continue;
+            uintptr_t olo, ohi, ilo, ihi;
+            view_span(views[o].a, geo.H, geo.W, views[o].c, &olo, &ohi);
+            view_span(views[i].a, geo.H, geo.W, views[i].c, &ilo, &ihi);
+            if (olo < ihi && ilo < ohi) return CCP_ERR_BAD_ARG;
+        }
+    // from here on: launches on the handle's stream, nothing else
+    CCP_TRY(mg_refresh_begin(g, 1 + 3 * sets));
+    const long n = geo.ch_stride;
+    ReweightArgs a{};
+    a.x = g->x.p;
+    a.pitch = geo.pitch;
+    a.W = geo.W;
+    a.H = geo.H;
+    a.cpb = C / sets;
+    a.coupling = how->coupling;
+    a.scale = how->scale;
+    a.eps = how->epsilon;
+    a.u = image_view(how->u, 0.0);
+    a.gx = image_view(how->gx, 0.0);
+    a.gy = image_view(how->gy, 0.0);
+    a.bwx = image_view(how->base_wx, 1.0);
+    a.bwy = image_view(how->base_wy, 1.0);
+    a.lam = image_view(how->lambda, 0.0);
+    a.out_wx = adj_out(how->out_wx);
+    a.out_wy = adj_out(how->out_wy);
+    double *cons = g->has_fixed ? g->wcons.p : nullptr;
+    const dim3 grid = pixels(geo.W, geo.H, sets);
+    if (how->penalty == CCP_REWEIGHT_CHARBONNIER)
+        hipLaunchKernelGGL((k_weighted_reweight<kPhiCharbonnier>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
+    else if (how->penalty == CCP_REWEIGHT_HUBER)
+        hipLaunchKernelGGL((k_weighted_reweight<kPhiHuber>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
+    else
+        hipLaunchKernelGGL((k_weighted_reweight<kPhiReciprocal>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
+    CCP_HIP(hipGetLastError());
+    g->refreshed = true;
+    g->mg_nullspace.floating = -1;      // as refresh_device: the census verdict the host remembers is the old values'
+    return mg_refresh(g);
+}
+
 }  // namespace
 
 int ccp::weighted_apply(ccp_grid *g, int mode) { return mode == 0 ? weighted_apply_mode<0>(g) : weighted_apply_mode<1>(g); }
@@ -464,6 +543,11 @@ int ccp_grid_refresh_constrained_device(ccp_grid *g, const ccp_device_array *wx,
                                         const ccp_device_array *fixed)
 try {
     return refresh_device(g, wx, wy, lambda, fixed, true);
+} CCP_ABI_CATCH
+
+int ccp_grid_reweight_device(ccp_grid *g, const ccp_reweight *how)
+try {
+    return reweight_device(g, how);
 } CCP_ABI_CATCH
 
 int ccp_grid_reserve_constraints(ccp_grid *g, int32_t on)

@@ -38,6 +38,7 @@
 // the coarsening through a launcher of ccp_grid_weighted_api.hpp.  w_at and weighted_row are in ccp_grid_stencil.hpp.
 #pragma once
 
+#include "ccp_grid_adjoint.hpp"        // AdjOut, adj_store: the reweight pass's optional outputs
 #include "ccp_grid_mg.hpp"
 #include "ccp_view.hpp"
 
@@ -126,11 +127,57 @@ k_weighted_coef_fixed(ImageView wx, ImageView wy, ImageView lam, ImageView fixed
     if (threadIdx.x < 3 && tally[threadIdx.x]) atomicAdd(count + 1 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
 }
 
+// The tail of a pass that gives the installed operators new values and keeps their fixed set: pixel (x, y) of set `ch`
+// from its lambda l, its own east and south weights e, s (+0.0 where the edge is absent) and the weights of the edges from
+// the north and the west (the neighbours' s and e), which `north()` and `west()` yield where those edges exist --
+// k_weighted_refresh reads them from views, k_weighted_reweight forms them -- so that the two passes cannot drift apart:
+// the check of l, e, s, the marks from the sign of the stored lambda plane, the sums dd and lp in their order, the stores
+// (cons: null without the three planes) and the pixel's two tallies.  (The two weights arrive as callables so that
+// k_weighted_refresh keeps the instruction order, and with it the registers, it had before this function existed.)
+template <class North, class West>
+__device__ __forceinline__ void weighted_refresh_tail(double l, double e, double s, North north, West west, int x, int y, int ch, int W, int H,
+                                                      long pitch, double *op, long plane, long op_stride, double *cons, long cons_stride,
+                                                      unsigned long long *__restrict__ count, unsigned &n_dead, unsigned &n_edges)
+{
+    if (!(weight_ok(l) && weight_ok(e) && weight_ok(s))) atomicOr(count, 1ull);
+    double *o = op + (long)ch * op_stride;
+    const double *mark = o + 3 * plane;
+    const long at = w_at(pitch, x, y);
+    const bool fp = mark[at] < 0.0;
+    const bool fN = y >= 1 && mark[w_at(pitch, x, y - 1)] < 0.0, fW = x >= 1 && mark[w_at(pitch, x - 1, y)] < 0.0;
+    const bool fE = x + 1 < W && mark[w_at(pitch, x + 1, y)] < 0.0, fS = y + 1 < H && mark[w_at(pitch, x, y + 1)] < 0.0;
+    const double wN = y >= 1 ? north() : 0.0, wW = x >= 1 ? west() : 0.0;
+    double dd = l;
+    if (y >= 1) dd += wN;
+    if (x >= 1) dd += wW;
+    if (x + 1 < W) dd += e;
+    if (y + 1 < H) dd += s;
+    double lp = l;
+    if (fN) lp += wN;
+    if (fW) lp += wW;
+    if (fE) lp += e;
+    if (fS) lp += s;
+    const bool be = x + 1 < W && fp != fE, bs = y + 1 < H && fp != fS;   // edges with exactly one fixed end
+    o[at] = fp ? 0.0 : dd;
+    o[plane + at] = fp || fE ? 0.0 : e;
+    o[2 * plane + at] = fp || fS ? 0.0 : s;
+    o[3 * plane + at] = fp ? -1.0 : weight_ok(l) ? l : 0.0;
+    if (cons) {
+        double *k = cons + (long)ch * cons_stride;
+        k[at] = be ? e : 0.0;
+        k[plane + at] = bs ? s : 0.0;
+        k[2 * plane + at] = fp ? 0.0 : lp;
+    }
+    n_dead = !fp && dd == 0.0;
+    n_edges = (unsigned)be + (unsigned)bs;
+}
+
 // ccp_grid_refresh_weights_device: new values for the installed operators, the fixed set kept.  The planes of every set
 // are rewritten as k_weighted_coef_fixed forms them (which, where no pixel is fixed, are k_weighted_coef's: the same
 // sums in the same order), with one difference in where the fixed flags come from: the sign of the stored lambda plane
 // (< 0 on a fixed pixel) instead of a mask view.  cons: null when the handle has no fixed pixel (no plane is negative
 // then, and the three extra planes do not exist).
+// (All of that is weighted_refresh_tail, above.)
 // The lambda plane is rewritten in place while the neighbours' threads read it.  That is sound because the SIGN of an
 // entry never changes here: a fixed pixel's entry is stored as the -1 it holds, a free pixel's as a value that is >= 0 and
 // not NaN -- a lambda that fails the check is stored as +0.0, so a refused refresh poisons the operator's values but
@@ -151,37 +198,118 @@ k_weighted_refresh(ImageView wx, ImageView wy, ImageView lam, int W, int H, long
         const double l = lam(y, x, ch);
         const double e = x + 1 < W ? wx(y, x, ch) : 0.0;
         const double s = y + 1 < H ? wy(y, x, ch) : 0.0;
-        if (!(weight_ok(l) && weight_ok(e) && weight_ok(s))) atomicOr(count, 1ull);
-        double *o = op + (long)ch * op_stride;
-        const double *mark = o + 3 * plane;
-        const long at = w_at(pitch, x, y);
-        const bool fp = mark[at] < 0.0;
-        const bool fN = y >= 1 && mark[w_at(pitch, x, y - 1)] < 0.0, fW = x >= 1 && mark[w_at(pitch, x - 1, y)] < 0.0;
-        const bool fE = x + 1 < W && mark[w_at(pitch, x + 1, y)] < 0.0, fS = y + 1 < H && mark[w_at(pitch, x, y + 1)] < 0.0;
-        const double wN = y >= 1 ? wy(y - 1, x, ch) : 0.0, wW = x >= 1 ? wx(y, x - 1, ch) : 0.0;
-        double dd = l;
-        if (y >= 1) dd += wN;
-        if (x >= 1) dd += wW;
-        if (x + 1 < W) dd += e;
-        if (y + 1 < H) dd += s;
-        double lp = l;
-        if (fN) lp += wN;
-        if (fW) lp += wW;
-        if (fE) lp += e;
-        if (fS) lp += s;
-        const bool be = x + 1 < W && fp != fE, bs = y + 1 < H && fp != fS;   // edges with exactly one fixed end
-        o[at] = fp ? 0.0 : dd;
-        o[plane + at] = fp || fE ? 0.0 : e;
-        o[2 * plane + at] = fp || fS ? 0.0 : s;
-        o[3 * plane + at] = fp ? -1.0 : weight_ok(l) ? l : 0.0;
-        if (cons) {
-            double *k = cons + (long)ch * cons_stride;
-            k[at] = be ? e : 0.0;
-            k[plane + at] = bs ? s : 0.0;
-            k[2 * plane + at] = fp ? 0.0 : lp;
-        }
-        n_dead = !fp && dd == 0.0;
-        n_edges = (unsigned)be + (unsigned)bs;
+        weighted_refresh_tail(l, e, s, [&] { return wy(y - 1, x, ch); }, [&] { return wx(y, x - 1, ch); }, x, y, ch, W, H, pitch, op, plane,
+                              op_stride, cons, cons_stride, count, n_dead, n_edges);
+    }
+    if (n_dead) atomicAdd(&tally[0], n_dead);
+    if (n_edges) atomicAdd(&tally[1], n_edges);
+    __syncthreads();
+    if (threadIdx.x < 2 && tally[threadIdx.x]) atomicAdd(count + 2 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
+}
+
+// ---- ccp_grid_reweight_device: the weights formed from the solution, never stored ------------------------------------------
+// k_weighted_refresh with the reads of wx and wy replaced by arithmetic on u (a view, or the handle's x through w_at) and
+// the guidance (include/ccp_gs.h, "Reweighting a weighted operator from the solution", fixes the operation order;
+// tests/reweight_helpers.py is the same in numpy).  fp64 throughout, nothing contracted, only +, -, x, / and sqrt: every
+// one correctly rounded, so the weights have the model's bits.
+//
+// One value everywhere.  A thread owns pixel (x, y) and needs four weights: its own e and s, and wN, wW -- the s of
+// (x, y-1) and the e of (x-1, y), which those pixels' threads form too.  All of them come from reweight_pixel, the same
+// instructions on the same operands in the same order whoever asks, so a weight has one value wherever it is used (and
+// only its owner stores it to out_wx / out_wy and has it checked, as k_weighted_refresh's ownership of weight_ok).  With
+// CCP_REWEIGHT_PIXEL the neighbour's weight needs the neighbour's other edge: u at (x+1, y-1) and (x-1, y+1) as well.
+//
+// Memory.  The neighbours' u and guidance are re-read, not staged in LDS: a thread's 3 + 4 extra u reads per channel are
+// its lane neighbours' and the adjacent rows' own loads of the same pass and come from L1 / L2 (the rows of a column of
+// blocks are scheduled back to back), while a staged halo would cost a barrier and a second addressing path for the
+// view / colour-split cases for reads HBM never sees.  NOTES R38.1 has the resource report and the timing.
+struct ReweightArgs {
+    const double *x;             // the handle's x (colour-split, channels `plane` apart): read where u.p is null
+    long pitch;
+    int W, H, cpb;               // cpb: channels summed per set (all of them for the shared operator, 1 per channel)
+    int coupling;                // CCP_REWEIGHT_EDGE / _PIXEL
+    double scale, eps;
+    ImageView u, gx, gy, bwx, bwy, lam;
+    AdjOut out_wx, out_wy;
+};
+
+constexpr int kPhiCharbonnier = 0, kPhiHuber = 1, kPhiReciprocal = 2;      // CCP_REWEIGHT_CHARBONNIER, _HUBER, _RECIPROCAL
+
+template <int PHI>
+__device__ __forceinline__ double reweight_phi(double q, double eps)
+{
+    if (PHI == kPhiCharbonnier) return 1.0 / sqrt(q + eps * eps);
+    if (PHI == kPhiHuber) return 1.0 / fmax(sqrt(q), eps);
+    return 1.0 / (sqrt(q) + eps);
+}
+
+__device__ __forceinline__ double reweight_u(const ReweightArgs &a, long plane, int x, int y, int c)
+{
+    return a.u.p ? a.u(y, x, c) : a.x[(long)c * plane + w_at(a.pitch, x, y)];
+}
+
+// q of the edge from (x, y) to (x + dx, y + dy) (the caller knows it to be inside the canvas) over channels [c0, c1)
+// (a view's absence is asked of its pointer here and the default written out, so that no view's `dflt` is live: the pass
+// is short of scalar registers, not of anything else)
+__device__ __forceinline__ double reweight_q(const ReweightArgs &a, long plane, const ImageView &g, int x, int y, int dx, int dy, int c0, int c1)
+{
+    double acc = 0.0;
+    for (int c = c0; c < c1; ++c) {
+        const double r = (g.p ? g.f32(y, x, c) : 0.0) - (reweight_u(a, plane, x + dx, y + dy, c) - reweight_u(a, plane, x, y, c));
+        acc += r * r;
+    }
+    return acc;
+}
+
+// The east (want & 1) and south (want & 2) weight of pixel (x, y) of set `set`; +0.0 for an absent edge or one not asked for.
+template <int PHI>
+__device__ __forceinline__ void reweight_pixel(const ReweightArgs &a, long plane, int x, int y, int set, int want, double &e, double &s)
+{
+    const bool he = x + 1 < a.W, hs = y + 1 < a.H;
+    const int c0 = set * a.cpb, c1 = c0 + a.cpb;
+    const bool pixel = a.coupling != 0;
+    const double qx = he && (pixel || (want & 1)) ? reweight_q(a, plane, a.gx, x, y, 1, 0, c0, c1) : 0.0;
+    const double qy = hs && (pixel || (want & 2)) ? reweight_q(a, plane, a.gy, x, y, 0, 1, c0, c1) : 0.0;
+    const double qp = qx + qy;
+    e = s = 0.0;
+    if (he && (want & 1)) {
+        const double t = a.scale * reweight_phi<PHI>(pixel ? qp : qx, a.eps);
+        e = a.bwx.p ? a.bwx(y, x, set) * t : t;
+    }
+    if (hs && (want & 2)) {
+        const double t = a.scale * reweight_phi<PHI>(pixel ? qp : qy, a.eps);
+        s = a.bwy.p ? a.bwy(y, x, set) * t : t;
+    }
+}
+
+// op, cons: the sets 4 x plane and 3 x plane apart, as the handle keeps them (cons: null without the three planes); count:
+// as k_weighted_refresh's.  grid = (ceil(W/kBlock), H, sets).
+template <int PHI>
+__global__ void __launch_bounds__(kBlock)
+k_weighted_reweight(ReweightArgs a, double *op, long plane, double *cons, unsigned long long *__restrict__ count)
+{
+    __shared__ unsigned tally[2];
+    if (threadIdx.x < 2) tally[threadIdx.x] = 0;
+    __syncthreads();
+    const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y, ch = blockIdx.z;
+    unsigned n_dead = 0, n_edges = 0;
+    if (x < a.W) {
+        const double l = a.lam.p ? a.lam(y, x, ch) : 0.0;
+        double e, s;
+        reweight_pixel<PHI>(a, plane, x, y, ch, 3, e, s);
+        adj_store(a.out_wx, y, x, ch, e);
+        adj_store(a.out_wy, y, x, ch, s);
+        const auto north = [&] {
+            double we, ws;
+            reweight_pixel<PHI>(a, plane, x, y - 1, ch, 2, we, ws);
+            return ws;
+        };
+        const auto west = [&] {
+            double we, ws;
+            reweight_pixel<PHI>(a, plane, x - 1, y, ch, 1, we, ws);
+            return we;
+        };
+        weighted_refresh_tail(l, e, s, north, west, x, y, ch, a.W, a.H, a.pitch, op, plane, 4 * plane, cons, 3 * plane, count, n_dead, n_edges);
     }
     if (n_dead) atomicAdd(&tally[0], n_dead);
     if (n_edges) atomicAdd(&tally[1], n_edges);

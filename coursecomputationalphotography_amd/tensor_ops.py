@@ -550,6 +550,7 @@ class WeightedSolver:
     and consumes its result.  refresh_operator gives the installed operator new values the same way, enqueue only, so
     weights that a network or a reweighting step produces every step can sit in the same graph; refresh_constraints does the
     same with a new mask of fixed pixels, on a handle whose constraint planes exist (reserve_constraints before set_operator).
+    reweight IS such a reweighting step: it forms the weights on the device from the last solution (irls_solve, tv_denoise).
 
     H, W, C: the canvas and its channels; device: a torch device or a GPU index.  iterations: every solve enqueues
     exactly this many PCG iterations (<= 4096); a channel that reaches sqrt(r'r) < epsilon earlier stops there and the
@@ -654,6 +655,34 @@ class WeightedSolver:
         self._operator = (wx, wy, lam, self._operator[3])
         self._generation += 1
 
+    def reweight(self, penalty, coupling, scale, epsilon, u=None, gx=None, gy=None, base_wx=None, base_wy=None, data_weight=None, out=None):
+        """refresh_operator with weights formed on the device from the current solution, the reweighting step of an IRLS
+        loop (capi.Grid.reweight_tensor): w = base * (scale * phi(q)) per edge, q the squared residual of the edge against
+        gx / gy summed over the channels (all of them on a shared operator, channel c alone on an operator per channel).
+        penalty: "charbonnier" | "huber" | "reciprocal"; coupling: "edge" | "pixel"; u: None reads the handle's x -- the
+        last solve's solution -- else a u8 / float32 / float64 H x W x C tensor (a guide, or f for the first step);
+        base_wx, base_wy, data_weight: as refresh_operator's wx, wy, data_weight (None: 1, 1, 0).  Enqueue only, as
+        refresh_operator: it may be recorded by torch.cuda.graph between two solves.  Returns (wx, wy), the weights formed:
+        `out` if given (a pair of float32 / float64 tensors, H x W on a shared operator, H x W x C on one per channel), else
+        two new float64 tensors (inside a capture pass `out`).  They are recorded as the installed weights, so a later
+        solve_grad's backward re-installs the right ones; solve_grad(wx=, wy=) on them is the way to unroll the outer loop
+        by hand: the gradient of an IRLS result is not provided."""
+        import torch
+        if self._operator is None:
+            raise RuntimeError("WeightedSolver: set_operator first")
+        capi.reweight_ids(penalty, coupling)
+        dev = self.device.index
+        bwx, bwy, lam = (_weight(w, self.H, self.W, dev) for w in (base_wx, base_wy, data_weight))
+        if out is None:
+            shape = (self.H, self.W, self.C) if self.grid.operator_channels() > 1 else (self.H, self.W)
+            with torch.cuda.device(self.device):
+                out = (torch.empty(shape, dtype=torch.float64, device=self.device), torch.empty(shape, dtype=torch.float64, device=self.device))
+        wx, wy = out
+        self.grid.reweight_tensor(penalty, coupling, scale, epsilon, u=u, gx=gx, gy=gy, base_wx=bwx, base_wy=bwy, lam=lam, out_wx=wx, out_wy=wy)
+        self._operator = (wx, wy, lam, self._operator[3])
+        self._generation += 1
+        return wx, wy
+
     def reserve_constraints(self):
         """Before set_operator: keep the handle's constraint planes whether or not the operator fixes a pixel
         (capi.Grid.reserve_constraints), so that refresh_constraints may give it a fixed set later.  Results are unchanged
@@ -720,6 +749,76 @@ class WeightedSolver:
     def __exit__(self, *exc):
         self.close()
         return False
+
+
+def irls_solve(gx, gy, f, outer: int, iterations: int, penalty="charbonnier", coupling="edge", strength=1.0, epsilon=1e-2, data_weight=1.0,
+               wx=None, wy=None, fixed=None, values=None, tolerance=1e-10, hierarchy="rescaled", precision="f64", channels="sequential",
+               smoother="point", out_dtype=None, history=None):
+    """Robust gradient-domain fitting by iteratively reweighted least squares: `outer` steps of (reweight, assemble, solve)
+    on one WeightedSolver, every step a launch sequence -- after set_operator nothing synchronises until the caller reads
+    the result.  It minimises
+        E(u) = sum over edges 2 strength base psi(rho) + sum data_weight (u - f)^2,   psi'(rho) = rho phi(rho^2),
+    rho = sqrt(q) the residual of the edge (WeightedSolver.reweight: gx - (uE - u) over the channels, gy to the south):
+        "charbonnier": phi = 1 / sqrt(rho^2 + epsilon^2),   psi = sqrt(rho^2 + epsilon^2)
+        "huber":       phi = 1 / max(rho, epsilon),          psi = rho^2 / (2 epsilon) for rho < epsilon, rho - epsilon / 2 beyond
+        "reciprocal":  phi = 1 / (rho + epsilon),            psi = rho - epsilon log(1 + rho / epsilon)
+    coupling "edge" takes every edge's own rho (anisotropic: with zero guidance sum |du/dx| + |du/dy|); "pixel" takes
+    rho^2 = q_x + q_y per pixel for both of its forward edges and the sum then runs over pixels (isotropic; the energy
+    reading needs wx = wy there).  Each psi(sqrt(t)) is concave in t, so the weighted least-squares problem of a step
+    majorises E at the current iterate and E does not increase from step to step (up to the inner tolerance).
+    gx, gy: float32 H x W x C or None (0); f: u8 / float32 / float64 H x W x C, the data term and the first step's u (the
+    later steps reweight from the handle's x); wx, wy (the base weights), data_weight, fixed, values: as
+    WeightedSolver.set_operator's and solve's (an H x W x C weight: one operator per channel, each channel its own rho).
+    Every step solves warm-started from the previous solution, at most `iterations` PCG iterations to
+    sqrt(r'r) < tolerance * |b|.  history: None, or a list that receives one (u, report, wx, wy) of device tensors per
+    outer step (report C x 8, WeightedSolver.set_stop's; wx, wy the weights the step solved with): convergence is not
+    checked here, that would be a read-back.  Returns x as out_dtype (None: torch.uint8, clamped, for a u8 f, else float64).
+    The gradient of the result is not provided; unrolled differentiation is possible by hand with WeightedSolver.reweight's
+    `out` and solve_grad(wx=, wy=).  Strongly varying weights -- small epsilon, sharp edges -- are where smoother="line" helps."""
+    import torch
+    capi.reweight_ids(penalty, coupling)
+    if f is None:
+        raise ValueError("irls_solve needs f: the data term, and the image the first step reweights from")
+    if int(outer) < 1:
+        raise ValueError(f"outer must be at least 1, not {outer}")
+    dev = _device_index(f)
+    H, W = f.shape[0], f.shape[1]
+    C = f.shape[2] if f.dim() == 3 else 1
+    if out_dtype is None:
+        out_dtype = torch.uint8 if f.dtype == torch.uint8 else torch.float64
+    with WeightedSolver(H, W, C, dev, iterations=iterations, epsilon=0.0, hierarchy=hierarchy, precision=precision, channels=channels,
+                        smoother=smoother) as s:
+        s.set_operator(wx, wy, data_weight, fixed)
+        s.set_stop(relative=tolerance)
+        base_wx, base_wy, lam, _ = s._operator
+        x = f.to(torch.float64).reshape(H, W, C)
+        for k in range(int(outer)):
+            w = s.reweight(penalty, coupling, strength, epsilon, u=f if k == 0 else None, gx=gx, gy=gy, base_wx=base_wx, base_wy=base_wy,
+                           data_weight=lam)
+            report = None if history is None else torch.zeros((C, 8), dtype=torch.float64, device=x.device)
+            x, _ = s.solve(gx, gy, f, values, x0=x, report=report)
+            if history is not None:
+                history.append((x, report, w[0], w[1]))
+        if out_dtype == torch.uint8:
+            return s.grid.store_u8_tensor()
+        return x if out_dtype == torch.float64 else x.to(out_dtype)
+
+
+def tv_denoise(image, strength, outer: int = 10, iterations: int = 400, epsilon=1e-2, isotropic=True, data_weight=1.0, tolerance=1e-10,
+               hierarchy="rescaled", precision="f64", channels="sequential", smoother="point", history=None):
+    """Total-variation denoising (Rudin, Osher, Fatemi 1992) by irls_solve: u minimises
+    2 strength TV_epsilon(u) + sum data_weight (u - image)^2 with the Charbonnier-smoothed total variation -- isotropic:
+    sum over pixels sqrt(|grad u|^2 + epsilon^2), the gradient over all channels (vectorial TV); isotropic=False: the
+    anisotropic sum over edges sqrt(du^2 + epsilon^2).  Zero guidance, f = image, "pixel" or "edge" coupling.  image: a u8 or
+    float H x W (x C) tensor; strength and epsilon are in the image's own units (a u8 image: grey levels).  Returns the
+    image's dtype and shape (u8: clamped, as wls_smooth).  The other arguments are irls_solve's."""
+    import torch
+    f = image if image.dim() == 3 else image.unsqueeze(-1)
+    out_dtype = torch.uint8 if image.dtype == torch.uint8 else image.dtype
+    u = irls_solve(None, None, f, outer, iterations, penalty="charbonnier", coupling="pixel" if isotropic else "edge", strength=strength,
+                   epsilon=epsilon, data_weight=data_weight, tolerance=tolerance, hierarchy=hierarchy, precision=precision, channels=channels,
+                   smoother=smoother, out_dtype=out_dtype, history=history)
+    return u if image.dim() == 3 else u[..., 0]
 
 
 _PersistentSolve = None

@@ -1179,6 +1179,66 @@ int ccp_grid_reserve_constraints(ccp_grid *g, int32_t on);
 int ccp_grid_refresh_constrained_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy,
                                         const ccp_device_array *lambda, const ccp_device_array *fixed);
 
+/* ---- Reweighting a weighted operator from the solution by enqueue only (IRLS) -------------------------------------------------
+ * Total variation, L1 / Huber gradient fusion, edge-stopping smoothing from a guide: each is an outer loop around the
+ * weighted solve with weights that are a function of the current solution (iteratively reweighted least squares).
+ * ccp_grid_reweight_device is ccp_grid_refresh_weights_device whose weights are never stored: one pass reads the solution
+ * and the guidance, forms every edge's weight in registers and writes the operator's planes; then come the launches and
+ * the status word of the refresh.  K outer steps are K x (reweight, assemble, enqueue solve): launches only, recordable
+ * in one graph.
+ *   Definition (fp64 throughout, every input widened exactly, no multiply-add fused; only +, -, x, / and sqrt, each
+ *   correctly rounded, so the weights are reproducible to the bit; tests/reweight_helpers.py is the same in numpy).
+ *   The squared residual q_x of the east edge of (x, y), x + 1 < W:
+ *       acc = +0.0;  for each channel c of the channel set, in channel order:  r = gx - (uE - u);  acc += r * r;   q_x = acc
+ *   (u, uE: u at (x, y) and (x + 1, y); gx at (x, y)).  The south edge, y + 1 < H, gives q_y with gy and uS.  An absent
+ *   edge has q = +0.0.
+ *   The argument of phi:  CCP_REWEIGHT_EDGE: the east weight takes q = q_x, the south weight q = q_y (anisotropic).
+ *       CCP_REWEIGHT_PIXEL: both take q = q_x + q_y of the pixel that owns the two edges (isotropic).
+ *   phi:  CHARBONNIER 1 / sqrt(q + epsilon * epsilon);  HUBER 1 / fmax(sqrt(q), epsilon);  RECIPROCAL 1 / (sqrt(q) + epsilon).
+ *   The weight:  t = scale * phi(q);  w = base * t, or w = t when the base view is NULL.
+ *   The channel set: a shared operator sums all channels of the handle (vectorial TV: one operator for all channels); an
+ *   operator per channel (ccp_grid_operator_channels > 1) takes channel c alone for set c, and base_wx, base_wy and lambda
+ *   are then H x W x channels, read with stride_c as the per-channel refresh reads them.
+ *   One value everywhere: a weight is needed by both pixels of its edge, and both form it with the same instructions on the
+ *   same operands in the same order; the pixel that owns it (wx(x,y) and wy(x,y) belong to (x,y)) stores it to out_wx /
+ *   out_wy and has it checked.
+ *   u: NULL reads the handle's x -- on a fixed pixel the prescribed value the solve left there -- otherwise a U8, F32 or F64
+ *   view, H x W x channels (stride_c 0 broadcasts): a guide image, or f for the first outer step.  gx, gy: F32,
+ *   H x W x channels, NULL: 0.  base_wx, base_wy, lambda: as wx, wy, lambda of ccp_grid_refresh_weights_device (F32 or F64;
+ *   NULL: 1, 1, 0).  out_wx, out_wy: NULL, or F32 / F64 views that receive exactly the weights formed -- H x W for a shared
+ *   operator, H x W x channels for one per channel; the last column of out_wx and the last row of out_wy are +0.0; an F32
+ *   output is the fp64 weight rounded once.  They are for autograd, the adjoint pass and tests.
+ *   Contract: afterwards the handle holds, bit for bit, everything ccp_grid_refresh_weights_device(g, WX, WY, lambda)
+ *   leaves when WX and WY hold the weights defined above: the level-0 planes, ce, cs and lambda' where they exist, every
+ *   coarse level, the float copies, the census of CCP_MG_NULLSPACE_CONSTANT, the counts ccp_grid_constraint_info reads and
+ *   the operator status word.  The fixed set is kept (its marks are the sign of the stored lambda plane).  A weight that is
+ *   not finite or < 0 (a NaN in u, an overflow) sets CCP_OPERATOR_BAD_WEIGHT exactly as a bad refreshed weight does: the
+ *   next enqueue solve leaves x alone, the next good reweight or refresh restores everything.  (HUBER's fmax returns its
+ *   other argument for a NaN, as C's does: a NaN residual yields scale / epsilon there and is not reported.)
+ *   Launches on the handle's stream only: no allocation, no host synchronisation, no copy to or from host memory; it may be
+ *   issued during stream capture and returns CCP_OK.  Every mode the value refresh serves is served.
+ *   Refused on the host with nothing enqueued.  CCP_ERR_BAD_ARG: g or how NULL; an unknown penalty or coupling; epsilon not
+ *   > 0 or not finite; scale negative or not finite; a bad view (checked as the refresh's and, the outputs, as the adjoint
+ *   pass's: two elements of an output at one address; also an output that shares bytes with an input view, which the
+ *   neighbouring pixels' threads read).  CCP_ERR_STATE: no installed operator, or no successful ccp_grid_mg_prepare since
+ *   the last call that drops what prepare built.  CCP_ERR_UNSUPPORTED: not a weighted handle.
+ * Out of scope: host-pointer twins, the C++ facades, a robust data term (lambda reweighted from |u - f|), gradients through
+ * the outer loop (the weights are in out_wx / out_wy for a hand-unrolled one).  Additive: the ABI version does not change. */
+#define CCP_REWEIGHT_CHARBONNIER 0   /* phi = 1 / sqrt(q + eps*eps)      */
+#define CCP_REWEIGHT_HUBER       1   /* phi = 1 / fmax(sqrt(q), eps)     */
+#define CCP_REWEIGHT_RECIPROCAL  2   /* phi = 1 / (sqrt(q) + eps)        */
+#define CCP_REWEIGHT_EDGE  0         /* every edge from its own residual (anisotropic) */
+#define CCP_REWEIGHT_PIXEL 1         /* both forward edges of a pixel from q_x + q_y (isotropic) */
+typedef struct ccp_reweight {
+    int32_t penalty, coupling;
+    double scale, epsilon;           /* scale >= 0 and finite; epsilon > 0 and finite */
+    const ccp_device_array *u;       /* NULL: the handle's x */
+    const ccp_device_array *gx, *gy; /* F32, H x W x channels; NULL: 0 */
+    const ccp_device_array *base_wx, *base_wy, *lambda;   /* as ccp_grid_refresh_weights_device's wx, wy, lambda; NULL: 1, 1, 0 */
+    const ccp_device_array *out_wx, *out_wy;              /* F32 or F64; NULL: not written */
+} ccp_reweight;
+int ccp_grid_reweight_device(ccp_grid *g, const ccp_reweight *how);
+
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
 int ccp_grid_last_timing(ccp_grid *g, float *milliseconds, int32_t *kernel_launches);
