@@ -96,6 +96,7 @@ ABI_SYMBOLS = (
     "ccp_grid_mg_prepare", "ccp_grid_mg_conjugate_gradient_enqueue", "ccp_grid_mg_conjugate_gradient_enqueue_relative",
     "ccp_grid_refresh_weights_device", "ccp_grid_operator_status",
     "ccp_grid_reserve_constraints", "ccp_grid_refresh_constrained_device", "ccp_grid_reweight_device",
+    "ccp_grid_reweight_robust_device",
     "ccp_grid_set_mask_device", "ccp_mask_erode_cross_device", "ccp_panorama_begin_device", "ccp_panorama_add_device",
     "ccp_panorama_finish_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
@@ -170,6 +171,27 @@ class Reweight(C.Structure):
     """ccp_reweight: the penalty, the coupling, scale, epsilon and one ccp_device_array pointer per view (NULL: absent)."""
     _fields_ = [("penalty", C.c_int32), ("coupling", C.c_int32), ("scale", C.c_double), ("epsilon", C.c_double)] + \
                [(n, C.POINTER(DeviceArray)) for n in REWEIGHT_VIEWS]
+
+
+# ccp_grid_reweight_robust_device (ccp_gs.h, "Robust data term"): its penalties are ccp_grid_reweight_device's and
+# "quadratic" (phi = 1.0: the term is not reweighted), which reweight_ids keeps refusing for the older call
+ROBUST_PENALTIES = dict(REWEIGHT_PENALTIES, quadratic=3)
+
+
+def robust_ids(penalty, coupling, data_penalty):
+    """(CCP_REWEIGHT_* edge penalty, coupling, data penalty) of the names ccp_grid_reweight_robust_device takes: ValueError otherwise."""
+    for what, name in (("penalty", penalty), ("data_penalty", data_penalty)):
+        if name not in ROBUST_PENALTIES:
+            raise ValueError(f"{what} must be one of {sorted(ROBUST_PENALTIES)}, not {name!r}")
+    if coupling not in REWEIGHT_COUPLINGS:
+        raise ValueError(f"coupling must be one of {sorted(REWEIGHT_COUPLINGS)}, not {coupling!r}")
+    return ROBUST_PENALTIES[penalty], REWEIGHT_COUPLINGS[coupling], ROBUST_PENALTIES[data_penalty]
+
+
+class ReweightData(C.Structure):
+    """ccp_reweight_data: the data penalty, scale, epsilon, f and the output for the lambda formed (NULL: absent)."""
+    _fields_ = [("penalty", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_double), ("epsilon", C.c_double),
+                ("f", C.POINTER(DeviceArray)), ("out_lambda", C.POINTER(DeviceArray))]
 
 
 class PanoramaState(C.Structure):
@@ -342,6 +364,7 @@ def load() -> C.CDLL:
     L.ccp_grid_reserve_constraints.argtypes = [vp, i32]
     L.ccp_grid_refresh_constrained_device.argtypes = [vp, vp, vp, vp, vp]
     L.ccp_grid_reweight_device.argtypes = [vp, C.POINTER(Reweight)]
+    L.ccp_grid_reweight_robust_device.argtypes = [vp, C.POINTER(Reweight), C.POINTER(ReweightData)]
     L.ccp_grid_mg_level_channel.argtypes = [vp, i32, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
     L.ccp_grid_constraint_info_channel.argtypes = [vp, i32, vp, vp, vp]
     L.ccp_grid_adjoint_begin_device.argtypes = [vp, da]
@@ -1380,6 +1403,37 @@ class Grid:
         arrs["lambda"] = arrs.pop("lam")
         how = Reweight(ids[0], ids[1], float(scale), float(epsilon), *[None if arrs[n] is None else C.pointer(arrs[n]) for n in REWEIGHT_VIEWS])
         self._on_stream(lambda: self.L.ccp_grid_reweight_device(self.h, C.byref(how)), "ccp_grid_reweight_device")
+
+    def reweight_robust_tensor(self, penalty, coupling, scale, epsilon, data_penalty, data_scale, data_epsilon, f=None, u=None, gx=None,
+                               gy=None, base_wx=None, base_wy=None, lam=None, out_wx=None, out_wy=None, out_lambda=None):
+        """reweight_tensor with the data term reweighted in the same pass (ccp_grid_reweight_robust_device): the edges as
+        reweight_tensor forms them, and per pixel lambda = lam * (data_scale * phi_d(dq)), dq the sum of (f - u)^2 over the
+        channels (all of them on a shared operator, channel c alone on an operator per channel); lam None: 1.  penalty and
+        data_penalty: "charbonnier" | "huber" | "reciprocal" | "quadratic" (phi = 1: that term is not reweighted, and its
+        epsilon is not read); f: uint8 / float32 / float64 H x W x channels (H x W: every channel's), None only with
+        data_penalty "quadratic"; out_lambda: a float32 / float64 tensor shaped as out_wx that receives the lambda formed,
+        fixed pixels included.  The other arguments, the stream and the verdict: as reweight_tensor's."""
+        ids = robust_ids(penalty, coupling, data_penalty)
+        torch = self._torch()
+        floats, any_ = (torch.float32, torch.float64), (torch.uint8, torch.float32, torch.float64)
+        named = ((base_wx, "base_wx"), (base_wy, "base_wy"), (lam, "lam"))
+        outs = ((out_wx, "out_wx"), (out_wy, "out_wy"), (out_lambda, "out_lambda"))
+        per_channel = self.operator_channels() > 1 or (self.C == 1 and any(isinstance(t, torch.Tensor) and t.dim() == 3
+                                                                           for t in (base_wx, base_wy, lam, out_wx, out_wy, out_lambda)))
+        arrs = {"u": self._channel_array(u, "u", any_), "f": self._channel_array(f, "f", any_),
+                "gx": None if gx is None else self._hwc(gx, "gx", (torch.float32,))[0],
+                "gy": None if gy is None else self._hwc(gy, "gy", (torch.float32,))[0]}
+        if per_channel:
+            arrs.update({n: self._channel_array(t, n, floats) for t, n in named})
+            arrs.update({n: self._channel_array(t, n, floats, output=True) for t, n in outs})
+        else:
+            arrs.update({n: self._weight_array(t, n) for t, n in named})
+            arrs.update({n: None if t is None else self._plane_out(t, n) for t, n in outs})
+        arrs["lambda"] = arrs.pop("lam")
+        ptr = lambda n: None if arrs[n] is None else C.pointer(arrs[n])
+        how = Reweight(ids[0], ids[1], float(scale), float(epsilon), *[ptr(n) for n in REWEIGHT_VIEWS])
+        data = ReweightData(ids[2], 0, float(data_scale), 0.0 if data_epsilon is None else float(data_epsilon), ptr("f"), ptr("out_lambda"))
+        self._on_stream(lambda: self.L.ccp_grid_reweight_robust_device(self.h, C.byref(how), C.byref(data)), "ccp_grid_reweight_robust_device")
 
     def operator_status(self) -> int:
         """The operator status word of the last refresh_weights_tensor (0: good; 1: a bad weight, 2: out of float range in

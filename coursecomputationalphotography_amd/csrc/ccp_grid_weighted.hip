@@ -367,56 +367,86 @@ void view_span(const ccp_device_array *a, long H, long W, long C, uintptr_t *lo,
     *hi = *lo + (uintptr_t)((last + 1) * dtype_bytes(a->dtype));
 }
 
-// ccp_grid_reweight_device: refresh_device without a mask, the level-0 pass forming the weights instead of reading them
-int reweight_device(ccp_grid *g, const ccp_reweight *how)
+bool reweight_numbers_ok(double scale, double epsilon, bool with_epsilon)
+{
+    return (!with_epsilon || (epsilon > 0.0 && epsilon <= DBL_MAX)) && scale >= 0.0 && scale <= DBL_MAX;
+}
+
+// What ccp_grid_reweight_device (data: null) and ccp_grid_reweight_robust_device check on the host before anything is
+// enqueued, in one place, and the kernels' description of the edge term: the numbers, the installed operator, every view,
+// and that no output shares bytes with an input.
+int reweight_checked(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data, ReweightArgs *a)
 {
     CCP_TRY(weighted_handle(g));
     if (!how) return CCP_ERR_BAD_ARG;
-    if (how->penalty < CCP_REWEIGHT_CHARBONNIER || how->penalty > CCP_REWEIGHT_RECIPROCAL) return CCP_ERR_BAD_ARG;
+    const int last_penalty = data ? CCP_REWEIGHT_QUADRATIC : CCP_REWEIGHT_RECIPROCAL;
+    if (how->penalty < CCP_REWEIGHT_CHARBONNIER || how->penalty > last_penalty) return CCP_ERR_BAD_ARG;
     if (how->coupling != CCP_REWEIGHT_EDGE && how->coupling != CCP_REWEIGHT_PIXEL) return CCP_ERR_BAD_ARG;
-    if (!(how->epsilon > 0.0 && how->epsilon <= DBL_MAX) || !(how->scale >= 0.0 && how->scale <= DBL_MAX)) return CCP_ERR_BAD_ARG;
+    if (!reweight_numbers_ok(how->scale, how->epsilon, true)) return CCP_ERR_BAD_ARG;
+    if (data) {
+        if (data->penalty < CCP_REWEIGHT_CHARBONNIER || data->penalty > CCP_REWEIGHT_QUADRATIC || data->reserved != 0) return CCP_ERR_BAD_ARG;
+        if (!reweight_numbers_ok(data->scale, data->epsilon, data->penalty != CCP_REWEIGHT_QUADRATIC)) return CCP_ERR_BAD_ARG;
+        if (!data->f && data->penalty != CCP_REWEIGHT_QUADRATIC) return CCP_ERR_BAD_ARG;
+    }
     if (!g->has_op) return CCP_ERR_STATE;                                  // (the operator's kind decides the views' extents)
     const Geom &geo = g->geom;
     const int C = g->desc.channels, sets = g->per_channel ? C : 1;
+    constexpr int kInputs = 7, kViews = 10;
     struct {
         const ccp_device_array *a;
         unsigned dtypes;
         bool output;
         int c;
-    } views[8] = {{how->u, kF32F64 | kU8, false, C}, {how->gx, kF32, false, C},          {how->gy, kF32, false, C},
-                  {how->base_wx, kF32F64, false, sets}, {how->base_wy, kF32F64, false, sets}, {how->lambda, kF32F64, false, sets},
-                  {how->out_wx, kF32F64, true, sets},   {how->out_wy, kF32F64, true, sets}};
+    } views[kViews] = {{how->u, kF32F64 | kU8, false, C},
+                       {how->gx, kF32, false, C},
+                       {how->gy, kF32, false, C},
+                       {how->base_wx, kF32F64, false, sets},
+                       {how->base_wy, kF32F64, false, sets},
+                       {how->lambda, kF32F64, false, sets},
+                       {data ? data->f : nullptr, kF32F64 | kU8, false, C},
+                       {how->out_wx, kF32F64, true, sets},
+                       {how->out_wy, kF32F64, true, sets},
+                       {data ? data->out_lambda : nullptr, kF32F64, true, sets}};
     for (const auto &v : views)
         if (v.a) CCP_TRY(check_view(g, v.a, v.dtypes, v.output, 1, geo.H, geo.W, v.c));
     // an output that shares bytes with an input would be read by the neighbours' threads while its owner writes it
-    for (int o = 6; o < 8; ++o)
-        for (int i = 0; i < 6 && views[o].a; ++i) {
+    for (int o = kInputs; o < kViews; ++o)
+        for (int i = 0; i < kInputs && views[o].a; ++i) {
             if (!views[i].a) continue;
             uintptr_t olo, ohi, ilo, ihi;
             view_span(views[o].a, geo.H, geo.W, views[o].c, &olo, &ohi);
             view_span(views[i].a, geo.H, geo.W, views[i].c, &ilo, &ihi);
             if (olo < ihi && ilo < ohi) return CCP_ERR_BAD_ARG;
         }
+    a->x = g->x.p;
+    a->pitch = geo.pitch;
+    a->W = geo.W;
+    a->H = geo.H;
+    a->cpb = C / sets;
+    a->coupling = how->coupling;
+    a->scale = how->scale;
+    a->eps = how->epsilon;
+    a->u = image_view(how->u, 0.0);
+    a->gx = image_view(how->gx, 0.0);
+    a->gy = image_view(how->gy, 0.0);
+    a->bwx = image_view(how->base_wx, 1.0);
+    a->bwy = image_view(how->base_wy, 1.0);
+    a->lam = image_view(how->lambda, 0.0);
+    a->out_wx = adj_out(how->out_wx);
+    a->out_wy = adj_out(how->out_wy);
+    return CCP_OK;
+}
+
+// ccp_grid_reweight_device: refresh_device without a mask, the level-0 pass forming the weights instead of reading them
+int reweight_device(ccp_grid *g, const ccp_reweight *how)
+{
+    ReweightArgs a{};
+    CCP_TRY(reweight_checked(g, how, nullptr, &a));
+    const Geom &geo = g->geom;
+    const int sets = g->per_channel ? g->desc.channels : 1;
     // from here on: launches on the handle's stream, nothing else
     CCP_TRY(mg_refresh_begin(g, 1 + 3 * sets));
     const long n = geo.ch_stride;
-    ReweightArgs a{};
-    a.x = g->x.p;
-    a.pitch = geo.pitch;
-    a.W = geo.W;
-    a.H = geo.H;
-    a.cpb = C / sets;
-    a.coupling = how->coupling;
-    a.scale = how->scale;
-    a.eps = how->epsilon;
-    a.u = image_view(how->u, 0.0);
-    a.gx = image_view(how->gx, 0.0);
-    a.gy = image_view(how->gy, 0.0);
-    a.bwx = image_view(how->base_wx, 1.0);
-    a.bwy = image_view(how->base_wy, 1.0);
-    a.lam = image_view(how->lambda, 0.0);
-    a.out_wx = adj_out(how->out_wx);
-    a.out_wy = adj_out(how->out_wy);
     double *cons = g->has_fixed ? g->wcons.p : nullptr;
     const dim3 grid = pixels(geo.W, geo.H, sets);
     if (how->penalty == CCP_REWEIGHT_CHARBONNIER)
@@ -425,6 +455,59 @@ int reweight_device(ccp_grid *g, const ccp_reweight *how)
         hipLaunchKernelGGL((k_weighted_reweight<kPhiHuber>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
     else
         hipLaunchKernelGGL((k_weighted_reweight<kPhiReciprocal>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
+    CCP_HIP(hipGetLastError());
+    g->refreshed = true;
+    g->mg_nullspace.floating = -1;      // as refresh_device: the census verdict the host remembers is the old values'
+    return mg_refresh(g);
+}
+
+static_assert(kPhiQuadratic == CCP_REWEIGHT_QUADRATIC, "k_weighted_reweight_robust's PHI is the header's penalty id");
+
+// Rows per strip of k_weighted_reweight_robust, by tools/robust_bench.py (NOTES R39.1 has the figures of 4, 8, 16 and 32 at
+// both sizes): a tall strip forms fewer north weights twice, but a canvas cut into few strips leaves CUs without a block.
+// At 4096^2 x 3 the pass was the faster the taller the strip (32: 16 x 128 blocks, 8 per CU of the 256), at 752 x 566 x 3 the
+// slower (4: 3 x 142 blocks; 8 already leaves CUs idle and costs 28 %).  So: the tallest strip that still makes 8 blocks per
+// CU, else 4.  CCP_GS_ROBUST_ROWS = 4 | 8 | 16 | 32 overrides it, for that measurement and for the tests of every strip
+// height on small canvases; the bits do not depend on it.
+int robust_rows(int W, int H, int sets)
+{
+    if (const char *e = getenv("CCP_GS_ROBUST_ROWS")) {
+        const int r = atoi(e);
+        if (r == 4 || r == 8 || r == 16 || r == 32) return r;
+    }
+    const long columns = (W + kBlock - 1) / kBlock, enough = 8 * 256;
+    for (int r = 32; r > 4; r /= 2)
+        if (columns * ((H + r - 1) / r) * sets >= enough) return r;
+    return 4;
+}
+
+// ccp_grid_reweight_robust_device: reweight_device whose level-0 pass forms lambda from |u - f| as well
+int reweight_robust_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data)
+{
+    if (!data) return CCP_ERR_BAD_ARG;
+    RobustArgs a{};
+    CCP_TRY(reweight_checked(g, how, data, &a.r));
+    const Geom &geo = g->geom;
+    const int sets = g->per_channel ? g->desc.channels : 1;
+    // from here on: launches on the handle's stream, nothing else
+    CCP_TRY(mg_refresh_begin(g, 1 + 3 * sets));
+    const long n = geo.ch_stride;
+    a.rows = robust_rows(geo.W, geo.H, sets);
+    a.dphi = data->penalty;
+    a.dscale = data->scale;
+    a.deps = data->penalty == CCP_REWEIGHT_QUADRATIC ? 1.0 : data->epsilon;   // (not read for QUADRATIC)
+    a.f = image_view(data->f, 0.0);
+    a.out_lam = adj_out(data->out_lambda);
+    double *cons = g->has_fixed ? g->wcons.p : nullptr;
+    const dim3 grid((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)((geo.H + a.rows - 1) / a.rows), (unsigned)sets);
+    if (how->penalty == CCP_REWEIGHT_CHARBONNIER)
+        hipLaunchKernelGGL((k_weighted_reweight_robust<kPhiCharbonnier>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
+    else if (how->penalty == CCP_REWEIGHT_HUBER)
+        hipLaunchKernelGGL((k_weighted_reweight_robust<kPhiHuber>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
+    else if (how->penalty == CCP_REWEIGHT_RECIPROCAL)
+        hipLaunchKernelGGL((k_weighted_reweight_robust<kPhiReciprocal>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
+    else
+        hipLaunchKernelGGL((k_weighted_reweight_robust<kPhiQuadratic>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
     CCP_HIP(hipGetLastError());
     g->refreshed = true;
     g->mg_nullspace.floating = -1;      // as refresh_device: the census verdict the host remembers is the old values'
@@ -548,6 +631,11 @@ try {
 int ccp_grid_reweight_device(ccp_grid *g, const ccp_reweight *how)
 try {
     return reweight_device(g, how);
+} CCP_ABI_CATCH
+
+int ccp_grid_reweight_robust_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data)
+try {
+    return reweight_robust_device(g, how, data);
 } CCP_ABI_CATCH
 
 int ccp_grid_reserve_constraints(ccp_grid *g, int32_t on)

@@ -317,6 +317,155 @@ k_weighted_reweight(ReweightArgs a, double *op, long plane, double *cons, unsign
     if (threadIdx.x < 2 && tally[threadIdx.x]) atomicAdd(count + 2 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
 }
 
+// ---- ccp_grid_reweight_robust_device: the edge weights AND lambda formed from the solution ----------------------------------
+// k_weighted_reweight with a data term that is reweighted too (include/ccp_gs.h, "Robust data term", fixes the operation
+// order; tests/robust_helpers.py is the same in numpy), built so that every weight is formed ONCE: k_weighted_reweight
+// forms four weights per pixel of which two are its neighbours', and fp64 sqrt and division bound it (NOTES R38.1).
+//
+// Geometry.  grid = (ceil(W/kBlock), ceil(H/rows), sets): a thread owns column x and marches down the `rows` rows of its
+// strip.  Per row it forms its own e, s and lambda (robust_pixel, one pass over the channels that reads u(x, y) once for
+// q_x, q_y and the data residual).  wN is the s it formed for the row above, kept in a register; in the strip's first row
+// it forms the s of (x, y0 - 1) itself.  wW is the left lane's e of this row: every lane writes its e to one of two LDS
+// rows (east[row & 1]), one barrier, then reads its left neighbour's; lane 0 of a block with x >= 1 forms the e of
+// (x - 1, y) itself.  Two rows suffice with one barrier per row: a row's buffer is written again two rows later, and the
+// barrier of the row in between lies after every read of it.
+//
+// Bits.  Whoever forms a weight calls robust_pixel -- the same instructions on the same operands in the same order, every
+// one of them a correctly rounded fp64 operation -- and a value that went through a register or LDS is the value, so a
+// weight has one value wherever it is used, as in k_weighted_reweight.  With CCP_REWEIGHT_PIXEL the two forward edges of
+// a pixel share one phi; with _EDGE each has its own; lambda costs one more unless its penalty is QUADRATIC.
+//
+// Barriers.  Every __syncthreads() below is reached by every thread of the block the same number of times: the trip count
+// is the kernel argument `rows`, no thread returns early, and lanes past W and rows past H skip the arithmetic and the
+// stores, not the barrier.
+//
+// The tail is weighted_refresh_tail, with callables that hand over the two carried weights; the thread's tallies are
+// summed over its rows before the block's one atomic per non-zero count.
+constexpr int kPhiQuadratic = 3;                                          // CCP_REWEIGHT_QUADRATIC: phi = 1.0, q not formed
+
+struct RobustArgs {
+    ReweightArgs r;              // the edge term, as k_weighted_reweight's; r.lam: the base lambda (null: 1)
+    int rows;                    // rows per strip: every thread makes exactly this many trips
+    int dphi;                    // the data penalty, CCP_REWEIGHT_* (uniform over the launch)
+    double dscale, deps;
+    ImageView f;                 // null only with dphi == kPhiQuadratic
+    AdjOut out_lam;
+};
+
+template <int PHI>
+__device__ __forceinline__ double robust_phi(double q, double eps)
+{
+    if constexpr (PHI == kPhiQuadratic)
+        return 1.0;
+    else
+        return reweight_phi<PHI>(q, eps);
+}
+
+__device__ __forceinline__ double robust_phi_data(int phi, double q, double eps)
+{
+    if (phi == kPhiCharbonnier) return reweight_phi<kPhiCharbonnier>(q, eps);
+    if (phi == kPhiHuber) return reweight_phi<kPhiHuber>(q, eps);
+    if (phi == kPhiReciprocal) return reweight_phi<kPhiReciprocal>(q, eps);
+    return 1.0;
+}
+
+// The east (want & 1) and south (want & 2) weight and the lambda (want & 4) of pixel (x, y) of set `set`; +0.0 for an
+// absent edge or a value not asked for.  The owner asks for all three, a neighbour for the one weight it needs.
+template <int PHI>
+__device__ __forceinline__ void robust_pixel(const RobustArgs &a, long plane, int x, int y, int set, int want, double &e, double &s, double &l)
+{
+    const ReweightArgs &r = a.r;
+    const bool he = x + 1 < r.W, hs = y + 1 < r.H;
+    const bool pixel = r.coupling != 0;
+    const bool we = he && (want & 1), ws = hs && (want & 2), wl = (want & 4) != 0;
+    // which sums are formed: with PIXEL coupling either weight needs both of the pixel's edges
+    const bool nx = PHI != kPhiQuadratic && he && (pixel ? (want & 3) != 0 : we);
+    const bool ny = PHI != kPhiQuadratic && hs && (pixel ? (want & 3) != 0 : ws);
+    const bool nd = wl && a.dphi != kPhiQuadratic;
+    double qx = 0.0, qy = 0.0, dq = 0.0;
+    if (nx || ny || nd) {
+        const int c0 = set * r.cpb, c1 = c0 + r.cpb;
+        for (int c = c0; c < c1; ++c) {
+            const double u = reweight_u(r, plane, x, y, c);
+            if (nx) {
+                const double d = (r.gx.p ? r.gx.f32(y, x, c) : 0.0) - (reweight_u(r, plane, x + 1, y, c) - u);
+                qx += d * d;
+            }
+            if (ny) {
+                const double d = (r.gy.p ? r.gy.f32(y, x, c) : 0.0) - (reweight_u(r, plane, x, y + 1, c) - u);
+                qy += d * d;
+            }
+            if (nd) {
+                const double d = a.f(y, x, c) - u;
+                dq += d * d;
+            }
+        }
+    }
+    double te = 0.0, ts = 0.0;
+    if (pixel) {
+        if (we || ws) te = ts = r.scale * robust_phi<PHI>(qx + qy, r.eps);     // one phi for both forward edges
+    } else {
+        if (we) te = r.scale * robust_phi<PHI>(qx, r.eps);
+        if (ws) ts = r.scale * robust_phi<PHI>(qy, r.eps);
+    }
+    e = s = l = 0.0;
+    if (we) e = r.bwx.p ? r.bwx(y, x, set) * te : te;
+    if (ws) s = r.bwy.p ? r.bwy(y, x, set) * ts : ts;
+    if (wl) {
+        const double t = a.dscale * robust_phi_data(a.dphi, dq, a.deps);
+        l = r.lam.p ? r.lam(y, x, set) * t : t;
+    }
+}
+
+// op, cons, count: as k_weighted_reweight's.  grid = (ceil(W/kBlock), ceil(H/a.rows), sets).
+template <int PHI>
+__global__ void __launch_bounds__(kBlock)
+k_weighted_reweight_robust(RobustArgs a, double *op, long plane, double *cons, unsigned long long *__restrict__ count)
+{
+    __shared__ double east[2][kBlock];
+    __shared__ unsigned tally[2];
+    if (threadIdx.x < 2) tally[threadIdx.x] = 0;
+    __syncthreads();
+    const int x = blockIdx.x * kBlock + threadIdx.x, y0 = blockIdx.y * a.rows, ch = blockIdx.z;
+    const bool column = x < a.r.W;
+    unsigned t_dead = 0, t_edges = 0;
+    double wN = 0.0;                                                       // the s of the row above
+    if (column && y0 >= 1) {
+        double ne, nl;
+        robust_pixel<PHI>(a, plane, x, y0 - 1, ch, 2, ne, wN, nl);
+    }
+    for (int i = 0; i < a.rows; ++i) {
+        const int y = y0 + i;
+        const bool live = column && y < a.r.H;
+        double e = 0.0, s = 0.0, l = 0.0;
+        if (live) robust_pixel<PHI>(a, plane, x, y, ch, 7, e, s, l);
+        east[i & 1][threadIdx.x] = e;
+        __syncthreads();                                                   // every thread, every trip
+        if (live) {
+            double wW = 0.0;
+            if (threadIdx.x >= 1) {
+                wW = east[i & 1][threadIdx.x - 1];
+            } else if (x >= 1) {
+                double ws, wl;
+                robust_pixel<PHI>(a, plane, x - 1, y, ch, 1, wW, ws, wl);
+            }
+            adj_store(a.r.out_wx, y, x, ch, e);
+            adj_store(a.r.out_wy, y, x, ch, s);
+            adj_store(a.out_lam, y, x, ch, l);
+            unsigned n_dead = 0, n_edges = 0;
+            weighted_refresh_tail(l, e, s, [&] { return wN; }, [&] { return wW; }, x, y, ch, a.r.W, a.r.H, a.r.pitch, op, plane, 4 * plane, cons,
+                                  3 * plane, count, n_dead, n_edges);
+            t_dead += n_dead;
+            t_edges += n_edges;
+            wN = s;
+        }
+    }
+    if (t_dead) atomicAdd(&tally[0], t_dead);
+    if (t_edges) atomicAdd(&tally[1], t_edges);
+    __syncthreads();
+    if (threadIdx.x < 2 && tally[threadIdx.x]) atomicAdd(count + 2 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
+}
+
 // ccp_grid_refresh_constrained_device: new values AND a new fixed set for the installed operators, on a handle whose
 // three extra planes exist.  k_weighted_coef_fixed's arithmetic in its order -- the flags from the mask view, dd and lp
 // summed over the same operands, every weight checked, a fixed pixel's too -- so that the planes have the bits the setter

@@ -655,7 +655,8 @@ class WeightedSolver:
         self._operator = (wx, wy, lam, self._operator[3])
         self._generation += 1
 
-    def reweight(self, penalty, coupling, scale, epsilon, u=None, gx=None, gy=None, base_wx=None, base_wy=None, data_weight=None, out=None):
+    def reweight(self, penalty, coupling, scale, epsilon, u=None, gx=None, gy=None, base_wx=None, base_wy=None, data_weight=None, out=None,
+                 *, data_penalty=None, data_scale=1.0, data_epsilon=None, f=None):
         """refresh_operator with weights formed on the device from the current solution, the reweighting step of an IRLS
         loop (capi.Grid.reweight_tensor): w = base * (scale * phi(q)) per edge, q the squared residual of the edge against
         gx / gy summed over the channels (all of them on a shared operator, channel c alone on an operator per channel).
@@ -666,17 +667,35 @@ class WeightedSolver:
         `out` if given (a pair of float32 / float64 tensors, H x W on a shared operator, H x W x C on one per channel), else
         two new float64 tensors (inside a capture pass `out`).  They are recorded as the installed weights, so a later
         solve_grad's backward re-installs the right ones; solve_grad(wx=, wy=) on them is the way to unroll the outer loop
-        by hand: the gradient of an IRLS result is not provided."""
+        by hand: the gradient of an IRLS result is not provided.
+
+        data_penalty (keyword only): None makes exactly the call above.  "charbonnier" | "huber" | "reciprocal" |
+        "quadratic" reweights the data term in the same pass (capi.Grid.reweight_robust_tensor): per pixel
+        lambda = data_weight * (data_scale * phi_d(dq)), dq the sum of (f - u)^2 over the channels of the operator, phi_d on
+        data_epsilon (data_weight None: 1 there; "quadratic": phi_d = 1, f and data_epsilon are not read; `penalty` may
+        then be "quadratic" as well).  Returns (wx, wy, lam), `out` then a pair as above or a triple; the lambda formed is
+        recorded as the installed one, for solve_grad's backward."""
         import torch
         if self._operator is None:
             raise RuntimeError("WeightedSolver: set_operator first")
-        capi.reweight_ids(penalty, coupling)
+        if data_penalty is None:
+            capi.reweight_ids(penalty, coupling)
+        else:
+            capi.robust_ids(penalty, coupling, data_penalty)
         dev = self.device.index
         bwx, bwy, lam = (_weight(w, self.H, self.W, dev) for w in (base_wx, base_wy, data_weight))
-        if out is None:
+        n_out = 2 if data_penalty is None else 3
+        if out is None or len(out) < n_out:
             shape = (self.H, self.W, self.C) if self.grid.operator_channels() > 1 else (self.H, self.W)
             with torch.cuda.device(self.device):
-                out = (torch.empty(shape, dtype=torch.float64, device=self.device), torch.empty(shape, dtype=torch.float64, device=self.device))
+                out = tuple(out or ()) + tuple(torch.empty(shape, dtype=torch.float64, device=self.device) for _ in range(n_out - len(out or ())))
+        if data_penalty is not None:
+            wx, wy, formed = out
+            self.grid.reweight_robust_tensor(penalty, coupling, scale, epsilon, data_penalty, data_scale, data_epsilon, f=f, u=u, gx=gx, gy=gy,
+                                             base_wx=bwx, base_wy=bwy, lam=lam, out_wx=wx, out_wy=wy, out_lambda=formed)
+            self._operator = (wx, wy, formed, self._operator[3])
+            self._generation += 1
+            return wx, wy, formed
         wx, wy = out
         self.grid.reweight_tensor(penalty, coupling, scale, epsilon, u=u, gx=gx, gy=gy, base_wx=bwx, base_wy=bwy, lam=lam, out_wx=wx, out_wy=wy)
         self._operator = (wx, wy, lam, self._operator[3])
@@ -753,7 +772,7 @@ class WeightedSolver:
 
 def irls_solve(gx, gy, f, outer: int, iterations: int, penalty="charbonnier", coupling="edge", strength=1.0, epsilon=1e-2, data_weight=1.0,
                wx=None, wy=None, fixed=None, values=None, tolerance=1e-10, hierarchy="rescaled", precision="f64", channels="sequential",
-               smoother="point", out_dtype=None, history=None):
+               smoother="point", out_dtype=None, history=None, data_penalty=None, data_epsilon=None, first_step="quadratic"):
     """Robust gradient-domain fitting by iteratively reweighted least squares: `outer` steps of (reweight, assemble, solve)
     on one WeightedSolver, every step a launch sequence -- after set_operator nothing synchronises until the caller reads
     the result.  It minimises
@@ -774,9 +793,32 @@ def irls_solve(gx, gy, f, outer: int, iterations: int, penalty="charbonnier", co
     outer step (report C x 8, WeightedSolver.set_stop's; wx, wy the weights the step solved with): convergence is not
     checked here, that would be a read-back.  Returns x as out_dtype (None: torch.uint8, clamped, for a u8 f, else float64).
     The gradient of the result is not provided; unrolled differentiation is possible by hand with WeightedSolver.reweight's
-    `out` and solve_grad(wx=, wy=).  Strongly varying weights -- small epsilon, sharp edges -- are where smoother="line" helps."""
+    `out` and solve_grad(wx=, wy=).  Strongly varying weights -- small epsilon, sharp edges -- are where smoother="line" helps.
+
+    data_penalty: None -- the quadratic data term above, and exactly the calls made before this argument existed -- or
+    "charbonnier" | "huber" | "reciprocal": the data term is robust as well, and every step reweights the edges and lambda
+    in one call (WeightedSolver.reweight(data_penalty=...)).  The loop then minimises
+        E(u) = sum over edges 2 strength base psi(rho) + sum over pixels 2 data_weight psi_d(delta),
+    delta^2 = sum over the channel set of (u - f)^2 (all channels on a shared operator, channel c alone on an operator per
+    channel), psi_d the penalty above on data_epsilon; psi_d(sqrt(t)) is concave as well, so the step's least-squares
+    problem still majorises E.  data_weight: a python number is the call's data_scale (lambda = data_weight * phi_d), a
+    tensor its base lambda with data_scale 1.  first_step: the first step reweights from u = f, where every data residual is
+    0 and a robust lambda would be data_weight * phi_d(0) everywhere -- data_weight / data_epsilon, a uniform weight that
+    depends on data_epsilon and knows nothing of the outliers; "quadratic" (the default) therefore gives step 0 the quadratic data term
+    (data_penalty "quadratic": lambda = data_weight) and "robust" the robust one.  The step-0 problem of "quadratic"
+    majorises another energy, so the descent property holds from the second step on.  history entries are then
+    (u, report, wx, wy, lam), lam the lambda the step solved with."""
     import torch
-    capi.reweight_ids(penalty, coupling)
+    if data_penalty is None:
+        capi.reweight_ids(penalty, coupling)
+    else:
+        capi.robust_ids(penalty, coupling, data_penalty)
+        if data_penalty == "quadratic" or penalty == "quadratic":
+            raise ValueError('irls_solve: "quadratic" is data_penalty=None (and no edge penalty); WeightedSolver.reweight takes it')
+        if first_step not in ("quadratic", "robust"):
+            raise ValueError(f'first_step must be "quadratic" or "robust", not {first_step!r}')
+        if data_epsilon is None:
+            raise ValueError("irls_solve: a robust data term needs data_epsilon")
     if f is None:
         raise ValueError("irls_solve needs f: the data term, and the image the first step reweights from")
     if int(outer) < 1:
@@ -792,13 +834,21 @@ def irls_solve(gx, gy, f, outer: int, iterations: int, penalty="charbonnier", co
         s.set_stop(relative=tolerance)
         base_wx, base_wy, lam, _ = s._operator
         x = f.to(torch.float64).reshape(H, W, C)
+        robust = {}
+        if data_penalty is not None:
+            scalar = not isinstance(data_weight, torch.Tensor)
+            robust = dict(data_scale=float(data_weight) if scalar else 1.0, data_epsilon=data_epsilon, f=f)
+            if scalar:
+                lam = None
         for k in range(int(outer)):
+            if data_penalty is not None:
+                robust["data_penalty"] = "quadratic" if k == 0 and first_step == "quadratic" else data_penalty
             w = s.reweight(penalty, coupling, strength, epsilon, u=f if k == 0 else None, gx=gx, gy=gy, base_wx=base_wx, base_wy=base_wy,
-                           data_weight=lam)
+                           data_weight=lam, **robust)
             report = None if history is None else torch.zeros((C, 8), dtype=torch.float64, device=x.device)
             x, _ = s.solve(gx, gy, f, values, x0=x, report=report)
             if history is not None:
-                history.append((x, report, w[0], w[1]))
+                history.append((x, report) + tuple(w))
         if out_dtype == torch.uint8:
             return s.grid.store_u8_tensor()
         return x if out_dtype == torch.float64 else x.to(out_dtype)
@@ -818,6 +868,25 @@ def tv_denoise(image, strength, outer: int = 10, iterations: int = 400, epsilon=
     u = irls_solve(None, None, f, outer, iterations, penalty="charbonnier", coupling="pixel" if isotropic else "edge", strength=strength,
                    epsilon=epsilon, data_weight=data_weight, tolerance=tolerance, hierarchy=hierarchy, precision=precision, channels=channels,
                    smoother=smoother, out_dtype=out_dtype, history=history)
+    return u if image.dim() == 3 else u[..., 0]
+
+
+def tv_l1_denoise(image, strength, outer: int = 12, iterations: int = 400, epsilon=1e-2, data_epsilon=5e-2, isotropic=True, data_weight=1.0,
+                  tolerance=1e-10, hierarchy="rescaled", precision="f64", channels="sequential", smoother="point", first_step="quadratic",
+                  history=None):
+    """TV-L1 denoising by irls_solve: tv_denoise with the data term an L1 norm as well, u minimises
+    2 strength TV_epsilon(u) + 2 data_weight sum over pixels sqrt(|u - image|^2 + data_epsilon^2), both Charbonnier-smoothed,
+    |u - image| over all channels.  Where tv_denoise follows an outlier -- salt and pepper, a dead pixel -- as hard as its
+    square, this replaces it from its neighbourhood.  image, strength, epsilon, isotropic and the return value: as
+    tv_denoise's; data_epsilon: in the image's own units, as epsilon; first_step and the other arguments: irls_solve's
+    (history entries carry the lambda of each step)."""
+    import torch
+    f = image if image.dim() == 3 else image.unsqueeze(-1)
+    out_dtype = torch.uint8 if image.dtype == torch.uint8 else image.dtype
+    u = irls_solve(None, None, f, outer, iterations, penalty="charbonnier", coupling="pixel" if isotropic else "edge", strength=strength,
+                   epsilon=epsilon, data_weight=data_weight, tolerance=tolerance, hierarchy=hierarchy, precision=precision, channels=channels,
+                   smoother=smoother, out_dtype=out_dtype, history=history, data_penalty="charbonnier", data_epsilon=data_epsilon,
+                   first_step=first_step)
     return u if image.dim() == 3 else u[..., 0]
 
 

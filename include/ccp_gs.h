@@ -1222,8 +1222,8 @@ int ccp_grid_refresh_constrained_device(ccp_grid *g, const ccp_device_array *wx,
  *   pass's: two elements of an output at one address; also an output that shares bytes with an input view, which the
  *   neighbouring pixels' threads read).  CCP_ERR_STATE: no installed operator, or no successful ccp_grid_mg_prepare since
  *   the last call that drops what prepare built.  CCP_ERR_UNSUPPORTED: not a weighted handle.
- * Out of scope: host-pointer twins, the C++ facades, a robust data term (lambda reweighted from |u - f|), gradients through
- * the outer loop (the weights are in out_wx / out_wy for a hand-unrolled one).  Additive: the ABI version does not change. */
+ * Out of scope: host-pointer twins, the C++ facades, gradients through the outer loop (the weights are in out_wx / out_wy
+ * for a hand-unrolled one).  Additive: the ABI version does not change. */
 #define CCP_REWEIGHT_CHARBONNIER 0   /* phi = 1 / sqrt(q + eps*eps)      */
 #define CCP_REWEIGHT_HUBER       1   /* phi = 1 / fmax(sqrt(q), eps)     */
 #define CCP_REWEIGHT_RECIPROCAL  2   /* phi = 1 / (sqrt(q) + eps)        */
@@ -1238,6 +1238,50 @@ typedef struct ccp_reweight {
     const ccp_device_array *out_wx, *out_wy;              /* F32 or F64; NULL: not written */
 } ccp_reweight;
 int ccp_grid_reweight_device(ccp_grid *g, const ccp_reweight *how);
+
+/* ---- Robust data term: lambda reweighted from |u - f| in the same pass ---------------------------------------------------------
+ * TV-L1, Huber data fidelity, gradient fusion that rejects ghosts or dead pixels, a confidence map the solve estimates
+ * itself: the outer loop above with the data term sum lambda (u - f)^2 reweighted as well.
+ * ccp_grid_reweight_robust_device is ccp_grid_reweight_device whose pass also forms lambda from the data residual, so that
+ * one outlier in f no longer pulls the solution as hard as its square.  ccp_grid_assemble_*_rhs_device reads lambda from the
+ * handle's stored plane, so the reweighted lambda reaches b with no further call.
+ *   Definition (fp64 throughout, every input widened exactly, no multiply-add fused; only +, -, x, / and sqrt, each
+ *   correctly rounded; tests/robust_helpers.py is the same in numpy).
+ *   Edges: exactly as ccp_grid_reweight_device defines them from `how`, with one addition: how->penalty may be
+ *   CCP_REWEIGHT_QUADRATIC.  Then phi = 1.0 and q is not formed:  t = scale * 1.0;  w = base * t, or w = t.
+ *   (ccp_grid_reweight_device keeps refusing that penalty.)
+ *   Data, pixel (x, y) of set k:
+ *       acc = +0.0;  for each channel c of the channel set, in channel order:  r = f - u;  acc += r * r;   dq = acc
+ *   (u: how->u at (x, y), or the handle's x where how->u is NULL; f: data->f at (x, y)).
+ *       t = data->scale * phi_d(dq)   with the three phi above on data->epsilon, or phi_d = 1.0 for QUADRATIC (dq not formed)
+ *       lambda = how->lambda(y, x, k) * t,   or lambda = t where how->lambda is NULL.
+ *   A fixed pixel forms and checks its lambda as a free one does (u there is the prescribed value) and keeps its mark: the
+ *   stored plane holds -1 there.  out_lambda receives the lambda formed at every pixel, fixed ones included -- H x W for a
+ *   shared operator, H x W x channels for one per channel; an F32 output is the fp64 value rounded once.
+ *   Contract: afterwards the handle holds, bit for bit, everything ccp_grid_refresh_weights_device(g, WX, WY, L) leaves when
+ *   WX, WY and L hold the weights and the lambda defined above: the level-0 planes, ce, cs and lambda' where they exist,
+ *   every coarse level, the float copies, the census, the counts and the operator status word.  So with data->penalty
+ *   QUADRATIC, data->scale 1 and how->lambda given (base * 1.0 is base) the call equals ccp_grid_reweight_device(g, how) bit
+ *   for bit; and under CCP_MG_NULLSPACE_CONSTANT a lambda that is not 0 everywhere yields CCP_OPERATOR_NOT_FLOATING, as a
+ *   refreshed one does, while data->scale 0 keeps the operator floating.  A lambda that is not finite or < 0 (a NaN in f, an
+ *   overflow) sets CCP_OPERATOR_BAD_WEIGHT as a bad refreshed lambda does.
+ *   Launches on the handle's stream only: no allocation, no host synchronisation, no copy, no memset; it may be issued
+ *   during stream capture and returns CCP_OK.  Every mode the value refresh serves is served.
+ *   Refused on the host with nothing enqueued.  CCP_ERR_BAD_ARG: g, how or data NULL; an unknown penalty or coupling;
+ *   reserved != 0; a scale negative or not finite; an epsilon not > 0 or not finite (data->epsilon is not read for
+ *   QUADRATIC); f NULL with a penalty other than QUADRATIC; a bad view; out_lambda with two elements at one address or
+ *   sharing bytes with any input view, f and how->lambda included (out_wx, out_wy: as ccp_grid_reweight_device checks
+ *   them, against f too).  CCP_ERR_STATE and CCP_ERR_UNSUPPORTED: as ccp_grid_reweight_device.
+ * Out of scope: host-pointer twins, the C++ facades, gradients through the outer loop (the lambda formed is in out_lambda
+ * for a hand-unrolled one).  Additive: the ABI version does not change. */
+#define CCP_REWEIGHT_QUADRATIC 3     /* phi = 1.0: the term is not reweighted (this call only) */
+typedef struct ccp_reweight_data {
+    int32_t penalty, reserved;       /* CCP_REWEIGHT_CHARBONNIER | _HUBER | _RECIPROCAL | _QUADRATIC; reserved 0 */
+    double scale, epsilon;           /* scale >= 0, finite; epsilon > 0, finite (not read for QUADRATIC) */
+    const ccp_device_array *f;       /* U8 / F32 / F64, H x W x channels (stride_c 0 broadcasts); NULL only with QUADRATIC */
+    const ccp_device_array *out_lambda; /* F32 / F64, H x W (shared) or H x W x channels (per channel); NULL: not written */
+} ccp_reweight_data;
+int ccp_grid_reweight_robust_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data);
 
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
