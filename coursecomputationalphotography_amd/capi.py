@@ -420,6 +420,11 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _refs(arrs):
+    """byref of every ccp_device_array of `arrs`, None (a NULL argument) kept."""
+    return [None if a is None else C.byref(a) for a in arrs]
+
+
 def _f64(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float64)
 
@@ -1035,8 +1040,12 @@ class Grid:
     def _device(self):
         return self._torch().device("cuda", self.desc.device)
 
-    def _hwc(self, t, name, dtypes, rows=None, output=False):
-        """Check tensor `t` and return (ccp_device_array, t viewed as rows x W x C)."""
+    def _array(self, t, name, dtypes, shape, output=False, optional=True):
+        """The one check of a tensor argument, in this order: a torch tensor, on the handle's device, of one of `dtypes`,
+        of extents `shape` (None: any), without a negative stride and, an output, without overlapping elements.  Returns
+        its ccp_device_array (a stride the tensor lacks is 0), or None for None where `optional`."""
+        if t is None and optional:
+            return None
         torch = self._torch()
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a torch tensor")
@@ -1045,17 +1054,24 @@ class Grid:
         codes = {torch.uint8: DTYPE_U8, torch.float32: DTYPE_F32, torch.float64: DTYPE_F64}
         if t.dtype not in dtypes:
             raise ValueError(f"{name} must have dtype {' or '.join(str(d) for d in dtypes)}, not {t.dtype}")
-        rows = self.H if rows is None else rows
-        if t.dim() == 2 and self.C == 1:
-            t = t.unsqueeze(-1)
-        if tuple(t.shape) != (rows, self.W, self.C):
-            raise ValueError(f"{name} must be {rows} x {self.W} x {self.C}, not {tuple(t.shape)}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must be {' x '.join(str(n) for n in shape)}, not {tuple(t.shape)}")
         if any(s < 0 for s in t.stride()):
             raise ValueError(f"{name} has a negative stride")
         if output and not _no_overlap(t.shape, t.stride()):
             raise ValueError(f"{name} is an output whose elements overlap")
-        sy, sx, sc = t.stride()
-        return DeviceArray(t.data_ptr(), codes[t.dtype], 0, 0, sy, sx, sc), t
+        return DeviceArray(t.data_ptr(), codes[t.dtype], 0, 0, *t.stride(), *[0] * (3 - t.dim()))
+
+    def _hwc(self, t, name, dtypes, rows=None, output=False):
+        """Check tensor `t` and return (ccp_device_array, t viewed as rows x W x C)."""
+        if isinstance(t, self._torch().Tensor) and t.dim() == 2 and self.C == 1:
+            t = t.unsqueeze(-1)
+        shape = (self.H if rows is None else rows, self.W, self.C)
+        return self._array(t, name, dtypes, shape, output=output, optional=False), t
+
+    def _image(self, t, name, dtypes):
+        """ccp_device_array of an optional H x W x channels tensor (None: None)."""
+        return None if t is None else self._hwc(t, name, dtypes)[0]
 
     def _on_stream(self, fn, what):
         """Run `fn()` (a library call) on torch's current stream of this device, restoring the handle's stream."""
@@ -1133,20 +1149,9 @@ class Grid:
             label = label.unsqueeze(-1)
         if tuple(label.shape) != (self.H, self.W, 1):
             raise ValueError(f"label must be {self.H} x {self.W}")
-        lab = DeviceArray(*self._label_array(label))
+        lab = self._array(label, "label", (torch.uint8,), None)
         self._on_stream(lambda: self.L.ccp_grid_assemble_from_images_device(self.h, C.byref(arr), n, C.byref(lab), 1 if init_x else 0),
                         "ccp_grid_assemble_from_images_device")
-
-    def _label_array(self, label):
-        torch = self._torch()
-        if label.device.type != "cuda" or label.device.index != self.desc.device:
-            raise ValueError(f"label must be on cuda:{self.desc.device}, not {label.device}")
-        if label.dtype != torch.uint8:
-            raise ValueError(f"label must have dtype torch.uint8, not {label.dtype}")
-        if any(s < 0 for s in label.stride()):
-            raise ValueError("label has a negative stride")
-        sy, sx, sc = label.stride()
-        return label.data_ptr(), DTYPE_U8, 0, 0, sy, sx, sc
 
     def store_u8_tensor(self, out=None):
         """store_u8 into a u8 H x W x channels tensor (allocated when `out` is None)."""
@@ -1256,23 +1261,10 @@ class Grid:
         check(self.L.ccp_grid_assemble_weighted_rhs(self.h, _ptr(gx), _ptr(gy), row, _ptr(f), row, 1 if init_x else 0),
               "ccp_grid_assemble_weighted_rhs")
 
-    def _weight_array(self, t, name):
+    def _weight_array(self, t, name, output=False):
         """ccp_device_array of an H x W float32 / float64 tensor (a broadcast view of a scalar is fine), or None."""
-        if t is None:
-            return None
         torch = self._torch()
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch tensor")
-        if t.device.type != "cuda" or t.device.index != self.desc.device:
-            raise ValueError(f"{name} must be on cuda:{self.desc.device}, not {t.device}")
-        if t.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"{name} must have dtype torch.float32 or torch.float64, not {t.dtype}")
-        if tuple(t.shape) != (self.H, self.W):
-            raise ValueError(f"{name} must be {self.H} x {self.W}, not {tuple(t.shape)}")
-        if any(s < 0 for s in t.stride()):
-            raise ValueError(f"{name} has a negative stride")
-        sy, sx = t.stride()
-        return DeviceArray(t.data_ptr(), DTYPE_F64 if t.dtype == torch.float64 else DTYPE_F32, 0, 0, sy, sx, 0)
+        return self._array(t, name, (torch.float32, torch.float64), (self.H, self.W), output=output)
 
     def _mask_array(self, fixed, name="fixed"):
         """ccp_device_array of an H x W uint8, bool, float32 or float64 mask tensor."""
@@ -1280,9 +1272,7 @@ class Grid:
         if isinstance(fixed, torch.Tensor) and fixed.dtype == torch.bool:
             fixed = fixed.view(torch.uint8)
         if isinstance(fixed, torch.Tensor) and fixed.dtype == torch.uint8:
-            if tuple(fixed.shape) != (self.H, self.W):
-                raise ValueError(f"{name} must be {self.H} x {self.W}, not {tuple(fixed.shape)}")
-            return DeviceArray(*self._label_array(fixed.unsqueeze(-1)))
+            return self._array(fixed, name, (torch.uint8,), (self.H, self.W))
         return self._weight_array(fixed, name)
 
     def _channel_array(self, t, name, dtypes, output=False):
@@ -1297,6 +1287,25 @@ class Grid:
             t = t.unsqueeze(-1).expand(-1, -1, self.C)
         return self._hwc(t, name, dtypes, output=output)[0]
 
+    def _operator_marshal(self, tensors, n_op=None):
+        """How the operator-shaped arguments of a call are passed.  Returns (per_channel, arr): per_channel when the handle
+        has one operator per channel (n_op, by default operator_channels(), > 1), or has one channel and any of `tensors`
+        has 3 dimensions (one channel: the two layouts address the same elements and the library says 1 for both, so the
+        tensors decide); arr(t, name, kind) is the ccp_device_array of a weight ("plane"), a mask of fixed pixels ("mask")
+        or an output ("out"), None for None: H x W on a shared operator, H x W x channels on one per channel."""
+        torch = self._torch()
+        n_op = self.operator_channels() if n_op is None else n_op
+        per_channel = n_op > 1 or (self.C == 1 and any(isinstance(t, torch.Tensor) and t.dim() == 3 for t in tensors))
+        floats = (torch.float32, torch.float64)
+
+        def arr(t, name, kind="plane"):
+            if per_channel:
+                return self._channel_array(t, name, (torch.uint8,) + floats if kind == "mask" else floats, output=kind == "out")
+            if kind == "mask":
+                return None if t is None else self._mask_array(t, name)
+            return self._weight_array(t, name, output=kind == "out")
+        return per_channel, arr
+
     def set_weights_per_channel_tensor(self, wx=None, wy=None, lam=None, fixed=None):
         """One operator PER CHANNEL from H x W x channels float32 / float64 tensors (an H x W tensor or an expanded scalar
         serves every channel); fixed: H x W x channels uint8, bool, float32 or float64 (!= 0: fixed), None: no fixed
@@ -1307,8 +1316,7 @@ class Grid:
         floats = (torch.float32, torch.float64)
         arrs = [self._channel_array(t, n, floats) for t, n in ((wx, "wx"), (wy, "wy"), (lam, "lam"))]
         arrs.append(self._channel_array(fixed, "fixed", (torch.uint8,) + floats))
-        refs = [None if a is None else C.byref(a) for a in arrs]
-        self._on_stream(lambda: self.L.ccp_grid_set_weights_per_channel_device(self.h, *refs),
+        self._on_stream(lambda: self.L.ccp_grid_set_weights_per_channel_device(self.h, *_refs(arrs)),
                         "ccp_grid_set_weights_per_channel_device")
 
     def set_mask_tensor(self, mask):
@@ -1320,8 +1328,7 @@ class Grid:
     def set_weights_tensor(self, wx=None, wy=None, lam=None, fixed=None):
         """set_weights from H x W float32 / float64 tensors (expanded scalars broadcast); synchronises (the verdict).
         fixed: an H x W uint8, bool, float32 or float64 tensor (!= 0: fixed), read on the device; None: no fixed pixels."""
-        arrs = [self._weight_array(t, n) for t, n in ((wx, "wx"), (wy, "wy"), (lam, "lam"))]
-        refs = [None if a is None else C.byref(a) for a in arrs]
+        refs = _refs([self._weight_array(t, n) for t, n in ((wx, "wx"), (wy, "wy"), (lam, "lam"))])
         if fixed is None:
             self._on_stream(lambda: self.L.ccp_grid_set_weights_device(self.h, *refs), "ccp_grid_set_weights_device")
             return
@@ -1336,14 +1343,8 @@ class Grid:
         hierarchy kind and every mode stay; None takes the setters' defaults.  Needs an installed operator and mg_prepare
         (CcpError STATE otherwise).  The verdict stays on the device: operator_status(), or field 5 of the enqueue solve's
         report.  A refused refresh poisons the operator until the next good one; it never drops it."""
-        torch = self._torch()
-        named = ((wx, "wx"), (wy, "wy"), (lam, "lam"))
-        per_channel = self.operator_channels() > 1 or (self.C == 1 and any(isinstance(t, torch.Tensor) and t.dim() == 3 for t, _ in named))
-        if per_channel:
-            arrs = [self._channel_array(t, n, (torch.float32, torch.float64)) for t, n in named]
-        else:
-            arrs = [self._weight_array(t, n) for t, n in named]
-        refs = [None if a is None else C.byref(a) for a in arrs]
+        _, arr = self._operator_marshal((wx, wy, lam))
+        refs = _refs([arr(t, n) for t, n in ((wx, "wx"), (wy, "wy"), (lam, "lam"))])
         self._on_stream(lambda: self.L.ccp_grid_refresh_weights_device(self.h, *refs), "ccp_grid_refresh_weights_device")
 
     def reserve_constraints(self, on=True):
@@ -1359,18 +1360,8 @@ class Grid:
         refresh_weights_tensor needs and the constraint planes: reserve_constraints() before the setter, or a setter's
         mask with a fixed pixel (CcpError STATE otherwise).  Afterwards the handle holds what the setter with the same
         four tensors and mg_prepare form on a fresh reserved handle, bit for bit; constraint_info reports the new set."""
-        torch = self._torch()
-        named = ((wx, "wx"), (wy, "wy"), (lam, "lam"))
-        per_channel = self.operator_channels() > 1 or (self.C == 1 and any(isinstance(t, torch.Tensor) and t.dim() == 3
-                                                                           for t in (wx, wy, lam, fixed)))
-        if per_channel:
-            floats = (torch.float32, torch.float64)
-            arrs = [self._channel_array(t, n, floats) for t, n in named]
-            arrs.append(self._channel_array(fixed, "fixed", (torch.uint8,) + floats))
-        else:
-            arrs = [self._weight_array(t, n) for t, n in named]
-            arrs.append(None if fixed is None else self._mask_array(fixed))
-        refs = [None if a is None else C.byref(a) for a in arrs]
+        _, arr = self._operator_marshal((wx, wy, lam, fixed))
+        refs = _refs([arr(t, n) for t, n in ((wx, "wx"), (wy, "wy"), (lam, "lam"))] + [arr(fixed, "fixed", "mask")])
         self._on_stream(lambda: self.L.ccp_grid_refresh_constrained_device(self.h, *refs), "ccp_grid_refresh_constrained_device")
 
     def reweight_tensor(self, penalty, coupling, scale, epsilon, u=None, gx=None, gy=None, base_wx=None, base_wy=None, lam=None,
@@ -1386,23 +1377,28 @@ class Grid:
         shared operator and H x W x channels on one per channel, that receive the weights formed (not overlapping any
         input).  Enqueued on torch's current stream: no allocation, no synchronisation; the verdict is operator_status()."""
         ids = reweight_ids(penalty, coupling)
+        self._reweight(ids, scale, epsilon, u, gx, gy, base_wx, base_wy, lam, out_wx, out_wy)
+
+    def _reweight(self, ids, scale, epsilon, u, gx, gy, base_wx, base_wy, lam, out_wx, out_wy, data=None):
+        """reweight_tensor (data None: ccp_grid_reweight_device) and reweight_robust_tensor (data: data_scale, data_epsilon,
+        f, out_lambda; ccp_grid_reweight_robust_device) behind their checks of the names."""
         torch = self._torch()
-        floats, any_ = (torch.float32, torch.float64), (torch.uint8, torch.float32, torch.float64)
+        any_ = (torch.uint8, torch.float32, torch.float64)
         named = ((base_wx, "base_wx"), (base_wy, "base_wy"), (lam, "lam"))
-        per_channel = self.operator_channels() > 1 or (self.C == 1 and any(isinstance(t, torch.Tensor) and t.dim() == 3
-                                                                           for t in (base_wx, base_wy, lam, out_wx, out_wy)))
-        arrs = {"u": self._channel_array(u, "u", any_),
-                "gx": None if gx is None else self._hwc(gx, "gx", (torch.float32,))[0],
-                "gy": None if gy is None else self._hwc(gy, "gy", (torch.float32,))[0]}
-        if per_channel:
-            arrs.update({n: self._channel_array(t, n, floats) for t, n in named})
-            arrs.update({n: self._channel_array(t, n, floats, output=True) for t, n in ((out_wx, "out_wx"), (out_wy, "out_wy"))})
-        else:
-            arrs.update({n: self._weight_array(t, n) for t, n in named})
-            arrs.update({n: None if t is None else self._plane_out(t, n) for t, n in ((out_wx, "out_wx"), (out_wy, "out_wy"))})
+        outs = ((out_wx, "out_wx"), (out_wy, "out_wy")) + (((data[3], "out_lambda"),) if data else ())
+        _, arr = self._operator_marshal([t for t, _ in named + outs])
+        arrs = {"u": self._channel_array(u, "u", any_), "f": self._channel_array(data[2], "f", any_) if data else None,
+                "gx": self._image(gx, "gx", (torch.float32,)), "gy": self._image(gy, "gy", (torch.float32,))}
+        arrs.update({n: arr(t, n) for t, n in named})
+        arrs.update({n: arr(t, n, "out") for t, n in outs})
         arrs["lambda"] = arrs.pop("lam")
-        how = Reweight(ids[0], ids[1], float(scale), float(epsilon), *[None if arrs[n] is None else C.pointer(arrs[n]) for n in REWEIGHT_VIEWS])
-        self._on_stream(lambda: self.L.ccp_grid_reweight_device(self.h, C.byref(how)), "ccp_grid_reweight_device")
+        ptr = lambda n: None if arrs[n] is None else C.pointer(arrs[n])
+        how = Reweight(ids[0], ids[1], float(scale), float(epsilon), *[ptr(n) for n in REWEIGHT_VIEWS])
+        if data is None:
+            self._on_stream(lambda: self.L.ccp_grid_reweight_device(self.h, C.byref(how)), "ccp_grid_reweight_device")
+            return
+        rob = ReweightData(ids[2], 0, float(data[0]), 0.0 if data[1] is None else float(data[1]), ptr("f"), ptr("out_lambda"))
+        self._on_stream(lambda: self.L.ccp_grid_reweight_robust_device(self.h, C.byref(how), C.byref(rob)), "ccp_grid_reweight_robust_device")
 
     def reweight_robust_tensor(self, penalty, coupling, scale, epsilon, data_penalty, data_scale, data_epsilon, f=None, u=None, gx=None,
                                gy=None, base_wx=None, base_wy=None, lam=None, out_wx=None, out_wy=None, out_lambda=None):
@@ -1414,26 +1410,7 @@ class Grid:
         data_penalty "quadratic"; out_lambda: a float32 / float64 tensor shaped as out_wx that receives the lambda formed,
         fixed pixels included.  The other arguments, the stream and the verdict: as reweight_tensor's."""
         ids = robust_ids(penalty, coupling, data_penalty)
-        torch = self._torch()
-        floats, any_ = (torch.float32, torch.float64), (torch.uint8, torch.float32, torch.float64)
-        named = ((base_wx, "base_wx"), (base_wy, "base_wy"), (lam, "lam"))
-        outs = ((out_wx, "out_wx"), (out_wy, "out_wy"), (out_lambda, "out_lambda"))
-        per_channel = self.operator_channels() > 1 or (self.C == 1 and any(isinstance(t, torch.Tensor) and t.dim() == 3
-                                                                           for t in (base_wx, base_wy, lam, out_wx, out_wy, out_lambda)))
-        arrs = {"u": self._channel_array(u, "u", any_), "f": self._channel_array(f, "f", any_),
-                "gx": None if gx is None else self._hwc(gx, "gx", (torch.float32,))[0],
-                "gy": None if gy is None else self._hwc(gy, "gy", (torch.float32,))[0]}
-        if per_channel:
-            arrs.update({n: self._channel_array(t, n, floats) for t, n in named})
-            arrs.update({n: self._channel_array(t, n, floats, output=True) for t, n in outs})
-        else:
-            arrs.update({n: self._weight_array(t, n) for t, n in named})
-            arrs.update({n: None if t is None else self._plane_out(t, n) for t, n in outs})
-        arrs["lambda"] = arrs.pop("lam")
-        ptr = lambda n: None if arrs[n] is None else C.pointer(arrs[n])
-        how = Reweight(ids[0], ids[1], float(scale), float(epsilon), *[ptr(n) for n in REWEIGHT_VIEWS])
-        data = ReweightData(ids[2], 0, float(data_scale), 0.0 if data_epsilon is None else float(data_epsilon), ptr("f"), ptr("out_lambda"))
-        self._on_stream(lambda: self.L.ccp_grid_reweight_robust_device(self.h, C.byref(how), C.byref(data)), "ccp_grid_reweight_robust_device")
+        self._reweight(ids, scale, epsilon, u, gx, gy, base_wx, base_wy, lam, out_wx, out_wy, data=(data_scale, data_epsilon, f, out_lambda))
 
     def operator_status(self) -> int:
         """The operator status word of the last refresh_weights_tensor (0: good; 1: a bad weight, 2: out of float range in
@@ -1446,21 +1423,16 @@ class Grid:
         """assemble_constrained_rhs from H x W x channels tensors: gx, gy float32; f and values u8, float32 or float64."""
         torch = self._torch()
         any_ = (torch.uint8, torch.float32, torch.float64)
-        a = None if gx is None else self._hwc(gx, "gx", (torch.float32,))[0]
-        b = None if gy is None else self._hwc(gy, "gy", (torch.float32,))[0]
-        c = None if f is None else self._hwc(f, "f", any_)[0]
-        d = None if values is None else self._hwc(values, "values", any_)[0]
-        refs = [None if v is None else C.byref(v) for v in (a, b, c, d)]
+        refs = _refs([self._image(gx, "gx", (torch.float32,)), self._image(gy, "gy", (torch.float32,)), self._image(f, "f", any_),
+                      self._image(values, "values", any_)])
         self._on_stream(lambda: self.L.ccp_grid_assemble_constrained_rhs_device(self.h, *refs, 1 if init_x else 0),
                         "ccp_grid_assemble_constrained_rhs_device")
 
     def assemble_weighted_rhs_tensor(self, gx=None, gy=None, f=None, init_x: bool = False):
         """assemble_weighted_rhs from H x W x channels tensors: gx, gy float32, f u8, float32 or float64."""
         torch = self._torch()
-        a = None if gx is None else self._hwc(gx, "gx", (torch.float32,))[0]
-        b = None if gy is None else self._hwc(gy, "gy", (torch.float32,))[0]
-        c = None if f is None else self._hwc(f, "f", (torch.uint8, torch.float32, torch.float64))[0]
-        refs = [None if v is None else C.byref(v) for v in (a, b, c)]
+        refs = _refs([self._image(gx, "gx", (torch.float32,)), self._image(gy, "gy", (torch.float32,)),
+                      self._image(f, "f", (torch.uint8, torch.float32, torch.float64))])
         self._on_stream(lambda: self.L.ccp_grid_assemble_weighted_rhs_device(self.h, *refs, 1 if init_x else 0),
                         "ccp_grid_assemble_weighted_rhs_device")
 
@@ -1471,13 +1443,6 @@ class Grid:
         torch = self._torch()
         arr, _ = self._hwc(grad, "grad", (torch.float32, torch.float64))
         self._on_stream(lambda: self.L.ccp_grid_adjoint_begin_device(self.h, C.byref(arr)), "ccp_grid_adjoint_begin_device")
-
-    def _plane_out(self, t, name):
-        """ccp_device_array of an H x W float32 / float64 output tensor."""
-        arr = self._weight_array(t, name)
-        if not _no_overlap(t.shape, t.stride()):
-            raise ValueError(f"{name} is an output whose elements overlap")
-        return arr
 
     def weighted_adjoint_tensor(self, u, grad=None, gx=None, gy=None, f=None, wx=None, wy=None, lam=None, fixed=None,
                                 want=("wx", "wy", "lam", "gx", "gy", "f", "values"), out=None, dtype=None):
@@ -1493,12 +1458,9 @@ class Grid:
         torch = self._torch()
         want = tuple(want)
         n_op = C.c_int32(1)                                          # (no operator, not weighted: the call below refuses)
-        per_channel = self.L.ccp_grid_operator_channels(self.h, C.byref(n_op)) == 0 and n_op.value > 1
-        if self.C == 1:
-            # one channel: the two layouts address the same elements, and ccp_grid_operator_channels cannot tell them apart
-            # (it says 1 for both), so the tensors decide: an H x W x 1 weight, mask or weight gradient is a stack of one
-            given = [wx, wy, lam, fixed] + [(out or {}).get(n) for n in ("wx", "wy", "lam")]
-            per_channel = any(isinstance(t, torch.Tensor) and t.dim() == 3 for t in given)
+        if self.L.ccp_grid_operator_channels(self.h, C.byref(n_op)) != 0:
+            n_op.value = 1
+        per_channel, arr = self._operator_marshal([wx, wy, lam, fixed] + [(out or {}).get(n) for n in ("wx", "wy", "lam")], n_op.value)
         planes, images = ("wx", "wy", "lam"), ("gx", "gy", "f", "values")
         unknown = [n for n in want if n not in planes + images] + [n for n in (out or {}) if n not in want]
         if unknown:
@@ -1506,17 +1468,9 @@ class Grid:
         if "values" in want and grad is None:
             raise ValueError("the gradient of values needs grad")
         floats, any_ = (torch.float32, torch.float64), (torch.uint8, torch.float32, torch.float64)
-        ins = {"u": self._hwc(u, "u", (torch.float64,))[0],
-               "grad_x": None if grad is None else self._hwc(grad, "grad", floats)[0],
-               "gx": None if gx is None else self._hwc(gx, "gx", (torch.float32,))[0],
-               "gy": None if gy is None else self._hwc(gy, "gy", (torch.float32,))[0],
-               "f": None if f is None else self._hwc(f, "f", any_)[0]}
-        if per_channel:
-            ins.update({"wx": self._channel_array(wx, "wx", floats), "wy": self._channel_array(wy, "wy", floats),
-                        "lambda": self._channel_array(lam, "lam", floats), "fixed": self._channel_array(fixed, "fixed", any_)})
-        else:
-            ins.update({"wx": self._weight_array(wx, "wx"), "wy": self._weight_array(wy, "wy"), "lambda": self._weight_array(lam, "lam"),
-                        "fixed": None if fixed is None else self._mask_array(fixed)})
+        ins = {"u": self._hwc(u, "u", (torch.float64,))[0], "grad_x": self._image(grad, "grad", floats),
+               "gx": self._image(gx, "gx", (torch.float32,)), "gy": self._image(gy, "gy", (torch.float32,)), "f": self._image(f, "f", any_),
+               "wx": arr(wx, "wx"), "wy": arr(wy, "wy"), "lambda": arr(lam, "lam"), "fixed": arr(fixed, "fixed", "mask")}
         result, outs = {}, {}
         for n in want:
             t = (out or {}).get(n)
@@ -1525,7 +1479,7 @@ class Grid:
                 with torch.cuda.device(self._device()):
                     t = torch.empty(shape, dtype=dtype or torch.float64, device=self._device())
             plane = n in planes and not per_channel
-            outs["g_lambda" if n == "lam" else "g_" + n] = self._plane_out(t, n) if plane else self._hwc(t, n, floats, output=True)[0]
+            outs["g_lambda" if n == "lam" else "g_" + n] = arr(t, n, "out") if plane else self._hwc(t, n, floats, output=True)[0]
             result[n] = t
         a = AdjointInputs(*[None if ins[n] is None else C.pointer(ins[n]) for n in ADJOINT_INPUTS])
         b = AdjointOutputs(*[None if outs.get(n) is None else C.pointer(outs[n]) for n in ADJOINT_OUTPUTS])

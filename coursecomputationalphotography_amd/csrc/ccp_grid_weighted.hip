@@ -273,22 +273,30 @@ int count_live(ccp_grid *g, const double *d, long *live)
     return CCP_OK;
 }
 
+// the three weight views of a setter or a refresh, checked in their order (H x W x channels); an absent one reads 1, 1, 0
+int weight_views(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda, int channels,
+                 ImageView v[3])
+{
+    const ccp_device_array *src[3] = {wx, wy, lambda};
+    const double dflt[3] = {1.0, 1.0, 0.0};
+    for (int i = 0; i < 3; ++i) {
+        if (src[i]) CCP_TRY(check_view(g, src[i], kF32F64, false, 1, g->geom.H, g->geom.W, channels));
+        v[i] = image_view(src[i], dflt[i]);
+    }
+    return CCP_OK;
+}
+
 // ccp_grid_set_weights_[constrained_]device and ccp_grid_set_weights_per_channel_device: the views are H x W for the
 // shared operator and H x W x channels for one operator per channel
 int set_weights_device(ccp_grid *g, bool per_channel, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
                        const ccp_device_array *fixed)
 {
     CCP_TRY(weighted_handle(g));
-    const int W = g->desc.width, H = g->desc.height, C = per_channel ? g->desc.channels : 1;
-    const ccp_device_array *src[3] = {wx, wy, lambda};
-    const double dflt[3] = {1.0, 1.0, 0.0};
+    const int C = per_channel ? g->desc.channels : 1;
     ImageView v[3];
-    for (int i = 0; i < 3; ++i) {
-        if (src[i]) CCP_TRY(check_view(g, src[i], kF32F64, false, 1, H, W, C));
-        v[i] = image_view(src[i], dflt[i]);
-    }
+    CCP_TRY(weight_views(g, wx, wy, lambda, C, v));
     if (!fixed) return form_operator(g, per_channel, v[0], v[1], v[2], nullptr);
-    CCP_TRY(check_view(g, fixed, kF32F64 | kU8, false, 1, H, W, C));
+    CCP_TRY(check_view(g, fixed, kF32F64 | kU8, false, 1, g->geom.H, g->geom.W, C));
     const ImageView m = image_view(fixed, 0.0);
     return form_operator(g, per_channel, v[0], v[1], v[2], &m);
 }
@@ -315,9 +323,22 @@ int weighted_apply_mode(ccp_grid *g)
     return CCP_OK;
 }
 
+// Every enqueue-only pass that gives the installed operators new values: `launch` enqueues the kernel that rewrites level 0
+// and counts into the first `words` words of rcount, which mg_refresh_begin clears with the status word; mg_refresh rebuilds
+// what mg_prepare derived.  Launches on the handle's stream, nothing else.
+template <typename Launch>
+int refresh_pass(ccp_grid *g, int words, Launch &&launch)
+{
+    CCP_TRY(mg_refresh_begin(g, words));
+    launch();
+    CCP_HIP(hipGetLastError());
+    g->refreshed = true;
+    g->mg_nullspace.floating = -1;      // the census verdict the host remembers is the old values': a later prepare or solve asks again
+    return mg_refresh(g);
+}
+
 // ccp_grid_refresh_weights_device (with_mask false: the fixed set the lambda plane marks is kept) and
-// ccp_grid_refresh_constrained_device (the fixed set of `fixed`, NULL: the empty one): one check of the views, one
-// mg_refresh_begin / mg_refresh pair around the pass over level 0
+// ccp_grid_refresh_constrained_device (the fixed set of `fixed`, NULL: the empty one)
 int refresh_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_array *wy, const ccp_device_array *lambda,
                    const ccp_device_array *fixed, bool with_mask)
 {
@@ -325,37 +346,40 @@ int refresh_device(ccp_grid *g, const ccp_device_array *wx, const ccp_device_arr
     if (!g->has_op) return CCP_ERR_STATE;                                  // (the operator's kind decides the views' extents)
     const Geom &geo = g->geom;
     const int sets = g->per_channel ? g->desc.channels : 1;
-    const ccp_device_array *src[3] = {wx, wy, lambda};
-    const double dflt[3] = {1.0, 1.0, 0.0};
     ImageView v[3];
-    for (int i = 0; i < 3; ++i) {
-        if (src[i]) CCP_TRY(check_view(g, src[i], kF32F64, false, 1, geo.H, geo.W, sets));
-        v[i] = image_view(src[i], dflt[i]);
-    }
+    CCP_TRY(weight_views(g, wx, wy, lambda, sets, v));
     if (fixed) CCP_TRY(check_view(g, fixed, kF32F64 | kU8, false, 1, geo.H, geo.W, sets));
     if (with_mask && !g->has_fixed) return CCP_ERR_STATE;                  // the three planes: reserved, or a setter's mask had a fixed pixel
-    // from here on: launches on the handle's stream, nothing else.  The first clears the status word and rcount (a new
-    // fixed set: the fixed-pixel words behind it too, which a value refresh leaves as they are).
-    CCP_TRY(mg_refresh_begin(g, with_mask ? kRefreshFixedAt + sets : 1 + 3 * sets));
     const long n = geo.ch_stride;
-    if (with_mask)
+    if (!with_mask)
+        return refresh_pass(g, 1 + 3 * sets, [&] {
+            hipLaunchKernelGGL(k_weighted_refresh, pixels(geo.W, geo.H, sets), dim3(kBlock), 0, g->stream, v[0], v[1], v[2], geo.W, geo.H,
+                               geo.pitch, g->wop.p, n, 4 * n, g->has_fixed ? g->wcons.p : nullptr, 3 * n, g->rcount.p);
+        });
+    // a new fixed set: its words behind the others are cleared and counted too, and ccp_grid_constraint_info reads them from now on
+    return refresh_pass(g, kRefreshFixedAt + sets, [&] {
         hipLaunchKernelGGL(k_weighted_fixed_refresh, pixels(geo.W, geo.H, sets), dim3(kBlock), 0, g->stream, v[0], v[1], v[2],
                            image_view(fixed, 0.0), geo.W, geo.H, geo.pitch, g->wop.p, n, 4 * n, g->wcons.p, 3 * n, g->rcount.p,
                            g->rcount.p + kRefreshFixedAt);
-    else
-        hipLaunchKernelGGL(k_weighted_refresh, pixels(geo.W, geo.H, sets), dim3(kBlock), 0, g->stream, v[0], v[1], v[2], geo.W, geo.H, geo.pitch,
-                           g->wop.p, n, 4 * n, g->has_fixed ? g->wcons.p : nullptr, 3 * n, g->rcount.p);
-    CCP_HIP(hipGetLastError());
-    g->refreshed = true;
-    if (with_mask) g->fixed_on_device = true;   // the host's pc_fixed is the old set's: ccp_grid_constraint_info reads the device's from now on
-    g->mg_nullspace.floating = -1;      // the census verdict the host remembers is the old values': a later prepare or solve asks again
-    return mg_refresh(g);
+        g->fixed_on_device = true;
+    });
 }
 
 AdjOut adj_out(const ccp_device_array *a);                               // (with the adjoint pass, below)
 
 static_assert(kPhiCharbonnier == CCP_REWEIGHT_CHARBONNIER && kPhiHuber == CCP_REWEIGHT_HUBER && kPhiReciprocal == CCP_REWEIGHT_RECIPROCAL,
               "k_weighted_reweight's PHI is the header's penalty id");
+static_assert(kPhiQuadratic == CCP_REWEIGHT_QUADRATIC, "k_weighted_reweight_robust's PHI is the header's penalty id");
+
+// a checked penalty id as a template argument: f(P) with decltype(P)::value == penalty (as with_bool, for the kernels' PHI)
+template <typename F>
+void with_phi(int penalty, F &&f)
+{
+    if (penalty == kPhiCharbonnier) f(std::integral_constant<int, kPhiCharbonnier>{});
+    else if (penalty == kPhiHuber) f(std::integral_constant<int, kPhiHuber>{});
+    else if (penalty == kPhiReciprocal) f(std::integral_constant<int, kPhiReciprocal>{});
+    else f(std::integral_constant<int, kPhiQuadratic>{});
+}
 
 // the bytes [lo, hi) a view of extents H x W x C spans
 void view_span(const ccp_device_array *a, long H, long W, long C, uintptr_t *lo, uintptr_t *hi)
@@ -437,32 +461,6 @@ int reweight_checked(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_da
     return CCP_OK;
 }
 
-// ccp_grid_reweight_device: refresh_device without a mask, the level-0 pass forming the weights instead of reading them
-int reweight_device(ccp_grid *g, const ccp_reweight *how)
-{
-    ReweightArgs a{};
-    CCP_TRY(reweight_checked(g, how, nullptr, &a));
-    const Geom &geo = g->geom;
-    const int sets = g->per_channel ? g->desc.channels : 1;
-    // from here on: launches on the handle's stream, nothing else
-    CCP_TRY(mg_refresh_begin(g, 1 + 3 * sets));
-    const long n = geo.ch_stride;
-    double *cons = g->has_fixed ? g->wcons.p : nullptr;
-    const dim3 grid = pixels(geo.W, geo.H, sets);
-    if (how->penalty == CCP_REWEIGHT_CHARBONNIER)
-        hipLaunchKernelGGL((k_weighted_reweight<kPhiCharbonnier>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
-    else if (how->penalty == CCP_REWEIGHT_HUBER)
-        hipLaunchKernelGGL((k_weighted_reweight<kPhiHuber>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
-    else
-        hipLaunchKernelGGL((k_weighted_reweight<kPhiReciprocal>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
-    CCP_HIP(hipGetLastError());
-    g->refreshed = true;
-    g->mg_nullspace.floating = -1;      // as refresh_device: the census verdict the host remembers is the old values'
-    return mg_refresh(g);
-}
-
-static_assert(kPhiQuadratic == CCP_REWEIGHT_QUADRATIC, "k_weighted_reweight_robust's PHI is the header's penalty id");
-
 // Rows per strip of k_weighted_reweight_robust, by tools/robust_bench.py (NOTES R39.1 has the figures of 4, 8, 16 and 32 at
 // both sizes): a tall strip forms fewer north weights twice, but a canvas cut into few strips leaves CUs without a block.
 // At 4096^2 x 3 the pass was the faster the taller the strip (32: 16 x 128 blocks, 8 per CU of the 256), at 752 x 566 x 3 the
@@ -481,37 +479,37 @@ int robust_rows(int W, int H, int sets)
     return 4;
 }
 
-// ccp_grid_reweight_robust_device: reweight_device whose level-0 pass forms lambda from |u - f| as well
-int reweight_robust_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data)
+// ccp_grid_reweight_device (data: null) and ccp_grid_reweight_robust_device: refresh_device without a mask whose level-0 pass
+// forms the weights (with `data`: lambda from |u - f| too, in the marching kernel)
+int reweight_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data)
 {
-    if (!data) return CCP_ERR_BAD_ARG;
     RobustArgs a{};
     CCP_TRY(reweight_checked(g, how, data, &a.r));
     const Geom &geo = g->geom;
     const int sets = g->per_channel ? g->desc.channels : 1;
-    // from here on: launches on the handle's stream, nothing else
-    CCP_TRY(mg_refresh_begin(g, 1 + 3 * sets));
     const long n = geo.ch_stride;
+    double *cons = g->has_fixed ? g->wcons.p : nullptr;
+    if (!data)
+        return refresh_pass(g, 1 + 3 * sets, [&] {
+            with_phi(how->penalty, [&](auto P) {
+                if constexpr (decltype(P)::value != kPhiQuadratic)           // (which reweight_checked refuses without `data`)
+                    hipLaunchKernelGGL((k_weighted_reweight<decltype(P)::value>), pixels(geo.W, geo.H, sets), dim3(kBlock), 0, g->stream, a.r,
+                                       g->wop.p, n, cons, g->rcount.p);
+            });
+        });
     a.rows = robust_rows(geo.W, geo.H, sets);
     a.dphi = data->penalty;
     a.dscale = data->scale;
     a.deps = data->penalty == CCP_REWEIGHT_QUADRATIC ? 1.0 : data->epsilon;   // (not read for QUADRATIC)
     a.f = image_view(data->f, 0.0);
     a.out_lam = adj_out(data->out_lambda);
-    double *cons = g->has_fixed ? g->wcons.p : nullptr;
     const dim3 grid((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)((geo.H + a.rows - 1) / a.rows), (unsigned)sets);
-    if (how->penalty == CCP_REWEIGHT_CHARBONNIER)
-        hipLaunchKernelGGL((k_weighted_reweight_robust<kPhiCharbonnier>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
-    else if (how->penalty == CCP_REWEIGHT_HUBER)
-        hipLaunchKernelGGL((k_weighted_reweight_robust<kPhiHuber>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
-    else if (how->penalty == CCP_REWEIGHT_RECIPROCAL)
-        hipLaunchKernelGGL((k_weighted_reweight_robust<kPhiReciprocal>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
-    else
-        hipLaunchKernelGGL((k_weighted_reweight_robust<kPhiQuadratic>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons, g->rcount.p);
-    CCP_HIP(hipGetLastError());
-    g->refreshed = true;
-    g->mg_nullspace.floating = -1;      // as refresh_device: the census verdict the host remembers is the old values'
-    return mg_refresh(g);
+    return refresh_pass(g, 1 + 3 * sets, [&] {
+        with_phi(how->penalty, [&](auto P) {
+            hipLaunchKernelGGL((k_weighted_reweight_robust<decltype(P)::value>), grid, dim3(kBlock), 0, g->stream, a, g->wop.p, n, cons,
+                               g->rcount.p);
+        });
+    });
 }
 
 }  // namespace
@@ -630,12 +628,13 @@ try {
 
 int ccp_grid_reweight_device(ccp_grid *g, const ccp_reweight *how)
 try {
-    return reweight_device(g, how);
+    return reweight_device(g, how, nullptr);
 } CCP_ABI_CATCH
 
 int ccp_grid_reweight_robust_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data)
 try {
-    return reweight_robust_device(g, how, data);
+    if (!data) return CCP_ERR_BAD_ARG;
+    return reweight_device(g, how, data);
 } CCP_ABI_CATCH
 
 int ccp_grid_reserve_constraints(ccp_grid *g, int32_t on)

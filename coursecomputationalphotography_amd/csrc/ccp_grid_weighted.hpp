@@ -74,78 +74,27 @@ k_weighted_coef(ImageView wx, ImageView wy, ImageView lam, int W, int H, long pi
     o[3 * plane + at] = l;
 }
 
-// k_weighted_coef with a mask of fixed pixels per set (channel k of `fixed`, != 0 is fixed): the planes described at the
-// top, ce, cs, lambda' of set k at cons + k * cons_stride, every weight checked as there (the fixed pixels' weights too).
-// count[0]: the verdict of all sets; count[1 + 3 k ..]: set k's fixed pixels, free pixels with d = 0 and edges with
-// exactly one fixed end -- per block in LDS, then one atomic per non-zero count.
-static __global__ void __launch_bounds__(kBlock)
-k_weighted_coef_fixed(ImageView wx, ImageView wy, ImageView lam, ImageView fixed, int W, int H, long pitch, double *__restrict__ op, long plane,
-                      long op_stride, double *__restrict__ cons, long cons_stride, unsigned long long *__restrict__ count)
-{
-    __shared__ unsigned tally[3];
-    if (threadIdx.x < 3) tally[threadIdx.x] = 0;
-    __syncthreads();
-    const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y, ch = blockIdx.z;
-    unsigned n_fixed = 0, n_dead = 0, n_edges = 0;
-    if (x < W) {
-        const double l = lam(y, x, ch);
-        const double e = x + 1 < W ? wx(y, x, ch) : 0.0;
-        const double s = y + 1 < H ? wy(y, x, ch) : 0.0;
-        if (!(weight_ok(l) && weight_ok(e) && weight_ok(s))) atomicOr(count, 1ull);
-        const bool fp = fixed(y, x, ch) != 0;
-        const bool fN = y >= 1 && fixed(y - 1, x, ch) != 0, fW = x >= 1 && fixed(y, x - 1, ch) != 0;
-        const bool fE = x + 1 < W && fixed(y, x + 1, ch) != 0, fS = y + 1 < H && fixed(y + 1, x, ch) != 0;
-        const double wN = y >= 1 ? wy(y - 1, x, ch) : 0.0, wW = x >= 1 ? wx(y, x - 1, ch) : 0.0;
-        double dd = l;
-        if (y >= 1) dd += wN;
-        if (x >= 1) dd += wW;
-        if (x + 1 < W) dd += e;
-        if (y + 1 < H) dd += s;
-        double lp = l;
-        if (fN) lp += wN;
-        if (fW) lp += wW;
-        if (fE) lp += e;
-        if (fS) lp += s;
-        const bool be = x + 1 < W && fp != fE, bs = y + 1 < H && fp != fS;   // edges with exactly one fixed end
-        double *__restrict__ o = op + (long)ch * op_stride, *__restrict__ k = cons + (long)ch * cons_stride;
-        const long at = w_at(pitch, x, y);
-        o[at] = fp ? 0.0 : dd;
-        o[plane + at] = fp || fE ? 0.0 : e;
-        o[2 * plane + at] = fp || fS ? 0.0 : s;
-        o[3 * plane + at] = fp ? -1.0 : l;
-        k[at] = be ? e : 0.0;
-        k[plane + at] = bs ? s : 0.0;
-        k[2 * plane + at] = fp ? 0.0 : lp;
-        n_fixed = fp;
-        n_dead = !fp && dd == 0.0;
-        n_edges = (unsigned)be + (unsigned)bs;
-    }
-    if (n_fixed) atomicAdd(&tally[0], n_fixed);
-    if (n_dead) atomicAdd(&tally[1], n_dead);
-    if (n_edges) atomicAdd(&tally[2], n_edges);
-    __syncthreads();
-    if (threadIdx.x < 3 && tally[threadIdx.x]) atomicAdd(count + 1 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
-}
-
-// The tail of a pass that gives the installed operators new values and keeps their fixed set: pixel (x, y) of set `ch`
-// from its lambda l, its own east and south weights e, s (+0.0 where the edge is absent) and the weights of the edges from
-// the north and the west (the neighbours' s and e), which `north()` and `west()` yield where those edges exist --
-// k_weighted_refresh reads them from views, k_weighted_reweight forms them -- so that the two passes cannot drift apart:
-// the check of l, e, s, the marks from the sign of the stored lambda plane, the sums dd and lp in their order, the stores
-// (cons: null without the three planes) and the pixel's two tallies.  (The two weights arrive as callables so that
-// k_weighted_refresh keeps the instruction order, and with it the registers, it had before this function existed.)
-template <class North, class West>
-__device__ __forceinline__ void weighted_refresh_tail(double l, double e, double s, North north, West west, int x, int y, int ch, int W, int H,
-                                                      long pitch, double *op, long plane, long op_stride, double *cons, long cons_stride,
-                                                      unsigned long long *__restrict__ count, unsigned &n_dead, unsigned &n_edges)
+// The formation of pixel (x, y) of set `ch` where fixed pixels may exist, ONE body for every kernel below that forms the
+// planes described at the top, so that the setter, the refreshes and the reweights cannot drift apart: the check of its
+// lambda l and its own east and south weights e, s (+0.0 where the edge is absent), the five fixed flags from
+// `fixed_at(x, y)` (a mask view, or the sign of the stored lambda plane), the weights of the edges from the north and the
+// west (the neighbours' s and e) from `north()` and `west()` where those edges exist (read from views, formed, or carried
+// in a register), the sums dd and lp in their order, the stores and the pixel's three tallies.
+// POISON: a lambda that fails the check is stored as +0.0 (every refresh: a refused one poisons the operator's values but
+// never its fixed marks, which stay -1); the setter stores it as it is and drops the operator.  CONS: the three extra
+// planes exist whatever `cons` says (the mask kernels); otherwise cons is null without them.
+// Order.  north() and west() are evaluated after the flags, and the planes' addresses are formed after be / bs, just before
+// the first store: the instruction order the kernels had before this function existed, which their pinned register
+// counts (tests/test_isa_refresh*.py) depend on.
+template <bool POISON, bool CONS, class Fixed, class North, class West>
+__device__ __forceinline__ void weighted_form(double l, double e, double s, Fixed fixed_at, North north, West west, int x, int y, int ch, int W,
+                                              int H, long pitch, double *op, long plane, long op_stride, double *cons, long cons_stride,
+                                              unsigned long long *__restrict__ count, unsigned &n_fixed, unsigned &n_dead, unsigned &n_edges)
 {
     if (!(weight_ok(l) && weight_ok(e) && weight_ok(s))) atomicOr(count, 1ull);
-    double *o = op + (long)ch * op_stride;
-    const double *mark = o + 3 * plane;
-    const long at = w_at(pitch, x, y);
-    const bool fp = mark[at] < 0.0;
-    const bool fN = y >= 1 && mark[w_at(pitch, x, y - 1)] < 0.0, fW = x >= 1 && mark[w_at(pitch, x - 1, y)] < 0.0;
-    const bool fE = x + 1 < W && mark[w_at(pitch, x + 1, y)] < 0.0, fS = y + 1 < H && mark[w_at(pitch, x, y + 1)] < 0.0;
+    const bool fp = fixed_at(x, y);
+    const bool fN = y >= 1 && fixed_at(x, y - 1), fW = x >= 1 && fixed_at(x - 1, y);
+    const bool fE = x + 1 < W && fixed_at(x + 1, y), fS = y + 1 < H && fixed_at(x, y + 1);
     const double wN = y >= 1 ? north() : 0.0, wW = x >= 1 ? west() : 0.0;
     double dd = l;
     if (y >= 1) dd += wN;
@@ -158,26 +107,95 @@ __device__ __forceinline__ void weighted_refresh_tail(double l, double e, double
     if (fE) lp += e;
     if (fS) lp += s;
     const bool be = x + 1 < W && fp != fE, bs = y + 1 < H && fp != fS;   // edges with exactly one fixed end
+    double *o = op + (long)ch * op_stride;
+    const long at = w_at(pitch, x, y);
     o[at] = fp ? 0.0 : dd;
     o[plane + at] = fp || fE ? 0.0 : e;
     o[2 * plane + at] = fp || fS ? 0.0 : s;
-    o[3 * plane + at] = fp ? -1.0 : weight_ok(l) ? l : 0.0;
-    if (cons) {
+    o[3 * plane + at] = fp ? -1.0 : !POISON || weight_ok(l) ? l : 0.0;
+    if (CONS || cons) {
         double *k = cons + (long)ch * cons_stride;
         k[at] = be ? e : 0.0;
         k[plane + at] = bs ? s : 0.0;
         k[2 * plane + at] = fp ? 0.0 : lp;
     }
+    n_fixed = fp;
     n_dead = !fp && dd == 0.0;
     n_edges = (unsigned)be + (unsigned)bs;
 }
 
+// The two kernels that take the fixed set from a mask (channel k of `fixed`, != 0 is fixed), up to their block's counts:
+// every set's planes from the four views, every weight checked as k_weighted_coef checks it (the fixed pixels' weights
+// too); tally: the block's fixed pixels, free pixels with d = 0 and edges with exactly one fixed end, complete on return.
+template <bool POISON>
+__device__ __forceinline__ void weighted_mask_block(const ImageView &wx, const ImageView &wy, const ImageView &lam, const ImageView &fixed, int W,
+                                                    int H, long pitch, double *op, long plane, long op_stride, double *cons, long cons_stride,
+                                                    unsigned long long *__restrict__ count, unsigned (&tally)[3])
+{
+    if (threadIdx.x < 3) tally[threadIdx.x] = 0;
+    __syncthreads();
+    const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y, ch = blockIdx.z;
+    unsigned n_fixed = 0, n_dead = 0, n_edges = 0;
+    if (x < W) {
+        const double l = lam(y, x, ch);
+        const double e = x + 1 < W ? wx(y, x, ch) : 0.0;
+        const double s = y + 1 < H ? wy(y, x, ch) : 0.0;
+        weighted_form<POISON, true>(l, e, s, [&](int fx, int fy) { return fixed(fy, fx, ch) != 0; }, [&] { return wy(y - 1, x, ch); },
+                                    [&] { return wx(y, x - 1, ch); }, x, y, ch, W, H, pitch, op, plane, op_stride, cons, cons_stride, count,
+                                    n_fixed, n_dead, n_edges);
+    }
+    if (n_fixed) atomicAdd(&tally[0], n_fixed);
+    if (n_dead) atomicAdd(&tally[1], n_dead);
+    if (n_edges) atomicAdd(&tally[2], n_edges);
+    __syncthreads();
+}
+
+// k_weighted_coef with a mask of fixed pixels per set: the setter's kernel, ce, cs, lambda' of set k at
+// cons + k * cons_stride.  count[0]: the verdict of all sets; count[1 + 3 k ..]: set k's three counts, one atomic per
+// non-zero count of a block.  grid = (ceil(W/kBlock), H, sets).
+static __global__ void __launch_bounds__(kBlock)
+k_weighted_coef_fixed(ImageView wx, ImageView wy, ImageView lam, ImageView fixed, int W, int H, long pitch, double *__restrict__ op, long plane,
+                      long op_stride, double *__restrict__ cons, long cons_stride, unsigned long long *__restrict__ count)
+{
+    __shared__ unsigned tally[3];
+    weighted_mask_block<false>(wx, wy, lam, fixed, W, H, pitch, op, plane, op_stride, cons, cons_stride, count, tally);
+    if (threadIdx.x < 3 && tally[threadIdx.x]) atomicAdd(count + 1 + 3 * blockIdx.z + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
+}
+
+// ccp_grid_refresh_constrained_device: new values AND a new fixed set for the installed operators, on a handle whose
+// three extra planes exist: the setter's kernel but for the refresh's poisoned lambda and for where the counts go --
+// count[2 + 3 k], count[3 + 3 k] as k_weighted_refresh leaves them, and nfixed[k] set k's fixed pixels, words that only
+// this kernel counts into (a value refresh clears count[1 + 3 k] and does not recount it).  Nothing that is read here is
+// written here, so there is no in-place question.  grid = (ceil(W/kBlock), H, sets).
+static __global__ void __launch_bounds__(kBlock)
+k_weighted_fixed_refresh(ImageView wx, ImageView wy, ImageView lam, ImageView fixed, int W, int H, long pitch, double *__restrict__ op,
+                         long plane, long op_stride, double *__restrict__ cons, long cons_stride, unsigned long long *__restrict__ count,
+                         unsigned long long *__restrict__ nfixed)
+{
+    __shared__ unsigned tally[3];
+    weighted_mask_block<true>(wx, wy, lam, fixed, W, H, pitch, op, plane, op_stride, cons, cons_stride, count, tally);
+    const int ch = blockIdx.z;
+    if (threadIdx.x == 0 && tally[0]) atomicAdd(nfixed + ch, (unsigned long long)tally[0]);
+    if ((threadIdx.x == 1 || threadIdx.x == 2) && tally[threadIdx.x]) atomicAdd(count + 1 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
+}
+
+// weighted_form for a pass that keeps the fixed set: the flags are the sign of the stored lambda plane (< 0 on a fixed
+// pixel), and the fixed pixels are not counted (they do not change).
+template <class North, class West>
+__device__ __forceinline__ void weighted_refresh_tail(double l, double e, double s, North north, West west, int x, int y, int ch, int W, int H,
+                                                      long pitch, double *op, long plane, long op_stride, double *cons, long cons_stride,
+                                                      unsigned long long *__restrict__ count, unsigned &n_dead, unsigned &n_edges)
+{
+    const double *mark = op + (long)ch * op_stride + 3 * plane;
+    unsigned n_fixed;
+    weighted_form<true, false>(l, e, s, [&](int fx, int fy) { return mark[w_at(pitch, fx, fy)] < 0.0; }, north, west, x, y, ch, W, H, pitch, op,
+                               plane, op_stride, cons, cons_stride, count, n_fixed, n_dead, n_edges);
+}
+
 // ccp_grid_refresh_weights_device: new values for the installed operators, the fixed set kept.  The planes of every set
 // are rewritten as k_weighted_coef_fixed forms them (which, where no pixel is fixed, are k_weighted_coef's: the same
-// sums in the same order), with one difference in where the fixed flags come from: the sign of the stored lambda plane
-// (< 0 on a fixed pixel) instead of a mask view.  cons: null when the handle has no fixed pixel (no plane is negative
-// then, and the three extra planes do not exist).
-// (All of that is weighted_refresh_tail, above.)
+// sums in the same order), the fixed flags from the stored lambda plane (weighted_refresh_tail).  cons: null when the
+// handle has no fixed pixel (no plane is negative then, and the three extra planes do not exist).
 // The lambda plane is rewritten in place while the neighbours' threads read it.  That is sound because the SIGN of an
 // entry never changes here: a fixed pixel's entry is stored as the -1 it holds, a free pixel's as a value that is >= 0 and
 // not NaN -- a lambda that fails the check is stored as +0.0, so a refused refresh poisons the operator's values but
@@ -464,67 +482,6 @@ k_weighted_reweight_robust(RobustArgs a, double *op, long plane, double *cons, u
     if (t_edges) atomicAdd(&tally[1], t_edges);
     __syncthreads();
     if (threadIdx.x < 2 && tally[threadIdx.x]) atomicAdd(count + 2 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
-}
-
-// ccp_grid_refresh_constrained_device: new values AND a new fixed set for the installed operators, on a handle whose
-// three extra planes exist.  k_weighted_coef_fixed's arithmetic in its order -- the flags from the mask view, dd and lp
-// summed over the same operands, every weight checked, a fixed pixel's too -- so that the planes have the bits the setter
-// forms from the same four views; nothing that is read here is written here, so there is no in-place question.  What
-// differs is the refresh's: a lambda that fails the check is stored as +0.0 (a refused refresh poisons the values and
-// leaves the marks those of the mask), and the counts go where the refresh keeps them: count[0] the verdict of all sets,
-// count[2 + 3 k], count[3 + 3 k] set k's free pixels with d = 0 and edges with exactly one fixed end, as
-// k_weighted_refresh leaves them, and nfixed[k] set k's fixed pixels, words that only this kernel counts into (a value
-// refresh clears count[1 + 3 k] and does not recount it) -- per block in LDS, then one atomic per non-zero count.
-// grid = (ceil(W/kBlock), H, sets).
-static __global__ void __launch_bounds__(kBlock)
-k_weighted_fixed_refresh(ImageView wx, ImageView wy, ImageView lam, ImageView fixed, int W, int H, long pitch, double *__restrict__ op,
-                         long plane, long op_stride, double *__restrict__ cons, long cons_stride, unsigned long long *__restrict__ count,
-                         unsigned long long *__restrict__ nfixed)
-{
-    __shared__ unsigned tally[3];
-    if (threadIdx.x < 3) tally[threadIdx.x] = 0;
-    __syncthreads();
-    const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y, ch = blockIdx.z;
-    unsigned n_fixed = 0, n_dead = 0, n_edges = 0;
-    if (x < W) {
-        const double l = lam(y, x, ch);
-        const double e = x + 1 < W ? wx(y, x, ch) : 0.0;
-        const double s = y + 1 < H ? wy(y, x, ch) : 0.0;
-        if (!(weight_ok(l) && weight_ok(e) && weight_ok(s))) atomicOr(count, 1ull);
-        const bool fp = fixed(y, x, ch) != 0;
-        const bool fN = y >= 1 && fixed(y - 1, x, ch) != 0, fW = x >= 1 && fixed(y, x - 1, ch) != 0;
-        const bool fE = x + 1 < W && fixed(y, x + 1, ch) != 0, fS = y + 1 < H && fixed(y + 1, x, ch) != 0;
-        const double wN = y >= 1 ? wy(y - 1, x, ch) : 0.0, wW = x >= 1 ? wx(y, x - 1, ch) : 0.0;
-        double dd = l;
-        if (y >= 1) dd += wN;
-        if (x >= 1) dd += wW;
-        if (x + 1 < W) dd += e;
-        if (y + 1 < H) dd += s;
-        double lp = l;
-        if (fN) lp += wN;
-        if (fW) lp += wW;
-        if (fE) lp += e;
-        if (fS) lp += s;
-        const bool be = x + 1 < W && fp != fE, bs = y + 1 < H && fp != fS;   // edges with exactly one fixed end
-        double *__restrict__ o = op + (long)ch * op_stride, *__restrict__ k = cons + (long)ch * cons_stride;
-        const long at = w_at(pitch, x, y);
-        o[at] = fp ? 0.0 : dd;
-        o[plane + at] = fp || fE ? 0.0 : e;
-        o[2 * plane + at] = fp || fS ? 0.0 : s;
-        o[3 * plane + at] = fp ? -1.0 : weight_ok(l) ? l : 0.0;
-        k[at] = be ? e : 0.0;
-        k[plane + at] = bs ? s : 0.0;
-        k[2 * plane + at] = fp ? 0.0 : lp;
-        n_fixed = fp;
-        n_dead = !fp && dd == 0.0;
-        n_edges = (unsigned)be + (unsigned)bs;
-    }
-    if (n_fixed) atomicAdd(&tally[0], n_fixed);
-    if (n_dead) atomicAdd(&tally[1], n_dead);
-    if (n_edges) atomicAdd(&tally[2], n_edges);
-    __syncthreads();
-    if (threadIdx.x == 0 && tally[0]) atomicAdd(nfixed + ch, (unsigned long long)tally[0]);
-    if ((threadIdx.x == 1 || threadIdx.x == 2) && tally[threadIdx.x]) atomicAdd(count + 1 + 3 * ch + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
 }
 
 // b of `cpb` channels per block from one set of the stored operator: block z takes channels [z cpb, (z + 1) cpb) and the
