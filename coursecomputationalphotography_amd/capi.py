@@ -96,7 +96,7 @@ ABI_SYMBOLS = (
     "ccp_grid_mg_prepare", "ccp_grid_mg_conjugate_gradient_enqueue", "ccp_grid_mg_conjugate_gradient_enqueue_relative",
     "ccp_grid_refresh_weights_device", "ccp_grid_operator_status",
     "ccp_grid_reserve_constraints", "ccp_grid_refresh_constrained_device", "ccp_grid_reweight_device",
-    "ccp_grid_reweight_robust_device",
+    "ccp_grid_reweight_robust_device", "ccp_grid_reweight_adjoint_device",
     "ccp_grid_set_mask_device", "ccp_mask_erode_cross_device", "ccp_panorama_begin_device", "ccp_panorama_add_device",
     "ccp_panorama_finish_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
@@ -192,6 +192,16 @@ class ReweightData(C.Structure):
     """ccp_reweight_data: the data penalty, scale, epsilon, f and the output for the lambda formed (NULL: absent)."""
     _fields_ = [("penalty", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_double), ("epsilon", C.c_double),
                 ("f", C.POINTER(DeviceArray)), ("out_lambda", C.POINTER(DeviceArray))]
+
+
+# ccp_grid_reweight_adjoint_device (ccp_gs.h, "Backpropagating through a reweight")
+REWEIGHT_GRADS_IN = ("grad_wx", "grad_wy", "grad_lambda")
+REWEIGHT_GRADS_OUT = ("g_u", "g_gx", "g_gy", "g_f", "g_base_wx", "g_base_wy", "g_lambda")
+
+
+class ReweightGrads(C.Structure):
+    """ccp_reweight_grads: one ccp_device_array pointer per upstream gradient (NULL: 0) and per output (NULL: not computed)."""
+    _fields_ = [(n, C.POINTER(DeviceArray)) for n in REWEIGHT_GRADS_IN + REWEIGHT_GRADS_OUT]
 
 
 class PanoramaState(C.Structure):
@@ -365,6 +375,7 @@ def load() -> C.CDLL:
     L.ccp_grid_refresh_constrained_device.argtypes = [vp, vp, vp, vp, vp]
     L.ccp_grid_reweight_device.argtypes = [vp, C.POINTER(Reweight)]
     L.ccp_grid_reweight_robust_device.argtypes = [vp, C.POINTER(Reweight), C.POINTER(ReweightData)]
+    L.ccp_grid_reweight_adjoint_device.argtypes = [vp, C.POINTER(Reweight), C.POINTER(ReweightData), C.POINTER(ReweightGrads)]
     L.ccp_grid_mg_level_channel.argtypes = [vp, i32, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
     L.ccp_grid_constraint_info_channel.argtypes = [vp, i32, vp, vp, vp]
     L.ccp_grid_adjoint_begin_device.argtypes = [vp, da]
@@ -1411,6 +1422,56 @@ class Grid:
         fixed pixels included.  The other arguments, the stream and the verdict: as reweight_tensor's."""
         ids = robust_ids(penalty, coupling, data_penalty)
         self._reweight(ids, scale, epsilon, u, gx, gy, base_wx, base_wy, lam, out_wx, out_wy, data=(data_scale, data_epsilon, f, out_lambda))
+
+    def reweight_adjoint_tensor(self, penalty, coupling, scale, epsilon, u, gx=None, gy=None, base_wx=None, base_wy=None, lam=None,
+                                data_penalty=None, data_scale=1.0, data_epsilon=None, f=None, grad_wx=None, grad_wy=None, grad_lambda=None,
+                                want=("u", "gx", "gy", "base_wx", "base_wy"), out=None, dtype=None):
+        """The backward pass of reweight_tensor (data_penalty None) or reweight_robust_tensor in one launch
+        (ccp_grid_reweight_adjoint_device): from the upstream gradients grad_wx, grad_wy (and grad_lambda) of the weights
+        formed -- float32 / float64, shaped as the weights, None: 0 -- the gradients with respect to what they were formed
+        from.  The forward's arguments as the forward took them, but `u` is required (the tensor the weights were formed
+        from).  want: of "u", "gx", "gy", "f" (H x W x channels) and "base_wx", "base_wy", "lam" (H x W on a shared
+        operator, H x W x channels on one per channel); "f" and "lam" (the base lambda's) need data_penalty.  Only those
+        are computed.  Returns {name: tensor}; a tensor given in `out` ({name: tensor}, float32 or float64, any
+        non-overlapping view that shares no bytes with an input) is filled, the others are allocated as `dtype` (float64
+        by default).  Enqueued on torch's current stream; the handle's operator, x and b are not touched."""
+        torch = self._torch()
+        ids = reweight_ids(penalty, coupling) if data_penalty is None else robust_ids(penalty, coupling, data_penalty)
+        want, out = tuple(want), dict(out or {})
+        planes, images = ("base_wx", "base_wy", "lam"), ("u", "gx", "gy", "f")
+        unknown = [n for n in want if n not in planes + images] + [n for n in out if n not in want]
+        if unknown:
+            raise ValueError(f"unknown or unrequested gradients: {unknown}")
+        if data_penalty is None and (grad_lambda is not None or "f" in want or "lam" in want):
+            raise ValueError("grad_lambda and the gradients of f and lam need data_penalty")
+        if u is None:
+            raise ValueError("u is required: the tensor the weights were formed from")
+        floats, any_ = (torch.float32, torch.float64), (torch.uint8, torch.float32, torch.float64)
+        named = ((base_wx, "base_wx"), (base_wy, "base_wy"), (lam, "lam"), (grad_wx, "grad_wx"), (grad_wy, "grad_wy"), (grad_lambda, "grad_lambda"))
+        per_channel, arr = self._operator_marshal([t for t, _ in named] + [out.get(n) for n in planes])
+        arrs = {"u": self._channel_array(u, "u", any_), "f": self._channel_array(f, "f", any_),
+                "gx": self._image(gx, "gx", (torch.float32,)), "gy": self._image(gy, "gy", (torch.float32,)), "out_wx": None, "out_wy": None}
+        arrs.update({n: arr(t, n) for t, n in named})
+        arrs["lambda"] = arrs.pop("lam")
+        result, outs = {}, {}
+        for n in want:
+            t = out.get(n)
+            if t is None:
+                shape = (self.H, self.W) if n in planes and not per_channel else (self.H, self.W, self.C)
+                with torch.cuda.device(self._device()):
+                    t = torch.empty(shape, dtype=dtype or torch.float64, device=self._device())
+            plane = n in planes and not per_channel
+            outs["g_lambda" if n == "lam" else "g_" + n] = arr(t, n, "out") if plane else self._hwc(t, n, floats, output=True)[0]
+            result[n] = t
+        ptr = lambda d, n: None if d.get(n) is None else C.pointer(d[n])
+        how = Reweight(ids[0], ids[1], float(scale), float(epsilon), *[ptr(arrs, n) for n in REWEIGHT_VIEWS])
+        io = ReweightGrads(*([ptr(arrs, n) for n in REWEIGHT_GRADS_IN] + [ptr(outs, n) for n in REWEIGHT_GRADS_OUT]))
+        rob = None
+        if data_penalty is not None:
+            rob = ReweightData(ids[2], 0, float(data_scale), 0.0 if data_epsilon is None else float(data_epsilon), ptr(arrs, "f"), None)
+        self._on_stream(lambda: self.L.ccp_grid_reweight_adjoint_device(self.h, C.byref(how), None if rob is None else C.byref(rob), C.byref(io)),
+                        "ccp_grid_reweight_adjoint_device")
+        return result
 
     def operator_status(self) -> int:
         """The operator status word of the last refresh_weights_tensor (0: good; 1: a bad weight, 2: out of float range in

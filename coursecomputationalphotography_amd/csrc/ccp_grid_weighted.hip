@@ -5,6 +5,7 @@
 #include "ccp_grid_handle.hpp"
 #include "ccp_grid_pco.hpp"
 #include "ccp_grid_weighted.hpp"
+#include "ccp_grid_reweight_adjoint.hpp"
 #include "ccp_grid_adjoint.hpp"
 #include "ccp_grid_weighted_api.hpp"
 #include "ccp_view_check.hpp"
@@ -512,6 +513,67 @@ int reweight_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_dat
     });
 }
 
+// ccp_grid_reweight_adjoint_device: the forward calls' checks on `how` and `data` with their outputs left out
+// (reweight_checked), then the gradient views, and one launch of the marching kernel on the handle's stream.
+int reweight_adjoint_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data, const ccp_reweight_grads *io)
+{
+    CCP_TRY(weighted_handle(g));
+    if (!how || !io || !how->u) return CCP_ERR_BAD_ARG;
+    if (!data && (io->grad_lambda || io->g_f || io->g_lambda)) return CCP_ERR_BAD_ARG;
+    ccp_reweight fwd = *how;
+    fwd.out_wx = fwd.out_wy = nullptr;                                     // ignored here
+    ccp_reweight_data fwd_data{};
+    if (data) {
+        fwd_data = *data;
+        fwd_data.out_lambda = nullptr;
+    }
+    ReweightAdjointArgs a{};
+    CCP_TRY(reweight_checked(g, &fwd, data ? &fwd_data : nullptr, &a.f.r));
+    const Geom &geo = g->geom;
+    const int C = g->desc.channels, sets = g->per_channel ? C : 1;
+    constexpr int kInputs = 10, kViews = 17;
+    struct {
+        const ccp_device_array *a;
+        int c;
+    } views[kViews] = {{how->u, C},          {how->gx, C},         {how->gy, C},        {how->base_wx, sets}, {how->base_wy, sets},
+                       {how->lambda, sets},  {data ? data->f : nullptr, C},             {io->grad_wx, sets},  {io->grad_wy, sets},
+                       {io->grad_lambda, sets}, {io->g_u, C},      {io->g_gx, C},       {io->g_gy, C},        {io->g_f, C},
+                       {io->g_base_wx, sets}, {io->g_base_wy, sets}, {io->g_lambda, sets}};
+    for (int i = 7; i < kViews; ++i)
+        if (views[i].a) CCP_TRY(check_view(g, views[i].a, kF32F64, i >= kInputs, 1, geo.H, geo.W, views[i].c));
+    // an output that shares bytes with an input or with another output: the neighbours' threads read the one, and two
+    // stores to one address have no order
+    for (int o = kInputs; o < kViews; ++o)
+        for (int i = 0; i < kViews && views[o].a; ++i) {
+            if (i == o || !views[i].a) continue;
+            uintptr_t olo, ohi, ilo, ihi;
+            view_span(views[o].a, geo.H, geo.W, views[o].c, &olo, &ohi);
+            view_span(views[i].a, geo.H, geo.W, views[i].c, &ilo, &ihi);
+            if (olo < ihi && ilo < ohi) return CCP_ERR_BAD_ARG;
+        }
+    a.f.rows = robust_rows(geo.W, geo.H, sets);
+    a.f.dphi = data ? data->penalty : -1;
+    a.f.dscale = data ? data->scale : 1.0;
+    a.f.deps = data && data->penalty != CCP_REWEIGHT_QUADRATIC ? data->epsilon : 1.0;   // (not read for QUADRATIC)
+    a.f.f = image_view(data ? data->f : nullptr, 0.0);
+    a.grad_wx = image_view(io->grad_wx, 0.0);
+    a.grad_wy = image_view(io->grad_wy, 0.0);
+    a.grad_lam = image_view(io->grad_lambda, 0.0);
+    a.g_u = adj_out(io->g_u);
+    a.g_gx = adj_out(io->g_gx);
+    a.g_gy = adj_out(io->g_gy);
+    a.g_f = adj_out(io->g_f);
+    a.g_bwx = adj_out(io->g_base_wx);
+    a.g_bwy = adj_out(io->g_base_wy);
+    a.g_lam = adj_out(io->g_lambda);
+    const dim3 grid((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)((geo.H + a.f.rows - 1) / a.f.rows), (unsigned)sets);
+    with_phi(how->penalty, [&](auto P) {
+        hipLaunchKernelGGL((k_weighted_reweight_adjoint<decltype(P)::value>), grid, dim3(kBlock), 0, g->stream, a, geo.ch_stride);
+    });
+    CCP_HIP(hipGetLastError());
+    return CCP_OK;
+}
+
 }  // namespace
 
 int ccp::weighted_apply(ccp_grid *g, int mode) { return mode == 0 ? weighted_apply_mode<0>(g) : weighted_apply_mode<1>(g); }
@@ -635,6 +697,11 @@ int ccp_grid_reweight_robust_device(ccp_grid *g, const ccp_reweight *how, const 
 try {
     if (!data) return CCP_ERR_BAD_ARG;
     return reweight_device(g, how, data);
+} CCP_ABI_CATCH
+
+int ccp_grid_reweight_adjoint_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data, const ccp_reweight_grads *io)
+try {
+    return reweight_adjoint_device(g, how, data, io);
 } CCP_ABI_CATCH
 
 int ccp_grid_reserve_constraints(ccp_grid *g, int32_t on)

@@ -666,8 +666,8 @@ class WeightedSolver:
         refresh_operator: it may be recorded by torch.cuda.graph between two solves.  Returns (wx, wy), the weights formed:
         `out` if given (a pair of float32 / float64 tensors, H x W on a shared operator, H x W x C on one per channel), else
         two new float64 tensors (inside a capture pass `out`).  They are recorded as the installed weights, so a later
-        solve_grad's backward re-installs the right ones; solve_grad(wx=, wy=) on them is the way to unroll the outer loop
-        by hand: the gradient of an IRLS result is not provided.
+        solve_grad's backward re-installs the right ones.  They carry no grad_fn: reweight_grad is this call as a
+        differentiable function, and irls_solve_grad the whole outer loop.
 
         data_penalty (keyword only): None makes exactly the call above.  "charbonnier" | "huber" | "reciprocal" |
         "quadratic" reweights the data term in the same pass (capi.Grid.reweight_robust_tensor): per pixel
@@ -701,6 +701,48 @@ class WeightedSolver:
         self._operator = (wx, wy, lam, self._operator[3])
         self._generation += 1
         return wx, wy
+
+    def reweight_grad(self, penalty, coupling, scale, epsilon, u, gx=None, gy=None, base_wx=None, base_wy=None, data_weight=None, *,
+                      data_penalty=None, data_scale=1.0, data_epsilon=None, f=None):
+        """reweight as a differentiable function: it installs the weights exactly as reweight does (the same call, the same
+        bits) and returns them -- (wx, wy), or (wx, wy, lam) with data_penalty -- as new float64 tensors with a grad_fn, so
+        that solve_grad(wx=, wy=, data_weight=) on them unrolls an IRLS step that autograd can differentiate.  u: a tensor,
+        required (the image the weights are formed from: f for the first step, the previous step's result later).
+        Backward is one launch (capi.Grid.reweight_adjoint_tensor) and once-differentiable; it returns gradients for u, gx,
+        gy, base_wx, base_wy and, with data_penalty, data_weight and f, each in its input's dtype and shape.  u8 inputs and
+        python scalars get none; scale, the epsilons and data_scale get none (a learnable strength is a base weight with
+        scale 1).  A 0-dim tensor is expanded to H x W and, on an operator per channel, an H x W tensor to H x W x C here,
+        outside the autograd function, so that torch sums its gradient: solve_grad's rule.  Without data_penalty lambda is
+        not formed here: data_weight passes through to the handle, and its gradient is solve_grad(data_weight=)'s alone.
+        The tensors saved for backward are the inputs; nothing of the handle's state is needed then, so several forwards
+        may precede their backwards."""
+        import torch
+        if self._operator is None:
+            raise RuntimeError("WeightedSolver: set_operator first")
+        if data_penalty is None:
+            capi.reweight_ids(penalty, coupling)
+        else:
+            capi.robust_ids(penalty, coupling, data_penalty)
+        if not isinstance(u, torch.Tensor):
+            raise ValueError("reweight_grad needs u, the tensor the weights are formed from")
+        stacked = self.grid.operator_channels() > 1 or _per_channel(base_wx, base_wy, data_weight)
+
+        def plane(w):
+            if isinstance(w, torch.Tensor) and w.dim() == 0:
+                w = w.expand(self.H, self.W)
+            w = _weight(w, self.H, self.W, self.device.index)
+            if stacked and w is not None and w.dim() == 2:
+                w = w.unsqueeze(-1).expand(self.H, self.W, self.C)
+            return w
+
+        def image(t):
+            if isinstance(t, torch.Tensor) and t.dim() == 2:
+                t = t.unsqueeze(-1).expand(self.H, self.W, self.C)
+            return t
+
+        cfg = dict(penalty=penalty, coupling=coupling, scale=float(scale), epsilon=float(epsilon), data_penalty=data_penalty,
+                   data_scale=float(data_scale), data_epsilon=data_epsilon)
+        return _reweight_function().apply(image(u), gx, gy, plane(base_wx), plane(base_wy), plane(data_weight), image(f), self, cfg)
 
     def reserve_constraints(self):
         """Before set_operator: keep the handle's constraint planes whether or not the operator fixes a pixel
@@ -792,8 +834,8 @@ def irls_solve(gx, gy, f, outer: int, iterations: int, penalty="charbonnier", co
     sqrt(r'r) < tolerance * |b|.  history: None, or a list that receives one (u, report, wx, wy) of device tensors per
     outer step (report C x 8, WeightedSolver.set_stop's; wx, wy the weights the step solved with): convergence is not
     checked here, that would be a read-back.  Returns x as out_dtype (None: torch.uint8, clamped, for a u8 f, else float64).
-    The gradient of the result is not provided; unrolled differentiation is possible by hand with WeightedSolver.reweight's
-    `out` and solve_grad(wx=, wy=).  Strongly varying weights -- small epsilon, sharp edges -- are where smoother="line" helps.
+    The result carries no grad_fn: irls_solve_grad is this loop unrolled for autograd (WeightedSolver.reweight_grad and
+    solve_grad(wx=, wy=)), with the same values.  Strongly varying weights -- small epsilon, sharp edges -- are where smoother="line" helps.
 
     data_penalty: None -- the quadratic data term above, and exactly the calls made before this argument existed -- or
     "charbonnier" | "huber" | "reciprocal": the data term is robust as well, and every step reweights the edges and lambda
@@ -888,6 +930,176 @@ def tv_l1_denoise(image, strength, outer: int = 12, iterations: int = 400, epsil
                    smoother=smoother, out_dtype=out_dtype, history=history, data_penalty="charbonnier", data_epsilon=data_epsilon,
                    first_step=first_step)
     return u if image.dim() == 3 else u[..., 0]
+
+
+def irls_solve_grad(gx, gy, f, outer: int, iterations: int, penalty="charbonnier", coupling="edge", strength=1.0, epsilon=1e-2, data_weight=1.0,
+                    wx=None, wy=None, fixed=None, values=None, tolerance=1e-10, hierarchy="rescaled", precision="f64", channels="sequential",
+                    smoother="point", history=None, data_penalty=None, data_epsilon=None, first_step="quadratic", strict: bool = True,
+                    adjoint_history=None):
+    """irls_solve unrolled for autograd: the same `outer` x (reweight, assemble, solve) on one WeightedSolver, through
+    reweight_grad and solve_grad(wx=, wy=, data_weight=).  Returns x, a float64 H x W x C tensor with a grad_fn towards gx, gy,
+    f, values, wx, wy (the base weights), a tensor data_weight and a tensor strength; u8 inputs and python numbers get no
+    gradient.  Step 0 reweights from f, step k from step k - 1's returned tensor, which holds the handle's x: with a
+    python-number strength the calls are irls_solve's and a refresh with the weights just formed, and x has irls_solve's bits.
+    Arguments as irls_solve's (no out_dtype: float64); a 0-dim wx, wy or data_weight is expanded to H x W.
+
+    strength: a python number is the reweight's scale, as in irls_solve.  A 0-dim tensor is folded into the base weights --
+    base = strength.expand(H, W), times wx / wy where given -- with scale 1.0, so that its gradient is the sum of the base
+    weights' gradients and needs no read-back (the weights then differ from the number's in the last bits).
+
+    Backward walks the steps in reverse: per step the adjoint right-hand side, one more enqueue solve to the same relative
+    tolerance, the gradient pass, and one launch for the adjoint of the reweight.  It is enqueue-only; adjoint_history: None,
+    or a list that receives `outer` C x 8 report tensors here, each filled when its step's backward has run.
+    strict (the default): the `outer` forward reports are read back once after the loop -- the one synchronisation -- and a
+    solve that did not converge raises RuntimeError: the gradient of an unconverged solve is not the gradient.
+    history: as irls_solve's.
+
+    Memory.  Per outer step u, wx, wy (and lam) stay alive until backward, beside the inputs, and the handle -- x, b, the
+    operator planes, the hierarchy and the PCG vectors -- lives as long as the graph does."""
+    import torch
+    if data_penalty is None:
+        capi.reweight_ids(penalty, coupling)
+    else:
+        capi.robust_ids(penalty, coupling, data_penalty)
+        if data_penalty == "quadratic" or penalty == "quadratic":
+            raise ValueError('irls_solve_grad: "quadratic" is data_penalty=None (and no edge penalty); WeightedSolver.reweight_grad takes it')
+        if first_step not in ("quadratic", "robust"):
+            raise ValueError(f'first_step must be "quadratic" or "robust", not {first_step!r}')
+        if data_epsilon is None:
+            raise ValueError("irls_solve_grad: a robust data term needs data_epsilon")
+    if f is None:
+        raise ValueError("irls_solve_grad needs f: the data term, and the image the first step reweights from")
+    if int(outer) < 1:
+        raise ValueError(f"outer must be at least 1, not {outer}")
+    dev = _device_index(f)
+    H, W = f.shape[0], f.shape[1]
+    if f.dim() == 2:
+        f = f.unsqueeze(-1)
+    C = f.shape[2]
+    flat = lambda w: w.expand(H, W) if isinstance(w, torch.Tensor) and w.dim() == 0 else w
+    wx, wy, data_weight = flat(wx), flat(wy), flat(data_weight)
+    s = WeightedSolver(H, W, C, dev, iterations=iterations, epsilon=0.0, hierarchy=hierarchy, precision=precision, channels=channels,
+                       smoother=smoother)              # (not closed here: backward needs it; it goes with the graph)
+    try:
+        s.set_operator(wx, wy, data_weight, fixed)
+        s.set_stop(relative=tolerance)
+        base_wx, base_wy, lam, _ = s._operator
+        scale = strength
+        if isinstance(strength, torch.Tensor):
+            if strength.dim() != 0:
+                raise ValueError("a tensor strength must be 0-dim")
+            scale = 1.0
+            base_wx = strength.expand(H, W) if wx is None else strength * wx
+            base_wy = strength.expand(H, W) if wy is None else strength * wy
+        robust = {}
+        if data_penalty is not None:
+            scalar = not isinstance(data_weight, torch.Tensor)
+            robust = dict(data_scale=float(data_weight) if scalar else 1.0, data_epsilon=data_epsilon, f=f)
+            if scalar:
+                lam = None
+        x = f.detach().to(torch.float64)
+        u_in, reports = f, []
+        for k in range(int(outer)):
+            if data_penalty is not None:
+                robust["data_penalty"] = "quadratic" if k == 0 and first_step == "quadratic" else data_penalty
+            w = s.reweight_grad(penalty, coupling, scale, epsilon, u_in, gx=gx, gy=gy, base_wx=base_wx, base_wy=base_wy, data_weight=lam, **robust)
+            report, adjoint = (torch.zeros((C, 8), dtype=torch.float64, device=x.device) for _ in range(2))
+            # the data weight of the solve: the lambda just formed, else the caller's tensor (a number stays the installed one)
+            solve_lam = w[2] if data_penalty is not None else (lam if isinstance(data_weight, torch.Tensor) else None)
+            u_in, _ = s.solve_grad(gx, gy, f, values, x0=x, report=report, adjoint_report=adjoint, wx=w[0], wy=w[1], data_weight=solve_lam)
+            x = u_in.detach()
+            reports.append(report)
+            if adjoint_history is not None:
+                adjoint_history.append(adjoint)
+            if history is not None:
+                history.append((x, report) + tuple(t.detach() for t in w))
+        if strict and not bool(torch.stack(reports)[:, :, 1].all()):
+            its = [[int(i) for i in r[:, 0].tolist()] for r in reports]
+            raise RuntimeError(f"irls_solve_grad: a forward solve did not converge (iterations per step and channel {its}); the gradient "
+                               "of an unconverged solve is not the gradient: raise `iterations`, loosen `tolerance`, or pass strict=False")
+        return u_in
+    except BaseException:
+        s.close()
+        raise
+
+
+def tv_denoise_grad(image, strength, outer: int = 10, iterations: int = 400, epsilon=1e-2, isotropic=True, data_weight=1.0, tolerance=1e-10,
+                    hierarchy="rescaled", precision="f64", channels="sequential", smoother="point", history=None, strict: bool = True,
+                    adjoint_history=None):
+    """tv_denoise as a differentiable function of the image, of a 0-dim tensor strength and of a tensor data_weight
+    (irls_solve_grad: zero guidance, f = image, Charbonnier, "pixel" or "edge" coupling).  Returns float64, the image's shape."""
+    f = image if image.dim() == 3 else image.unsqueeze(-1)
+    u = irls_solve_grad(None, None, f, outer, iterations, penalty="charbonnier", coupling="pixel" if isotropic else "edge", strength=strength,
+                        epsilon=epsilon, data_weight=data_weight, tolerance=tolerance, hierarchy=hierarchy, precision=precision,
+                        channels=channels, smoother=smoother, history=history, strict=strict, adjoint_history=adjoint_history)
+    return u if image.dim() == 3 else u[..., 0]
+
+
+def tv_l1_denoise_grad(image, strength, outer: int = 12, iterations: int = 400, epsilon=1e-2, data_epsilon=5e-2, isotropic=True, data_weight=1.0,
+                       tolerance=1e-10, hierarchy="rescaled", precision="f64", channels="sequential", smoother="point", first_step="quadratic",
+                       history=None, strict: bool = True, adjoint_history=None):
+    """tv_l1_denoise as a differentiable function, as tv_denoise_grad is tv_denoise's (the data term Charbonnier on
+    data_epsilon as well).  Returns float64, the image's shape."""
+    f = image if image.dim() == 3 else image.unsqueeze(-1)
+    u = irls_solve_grad(None, None, f, outer, iterations, penalty="charbonnier", coupling="pixel" if isotropic else "edge", strength=strength,
+                        epsilon=epsilon, data_weight=data_weight, tolerance=tolerance, hierarchy=hierarchy, precision=precision,
+                        channels=channels, smoother=smoother, history=history, data_penalty="charbonnier", data_epsilon=data_epsilon,
+                        first_step=first_step, strict=strict, adjoint_history=adjoint_history)
+    return u if image.dim() == 3 else u[..., 0]
+
+
+_ReweightGrad = None
+
+
+def _reweight_function():
+    """The torch.autograd.Function behind WeightedSolver.reweight_grad (built on first use, as _solve_function)."""
+    global _ReweightGrad
+    if _ReweightGrad is not None:
+        return _ReweightGrad
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    names = ("u", "gx", "gy", "base_wx", "base_wy", "lam", "f")
+
+    class ReweightGrad(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, u, gx, gy, base_wx, base_wy, lam, f, solver, cfg):
+            robust = {}
+            if cfg["data_penalty"] is not None:
+                robust = dict(data_penalty=cfg["data_penalty"], data_scale=cfg["data_scale"], data_epsilon=cfg["data_epsilon"], f=f)
+            w = solver.reweight(cfg["penalty"], cfg["coupling"], cfg["scale"], cfg["epsilon"], u=u, gx=gx, gy=gy, base_wx=base_wx,
+                                base_wy=base_wy, data_weight=lam, **robust)
+            ctx.solver, ctx.cfg = solver, cfg
+            ctx.present = [t is not None for t in (u, gx, gy, base_wx, base_wy, lam, f)]
+            ctx.save_for_backward(*[t for t in (u, gx, gy, base_wx, base_wy, lam, f) if t is not None])
+            return tuple(w)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, *grads):
+            it = iter(ctx.saved_tensors)
+            inputs = {n: next(it) if p else None for n, p in zip(names, ctx.present)}
+            cfg = ctx.cfg
+            with_data = cfg["data_penalty"] is not None
+            want = tuple(n for n, need in zip(names, ctx.needs_input_grad[:7])
+                         if need and inputs[n] is not None and (with_data or n not in ("lam", "f")))
+            got = {}
+            if want:
+                floats = (torch.float32, torch.float64)
+                grads = [None if g is None else (g if g.dtype in floats else g.to(torch.float64)) for g in grads]
+                out = {n: torch.empty(inputs[n].shape, dtype=inputs[n].dtype, device=inputs[n].device) for n in want}
+                robust = {}
+                if with_data:
+                    robust = dict(data_penalty=cfg["data_penalty"], data_scale=cfg["data_scale"], data_epsilon=cfg["data_epsilon"],
+                                  f=inputs["f"], grad_lambda=grads[2])
+                got = ctx.solver.grid.reweight_adjoint_tensor(cfg["penalty"], cfg["coupling"], cfg["scale"], cfg["epsilon"], inputs["u"],
+                                                              gx=inputs["gx"], gy=inputs["gy"], base_wx=inputs["base_wx"],
+                                                              base_wy=inputs["base_wy"], lam=inputs["lam"], grad_wx=grads[0],
+                                                              grad_wy=grads[1], want=want, out=out, **robust)
+            return tuple(got.get(n) for n in names) + (None, None)
+
+    _ReweightGrad = ReweightGrad
+    return ReweightGrad
 
 
 _PersistentSolve = None

@@ -1222,8 +1222,8 @@ int ccp_grid_refresh_constrained_device(ccp_grid *g, const ccp_device_array *wx,
  *   pass's: two elements of an output at one address; also an output that shares bytes with an input view, which the
  *   neighbouring pixels' threads read).  CCP_ERR_STATE: no installed operator, or no successful ccp_grid_mg_prepare since
  *   the last call that drops what prepare built.  CCP_ERR_UNSUPPORTED: not a weighted handle.
- * Out of scope: host-pointer twins, the C++ facades, gradients through the outer loop (the weights are in out_wx / out_wy
- * for a hand-unrolled one).  Additive: the ABI version does not change. */
+ * Out of scope: host-pointer twins, the C++ facades.  Gradients through the outer loop: "Backpropagating through a
+ * reweight", below (the weights are in out_wx / out_wy).  Additive: the ABI version does not change. */
 #define CCP_REWEIGHT_CHARBONNIER 0   /* phi = 1 / sqrt(q + eps*eps)      */
 #define CCP_REWEIGHT_HUBER       1   /* phi = 1 / fmax(sqrt(q), eps)     */
 #define CCP_REWEIGHT_RECIPROCAL  2   /* phi = 1 / (sqrt(q) + eps)        */
@@ -1272,8 +1272,8 @@ int ccp_grid_reweight_device(ccp_grid *g, const ccp_reweight *how);
  *   QUADRATIC); f NULL with a penalty other than QUADRATIC; a bad view; out_lambda with two elements at one address or
  *   sharing bytes with any input view, f and how->lambda included (out_wx, out_wy: as ccp_grid_reweight_device checks
  *   them, against f too).  CCP_ERR_STATE and CCP_ERR_UNSUPPORTED: as ccp_grid_reweight_device.
- * Out of scope: host-pointer twins, the C++ facades, gradients through the outer loop (the lambda formed is in out_lambda
- * for a hand-unrolled one).  Additive: the ABI version does not change. */
+ * Out of scope: host-pointer twins, the C++ facades.  Gradients through the outer loop: "Backpropagating through a
+ * reweight", below (the lambda formed is in out_lambda).  Additive: the ABI version does not change. */
 #define CCP_REWEIGHT_QUADRATIC 3     /* phi = 1.0: the term is not reweighted (this call only) */
 typedef struct ccp_reweight_data {
     int32_t penalty, reserved;       /* CCP_REWEIGHT_CHARBONNIER | _HUBER | _RECIPROCAL | _QUADRATIC; reserved 0 */
@@ -1282,6 +1282,58 @@ typedef struct ccp_reweight_data {
     const ccp_device_array *out_lambda; /* F32 / F64, H x W (shared) or H x W x channels (per channel); NULL: not written */
 } ccp_reweight_data;
 int ccp_grid_reweight_robust_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data);
+
+/* ---- Backpropagating through a reweight: the adjoint of the two passes above -------------------------------------------------
+ * A learnable TV / TV-L1 / Huber-fusion layer is an unrolled IRLS loop whose strength, base weights, guidance or input come
+ * out of a network.  ccp_grid_weighted_adjoint_device differentiates each solve with respect to its weights; this call
+ * closes the loop: given dL/dwx, dL/dwy (and dL/dlambda) it forms, in one pass, the gradients with respect to everything
+ * ccp_grid_reweight_device (data NULL) or ccp_grid_reweight_robust_device (data given) formed those weights from.
+ *   Definition (fp64 throughout, every input widened exactly, no multiply-add fused; only +, -, x, /, sqrt and
+ *   comparisons; tests/reweight_adjoint_helpers.py is the same in numpy).  q_x, q_y, dq, phi and the channel set: exactly
+ *   the forward's (phi of QUADRATIC is 1.0 and its q is not formed).  r_c: the forward's r of channel c, recomputed.
+ *   psi(q), with d phi / d r_c = psi * r_c, from q and the phi formed of it:
+ *       CHARBONNIER  p = phi * phi;  psi = -(p * phi)
+ *       HUBER        sqrt(q) > epsilon ? -((phi * phi) * phi) : +0.0        (the kink belongs to the flat side)
+ *       RECIPROCAL   q > 0 ? -((phi * phi) / sqrt(q)) : +0.0                (q = 0: the subgradient is taken as 0)
+ *       QUADRATIC    +0.0
+ *   Gwx, Gwy, Glambda: the upstream gradients at (x, y) of set k (a NULL view reads +0.0).  A NULL base reads 1.0 and skips
+ *   its multiply.
+ *   CCP_REWEIGHT_EDGE:   k_x = ((Gwx * base_x) * scale) * psi(q_x);   k_y = ((Gwy * base_y) * scale) * psi(q_y).
+ *   CCP_REWEIGHT_PIXEL:  a = +0.0;  if the east edge exists: a += Gwx * base_x;  if the south edge exists: a += Gwy * base_y;
+ *                        k_x = k_y = (a * scale) * psi(q_x + q_y).
+ *   Data (data given):   d_c = f - u;   k_d = ((Glambda * lambda_base) * data->scale) * psi_d(dq)   (f NULL reads +0.0).
+ *   Per channel c of the set, in channel order:
+ *       e = k_x * rx_c (the east edge exists; else +0.0);  g_gx = e;     s = k_y * ry_c (south; else +0.0);  g_gy = s;
+ *       t = +0.0;  t += e (east exists);  t += s (south exists);  t -= e of (x-1, y) (x >= 1);  t -= s of (x, y-1) (y >= 1);
+ *       g_f = k_d * d_c;  t -= g_f   (data given, applied last);     g_u = t.
+ *   With an operator per channel the neighbours' terms are those of the same channel.  An edge's e (s) has one value: both
+ *   of its pixels form it from the same k and the same r.
+ *       g_base_wx = Gwx * (scale * phi_x);   g_base_wy = Gwy * (scale * phi_y);   g_lambda = Glambda * (data->scale * phi_d)
+ *   with the phi the forward used for that edge or pixel.  The last column of g_gx and g_base_wx and the last row of g_gy
+ *   and g_base_wy are written +0.0; every element of a given output is written; an F32 output is the fp64 value rounded once.
+ *   Fixed pixels get no special case: g_u is the gradient with respect to the u that was read (at a fixed pixel that is the
+ *   prescribed value, and ccp_grid_weighted_adjoint_device's g_values carries it on).  Nothing is validated and there is no
+ *   status word: a NaN in gives a NaN out.  Gradients with respect to the epsilons and the scales are not formed (a
+ *   learnable strength is a base weight with scale 1: its gradient is the sum of g_base_wx and g_base_wy).
+ *   Arguments.  how, data: read exactly as the two forward calls read them -- penalties, coupling, scales, epsilons, gx, gy,
+ *   the base views (how->lambda is the base lambda of the robust call) and f -- but how->u is required (the handle's x is
+ *   long overwritten when backward runs) and how->out_wx, how->out_wy, data->out_lambda are ignored.  The handle supplies the
+ *   stream, the device, the canvas and the channel set (ccp_grid_operator_channels); its operator, x and b are not touched.
+ *   Launches on the handle's stream only: no allocation, no host synchronisation, no copy, no memset; it may be issued
+ *   during stream capture and returns CCP_OK.
+ *   Refused on the host with nothing enqueued.  CCP_ERR_BAD_ARG: g, how or io NULL, or how->u NULL; whatever the forward
+ *   call refuses in how and data (so QUADRATIC edges need data); data NULL while grad_lambda, g_f or g_lambda is given; a bad
+ *   view; an output with two elements at one address, or one that shares bytes with any input or any other output.
+ *   CCP_ERR_STATE: no installed operator.  CCP_ERR_UNSUPPORTED: not a weighted handle.
+ * Out of scope: implicit differentiation at the IRLS fixed point, double backward, host-pointer twins, the C++ facades, the
+ * row-block calls.  Additive: the ABI version does not change. */
+typedef struct ccp_reweight_grads {
+    const ccp_device_array *grad_wx, *grad_wy, *grad_lambda;       /* upstream, F32/F64; H x W, or H x W x channels per channel; NULL: 0 */
+    const ccp_device_array *g_u, *g_gx, *g_gy, *g_f;               /* out, F32/F64, H x W x channels; NULL: not computed */
+    const ccp_device_array *g_base_wx, *g_base_wy, *g_lambda;      /* out, F32/F64, H x W or H x W x channels; NULL: not computed */
+} ccp_reweight_grads;
+int ccp_grid_reweight_adjoint_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data /* NULL: plain reweight */,
+                                     const ccp_reweight_grads *io);
 
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
