@@ -96,7 +96,7 @@ ABI_SYMBOLS = (
     "ccp_grid_mg_prepare", "ccp_grid_mg_conjugate_gradient_enqueue", "ccp_grid_mg_conjugate_gradient_enqueue_relative",
     "ccp_grid_refresh_weights_device", "ccp_grid_operator_status",
     "ccp_grid_reserve_constraints", "ccp_grid_refresh_constrained_device", "ccp_grid_reweight_device",
-    "ccp_grid_reweight_robust_device", "ccp_grid_reweight_adjoint_device",
+    "ccp_grid_reweight_robust_device", "ccp_grid_reweight_adjoint_device", "ccp_grid_irls_adjoint_step_device",
     "ccp_grid_set_mask_device", "ccp_mask_erode_cross_device", "ccp_panorama_begin_device", "ccp_panorama_add_device",
     "ccp_panorama_finish_device",
     "ccp_comm_probe", "ccp_comm_unique_id", "ccp_comm_create", "ccp_comm_destroy", "ccp_comm_info", "ccp_comm_all_reduce_sum", "ccp_comm_all_reduce_max",
@@ -202,6 +202,11 @@ REWEIGHT_GRADS_OUT = ("g_u", "g_gx", "g_gy", "g_f", "g_base_wx", "g_base_wy", "g
 class ReweightGrads(C.Structure):
     """ccp_reweight_grads: one ccp_device_array pointer per upstream gradient (NULL: 0) and per output (NULL: not computed)."""
     _fields_ = [(n, C.POINTER(DeviceArray)) for n in REWEIGHT_GRADS_IN + REWEIGHT_GRADS_OUT]
+
+
+class IrlsAdjointStep(C.Structure):
+    """ccp_irls_adjoint_step (ccp_gs.h, "Differentiating IRLS at its fixed point"): G, the mask of fixed pixels, the report."""
+    _fields_ = [(n, C.POINTER(DeviceArray)) for n in ("grad_x", "fixed", "report")]
 
 
 class PanoramaState(C.Structure):
@@ -376,6 +381,7 @@ def load() -> C.CDLL:
     L.ccp_grid_reweight_device.argtypes = [vp, C.POINTER(Reweight)]
     L.ccp_grid_reweight_robust_device.argtypes = [vp, C.POINTER(Reweight), C.POINTER(ReweightData)]
     L.ccp_grid_reweight_adjoint_device.argtypes = [vp, C.POINTER(Reweight), C.POINTER(ReweightData), C.POINTER(ReweightGrads)]
+    L.ccp_grid_irls_adjoint_step_device.argtypes = [vp, C.POINTER(Reweight), C.POINTER(ReweightData), C.POINTER(IrlsAdjointStep)]
     L.ccp_grid_mg_level_channel.argtypes = [vp, i32, i32] + [C.POINTER(i32)] * 3 + [vp] * 3
     L.ccp_grid_constraint_info_channel.argtypes = [vp, i32, vp, vp, vp]
     L.ccp_grid_adjoint_begin_device.argtypes = [vp, da]
@@ -1472,6 +1478,39 @@ class Grid:
         self._on_stream(lambda: self.L.ccp_grid_reweight_adjoint_device(self.h, C.byref(how), None if rob is None else C.byref(rob), C.byref(io)),
                         "ccp_grid_reweight_adjoint_device")
         return result
+
+    def irls_adjoint_step_tensor(self, penalty, coupling, scale, epsilon, u, grad, gx=None, gy=None, base_wx=None, base_wy=None, lam=None,
+                                 data_penalty=None, data_scale=1.0, data_epsilon=None, f=None, fixed=None, report=None):
+        """One step z := G + J'z of the adjoint iteration at an IRLS fixed point, in one launch
+        (ccp_grid_irls_adjoint_step_device): with v in the handle's x (the solution of A v = z_old) and z_old in its b, b
+        becomes G + g_u on the free live pixels and 0 elsewhere, g_u what weighted_adjoint_tensor's "wx", "wy" ("lam")
+        gradients of (v, u) and then reweight_adjoint_tensor's "u" gradient of those give, bit for bit; x is left alone,
+        so the next enqueue solve starts from the previous v.  The reweight's arguments as reweight_adjoint_tensor takes
+        them (`u`: the fixed point, required); grad: G = dL/du, float32 / float64 H x W x channels; fixed: the mask as
+        weighted_adjoint_tensor takes it; report: None or a float64 channels x 2 tensor that receives
+        (sum (z_new - z_old)^2, sum z_new^2) per channel over its free live pixels, the same bits for the same inputs.
+        Needs mg_prepare (CcpError STATE otherwise).  Enqueued on torch's current stream: no allocation, no
+        synchronisation."""
+        torch = self._torch()
+        ids = reweight_ids(penalty, coupling) if data_penalty is None else robust_ids(penalty, coupling, data_penalty)
+        if u is None or grad is None:
+            raise ValueError("u (the fixed point) and grad (dL/du) are required")
+        floats, any_ = (torch.float32, torch.float64), (torch.uint8, torch.float32, torch.float64)
+        named = ((base_wx, "base_wx"), (base_wy, "base_wy"), (lam, "lam"))
+        _, arr = self._operator_marshal([t for t, _ in named] + [fixed])
+        arrs = {"u": self._channel_array(u, "u", any_), "f": self._channel_array(f, "f", any_),
+                "gx": self._image(gx, "gx", (torch.float32,)), "gy": self._image(gy, "gy", (torch.float32,)), "out_wx": None, "out_wy": None}
+        arrs.update({n: arr(t, n) for t, n in named})
+        arrs["lambda"] = arrs.pop("lam")
+        ptr = lambda a: None if a is None else C.pointer(a)
+        how = Reweight(ids[0], ids[1], float(scale), float(epsilon), *[ptr(arrs[n]) for n in REWEIGHT_VIEWS])
+        rob = None
+        if data_penalty is not None:
+            rob = ReweightData(ids[2], 0, float(data_scale), 0.0 if data_epsilon is None else float(data_epsilon), ptr(arrs["f"]), None)
+        rep = self._enqueue_report(report, 2)
+        step =IrlsAdjointStep(ptr(self._hwc(grad, "grad", floats)[0]), ptr(arr(fixed, "fixed", "mask")), ptr(rep))
+        self._on_stream(lambda: self.L.ccp_grid_irls_adjoint_step_device(self.h, C.byref(how), None if rob is None else C.byref(rob),
+                                                                         C.byref(step)), "ccp_grid_irls_adjoint_step_device")
 
     def operator_status(self) -> int:
         """The operator status word of the last refresh_weights_tensor (0: good; 1: a bad weight, 2: out of float range in

@@ -1629,14 +1629,23 @@ RefreshPlan refresh_plan(const GridMgView &v, const MgHierarchy &h)
 
 // Is the handle one block with an operator, and is what the last ccp_grid_mg_prepare built still there and built for the
 // handle's present options?  (Any smoothing_sweeps: no coefficient depends on them.)  CCP_ERR_STATE with nothing enqueued
-// otherwise.  If so, the refresh's first launch: every word its kernels OR or count into, zeroed (n_counts of op_verdict).
-int ccp::mg_refresh_begin(ccp_grid *g, int n_counts)
+// otherwise.
+int ccp::mg_prepared(ccp_grid *g)
 {
     GridMgView v{};
     CCP_TRY(check_handle(g, &v));
     MgHierarchy *h = *v.cache;
     const bool ready = h && h->prepared && h->estate.p && cache_serves(v, *h) && h->prep_cfg == v.cfg && h->prep_channels == v.channels;
-    if (!ready) return CCP_ERR_STATE;
+    return ready ? CCP_OK : CCP_ERR_STATE;
+}
+
+// mg_prepared, and if so the refresh's first launch: every word its kernels OR or count into, zeroed (n_counts of op_verdict)
+int ccp::mg_refresh_begin(ccp_grid *g, int n_counts)
+{
+    CCP_TRY(mg_prepared(g));
+    GridMgView v{};
+    CCP_TRY(check_handle(g, &v));
+    MgHierarchy *h = *v.cache;
     const RefreshPlan plan = refresh_plan(v, *h);
     hipLaunchKernelGGL(k_mge_clear, dim3(1), dim3(kBlock), 0, v.stream, v.op_status, v.op_verdict, n_counts, plan.f32 ? h->fbad.p : nullptr,
                        plan.census ? h->nscount.p : nullptr);

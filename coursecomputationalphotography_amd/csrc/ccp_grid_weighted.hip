@@ -1,11 +1,13 @@
 // ccp_grid_weighted.hip — everything only a weighted handle (CCP_GRID_WEIGHTED) accepts: its operator, right-hand side,
-// constraint counts, product and adjoint, with the operator kernels (ccp_grid_weighted.hpp, ccp_grid_adjoint.hpp); and the
+// constraint counts, product and adjoints, with the operator kernels (ccp_grid_weighted.hpp, ccp_grid_adjoint.hpp,
+// ccp_grid_reweight_adjoint.hpp, ccp_grid_irls_adjoint.hpp); and the
 // launchers of the coarsening and of the per-channel batched mode's kernels (ccp_grid_pco.hpp) that ccp_grid_mg.hip calls
 // (ccp_grid_weighted_api.hpp).
 #include "ccp_grid_handle.hpp"
 #include "ccp_grid_pco.hpp"
 #include "ccp_grid_weighted.hpp"
 #include "ccp_grid_reweight_adjoint.hpp"
+#include "ccp_grid_irls_adjoint.hpp"
 #include "ccp_grid_adjoint.hpp"
 #include "ccp_grid_weighted_api.hpp"
 #include "ccp_view_check.hpp"
@@ -574,6 +576,57 @@ int reweight_adjoint_device(ccp_grid *g, const ccp_reweight *how, const ccp_rewe
     return CCP_OK;
 }
 
+// ccp_grid_irls_adjoint_step_device: the reweight adjoint's checks on `how` and `data`, then G, the mask and the report, then
+// that ccp_grid_mg_prepare's work stands (b and x are the solve's); two launches on the handle's stream (one without a
+// report).  The blocks' partial sums go to the handle's `partial`, which no weighted solve reads across calls.
+int irls_adjoint_step_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data, const ccp_irls_adjoint_step *step)
+{
+    CCP_TRY(weighted_handle(g));
+    if (!how || !step || !how->u || !step->grad_x) return CCP_ERR_BAD_ARG;
+    ccp_reweight fwd = *how;
+    fwd.out_wx = fwd.out_wy = nullptr;                                     // ignored here
+    ccp_reweight_data fwd_data{};
+    if (data) {
+        fwd_data = *data;
+        fwd_data.out_lambda = nullptr;
+    }
+    IrlsAdjointArgs a{};
+    CCP_TRY(reweight_checked(g, &fwd, data ? &fwd_data : nullptr, &a.f.r));
+    const Geom &geo = g->geom;
+    const int C = g->desc.channels, sets = g->per_channel ? C : 1;
+    CCP_TRY(check_view(g, step->grad_x, kF32F64, false, 1, geo.H, geo.W, C));
+    if (step->fixed) CCP_TRY(check_view(g, step->fixed, kF32F64 | kU8, false, 1, geo.H, geo.W, sets));
+    if (step->report) CCP_TRY(check_view(g, step->report, 1u << CCP_DTYPE_F64, true, 1, C, 2, 1));
+    CCP_TRY(mg_prepared(g));
+    a.f.rows = robust_rows(geo.W, geo.H, sets);
+    const dim3 grid((unsigned)((geo.W + kBlock - 1) / kBlock), (unsigned)((geo.H + a.f.rows - 1) / a.f.rows), (unsigned)sets);
+    const long blocks = (long)grid.x * grid.y;
+    if (step->report && (size_t)(2 * C * blocks) > g->partial.n) return CCP_ERR_STATE;   // (the handle sizes it by rows, not strips)
+    a.f.dphi = data ? data->penalty : -1;
+    a.f.dscale = data ? data->scale : 1.0;
+    a.f.deps = data && data->penalty != CCP_REWEIGHT_QUADRATIC ? data->epsilon : 1.0;   // (not read for QUADRATIC)
+    a.f.f = image_view(data ? data->f : nullptr, 0.0);
+    a.v = g->x.p;
+    a.b = g->b.p;
+    a.d = g->wop.p;
+    a.plane = geo.ch_stride;
+    a.dset = g->per_channel ? 4 * geo.ch_stride : 0;
+    a.grad = image_view(step->grad_x, 0.0);
+    a.fixed = image_view(step->fixed, 0.0);
+    a.part = step->report ? g->partial.p : nullptr;
+    with_phi(how->penalty, [&](auto P) {
+        hipLaunchKernelGGL((k_irls_adjoint_step<decltype(P)::value>), grid, dim3(kBlock), 0, g->stream, a);
+    });
+    CCP_HIP(hipGetLastError());
+    if (step->report) {
+        hipLaunchKernelGGL(k_irls_adjoint_report, dim3((unsigned)C), dim3(kBlock), 0, g->stream, g->partial.p, blocks,
+                           static_cast<double *>(const_cast<void *>(step->report->data)), (long)step->report->stride_y,
+                           (long)step->report->stride_x);
+        CCP_HIP(hipGetLastError());
+    }
+    return CCP_OK;
+}
+
 }  // namespace
 
 int ccp::weighted_apply(ccp_grid *g, int mode) { return mode == 0 ? weighted_apply_mode<0>(g) : weighted_apply_mode<1>(g); }
@@ -702,6 +755,11 @@ try {
 int ccp_grid_reweight_adjoint_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data, const ccp_reweight_grads *io)
 try {
     return reweight_adjoint_device(g, how, data, io);
+} CCP_ABI_CATCH
+
+int ccp_grid_irls_adjoint_step_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data, const ccp_irls_adjoint_step *step)
+try {
+    return irls_adjoint_step_device(g, how, data, step);
 } CCP_ABI_CATCH
 
 int ccp_grid_reserve_constraints(ccp_grid *g, int32_t on)

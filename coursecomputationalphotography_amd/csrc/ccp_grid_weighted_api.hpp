@@ -35,6 +35,8 @@ int pco_apply(hipStream_t s, bool dot, dim3 grid, int C, const MgLevel &lv, long
 // CCP_ERR_STATE with nothing enqueued unless ccp_grid_mg_prepare's work stands; else one launch: the status word, n_counts
 // words of the refresh pass's counts and the mode's verdict words zeroed
 int mg_refresh_begin(ccp_grid *g, int n_counts);
+// the same question alone, nothing enqueued: CCP_OK while ccp_grid_mg_prepare's work stands (b and x are the enqueue solve's)
+int mg_prepared(ccp_grid *g);
 int mg_refresh(ccp_grid *g);         // the coarse levels, float copies, census and status word from the new level 0: launches only
 
 }  // namespace ccp

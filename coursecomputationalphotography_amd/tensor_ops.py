@@ -801,6 +801,72 @@ class WeightedSolver:
             weights = tuple(plane(w, old) for w, old in zip((wx, wy, data_weight), self._operator[:3]))
         return _persistent_function().apply(gx, gy, f, values, x0, *weights, self, report, adjoint_report, weights != (None, None, None)), report
 
+    def fixed_point_grad(self, u, penalty, coupling, scale, epsilon, gx, gy, f, values=None, base_wx=None, base_wy=None, data_weight=None, *,
+                         backward_steps, backward_tolerance=None, check_every=8, backward_history=None, strict=True, data_penalty=None,
+                         data_scale=1.0, data_epsilon=None):
+        """Attach the gradient of an IRLS fixed point to u: u is taken to be a fixed point of the step u -> solve(w(u)) on this
+        solver (the loop of irls_solve run until it stopped moving; the reweight's arguments, gx, gy, f, values and the
+        base weights as that loop took them), and the call returns u unchanged -- the same storage, detached -- with a
+        grad_fn towards gx, gy, f, values, base_wx, base_wy and data_weight.  The forward installs w(u)
+        (reweight(u=u): one launch) and saves u and the inputs, nothing else: no iterate, no weights, so the memory does not
+        depend on how many steps produced u.  u8 inputs and python numbers get no gradient; a 0-dim tensor is expanded to
+        H x W and, on an operator per channel, an H x W tensor to H x W x C outside the autograd function (reweight_grad's rule).
+
+        Backward (once-differentiable, enqueue only unless backward_tolerance is given).  With G = dL/du and J the Jacobian
+        of one IRLS step at u, z = (I - J')^-1 G is reached by z_0 = G, z_{k+1} = G + J'z_k:
+          1. if a later call has moved the handle's operator, w(u) is installed again (reweight(u=u));
+          2. adjoint_begin with G and one enqueue solve: v = A^-1 z_0;
+          3. `backward_steps` times: the fused step (capi.Grid.irls_adjoint_step_tensor: z := G + J'z from v, in one launch),
+             then an enqueue solve to the solver's stop test, warm-started from the previous v;
+          4. the gradient pass and the reweight's adjoint once, for the parameter gradients, each in its input's dtype
+             and shape (float32 ones are formed in float64 and rounded once).
+        The z iteration converges at the forward loop's own linear rate -- on 16 x 12 x 2, epsilon 5e-2: 35 forward steps
+        to an update of 1e-12 and 36 backward steps to the same relative change; Huber / edge 49 and 50, TV-L1 19 and 16 --
+        so backward_steps of about the forward's step count is the natural choice.  A finite backward_steps is a truncated
+        Neumann series: the gradient lacks the terms beyond J'^backward_steps.  "reciprocal" carries no convexity guarantee,
+        and with it neither loop need converge.
+        backward_tolerance: None -- no synchronisation; a number: the step's report is read every `check_every` steps
+        and the loop ends once ||z_new - z_old|| <= backward_tolerance * ||G||; with `strict`, RuntimeError if
+        backward_steps is reached first.  backward_history: None, or a list that receives one channels x 2 report tensor
+        per step made, (sum (z_new - z_old)^2, sum z_new^2) per channel.
+        data_penalty, data_scale, data_epsilon: the robust data term, as reweight's (data_weight is then the base lambda).
+        The gradient is that of the fixed point: where u is not one -- the forward loop stopped early -- it is wrong by
+        O(||u_K - u_{K-1}||)."""
+        import torch
+        if self.nullspace != capi.MG_NULLSPACES["none"]:
+            _no_nullspace("constant", "WeightedSolver.fixed_point_grad")
+        if self._operator is None:
+            raise RuntimeError("WeightedSolver: set_operator first")
+        if data_penalty is None:
+            capi.reweight_ids(penalty, coupling)
+        else:
+            capi.robust_ids(penalty, coupling, data_penalty)
+        if not isinstance(u, torch.Tensor) or f is None:
+            raise ValueError("fixed_point_grad needs u, the fixed point, and f")
+        if int(backward_steps) < 0 or int(check_every) < 1:
+            raise ValueError("backward_steps must be >= 0 and check_every >= 1")
+        stacked = self.grid.operator_channels() > 1 or _per_channel(base_wx, base_wy, data_weight)
+
+        def plane(w):
+            if isinstance(w, torch.Tensor) and w.dim() == 0:
+                w = w.expand(self.H, self.W)
+            w = _weight(w, self.H, self.W, self.device.index)
+            if stacked and w is not None and w.dim() == 2:
+                w = w.unsqueeze(-1).expand(self.H, self.W, self.C)
+            return w
+
+        def image(t):
+            if isinstance(t, torch.Tensor) and t.dim() == 2:
+                t = t.unsqueeze(-1).expand(self.H, self.W, self.C)
+            return t
+
+        cfg = dict(penalty=penalty, coupling=coupling, scale=float(scale), epsilon=float(epsilon), data_penalty=data_penalty,
+                   data_scale=float(data_scale), data_epsilon=data_epsilon, steps=int(backward_steps),
+                   tolerance=None if backward_tolerance is None else float(backward_tolerance), check_every=int(check_every),
+                   history=backward_history, strict=bool(strict))
+        return _fixed_point_function().apply(image(u.detach()), gx, gy, image(f), image(values), plane(base_wx), plane(base_wy),
+                                             plane(data_weight), self, cfg)
+
     def close(self):
         self.grid.close()
 
@@ -810,6 +876,28 @@ class WeightedSolver:
     def __exit__(self, *exc):
         self.close()
         return False
+
+
+def _irls_steps(s, gx, gy, f, values, x, outer, penalty, coupling, strength, epsilon, base_wx, base_wy, lam, robust, data_penalty, first_step,
+                history, last_report=None):
+    """irls_solve's loop on solver `s` from x: `outer` x (reweight -- step 0 from f, step k from the handle's x -- then the
+    warm-started solve).  last_report: None, or a C x 8 tensor for the last step's report where `history` is None.  Returns
+    (x, the x the last step started from).  Enqueue only."""
+    import torch
+    before = x
+    for k in range(int(outer)):
+        if data_penalty is not None:
+            robust["data_penalty"] = "quadratic" if k == 0 and first_step == "quadratic" else data_penalty
+        w = s.reweight(penalty, coupling, strength, epsilon, u=f if k == 0 else None, gx=gx, gy=gy, base_wx=base_wx, base_wy=base_wy,
+                       data_weight=lam, **robust)
+        report = None if history is None else torch.zeros((s.C, 8), dtype=torch.float64, device=x.device)
+        if report is None and k == int(outer) - 1:
+            report = last_report
+        before = x
+        x, _ = s.solve(gx, gy, f, values, x0=x, report=report)
+        if history is not None:
+            history.append((x, report) + tuple(w))
+    return x, before
 
 
 def irls_solve(gx, gy, f, outer: int, iterations: int, penalty="charbonnier", coupling="edge", strength=1.0, epsilon=1e-2, data_weight=1.0,
@@ -882,15 +970,8 @@ def irls_solve(gx, gy, f, outer: int, iterations: int, penalty="charbonnier", co
             robust = dict(data_scale=float(data_weight) if scalar else 1.0, data_epsilon=data_epsilon, f=f)
             if scalar:
                 lam = None
-        for k in range(int(outer)):
-            if data_penalty is not None:
-                robust["data_penalty"] = "quadratic" if k == 0 and first_step == "quadratic" else data_penalty
-            w = s.reweight(penalty, coupling, strength, epsilon, u=f if k == 0 else None, gx=gx, gy=gy, base_wx=base_wx, base_wy=base_wy,
-                           data_weight=lam, **robust)
-            report = None if history is None else torch.zeros((C, 8), dtype=torch.float64, device=x.device)
-            x, _ = s.solve(gx, gy, f, values, x0=x, report=report)
-            if history is not None:
-                history.append((x, report) + tuple(w))
+        x, _ = _irls_steps(s, gx, gy, f, values, x, outer, penalty, coupling, strength, epsilon, base_wx, base_wy, lam, robust, data_penalty,
+                           first_step, history)
         if out_dtype == torch.uint8:
             return s.grid.store_u8_tensor()
         return x if out_dtype == torch.float64 else x.to(out_dtype)
@@ -955,7 +1036,8 @@ def irls_solve_grad(gx, gy, f, outer: int, iterations: int, penalty="charbonnier
     history: as irls_solve's.
 
     Memory.  Per outer step u, wx, wy (and lam) stay alive until backward, beside the inputs, and the handle -- x, b, the
-    operator planes, the hierarchy and the PCG vectors -- lives as long as the graph does."""
+    operator planes, the hierarchy and the PCG vectors -- lives as long as the graph does.  irls_solve_implicit
+    differentiates the loop at its fixed point instead: the converged solution's gradient, from u and the inputs alone."""
     import torch
     if data_penalty is None:
         capi.reweight_ids(penalty, coupling)
@@ -1160,3 +1242,230 @@ def _persistent_function():
 
     _PersistentSolve = PersistentSolve
     return PersistentSolve
+
+
+_FixedPointGrad = None
+
+
+def _fixed_point_function():
+    """The torch.autograd.Function behind WeightedSolver.fixed_point_grad (built on first use, as _solve_function)."""
+    global _FixedPointGrad
+    if _FixedPointGrad is not None:
+        return _FixedPointGrad
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    names = ("gx", "gy", "f", "values", "base_wx", "base_wy", "lam")
+
+    def install(solver, cfg, u, t):
+        """reweight(u=u): the operator A(w(u)) on the handle; and, where a later call may have moved the mask too, the mask"""
+        robust = {}
+        if cfg["data_penalty"] is not None:
+            robust = dict(data_penalty=cfg["data_penalty"], data_scale=cfg["data_scale"], data_epsilon=cfg["data_epsilon"], f=t["f"])
+        fixed = solver._operator[3]
+        w = solver.reweight(cfg["penalty"], cfg["coupling"], cfg["scale"], cfg["epsilon"], u=u, gx=t["gx"], gy=t["gy"], base_wx=t["base_wx"],
+                            base_wy=t["base_wy"], data_weight=t["lam"], **robust)
+        return fixed, w
+
+    class FixedPointGrad(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, u, gx, gy, f, values, base_wx, base_wy, lam, solver, cfg):
+            t = dict(zip(names, (gx, gy, f, values, base_wx, base_wy, lam)))
+            ctx.fixed, _ = install(solver, cfg, u, t)
+            ctx.solver, ctx.cfg, ctx.generation = solver, cfg, solver._generation
+            ctx.present = [v is not None for v in t.values()]
+            ctx.save_for_backward(*[v for v in t.values() if v is not None], u)
+            return u.detach()
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad):
+            saved = list(ctx.saved_tensors)
+            u = saved[-1]
+            it = iter(saved[:-1])
+            t = {n: next(it) if p else None for n, p in zip(names, ctx.present)}
+            solver, cfg = ctx.solver, ctx.cfg
+            g = solver.grid
+            robust = cfg["data_penalty"] is not None
+            if solver._generation != ctx.generation:       # the handle holds a later call's operator: back to w(u)
+                _, w = install(solver, cfg, u, t)
+                if solver._planes:                         # ... and perhaps a later mask
+                    solver.refresh_constraints(w[0], w[1], w[2] if robust else t["lam"], ctx.fixed)
+                ctx.generation = solver._generation
+            wx, wy, lam_op, fixed = solver._operator
+            grad = grad.reshape(u.shape)
+            if grad.dtype not in (torch.float32, torch.float64):
+                grad = grad.to(torch.float64)
+            how = dict(gx=t["gx"], gy=t["gy"], base_wx=t["base_wx"], base_wy=t["base_wy"], lam=t["lam"])
+            if robust:
+                how.update(data_penalty=cfg["data_penalty"], data_scale=cfg["data_scale"], data_epsilon=cfg["data_epsilon"], f=t["f"])
+            args = (cfg["penalty"], cfg["coupling"], cfg["scale"], cfg["epsilon"], u)
+            g.adjoint_begin_tensor(grad)
+            solver._enqueue_pcg(None)
+            tol, history = cfg["tolerance"], cfg["history"]
+            shared = torch.zeros((solver.C, 2), dtype=torch.float64, device=u.device) if tol is not None and history is None else None
+            bound = None if tol is None else tol * tol * float(grad.to(torch.float64).pow(2).sum())
+            done = tol is None
+            for k in range(cfg["steps"]):
+                report = shared
+                if history is not None:
+                    report = torch.zeros((solver.C, 2), dtype=torch.float64, device=u.device)
+                    history.append(report)
+                g.irls_adjoint_step_tensor(*args, grad, fixed=fixed, report=report, **how)
+                solver._enqueue_pcg(None)
+                if tol is not None and ((k + 1) % cfg["check_every"] == 0 or k + 1 == cfg["steps"]):
+                    if float(report[:, 0].sum()) <= bound:   # (the one read-back per check)
+                        done = True
+                        break
+            if not done and cfg["strict"]:
+                raise RuntimeError(f"fixed_point_grad: the adjoint iteration did not reach backward_tolerance {tol} within {cfg['steps']} "
+                                   "steps; raise backward_steps, loosen backward_tolerance, or pass strict=False")
+            need = dict(zip(names, ctx.needs_input_grad[1:8]))
+            need = {n: bool(y) and t[n] is not None for n, y in need.items()}
+            # the gradient pass: the weights' gradients always (the reweight's adjoint is fed with them), the rest as asked
+            want = ("wx", "wy", "lam") + tuple(n for n in ("gx", "gy", "f") if need[n])
+            got = g.weighted_adjoint_tensor(u, None, t["gx"], t["gy"], t["f"], wx, wy, lam_op, fixed, want=want)
+            back_names = {"gx": "gx", "gy": "gy", "base_wx": "base_wx", "base_wy": "base_wy"}
+            if robust:
+                back_names.update(f="f", lam="lam")
+            want_back = ("u",) + tuple(m for n, m in back_names.items() if need[n])
+            back = g.reweight_adjoint_tensor(*args, grad_wx=got["wx"], grad_wy=got["wy"], grad_lambda=got["lam"] if robust else None,
+                                             want=want_back, **how)
+            out = {}
+            for n in ("gx", "gy", "f"):
+                if need[n]:
+                    out[n] = got[n] + back[n] if n in back else got[n]
+            for n in ("base_wx", "base_wy"):
+                if need[n]:
+                    out[n] = back[n]
+            if need["lam"]:
+                out["lam"] = back["lam"] if robust else got["lam"]
+            if need["values"]:                             # z at every pixel, the fixed ones included: G + g_u of the last v
+                z = grad.to(torch.float64) + back["u"]
+                out["values"] = g.weighted_adjoint_tensor(u, z, t["gx"], t["gy"], t["f"], wx, wy, lam_op, fixed, want=("values",))["values"]
+            grads = tuple(None if n not in out else out[n].to(t[n].dtype).reshape(t[n].shape) for n in names)
+            return (None,) + grads + (None, None)
+
+    _FixedPointGrad = FixedPointGrad
+    return FixedPointGrad
+
+
+def irls_solve_implicit(gx, gy, f, outer: int, iterations: int, penalty="charbonnier", coupling="edge", strength=1.0, epsilon=1e-2,
+                        data_weight=1.0, wx=None, wy=None, fixed=None, values=None, tolerance=1e-10, hierarchy="rescaled", precision="f64",
+                        channels="sequential", smoother="point", history=None, data_penalty=None, data_epsilon=None, first_step="quadratic",
+                        strict: bool = True, backward_steps=None, backward_tolerance=None, check_every: int = 8, backward_history=None):
+    """irls_solve differentiated at its fixed point instead of unrolled: the forward is irls_solve's own loop on one
+    WeightedSolver under torch.no_grad() -- warm-started, enqueue only, no autograd node per step, the value irls_solve's bit
+    for bit (with a python-number strength) -- and WeightedSolver.fixed_point_grad then gives the result a grad_fn towards
+    gx, gy, f, values, wx, wy (the base weights), a tensor data_weight and a 0-dim tensor strength.  Returns float64 H x W x C.
+    Arguments as irls_solve_grad's; strength as there (a 0-dim tensor is folded into the base weights with scale 1).
+
+    The gradient is that of the FIXED POINT, the minimiser the loop converges to, not of the `outer`-step truncation
+    irls_solve_grad differentiates; where the forward has not converged it is wrong by O(||u_K - u_{K-1}||).  strict (the
+    default): the last forward step's update is read once -- the one synchronisation of the forward -- and RuntimeError is
+    raised unless ||u_K - u_{K-1}|| <= tolerance * ||u_K|| and the last solve reports converged.  Memory: u and the inputs
+    are saved, whatever `outer` is; the handle lives as long as the graph does.
+
+    backward_steps (None: `outer`), backward_tolerance, check_every, backward_history: fixed_point_grad's.  The z iteration
+    of the backward converges at the forward's own linear rate (on 16 x 12 x 2, epsilon 5e-2, TV: 35 forward steps to an
+    update of 1e-12, 36 backward steps to the same relative change; Huber / edge 49 and 50; TV-L1 19 and 16), and a finite
+    backward_steps is a truncated Neumann series.  "reciprocal" carries no convexity guarantee: neither loop need converge.
+    What WeightedSolver.solve_grad refuses is refused here the same way."""
+    import torch
+    if data_penalty is None:
+        capi.reweight_ids(penalty, coupling)
+    else:
+        capi.robust_ids(penalty, coupling, data_penalty)
+        if data_penalty == "quadratic" or penalty == "quadratic":
+            raise ValueError('irls_solve_implicit: "quadratic" is data_penalty=None (and no edge penalty)')
+        if first_step not in ("quadratic", "robust"):
+            raise ValueError(f'first_step must be "quadratic" or "robust", not {first_step!r}')
+        if data_epsilon is None:
+            raise ValueError("irls_solve_implicit: a robust data term needs data_epsilon")
+    if f is None:
+        raise ValueError("irls_solve_implicit needs f: the data term, and the image the first step reweights from")
+    if int(outer) < 1:
+        raise ValueError(f"outer must be at least 1, not {outer}")
+    dev = _device_index(f)
+    H, W = f.shape[0], f.shape[1]
+    if f.dim() == 2:
+        f = f.unsqueeze(-1)
+    C = f.shape[2]
+    flat = lambda w: w.expand(H, W) if isinstance(w, torch.Tensor) and w.dim() == 0 else w
+    wx, wy, data_weight = flat(wx), flat(wy), flat(data_weight)
+    scale, base_wx, base_wy = strength, wx, wy
+    if isinstance(strength, torch.Tensor):
+        if strength.dim() != 0:
+            raise ValueError("a tensor strength must be 0-dim")
+        scale = 1.0
+        base_wx = strength.expand(H, W) if wx is None else strength * wx
+        base_wy = strength.expand(H, W) if wy is None else strength * wy
+    off = lambda t: t.detach() if isinstance(t, torch.Tensor) else t
+    s = WeightedSolver(H, W, C, dev, iterations=iterations, epsilon=0.0, hierarchy=hierarchy, precision=precision, channels=channels,
+                       smoother=smoother)              # (not closed here: backward needs it; it goes with the graph)
+    try:
+        scalar = not isinstance(data_weight, torch.Tensor)
+        with torch.no_grad():
+            s.set_operator(off(wx), off(wy), off(data_weight), fixed)
+            s.set_stop(relative=tolerance)
+            _, _, lam, _ = s._operator
+            robust = {}
+            if data_penalty is not None:
+                robust = dict(data_scale=float(data_weight) if scalar else 1.0, data_epsilon=data_epsilon, f=off(f))
+                if scalar:
+                    lam = None
+            report = torch.zeros((C, 8), dtype=torch.float64, device=f.device) if strict and history is None else None
+            x, before = _irls_steps(s, off(gx), off(gy), off(f), off(values), off(f).to(torch.float64), outer, penalty, coupling, scale, epsilon,
+                                    off(base_wx), off(base_wy), lam, robust, data_penalty, first_step, history, report)
+            if strict:
+                last = report if history is None else history[-1][1]
+                moved, size, ok = torch.stack([(x - before).norm(), x.norm(), last[:, 1].min()]).tolist()
+                if not ok or not moved <= tolerance * size:
+                    raise RuntimeError(f"irls_solve_implicit: after {outer} steps the forward loop still moves by {moved:.3g} (||u|| = "
+                                       f"{size:.3g}; last solve converged: {bool(ok)}): the fixed point's gradient is wrong by about that. "
+                                       "Raise `outer` (or `iterations`), or pass strict=False")
+            del report, before
+        # the differentiable data weight: the caller's tensor (a number stays a number: no gradient, and the robust call's scale)
+        grad_lam = data_weight if not scalar else (None if data_penalty is not None else lam)
+        return s.fixed_point_grad(x, penalty, coupling, scale, epsilon, gx, gy, f, values, base_wx, base_wy, grad_lam,
+                                  backward_steps=int(outer) if backward_steps is None else backward_steps, backward_tolerance=backward_tolerance,
+                                  check_every=check_every, backward_history=backward_history, strict=strict,
+                                  **({} if data_penalty is None else dict(data_penalty=data_penalty, data_scale=robust["data_scale"],
+                                                                          data_epsilon=data_epsilon)))
+    except BaseException:
+        s.close()
+        raise
+
+
+def tv_denoise_implicit(image, strength, outer: int = 40, iterations: int = 400, epsilon=1e-2, isotropic=True, data_weight=1.0,
+                        tolerance=1e-10, hierarchy="rescaled", precision="f64", channels="sequential", smoother="point", history=None,
+                        strict: bool = True, backward_steps=None, backward_tolerance=None, check_every: int = 8, backward_history=None):
+    """tv_denoise differentiated at its fixed point (irls_solve_implicit: zero guidance, f = image, Charbonnier, "pixel" or
+    "edge" coupling): a differentiable function of the image, of a 0-dim tensor strength and of a tensor data_weight whose
+    memory does not grow with `outer`.  The gradient is the fixed point's: wrong by O(||u_K - u_{K-1}||) where the forward
+    has not converged, which strict (the default) checks with one read-back; a finite backward_steps (None: `outer`) is a
+    truncated Neumann series that converges at the forward's rate.  Returns float64, the image's shape."""
+    f = image if image.dim() == 3 else image.unsqueeze(-1)
+    u = irls_solve_implicit(None, None, f, outer, iterations, penalty="charbonnier", coupling="pixel" if isotropic else "edge",
+                            strength=strength, epsilon=epsilon, data_weight=data_weight, tolerance=tolerance, hierarchy=hierarchy,
+                            precision=precision, channels=channels, smoother=smoother, history=history, strict=strict,
+                            backward_steps=backward_steps, backward_tolerance=backward_tolerance, check_every=check_every,
+                            backward_history=backward_history)
+    return u if image.dim() == 3 else u[..., 0]
+
+
+def tv_l1_denoise_implicit(image, strength, outer: int = 40, iterations: int = 400, epsilon=1e-2, data_epsilon=5e-2, isotropic=True,
+                           data_weight=1.0, tolerance=1e-10, hierarchy="rescaled", precision="f64", channels="sequential", smoother="point",
+                           first_step="quadratic", history=None, strict: bool = True, backward_steps=None, backward_tolerance=None,
+                           check_every: int = 8, backward_history=None):
+    """tv_l1_denoise differentiated at its fixed point, as tv_denoise_implicit is tv_denoise's (the data term Charbonnier on
+    data_epsilon as well); the same caveats: the fixed point's gradient, wrong by O(||u_K - u_{K-1}||) where the forward has
+    not converged (strict checks it), and a truncated Neumann series for a finite backward_steps.  Returns float64, the
+    image's shape."""
+    f = image if image.dim() == 3 else image.unsqueeze(-1)
+    u = irls_solve_implicit(None, None, f, outer, iterations, penalty="charbonnier", coupling="pixel" if isotropic else "edge",
+                            strength=strength, epsilon=epsilon, data_weight=data_weight, tolerance=tolerance, hierarchy=hierarchy,
+                            precision=precision, channels=channels, smoother=smoother, history=history, data_penalty="charbonnier",
+                            data_epsilon=data_epsilon, first_step=first_step, strict=strict, backward_steps=backward_steps,
+                            backward_tolerance=backward_tolerance, check_every=check_every, backward_history=backward_history)
+    return u if image.dim() == 3 else u[..., 0]

@@ -1325,8 +1325,8 @@ int ccp_grid_reweight_robust_device(ccp_grid *g, const ccp_reweight *how, const 
  *   call refuses in how and data (so QUADRATIC edges need data); data NULL while grad_lambda, g_f or g_lambda is given; a bad
  *   view; an output with two elements at one address, or one that shares bytes with any input or any other output.
  *   CCP_ERR_STATE: no installed operator.  CCP_ERR_UNSUPPORTED: not a weighted handle.
- * Out of scope: implicit differentiation at the IRLS fixed point, double backward, host-pointer twins, the C++ facades, the
- * row-block calls.  Additive: the ABI version does not change. */
+ * Out of scope: double backward, host-pointer twins, the C++ facades, the row-block calls (differentiating at the IRLS fixed
+ * point instead of unrolling: the next section).  Additive: the ABI version does not change. */
 typedef struct ccp_reweight_grads {
     const ccp_device_array *grad_wx, *grad_wy, *grad_lambda;       /* upstream, F32/F64; H x W, or H x W x channels per channel; NULL: 0 */
     const ccp_device_array *g_u, *g_gx, *g_gy, *g_f;               /* out, F32/F64, H x W x channels; NULL: not computed */
@@ -1334,6 +1334,52 @@ typedef struct ccp_reweight_grads {
 } ccp_reweight_grads;
 int ccp_grid_reweight_adjoint_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data /* NULL: plain reweight */,
                                      const ccp_reweight_grads *io);
+
+/* ---- Differentiating IRLS at its fixed point: one fused step of the adjoint iteration ------------------------------------------
+ * Let u^ be a fixed point of the IRLS step u -> solve(w(u)), A = A(w(u^)) the operator the reweight installs from u^, and J
+ * the Jacobian of one step at u^.  With G = dL/du^ the adjoint state z solves (I - J') z = G and is reached by z_0 = G,
+ * z_{k+1} = G + J' z_k, at the forward loop's own linear rate.  One product J'z is what one unrolled backward step forms:
+ * solve A v = z on the free pixels (ccp_grid_adjoint_begin_device and the enqueue solve: v in the handle's x, z in its b),
+ * ccp_grid_weighted_adjoint_device's g_wx, g_wy (g_lambda) of (v, u^), and ccp_grid_reweight_adjoint_device's g_u of those.
+ * This call is the last two and the update of z in ONE pass, the three intermediate planes kept in registers; it leaves x
+ * alone, so that the next solve A v = z_new starts warm from the previous v.  Memory does not grow with the step count.
+ *   Inputs.  how, data: read exactly as ccp_grid_reweight_adjoint_device reads them (how->u = u^ is required, the outputs in
+ *   them are ignored).  v: the handle's x, read as +0.0 at a fixed pixel whatever it holds there.  z_old: the handle's b.
+ *   Definition (fp64 throughout, every input widened exactly, no multiply-add fused; tests/fixed_point_helpers.py is the
+ *   same in numpy).  Per set and pixel:
+ *     Gwx, Gwy: ccp_grid_weighted_adjoint_device's g_wx, g_wy of (v, u^, gx, gy): acc from +0.0, per channel of the set in
+ *       channel order  s = vE - v;  r = gx - (uE - u);  acc += s * r  (the south edge likewise); a shared operator sums the
+ *       handle's channels, a per-channel operator takes channel c alone.  With data, Glambda is that call's g_lambda:
+ *       accl += v * (f - u) from +0.0, and +0.0 at a fixed pixel.
+ *     g_u: exactly ccp_grid_reweight_adjoint_device's g_u for those upstream values: psi, k_x / k_y / k_d, e, s and the
+ *       four-term sum with the data term last.
+ *     z_new = G + g_u  (G widened exactly, one addition).
+ *   Writes.  b := z_new on free live pixels and +0.0 on fixed and dead ones (ccp_grid_adjoint_begin_device's rule: the
+ *   installed d != 0).  x, the operator, the hierarchy, the counts and the status word are not touched.  So b afterwards
+ *   holds, bit for bit, what the two existing adjoint calls with F64 intermediate planes, then G + g_u, then
+ *   ccp_grid_adjoint_begin_device's masking leave there -- but x is kept.
+ *   report (F64, channels x 2: element (c, k) at c * stride_y + k * stride_x; NULL: not written):
+ *   report[c] = (sum (z_new - z_old)^2, sum z_new^2) over channel c's free live pixels, by a two-stage reduction in a fixed
+ *   order without floating-point atomics: the same inputs give the same bits.  The partial sums live in memory the handle
+ *   has owned since ccp_grid_create (its per-block partial-sum buffer, which no call on a weighted handle reads across
+ *   calls); the caller passes no workspace.
+ *   Launches on the handle's stream only: no allocation, no memset, no host synchronisation, no copy; it may be issued
+ *   during stream capture and returns CCP_OK.
+ *   Refused on the host with nothing enqueued and b untouched.  As ccp_grid_reweight_adjoint_device: CCP_ERR_BAD_ARG for g,
+ *   how or how->u NULL, whatever the forward call refuses in how and data, a bad view; CCP_ERR_STATE without an installed
+ *   operator; CCP_ERR_UNSUPPORTED on a handle that is not weighted.  And: step or step->grad_x NULL: CCP_ERR_BAD_ARG; no
+ *   successful ccp_grid_mg_prepare for the handle's present options: CCP_ERR_STATE (b and x must be the solve's).
+ * Out of scope: Krylov or Anderson acceleration of the z iteration (A + C is symmetric for the convex penalties, so an outer
+ * CG preconditioned by the solve is the obvious follow-up); the Hessian-weight shortcut for EDGE coupling on single-channel
+ * sets; gradients with respect to the epsilons; double backward, host-pointer twins, the C++ facades, the row-block calls.
+ * Additive: the ABI version does not change. */
+typedef struct ccp_irls_adjoint_step {
+    const ccp_device_array *grad_x;    /* G, F32/F64, H x W x channels, required */
+    const ccp_device_array *fixed;     /* the mask as ccp_grid_weighted_adjoint_device takes it; NULL: none */
+    const ccp_device_array *report;    /* F64, channels x 2; NULL: not written */
+} ccp_irls_adjoint_step;
+int ccp_grid_irls_adjoint_step_device(ccp_grid *g, const ccp_reweight *how, const ccp_reweight_data *data /* NULL: plain */,
+                                      const ccp_irls_adjoint_step *step);
 
 /* Device time of the last ccp_grid_sweep / ccp_grid_gauss_seidel in milliseconds and the
  * number of half-sweep kernel launches it issued (HIP events on the handle's stream). */
